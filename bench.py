@@ -49,6 +49,9 @@ HBM_PEAK_GBPS = 8000.0      # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_
 KERNEL_SOURCES = ("gpuar_amd/csrc/gpuar_kernels.hip", "gpuar_amd/csrc/lane_codec.h")
 LINE_LIMIT = 4096                   # bytes: the driver keeps ~8 KB of stdout + stderr; round 5's 22 KB line fell out of it
 DETAIL_FILE = "bench_detail.json"   # everything the line leaves out (prose provenance, every roofline object, per-rank arrays)
+DUMP_SAMPLE_PACKETS = 512           # --dump-outputs: packets whose slot and decoded bytes are written (+ the first and the last)
+DUMP_CLEN_PACKETS = 1 << 20         # --dump-outputs: compressed lengths written (every packet of the 8 GiB default; a stride beyond)
+DUMP_LIMIT_BYTES = 64 * 10**6        # --dump-outputs: what the written arrays may take in all (the sample above takes ~39 MB)
 
 
 def parse_args(argv=None):
@@ -79,7 +82,14 @@ def parse_args(argv=None):
     ap.add_argument("--live-traffic-timeout", type=float, default=150.0, help="seconds each of the two counter passes may take")
     ap.add_argument("--detail-file", default=None,
                     help=f"where the full result object goes (default: {DETAIL_FILE} next to bench.py, and a copy under gpurun_out/ when that exists)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (rank 0's shard: a seeded sample of "
+                         "its slots and decoded packets, every packet's compressed length) to DIR/<name>.npy, float32/float64, "
+                         "<= 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def kernel_source_stamp(root=ROOT):
@@ -845,11 +855,53 @@ def checker_kind():
     return O.require_best().kind              # raises where the pinned reference binary is expected and missing
 
 
-def run_pass(args, H, ctl, dev, steps, warmup):
+def output_sample(d_slots, d_out, n, npk, slot=8704, packet=8192, seed=0):
+    """What one step of the hot path handed its caller -- the slots encode wrote and the bytes decode wrote -- as host arrays
+    for --dump-outputs, a fixed sample of them so that two builds can be compared output for output:
+      packet_index  [k]           float64  the sampled packets: DUMP_SAMPLE_PACKETS drawn with `seed`, plus the first and the last
+      slots         [k, slot]     float32  their slots, bytes at and beyond the packet's compressed length (undefined) as 0
+      decoded       [k, packet]   float32  their decoded bytes, bytes beyond the shard's `n` (undefined) as 0
+      clen          [m]           float32  compressed length of packets 0, s, 2s, ... (s = 1 up to DUMP_CLEN_PACKETS packets)
+    The sample depends on the shard's size alone."""
+    import numpy as np
+    import torch
+    dev = d_slots.device
+    slots = d_slots[:npk * slot].view(npk, slot)
+    pick = np.random.default_rng(seed).choice(npk, size=min(npk, DUMP_SAMPLE_PACKETS), replace=False)
+    pick = np.unique(np.concatenate([pick, [0, npk - 1]]))
+    idx = torch.from_numpy(pick).to(dev)
+
+    def clen_of(rows):
+        return rows[:, 0].to(torch.int32) | (rows[:, 1].to(torch.int32) << 8)
+
+    s = slots.index_select(0, idx)
+    s = torch.where(torch.arange(slot, device=dev)[None, :] < clen_of(s)[:, None], s, torch.zeros_like(s))
+    d = d_out[:npk * packet].view(npk, packet).index_select(0, idx)
+    valid = (n - idx * packet).clamp(0, packet)
+    d = torch.where(torch.arange(packet, device=dev)[None, :] < valid[:, None], d, torch.zeros_like(d))
+    stride = -(-npk // DUMP_CLEN_PACKETS)
+    out = {"packet_index": pick.astype(np.float64), "slots": s.float().cpu().numpy(), "decoded": d.float().cpu().numpy(),
+           "clen": clen_of(slots[::stride]).float().cpu().numpy()}
+    assert sum(a.nbytes for a in out.values()) <= DUMP_LIMIT_BYTES
+    return out
+
+
+def write_outputs(directory, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print(f"bench.py: wrote {', '.join(sorted(arrays))} ({sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB) to {directory}",
+          file=sys.stderr, flush=True)
+
+
+def run_pass(args, H, ctl, dev, steps, warmup, dump=False):
     """One measurement of the hot path under args.scaling: this rank's shard generated on the device, W untimed
     warm-up steps, then exactly `steps` steps (encode kernel + decode kernel) bracketed by barrier +
     torch.cuda.synchronize(), MAX over ranks; then, untimed, the per-kernel durations and the checks of what was
-    just timed.  Returns plain numbers plus the device buffers (for the side kernels and the gather probe)."""
+    just timed.  Returns plain numbers plus the device buffers (for the side kernels and the gather probe), and with `dump`
+    the output_sample() of the last timed step, taken before anything else runs on those buffers."""
     import torch
     world, rank = ctl.world, ctl.rank
     offset, n = plan_shard(args, world, rank)
@@ -878,6 +930,7 @@ def run_pass(args, H, ctl, dev, steps, warmup):
         decode()
     barrier()
     elapsed = ctl.max_over_ranks(time.perf_counter() - t0)
+    outputs = output_sample(d_slots, d_out, n, npk, H.SLOT, H.PACKET) if dump else None
 
     # ---- per-kernel durations (HIP events on the launch stream), untimed region ----
     reps = max(3, min(steps, 10))
@@ -898,7 +951,7 @@ def run_pass(args, H, ctl, dev, steps, warmup):
     md5_in = hashlib.md5(d_in[:sample].cpu().numpy().tobytes()).hexdigest()
     md5_out = hashlib.md5(d_out[:sample].cpu().numpy().tobytes()).hexdigest()
     return {"n": n, "npk": npk, "elapsed": elapsed, "enc_ms": enc_avg, "dec_ms": dec_avg, "status": status, "clocks": clocks,
-            "roundtrip_equal": roundtrip_equal, "md5_in": md5_in, "md5_out": md5_out,
+            "roundtrip_equal": roundtrip_equal, "md5_in": md5_in, "md5_out": md5_out, "outputs": outputs,
             "d_in": d_in, "d_slots": d_slots, "d_out": d_out}
 
 
@@ -991,8 +1044,10 @@ def main(argv=None):
     machine = {"cus": int(getattr(props, "multi_processor_count", MI355X_CUS) or MI355X_CUS), "clock_ghz": SHADER_CLOCK_GHZ}
 
     # ---- the pass the contract's `value` comes from ----
-    P = run_pass(args, H, ctl, dev, args.steps, args.warmup)
+    P = run_pass(args, H, ctl, dev, args.steps, args.warmup, dump=args.dump_outputs is not None and rank == 0)
     n, npk = P["n"], P["npk"]
+    if P["outputs"] is not None:
+        write_outputs(args.dump_outputs, P["outputs"])
     # ---- the roof, measured on this box in this run: a plain device copy of the same buffer (rank 0's figure is quoted) ----
     copy_peak = measure_copy_peak(H, P["d_in"], P["d_out"], n) if rank == 0 else None
     # ---- the kernels either side (compaction, encode + compaction, decode from the stream), untimed region ----

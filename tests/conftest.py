@@ -16,11 +16,3 @@ def pytest_configure(config):
 def port_oracle():
     from oracle import oracle as O
     return O.PortOracle()
-
-
-@pytest.fixture(scope="session")
-def ref_oracle():
-    from oracle import oracle as O
-    if not O.have_reference():
-        pytest.skip("oracle/_ref not built (needs /root/reference in the build container)")
-    return O.ReferenceOracle()

@@ -358,3 +358,49 @@ def test_live_traffic_replaces_the_replayed_figure_and_says_so():
     bare = bench_stub.full_result(1, "weak", traffic={"source": "none"})
     d = json.loads(bench.driver_line(bare))
     assert d["roofline"]["traffic"] is None and "traffic_from" not in d["roofline"]
+
+
+def test_steps_must_be_positive():
+    assert bench.parse_args(["--steps", "1"]).steps == 1
+    for bad in ("0", "-3"):
+        try:
+            bench.parse_args(["--steps", bad])
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(f"--steps {bad} was accepted")
+
+
+def test_output_sample_is_what_the_caller_got_and_nothing_undefined():
+    """--dump-outputs: a fixed packet sample of the slots and of the decoded bytes, the bytes no caller may read (slot bytes at
+    and beyond the packet's compressed length, output bytes beyond the shard) written as 0, every packet's compressed length;
+    float32 / float64 and within the size limit at the 8 GiB default.  (CPU tensors stand in for the device buffers.)"""
+    import numpy as np
+    import torch
+    slot, packet = 40, 32                                   # miniature slots and packets: the same layout
+    npk, n = 1500, 1500 * 32 - 7                            # more packets than the sample, a ragged last packet
+    rng = np.random.default_rng(1)
+    slots = rng.integers(0, 256, npk * slot, dtype=np.uint8)
+    clens = rng.integers(4, slot + 1, npk)
+    slots[0::slot], slots[1::slot] = clens & 0xFF, clens >> 8
+    decoded = rng.integers(0, 256, npk * packet, dtype=np.uint8)
+    a = bench.output_sample(torch.from_numpy(slots), torch.from_numpy(decoded), n, npk, slot, packet)
+    assert set(a) == {"packet_index", "slots", "decoded", "clen"}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    pick = a["packet_index"].astype(np.int64)
+    assert pick[0] == 0 and pick[-1] == npk - 1 and len(pick) == bench.DUMP_SAMPLE_PACKETS + 2 and (np.diff(pick) > 0).all()
+    assert a["slots"].shape == (len(pick), slot) and a["decoded"].shape == (len(pick), packet)
+    for row, p in enumerate(pick):
+        c = clens[p]
+        assert (a["slots"][row, :c] == slots[p * slot:p * slot + c]).all() and (a["slots"][row, c:] == 0).all()
+        valid = min(packet, n - p * packet)
+        assert (a["decoded"][row, :valid] == decoded[p * packet:p * packet + valid]).all() and (a["decoded"][row, valid:] == 0).all()
+    assert (a["clen"] == clens).all()
+    # the same shard size gives the same sample: two runs compare output for output
+    b = bench.output_sample(torch.from_numpy(slots), torch.from_numpy(decoded), n, npk, slot, packet)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    # the 8 GiB default and a shard four times as large stay within the limit (sizes only: clen sampled with a stride)
+    for npk_big in (1 << 20, 1 << 22):
+        stride = -(-npk_big // bench.DUMP_CLEN_PACKETS)
+        nbytes = 8 * (bench.DUMP_SAMPLE_PACKETS + 2) + 4 * (bench.DUMP_SAMPLE_PACKETS + 2) * (8704 + 8192) + 4 * -(-npk_big // stride)
+        assert nbytes <= bench.DUMP_LIMIT_BYTES, (npk_big, nbytes)

@@ -939,3 +939,29 @@ def test_config4_last_rank_of_zipf_64gib_over_8_gpus(H, oracle):
     off, n = sharding.weak_shard(8 << 30, 7)
     assert (off, n) == (56 << 30, 8 << 30)
     _shard_at_true_offset(H, oracle, "zipf", 1, off, n, (0.78, 0.80))
+
+
+def test_bench_dump_outputs_are_the_codecs_outputs(H, oracle, tmp_path):
+    """bench.py --dump-outputs: what the last timed step handed its caller, sampled -- each sampled packet's slot is the checker's
+    packet of the same input bytes, its decoded bytes are those input bytes, and the clen of every packet is its slot's header."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "GPUAR_OVERSUBSCRIBE_DEVICES")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--gib-per-gpu", "0.25", "--no-cpu-baseline",
+           "--no-small-config", "--no-by-kind", "--no-live-traffic", "--detail-file", str(tmp_path / "detail.json"), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    line, d = bench_line_and_detail(r, tmp_path)
+    assert line["steps"] == 3 and d["roundtrip_equal"] is True
+    a = {name: np.load(out / f"{name}.npy") for name in ("packet_index", "slots", "decoded", "clen")}
+    assert sum(v.nbytes for v in a.values()) <= 64 * 10**6 and all(v.dtype in (np.float32, np.float64) for v in a.values())
+    n = 1 << 28
+    npk = n // 8192
+    assert a["clen"].shape == (npk,) and a["slots"].shape[1] == H.SLOT and a["decoded"].shape[1] == H.PACKET
+    for row, p in enumerate(a["packet_index"].astype(np.int64)):
+        data = synth.generate("uniform", 42, 8192, offset=int(p) * 8192)
+        want = np.frombuffer(oracle.encode_packet(data), dtype=np.uint8)
+        assert a["clen"][p] == want.size and np.array_equal(a["slots"][row, :want.size], want), p
+        assert not a["slots"][row, want.size:].any() and np.array_equal(a["decoded"][row], data), p

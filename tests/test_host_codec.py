@@ -5,8 +5,8 @@ arCompress / arDecompress / initializeAdaptiveProbabilityRangeList
 
 Anchors: the tiny vectors of SURVEY.md section 8(b), tests/golden/ref_vectors.json,
 tests/golden/model_vectors.json (caller-owned model carried across calls, from
-oracle/_ref), the C restatement in oracle/, and -- where the build container has
-it -- oracle/_ref live on seeded inputs, including corrupted packets.  No GPU.
+oracle/_ref), the C restatement in oracle/, and tests/golden/seeded_vectors.json
+(oracle/_ref on seeded inputs, including corrupted packets).  No GPU.
 """
 import ctypes as C
 import hashlib
@@ -24,6 +24,12 @@ with open(os.path.join(GOLD, "model_vectors.json")) as f:
     MODELV = json.load(f)
 with open(os.path.join(GOLD, "ref_vectors.json")) as f:
     REFV = json.load(f)["cases"]
+with open(os.path.join(GOLD, "seeded_vectors.json")) as f:
+    SEEDED = json.load(f)
+
+
+def md5(b):
+    return hashlib.md5(bytes(b)).hexdigest()
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -140,33 +146,31 @@ def test_same_symbols_in_both_libraries():
     assert out[:n].tobytes().hex() == "0900050068650823e3" and total.value == 261
 
 
-def test_live_against_reference_with_carried_models(ref_oracle):
-    rng = np.random.default_rng(5)
-    for trial in range(40):
-        kind = synth.KINDS[trial % 3]
-        sizes = [int(x) for x in rng.integers(0, 4000, size=int(rng.integers(2, 5)))]
-        r, t = ref_oracle.model_init()
-        r2, t2 = ref_oracle.model_init()
+def test_carried_models_match_reference_seeded_chains():
+    """40 chains of 2-4 segments, the model carried from call to call, against the reference's packets and model state after
+    every call (tests/golden/seeded_vectors.json; the reference's own decoder left the same state and bytes there)."""
+    chains = SEEDED["carried_models"]
+    assert len(chains) == 40
+    for trial, chain in enumerate(chains):
         enc, dec = HC.Model(), HC.Model()
-        off = 0
-        for n in sizes:
-            data = synth.generate(kind, trial + 1, n, offset=off).tobytes()
-            off += n
-            want, r, t = ref_oracle.encode_packet_model(data, r, t)
-            assert HC.encode_packet(data, enc) == want
-            assert enc.total == t and np.array_equal(enc.ranges, r)
-            back, r2, t2 = ref_oracle.decode_packet_model(want, r2, t2)
-            assert HC.decode_packet(want, dec) == back == data
-            assert dec.total == t2 and np.array_equal(dec.ranges, r2)
+        for seg in chain["segments"]:
+            data = synth.generate(chain["kind"], chain["seed"], seg["n"], offset=seg["offset"]).tobytes()
+            pkt = HC.encode_packet(data, enc)
+            assert len(pkt) == seg["clen"] and md5(pkt) == seg["packet_md5"], (trial, seg["offset"])
+            assert enc.total == seg["total_after"] and md5(enc.ranges.astype("<u2").tobytes()) == seg["ranges_after_md5"]
+            assert HC.decode_packet(pkt, dec) == data
+            assert dec.total == seg["total_after"] and md5(dec.ranges.astype("<u2").tobytes()) == seg["ranges_after_md5"]
 
 
-def test_live_against_reference_on_corrupted_packets(ref_oracle):
+def test_corrupted_packets_decode_like_the_reference():
     # a damaged packet must decode to the same bytes (and stop at the same place) as the reference
-    rng = np.random.default_rng(9)
-    for trial in range(200):
-        kind = synth.KINDS[trial % 3]
-        data = synth.generate(kind, trial + 3, int(rng.integers(1, 3000))).tobytes()
-        pkt = bytearray(ref_oracle.encode_packet(data))
-        for _ in range(int(rng.integers(1, 4))):
-            pkt[int(rng.integers(4, len(pkt)))] ^= 1 << int(rng.integers(0, 8))
-        assert HC.decode_packet(bytes(pkt)) == ref_oracle.decode_packet(bytes(pkt)), trial
+    cases = SEEDED["corrupted_packets"]
+    assert len(cases) == 200
+    for trial, c in enumerate(cases):
+        data = synth.generate(c["kind"], c["seed"], c["n"]).tobytes()
+        pkt = bytearray(HC.encode_packet(data))
+        assert md5(pkt) == c["packet_md5"], trial
+        for byte, bit in c["flips"]:
+            pkt[byte] ^= 1 << bit
+        back = HC.decode_packet(bytes(pkt))
+        assert len(back) == c["decoded_len"] and md5(back) == c["decoded_md5"], trial

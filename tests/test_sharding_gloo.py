@@ -33,6 +33,16 @@ def test_plan_shards_properties():
     assert sharding.weak_shard(8 << 30, 3) == (3 * (8 << 30), 8 << 30)
 
 
+class GlooDist:
+    """torch.distributed for the CPU ranks of these tests, with gloo's own barrier.  dist.barrier() first asks torch which
+    accelerator the machine has, and on a GPU box that query opens the GPU in every rank that makes it: eight CPU ranks would be
+    eight processes holding the GPU, more than such a box admits.  dist.monitored_barrier() is gloo's and asks nothing."""
+    barrier = staticmethod(dist.monitored_barrier)
+
+    def __getattr__(self, name):
+        return getattr(dist, name)
+
+
 def _worker(rank, world, port, n, kind, seed, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -44,7 +54,7 @@ def _worker(rank, world, port, n, kind, seed, q):
     dist.all_gather(sizes, torch.tensor([seg.size], dtype=torch.int64))
     t = torch.tensor([0.5 + rank], dtype=torch.float64)               # stand-in for the per-rank elapsed time
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    dist.barrier()
+    dist.monitored_barrier()                                          # (not dist.barrier(): see GlooDist)
     q.put((rank, seg.tobytes(), [int(s.item()) for s in sizes], float(t.item())))
     dist.destroy_process_group()
 
@@ -85,7 +95,7 @@ def _worker8(rank, world, port, q):
     off, n = sharding.plan_shards(total, world)[rank]
     weak = bench.plan_shard(bench.parse_args(["--gpus", "8", "--gib-per-gpu", "0.125"]), world, rank)
     seg = O.PortOracle().encode_stream(synth.generate("uniform", 42, n, offset=off))
-    ctl = bench.Control(dist, world, rank, cpu, True, "gloo", device_sync=lambda: None)      # (no device here: the barrier's GPU sync is a no-op)
+    ctl = bench.Control(GlooDist(), world, rank, cpu, True, "gloo", device_sync=lambda: None)      # (no device here: the barrier's GPU sync is a no-op)
     rows = ctl.gather_rows([1, int(seg.size), n, 1, 1000 + rank, 2000 + rank])
     slowest = ctl.max_over_ranks(0.25 * (rank + 1))
     fewest = ctl.min_over_ranks(100 + rank)
