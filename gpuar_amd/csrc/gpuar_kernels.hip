@@ -1213,7 +1213,8 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
     // finds s with cumLo*range <= R0 < cumHi*range for R0 = (off + 1)*total - 1 < range*total; then
     // dn = floor(cumLo*range/total) <= off and (off + 1)*total <= cumHi*range gives off + 1 <= up, so
     // 0 <= off - dn < up - dn = width, and appending n stream bits to both keeps ((off - dn) : bits) << n below
-    // width << n.  Round 2 carried a per-symbol minimum for it; 65 million symbols of garbage never raised it.)
+    // width << n.  Round 2 carried a per-symbol minimum for it; 65 million symbols of garbage never raised it.  The
+    // reference decodes every packet of tests/damage_sweep.py to its full ulen, as this argument says it must.)
     uint32_t kff = 0xFFFFu;                    // low half stays 0xFFFF, high half is scratch of the renormalisation
     const uint32_t k64k = 0x10000u, k64k1 = 0x10001u;
     const uint32_t minus_half = 0xFFFF8000u;               // (2 * width - 1) << 15 = (width << 16) + this: see renorm_count
@@ -1231,6 +1232,12 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
     // ~4000 cycles ago.  Offsets are counted from base16 = base rounded down to 16 bytes, so pieces are
     // aligned (an aligned piece that holds one readable byte never crosses a page); past the end of what
     // may be read the last such piece is repeated (a well-formed packet decodes the same whatever follows).
+    // Unlike DecoderLane::fetch it is not masked: a damaged packet read past the end sees that piece, its
+    // bytes behind the end included, again and again instead of zeros (include/gpuar_hip.h,
+    // garDecompressExecutor; tests/test_gpu_damaged.py part 4).  Masking it costs: a build whose phase masked the
+    // landed piece in place (a v_cmp, s_and_saveexec, s_cbranch_execz and s_or per phase; the masks themselves on the
+    // rare path only) decoded the bench workload in 24.30 / 24.29 ms against 23.95 / 23.91 ms unmasked, interleaved
+    // runs on one MI355X: +1.5 %, against run-to-run noise of about 0.04 ms.
     // A lane consumes at most 16 bits per symbol (n = e + u <= 16: range' = width << n <= 2^16, whatever the
     // bits are) = 16 bytes per phase of EIGHT symbols (rounds 1-3 reckoned with 31 bits and ran the phase every
     // four), a phase brings 16.  The reader's position A is the offset of the dword `ahead` holds, as of the last even step

@@ -1141,6 +1141,7 @@ struct DecoderLane {
     const uint8_t *base;       // start of the bytes this wavefront reads (the same in every lane: a scalar on the GPU)
     uint32_t next;             // offset from base of the dword after `ahead` (base + next is 4-byte aligned)
     uint32_t last;             // offset of the last dword that still holds a readable byte
+    uint32_t tail;             // the readable bytes of that dword, as a mask of the dword as loaded
     uint32_t lo;               // lower bound of the interval (< 2^15 between symbols)
     uint32_t range;            // hi - lo + 1  (2^14 < range <= 2^16 between symbols)
     uint32_t off;              // code - lo
@@ -1149,13 +1150,16 @@ struct DecoderLane {
     bool bad;
 
     // An aligned dword that holds at least one readable byte never crosses a
-    // page, so it is loaded whole; past the last such dword the reader simply
-    // keeps re-reading it (a well-formed packet decodes the same whatever
-    // follows it), which costs one v_min instead of a compare and a branch.
+    // page, so it is loaded whole; its bytes at or beyond the limit are masked
+    // off, and past it nothing more is loaded: the reader sees zeros there, as
+    // the reference does behind its input (ref_decode_packet's staging, and
+    // host_codec.cpp's BitSource).
     GPUAR_LANE uint32_t fetch() {
-        const uint32_t w = load32(base + (next < last ? next : last));
+        const uint32_t at = next < last ? next : last;
+        const uint32_t w = load32(base + at);
+        const uint32_t keep = next < last ? 0xFFFFFFFFu : (next == last ? tail : 0u);
         next += 4;
-        return w;
+        return w & keep;
     }
 
     // the next 32 stream bits, left-aligned
@@ -1174,7 +1178,8 @@ struct DecoderLane {
     }
 
     // The packet starts `pkt_off` bytes after `uniform_base`; bytes up to `limit_off` (exclusive, > pkt_off
-    // for a live lane) may be read.  A dead lane (live == false) reads the dword at uniform_base.
+    // for a live lane) may be read; a packet whose 4-byte header does not end by then is bad and decodes nothing.
+    // A dead lane (live == false) reads the dword at uniform_base.
     GPUAR_LANE void open(uint8_t *col, const uint8_t *uniform_base, uint32_t pkt_off, uint32_t limit_off, bool live) {
         model.col = col;
         model.reset();
@@ -1184,18 +1189,25 @@ struct DecoderLane {
         outword = 0;
         uint32_t body = 0;
         last = 0;
+        tail = 0xFFFFFFFFu;
         if (live) {
             const uint8_t *pkt = base + pkt_off;
-            const uint32_t clen = pkt[0] | (static_cast<uint32_t>(pkt[1]) << 8);
-            ulen = pkt[2] | (static_cast<uint32_t>(pkt[3]) << 8);
-            if (ulen > kPacket || clen < kHdr) {   // the reference would run off its buffers here
+            if (limit_off < pkt_off + kHdr) {      // the header itself is not inside what may be read
                 bad = true;
-                ulen = 0;
+            } else {
+                const uint32_t clen = pkt[0] | (static_cast<uint32_t>(pkt[1]) << 8);
+                ulen = pkt[2] | (static_cast<uint32_t>(pkt[3]) << 8);
+                if (ulen > kPacket || clen < kHdr) {   // the reference would run off its buffers here
+                    bad = true;
+                    ulen = 0;
+                }
             }
             body = pkt_off + kHdr;
             // offset of the dword holding byte limit_off - 1, counted from an aligned address
             const uint32_t skew = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(base) & 3u);
             last = ((limit_off - 1u + skew) & ~3u) - skew;
+            const uint32_t readable = limit_off - last;        // 1 ... 4 bytes of that dword (little-endian: the low ones)
+            tail = readable >= 4u ? 0xFFFFFFFFu : (1u << (8u * readable)) - 1u;
         }
         const uint32_t misalign = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(base + body) & 3u);
         next = body - misalign;

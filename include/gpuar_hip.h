@@ -51,8 +51,10 @@ extern "C" {
  * device's fallback word that gpuar_hip_status reads). */
 #define GPUAR_STATUS_SLOT_OVERFLOW  0x1u /* a packet outgrew its 8704-byte slot; its slot is truncated
                                             (the reference would write past the slot, SURVEY.md s.7 risk 3) */
-#define GPUAR_STATUS_BAD_PACKET     0x2u /* decode met a malformed packet (ulen > 8192, clen < 4, or a code
-                                            value outside the model, src/gpuar_kernel.cu:873-877)          */
+#define GPUAR_STATUS_BAD_PACKET     0x2u /* decode met a header it refuses (ulen > 8192 or clen < 4); that
+                                            packet's output is left unwritten.  Any other damage is decoded as
+                                            the reference decodes it: its third exit, a code value no symbol
+                                            owns (src/gpuar_kernel.cu:873-877), cannot be reached            */
 
 /* ------------------------------------------------------------------------
  * Reference-named entry points (the reference's kernel object exports these;
@@ -77,8 +79,14 @@ void garCompressExecutor(const uint8_t *source, size_t size, uint8_t *destinatio
 
 /* Replaces garDecompressExecutor (src/gpuar_kernel.cu:946-954): `size` is
  * numPackets*8704 (src/gpu_compressor.cpp:357); every slot that STARTS inside
- * `size` is decoded (index*8704 < size, src/gpuar_kernel.cu:916-934) and nothing
- * at or beyond source + size is read; slot p decodes to destination + p*8192. */
+ * `size` is decoded (index*8704 < size, src/gpuar_kernel.cu:916-934); slot p
+ * decodes to destination + p*8192.  Bytes behind source + size may be loaded
+ * from the 16-byte-aligned piece of memory that holds its last byte, and no
+ * further: a packet whose decoding runs past the end gets unspecified bytes
+ * within its own ulen (the reference would read zeros there; a packet shorter
+ * than 64 bytes does read zeros), and bytes more than 15 behind the end never
+ * change any output.  A slot whose 4-byte header does not lie in front of the
+ * end is flagged GPUAR_STATUS_BAD_PACKET and writes nothing. */
 void garDecompressExecutor(const uint8_t *source, size_t size, uint8_t *destination, uint32_t numBlocks);
 
 /* ------------------------------------------------------------------------
@@ -137,7 +145,9 @@ int gpuar_hip_compact(const uint8_t *d_slots, size_t n_packets, uint8_t *d_strea
 /* Decode straight from a back-to-back packet stream: d_offsets[p] is the byte
  * offset of packet p in d_stream (n_packets+1 entries; the host builds it by
  * walking `off += clen`, src/gpu_compressor.cpp:299-312, or keeps the array
- * gpuar_hip_compact produced). */
+ * gpuar_hip_compact produced).  A packet's reader may run on into the packets
+ * behind it, as the reference's does, up to d_stream + d_offsets[n_packets];
+ * behind that end the same holds as for garDecompressExecutor's `size`. */
 int gpuar_hip_decode_stream(const uint8_t *d_stream, const uint64_t *d_offsets, size_t n_packets,
                             uint8_t *d_out, uint32_t *d_status, void *stream);
 

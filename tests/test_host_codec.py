@@ -174,3 +174,20 @@ def test_corrupted_packets_decode_like_the_reference():
             pkt[byte] ^= 1 << bit
         back = HC.decode_packet(bytes(pkt))
         assert len(back) == c["decoded_len"] and md5(back) == c["decoded_md5"], trial
+
+
+def test_damaged_packets_decode_like_the_reference():
+    """The 1024 damaged packets of tests/golden/damaged_vectors.json (tests/damage_sweep.py: bit flips, bursts, cuts,
+    raised and lowered ulen, random bodies, empty bodies, spliced headers) through arDecompress: the reference's
+    decoded length and md5.  The packets are rebuilt from this codec's own encodings and pinned by their md5."""
+    import damage_sweep as DS
+    import length_sweep as LS
+    with open(os.path.join(GOLD, "damaged_vectors.json")) as f:
+        cases = json.load(f)["cases"]
+    assert len(cases) == 1024 and {c["class"] for c in cases} == set(DS.CLASSES)
+    encode = lambda m: np.frombuffer(HC.encode_packet(LS.packet(m).tobytes()), dtype=np.uint8)  # noqa: E731
+    for c in cases:
+        pkt, cls = DS.damaged(c["n"], encode)
+        assert md5(pkt.tobytes()) == c["packet_md5"] and cls == c["class"], c["n"]
+        back = HC.decode_packet(pkt.tobytes())
+        assert len(back) == c["decoded_len"] and md5(back) == c["decoded_md5"], f"packet {c['n']} ({cls})"

@@ -338,3 +338,142 @@ def test_lane_decoder_at_every_packet_length(emu, length_sweep, layout):
             pytest.fail(f"{layout}: packet {i} (ulen {p.size}, lane {lane}) differs first at byte {at}: "
                         f"{got[lane, at]:#04x} != {p[at]:#04x}")
         assert not got[lane, p.size:].any(), (layout, i, lane)       # nothing written after ulen
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# damaged packets (tests/damage_sweep.py): DecoderLane is the GPU's partial-block path and the decoder of `gpuar d --host`
+# ---------------------------------------------------------------------------------------------------------------------
+def emu_decode_one(lib, pkt: np.ndarray, behind: int = 0x00, limit: int = None, skew: int = 0):
+    """DecoderLane on one packet whose readable bytes end at `limit` (default: the packet's end), with 64 bytes of
+    `behind` after the limit in the same allocation, the packet starting `skew` bytes past a 4-byte boundary:
+    (output row with 0xA5 after ulen, bad)."""
+    limit = pkt.size if limit is None else limit
+    buf = np.full(skew + limit + 64, behind, dtype=np.uint8)
+    assert buf.ctypes.data % 4 == 0
+    buf[:skew] = 0x77
+    buf[skew:skew + limit] = pkt[:limit]
+    offs = np.asarray([skew, skew + limit], dtype=np.uint64)
+    out = np.full(8192 + 64, 0xA5, dtype=np.uint8)
+    bad = lib.emu_decode_stream(buf.ctypes.data_as(u8p), offs.ctypes.data_as(u64p), 1, out.ctypes.data_as(u8p))
+    return out, bad
+
+
+def _check_damaged(lib, pkt, want: bytes, what):
+    """Both paddings behind the packet decode to `want` (the reference's zero-padded decode), nothing is flagged,
+    and nothing is written after it."""
+    for behind in (0x00, 0xEE):
+        out, bad = emu_decode_one(lib, pkt, behind)
+        got = out[:len(want)].tobytes()
+        if got != want:
+            at = next(i for i in range(len(want)) if got[i] != want[i])
+            pytest.fail(f"{what}, {behind:#04x} behind the packet: {len(want)} bytes, first wrong at byte {at}: "
+                        f"{got[at]:#04x} != {want[at]:#04x}")
+        assert bad == 0, what
+        assert (out[len(want):] == 0xA5).all(), f"{what}: written after ulen {len(want)}"
+
+
+@pytest.fixture(scope="module")
+def damaged_sweep(port_oracle):
+    """tests/damage_sweep.py's 8192 damaged packets, made from the port oracle's encodings (pinned to the reference's)."""
+    import damage_sweep as DS
+    import length_sweep as LS
+    return DS, DS.sweep(lambda m: port_oracle.encode_stream(LS.packet(m)))
+
+
+def test_lane_decoder_on_every_damaged_packet_against_the_reference(emu, damaged_sweep):
+    """The whole damage sweep (8192 packets, eight classes) against the live reference, each packet's readable bytes
+    ending with it and 0x00 / 0xEE behind.  The reference decodes exactly ulen bytes of every one (if it ever stopped
+    early -- a code value no symbol owns -- that would contradict the off < range argument of decode_wave)."""
+    from oracle import oracle as O
+    if not O.have_reference():
+        pytest.skip("oracle/_ref not built here: test_lane_decoder_on_damaged_vectors holds the same decoder to its stored outputs")
+    ref = O.ReferenceOracle()
+    DS, (pkts, classes) = damaged_sweep
+    for n, (pkt, cls) in enumerate(zip(pkts, classes), 1):
+        want = ref.decode_packet(pkt.tobytes())
+        assert len(want) == DS.fields(pkt)[1], f"the reference stopped early on packet {n} ({cls}): {len(want)} bytes"
+        _check_damaged(emu, pkt, want, f"packet {n} ({cls})")
+
+
+def test_lane_decoder_on_damaged_vectors(emu, damaged_sweep):
+    """1024 of the sweep's damaged packets against the reference's stored decode (tests/golden/damaged_vectors.json):
+    the same check where oracle/_ref is absent."""
+    import hashlib
+    import json
+    DS, (pkts, classes) = damaged_sweep
+    with open(os.path.join(HERE, "golden", "damaged_vectors.json")) as f:
+        cases = json.load(f)["cases"]
+    assert len(cases) == 1024 and {c["class"] for c in cases} == set(DS.CLASSES)
+    for c in cases:
+        pkt = pkts[c["n"] - 1]
+        assert hashlib.md5(pkt.tobytes()).hexdigest() == c["packet_md5"] and classes[c["n"] - 1] == c["class"], c["n"]
+        assert c["decoded_len"] == DS.fields(pkt)[1], c["n"]
+        for behind, skew in ((0x00, 0), (0xEE, c["n"] % 4)):
+            out, bad = emu_decode_one(emu, pkt, behind, skew=skew)
+            got = out[:c["decoded_len"]].tobytes()
+            assert hashlib.md5(got).hexdigest() == c["decoded_md5"], f"packet {c['n']} ({c['class']}), {behind:#04x} behind, skew {skew}"
+            assert bad == 0 and (out[c["decoded_len"]:] == 0xA5).all(), c["n"]
+
+
+def test_lane_decoder_on_corrupted_packets(emu):
+    """The 200 bit-flipped packets of tests/golden/seeded_vectors.json (what host_codec.cpp is held to) through
+    DecoderLane: the reference's decoded length and md5."""
+    import hashlib
+    import json
+    from gpuar_amd import host as HC
+    from gpuar_amd import synth
+    with open(os.path.join(HERE, "golden", "seeded_vectors.json")) as f:
+        cases = json.load(f)["corrupted_packets"]
+    assert len(cases) == 200
+    for trial, c in enumerate(cases):
+        data = synth.generate(c["kind"], c["seed"], c["n"]).tobytes()
+        pkt = bytearray(HC.encode_packet(data))
+        assert hashlib.md5(pkt).hexdigest() == c["packet_md5"], trial
+        for byte, bit in c["flips"]:
+            pkt[byte] ^= 1 << bit
+        out, bad = emu_decode_one(emu, np.frombuffer(bytes(pkt), dtype=np.uint8))
+        assert bad == 0 and hashlib.md5(out[:c["decoded_len"]].tobytes()).hexdigest() == c["decoded_md5"], trial
+        assert (out[c["decoded_len"]:] == 0xA5).all(), trial
+
+
+def test_lane_decoder_refuses_invalid_headers(emu, damaged_sweep, port_oracle):
+    """ulen > 8192 or clen < 4: flagged, nothing written (the reference would run off its buffers); ulen = 0 with a
+    valid clen writes nothing and is not flagged."""
+    import length_sweep as LS
+    DS = damaged_sweep[0]
+    for pkt, what in DS.invalid(lambda m: port_oracle.encode_stream(LS.packet(m))):
+        out, bad = emu_decode_one(emu, pkt)
+        assert bad == 1 and (out == 0xA5).all(), what
+    zero = port_oracle.encode_stream(LS.packet(100))
+    zero[2:4] = 0
+    out, bad = emu_decode_one(emu, zero)
+    assert bad == 0 and (out == 0xA5).all()
+
+
+def test_bytes_behind_the_limit_never_change_the_output(emu, port_oracle):
+    """A packet whose readable bytes end inside it (clen and ulen kept, the limit at the cut) decodes as the reference
+    decodes the bytes in front of the limit followed by zeros, whatever lies behind the limit: DecoderLane masks the
+    bytes of the last dword at or beyond the limit and loads nothing after it.  64 packets of 8192 bytes, cut at every
+    alignment mod 16, each at every start skew mod 4 (the dword boundaries fall elsewhere in the packet); the expectation is host_codec.cpp's arDecompress on the bytes in front of the cut (held to the
+    reference by tests/test_host_codec.py)."""
+    from gpuar_amd import host as HC
+    from gpuar_amd import synth
+    rng = np.random.default_rng(20261015)
+    for trial in range(64):
+        data = synth.generate(synth.KINDS[trial % 3], 500 + trial, 8192)
+        pkt = port_oracle.encode_stream(data)
+        cut = int(rng.integers(8, pkt.size - 32)) // 16 * 16 + trial % 16
+        want = HC.decode_packet(pkt[:cut].tobytes())
+        assert len(want) == 8192, trial
+        for skew in range(4):
+            rows = []
+            for behind in (0x00, 0xEE, 0xFF):
+                out, bad = emu_decode_one(emu, pkt, behind, limit=cut, skew=skew)
+                assert bad == 0 and (out[8192:] == 0xA5).all(), (trial, behind, skew)
+                rows.append(out[:8192].tobytes())
+            assert rows[0] == rows[1] == rows[2], f"trial {trial}, skew {skew}: the output depends on the bytes behind the limit (cut {cut})"
+            assert rows[0] == want, f"trial {trial}, skew {skew}: differs from the reference's zero-padded decode (cut {cut})"
+    for cut in (1, 2, 3):                                  # the header itself cut: flagged, nothing written
+        for skew in range(4):
+            out, bad = emu_decode_one(emu, pkt, 0xEE, limit=cut, skew=skew)
+            assert bad == 1 and (out == 0xA5).all(), (cut, skew)
