@@ -1,0 +1,151 @@
+"""Many tensors compressed and decompressed in one launch (gpuar_hip_encode_batch / decode_batch / decode_stream_batch).
+
+Each tensor is taken as its bytes and coded exactly as if it were encoded alone: buffer b's stream is the bytes
+`gpuar c` writes for it behind the 20-byte header (Compressed.gip(b)).  The descriptors are built on the host and go to
+the device in one copy; the status word is checked after every call and any bit raises.  There is no CPU fallback and
+no silent copy: a tensor that is not 16-byte aligned is refused before anything is launched.
+
+    c = batch.compress([w1, w2, w3])          # contiguous CUDA tensors on one device
+    outs = batch.decompress(c)                # uint8 tensors, one per input
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+from . import hip as H
+from .hip import GpuarError
+
+
+def _tensor_bytes(t, name):
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise GpuarError(f"{name} is not a tensor")
+    if not t.is_cuda:
+        raise GpuarError(f"{name} is not a CUDA tensor")
+    if not t.is_contiguous():
+        raise GpuarError(f"{name} is not contiguous")
+    return t.numel() * t.element_size()
+
+
+def describe(tensors, what="tensors"):
+    """Host-side descriptors of a list of tensors: (device, pointers, sizes, first_packet, packet count).  Raises GpuarError
+    for anything the kernels could not take: a non-CUDA or non-contiguous tensor, tensors on different devices, or a
+    non-empty tensor whose data is not 16-byte aligned."""
+    tensors = list(tensors)
+    ptrs, sizes, device = [], [], None
+    for i, t in enumerate(tensors):
+        n = _tensor_bytes(t, f"{what}[{i}]")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise GpuarError(f"{what}[{i}] is on {t.device}, the batch on {device}")
+        if n and t.data_ptr() % 16:
+            raise GpuarError(f"{what}[{i}] is not 16-byte aligned (data_ptr() % 16 = {t.data_ptr() % 16}); pass an aligned copy")
+        ptrs.append(t.data_ptr() if n else 0)
+        sizes.append(n)
+    first_packet, n_packets = H.batch_packet_count(sizes)
+    return device, ptrs, sizes, first_packet, n_packets
+
+
+def _upload(device, *rows):
+    """The descriptor rows (lists of ints) as ONE int64 device tensor (one copy), returned split back into rows."""
+    import torch
+    flat = [v if v < (1 << 63) else v - (1 << 64) for row in rows for v in row]
+    host = torch.tensor(flat or [0], dtype=torch.int64).pin_memory() if torch.cuda.is_available() else torch.tensor(flat or [0], dtype=torch.int64)
+    dev = host.to(device, non_blocking=True)
+    out, at = [], 0
+    for row in rows:
+        out.append(dev[at:at + len(row)])
+        at += len(row)
+    return out, host
+
+
+def _nothing():
+    import contextlib
+    return contextlib.nullcontext()
+
+
+def _raise_on_status(d_status, what):
+    flags = int(d_status.item())
+    if flags:
+        names = [n for bit, n in ((H.STATUS_SLOT_OVERFLOW, "SLOT_OVERFLOW"), (H.STATUS_BAD_PACKET, "BAD_PACKET"),
+                                  (H.STATUS_BAD_BATCH, "BAD_BATCH")) if flags & bit]
+        raise GpuarError(f"{what}: device status {flags:#x} ({', '.join(names) or 'unknown'})")
+
+
+@dataclass
+class Compressed:
+    """A compressed batch: `stream` (uint8, device, exactly the compressed bytes) holds every buffer's packets back to back
+    in batch order, `offsets`
+    (int64, device, n_packets + 1) the packet offsets in it, `first_packet` (host list, n_buffers + 1) which packets
+    belong to which buffer, `sizes` the buffers' byte counts."""
+    stream: object
+    offsets: object
+    first_packet: list
+    sizes: list
+
+    @property
+    def n_buffers(self) -> int:
+        return len(self.sizes)
+
+    @property
+    def n_packets(self) -> int:
+        return self.first_packet[-1]
+
+    def _offsets_host(self):
+        if getattr(self, "_off", None) is None:
+            self._off = self.offsets.cpu().tolist()
+        return self._off
+
+    def payload(self, b: int):
+        """A view of buffer b's packet stream (the bytes behind the header of its .gip file)."""
+        off = self._offsets_host()
+        return self.stream[off[self.first_packet[b]]:off[self.first_packet[b + 1]]]
+
+    def gip(self, b: int) -> bytes:
+        """Buffer b as a whole .gip file: what `gpuar c` writes for it."""
+        p = self.payload(b)
+        return H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
+
+
+def compress(tensors, mode=None, stream=None) -> Compressed:
+    """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
+    compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode)."""
+    import torch
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    n = len(sizes)
+    with torch.cuda.stream(stream) if stream is not None else _nothing():
+        (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
+        d_status = torch.zeros(1, dtype=torch.int32, device=device)
+        d_slots = H.encode_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
+        d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
+        _raise_on_status(d_status, "encode_batch")
+        # compact() wrote into a buffer of n_packets * 8704 bytes: keep only the compressed bytes (one copy), so that the
+        # result takes what it compressed to, not ~1.06 x the input
+        used = int(d_offsets[-1].item())
+        d_stream = d_stream[:used].clone()
+        del d_slots
+    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes)
+
+
+def decompress(c: Compressed, out=None, stream=None):
+    """Decode every buffer of `c` in one launch.  Returns a list of uint8 tensors, or fills the caller's tensors `out` (one per
+    buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them."""
+    import torch
+    device = c.stream.device
+    if out is None:
+        out = [torch.empty(n, dtype=torch.uint8, device=device) for n in c.sizes]
+    elif len(out) != c.n_buffers:
+        raise GpuarError(f"out has {len(out)} tensors, the batch {c.n_buffers} buffers")
+    _dev, ptrs, room, _fp, _np = describe(out, "out")
+    for b, (have, need) in enumerate(zip(room, c.sizes)):
+        if have < need:
+            raise GpuarError(f"out[{b}] holds {have} bytes, buffer {b} needs {need}")
+    with torch.cuda.stream(stream) if stream is not None else _nothing():
+        (d_ptrs, d_room, d_fp), _keep = _upload(device, ptrs, room, c.first_packet)
+        d_status = torch.zeros(1, dtype=torch.int32, device=device)
+        H.decode_stream_batch(c.stream, c.offsets, d_fp, c.n_buffers, c.n_packets, d_ptrs, d_room, stream=stream, d_status=d_status)
+        _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
+    return out

@@ -198,8 +198,9 @@ __device__ __forceinline__ uint32_t byte_tag(uint32_t word, uint32_t kByte) {   
 // every touch of a line is a fetch from memory (rocprofv3 FETCH_SIZE: 3.3x the input with 16-byte
 // pieces and two modelers reading, 1.2-1.8x with 64-byte pieces, 1.01x now that one wavefront reads
 // and takes the whole 128-byte line at a time).
+template <bool kBatch = false>
 __device__ __forceinline__ void run_top(EncodeLds &lds, const uint8_t *in, uint32_t lane, uint32_t len,
-                                        uint32_t len_min, uint32_t n_phases) {
+                                        uint32_t len_min, uint32_t n_phases, uint32_t whole_max = 0) {
     constexpr uint32_t kChunkPhases = 8;                       // phases per fetch
     constexpr uint32_t kChunk = kChunkPhases * kPhase;         // 64 symbols = 64 bytes = 4 x 16-byte loads
     constexpr uint32_t kPieces = kChunk / 16u;
@@ -265,6 +266,55 @@ __device__ __forceinline__ void run_top(EncodeLds &lds, const uint8_t *in, uint3
     uint4 cur = make_uint4(0, 0, 0, 0), nxt = cur;
     if (k * kPhase < len) cur = load16_guarded(in + k * kPhase, len - k * kPhase);
     if (k * kPhase + 16u < len) nxt = load16_guarded(in + k * kPhase + 16u, len - (k * kPhase + 16u));
+    if constexpr (kBatch) {
+        // A batch (encode_batch_kernel): the lanes' lengths differ anywhere in the wavefront.  Every whole phase a lane
+        // owns runs on the whole-phase body, masked by the lane's own count of whole phases (a lane past it sits out with
+        // its state untouched); the lane's partial phase, if any, is deferred to ONE last phase in which every lane codes
+        // its own at its own symbol index.  The other roles defer it identically (ring slots and barrier counts agree).
+        const uint32_t whole = len / kPhase;
+        for (; k < whole_max; ++k) {
+            const uint32_t base = k * kPhase;
+            const bool odd = (k & 1u) != 0u;                   // wave-uniform: second half of `cur`
+            const uint32_t words[3] = {odd ? cur.z : cur.x, odd ? cur.w : cur.y, odd ? nxt.x : cur.z};
+            if (odd) {
+                cur = nxt;
+                const uint32_t ahead = base + kPhase + 16u;
+                if (ahead < len) nxt = load16_guarded(in + ahead, len - ahead);
+                else nxt = make_uint4(0, 0, 0, 0);
+            }
+            if (k < whole) {
+                uint32_t *out = &lds.sums[slot][0][lane];
+                lds.bytes[k & 1u][0][lane] = words[0];
+                lds.bytes[k & 1u][1][lane] = words[1];
+#pragma unroll
+                for (uint32_t j = 0; j < kPhase; ++j) {
+                    const uint32_t xn_tag = byte_tag(words[(j + 1) >> 2], (j + 1) & 3u);
+                    out[j * kLanes] = model.step_tag(model.next_tag, 256u + base + j, xn_tag);
+                }
+            }
+            slot = next_slot(slot);
+            lds_barrier();
+        }
+        if (k < n_phases) {                                    // the deferred partial phases, each lane at its own index
+            const uint32_t own = whole * kPhase, part = len - own;
+            const uint4 v = part ? load16_guarded(in + own, part) : make_uint4(0, 0, 0, 0);
+            lds.bytes[k & 1u][0][lane] = v.x;
+            lds.bytes[k & 1u][1][lane] = v.y;
+            uint32_t *out = &lds.sums[slot][0][lane];
+            uint64_t w = (static_cast<uint64_t>(v.y) << 32) | v.x;
+#pragma unroll 1
+            for (uint32_t j = 0; j < part; ++j) {
+                const uint32_t x = static_cast<uint32_t>(w) & 0xFFu;
+                w >>= 8;
+                out[j * kLanes] = model.step(x, 256u + own + j, static_cast<uint32_t>(w) & 0xFFu);
+            }
+            slot = next_slot(slot);
+            lds_barrier();
+            ++k;
+        }
+        for (; k < n_phases + 2u; ++k) lds_barrier();
+        return;
+    }
     for (; k < n_phases + 2u; ++k) {
         if (k < n_phases) {
             const uint32_t base = k * kPhase;
@@ -490,6 +540,209 @@ encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict_
             if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
         }
     }
+}
+
+// The low modeler of a batch: run_low's whole-phase body on the schedule of run_top<true>
+__device__ __forceinline__ void batch_low(EncodeLds &lds, uint32_t lane, uint32_t len, uint32_t len_min, uint32_t n_phases, uint32_t whole_max) {
+    LowModeler<7> model;
+    model.open(lds.tree, 2u * lane_column(lane), 0u);
+    lds_barrier();                                             // phase 0: the top modeler's first
+    uint32_t slot = 0, k = 0;
+    auto whole_phase = [&](uint32_t k) __attribute__((always_inline)) {     // the symbols of phase k, during phase k + 1
+        const uint32_t base = k * kPhase;
+        uint32_t *io = &lds.sums[slot][0][lane];
+        uint32_t part[kPhase], tag[kPhase];
+        const uint32_t bytes[2] = {lds.bytes[k & 1u][0][lane], lds.bytes[k & 1u][1][lane]};
+#pragma unroll
+        for (uint32_t j = 0; j < kPhase; ++j) part[j] = io[j * kLanes], tag[j] = byte_tag(bytes[j >> 2], j & 3u);
+        model.prime_tag(tag[0]);
+#pragma unroll
+        for (uint32_t j = 0; j < kPhase; ++j) {
+            if (j + 1u < kPhase) io[j * kLanes] = model.step_tag(tag[j], 256u + base + j, tag[j + 1u], part[j]);
+            else io[j * kLanes] = model.step_last_tag(tag[j], 256u + base + j, part[j]);
+        }
+    };
+    const uint32_t whole_min = len_min / kPhase;
+    for (; k < whole_min; ++k) {                               // every lane owns the phase
+        whole_phase(k);
+        slot = next_slot(slot);
+        lds_barrier();
+    }
+    const uint32_t whole = len / kPhase;
+    for (; k < whole_max; ++k) {                               // the lanes that own it; the others sit it out
+        if (k < whole) whole_phase(k);
+        slot = next_slot(slot);
+        lds_barrier();
+    }
+    if (k < n_phases) {                                        // the deferred partial phases, each lane at its own index
+        const uint32_t own = whole * kPhase, part = len - own;
+        uint32_t *io = &lds.sums[slot][0][lane];
+        uint64_t w = (static_cast<uint64_t>(lds.bytes[k & 1u][1][lane]) << 32) | lds.bytes[k & 1u][0][lane];
+#pragma unroll 1
+        for (uint32_t j = 0; j < part; ++j) {
+            const uint32_t t = model.tree.tag(static_cast<uint32_t>(w) & 0xFFu);
+            w >>= 8;
+            model.prime_tag(t);
+            io[j * kLanes] = model.step_last_tag(t, 256u + own + j, io[j * kLanes]);
+        }
+        lds_barrier();
+    }
+    lds_barrier();                                             // phase n_phases + 1: the coder's last
+}
+
+// encode_kernel's choice of roles by SIMD (see there), for encode_batch_kernel: 0 top modeler, 1 low modeler, 2 coder, 3 courier
+__device__ __forceinline__ uint32_t encode_role(EncodeLds &lds, uint32_t lane) {
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));        // HW_ID
+    const uint32_t simd = (hw >> 4) & 3u;
+    uint32_t *hello = &lds.sums[0][0][0];                      // (the ring is not in use yet)
+    if (lane == 0) hello[wave] = simd;
+    if (threadIdx.x == 0) {
+        const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));   // XCC_ID
+        hello[4] = atomicAdd(&g_cu_ticket[((xcc & 7u) << 8) | ((hw >> 8) & 0xFFu)], 1u);
+    }
+    __syncthreads();
+    const uint32_t seen = (1u << hello[0]) | (1u << hello[1]) | (1u << hello[2]) | (1u << hello[3]);
+    const uint32_t by_simd = (simd - hello[4] - 1u) & 3u;
+    const uint32_t role = __builtin_amdgcn_readfirstlane(seen == 0xFu ? by_simd : wave);   // 3 = idle
+    __syncthreads();
+    return role;
+}
+
+// The four roles of encode_kernel for a workgroup of 64 batch packets: lane l codes `len` bytes at `in` into slot
+// group * 64 + l.  The lanes' lengths may differ anywhere in the wavefront, so every role keeps each lane on the
+// whole-phase body for every whole phase the lane owns and defers its partial phase to one last phase (run_top<true>):
+// n_phases = (the most whole phases of any lane) + (1 if some lane has a partial phase), n_phases + 2 barriers per role.
+__device__ __forceinline__ void batch_roles(EncodeLds &lds, uint32_t role, size_t group, uint32_t lane, const uint8_t *in,
+                                            uint32_t len, bool live, uint8_t *__restrict__ dst, uint32_t *__restrict__ status) {
+    const uint32_t len_min = wave_max(~len) ^ 0xFFFFFFFFu;
+    const uint32_t whole_max = wave_max(len / kPhase);
+    const uint32_t n_phases = whole_max + (wave_max(len % kPhase) ? 1u : 0u);
+    if (role == 0) {
+        __builtin_amdgcn_s_setprio(kPrioTop);
+        run_top<true>(lds, in, lane, len, len_min, n_phases, whole_max);
+    } else if (role == 1) {
+        __builtin_amdgcn_s_setprio(kPrioLow);
+        batch_low(lds, lane, len, len_min, n_phases, whole_max);
+    } else if (role == 3) {
+        // the courier of encode_kernel; it carries the pairs of the whole phases only (the deferred phase's are per lane)
+        uint32_t *courier = reinterpret_cast<uint32_t *>(lds.tree + 255u * 128u);
+        const uint32_t *table = reinterpret_cast<const uint32_t *>(g_recip.r);
+        const uint32_t lane16 = lane & 15u;
+        uint32_t carried = table[lane16];
+        for (uint32_t k = 0; k < n_phases + 2u; ++k) {
+            if (lane < 16u) courier[((k + 1u) & 1u) * 16u + lane16] = carried;
+            const uint32_t next_phase = k < whole_max ? k : 0u;
+            carried = table[next_phase * 16u + lane16];
+            lds_barrier();
+        }
+    } else {
+        __builtin_amdgcn_s_setprio(kPrioCoder);
+        CarryCoderLane coder;
+        coder.open(dst + group * (kLanes * kSlot), lane * kSlot);
+        lds_barrier();                                       // phases 0 and 1: the modelers' first
+        lds_barrier();
+        uint32_t slot = 0, k = 0;
+        auto whole_phase = [&](uint32_t k) __attribute__((always_inline)) {   // the symbols of phase k, during phase k + 2
+            const uint32_t *in_ring = &lds.sums[slot][0][lane];
+            uint32_t cums[kPhase];
+#pragma unroll
+            for (uint32_t j = 0; j < kPhase; ++j) cums[j] = in_ring[j * kLanes];
+            Recip rc[kPhase];
+            const uint4 *pairs = reinterpret_cast<const uint4 *>(lds.tree + 255u * 128u + (k & 1u) * 64u);
+#pragma unroll
+            for (uint32_t q = 0; q < 4; ++q) {
+                const uint4 v = pairs[q];
+                rc[2 * q] = {v.x, v.y}, rc[2 * q + 1] = {v.z, v.w};
+            }
+            CarryCoderLane::Ahead next = coder.ahead(cums[0], rc[0]);
+#pragma unroll
+            for (uint32_t j = 0; j < kPhase; ++j) {
+                const CarryCoderLane::Narrowed now = coder.narrow(next);
+                if (j + 1u < kPhase) next = coder.ahead(cums[j + 1u], rc[j + 1u]);
+                coder.settle(now);
+            }
+        };
+        // three loops (whole phases of every lane, whole phases of some lanes, the deferred partial phase), not one loop
+        // with several bodies: see encode_kernel's coder
+        const uint32_t whole_min = len_min / kPhase;
+        for (; k < whole_min; ++k) {
+            whole_phase(k);
+            slot = next_slot(slot);
+            lds_barrier();
+        }
+        const uint32_t whole = len / kPhase;
+        for (; k < whole_max; ++k) {
+            if (k < whole) whole_phase(k);
+            slot = next_slot(slot);
+            lds_barrier();
+        }
+        if (k < n_phases) {                                  // the lane's own symbols, with its own reciprocals
+            const uint32_t own = whole * kPhase, part = len - own;
+            const uint32_t *in_ring = &lds.sums[slot][0][lane];
+#pragma unroll 1
+            for (uint32_t j = 0; j < part; ++j) coder.step(in_ring[j * kLanes], g_recip.r[own + j]);
+            lds_barrier();
+        }
+        if (live) {
+            bool overflowed;
+            coder.finish(len, overflowed);
+            if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
+        }
+    }
+}
+
+// One packet of a batch (gpuar_hip_encode_batch / decode_batch / decode_stream_batch): buffer b owns the batch packets
+// first_packet[b] .. first_packet[b + 1] - 1 in order, so the packet's buffer is the LAST b < n_buffers with
+// first_packet[b] <= packet (an upper-bound search: a zero-length buffer shares its first_packet with the buffer behind it,
+// which is the one that owns the packet).  log2(n_buffers) dependent loads per lane, once per packet.
+struct BatchLane {
+    const uint8_t *ptr;        // the packet's bytes in its buffer: ptrs[b] + j * 8192
+    uint32_t count;            // bytes of the buffer from there on, at most 8192 (0: the packet lies past the buffer's end)
+    bool owned;                // some buffer owns the packet and that buffer's pointer is 16-byte aligned
+};
+__device__ __forceinline__ BatchLane batch_lane(const uint8_t *const *ptrs, const uint64_t *bytes, const uint64_t *first_packet,
+                                                uint32_t n_buffers, uint64_t packet) {
+    uint32_t lo = 0, n = n_buffers;                          // first u in [0, n_buffers) with first_packet[u] > packet
+    while (n > 0u) {
+        const uint32_t half = n >> 1;
+        if (first_packet[lo + half] <= packet) lo += half + 1u, n -= half + 1u;
+        else n = half;
+    }
+    BatchLane r = {nullptr, 0u, false};
+    if (lo == 0u || packet >= first_packet[lo]) return r;   // in front of the first buffer, or behind the last one's packets
+    const uint32_t b = lo - 1u;
+    const uint64_t at = (packet - first_packet[b]) * kPacket;
+    const uint8_t *p = ptrs[b];
+    const uint64_t n_bytes = bytes[b];
+    r.owned = (reinterpret_cast<uintptr_t>(p) & 15u) == 0u;
+    r.ptr = p + at;
+    r.count = n_bytes > at ? static_cast<uint32_t>(n_bytes - at < kPacket ? n_bytes - at : kPacket) : 0u;
+    return r;
+}
+
+// Batch encode, throughput mode: the roles of encode_kernel over the packets of many buffers.  A packet whose descriptor is
+// unusable (no buffer owns it, it lies past its buffer's end, the buffer is misaligned) is a dead lane: BAD_BATCH, slot untouched.
+__global__ void __launch_bounds__(4 * kLanes)
+encode_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_t *__restrict__ bytes, const uint64_t *__restrict__ first_packet,
+                    uint32_t n_buffers, uint32_t n_packets, uint8_t *__restrict__ dst, uint32_t *__restrict__ status) {
+    __shared__ EncodeLds lds;
+
+    const size_t group = xcd_contiguous_group(blockIdx.x, gridDim.x);
+    if (group * kLanes >= n_packets) return;                 // grid padding: the whole workgroup, before any barrier
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t packet = group * kLanes + lane;
+    bool live = packet < n_packets;
+    BatchLane bl = {nullptr, 0u, false};
+    if (live) {
+        bl = batch_lane(ptrs, bytes, first_packet, n_buffers, packet);
+        if (!bl.owned || bl.count == 0u) {
+            live = false;
+            if ((threadIdx.x >> 6) == 0u) atomicOr(status, GPUAR_STATUS_BAD_BATCH);
+        }
+    }
+    const uint32_t role = encode_role(lds, lane);
+    batch_roles(lds, role, group, lane, live ? bl.ptr : nullptr, live ? bl.count : 0u, live, dst, status);
 }
 
 // ---------------------------------------------------------------------------
@@ -731,6 +984,201 @@ encode_small_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__res
             if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
         }
     }
+}
+
+// ---- batch, latency mode: the roles of encode_small_kernel on the schedule of run_top<true> (phases of kSmallPhase symbols):
+//      whole phases masked by each lane's own count of them, then one phase in which every lane codes its own partial phase
+template <int kUpperDepths>
+__device__ __forceinline__ void batch_small_upper(EncodeSmallLds &lds, const uint8_t *in, uint32_t lane, uint32_t len, uint32_t n_phases,
+                                                  uint32_t whole_max) {
+    PartialModeler<7, 1, kUpperDepths, 0, false> model;
+    PhaseBytes cur, nxt = load_phase(in, 0, len);
+    model.open(lds.tree, 2u * lane_column(lane), nxt.w[0] & 0xFFu);
+    const uint32_t whole = len / kSmallPhase;
+    uint32_t k = 0;
+    for (; k < whole_max; ++k) {
+        const uint32_t base = k * kSmallPhase;
+        cur = nxt;
+        nxt = load_phase(in, base + kSmallPhase, len);
+#pragma unroll
+        for (uint32_t q = 0; q < kSmallPhase / 4; ++q) lds.bytes[k % kByteBufs][q][lane] = cur.w[q];
+        if (k < whole) {
+            uint32_t *out = &lds.sums[k % kSumSlots][0][lane];
+#pragma unroll
+            for (uint32_t j = 0; j < kSmallPhase; ++j)
+                out[j * kLanes] = model.step(byte_of(cur, j), 256u + base + j, j + 1u < kSmallPhase ? byte_of(cur, j + 1u) : nxt.w[0] & 0xFFu);
+        }
+        lds_barrier();
+    }
+    if (k < n_phases) {
+        const uint32_t own = whole * kSmallPhase;
+        cur = load_phase(in, own, len);
+#pragma unroll
+        for (uint32_t q = 0; q < kSmallPhase / 4; ++q) lds.bytes[k % kByteBufs][q][lane] = cur.w[q];
+        uint32_t *out = &lds.sums[k % kSumSlots][0][lane];
+#pragma unroll
+        for (uint32_t j = 0; j < kSmallPhase; ++j)
+            if (own + j < len) out[j * kLanes] = model.step(byte_of(cur, j), 256u + own + j, j + 1u < kSmallPhase ? byte_of(cur, j + 1u) : 0u);
+        lds_barrier();
+        ++k;
+    }
+    for (; k < n_phases + kSmallLag; ++k) lds_barrier();
+}
+
+template <typename Model>
+__device__ __forceinline__ void batch_small_follow(EncodeSmallLds &lds, uint32_t lane, uint32_t len, uint32_t n_phases, uint32_t lag,
+                                                   uint32_t whole_max) {
+    Model model;
+    model.open(lds.tree, 2u * lane_column(lane), 0u);
+    for (uint32_t b = 0; b < lag; ++b) lds_barrier();
+    const uint32_t whole = len / kSmallPhase;
+    uint32_t k = 0;
+    for (; k < whole_max; ++k) {                               // whole phases, each lane up to its own count
+        if (k < whole) {
+            const uint32_t base = k * kSmallPhase;
+            uint32_t *io = &lds.sums[k % kSumSlots][0][lane];
+            PhaseBytes w;
+#pragma unroll
+            for (uint32_t q = 0; q < kSmallPhase / 4; ++q) w.w[q] = lds.bytes[k % kByteBufs][q][lane];
+            uint32_t part[kSmallPhase];
+#pragma unroll
+            for (uint32_t j = 0; j < kSmallPhase; ++j) part[j] = io[j * kLanes];
+            model.prime(w.w[0] & 0xFFu);
+#pragma unroll
+            for (uint32_t j = 0; j < kSmallPhase; ++j)
+                io[j * kLanes] = j + 1u < kSmallPhase ? model.step(byte_of(w, j), 256u + base + j, byte_of(w, j + 1u), part[j])
+                                                      : model.step_last(byte_of(w, j), 256u + base + j, part[j]);
+        }
+        lds_barrier();
+    }
+    if (k < n_phases) {                                        // the deferred phase: the lane's own partial phase
+        const uint32_t own = whole * kSmallPhase;
+        uint32_t *io = &lds.sums[k % kSumSlots][0][lane];
+        PhaseBytes w;
+#pragma unroll
+        for (uint32_t q = 0; q < kSmallPhase / 4; ++q) w.w[q] = lds.bytes[k % kByteBufs][q][lane];
+#pragma unroll
+        for (uint32_t j = 0; j < kSmallPhase; ++j) {            // (unrolled: the byte's position must be static)
+            const uint32_t x = byte_of(w, j);
+            if (own + j < len) {
+                model.prime(x);
+                io[j * kLanes] = model.step_last(x, 256u + own + j, io[j * kLanes]);
+            }
+        }
+        lds_barrier();
+    }
+    for (uint32_t b = lag; b < kSmallLag; ++b) lds_barrier();
+}
+
+__device__ __forceinline__ void batch_small_roles(EncodeSmallLds &lds, size_t group, uint32_t lane, uint32_t wave, const uint8_t *in,
+                                                  uint32_t len, bool live, uint8_t *__restrict__ dst, uint32_t *__restrict__ status) {
+    const uint32_t whole_max = wave_max(len / kSmallPhase);
+    const uint32_t n_phases = whole_max + (wave_max(len % kSmallPhase) ? 1u : 0u);
+    const uint32_t whole = len / kSmallPhase;
+    constexpr uint32_t kWaveInterval = 2u, kWaveSink = 3u, kWaveCourier = 6u;      // (encode_small_kernel's placement)
+    if (wave == 1u) {
+        batch_small_upper<2>(lds, in, lane, len, n_phases, whole_max);
+    } else if (wave == 4u) {
+        batch_small_follow<PartialModeler<7, 3, 2, 0, false>>(lds, lane, len, n_phases, 1u, whole_max);
+    } else if (wave == 5u) {
+        batch_small_follow<PartialModeler<7, 5, 2, 0, false>>(lds, lane, len, n_phases, 2u, whole_max);
+    } else if (wave == 0u) {
+        batch_small_follow<DeepestModeler<7>>(lds, lane, len, n_phases, 3u, whole_max);
+    } else if (wave == kWaveCourier) {
+        // encode_small_kernel's courier; it carries the pairs of the whole phases only (the deferred phase's are per lane)
+        constexpr uint32_t kPhaseDwords = 2u * kSmallPhase;
+        const uint32_t *table = reinterpret_cast<const uint32_t *>(g_recip.r);
+        const uint32_t mine = lane & (kPhaseDwords - 1u);
+        uint32_t carried = table[mine];
+        for (uint32_t t = 0; t < n_phases + kSmallLag; ++t) {
+            constexpr uint32_t kAhead = kSmallLag - 2u;
+            if (lane < kPhaseDwords) lds.recips((t + kAhead) & 1u)[mine] = carried;
+            const uint32_t next_phase = t + 1u >= kAhead && t + 1u - kAhead < whole_max ? t + 1u - kAhead : 0u;
+            carried = table[next_phase * kPhaseDwords + mine];
+            lds_barrier();
+        }
+    } else if (wave == kWaveInterval) {
+        CarryIntervalLane interval;
+        interval.open();
+        for (uint32_t b = 0; b < kSmallLag - 1u; ++b) lds_barrier();
+        uint32_t k = 0;
+        for (; k < whole_max; ++k) {
+            if (k < whole) {
+                const uint32_t *sums = &lds.sums[k % kSumSlots][0][lane];
+                uint32_t *out = &lds.words[k & 1u][0][lane];
+                uint32_t cums[kSmallPhase];
+#pragma unroll
+                for (uint32_t j = 0; j < kSmallPhase; ++j) cums[j] = sums[j * kLanes];
+                Recip rc[kSmallPhase];
+                const uint4 *pairs = reinterpret_cast<const uint4 *>(lds.recips(k & 1u));
+#pragma unroll
+                for (uint32_t q = 0; q < kSmallPhase / 2; ++q) {
+                    const uint4 v = pairs[q];
+                    rc[2 * q] = {v.x, v.y}, rc[2 * q + 1] = {v.z, v.w};
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < kSmallPhase; ++j) out[j * kLanes] = interval.step(cums[j], rc[j]);
+            }
+            lds_barrier();
+        }
+        if (k < n_phases) {                                    // the lane's own partial phase, its own reciprocals
+            const uint32_t own = whole * kSmallPhase;
+            const uint32_t *sums = &lds.sums[k % kSumSlots][0][lane];
+            uint32_t *out = &lds.words[k & 1u][0][lane];
+#pragma unroll 1
+            for (uint32_t j = 0; own + j < len; ++j) out[j * kLanes] = interval.step(sums[j * kLanes], g_recip.r[own + j]);
+            lds_barrier();
+        }
+        lds_barrier();
+    } else if (wave == kWaveSink) {
+        CarrySinkLane sink;
+        sink.open(dst + group * (kLanes * kSlot), lane * kSlot);
+        for (uint32_t b = 0; b < kSmallLag; ++b) lds_barrier();
+        uint32_t k = 0;
+        for (; k < whole_max; ++k) {
+            if (k < whole) {
+                const uint32_t *in_words = &lds.words[k & 1u][0][lane];
+                uint32_t w[kSmallPhase];
+#pragma unroll
+                for (uint32_t j = 0; j < kSmallPhase; ++j) w[j] = in_words[j * kLanes];
+#pragma unroll
+                for (uint32_t j = 0; j < kSmallPhase; ++j) sink.take(w[j]);
+            }
+            lds_barrier();
+        }
+        if (k < n_phases) {
+            const uint32_t *in_words = &lds.words[k & 1u][0][lane];
+#pragma unroll 1
+            for (uint32_t j = 0; whole * kSmallPhase + j < len; ++j) sink.take(in_words[j * kLanes]);
+            lds_barrier();
+        }
+        if (live) {
+            bool overflowed;
+            sink.finish(len, overflowed);
+            if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
+        }
+    }
+}
+
+// Batch encode, latency mode (see encode_batch_kernel)
+__global__ void __launch_bounds__(kSmallWaves * kLanes)
+encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_t *__restrict__ bytes, const uint64_t *__restrict__ first_packet,
+                          uint32_t n_buffers, uint32_t n_packets, uint8_t *__restrict__ dst, uint32_t *__restrict__ status) {
+    __shared__ EncodeSmallLds lds;
+    const size_t group = blockIdx.x;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const size_t packet = group * kLanes + lane;
+    bool live = packet < n_packets;
+    BatchLane bl = {nullptr, 0u, false};
+    if (live) {
+        bl = batch_lane(ptrs, bytes, first_packet, n_buffers, packet);
+        if (!bl.owned || bl.count == 0u) {
+            live = false;
+            if (wave == 0u) atomicOr(status, GPUAR_STATUS_BAD_BATCH);
+        }
+    }
+    batch_small_roles(lds, group, lane, wave, live ? bl.ptr : nullptr, live ? bl.count : 0u, live, dst, status);
 }
 
 // ---------------------------------------------------------------------------
@@ -1170,10 +1618,13 @@ constexpr uint32_t kDecodeLdsQuads = (kDecodeRecords + kRingPieces) * kLanes;
 // `base` is the same in every lane (4-byte aligned); lane offsets are 32-bit.  `col` = this lane's 8-byte
 // column of the workgroup's LDS (72 half-records, 512 bytes apart); `ring` = this lane's dword 0 in the 4 KiB
 // stream-ring region behind the records (16 dwords per lane, 256 bytes apart; the region is 4 KiB-aligned).
+// kBatch, `room`: the bytes the lane's output may take (a batch buffer's rest); a packet whose ulen exceeds it is BAD_PACKET
+// and writes nothing.
+template <bool kBatch = false>
 __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const uint8_t *base, uint32_t pkt_off, uint32_t limit_off,
-                                            uint8_t *out, bool live, uint32_t *status) {
+                                            uint8_t *out, bool live, uint32_t *status, uint32_t room = kPacket) {
     DecoderLane<9> dec;
-    dec.open(col, base, pkt_off, limit_off, live);
+    dec.template open<kBatch>(col, base, pkt_off, limit_off, live, room);
     const uint32_t len_max = wave_max(dec.ulen);
     // Whole blocks of 64 symbols: the 64 output bytes gather in 16 registers and leave as four
     // back-to-back 16-byte stores, i.e. one whole 64-byte sector of this lane's output line
@@ -1515,6 +1966,68 @@ decode_stream_kernel(const uint8_t *__restrict__ stream, const uint64_t *__restr
     clock_sample(1u, blockIdx.x, lane, 1u);
 }
 
+// The output of a batch packet (gpuar_hip_decode_batch, decode_stream_batch): packet j of buffer b writes at outs[b] + j * 8192
+// and has the buffer's rest from there, at most 8192 bytes, as its room.  A packet no buffer owns, that lies past its
+// buffer's end, or whose buffer is misaligned is a dead lane (BAD_BATCH, nothing written), as in the batch encoders.
+__device__ __forceinline__ bool batch_output(uint8_t *const *outs, const uint64_t *out_bytes, const uint64_t *first_packet, uint32_t n_buffers,
+                                             size_t packet, bool live, uint8_t *&out, uint32_t &room, uint32_t *status) {
+    out = nullptr;
+    room = 0u;
+    if (!live) return false;
+    const BatchLane bl = batch_lane(reinterpret_cast<const uint8_t *const *>(outs), out_bytes, first_packet, n_buffers, packet);
+    if (!bl.owned || bl.count == 0u) {
+        atomicOr(status, GPUAR_STATUS_BAD_BATCH);
+        return false;
+    }
+    out = const_cast<uint8_t *>(bl.ptr);
+    room = bl.count;
+    return true;
+}
+
+// decode_slots_kernel over the slots of a batch: slot p = batch packet p, lane p % 64 of group p / 64 (the slot addressing
+// and the hand-scheduled step are decode_slots_kernel's; only the output pointer and the room check are per lane)
+__global__ void __launch_bounds__(kLanes)
+decode_slots_batch_kernel(const uint8_t *__restrict__ slots, const uint64_t *__restrict__ first_packet, uint32_t n_buffers, uint32_t n_packets,
+                          uint8_t *const *__restrict__ outs, const uint64_t *__restrict__ out_bytes, uint32_t *__restrict__ status) {
+    __shared__ __attribute__((aligned(4096))) uint4 lds[kDecodeLdsQuads];
+    const uint32_t lane = threadIdx.x;
+    const size_t packet = static_cast<size_t>(blockIdx.x) * kLanes + lane;
+    const size_t group_at = static_cast<size_t>(blockIdx.x) * (kLanes * kSlot);
+    const uint8_t *group_slots = slots + group_at;                                                // wave-uniform
+    const size_t group_left = static_cast<size_t>(n_packets) * kSlot - group_at;
+    const uint32_t slot_end = (lane + 1u) * kSlot;
+    const uint32_t limit_off = group_left < slot_end ? static_cast<uint32_t>(group_left) : slot_end;
+    uint8_t *out;
+    uint32_t room;
+    const bool live = batch_output(outs, out_bytes, first_packet, n_buffers, packet, packet < n_packets, out, room, status);
+    decode_wave<true>(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, group_slots, lane * kSlot, limit_off,
+                      out, live, status, room);
+}
+
+// decode_stream_kernel over the compacted stream of a batch: offsets in batch order, as gpuar_hip_compact of the batch's
+// slots produced them, so consecutive packets of a group are still adjacent (wave-uniform base, 32-bit lane offsets)
+__global__ void __launch_bounds__(kLanes)
+decode_stream_batch_kernel(const uint8_t *__restrict__ stream, const uint64_t *__restrict__ offsets, const uint64_t *__restrict__ first_packet,
+                           uint32_t n_buffers, uint32_t n_packets, uint8_t *const *__restrict__ outs, const uint64_t *__restrict__ out_bytes,
+                           uint32_t *__restrict__ status) {
+    __shared__ __attribute__((aligned(4096))) uint4 lds[kDecodeLdsQuads];
+    const uint32_t lane = threadIdx.x;
+    const size_t packet = static_cast<size_t>(blockIdx.x) * kLanes + lane;
+    const bool in_range = packet < n_packets;
+    const uint64_t first = offsets[static_cast<size_t>(blockIdx.x) * kLanes] & ~3ull;
+    const uint32_t first_hi = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(first >> 32))));
+    const uint32_t first_lo = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<uint32_t>(first))));
+    const uint8_t *group_stream = stream + ((static_cast<uint64_t>(first_hi) << 32) | first_lo);
+    const uint64_t left = offsets[n_packets] - first;                       // bytes from the base to the end of the stream
+    const uint32_t limit_off = left < 0x7FFFFFFFull ? static_cast<uint32_t>(left) : 0x7FFFFFFFu;
+    const uint32_t pkt_off = in_range ? static_cast<uint32_t>(offsets[packet] - first) : 0u;
+    uint8_t *out;
+    uint32_t room;
+    const bool live = batch_output(outs, out_bytes, first_packet, n_buffers, packet, in_range, out, room, status);
+    decode_wave<true>(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, group_stream, pkt_off, limit_off,
+                      out, live, status, room);
+}
+
 // ---------------------------------------------------------------------------
 // Compaction: exclusive scan of the packet lengths, then a gather of the
 // defined bytes of every slot into one back-to-back stream.
@@ -1830,6 +2343,79 @@ int gpuar_hip_decode_stream(const uint8_t *d_stream, const uint64_t *d_offsets, 
     const uint32_t blocks = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
     gpuar::decode_stream_kernel<<<blocks, gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
         d_stream, d_offsets, static_cast<uint32_t>(n_packets), d_out, status);
+    return check_launch();
+}
+
+size_t gpuar_hip_batch_packet_count(const uint64_t *bytes, size_t n_buffers, uint64_t *first_packet) {
+    if (n_buffers && !bytes) return 0;
+    size_t total = 0;
+    for (size_t b = 0; b < n_buffers; ++b) {
+        if (first_packet) first_packet[b] = total;
+        total += gpuar_hip_packet_count(bytes[b]);
+    }
+    if (first_packet) first_packet[n_buffers] = total;
+    return total;
+}
+
+// the host-side checks every batch call makes before any device work; d_packets (the slots or the stream) must be aligned to
+// packets_align bytes; *status_out: where the launch reports
+static int batch_arguments(const void *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers,
+                           size_t n_packets, const void *d_packets, uintptr_t packets_align, uint32_t *d_status, uint32_t **status_out) {
+    if (!d_ptrs || !d_bytes || !d_first_packet || !d_packets) return GPUAR_ERR_ARGUMENT;
+    if (n_packets > 0xFFFFFFFFull || n_buffers > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_first_packet) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_packets) & (packets_align - 1u)))
+        return GPUAR_ERR_ALIGNMENT;
+    *status_out = status_word(d_status);
+    return *status_out ? GPUAR_OK : GPUAR_ERR_NO_DEVICE;
+}
+
+int gpuar_hip_encode_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                           size_t n_buffers, size_t n_packets, uint8_t *d_slots, uint32_t *d_status, void *stream, int mode) {
+    if (mode != GPUAR_MODE_AUTO && mode != GPUAR_MODE_THROUGHPUT && mode != GPUAR_MODE_LATENCY) return GPUAR_ERR_ARGUMENT;
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_slots, 16u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    const uint32_t groups = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool latency = mode == GPUAR_MODE_LATENCY || (mode == GPUAR_MODE_AUTO && groups <= gpuar::kSmallGroups);   // as gpuar_hip_encode_mode
+    if (latency) {
+        gpuar::encode_small_batch_kernel<<<groups, gpuar::kSmallWaves * gpuar::kLanes, 0, s>>>(
+            d_in_ptrs, d_in_bytes, d_first_packet, static_cast<uint32_t>(n_buffers), static_cast<uint32_t>(n_packets), d_slots, status);
+        return check_launch();
+    }
+    const uint32_t blocks = (groups + 7u) & ~7u;              // see xcd_contiguous_group
+    gpuar::encode_batch_kernel<<<blocks, 4 * gpuar::kLanes, 0, s>>>(
+        d_in_ptrs, d_in_bytes, d_first_packet, static_cast<uint32_t>(n_buffers), static_cast<uint32_t>(n_packets), d_slots, status);
+    return check_launch();
+}
+
+int gpuar_hip_decode_batch(const uint8_t *d_slots, const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                           uint8_t *const *d_out_ptrs, const uint64_t *d_out_bytes, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_slots, 16u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    const uint32_t blocks = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
+    gpuar::decode_slots_batch_kernel<<<blocks, gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
+        d_slots, d_first_packet, static_cast<uint32_t>(n_buffers), static_cast<uint32_t>(n_packets), d_out_ptrs, d_out_bytes, status);
+    return check_launch();
+}
+
+int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_offsets, const uint64_t *d_first_packet,
+                                  size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                  const uint64_t *d_out_bytes, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_offsets) return GPUAR_ERR_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_stream, 4u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    const uint32_t blocks = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
+    gpuar::decode_stream_batch_kernel<<<blocks, gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
+        d_stream, d_offsets, d_first_packet, static_cast<uint32_t>(n_buffers), static_cast<uint32_t>(n_packets), d_out_ptrs, d_out_bytes, status);
     return check_launch();
 }
 

@@ -1179,8 +1179,12 @@ struct DecoderLane {
 
     // The packet starts `pkt_off` bytes after `uniform_base`; bytes up to `limit_off` (exclusive, > pkt_off
     // for a live lane) may be read; a packet whose 4-byte header does not end by then is bad and decodes nothing.
-    // A dead lane (live == false) reads the dword at uniform_base.
-    GPUAR_LANE void open(uint8_t *col, const uint8_t *uniform_base, uint32_t pkt_off, uint32_t limit_off, bool live) {
+    // A dead lane (live == false) reads the dword at uniform_base.  `room`: the bytes its output may take (a batch
+    // buffer's rest, gpuar_hip_decode_batch); a header whose ulen exceeds it is bad as well.  (kRoom: the caller has a room of
+    // its own -- a separate instantiation, so that the single-buffer kernels' code does not change with the batch kernels' calls.)
+    template <bool kRoom = false>
+    GPUAR_LANE void open(uint8_t *col, const uint8_t *uniform_base, uint32_t pkt_off, uint32_t limit_off, bool live,
+                         uint32_t room = kPacket) {
         model.col = col;
         model.reset();
         base = uniform_base;
@@ -1197,7 +1201,7 @@ struct DecoderLane {
             } else {
                 const uint32_t clen = pkt[0] | (static_cast<uint32_t>(pkt[1]) << 8);
                 ulen = pkt[2] | (static_cast<uint32_t>(pkt[3]) << 8);
-                if (ulen > kPacket || clen < kHdr) {   // the reference would run off its buffers here
+                if (ulen > kPacket || (kRoom && ulen > room) || clen < kHdr) {   // the reference would run off its buffers here
                     bad = true;
                     ulen = 0;
                 }

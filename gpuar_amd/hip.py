@@ -14,6 +14,7 @@ SLOT = 8704
 HEADER_LEN = 20
 STATUS_SLOT_OVERFLOW = 0x1
 STATUS_BAD_PACKET = 0x2
+STATUS_BAD_BATCH = 0x4
 KIND_ID = {"uniform": 0, "zipf": 1, "text": 2}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +24,7 @@ EXPORTS = [
     "gpuar_hip_packet_count", "gpuar_hip_encode", "gpuar_hip_encode_mode", "gpuar_hip_decode", "gpuar_hip_compact",
     "gpuar_hip_decode_stream", "gpuar_hip_status", "gpuar_hip_last_error", "gpuar_hip_error_string",
     "gpuar_hip_version", "gpuar_hip_abi_version", "gpuar_hip_generate", "gpuar_hip_copy", "gpuar_hip_clock_samples",
+    "gpuar_hip_batch_packet_count", "gpuar_hip_encode_batch", "gpuar_hip_decode_batch", "gpuar_hip_decode_stream_batch",
 ]
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -84,6 +86,14 @@ def load() -> C.CDLL:
     lib.gpuar_hip_copy.argtypes = [vp, vp, sz, vp]
     lib.gpuar_hip_clock_samples.restype = C.c_int
     lib.gpuar_hip_clock_samples.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_int]
+    lib.gpuar_hip_batch_packet_count.restype = sz
+    lib.gpuar_hip_batch_packet_count.argtypes = [C.POINTER(C.c_uint64), sz, C.POINTER(C.c_uint64)]
+    lib.gpuar_hip_encode_batch.restype = C.c_int
+    lib.gpuar_hip_encode_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, C.c_int]
+    lib.gpuar_hip_decode_batch.restype = C.c_int
+    lib.gpuar_hip_decode_batch.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
+    lib.gpuar_hip_decode_stream_batch.restype = C.c_int
+    lib.gpuar_hip_decode_stream_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     # a build with timing switches (tools/exp_build.sh -DGPUAR_EXP_...) decodes / encodes garbage by design: it is loaded only from
@@ -189,6 +199,63 @@ def decode_stream(d_stream, d_offsets, n_packets: int, d_out=None, stream=None, 
     _check(load().gpuar_hip_decode_stream(d_stream.data_ptr(), d_offsets.data_ptr(), n_packets, d_out.data_ptr(),
                                           _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_decode_stream")
     return d_out
+
+
+def batch_packet_count(sizes):
+    """(first_packet as a list of n + 1 ints, packet count) for buffers of `sizes` bytes (gpuar_hip_batch_packet_count)."""
+    n = len(sizes)
+    arr = (C.c_uint64 * max(n, 1))(*sizes)
+    fp = (C.c_uint64 * (n + 1))()
+    total = load().gpuar_hip_batch_packet_count(arr, n, fp)
+    return list(fp), int(total)
+
+
+def _require_u64_desc(t, name, n):
+    """A batch descriptor array: a contiguous 8-byte CUDA tensor (int64 / uint64) of at least n entries."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.element_size() == 8 and t.is_contiguous() and t.numel() >= n):
+        raise GpuarError(f"{name} must be a contiguous 64-bit CUDA tensor of at least {n} entries")
+
+
+def encode_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_slots=None, stream=None, d_status=None, mode=None,
+                 device=None):
+    """Encode a batch of buffers into n_packets slots (gpuar_hip_encode_batch).  d_ptrs / d_bytes / d_first_packet: device
+    descriptor tensors (int64: buffer addresses, byte counts, n_buffers + 1 first packets).  `mode` as for encode()."""
+    import torch
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_slots is None:
+        d_slots = torch.empty(max(n_packets, 1) * SLOT, dtype=torch.uint8, device=device or d_ptrs.device)
+    _require_cuda_u8(d_slots, "d_slots")
+    if d_slots.numel() < n_packets * SLOT:
+        raise GpuarError("d_slots too small")
+    _check(load().gpuar_hip_encode_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                         d_slots.data_ptr(), _status_ptr(d_status), _stream_handle(stream),
+                                         _mode_id(mode, "GPUAR_ENCODE_MODE")), "gpuar_hip_encode_batch")
+    return d_slots
+
+
+def decode_batch(d_slots, d_first_packet, n_buffers: int, n_packets: int, d_out_ptrs, d_out_bytes, stream=None, d_status=None):
+    """Decode n_packets slots of a batch into the buffers d_out_ptrs[b] (room d_out_bytes[b]) (gpuar_hip_decode_batch)."""
+    _require_cuda_u8(d_slots, "d_slots")
+    if d_slots.numel() < n_packets * SLOT:
+        raise GpuarError("d_slots too small")
+    for t, name, n in ((d_out_ptrs, "d_out_ptrs", n_buffers), (d_out_bytes, "d_out_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    _check(load().gpuar_hip_decode_batch(d_slots.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(),
+                                         d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_decode_batch")
+
+
+def decode_stream_batch(d_stream, d_offsets, d_first_packet, n_buffers: int, n_packets: int, d_out_ptrs, d_out_bytes, stream=None,
+                        d_status=None):
+    """Decode a batch from its compacted stream (offsets in batch order, as compact() made them) (gpuar_hip_decode_stream_batch)."""
+    _require_cuda_u8(d_stream, "d_stream")
+    for t, name, n in ((d_offsets, "d_offsets", n_packets + 1), (d_out_ptrs, "d_out_ptrs", n_buffers), (d_out_bytes, "d_out_bytes", n_buffers),
+                       (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    _check(load().gpuar_hip_decode_stream_batch(d_stream.data_ptr(), d_offsets.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                                d_out_ptrs.data_ptr(), d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream)),
+           "gpuar_hip_decode_stream_batch")
 
 
 def status() -> int:

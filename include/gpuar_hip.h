@@ -56,6 +56,11 @@ extern "C" {
                                             the reference decodes it: its third exit, a code value no symbol
                                             owns (src/gpuar_kernel.cu:873-877), cannot be reached            */
 
+#define GPUAR_STATUS_BAD_BATCH      0x4u /* batch calls only: a packet whose descriptor is unusable -- no buffer owns it, it
+                                            starts at or past its buffer's end (the buffer's d_in_bytes / d_out_bytes), or its
+                                            buffer's pointer is not 16-byte aligned.  That packet is skipped: its slot (encode)
+                                            or output (decode) is left untouched */
+
 /* ------------------------------------------------------------------------
  * Reference-named entry points (the reference's kernel object exports these;
  * declarations: /root/reference/src/gpuar.h:74,77,78).
@@ -150,6 +155,48 @@ int gpuar_hip_compact(const uint8_t *d_slots, size_t n_packets, uint8_t *d_strea
  * behind that end the same holds as for garDecompressExecutor's `size`. */
 int gpuar_hip_decode_stream(const uint8_t *d_stream, const uint64_t *d_offsets, size_t n_packets,
                             uint8_t *d_out, uint32_t *d_status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Batches: many independent buffers in one launch.
+ *
+ * A batch is n_buffers buffers; buffer b owns the batch packets first_packet[b] .. first_packet[b+1] - 1, i.e.
+ * ceil(bytes[b] / 8192) of them (a zero-byte buffer owns none), back to back in batch order, and batch packet p lives
+ * in slot p (d_slots + p * 8704).  Each buffer is coded EXACTLY as if it were encoded alone: its slots are the bytes
+ * gpuar_hip_encode gives for it.  So gpuar_hip_compact of the batch's n_packets slots is the batch's compaction, and
+ * buffer b's stream is d_stream[offsets[first_packet[b]] .. offsets[first_packet[b+1]]) -- what `gpuar c` writes for
+ * that buffer behind its 20-byte header.
+ *
+ * All d_* arrays live in device memory: d_in_ptrs / d_out_ptrs (n_buffers device pointers), d_in_bytes / d_out_bytes
+ * (n_buffers u64), d_first_packet (n_buffers + 1 u64), all three 8-byte aligned.  The host-side checks return before
+ * any device work, as the single-buffer calls do: a null pointer, n_packets or n_buffers above 0xFFFFFFFF or a bad
+ * `mode` is GPUAR_ERR_ARGUMENT; a misaligned d_slots (16 bytes), d_stream (4), d_status (4) or descriptor array (8)
+ * GPUAR_ERR_ALIGNMENT.  n_packets == 0 is GPUAR_OK with no launch.  What the device finds wrong with a packet's
+ * descriptor is GPUAR_STATUS_BAD_BATCH in d_status, per packet (see there).
+ * ---------------------------------------------------------------------- */
+
+/* Host only: first_packet[0 .. n_buffers] from bytes[0 .. n_buffers-1] (host arrays; first_packet may be NULL to count
+ * only).  Returns the batch's packet count (0 if bytes is NULL while n_buffers is not 0). */
+size_t gpuar_hip_batch_packet_count(const uint64_t *bytes, size_t n_buffers, uint64_t *first_packet);
+
+/* Encode the batch's buffers (each 16-byte aligned) into n_packets slots at d_slots.  `mode` as in gpuar_hip_encode_mode,
+ * with the same 32768-packet switch for GPUAR_MODE_AUTO.  Both kernels keep a lane on its whole-phase step for every whole
+ * phase it owns, whatever its neighbours' lengths; only each packet's own partial phase goes symbol by symbol. */
+int gpuar_hip_encode_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                           size_t n_buffers, size_t n_packets, uint8_t *d_slots, uint32_t *d_status, void *stream, int mode);
+
+/* Decode n_packets slots of a batch: packet j of buffer b writes its header's ulen bytes at d_out_ptrs[b] + j * 8192
+ * (each d_out_ptrs[b] 16-byte aligned).  A packet that starts inside its buffer (j * 8192 < d_out_bytes[b]) but has
+ * j * 8192 + ulen > d_out_bytes[b] is GPUAR_STATUS_BAD_PACKET and writes nothing, so a damaged packet never writes into
+ * its neighbour's buffer; one that starts at or past the end is GPUAR_STATUS_BAD_BATCH; everything else decodes as
+ * gpuar_hip_decode does, with the same promises about what is read. */
+int gpuar_hip_decode_batch(const uint8_t *d_slots, const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                           uint8_t *const *d_out_ptrs, const uint64_t *d_out_bytes, uint32_t *d_status, void *stream);
+
+/* The same from the compacted stream of a batch: d_offsets (n_packets + 1 entries) in batch order, as gpuar_hip_compact
+ * of the batch's slots produced them; reads as gpuar_hip_decode_stream does. */
+int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_offsets, const uint64_t *d_first_packet,
+                                  size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                  const uint64_t *d_out_bytes, uint32_t *d_status, void *stream);
 
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
