@@ -7,9 +7,15 @@ no silent copy: a tensor that is not 16-byte aligned is refused before anything 
 
     c = batch.compress([w1, w2, w3])          # contiguous CUDA tensors on one device
     outs = batch.decompress(c)                # uint8 tensors, one per input
+
+With checksum=True, compress also keeps the CRC-32 (zlib.crc32) of every packet's uncompressed bytes (Compressed.crc32);
+decompress then checks what it decoded against them and raises GpuarError naming the buffer and packet that differ, and
+Compressed.gip(b) carries them in the file's trailer (version 2), which `gpuar d` verifies.
 """
 from __future__ import annotations
 
+import bisect
+import struct
 from dataclasses import dataclass
 
 from . import hip as H
@@ -69,7 +75,7 @@ def _raise_on_status(d_status, what):
     flags = int(d_status.item())
     if flags:
         names = [n for bit, n in ((H.STATUS_SLOT_OVERFLOW, "SLOT_OVERFLOW"), (H.STATUS_BAD_PACKET, "BAD_PACKET"),
-                                  (H.STATUS_BAD_BATCH, "BAD_BATCH")) if flags & bit]
+                                  (H.STATUS_BAD_BATCH, "BAD_BATCH"), (H.STATUS_CHECKSUM, "CHECKSUM")) if flags & bit]
         raise GpuarError(f"{what}: device status {flags:#x} ({', '.join(names) or 'unknown'})")
 
 
@@ -78,11 +84,13 @@ class Compressed:
     """A compressed batch: `stream` (uint8, device, exactly the compressed bytes) holds every buffer's packets back to back
     in batch order, `offsets`
     (int64, device, n_packets + 1) the packet offsets in it, `first_packet` (host list, n_buffers + 1) which packets
-    belong to which buffer, `sizes` the buffers' byte counts."""
+    belong to which buffer, `sizes` the buffers' byte counts, `crc32` (int32, device, n_packets; None unless compressed with
+    checksum=True) the CRC-32 of every packet's uncompressed bytes."""
     stream: object
     offsets: object
     first_packet: list
     sizes: list
+    crc32: object = None
 
     @property
     def n_buffers(self) -> int:
@@ -103,14 +111,31 @@ class Compressed:
         return self.stream[off[self.first_packet[b]]:off[self.first_packet[b + 1]]]
 
     def gip(self, b: int) -> bytes:
-        """Buffer b as a whole .gip file: what `gpuar c` writes for it."""
+        """Buffer b as a whole .gip file: what `gpuar c` writes for it (with CRCs: what `gpuar c --checksum` writes)."""
         p = self.payload(b)
-        return H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
+        out = H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
+        if self.crc32 is not None:
+            off = self._offsets_host()
+            lo, hi = self.first_packet[b], self.first_packet[b + 1]
+            clens = [off[i + 1] - off[i] for i in range(lo, hi)]
+            out += trailer_v2(clens, [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()])
+        return out
 
 
-def compress(tensors, mode=None, stream=None) -> Compressed:
+def trailer_v2(clens, crcs) -> bytes:
+    """The .gip trailer version 2: "GIPX" u32 2 u64 n | u16 clen[n] | pad to 4 | u32 crc32[n] | pad to 8 |
+    u64 trailer bytes "XPIG", little-endian."""
+    n = len(clens)
+    body = b"GIPX" + struct.pack("<IQ", 2, n) + struct.pack(f"<{n}H", *clens)
+    body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
+    body += bytes(-len(body) % 8)
+    return body + struct.pack("<Q", len(body) + 12) + b"XPIG"
+
+
+def compress(tensors, mode=None, stream=None, checksum=False) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
-    compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode)."""
+    compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
+    every packet (Compressed.crc32; one more launch on the same stream)."""
     import torch
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     if device is None:
@@ -121,18 +146,22 @@ def compress(tensors, mode=None, stream=None) -> Compressed:
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         d_slots = H.encode_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
         d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
+        d_crc = H.crc32_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device) if checksum else None
         _raise_on_status(d_status, "encode_batch")
         # compact() wrote into a buffer of n_packets * 8704 bytes: keep only the compressed bytes (one copy), so that the
         # result takes what it compressed to, not ~1.06 x the input
         used = int(d_offsets[-1].item())
         d_stream = d_stream[:used].clone()
         del d_slots
-    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes)
+    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
+                      crc32=d_crc[:n_packets] if d_crc is not None else None)
 
 
-def decompress(c: Compressed, out=None, stream=None):
+def decompress(c: Compressed, out=None, stream=None, verify=True):
     """Decode every buffer of `c` in one launch.  Returns a list of uint8 tensors, or fills the caller's tensors `out` (one per
-    buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them."""
+    buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them.  When `c` carries CRCs
+    and `verify` is true, the decoded bytes are checked against them (one more launch): a mismatch raises GpuarError naming
+    the first buffer and packet that differ."""
     import torch
     device = c.stream.device
     if out is None:
@@ -144,8 +173,19 @@ def decompress(c: Compressed, out=None, stream=None):
         if have < need:
             raise GpuarError(f"out[{b}] holds {have} bytes, buffer {b} needs {need}")
     with torch.cuda.stream(stream) if stream is not None else _nothing():
-        (d_ptrs, d_room, d_fp), _keep = _upload(device, ptrs, room, c.first_packet)
+        (d_ptrs, d_room, d_fp, d_sizes), _keep = _upload(device, ptrs, room, c.first_packet, c.sizes)
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         H.decode_stream_batch(c.stream, c.offsets, d_fp, c.n_buffers, c.n_packets, d_ptrs, d_room, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
+        if c.crc32 is not None and verify and c.n_packets:
+            d_first_bad = torch.full((1,), -1, dtype=torch.int64, device=device)
+            H.verify_crc32_batch(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets, c.crc32, d_first_bad, stream=stream, d_status=d_status)
+            flags = int(d_status.item())
+            if flags & H.STATUS_CHECKSUM:
+                p = int(d_first_bad.item())
+                b = bisect.bisect_right(c.first_packet, p) - 1
+                j = p - c.first_packet[b]
+                raise GpuarError(f"checksum mismatch: buffer {b}, packet {j} (batch packet {p}), bytes {j * H.PACKET} .. "
+                                 f"{min((j + 1) * H.PACKET, c.sizes[b])} of {c.sizes[b]} differ from what was compressed")
+            _raise_on_status(d_status, "verify_crc32_batch")
     return out

@@ -22,6 +22,7 @@
 //    hand-scheduled instruction stream; the packet stream reaches it through a per-lane ring in LDS, the per-symbol
 //    reciprocal multipliers as VECTOR operands, eight at a time by loads with a wave-uniform address (no scalar load,
 //    no v_readlane in the loop);
+//  * crc32_kernel: the per-packet CRC-32 of the .gip trailer, computed or verified;
 //  * compaction (scan + gather), synthetic-stream generators, a plain copy (the measured HBM roof).
 //
 // Bit-exact with the reference: same counts, same integer arithmetic, same
@@ -36,6 +37,7 @@
 #include "gpuar_hip.h"
 
 #include "lane_codec.h"
+#include "crc32.h"
 
 // The GPUAR_EXP_* switches below take pieces OUT of the kernels to price them (profiles/r0N_*budget*.txt, *attribution*.txt): such a
 // build produces WRONG output.  It only compiles when the build says it is one (tools/exp_build.sh defines GPUAR_EXPERIMENT_BUILD for
@@ -2230,6 +2232,160 @@ copy_kernel(const uint4 *__restrict__ src, uint4 *__restrict__ dst, size_t n_qua
     if (q < n_quads) dst[q] = src[q];
 }
 
+// ---------------------------------------------------------------------------
+// Per-packet CRC-32 (crc32.h): compute (crc[p] = CRC of packet p's uncompressed bytes) and verify (recompute,
+// compare with crc[p]: GPUAR_STATUS_CHECKSUM and an atomic min of p on a mismatch), for one buffer or a batch.
+//
+// One wavefront per packet, lane l on bytes [128 l, 128 l + 128), slicing-by-4 (four table reads per word).  The four tables
+// sit in LDS 32 times over, bank-private: entry x of copy b is at dword (x * 32 + b), and lane l reads copy l % 32, so every
+// ds_read_b32 of a 32-lane half hits 32 distinct banks whatever the data (one table for all lanes conflicts 3-4 ways).  That
+// is 128 KiB: one workgroup of 16 wavefronts per CU, persistent over the packets (16 x 8 KiB of loads in flight per CU hide
+// the memory latency without a second buffer per wavefront).  A full packet's lanes shift their raw CRCs by the GF(2) matrices of CrcLaneColumns
+// (kept in registers); a packet of 1-8191 bytes takes the general path: partial words byte by byte, the shift by
+// crc_mulmod with the constant of its own distance.  Nothing is read beyond the 16-byte piece that holds a packet's last
+// byte.  Separate kernels, not fused into the codec kernels (their schedules are pinned: DESIGN.md 4.3b).
+// ---------------------------------------------------------------------------
+__device__ const CrcTables g_crc_tables = CrcTables();
+__device__ const CrcShiftTable g_crc_shift = CrcShiftTable();
+__device__ const CrcLaneColumns g_crc_columns = CrcLaneColumns();
+constexpr uint32_t kCrcWaves = 16;
+constexpr uint32_t kCrcGroups = 256;       // one workgroup per CU of an MI355X (the LDS allows no second one)
+
+struct CrcArgs {
+    const uint8_t *in;                      // one buffer: `in`, `n_bytes` ...
+    size_t n_bytes;
+    const uint8_t *const *ptrs;             // ... or a batch (ptrs != nullptr)
+    const uint64_t *bytes;
+    const uint64_t *first_packet;
+    uint32_t n_buffers;
+    uint32_t n_packets;
+    uint32_t *crc;                          // compute: written; verify: read
+    unsigned long long *first_bad;          // verify: lowest mismatching packet (may be null)
+    uint32_t *status;
+};
+
+struct CrcPacket {
+    const uint8_t *ptr;
+    uint32_t count;                         // 0: no packet (or an unusable batch descriptor)
+};
+
+__device__ __forceinline__ CrcPacket crc_locate(const CrcArgs &a, uint32_t packet) {
+    CrcPacket r = {nullptr, 0u};
+    if (!a.ptrs) {
+        const size_t at = static_cast<size_t>(packet) * kPacket;
+        r.ptr = a.in + at;
+        r.count = a.n_bytes - at < kPacket ? static_cast<uint32_t>(a.n_bytes - at) : kPacket;
+        return r;
+    }
+    const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, packet);
+    if (bl.owned && bl.count) r.ptr = bl.ptr, r.count = bl.count;
+    return r;
+}
+
+// lane's quads of a packet: quad k (bytes 128 lane + 16 k ..) where it starts before the packet's end, else zeros.  (A pointer
+// read from the batch descriptors is generic to the compiler: it is named global here, so that the loads are global_ ones.)
+typedef uint32_t CrcQuad __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void crc_load(CrcQuad (&q)[8], const CrcPacket &p, uint32_t lane) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(p.ptr + kCrcChunk * lane));
+    if (p.count == kPacket) {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) q[k] = kCrcChunk * lane + 16u * k < p.count ? src[k] : CrcQuad(0u);
+    }
+}
+
+// one slicing-by-4 step; tab: the lane's copy (dword x * 32 of table t at t * 8192)
+__device__ __forceinline__ uint32_t crc_word(const uint32_t *tab, uint32_t c, uint32_t w) {
+    c ^= w;
+    return tab[(3u * 256u + (c & 255u)) * 32u] ^ tab[(2u * 256u + ((c >> 8) & 255u)) * 32u] ^
+           tab[(256u + ((c >> 16) & 255u)) * 32u] ^ tab[(c >> 24) * 32u];
+}
+
+__device__ __forceinline__ uint32_t crc_byte(const uint32_t *tab, uint32_t c, uint32_t b) {
+    return tab[((c ^ b) & 255u) * 32u] ^ (c >> 8);
+}
+
+__device__ __forceinline__ uint32_t wave_xor(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v ^= __shfl_xor(v, off);
+    return v;
+}
+
+// the packet's CRC-32 (in every lane)
+__device__ __forceinline__ uint32_t crc_packet(const uint32_t *tab, const CrcQuad (&q)[8], uint32_t count, uint32_t lane, const uint32_t (&col)[32]) {
+    uint32_t c = lane == 0u ? 0xFFFFFFFFu : 0u;          // lane 0 carries the initial value through the whole packet
+    if (count == kPacket) {                              // wave-uniform
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            c = crc_word(tab, c, q[k].x);
+            c = crc_word(tab, c, q[k].y);
+            c = crc_word(tab, c, q[k].z);
+            c = crc_word(tab, c, q[k].w);
+        }
+        uint32_t s = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 32; ++i) s ^= col[i] & (0u - ((c >> i) & 1u));
+        c = s;
+    } else {
+        const uint32_t start = kCrcChunk * lane;
+        const uint32_t have = count > start ? (count - start < kCrcChunk ? count - start : kCrcChunk) : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t at = 16u * k + 4u * j;
+                if (at + 4u <= have) {
+                    c = crc_word(tab, c, w[j]);
+                } else {
+                    for (uint32_t b = 0; at + b < have; ++b) c = crc_byte(tab, c, (w[j] >> (8u * b)) & 255u);
+                }
+            }
+        }
+        const uint32_t behind = have ? count - start - have : 0u;     // (a lane past the end has c = 0 and reads k[0])
+        c = crc_mulmod(c, g_crc_shift.k[behind]);
+    }
+    return wave_xor(c) ^ 0xFFFFFFFFu;
+}
+
+template <bool Verify>
+__global__ void __launch_bounds__(kCrcWaves * kLanes)
+crc32_kernel(CrcArgs a) {
+    __shared__ uint32_t lds[4 * 256 * 32];
+    for (uint32_t e = threadIdx.x; e < 4u * 256u * 32u; e += kCrcWaves * kLanes) lds[e] = g_crc_tables.t[e >> 13][(e >> 5) & 255u];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t col[32];
+#pragma unroll
+    for (uint32_t i = 0; i < 32; ++i) col[i] = g_crc_columns.c[i][lane];
+    __syncthreads();
+    const uint32_t *tab = lds + (lane & 31u);
+    const uint32_t stride = gridDim.x * kCrcWaves;
+    // (n_packets <= 2^32 - 1 and stride <= 4096: the index wraps only past the last packet, which `packet < next` catches)
+    for (uint32_t packet = blockIdx.x * kCrcWaves + (threadIdx.x >> 6), next; packet < a.n_packets; packet = next) {
+        next = packet + stride;
+        const CrcPacket p = crc_locate(a, packet);
+        if (p.count == 0u) {
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+        } else {
+            CrcQuad q[8];
+            crc_load(q, p, lane);
+            const uint32_t crc = crc_packet(tab, q, p.count, lane, col);
+            if (lane == 0u) {
+                if (!Verify) {
+                    a.crc[packet] = crc;
+                } else if (crc != a.crc[packet]) {
+                    atomicOr(a.status, GPUAR_STATUS_CHECKSUM);
+                    if (a.first_bad) atomicMin(a.first_bad, static_cast<unsigned long long>(packet));
+                }
+            }
+        }
+        if (next < packet) break;
+    }
+}
+
 }  // namespace gpuar
 
 // ===========================================================================
@@ -2417,6 +2573,106 @@ int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_off
     gpuar::decode_stream_batch_kernel<<<blocks, gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
         d_stream, d_offsets, d_first_packet, static_cast<uint32_t>(n_buffers), static_cast<uint32_t>(n_packets), d_out_ptrs, d_out_bytes, status);
     return check_launch();
+}
+
+static int launch_crc32(bool verify, const gpuar::CrcArgs &a, void *stream) {
+    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kCrcWaves - 1) / gpuar::kCrcWaves;
+    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kCrcGroups ? groups : gpuar::kCrcGroups);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (verify) gpuar::crc32_kernel<true><<<blocks, gpuar::kCrcWaves * gpuar::kLanes, 0, s>>>(a);
+    else gpuar::crc32_kernel<false><<<blocks, gpuar::kCrcWaves * gpuar::kLanes, 0, s>>>(a);
+    return check_launch();
+}
+
+// the single-buffer calls' checks; n_bytes == 0 is GPUAR_OK with no launch (*launch = false)
+static int crc32_arguments(const uint8_t *d_data, size_t n_bytes, const uint32_t *d_crc, const uint64_t *d_first_bad, uint32_t *d_status,
+                           uint32_t **status_out, bool *launch) {
+    *launch = false;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!d_data || !d_crc || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_data) || (reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_first_bad) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return GPUAR_ERR_ALIGNMENT;
+    *status_out = status_word(d_status);
+    if (!*status_out) return GPUAR_ERR_NO_DEVICE;
+    *launch = true;
+    return GPUAR_OK;
+}
+
+int gpuar_hip_crc32(const uint8_t *d_in, size_t n_bytes, uint32_t *d_crc, void *stream) {
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_crc, nullptr, nullptr, &status, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::CrcArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.crc = d_crc;
+    a.status = status;
+    return launch_crc32(false, a, stream);
+}
+
+int gpuar_hip_verify_crc32(const uint8_t *d_out, size_t n_bytes, const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status,
+                           void *stream) {
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_out, n_bytes, d_crc, d_first_bad, d_status, &status, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::CrcArgs a = {};
+    a.in = d_out;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.crc = const_cast<uint32_t *>(d_crc);
+    a.first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
+    a.status = status;
+    return launch_crc32(true, a, stream);
+}
+
+// the batch calls' checks: batch_arguments' (the buffers' pointer array stands in for the packets, 8-byte aligned), then
+// d_crc (4) and d_first_bad (8)
+static int crc32_batch_arguments(const uint8_t *const *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers,
+                                 size_t n_packets, const uint32_t *d_crc, const uint64_t *d_first_bad, uint32_t *d_status,
+                                 uint32_t **status_out) {
+    if (!d_crc || !d_ptrs || !d_bytes || !d_first_packet || n_packets > 0xFFFFFFFFull || n_buffers > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_first_bad) & 7u)) return GPUAR_ERR_ALIGNMENT;
+    return batch_arguments(d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_ptrs, 8u, d_status, status_out);
+}
+
+int gpuar_hip_crc32_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                          size_t n_buffers, size_t n_packets, uint32_t *d_crc, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_crc, nullptr, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::CrcArgs a = {};
+    a.ptrs = d_in_ptrs;
+    a.bytes = d_in_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.crc = d_crc;
+    a.status = status;
+    return launch_crc32(false, a, stream);
+}
+
+int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_t *d_out_bytes,
+                                 const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                                 const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_crc, d_first_bad, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::CrcArgs a = {};
+    a.ptrs = d_out_ptrs;
+    a.bytes = d_out_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.crc = const_cast<uint32_t *>(d_crc);
+    a.first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
+    a.status = status;
+    return launch_crc32(true, a, stream);
 }
 
 int gpuar_hip_status(uint32_t *flags) {

@@ -37,6 +37,16 @@ class Compressor {
     FILE *openFile = nullptr;
     FILE *saveFile = nullptr;
     bool writeIndex = false;          // append the packet-offset index trailer (packet_index.hpp)
+    bool writeChecksum = false;       // append the trailer with per-packet CRC-32s (version 2), which decompress verifies
+
+    // the error a decompress raises for a packet whose decoded bytes do not match the CRC-32 of its trailer
+    static std::runtime_error checksumError(size_t packet, uint64_t begin, uint64_t end) {
+        return std::runtime_error("Checksum mismatch: packet " + std::to_string(packet) + " (uncompressed bytes " + std::to_string(begin) +
+                                  " .. " + std::to_string(end) + ") does not decode to what was compressed");
+    }
+    static void warnMalformedTrailer() {
+        std::fprintf(stderr, "Warning: ignoring a malformed checksum trailer: nothing was verified\n");
+    }
 
     // where the packets of an open .gip end: the header's size field when it is sane (the reference's
     // reading, src/cpu_compressor.cpp:47-56), else the end of the file
@@ -57,6 +67,7 @@ class Compressor {
     void setOpenFileName(const std::string &fileName) { openFileName = fileName; }
     void setSaveFileName(const std::string &fileName) { saveFileName = fileName; }
     void setWriteIndex(bool on) { writeIndex = on; }
+    void setWriteChecksum(bool on) { writeChecksum = on; }
     virtual CompressionInfo compress(ProgressMonitor *monitor) = 0;
     virtual CompressionInfo decompress(ProgressMonitor *monitor) = 0;
     void closeFiles();

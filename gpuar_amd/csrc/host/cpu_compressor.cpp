@@ -11,6 +11,7 @@
 #include <thread>
 #include <vector>
 
+#include "../crc32.h"
 #include "../lane_codec.h"
 #include "file_header.hpp"
 #include "packet_index.hpp"
@@ -100,8 +101,10 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
 
     const unsigned nthreads = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
     std::vector<uint8_t> in(kBatchPackets * gpuar::kPacket + 16), slots(kBatchPackets * gpuar::kSlot);
-    std::vector<uint32_t> clen(kBatchPackets);
+    std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
+    std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
+    const bool trailer = writeIndex || writeChecksum;
     try {
         for (;;) {
             io_timer.start();
@@ -114,6 +117,7 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
                 const size_t off = p * gpuar::kPacket;
                 const uint32_t len = static_cast<uint32_t>(std::min<size_t>(gpuar::kPacket, got - off));
                 clen[p] = static_cast<uint32_t>(encode_one(in.data() + off, len, slots.data() + p * gpuar::kSlot));
+                if (writeChecksum) crc[p] = gpuar::crc32_update(0, in.data() + off, len);
             });
             process_timer.stop();
             io_timer.start();
@@ -121,14 +125,15 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
                 if (std::fwrite(slots.data() + p * gpuar::kSlot, clen[p], 1, saveFile) != 1)
                     throw std::runtime_error("Write data to file failed");
                 info.compressedFileSize += clen[p];
-                if (writeIndex) all_clens.push_back(static_cast<uint16_t>(clen[p]));
+                if (trailer) all_clens.push_back(static_cast<uint16_t>(clen[p]));
+                if (writeChecksum) all_crcs.push_back(crc[p]);
             }
             io_timer.stop();
             info.processedUncompressedSize += got;
             monitor->updateProgress(&info);
         }
         io_timer.start();
-        if (writeIndex) PacketIndex::write(saveFile, all_clens);
+        if (trailer) PacketIndex::write(saveFile, all_clens, writeChecksum ? &all_crcs : nullptr);
         FileHeader header;
         header.setCompressedFileSize(info.compressedFileSize);
         header.setUncompressedFileSize(info.uncompressedFileSize);
@@ -161,7 +166,12 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         info = header.getInfo(fileSize);
         const size_t stream_end = streamEnd(info, fileSize);
         std::vector<uint16_t> index;
-        const bool indexed = PacketIndex::read(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index);
+        std::vector<uint32_t> crcs;              // per packet, from a version-2 trailer: every decoded packet is checked against them
+        const PacketIndex::Found found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
+        if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
+        const bool indexed = found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
+        const bool verify = found == PacketIndex::Found::v2;
+        size_t first_packet = 0;                 // of the window
         io_timer.stop();
 
         // The stream is taken in windows of at most kBatchPackets packets, as GPUCompressor does:
@@ -213,6 +223,17 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                 ulen[p] = static_cast<uint32_t>(decode_one(window.data() + offsets[p], window.data() + bytes,
                                                            out.data() + p * gpuar::kPacket));
             });
+            if (verify) {
+                // the CRC covers the packet's original bytes: all of them 8192 long but the file's last one, which holds 1 .. 8192
+                for (size_t p = 0; p < np; ++p) {
+                    const size_t g = first_packet + p;
+                    const uint64_t begin = static_cast<uint64_t>(g) * gpuar::kPacket;
+                    if ((g + 1 < crcs.size() ? ulen[p] != gpuar::kPacket : ulen[p] == 0) ||
+                        gpuar::crc32_update(0, out.data() + p * gpuar::kPacket, ulen[p]) != crcs[g])
+                        throw checksumError(g, begin, begin + ulen[p]);
+                }
+            }
+            first_packet += np;
             process_timer.stop();
             io_timer.start();
             for (size_t p = 0; p < np; ++p) {

@@ -422,6 +422,8 @@ struct GPUCompressor::DeviceBuffers {
     uint64_t *d_offsets = nullptr;  // cap + 1, then this lane's status word
     uint64_t *h_offsets = nullptr;  // pinned, cap + 2: the word behind the offsets receives the status word
     uint32_t *d_status = nullptr;   // this lane's own status word (device): its launches report here, nobody else's do
+    uint32_t *d_crc = nullptr;      // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
+    uint32_t *h_crc = nullptr;      // pinned, the same
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
     // the lane's pinned pieces and which of them are free
@@ -451,6 +453,13 @@ struct GPUCompressor::DeviceBuffers {
         has_slots = compressing;
     }
     bool has_slots = false;
+    // room for a chunk's CRC-32s: only for a job that writes or verifies them (compress --checksum, decompress of a file with a
+    // version-2 trailer); the current device is the lane's
+    void allocateCrc() {
+        if (d_crc) return;
+        hip_check(hipMalloc(reinterpret_cast<void **>(&d_crc), crcBytes()), "hipMalloc");
+        hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_crc), crcBytes(), hipHostMallocDefault), "hipHostMalloc");
+    }
     void release() {
         if (!cap) return;
         (void)hipSetDevice(device);
@@ -459,6 +468,10 @@ struct GPUCompressor::DeviceBuffers {
         (void)hipFree(d_stream);
         (void)hipFree(d_offsets);
         (void)hipHostFree(h_offsets);
+        if (d_crc) (void)hipFree(d_crc);
+        if (h_crc) (void)hipHostFree(h_crc);
+        d_crc = nullptr;
+        h_crc = nullptr;
         for (auto &p : pieces) {
             if (p) (void)hipHostFree(p);
             p = nullptr;
@@ -577,33 +590,49 @@ struct GPUCompressor::DeviceBuffers {
     // what THIS chunk's launches reported (GPUAR_STATUS_*): the status word travels back with the offsets, on the
     // lane's own stream -- no device-wide synchronisation, no flag shared with another lane
     // `mode`: GPUAR_MODE_* -- which encode kernel (the caller knows whether this launch has the chip to itself)
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode) {
+    // `checksum`: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
+    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
         gpuar_check(gpuar_hip_encode_mode(d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
+        if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets, d_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        if (checksum) hip_check(hipMemcpyAsync(h_crc, d_crc, n_packets * sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipStreamSynchronize(stream), "sync");
         flags = *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1);
         noteBusy();
         return static_cast<size_t>(h_offsets[n_packets]);
     }
 
-    // d_stream[0..n_stream) with h_offsets[0..n_packets] -> d_plain[0..n_packets*8192); returns this chunk's status flags
-    uint32_t decodeChunk(size_t n_packets) {
+    // d_stream[0..n_stream) with h_offsets[0..n_packets] -> d_plain[0..n_packets*8192); returns this chunk's status flags.
+    // crcs (n_packets values, or null): the decoded packets -- n_plain bytes back to back -- are verified against them;
+    // GPUAR_STATUS_CHECKSUM in the flags then, and the chunk's lowest bad packet in `first_bad`
+    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr) {
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
+        uint64_t *d_first_bad = reinterpret_cast<uint64_t *>(d_crc + crcSlots());
+        if (crcs) {
+            std::memcpy(h_crc, crcs, n_packets * sizeof(uint32_t));
+            hip_check(hipMemcpyAsync(d_crc, h_crc, n_packets * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "H2D");
+            hip_check(hipMemsetAsync(d_first_bad, 0xFF, sizeof(uint64_t), stream), "memset");
+        }
         hip_check(hipEventRecord(t0, stream), "event");
         gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
+        if (crcs) gpuar_check(gpuar_hip_verify_crc32(d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        if (crcs) hip_check(hipMemcpyAsync(h_crc + crcSlots(), d_first_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipStreamSynchronize(stream), "sync");
         noteBusy();
+        if (crcs && first_bad) std::memcpy(first_bad, h_crc + crcSlots(), sizeof(uint64_t));
         return *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1);
     }
+    size_t crcSlots() const { return (cap + 1) / 2 * 2; }                       // u32 slots in front of the u64 (8-byte aligned)
+    size_t crcBytes() const { return crcSlots() * sizeof(uint32_t) + sizeof(uint64_t); }
 };
 
 GPUCompressor::GPUCompressor() {
@@ -752,7 +781,9 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
         // length is set at the end (best effort: a file system without fallocate just grows the file as it goes)
         // (the fallocate system call, not posix_fallocate: where the file system cannot do it, glibc's stand-in would write zeros)
         (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(FileHeader::HEADER_LENGTH + total_packets * kSlot));
-        std::vector<std::vector<uint16_t>> chunk_clens(writeIndex ? n_chunks : 0);     // for the optional index trailer
+        const bool trailer = writeIndex || writeChecksum;
+        std::vector<std::vector<uint16_t>> chunk_clens(trailer ? n_chunks : 0);        // for the optional index trailer
+        std::vector<std::vector<uint32_t>> chunk_crcs(writeChecksum ? n_chunks : 0);   // and the checksums in it
         std::vector<std::atomic<size_t>> next_of_device(G);
         for (auto &n : next_of_device) n = 0;
         std::vector<std::atomic<uint64_t>> device_bytes(G), device_chunks(G);      // what each device coded (GPUAR_TRACE)
@@ -782,13 +813,14 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (!b.cap) b.allocate(b.device, chunkPackets, true);
                             if (c == 0) trace("compress: its buffers allocated");
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
+                            if (writeChecksum) b.allocateCrc();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const uint64_t at = chunk_at[c];
                             const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
                             const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
                             if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
                             uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode);     // (synchronises the lane's stream)
+                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum);     // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(at, n_plain);
                             // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
                             // (src/gpu_compressor.cpp:146-150)
@@ -798,7 +830,8 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                                 throw std::runtime_error("a packet outgrew its 8704-byte slot (input bytes " + std::to_string(at) + " .. " +
                                                          std::to_string(at + n_plain) + ")");
                             const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
-                            if (writeIndex) {
+                            if (writeChecksum) chunk_crcs[c].assign(b.h_crc, b.h_crc + n_packets);
+                            if (trailer) {
                                 chunk_clens[c].resize(n_packets);
                                 for (size_t p = 0; p < n_packets; ++p) chunk_clens[c][p] = static_cast<uint16_t>(b.h_offsets[p + 1] - b.h_offsets[p]);
                             }
@@ -827,11 +860,13 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
             info.compressedFileSize = static_cast<size_t>(writer.finish(n_chunks));
         }
         uint64_t file_end = info.compressedFileSize;
-        if (writeIndex) {
+        if (trailer) {
             std::vector<uint16_t> all;
             for (const auto &v : chunk_clens) all.insert(all.end(), v.begin(), v.end());
+            std::vector<uint32_t> crcs;
+            for (const auto &v : chunk_crcs) crcs.insert(crcs.end(), v.begin(), v.end());
             if (std::fseek(saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
-            PacketIndex::write(saveFile, all);
+            PacketIndex::write(saveFile, all, writeChecksum ? &crcs : nullptr);
             if (std::fflush(saveFile) != 0) throw std::runtime_error("Write packet index failed");
             file_end = static_cast<uint64_t>(std::ftell(saveFile));
         }
@@ -910,6 +945,7 @@ struct ChunkMap {
     struct Chunk {
         uint64_t begin = 0, end = 0;     // file offsets of the chunk's first byte / one past its last
         size_t n_packets = 0;
+        size_t first_packet = 0;         // index of its first packet in the file
     };
     std::mutex lock;
     std::condition_variable more;
@@ -1009,7 +1045,11 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         mapped.warmFirstWindow(devices[0]);
         // packet lengths from the index trailer when the file has one (packet_index.hpp)
         std::vector<uint16_t> index;
-        const bool indexed = PacketIndex::read(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index);
+        std::vector<uint32_t> crcs;      // a version-2 trailer's CRC-32s: every decoded chunk is verified against them
+        const PacketIndex::Found found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
+        if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
+        const bool indexed = found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
+        const bool verify = found == PacketIndex::Found::v2;
 
         ChunkMap map;
         std::thread scanner;
@@ -1028,6 +1068,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
             for (size_t p = 0; p < index.size();) {
                 ChunkMap::Chunk c;
                 c.begin = at;
+                c.first_packet = p;
                 const size_t want = rampPackets(map.chunks.size(), chunkPackets);
                 while (p < index.size() && c.n_packets < want) {
                     const size_t clen = index[p++];
@@ -1045,10 +1086,11 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
             scanner = std::thread([&] {
                 try {
                     uint64_t at = FileHeader::HEADER_LENGTH;
-                    size_t n_pushed = 0;
+                    size_t n_pushed = 0, n_packets = 0;
                     while (at < stream_end && !stop_scan) {
                         ChunkMap::Chunk c;
                         c.begin = at;
+                        c.first_packet = n_packets;
                         const size_t want = rampPackets(n_pushed, chunkPackets);
                         while (at < stream_end && c.n_packets < want) {
                             uint8_t h[GPUAR_PACKET_HEADER_BYTES];
@@ -1063,6 +1105,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             ++c.n_packets;
                         }
                         c.end = at;
+                        n_packets += c.n_packets;
                         map.push(c);
                         ++n_pushed;
                     }
@@ -1109,6 +1152,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             if (failure.stop || !map.get(c, chunk)) break;
                             if (!b.cap) b.allocate(b.device, chunkPackets, false);
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
+                            if (verify) b.allocateCrc();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
                             const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
@@ -1141,7 +1185,24 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             const uint64_t out_at = place.take(c, produced);
                             device_bytes[g] += produced;
                             device_chunks[g] += 1;
-                            const uint32_t flags = b.decodeChunk(chunk.n_packets);        // (synchronises the lane's stream)
+                            if (verify) {
+                                // the CRCs cover the packets' original bytes, all 8192 long but the file's last, which holds 1 .. 8192: a
+                                // packet that says otherwise does not decode to them.  (With that, the chunk's `produced` bytes hold
+                                // exactly its n_packets packets, and the verify below covers every one of them: a last packet whose
+                                // ulen had become 0 would otherwise drop out of it.)
+                                for (size_t p = 0; p < chunk.n_packets; ++p) {
+                                    const uint8_t *pkt = bytes + b.h_offsets[p];
+                                    const size_t ulen = pkt[2] | (static_cast<size_t>(pkt[3]) << 8);
+                                    const size_t g = chunk.first_packet + p;
+                                    const uint64_t begin = static_cast<uint64_t>(g) * kPacket;
+                                    if (g + 1 < crcs.size() ? ulen != kPacket : ulen == 0)
+                                        throw checksumError(g, begin, begin + std::min<size_t>(ulen, kPacket));
+                                }
+                                if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
+                            }
+                            uint64_t first_bad = 0;
+                            const uint32_t flags = verify ? b.decodeChunk(chunk.n_packets, crcs.data() + chunk.first_packet, static_cast<size_t>(produced), &first_bad)
+                                                          : b.decodeChunk(chunk.n_packets);        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307
@@ -1149,6 +1210,11 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             if (flags & GPUAR_STATUS_BAD_PACKET)
                                 throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
                                                          " and " + std::to_string(chunk.end) + ")");
+                            if (flags & GPUAR_STATUS_CHECKSUM) {
+                                const size_t g = chunk.first_packet + static_cast<size_t>(first_bad);
+                                const uint64_t begin = static_cast<uint64_t>(g) * kPacket;
+                                throw checksumError(g, begin, std::min<uint64_t>(begin + kPacket, static_cast<uint64_t>(chunk.first_packet) * kPacket + produced));
+                            }
                             if (all_full) {
                                 b.drain(writer, c, b.d_plain, static_cast<size_t>(produced), out_at, static_cast<size_t>(produced));
                             } else {             // short packets inside the chunk: one piece per packet

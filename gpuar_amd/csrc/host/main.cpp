@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -55,13 +55,14 @@ void usage() {
     std::cout << "--threads     host threads for --host (default 1, 0 = all cores)" << std::endl;
     std::cout << "--batch       largest chunk of packets a pipeline lane takes at a time (default 65536 = 512 MiB)" << std::endl;
     std::cout << "--index       (compress) append the packet-offset index trailer; decompress uses it when present" << std::endl;
+    std::cout << "--checksum    (compress) append the trailer with a CRC-32 per packet (and the index); decompress verifies it when present" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
 }  // namespace
 
 int main(int argc, char **argv) {
-    bool decompress = false, host = false, help = argc <= 1, index = false;
+    bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip";
     bool has_in = false;
     int device = -1, gpus = 0, threads = 1;
@@ -85,6 +86,8 @@ int main(int argc, char **argv) {
             host = true;
         } else if (flag_name_is(argv[i], "index", &v)) {
             index = true;
+        } else if (flag_name_is(argv[i], "checksum", &v)) {
+            checksum = true;
         } else if (flag_name_is(argv[i], "nointeractive", &v)) {
         } else if (flag_name_is(argv[i], "in", &v)) {
             if (!take(&v)) break;
@@ -141,6 +144,7 @@ int main(int argc, char **argv) {
 #endif
         }
         compressor->setWriteIndex(index);
+        compressor->setWriteChecksum(checksum);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);
         CompressionInfo info;

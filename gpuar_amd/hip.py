@@ -15,6 +15,7 @@ HEADER_LEN = 20
 STATUS_SLOT_OVERFLOW = 0x1
 STATUS_BAD_PACKET = 0x2
 STATUS_BAD_BATCH = 0x4
+STATUS_CHECKSUM = 0x8
 KIND_ID = {"uniform": 0, "zipf": 1, "text": 2}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,6 +26,7 @@ EXPORTS = [
     "gpuar_hip_decode_stream", "gpuar_hip_status", "gpuar_hip_last_error", "gpuar_hip_error_string",
     "gpuar_hip_version", "gpuar_hip_abi_version", "gpuar_hip_generate", "gpuar_hip_copy", "gpuar_hip_clock_samples",
     "gpuar_hip_batch_packet_count", "gpuar_hip_encode_batch", "gpuar_hip_decode_batch", "gpuar_hip_decode_stream_batch",
+    "gpuar_hip_crc32", "gpuar_hip_verify_crc32", "gpuar_hip_crc32_batch", "gpuar_hip_verify_crc32_batch",
 ]
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -94,6 +96,14 @@ def load() -> C.CDLL:
     lib.gpuar_hip_decode_batch.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
     lib.gpuar_hip_decode_stream_batch.restype = C.c_int
     lib.gpuar_hip_decode_stream_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    lib.gpuar_hip_crc32.restype = C.c_int
+    lib.gpuar_hip_crc32.argtypes = [vp, sz, vp, vp]
+    lib.gpuar_hip_verify_crc32.restype = C.c_int
+    lib.gpuar_hip_verify_crc32.argtypes = [vp, sz, vp, vp, vp, vp]
+    lib.gpuar_hip_crc32_batch.restype = C.c_int
+    lib.gpuar_hip_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.gpuar_hip_verify_crc32_batch.restype = C.c_int
+    lib.gpuar_hip_verify_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     # a build with timing switches (tools/exp_build.sh -DGPUAR_EXP_...) decodes / encodes garbage by design: it is loaded only from
@@ -256,6 +266,75 @@ def decode_stream_batch(d_stream, d_offsets, d_first_packet, n_buffers: int, n_p
     _check(load().gpuar_hip_decode_stream_batch(d_stream.data_ptr(), d_offsets.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
                                                 d_out_ptrs.data_ptr(), d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream)),
            "gpuar_hip_decode_stream_batch")
+
+
+def _require_crc(t, name, n):
+    """A CRC array: a contiguous 4-byte CUDA tensor (int32 / uint32) of at least n entries."""
+    import torch
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.element_size() == 4 and t.is_contiguous() and t.numel() >= n):
+        raise GpuarError(f"{name} must be a contiguous 32-bit CUDA tensor of at least {n} entries")
+
+
+def _first_bad_ptr(d_first_bad):
+    if d_first_bad is None:
+        return None
+    import torch
+    if not (isinstance(d_first_bad, torch.Tensor) and d_first_bad.is_cuda and d_first_bad.element_size() == 8 and d_first_bad.numel() >= 1):
+        raise GpuarError("d_first_bad must be a CUDA tensor of one 64-bit word")
+    return d_first_bad.data_ptr()
+
+
+def crc32(d_in, n_bytes: int = None, d_crc=None, stream=None):
+    """The CRC-32 (zlib.crc32) of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in`
+    (gpuar_hip_crc32).  Returns d_crc: int32 CUDA tensor of packet_count(n_bytes) values (the uint32 bits; & 0xFFFFFFFF)."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    npk = packet_count(n)
+    if d_crc is None:
+        d_crc = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)
+    _require_crc(d_crc, "d_crc", npk)
+    _check(load().gpuar_hip_crc32(d_in.data_ptr(), n, d_crc.data_ptr(), _stream_handle(stream)), "gpuar_hip_crc32")
+    return d_crc
+
+
+def verify_crc32(d_out, d_crc, n_bytes: int = None, d_first_bad=None, d_status=None, stream=None):
+    """Compare the packets of the first `n_bytes` (default: all) bytes of `d_out` with the CRCs `d_crc` (gpuar_hip_verify_crc32):
+    a mismatch ORs STATUS_CHECKSUM into d_status (None: the fallback word) and takes the minimum of the packet index and
+    d_first_bad (a 1-element int64 CUDA tensor the caller set to -1, i.e. UINT64_MAX), when given."""
+    _require_cuda_u8(d_out, "d_out")
+    n = d_out.numel() if n_bytes is None else n_bytes
+    if n > d_out.numel():
+        raise GpuarError("n_bytes is larger than d_out")
+    _require_crc(d_crc, "d_crc", packet_count(n))
+    _check(load().gpuar_hip_verify_crc32(d_out.data_ptr(), n, d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status),
+                                         _stream_handle(stream)), "gpuar_hip_verify_crc32")
+
+
+def crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_crc=None, stream=None, d_status=None, device=None):
+    """The CRC-32 of every packet of a batch (gpuar_hip_crc32_batch; descriptors as for encode_batch): d_crc[p] for batch packet p."""
+    import torch
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_crc is None:
+        d_crc = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)
+    _require_crc(d_crc, "d_crc", n_packets)
+    _check(load().gpuar_hip_crc32_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                        d_crc.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_crc32_batch")
+    return d_crc
+
+
+def verify_crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_crc, d_first_bad=None, stream=None, d_status=None):
+    """Verify a batch's decoded buffers against d_crc (gpuar_hip_verify_crc32_batch): d_bytes holds each buffer's ORIGINAL size;
+    d_first_bad receives the lowest failing batch packet."""
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    _require_crc(d_crc, "d_crc", n_packets)
+    _check(load().gpuar_hip_verify_crc32_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                               d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status), _stream_handle(stream)),
+           "gpuar_hip_verify_crc32_batch")
 
 
 def status() -> int:

@@ -61,6 +61,8 @@ extern "C" {
                                             buffer's pointer is not 16-byte aligned.  That packet is skipped: its slot (encode)
                                             or output (decode) is left untouched */
 
+#define GPUAR_STATUS_CHECKSUM       0x8u /* verify calls only: a packet's bytes do not match its stored CRC-32 (see there) */
+
 /* ------------------------------------------------------------------------
  * Reference-named entry points (the reference's kernel object exports these;
  * declarations: /root/reference/src/gpuar.h:74,77,78).
@@ -197,6 +199,39 @@ int gpuar_hip_decode_batch(const uint8_t *d_slots, const uint64_t *d_first_packe
 int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_offsets, const uint64_t *d_first_packet,
                                   size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
                                   const uint64_t *d_out_bytes, uint32_t *d_status, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Per-packet CRC-32: CRC-32/ISO-HDLC, the CRC of zlib.crc32 and gzip (crc32("123456789") = 0xCBF43926), of each packet's
+ * UNCOMPRESSED bytes: crc[p] covers bytes [p * 8192, min((p + 1) * 8192, n_bytes)) of its buffer.  These are the checksums of
+ * the .gip trailer version 2; computed before encoding and verified after decoding, they check the whole
+ * pipeline, the codec included.
+ *
+ * Host-side checks as in the calls above, before any device work: a null data pointer or d_crc is GPUAR_ERR_ARGUMENT; a data
+ * pointer that is not 16-byte aligned, a d_crc not 4-byte, d_first_bad or a descriptor array not 8-byte, d_status not 4-byte
+ * aligned is GPUAR_ERR_ALIGNMENT.  n_bytes == 0 / n_packets == 0 is GPUAR_OK with no launch.  Nothing is read beyond the
+ * 16-byte-aligned piece of memory that holds a buffer's last byte.
+ * ---------------------------------------------------------------------- */
+
+/* crc[p] for the gpuar_hip_packet_count(n_bytes) packets of the n_bytes at d_in. */
+int gpuar_hip_crc32(const uint8_t *d_in, size_t n_bytes, uint32_t *d_crc, void *stream);
+
+/* Recomputes the CRC of every packet of the n_bytes at d_out (decoded output: packet p at d_out + p * 8192) and compares it with
+ * d_crc[p].  On a mismatch ORs GPUAR_STATUS_CHECKSUM into d_status (NULL: the fallback word, as for the other calls) and, if
+ * d_first_bad is not NULL, takes the atomic minimum of the packet's index and *d_first_bad: the caller sets it to UINT64_MAX
+ * before the call and finds the lowest failing packet there after it. */
+int gpuar_hip_verify_crc32(const uint8_t *d_out, size_t n_bytes, const uint32_t *d_crc,
+                           uint64_t *d_first_bad, uint32_t *d_status, void *stream);
+
+/* The same for a batch (descriptors as for gpuar_hip_encode_batch): d_crc[p] for batch packet p.  A packet whose descriptor is
+ * unusable is GPUAR_STATUS_BAD_BATCH in d_status, by the encoder's rules, and its d_crc[p] is left untouched. */
+int gpuar_hip_crc32_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                          size_t n_buffers, size_t n_packets, uint32_t *d_crc, uint32_t *d_status, void *stream);
+
+/* Verify for a batch: d_out_bytes holds each buffer's ORIGINAL size (what was compressed), not its room; d_first_bad receives the
+ * lowest failing BATCH packet index.  Unusable descriptors: GPUAR_STATUS_BAD_BATCH, that packet is not compared. */
+int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_t *d_out_bytes,
+                                 const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                                 const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status, void *stream);
 
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
