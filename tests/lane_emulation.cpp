@@ -128,6 +128,28 @@ static int encode_slots_device_rule(const uint8_t *in, size_t n_bytes, uint8_t *
     return any_overflow;
 }
 
+// What a decoder wavefront's lane does (SubtreeModel + DecoderLane).  kRoom: the batch decoders' instantiation, in which
+// packet p may write at most rooms[p] bytes.
+template <bool kRoom>
+static int decode_stream_with(const uint8_t *stream, const uint64_t *pkt_offsets, const uint32_t *rooms, size_t np, uint8_t *out)
+{
+    int bad = 0;
+    std::vector<uint64_t> records(kDecodeRecords * 2);       // 16 bytes each, 8-byte aligned storage
+    const uint8_t *limit = stream + pkt_offsets[np];
+    for (size_t p = 0; p < np; ++p) {
+        DecoderLane<3> dec;
+        uint8_t *o = out + p * kPacket;
+        const uint64_t readable = static_cast<uint64_t>(limit - (stream + pkt_offsets[p]));
+        dec.template open<kRoom>(reinterpret_cast<uint8_t *>(records.data()), stream + pkt_offsets[p], 0,
+                                 readable < 0x7FFFFFFFu ? static_cast<uint32_t>(readable) : 0x7FFFFFFFu, true,
+                                 kRoom ? rooms[p] : kPacket);
+        for (uint32_t i = 0; i < dec.ulen; ++i) dec.step(i, kDecode.c[i], o);
+        dec.finish(o);
+        bad += dec.bad ? 1 : 0;
+    }
+    return bad;
+}
+
 extern "C" {
 // encode_kernel's coder with the DEVICE's store rule (DeviceRuleCoder above) instead of take_top() + leave()
 int emu_encode_slots_device_rule(const uint8_t *in, size_t n_bytes, uint8_t *slots) { return encode_slots_device_rule(in, n_bytes, slots); }
@@ -237,25 +259,18 @@ int emu_encode_slots_split(const uint8_t *in, size_t n_bytes, uint8_t *slots)
     return any_overflow;
 }
 
-// What a decoder wavefront's lane does (SubtreeModel + DecoderLane).
 // pkt_offsets: np+1 byte offsets into `stream`; out: np * 8192 bytes.
 // Returns the number of packets flagged bad.
 int emu_decode_stream(const uint8_t *stream, const uint64_t *pkt_offsets, size_t np, uint8_t *out)
 {
-    int bad = 0;
-    std::vector<uint64_t> records(kDecodeRecords * 2);       // 16 bytes each, 8-byte aligned storage
-    const uint8_t *limit = stream + pkt_offsets[np];
-    for (size_t p = 0; p < np; ++p) {
-        DecoderLane<3> dec;
-        uint8_t *o = out + p * kPacket;
-        const uint64_t readable = static_cast<uint64_t>(limit - (stream + pkt_offsets[p]));
-        dec.open(reinterpret_cast<uint8_t *>(records.data()), stream + pkt_offsets[p], 0,
-                 readable < 0x7FFFFFFFu ? static_cast<uint32_t>(readable) : 0x7FFFFFFFu, true);
-        for (uint32_t i = 0; i < dec.ulen; ++i) dec.step(i, kDecode.c[i], o);
-        dec.finish(o);
-        bad += dec.bad ? 1 : 0;
-    }
-    return bad;
+    return decode_stream_with<false>(stream, pkt_offsets, nullptr, np, out);
+}
+
+// The same through DecoderLane::open<true> (decode_wave<true>: decode_slots_batch_kernel, decode_stream_batch_kernel):
+// packet p is refused, and writes nothing, when its ulen exceeds rooms[p] as well.  Returns the number refused.
+int emu_decode_stream_room(const uint8_t *stream, const uint64_t *pkt_offsets, const uint32_t *rooms, size_t np, uint8_t *out)
+{
+    return decode_stream_with<true>(stream, pkt_offsets, rooms, np, out);
 }
 
 // renorm_count(a, wd) against the reference's renormalisation loop (writeEncodedBits :321-367 / readEncodedBits :787-836:

@@ -11,17 +11,25 @@ Coverage of the hand-scheduled step: the whole sweep holds 30.9 million damaged 
 64-symbol blocks (the asm step, its stream ring and its handoff to the plain step); part 1 sends about 405 million
 damaged symbols through that step (five layouts, each through the slot decoder and four stream forms).
 
-1. decode (slots), decode_stream (slot-spaced and back-to-back, pointer skew 0 and 4), garDecompressExecutor.
+1. decode (slots), decode_stream (slot-spaced and back-to-back, pointer skew 0 and 4), garDecompressExecutor; and the
+   batch decoders (decode_batch, decode_stream_batch) on the same forms, each packet its own output buffer (in permuted
+   rows of a canary arena, zero-byte buffers among them) under three room rules: a room of 8192 (every row as the
+   single-buffer decoders give it), the clean length n the packet was made from (what batch.decompress passes: a
+   header whose ulen is above it is BAD_PACKET and its row keeps its canary), and ulen or ulen - 1 (exactly the second
+   kind refused).  A one-packet buffer of 0 bytes is BAD_BATCH, not BAD_PACKET.
 2. The 200 bit-flipped packets of tests/golden/seeded_vectors.json through both decoders.
 3. Invalid headers (ulen > 8192, clen < 4): the row keeps its canary, BAD_PACKET lands in that launch's word only,
-   every other row is right -- at every lane position, in a ragged last wavefront, in a wavefront of nothing else.
+   every other row is right -- at every lane position, in a ragged last wavefront, in a wavefront of nothing else;
+   through both single-buffer and both batch decoders.
 4. What lies behind the end of the caller's buffer (garDecompressExecutor's `size`, decode_stream's offsets[n]), as
    include/gpuar_hip.h states it.  A packet shorter than 64 bytes is decoded by DecoderLane alone, which sees zeros
    there: cut by the end, it decodes as the reference decodes its bytes and zeros, whatever lies behind the end.  The
    stream ring of the hand-scheduled step repeats the 16-byte piece that holds the last byte instead (masking it was
    measured at +1.5 % decode time, gpuar_kernels.hip), so for an 8192-byte packet only this holds: bytes more than 16
    behind the end never change any row, the cut packet stays in its row and nothing is flagged.  A packet whose header
-   is cut is flagged and writes nothing.
+   is cut is flagged and writes nothing.  decode_stream_batch (64 one-packet buffers of room 8192) is held to the same.
+
+The batch descriptors come from tests/batch_sweep.py.
 """
 import hashlib
 import json
@@ -31,6 +39,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import batch_sweep as BS
 import damage_sweep as DS
 import length_sweep as LS
 from gpuar_amd import synth
@@ -95,25 +104,27 @@ def _status():
     return torch.zeros(1, dtype=torch.int32, device="cuda")
 
 
-def _first_wrong_row(got, want, order, dmg, what):
-    """pytest.fail with the packet, lane, damage class, ulen and first differing byte of the first wrong row."""
+def _first_wrong_row(got, want, order, dmg, what, rooms=None):
+    """pytest.fail with the packet, lane, damage class, ulen (and room) and first differing byte of the first wrong row."""
     bad = (got != want).any(dim=1).nonzero().flatten()
     lane = int(bad[0])
     i = int(order[lane])
     ulen = int(dmg["ulens"][i]) if i >= 0 else 0
     cls = dmg["classes"][i] if i >= 0 else "invalid header"
+    room = "" if rooms is None else f", room {int(rooms[lane])}"
     g, w = got[lane].cpu().numpy(), want[lane].cpu().numpy()
     at = int(np.flatnonzero(g != w)[0])
     where = "inside ulen" if at < ulen else "after ulen (canary overwritten)"
     pytest.fail(f"{what}: {bad.numel()} rows wrong; first: packet {i + 1 if i >= 0 else '-'} ({cls}) at row {lane} "
-                f"(wavefront {lane // 64}, lane {lane % 64}), ulen {ulen}, byte {at} {where}: got {g[at]:#04x}, want {w[at]:#04x}")
+                f"(wavefront {lane // 64}, lane {lane % 64}), ulen {ulen}{room}, byte {at} {where}: got {g[at]:#04x}, want {w[at]:#04x}")
 
 
-def _check_rows(d_out, want, order, dmg, what):
+def _check_rows(d_out, want, order, dmg, what, rooms=None):
+    """d_out: the output arena (rows in lane order from its start), or the rows themselves as an (n, 8192) tensor."""
     n = order.size
-    got = d_out[:n * PACKET].view(n, PACKET)
+    got = d_out if d_out.dim() == 2 else d_out[:n * PACKET].view(n, PACKET)
     if not torch.equal(got, want):
-        _first_wrong_row(got, want, order, dmg, what)
+        _first_wrong_row(got, want, order, dmg, what, rooms)
 
 
 def _device_stream(stream: np.ndarray, skew: int):
@@ -124,6 +135,35 @@ def _device_stream(stream: np.ndarray, skew: int):
     d = raw[base:base + stream.size]
     assert d.data_ptr() % 16 == skew
     return raw, d
+
+
+PAD = 4096                                              # canary bytes in front of and behind every batch output arena
+
+
+def _launch_batch(H, via, d_src, d_offs, n, rooms, seed):
+    """Launch decode_batch (via "slots") or decode_stream_batch over n packets, packet i into its own output buffer of
+    rooms[i] bytes (tests/batch_sweep.py: seeded permuted rows of a canary arena, zero-byte buffers among them); no wait.
+    Returns what _batch_rows needs."""
+    bufs, rows = BS.one_packet_outputs(rooms, seed)
+    d_out = torch.full((n * PACKET + 2 * PAD,), CANARY, dtype=torch.uint8, device="cuda")
+    ptrs, nbytes, first = BS.columns(bufs, d_out.data_ptr() + PAD)
+    d = torch.tensor(ptrs + nbytes + first, dtype=torch.int64).cuda()
+    k = len(bufs)
+    word = _status()
+    if via == "slots":
+        H.decode_batch(d_src, d[2 * k:], k, n, d[:k], d[k:2 * k], d_status=word)
+    else:
+        H.decode_stream_batch(d_src, d_offs, d[2 * k:], k, n, d[:k], d[k:2 * k], d_status=word)
+    return d_out, rows, word, (d, d_src, d_offs)
+
+
+def _batch_rows(launched, n, what):
+    """After the launch: (its output rows in batch order, its status word); asserts nothing was written into the pads."""
+    d_out, rows, word, _ = launched
+    torch.cuda.synchronize()
+    assert bool(d_out[:PAD].eq(CANARY).all()) and bool(d_out[PAD + n * PACKET:].eq(CANARY).all()), \
+        f"{what}: written in front of the first or behind the last output row"
+    return d_out[PAD:PAD + n * PACKET].view(n, PACKET).index_select(0, torch.from_numpy(rows).cuda()), int(word.item())
 
 
 def _decode_stream(H, stream, offs, n, skew):
@@ -168,8 +208,7 @@ def _stream_rows(oracle, dmg, layout, spacing):
         stream, offs = DS.stream_form([dmg["pkts"][i] for i in order], spacing)
         views = [DS.reference_view(stream, int(offs[p]), int(offs[-1])) for p in range(order.size)]
         rows = _ref_rows(oracle, views, dmg["ulens"][order])
-        _STREAM_ROWS.clear()                            # (one layout's rows at a time: 64 MiB for the biggest)
-        _STREAM_ROWS[key] = (stream, offs, torch.from_numpy(rows).cuda())
+        _STREAM_ROWS[key] = (stream, offs, torch.from_numpy(rows).cuda())     # (kept for the batch tests: 340 MiB in all)
     return _STREAM_ROWS[key]
 
 
@@ -201,6 +240,88 @@ def test_garDecompressExecutor_on_damaged_packets(H, dmg):
     assert lib.gpuar_hip_last_error() == 0
     assert H.status() == 0
     _check_rows(d_out, dmg["rows"].index_select(0, torch.from_numpy(order).cuda()), order, dmg, "garDecompressExecutor")
+
+
+ROOM_RULES = ("8192", "clean_length", "ulen_or_ulen_minus_1")
+
+
+def _rooms(rule, order, dmg):
+    """Each lane's room under `rule`, and which lanes the batch decoders must refuse (ulen > room).  Every room is >= 1:
+    a one-packet buffer of 0 bytes is BAD_BATCH (test_batch_zero_room_is_bad_batch)."""
+    ulens = dmg["ulens"][order]
+    if rule == "8192":
+        rooms = np.full(order.size, PACKET, dtype=np.int64)
+    elif rule == "clean_length":                        # the packet was made from packet(n), n = order + 1
+        rooms = order + 1
+    else:                                               # a seeded half of the lanes with ulen >= 2 one byte short
+        short = (np.random.default_rng([DS.SEED, order.size]).random(order.size) < 0.5) & (ulens >= 2)
+        rooms = np.where(short, ulens - 1, np.maximum(ulens, 1))
+    return rooms, ulens > rooms
+
+
+def _check_batch_rules(H, via, d_src, d_offs, order, want, dmg, rule, what):
+    """One batch launch under room rule `rule`: the refused rows keep their whole canary, every other row is `want`'s, the
+    status word is exactly BAD_PACKET if any lane is refused and 0 otherwise."""
+    n = order.size
+    rooms, refused = _rooms(rule, order, dmg)
+    assert rule == "8192" or refused.any(), f"{what}: rule {rule} refuses nothing here"
+    what = f"{what}, rooms {rule}"
+    got, word = _batch_rows(_launch_batch(H, via, d_src, d_offs, n, rooms, n + len(rule)), n, what)
+    want_word = H.STATUS_BAD_PACKET if refused.any() else 0
+    assert word == want_word, f"{what}: status {word:#x}, want {want_word:#x} ({int(refused.sum())} lanes refused)"
+    want = want.clone()
+    if refused.any():
+        want[torch.from_numpy(np.flatnonzero(refused)).cuda()] = CANARY
+    _check_rows(got, want, order, dmg, what, rooms)
+
+
+@pytest.mark.parametrize("rule", ROOM_RULES)
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_decode_slots_batch_on_damaged_packets(H, dmg, layout, rule):
+    """decode_slots_batch_kernel on the slot form, one output buffer per packet, under each room rule (_rooms); with rooms
+    of 8192 exactly what test_decode_slots_on_damaged_packets demands of the single-buffer decoder."""
+    order = LAYOUTS[layout]
+    d_slots = torch.from_numpy(DS.slot_form([dmg["pkts"][i] for i in order])).cuda()
+    want = dmg["rows"].index_select(0, torch.from_numpy(order).cuda())
+    _check_batch_rules(H, "slots", d_slots, None, order, want, dmg, rule, f"decode_batch {layout}")
+
+
+@pytest.mark.parametrize("rule", ROOM_RULES)
+@pytest.mark.parametrize("skew", [0, 4])
+@pytest.mark.parametrize("spacing", ["slot_spaced", "back_to_back"])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_decode_stream_batch_on_damaged_packets(H, oracle, dmg, layout, spacing, skew, rule):
+    """decode_stream_batch_kernel on the stream forms of test_decode_stream_on_damaged_packets (the same rows, the reference
+    shown the same following bytes), one output buffer per packet, under each room rule."""
+    order = LAYOUTS[layout]
+    stream, offs, want = _stream_rows(oracle, dmg, layout, SLOT if spacing == "slot_spaced" else None)
+    raw, d_stream = _device_stream(stream, skew)
+    _check_batch_rules(H, "stream", d_stream, torch.from_numpy(offs).cuda(), order, want, dmg, rule,
+                       f"decode_stream_batch {layout}, {spacing}, skew {skew}")
+
+
+@pytest.mark.parametrize("via", ["slots", "stream"])
+def test_batch_zero_room_is_bad_batch(H, dmg, via):
+    """A one-packet buffer of 0 bytes (at lanes 0, 37 and 63 of one wavefront and lane 63 of the next) starts at its
+    buffer's end: BAD_BATCH exactly, not BAD_PACKET, and its row keeps its canary; the rest (room 8192) is right."""
+    order = LAYOUTS["permuted"][:128]
+    n = order.size
+    rooms = np.full(n, PACKET, dtype=np.int64)
+    zero = [0, 37, 63, 127]
+    rooms[zero] = 0
+    pkts = [dmg["pkts"][i] for i in order]
+    if via == "slots":
+        d_src, d_offs = torch.from_numpy(DS.slot_form(pkts)).cuda(), None
+    else:
+        stream, offs = DS.stream_form(pkts, DS.STREAM_TAIL)
+        raw, d_src = _device_stream(stream, 4)
+        d_offs = torch.from_numpy(offs).cuda()
+    what = f"decode_{via}_batch, zero-byte buffers at {zero}"
+    got, word = _batch_rows(_launch_batch(H, via, d_src, d_offs, n, rooms, 7), n, what)
+    assert word == H.STATUS_BAD_BATCH, f"{what}: status {word:#x}"
+    want = dmg["rows"].index_select(0, torch.from_numpy(order).cuda()).clone()
+    want[zero] = CANARY
+    _check_rows(got, want, order, dmg, what, rooms)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -250,27 +371,40 @@ def invalid(dmg):
 def _launch_with_invalid(H, dmg, order, bad_at, decoder):
     """One launch over the sweep packets `order`, with the invalid packets `bad_at` = {row: (packet, what)} in place of
     theirs; and a second launch in flight behind it over the same packets without them.  Slot form, or a stream whose
-    packets lie STREAM_TAIL apart (so every valid row's expectation is the slot form's).  Returns nothing: asserts."""
+    packets lie STREAM_TAIL apart (so every valid row's expectation is the slot form's); through decode / decode_stream,
+    or (decoder "slots_batch" / "stream_batch") their batch kernels, each packet its own output buffer of 8192 bytes.
+    Returns nothing: asserts."""
     n = order.size
     pkts = [bad_at[r][0] if r in bad_at else dmg["pkts"][i] for r, i in enumerate(order)]
     clean = [dmg["pkts"][i] for i in order]
+    via = decoder.split("_")[0]
     results = []
     for ps in (pkts, clean):
-        d_out = torch.full((n * PACKET,), CANARY, dtype=torch.uint8, device="cuda")
-        word = _status()
-        if decoder == "slots":
-            d_in = torch.from_numpy(DS.slot_form(ps)).cuda()
-            H.decode(d_in, n, d_out, d_status=word)
+        if via == "slots":
+            d_in, d_offs = torch.from_numpy(DS.slot_form(ps)).cuda(), None
         else:
             stream, offs = DS.stream_form(ps, DS.STREAM_TAIL)
             raw, d_in = _device_stream(stream, 4)
-            H.decode_stream(d_in, torch.from_numpy(offs).cuda(), n, d_out, d_status=word)
-        results.append((d_out, word, d_in))
-    torch.cuda.synchronize()
-    (d_out, word, _), (d_clean, word_clean, _) = results
+            d_offs = torch.from_numpy(offs).cuda()
+        if decoder.endswith("_batch"):
+            results.append(_launch_batch(H, via, d_in, d_offs, n, np.full(n, PACKET), n))
+            continue
+        d_out = torch.full((n * PACKET,), CANARY, dtype=torch.uint8, device="cuda")
+        word = _status()
+        if via == "slots":
+            H.decode(d_in, n, d_out, d_status=word)
+        else:
+            H.decode_stream(d_in, d_offs, n, d_out, d_status=word)
+        results.append((d_out, word, (d_in, d_offs)))
     where = f"{decoder}, invalid rows {sorted((r, bad_at[r][1]) for r in bad_at)[:4]}"
-    assert int(word.item()) == H.STATUS_BAD_PACKET, f"{where}: status {int(word.item()):#x}"
-    assert int(word_clean.item()) == 0, f"{where}: the flag reached the launch behind it"
+    if decoder.endswith("_batch"):
+        (d_out, word), (d_clean, word_clean) = (_batch_rows(r, n, where) for r in results)
+    else:
+        torch.cuda.synchronize()
+        (d_out, word, _), (d_clean, word_clean, _) = results
+        word, word_clean = int(word.item()), int(word_clean.item())
+    assert word == H.STATUS_BAD_PACKET, f"{where}: status {word:#x}"
+    assert word_clean == 0, f"{where}: the flag reached the launch behind it"
     want = dmg["rows"].index_select(0, torch.from_numpy(order).cuda()).clone()
     rows = torch.tensor(sorted(bad_at), dtype=torch.int64, device="cuda")
     want[rows] = CANARY                                  # an invalid packet's whole 8192-byte row keeps its canary
@@ -280,7 +414,7 @@ def _launch_with_invalid(H, dmg, order, bad_at, decoder):
     _check_rows(d_clean, dmg["rows"].index_select(0, torch.from_numpy(order).cuda()), order, dmg, where + " (clean launch)")
 
 
-@pytest.mark.parametrize("decoder", ["slots", "stream"])
+@pytest.mark.parametrize("decoder", ["slots", "stream", "slots_batch", "stream_batch"])
 def test_invalid_header_at_every_lane(H, dmg, invalid, decoder):
     """One wavefront per lane position 0 ... 63, the invalid header there (the six kinds in turn), damaged packets
     with valid headers in the other 63 lanes."""
@@ -290,7 +424,7 @@ def test_invalid_header_at_every_lane(H, dmg, invalid, decoder):
         _launch_with_invalid(H, dmg, order, {lane: invalid[lane % len(invalid)]}, decoder)
 
 
-@pytest.mark.parametrize("decoder", ["slots", "stream"])
+@pytest.mark.parametrize("decoder", ["slots", "stream", "slots_batch", "stream_batch"])
 def test_invalid_headers_in_ragged_and_all_invalid_wavefronts(H, dmg, invalid, decoder):
     """Invalid headers at lane 0 of a last wavefront with one live lane, at lane 62 of one with 63, and a wavefront
     in which every lane is invalid, between two wavefronts of valid packets."""
@@ -302,13 +436,22 @@ def test_invalid_headers_in_ragged_and_all_invalid_wavefronts(H, dmg, invalid, d
 
 
 def test_zero_ulen_writes_nothing_and_is_not_flagged(H, oracle):
-    """ulen = 0 behind a valid clen: no byte of the row is written and nothing is flagged, at lanes 0, 31 and 63."""
+    """ulen = 0 behind a valid clen: no byte of the row is written and nothing is flagged, at lanes 0, 31 and 63; through
+    both decoders and both batch decoders (each packet its own output buffer of 8192 bytes)."""
     pkt = oracle.encode_stream(LS.packet(5000))
     pkt[2:4] = 0
     clean = [oracle.encode_stream(LS.packet(m)) for m in range(1, 65)]
     ps = [pkt if r in (0, 31, 63) else clean[r] for r in range(64)]
-    for decoder in ("slots", "stream"):
-        if decoder == "slots":
+    for decoder in ("slots", "stream", "slots_batch", "stream_batch"):
+        if decoder == "slots_batch":
+            launched = _launch_batch(H, "slots", torch.from_numpy(DS.slot_form(ps)).cuda(), None, 64, np.full(64, PACKET), 64)
+            d_out, word = _batch_rows(launched, 64, decoder)
+        elif decoder == "stream_batch":
+            stream, offs = DS.stream_form(ps)
+            raw, d_stream = _device_stream(stream, 0)
+            launched = _launch_batch(H, "stream", d_stream, torch.from_numpy(offs).cuda(), 64, np.full(64, PACKET), 64)
+            d_out, word = _batch_rows(launched, 64, decoder)
+        elif decoder == "slots":
             d_out = torch.full((64 * PACKET,), CANARY, dtype=torch.uint8, device="cuda")
             word = _status()
             H.decode(torch.from_numpy(DS.slot_form(ps)).cuda(), 64, d_out, d_status=word)
@@ -318,7 +461,7 @@ def test_zero_ulen_writes_nothing_and_is_not_flagged(H, oracle):
             stream, offs = DS.stream_form(ps)
             d_out, word = _decode_stream(H, stream, offs, 64, 0)
         assert word == 0, decoder
-        rows = d_out.view(64, PACKET).cpu().numpy()
+        rows = d_out.reshape(64, PACKET).cpu().numpy()
         for r in range(64):
             if r in (0, 31, 63):
                 assert (rows[r] == CANARY).all(), (decoder, r)
@@ -421,7 +564,8 @@ def test_garDecompressExecutor_behind_size(H, oracle, tail_packets, last, cut):
 @pytest.mark.parametrize("last,cut", CASES)
 def test_decode_stream_behind_the_stream_end(H, oracle, tail_packets, last, cut, skew):
     """A back-to-back stream of 64 packets whose offsets[n] lies `cut` bytes into the last one: the same runs and
-    expectations as above, with this launch's own status word, at pointer skew 0 and 4."""
+    expectations as above, with this launch's own status word, at pointer skew 0 and 4; through decode_stream and through
+    decode_stream_batch (64 one-packet buffers of 8192 bytes in the rows of the same canary arena)."""
     data, encs, lasts = tail_packets
     enc = lasts[last][1]
     stream = np.concatenate(encs + [enc])
@@ -431,16 +575,23 @@ def test_decode_stream_behind_the_stream_end(H, oracle, tail_packets, last, cut,
     offs[64] = end
     want_row, want_word = _cut_expectation(oracle, enc, cut)
     exact = last == "short" or cut < 4
-    rows = []
-    for near, far in RUNS:
-        buf = np.concatenate([stream[:end], _behind(near, far, 256)])
-        raw, d_buf = _device_stream(buf, skew)
-        d_out = torch.full((64 * PACKET + 4096,), CANARY, dtype=torch.uint8, device="cuda")
-        word = _status()
-        H.decode_stream(d_buf, torch.from_numpy(offs).cuda(), 64, d_out, d_status=word)
-        torch.cuda.synchronize()
-        assert int(word.item()) == want_word, (last, cut, near, far)
-        out = d_out.cpu().numpy()
-        _check_cut_run(out, data, want_row, f"{last} packet cut at {cut}, {near:#04x}/{far:#04x} behind offsets[n]", exact)
-        rows.append(out[63 * PACKET:64 * PACKET])
-    _same_far_behind(rows, f"{last} packet cut at {cut}")
+    for decoder in ("decode_stream", "decode_stream_batch"):
+        rows = []
+        for near, far in RUNS:
+            buf = np.concatenate([stream[:end], _behind(near, far, 256)])
+            raw, d_buf = _device_stream(buf, skew)
+            d_offs = torch.from_numpy(offs).cuda()
+            d_out = torch.full((64 * PACKET + 4096,), CANARY, dtype=torch.uint8, device="cuda")
+            word = _status()
+            if decoder == "decode_stream":
+                H.decode_stream(d_buf, d_offs, 64, d_out, d_status=word)
+            else:
+                d = torch.tensor([d_out.data_ptr() + r * PACKET for r in range(64)] + [PACKET] * 64 + list(range(65)),
+                                 dtype=torch.int64).cuda()
+                H.decode_stream_batch(d_buf, d_offs, d[128:], 64, 64, d[:64], d[64:128], d_status=word)
+            torch.cuda.synchronize()
+            assert int(word.item()) == want_word, (decoder, last, cut, near, far)
+            out = d_out.cpu().numpy()
+            _check_cut_run(out, data, want_row, f"{decoder}: {last} packet cut at {cut}, {near:#04x}/{far:#04x} behind offsets[n]", exact)
+            rows.append(out[63 * PACKET:64 * PACKET])
+        _same_far_behind(rows, f"{decoder}: {last} packet cut at {cut}")

@@ -5,13 +5,21 @@
 2. Every tail residue through both encode kernels (throughput and latency mode).
 3. The auto-mode switch between the two encode kernels (32768 / 32769 packets).
 4. Compaction (scans + gather) against a plain concatenation of synthetic slots.
+5. Every packet length through both batch encoders (throughput and latency mode): each lane its own one-packet buffer,
+   the buffers scattered over a canary arena in permuted address order with zero-byte buffers among them, the bytes
+   between buffers 0x00 and then 0xFF; the slots equal the reference's, and decode back through both batch decoders.
+6. Every packet length through both batch decoders (slots; stream at pointer skew 0 and 4): one output buffer per packet
+   with a room of exactly its ulen, in permuted rows, and buffers of 1-5 packets whose packets in front of the last one
+   have a room of 8192 behind a shorter ulen.
 
-The packets of parts 1 and 2 come from tests/length_sweep.py (six source models in turn); its host half is
-tests/test_lane_emulation.py::test_lane_decoder_at_every_packet_length.  Fixed seeds throughout.
+The packets of parts 1, 2, 5 and 6 come from tests/length_sweep.py (six source models in turn), the batch descriptors
+from tests/batch_sweep.py; the host half is tests/test_lane_emulation.py::test_lane_decoder_at_every_packet_length.
+Fixed seeds throughout.
 """
 import numpy as np
 import pytest
 
+import batch_sweep as BS
 import length_sweep as LS
 from gpuar_amd import synth
 
@@ -61,17 +69,18 @@ def _status():
     return torch.zeros(1, dtype=torch.int32, device="cuda")
 
 
-def _first_wrong_row(got, want, order, sweep, what):
-    """pytest.fail with the packet, lane, ulen and first differing byte of the first output row that is wrong."""
+def _first_wrong_row(got, want, order, sweep, what, rooms=None):
+    """pytest.fail with the packet, lane, ulen (and room) and first differing byte of the first output row that is wrong."""
     bad = (got != want).any(dim=1).nonzero().flatten()
     lane = int(bad[0])
     i = int(order[lane])
     ulen = int(sweep["ulens"][i])
+    room = "" if rooms is None else f", room {int(rooms[lane])}"
     g, w = got[lane].cpu().numpy(), want[lane].cpu().numpy()
     at = int(np.flatnonzero(g != w)[0])
     where = "inside ulen" if at < ulen else "after ulen (canary overwritten)"
     pytest.fail(f"{what}: {bad.numel()} rows wrong; first: packet {i} at row {lane} (wavefront {lane // 64}, lane {lane % 64}), "
-                f"ulen {ulen}, byte {at} {where}: got {g[at]:#04x}, want {w[at]:#04x}")
+                f"ulen {ulen}{room}, byte {at} {where}: got {g[at]:#04x}, want {w[at]:#04x}")
 
 
 def _check_rows(d_out, order, sweep, what):
@@ -89,13 +98,11 @@ def _check_rows(d_out, order, sweep, what):
 LAYOUTS = LS.layouts()
 
 
-@pytest.mark.parametrize("skew", [0, 4])
-@pytest.mark.parametrize("layout", list(LAYOUTS))
-def test_decode_stream_at_every_packet_length(H, sweep, layout, skew):
-    order = LAYOUTS[layout]
-    n = order.size
+def _device_stream(sweep, order, skew):
+    """The packets of `order` back to back on the device at an address that is `skew` mod 16 (its own allocation, 64 bytes
+    of slack): (allocation, stream, offsets)."""
     stream = np.concatenate([sweep["encs"][i] for i in order])
-    offs = np.zeros(n + 1, dtype=np.int64)
+    offs = np.zeros(order.size + 1, dtype=np.int64)
     offs[1:] = np.cumsum(sweep["clens"][order])
     assert offs[-1] == stream.size
     raw = torch.zeros(stream.size + 64, dtype=torch.uint8, device="cuda")
@@ -103,9 +110,18 @@ def test_decode_stream_at_every_packet_length(H, sweep, layout, skew):
     raw[base:base + stream.size] = torch.from_numpy(stream).cuda()
     d_stream = raw[base:base + stream.size]
     assert d_stream.data_ptr() % 16 == skew
+    return raw, d_stream, torch.from_numpy(offs).cuda()
+
+
+@pytest.mark.parametrize("skew", [0, 4])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_decode_stream_at_every_packet_length(H, sweep, layout, skew):
+    order = LAYOUTS[layout]
+    n = order.size
+    raw, d_stream, d_offs = _device_stream(sweep, order, skew)
     d_out = torch.full((n * PACKET,), CANARY, dtype=torch.uint8, device="cuda")
     word = _status()
-    H.decode_stream(d_stream, torch.from_numpy(offs).cuda(), n, d_out, d_status=word)
+    H.decode_stream(d_stream, d_offs, n, d_out, d_status=word)
     torch.cuda.synchronize()
     assert int(word.item()) == 0, f"{layout} skew {skew}: status {int(word.item()):#x}"
     _check_rows(d_out, order, sweep, f"decode_stream {layout} skew {skew}")
@@ -291,3 +307,124 @@ def test_compact_equals_a_plain_concatenation(H, n):
             at = int((got != want).nonzero()[0]) - int(want_offs[p] - want_offs[a])
             pytest.fail(f"{n} packets: packet {p} (clen {clens[p]}, destination offset {int(want_offs[p])}, "
                         f"alignment {int(want_offs[p]) % 16}) differs first at byte {at}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. and 6. every packet length through the batch kernels
+# ---------------------------------------------------------------------------------------------------------------------
+PAD = 4096                                             # canary bytes in front of and behind every output arena
+
+
+def _batch_desc(bufs, base):
+    """tests/batch_sweep.py's buffers at device address `base` as the three descriptor arrays (one upload), and their count."""
+    ptrs, nbytes, first = BS.columns(bufs, base)
+    d = torch.tensor(ptrs + nbytes + first, dtype=torch.int64).cuda()
+    k = len(bufs)
+    return d[:k], d[k:2 * k], d[2 * k:], k
+
+
+def _decode_batch(H, via, d_src, d_offs, n, bufs, rows):
+    """One launch of decode_batch (via "slots") or decode_stream_batch over n packets into `bufs`, laid out in the rows of a
+    canary arena with PAD canary bytes on either side: (the rows in batch order, the launch's status word, pads intact)."""
+    d_out = torch.full((n * PACKET + 2 * PAD,), CANARY, dtype=torch.uint8, device="cuda")
+    d_ptrs, d_bytes, d_fp, k = _batch_desc(bufs, d_out.data_ptr() + PAD)
+    word = _status()
+    if via == "slots":
+        H.decode_batch(d_src, d_fp, k, n, d_ptrs, d_bytes, d_status=word)
+    else:
+        H.decode_stream_batch(d_src, d_offs, d_fp, k, n, d_ptrs, d_bytes, d_status=word)
+    torch.cuda.synchronize()
+    pads = bool(d_out[:PAD].eq(CANARY).all()) and bool(d_out[PAD + n * PACKET:].eq(CANARY).all())
+    got = d_out[PAD:PAD + n * PACKET].view(n, PACKET).index_select(0, torch.from_numpy(np.asarray(rows)).cuda())
+    return got, int(word.item()), pads
+
+
+def _check_batch_rows(got, word, pads, order, sweep, rooms, what):
+    assert word == 0, f"{what}: status {word:#x}"
+    assert pads, f"{what}: written in front of the first or behind the last output row"
+    want = sweep["rows"].index_select(0, torch.from_numpy(order).cuda())
+    if not torch.equal(got, want):
+        _first_wrong_row(got, want, order, sweep, what, rooms)
+
+
+@pytest.mark.parametrize("mode", ["throughput", "latency"])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_encode_batch_at_every_packet_length(H, sweep, layout, mode):
+    """encode_batch_kernel / encode_small_batch_kernel with lanes of any lengths side by side: lane i is its own buffer
+    holding packet order[i] + 1, so a wavefront's lanes own different numbers of whole phases and each partial phase waits
+    for the final one.  The buffers lie 16-byte aligned in one arena in a seeded permuted address order, with zero-byte
+    buffers at the front, the end and in runs between them; the bytes between buffers are 0x00 in one run and 0xFF in a
+    second.  Each run: status 0, the input arena unchanged, every slot's clen bytes equal to the reference's encoding.  Both
+    runs give the same slots byte for byte (nothing behind a buffer's end reaches its packet), and the slots decode back
+    through both batch decoders."""
+    order = LAYOUTS[layout]
+    n = order.size
+    sizes = sweep["ulens"][order]
+    bufs, total = BS.scattered_inputs(sizes, n)
+    starts = [off for off, _, _ in bufs if off is not None]               # lane order
+    idx = torch.from_numpy(order).cuda()
+    want = sweep["slots"].index_select(0, idx)
+    keep = torch.arange(SLOT, device="cuda")[None, :] < sweep["d_clens"].index_select(0, idx)[:, None]
+    runs = []
+    for fill in (0x00, 0xFF):
+        host = np.full(total, fill, dtype=np.uint8)
+        for at, i in zip(starts, order):
+            host[at:at + i + 1] = sweep["pkts"][i]
+        d_arena = torch.from_numpy(host).cuda()
+        d_before = d_arena.clone()
+        assert d_arena.data_ptr() % 16 == 0
+        d_ptrs, d_bytes, d_fp, k = _batch_desc(bufs, d_arena.data_ptr())
+        d_slots = torch.full((n * SLOT,), 0xEE, dtype=torch.uint8, device="cuda")
+        word = _status()
+        H.encode_batch(d_ptrs, d_bytes, d_fp, k, n, d_slots=d_slots, d_status=word, mode=mode)
+        torch.cuda.synchronize()
+        what = f"encode_batch {mode}, {layout}, {fill:#04x} between buffers"
+        assert int(word.item()) == 0, f"{what}: status {int(word.item()):#x}"
+        assert torch.equal(d_arena, d_before), f"{what}: the input arena changed"
+        got = d_slots.view(n, SLOT)
+        if not torch.equal(torch.where(keep, got, 0), torch.where(keep, want, 0)):
+            bad = (torch.where(keep, got, 0) != torch.where(keep, want, 0)).any(dim=1).nonzero().flatten()
+            lane = int(bad[0])
+            i = int(order[lane])
+            at = int((got[lane] != want[lane])[:int(sweep["clens"][i])].nonzero()[0])
+            pytest.fail(f"{what}: {bad.numel()} slots wrong; first: packet {i} (ulen {i + 1}, clen {int(sweep['clens'][i])}) "
+                        f"at batch packet {lane} (wavefront {lane // 64}, lane {lane % 64}), byte {at}: "
+                        f"got {int(got[lane, at]):#04x}, want {int(want[lane, at]):#04x}")
+        runs.append(d_slots)
+    if not torch.equal(runs[0], runs[1]):
+        lane = int((runs[0].view(n, SLOT) != runs[1].view(n, SLOT)).any(dim=1).nonzero()[0])
+        pytest.fail(f"encode_batch {mode}, {layout}: the slots depend on the bytes between buffers; first at batch packet {lane} "
+                    f"(packet {int(order[lane])}, wavefront {lane // 64}, lane {lane % 64})")
+    out_bufs, rows = BS.one_packet_outputs(sizes, n + 1)
+    d_stream, d_offs = H.compact(runs[0], n)
+    for via, d_src in (("slots", runs[0]), ("stream", d_stream)):
+        got, word, pads = _decode_batch(H, via, d_src, d_offs, n, out_bufs, rows)
+        _check_batch_rows(got, word, pads, order, sweep, sizes, f"encode_batch {mode}, {layout}: round trip through {via}")
+
+
+@pytest.mark.parametrize("outputs", ["one_per_packet", "multi_packet"])
+@pytest.mark.parametrize("source", ["slots", "stream_skew0", "stream_skew4"])
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+def test_decode_batch_at_every_packet_length(H, sweep, layout, source, outputs):
+    """decode_slots_batch_kernel / decode_stream_batch_kernel on the sweep's reference slots, and on them back to back at
+    pointer skew 0 and 4.  one_per_packet: each packet its own buffer, out_bytes = its ulen exactly (the room boundary at
+    every length), in a seeded permutation of the arena's rows.  multi_packet: consecutive packets in buffers of 1-5,
+    out_bytes = (k - 1) * 8192 + the last one's ulen, so the others have a room of 8192 and a canary behind their ulen.
+    Zero-byte buffers among them.  Every row equals its packet with the canary behind it, status 0."""
+    order = LAYOUTS[layout]
+    n = order.size
+    ulens = sweep["ulens"][order]
+    if outputs == "one_per_packet":
+        bufs, rows = BS.one_packet_outputs(ulens, n + 2)
+    else:
+        bufs, rows = BS.grouped_outputs(ulens, n + 3), np.arange(n)
+    rooms = BS.lane_rooms(bufs)
+    assert rooms.size == n and (rooms >= ulens).all()
+    if source == "slots":
+        via, raw, d_offs = "slots", None, None
+        d_src = sweep["slots"].index_select(0, torch.from_numpy(order).cuda()).reshape(-1)
+    else:
+        via = "stream"
+        raw, d_src, d_offs = _device_stream(sweep, order, int(source[-1]))
+    got, word, pads = _decode_batch(H, via, d_src, d_offs, n, bufs, rows)
+    _check_batch_rows(got, word, pads, order, sweep, rooms, f"decode_{via}_batch {layout}, {source}, {outputs}")

@@ -19,6 +19,7 @@ from test_oracle_golden import REFV, case_input
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 u8p = C.POINTER(C.c_uint8)
+u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
 
 
@@ -47,6 +48,8 @@ def emu():
     lib.emu_device_rule_rare_events.argtypes = []
     lib.emu_decode_stream.restype = C.c_int
     lib.emu_decode_stream.argtypes = [u8p, u64p, C.c_size_t, u8p]
+    lib.emu_decode_stream_room.restype = C.c_int
+    lib.emu_decode_stream_room.argtypes = [u8p, u64p, u32p, C.c_size_t, u8p]
     lib.emu_check_recip.restype = C.c_uint64
     lib.emu_check_recip.argtypes = [C.c_uint32]
     lib.emu_check_renorm_count.restype = C.c_uint64
@@ -448,6 +451,52 @@ def test_lane_decoder_refuses_invalid_headers(emu, damaged_sweep, port_oracle):
     zero[2:4] = 0
     out, bad = emu_decode_one(emu, zero)
     assert bad == 0 and (out == 0xA5).all()
+
+
+def test_lane_decoder_room_rule(emu, damaged_sweep, port_oracle):
+    """DecoderLane::open<true>, the batch decoders' instantiation (emu_decode_stream_room): over the damage sweep and
+    DS.invalid(), back to back, with every packet's room 8192, its clean length n, its ulen, ulen - 1, and a seeded mix of
+    those four: a packet is refused exactly when its ulen exceeds its room or its header is invalid, a refused packet's
+    output is untouched, and every other output is byte-equal to emu_decode_stream's.  Each rule runs over outputs
+    filled with 0x00 and with 0xFF: a packet that writes anything changes one of the two."""
+    import length_sweep as LS
+    DS, (pkts, classes) = damaged_sweep
+    invalid = DS.invalid(lambda m: port_oracle.encode_stream(LS.packet(m)))
+    allp = pkts + [p for p, _ in invalid]
+    what = [f"packet {n} ({c})" for n, c in enumerate(classes, 1)] + [f"invalid header ({w})" for _, w in invalid]
+    np_ = len(allp)
+    stream, offs = DS.stream_form(allp)
+    offs = offs.astype(np.uint64)
+    fields = np.asarray([DS.fields(p) for p in allp], dtype=np.int64)
+    clen, ulen = fields[:, 0], fields[:, 1]
+    valid = (ulen <= 8192) & (clen >= 4)
+    clean_n = np.asarray([n for n in range(1, len(pkts) + 1)] + [8192] * len(invalid), dtype=np.int64)
+    want = np.zeros(np_ * 8192, dtype=np.uint8)
+    assert emu.emu_decode_stream(stream.ctypes.data_as(u8p), offs.ctypes.data_as(u64p), np_, want.ctypes.data_as(u8p)) \
+        == int((~valid).sum())
+    want = want.reshape(np_, 8192)
+    rules = {"8192": np.full(np_, 8192), "clean length n": clean_n, "ulen": ulen, "ulen - 1": np.maximum(ulen - 1, 0)}
+    pick = np.random.default_rng(LS.SEED + 91).integers(0, 4, np_)
+    rules["mixed"] = np.choose(pick, list(rules.values()))
+    for rule, rooms in rules.items():
+        rooms = np.ascontiguousarray(rooms, dtype=np.uint32)
+        refused = ~valid | (ulen > rooms)
+        for fill in (0x00, 0xFF):
+            out = np.full(np_ * 8192, fill, dtype=np.uint8)
+            got = emu.emu_decode_stream_room(stream.ctypes.data_as(u8p), offs.ctypes.data_as(u64p), rooms.ctypes.data_as(u32p),
+                                             np_, out.ctypes.data_as(u8p))
+            out = out.reshape(np_, 8192)
+            untouched = (out == fill).all(axis=1)
+            for p in np.flatnonzero(refused & ~untouched):
+                pytest.fail(f"rule {rule}, fill {fill:#04x}: {what[p]}, ulen {ulen[p]}, room {rooms[p]}: refused, but written")
+            for p in np.flatnonzero(~refused):
+                u = int(ulen[p])
+                if not (np.array_equal(out[p, :u], want[p, :u]) and (out[p, u:] == fill).all()):
+                    at = int(np.flatnonzero(np.concatenate([out[p, :u] != want[p, :u], out[p, u:] != fill]))[0])
+                    pytest.fail(f"rule {rule}, fill {fill:#04x}: {what[p]}, ulen {u}, room {rooms[p]}: must decode, but "
+                                f"differs from emu_decode_stream's output first at byte {at}")
+            assert got == int(refused.sum()), f"rule {rule}: {got} packets refused, want {int(refused.sum())}"
+        assert refused[valid].any() == (rule not in ("8192", "ulen")), f"rule {rule}: {int(refused[valid].sum())} valid packets refused"
 
 
 def test_bytes_behind_the_limit_never_change_the_output(emu, port_oracle):

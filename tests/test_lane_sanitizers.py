@@ -1,8 +1,8 @@
 """The per-lane codec (gpuar_amd/csrc/lane_codec.h) under AddressSanitizer + UBSan on the CPU.
 
 GPU sanitizers are not available on the pool, so the same source the kernels run per lane is
-exercised here with the host build: every golden fixture through encode + decode, plus malformed
-packets, with shifts, indices and buffer bounds checked by the sanitizers."""
+exercised here with the host build: every golden fixture through encode + decode (and the batch decoders' room
+rule), plus malformed packets, with shifts, indices and buffer bounds checked by the sanitizers."""
 import os
 import subprocess
 import sys
@@ -18,9 +18,10 @@ sys.path.insert(0, %(tests)r); sys.path.insert(0, %(root)r)
 from test_oracle_golden import REFV, case_input
 from oracle import oracle as O
 lib = C.CDLL(%(so)r)
-u8p = C.POINTER(C.c_uint8); u64p = C.POINTER(C.c_uint64)
+u8p = C.POINTER(C.c_uint8); u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64)
 lib.emu_encode_slots.argtypes = [u8p, C.c_size_t, u8p]
 lib.emu_decode_stream.argtypes = [u8p, u64p, C.c_size_t, u8p]
+lib.emu_decode_stream_room.argtypes = [u8p, u64p, u32p, C.c_size_t, u8p]
 P = O.PortOracle()
 for c in REFV:
     data = case_input(c)
@@ -36,6 +37,13 @@ for c in REFV:
     padded = np.concatenate([stream, np.zeros(16, dtype=np.uint8)]); out = np.zeros(npk * 8192, dtype=np.uint8)
     lib.emu_decode_stream(padded.ctypes.data_as(u8p), offs.ctypes.data_as(u64p), npk, out.ctypes.data_as(u8p))
     assert np.array_equal(out[:data.size], data), c["name"]
+    if npk:                                                  # the batch decoders' room rule: the last packet one byte short
+        rooms = np.full(npk, 8192, dtype=np.uint32); rooms[-1] = data.size - (npk - 1) * 8192 - 1
+        out = np.zeros(npk * 8192, dtype=np.uint8)
+        got = lib.emu_decode_stream_room(padded.ctypes.data_as(u8p), offs.ctypes.data_as(u64p), rooms.ctypes.data_as(u32p), npk,
+                                         out.ctypes.data_as(u8p))
+        keep = (npk - 1) * 8192
+        assert got == 1 and np.array_equal(out[:keep], data[:keep]) and not out[keep:].any(), c["name"]
 rng = np.random.default_rng(3)
 for t in range(30):
     blob = rng.integers(0, 256, 9000, dtype=np.uint8)
