@@ -29,6 +29,7 @@
 // bitstream.  No MFMA: this is integer, bit-serial
 // work bounded by VALU issue and LDS operations, not by HBM.
 #include <hip/hip_runtime.h>
+#include <mutex>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -60,6 +61,7 @@ struct MulTable {
 __device__ const MulTable g_mul = MulTable();
 __constant__ DecodeConstTable g_decode = DecodeConstTable();
 __device__ uint32_t g_status = 0;
+__device__ uint32_t g_status_taken;         // what take_status_kernel took out of g_status, for gpuar_hip_status to copy back
 __device__ uint32_t g_cu_ticket[2048];      // one arrival counter per CU (XCC, SE, SH, CU), see encode_kernel
 // What the shader clock really was while the two throughput kernels ran (measurement support, gpuar_hip_clock_samples): every
 // 64th workgroup notes how many shader-clock ticks (s_memtime) and how many ticks of the constant 100 MHz clock
@@ -2386,6 +2388,14 @@ crc32_kernel(CrcArgs a) {
     }
 }
 
+// gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
+// moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
+// followed by a separate clear would drop a bit that arrives between the two.
+__global__ void __launch_bounds__(kLanes)
+take_status_kernel() {
+    if (threadIdx.x == 0) g_status_taken = atomicExch(&g_status, 0u);
+}
+
 }  // namespace gpuar
 
 // ===========================================================================
@@ -2679,13 +2689,17 @@ int gpuar_hip_status(uint32_t *flags) {
     if (!flags) return GPUAR_ERR_ARGUMENT;
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return static_cast<int>(e);
+    // g_status_taken is one word per device: one caller at a time between the exchange and the copy that reads it
+    static std::mutex taking;
+    std::lock_guard<std::mutex> hold(taking);
+    gpuar::take_status_kernel<<<1, gpuar::kLanes, 0, nullptr>>>();      // the copy below waits for it (same stream)
+    const int launched = check_launch();
+    if (launched != GPUAR_OK) return launched;
     uint32_t v = 0;
-    e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(gpuar::g_status), sizeof v);
+    e = hipMemcpyFromSymbol(&v, HIP_SYMBOL(gpuar::g_status_taken), sizeof v);
     if (e != hipSuccess) return static_cast<int>(e);
-    const uint32_t zero = 0;
-    e = hipMemcpyToSymbol(HIP_SYMBOL(gpuar::g_status), &zero, sizeof zero);
     *flags = v;
-    return e == hipSuccess ? GPUAR_OK : static_cast<int>(e);
+    return GPUAR_OK;
 }
 
 int gpuar_hip_last_error(void) {

@@ -339,7 +339,8 @@ def verify_crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packet
 
 def status() -> int:
     """Reads and clears the device's FALLBACK status word -- what launches without a d_status of their own
-    reported (synchronises the device)."""
+    reported (synchronises the device).  The read and the clear are one atomic exchange on the device: every bit a
+    launch ORs into the word is reported by exactly one status() call, even while other threads launch into it."""
     flags = C.c_uint32(0)
     _check(load().gpuar_hip_status(C.byref(flags)), "gpuar_hip_status")
     return int(flags.value)

@@ -236,7 +236,11 @@ int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
- * single-stream legacy use, not for pipelines (pass `d_status` there). */
+ * single-stream legacy use, not for pipelines (pass `d_status` there).
+ * The read and the clear are one atomic exchange on the device, so every bit
+ * a launch ORs into the word is reported by exactly one gpuar_hip_status call,
+ * even while other host threads launch into it: a bit that arrives during a
+ * call is either in that call's *flags or left for the next call. */
 int gpuar_hip_status(uint32_t *flags);
 
 /* Last error recorded by a void-returning reference-named entry point on this

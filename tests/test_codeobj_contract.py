@@ -120,6 +120,8 @@ def test_every_kernel_keeps_its_lds_registers_and_no_scratch(code_object):
     assert meta["encode_kernel"]["group_segment_fixed_size"] == 39936
     assert meta["decode_slots_kernel"]["group_segment_fixed_size"] == 40960 == meta["decode_stream_kernel"]["group_segment_fixed_size"]
     assert meta["encode_kernel"]["max_flat_workgroup_size"] == 256 and meta["decode_slots_kernel"]["max_flat_workgroup_size"] == 64
+    # gpuar_hip_status's read-and-clear of the fallback word: one wavefront, no LDS
+    assert meta["take_status_kernel"]["group_segment_fixed_size"] == 0 and meta["take_status_kernel"]["max_flat_workgroup_size"] == 64
 
 
 def test_the_resource_check_does_fail_when_a_kernel_outgrows_its_share():
