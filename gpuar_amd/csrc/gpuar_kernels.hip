@@ -403,6 +403,26 @@ __device__ __forceinline__ void run_low(EncodeLds &lds, uint32_t lane, uint32_t 
     lds_barrier();                                             // phase n_phases + 1: the coder's last
 }
 
+// The coder (CoderLane, CarryCoderLane), two phases behind the top modeler: slot address = (wave-uniform base of this group's
+// first slot) + lane * 8704; phases 0 and 1 are the modelers' first
+template <typename Coder>
+__device__ __forceinline__ void coder_open(Coder &coder, uint8_t *dst, size_t group, uint32_t lane) {
+    __builtin_amdgcn_s_setprio(kPrioCoder);
+    coder.open(dst + group * (kLanes * kSlot), lane * kSlot);
+    lds_barrier();
+    lds_barrier();
+}
+
+// The end of a coding lane (CoderLane, CarryCoderLane, CarrySinkLane): the packet's header, SLOT_OVERFLOW if it did not fit
+template <typename Lane>
+__device__ __forceinline__ void finish_lane(Lane &coder, bool live, uint32_t len, uint32_t *status) {
+    if (live) {
+        bool overflowed;
+        coder.finish(len, overflowed);
+        if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
+    }
+}
+
 __global__ void __launch_bounds__(4 * kLanes)
 encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict__ dst, uint32_t n_packets, uint32_t *__restrict__ status) {
     __shared__ EncodeLds lds;
@@ -467,18 +487,12 @@ encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict_
         }
         clock_sample(0u, group, lane, 1u);
     } else {
-        // ------------------------------- coder -------------------------------
-        __builtin_amdgcn_s_setprio(kPrioCoder);
-        // slot address = (wave-uniform base of this block's first slot) + lane * 8704
-        uint8_t *block_slots = dst + group * (kLanes * kSlot);
 #ifdef GPUAR_CODER_OWED_BITS            // (A/B builds only: the coder of rounds 1-3)
         CoderLane coder;
 #else
         CarryCoderLane coder;                // the lower bound as a 64-bit window, carries instead of owed bits (lane_codec.h)
 #endif
-        coder.open(block_slots, lane * kSlot);
-        lds_barrier();                                       // phases 0 and 1: the modelers' first
-        lds_barrier();
+        coder_open(coder, dst, group, lane);
         uint32_t slot = 0, k = 0;
         // Two loops, not one loop with two bodies: with both bodies in one loop the coder's eight state registers were copied
         // to the whole-phase body's own set at the top of every phase and back at its end (16 of ~280 vector instructions).
@@ -641,11 +655,8 @@ __device__ __forceinline__ void batch_roles(EncodeLds &lds, uint32_t role, size_
             lds_barrier();
         }
     } else {
-        __builtin_amdgcn_s_setprio(kPrioCoder);
         CarryCoderLane coder;
-        coder.open(dst + group * (kLanes * kSlot), lane * kSlot);
-        lds_barrier();                                       // phases 0 and 1: the modelers' first
-        lds_barrier();
+        coder_open(coder, dst, group, lane);
         uint32_t slot = 0, k = 0;
         auto whole_phase = [&](uint32_t k) __attribute__((always_inline)) {   // the symbols of phase k, during phase k + 2
             const uint32_t *in_ring = &lds.sums[slot][0][lane];
@@ -688,11 +699,7 @@ __device__ __forceinline__ void batch_roles(EncodeLds &lds, uint32_t role, size_
             for (uint32_t j = 0; j < part; ++j) coder.step(in_ring[j * kLanes], g_recip.r[own + j]);
             lds_barrier();
         }
-        if (live) {
-            bool overflowed;
-            coder.finish(len, overflowed);
-            if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
-        }
+        finish_lane(coder, live, len, status);
     }
 }
 
@@ -885,6 +892,15 @@ __device__ __forceinline__ void small_follow(EncodeSmallLds &lds, uint32_t lane,
     for (uint32_t b = lag; b < kSmallLag; ++b) lds_barrier();
 }
 
+// SINK's body for a phase the lane owns completely
+__device__ __forceinline__ void sink_whole_phase(CarrySinkLane &sink, const uint32_t *in_words) {
+    uint32_t w[kSmallPhase];
+#pragma unroll
+    for (uint32_t j = 0; j < kSmallPhase; ++j) w[j] = in_words[j * kLanes];
+#pragma unroll
+    for (uint32_t j = 0; j < kSmallPhase; ++j) sink.take(w[j]);
+}
+
 __global__ void __launch_bounds__(kSmallWaves * kLanes)
 encode_small_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict__ dst, uint32_t n_packets, uint32_t *__restrict__ status) {
     __shared__ EncodeSmallLds lds;
@@ -970,11 +986,7 @@ encode_small_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__res
             const uint32_t base = k * kSmallPhase;
             const uint32_t *in_words = &lds.words[k & 1u][0][lane];
             if (base + kSmallPhase <= len_min) {
-                uint32_t w[kSmallPhase];
-#pragma unroll
-                for (uint32_t j = 0; j < kSmallPhase; ++j) w[j] = in_words[j * kLanes];
-#pragma unroll
-                for (uint32_t j = 0; j < kSmallPhase; ++j) sink.take(w[j]);
+                sink_whole_phase(sink, in_words);
             } else {
 #pragma unroll 1
                 for (uint32_t j = 0; j < kSmallPhase; ++j)
@@ -982,11 +994,7 @@ encode_small_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__res
             }
             lds_barrier();
         }
-        if (live) {
-            bool overflowed;
-            sink.finish(len, overflowed);
-            if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
-        }
+        finish_lane(sink, live, len, status);
     }
 }
 
@@ -1140,14 +1148,7 @@ __device__ __forceinline__ void batch_small_roles(EncodeSmallLds &lds, size_t gr
         for (uint32_t b = 0; b < kSmallLag; ++b) lds_barrier();
         uint32_t k = 0;
         for (; k < whole_max; ++k) {
-            if (k < whole) {
-                const uint32_t *in_words = &lds.words[k & 1u][0][lane];
-                uint32_t w[kSmallPhase];
-#pragma unroll
-                for (uint32_t j = 0; j < kSmallPhase; ++j) w[j] = in_words[j * kLanes];
-#pragma unroll
-                for (uint32_t j = 0; j < kSmallPhase; ++j) sink.take(w[j]);
-            }
+            if (k < whole) sink_whole_phase(sink, &lds.words[k & 1u][0][lane]);
             lds_barrier();
         }
         if (k < n_phases) {
@@ -1156,11 +1157,7 @@ __device__ __forceinline__ void batch_small_roles(EncodeSmallLds &lds, size_t gr
             for (uint32_t j = 0; whole * kSmallPhase + j < len; ++j) sink.take(in_words[j * kLanes]);
             lds_barrier();
         }
-        if (live) {
-            bool overflowed;
-            sink.finish(len, overflowed);
-            if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
-        }
+        finish_lane(sink, live, len, status);
     }
 }
 
@@ -1928,21 +1925,27 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
     }
 }
 
+// A group's slots (wave-uniform base) and what the lane may read: its slot, cut short where the `n_bytes` of slots end
+// (the last slot of garDecompressExecutor's `size` bytes may be a partial one, src/gpuar_kernel.cu:916-934)
+__device__ __forceinline__ const uint8_t *group_slots(const uint8_t *slots, size_t n_bytes, uint32_t lane, uint32_t &limit_off) {
+    const size_t group_at = static_cast<size_t>(blockIdx.x) * (kLanes * kSlot);
+    const uint8_t *base = slots + group_at;                                                       // wave-uniform
+    const size_t group_left = n_bytes - group_at;
+    const uint32_t slot_end = (lane + 1u) * kSlot;
+    limit_off = group_left < slot_end ? static_cast<uint32_t>(group_left) : slot_end;
+    return base;
+}
+
 __global__ void __launch_bounds__(kLanes)
 decode_slots_kernel(const uint8_t *__restrict__ slots, uint32_t n_packets, size_t n_bytes, uint8_t *__restrict__ out, uint32_t *__restrict__ status) {
     __shared__ __attribute__((aligned(4096))) uint4 lds[kDecodeLdsQuads];    // 40 KiB: 72 half-records x 64 lanes x 8 B, then 4 KiB of stream rings
     const uint32_t lane = threadIdx.x;
     const size_t packet = static_cast<size_t>(blockIdx.x) * kLanes + lane;
     const bool live = packet < n_packets;
-    const size_t group_at = static_cast<size_t>(blockIdx.x) * (kLanes * kSlot);
-    const uint8_t *group_slots = slots + group_at;                                                // wave-uniform
-    // what may be read: the lane's slot, cut short where the caller's buffer ends (the last slot of garDecompressExecutor's
-    // `size` bytes may be a partial one, src/gpuar_kernel.cu:916-934)
-    const size_t group_left = n_bytes - group_at;
-    const uint32_t slot_end = (lane + 1u) * kSlot;
-    const uint32_t limit_off = group_left < slot_end ? static_cast<uint32_t>(group_left) : slot_end;
+    uint32_t limit_off;
+    const uint8_t *base = group_slots(slots, n_bytes, lane, limit_off);
     clock_sample(1u, blockIdx.x, lane, 0u);
-    decode_wave(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, group_slots, lane * kSlot, limit_off,
+    decode_wave(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, base, lane * kSlot, limit_off,
                 out + (live ? packet : 0) * static_cast<size_t>(kPacket), live, status);
     clock_sample(1u, blockIdx.x, lane, 1u);
 }
@@ -1996,15 +1999,12 @@ decode_slots_batch_kernel(const uint8_t *__restrict__ slots, const uint64_t *__r
     __shared__ __attribute__((aligned(4096))) uint4 lds[kDecodeLdsQuads];
     const uint32_t lane = threadIdx.x;
     const size_t packet = static_cast<size_t>(blockIdx.x) * kLanes + lane;
-    const size_t group_at = static_cast<size_t>(blockIdx.x) * (kLanes * kSlot);
-    const uint8_t *group_slots = slots + group_at;                                                // wave-uniform
-    const size_t group_left = static_cast<size_t>(n_packets) * kSlot - group_at;
-    const uint32_t slot_end = (lane + 1u) * kSlot;
-    const uint32_t limit_off = group_left < slot_end ? static_cast<uint32_t>(group_left) : slot_end;
+    uint32_t limit_off;
+    const uint8_t *base = group_slots(slots, static_cast<size_t>(n_packets) * kSlot, lane, limit_off);
     uint8_t *out;
     uint32_t room;
     const bool live = batch_output(outs, out_bytes, first_packet, n_buffers, packet, packet < n_packets, out, room, status);
-    decode_wave<true>(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, group_slots, lane * kSlot, limit_off,
+    decode_wave<true>(reinterpret_cast<uint8_t *>(lds) + 8u * lane, reinterpret_cast<uint8_t *>(lds + kDecodeRecords * kLanes) + 4u * lane, base, lane * kSlot, limit_off,
                       out, live, status, room);
 }
 
