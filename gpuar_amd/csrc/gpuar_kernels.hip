@@ -40,12 +40,6 @@
 #include "lane_codec.h"
 #include "crc32.h"
 
-// The GPUAR_EXP_* switches below take pieces OUT of the kernels to price them (profiles/r0N_*budget*.txt, *attribution*.txt): such a
-// build produces WRONG output.  It only compiles when the build says it is one (tools/exp_build.sh defines GPUAR_EXPERIMENT_BUILD for
-// any flag of that family), and the library then says so in gpuar_hip_version(), which gpuar_amd/hip.py refuses to load as the product.
-#if (defined(GPUAR_EXP_NO_ADDS) || defined(GPUAR_EXP_NO_CODER) || defined(GPUAR_EXP_NO_LOW) || defined(GPUAR_EXP_NO_READS) || defined(GPUAR_EXP_NO_RING) || defined(GPUAR_EXP_NO_RING_MUL) || defined(GPUAR_EXP_NO_RING_VMCNT) || defined(GPUAR_EXP_NO_RING_WRITES) || defined(GPUAR_EXP_NO_SEARCH) || defined(GPUAR_EXP_NO_STORES) || defined(GPUAR_EXP_NO_STREAM) || defined(GPUAR_EXP_NO_STREAM_READ) || defined(GPUAR_EXP_NO_WAIT1) || defined(GPUAR_EXP_NO_WAIT2)) && !defined(GPUAR_EXPERIMENT_BUILD)
-#error "a GPUAR_EXP_* switch without GPUAR_EXPERIMENT_BUILD: these builds decode / encode garbage; use tools/exp_build.sh"
-#endif
 namespace gpuar {
 
 __constant__ RecipTable g_recip = RecipTable();
@@ -135,12 +129,7 @@ constexpr uint32_t kPhase = 8;
 // roles swapped -- whoever walks four LDS levels has to go first, the three-level modeler last.
 // Round 4 (the coder in carry form, ten vector instructions shorter): top > low > coder.  With the old order the lighter coder
 // bought nothing (5.14 ms for 6 + 1 and 5 + 2 depths alike); with the coder last 4.96-4.99 ms for 5 + 2, 4 + 3 and 3 + 4.
-#ifndef GPUAR_PRIO_TOP
-#define GPUAR_PRIO_TOP 3
-#define GPUAR_PRIO_CODER 0
-#define GPUAR_PRIO_LOW 2
-#endif
-constexpr int kPrioTop = GPUAR_PRIO_TOP, kPrioCoder = GPUAR_PRIO_CODER, kPrioLow = GPUAR_PRIO_LOW;
+constexpr int kPrioTop = 3, kPrioCoder = 0, kPrioLow = 2;
 
 // The three roles work one phase apart -- the top modeler on the symbols of phase p, the low modeler on those of
 // p - 1, the coder on those of p - 2 -- and hand a phase on IN PLACE: the top modeler writes its part of
@@ -370,9 +359,6 @@ __device__ __forceinline__ void run_low(EncodeLds &lds, uint32_t lane, uint32_t 
 #pragma unroll
             for (uint32_t j = 0; j < kPhase; ++j) part[j] = io[j * kLanes], tag[j] = byte_tag(bytes[j >> 2], j & 3u);
             model.prime_tag(tag[0]);
-#ifdef GPUAR_EXP_NO_LOW          // (timing experiments only)
-            if (false)
-#endif
 #pragma unroll
             for (uint32_t j = 0; j < kPhase; ++j) {
                 if (j + 1u < kPhase) io[j * kLanes] = model.step_tag(tag[j], 256u + base + j, tag[j + 1u], part[j]);
@@ -487,11 +473,7 @@ encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict_
         }
         clock_sample(0u, group, lane, 1u);
     } else {
-#ifdef GPUAR_CODER_OWED_BITS            // (A/B builds only: the coder of rounds 1-3)
-        CoderLane coder;
-#else
         CarryCoderLane coder;                // the lower bound as a 64-bit window, carries instead of owed bits (lane_codec.h)
-#endif
         coder_open(coder, dst, group, lane);
         uint32_t slot = 0, k = 0;
         // Two loops, not one loop with two bodies: with both bodies in one loop the coder's eight state registers were copied
@@ -513,26 +495,18 @@ encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict_
                         rc[2 * q] = {v.x, v.y}, rc[2 * q + 1] = {v.z, v.w};
                     }
                 }
-#ifdef GPUAR_CODER_OWED_BITS
-#pragma unroll
-                for (uint32_t j = 0; j < kPhase; ++j) coder.step(cums[j], rc[j]);
-#else
                 // the step in its three pieces (lane_codec.h): the NEXT symbol's two divisions sit between this symbol's
                 // "who stores?" compare and the store region that reads the answer.
                 // (Measured and not kept: a wave-uniform choice per phase between this and a store region that does not
                 // clamp its address -- one vector instruction fewer per symbol while every lane has room for the phase's
                 // eight dwords: +1 % with the reciprocals coming through LDS, +20 % while they came by scalar loads.)
                 CarryCoderLane::Ahead next = coder.ahead(cums[0], rc[0]);
-#ifdef GPUAR_EXP_NO_CODER        // (timing experiments only: what the kernel takes when the coder only meets its barriers)
-                if (false)
-#endif
 #pragma unroll
                 for (uint32_t j = 0; j < kPhase; ++j) {
                     const CarryCoderLane::Narrowed now = coder.narrow(next);
                     if (j + 1u < kPhase) next = coder.ahead(cums[j + 1u], rc[j + 1u]);
                     coder.settle(now);
                 }
-#endif
             }
             slot = next_slot(slot);
             lds_barrier();
@@ -784,10 +758,9 @@ constexpr uint32_t kSmallLag = kSmallTreeRoles + 1u;   // the last role (SINK) w
 constexpr uint32_t kSumSlots = kSmallLag;    // a slot of sums is alive from UPPER's phase to INTERVAL's, kSmallLag - 1 phases later
 constexpr uint32_t kByteBufs = kSmallTreeRoles;   // the bytes of a phase are read by the other tree roles, up to kSmallTreeRoles - 1 phases later
 constexpr uint32_t kSmallWaves = kSmallTreeRoles + 3u;   // + INTERVAL, SINK, COURIER
-#ifndef GPUAR_SMALL_PHASE
-#define GPUAR_SMALL_PHASE 16                 // (8: 0.71 ms for 64 MiB; 16: 0.68 -- half as many barriers; 64 KiB of LDS per workgroup then)
-#endif
-constexpr uint32_t kSmallPhase = GPUAR_SMALL_PHASE;   // symbols per phase: the roles meet at a barrier once per phase
+// symbols per phase: the roles meet at a barrier once per phase (8: 0.71 ms for 64 MiB; 16: 0.68 -- half as many barriers; 64 KiB
+// of LDS per workgroup then)
+constexpr uint32_t kSmallPhase = 16;
 static_assert(kSmallPhase == 8 || kSmallPhase == 16, "a phase is 2 or 4 input dwords; the courier's lanes carry one dword of reciprocals each");
 struct alignas(16) EncodeSmallLds {
     uint8_t tree[kTreeRows * kLanes * 2];     // 32 KiB
@@ -1236,74 +1209,38 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
 // that kept a select of the increment there needed a lane mask carried between statements in a scalar register).
 // The same text serves the one wavefront of a file that holds its short last packet (lanes drop out under `if`).
 // It uses decode_wave's locals by name.
-// (timing experiments only, garbage out: profiles/r06_decode_step_budget.txt prices the step's LDS operations and waits by
-// building the kernel without them, one kind at a time)
-#ifdef GPUAR_EXP_NO_READS
-#define GPUAR_LDS_READ(TEXT) ""
-#else
-#define GPUAR_LDS_READ(TEXT) TEXT
-#endif
-#ifdef GPUAR_EXP_NO_ADDS
-#define GPUAR_LDS_ADD(TEXT) ""
-#else
-#define GPUAR_LDS_ADD(TEXT) TEXT
-#endif
-#ifdef GPUAR_EXP_NO_STREAM_READ
-#define GPUAR_LDS_STREAM_READ(TEXT) ""
-#else
-#define GPUAR_LDS_STREAM_READ(TEXT) TEXT
-#endif
+// This section holds the shipped step only.  The placements that lost their A/B and the builds that priced the step by taking
+// pieces out of it (profiles/r06_decode_step_budget.txt) were deleted once their numbers were written down in the comments
+// below; their code is in git at 220c1c2.
 // The model's total (256 + position, the same in every lane) reaches the step as a VECTOR register that the step itself counts up in
 // an LDS shadow (round 6b).  Rounds 2-6a passed it as a scalar operand, which the compiler formed by one s_or per statement right in
 // front of the step's first instruction -- on the chain, and a scalar instruction costs a lone wavefront a slot like any other.
-#define GPUAR_HEAD_R0 \
-            "v_mul_u32_u24_sdwa %[R0], %[off], %[totv]" GPUAR_SDWA_W0 /* off = the low half of lo : off */
-#define GPUAR_HEAD_R0_ADD \
-            "v_add3_u32 %[R0], %[R0], %[totv], -1\n\t" /* off*total + total - 1 */
-#define GPUAR_TOTAL_STEP "v_add_u32 %[totv], 1, %[totv]\n\t"
-#ifndef GPUAR_DEC_TOTAL_PLACE
-#define GPUAR_DEC_TOTAL_PLACE 1          /* (A/B: 1 = counted up in the first LDS shadow, 2 = in the second; the same) */
-#endif
-#if GPUAR_DEC_TOTAL_PLACE == 1
-#define GPUAR_TOTAL_STEP_EARLY GPUAR_TOTAL_STEP
-#define GPUAR_TOTAL_STEP_LATE ""
-#else
-#define GPUAR_TOTAL_STEP_EARLY ""
-#define GPUAR_TOTAL_STEP_LATE GPUAR_TOTAL_STEP
-#endif
+#define GPUAR_TOTAL_STEP "v_add_u32 %[totv], 1, %[totv]\n\t" /* counted up in the first LDS shadow (in the second: the same) */
 // A record read goes out as soon as its address is there: the remainder's minimum behind the decision in front of it (which the
-// address does not need) is taken in the read's shadow (round 6b: 24.06 -> 23.87 ms; GPUAR_DEC_MIN_EARLY=1: in front of the read, as
-// in rounds 2-6a).  The step's time is the vector instructions OUTSIDE the two LDS round trips + the round trips: both shadows are
+// address does not need) is taken in the read's shadow (round 6b; in front of the read, as in rounds 2-6a: 24.06 against
+// 23.87 ms).  The step's time is the vector instructions OUTSIDE the two LDS round trips + the round trips: both shadows are
 // full (moving the instruction that files the symbol into the next step's first shadow changed nothing: 23.82 / 23.83 against
 // 23.82 / 23.85), so only what shortens the stretch in front of a read still pays.
-#ifdef GPUAR_DEC_MIN_EARLY
-#define GPUAR_MIN_BEFORE_READ(TEXT) TEXT
-#define GPUAR_MIN_BEHIND_READ(TEXT) ""
-#else
-#define GPUAR_MIN_BEFORE_READ(TEXT) ""
-#define GPUAR_MIN_BEHIND_READ(TEXT) TEXT
-#endif
-#define GPUAR_A_HEAD \
-            GPUAR_HEAD_R0 \
+#define GPUAR_STEP_HEAD \
+            "v_mul_u32_u24_sdwa %[R0], %[off], %[totv]" GPUAR_SDWA_W0 /* off = the low half of lo : off */ \
             "v_mul_u32_u24 %[t0], %[root], %[rng]\n\t" \
-            GPUAR_HEAD_R0_ADD \
+            "v_add3_u32 %[R0], %[R0], %[totv], -1\n\t" /* off*total + total - 1 */ \
             "v_sub_co_u32 %[t1], %[m0], %[R0], %[t0]\n\t" /* borrow = went left at depth 0 */ \
             "v_min_u32 %[R], %[R0], %[t1]\n\t" \
             "v_cndmask_b32 %[t2], %[h1], %[h0], %[m0]\n\t" /* the depth-1 node on the path */ \
             "v_mul_u32_u24 %[t0], %[t2], %[rng]\n\t" \
             "v_sub_co_u32 %[t1], %[m1], %[R], %[t0]\n\t" \
-            GPUAR_MIN_BEFORE_READ("v_min_u32 %[R], %[R], %[t1]\n\t") \
             "v_cndmask_b32 %[np], 0, 2, %[m0]\n\t" \
             "v_addc_co_u32 %[np], vcc, %[np], 0, %[m1]\n\t" /* complemented top two symbol bits */ \
             "v_lshl_add_u32 %[am], %[np], 10, %[col]\n\t" \
-            GPUAR_LDS_READ("ds_read2_b64 v[200:203], %[am] offset1:64\n\t") /* READ #1: mid record, right half -> v200:201, left half -> v202:203 */ \
-            GPUAR_MIN_BEHIND_READ("v_min_u32 %[R], %[R], %[t1]\n\t") /* (the remainder behind the second decision: the record's address does not need it) */ \
+            "ds_read2_b64 v[200:203], %[am] offset1:64\n\t" /* READ #1: mid record, right half -> v200:201, left half -> v202:203 */ \
+            "v_min_u32 %[R], %[R], %[t1]\n\t" /* (the remainder behind the second decision: the record's address does not need it) */
 
-#define GPUAR_A_SHADOW_PLAIN \
+#define GPUAR_SHADOW_PLAIN \
          /* in its shadow: the half of the PREVIOUS symbol's low record its path went through takes its increments by ONE \
             64-bit LDS add (v204: +1 on the count, +0x10000 on the child if left; v205: the grandchild's, if left there); no field \
             can carry into its neighbour (counts stay below 2^14) */ \
-            GPUAR_LDS_ADD("ds_add_u64 %[oaddr], v[204:205]\n\t")
+            "ds_add_u64 %[oaddr], v[204:205]\n\t"
 // The same with the previous symbol's low half ADDRESSED here -- one shift-add off the end of the chain into a shadow in which
 // the wavefront waits anyway (round 4: 26.64 -> 26.42 ms).  Measured and not kept: the filing of the previous symbol here
 // as well (its last decision's lane mask saved by s_mov_b64 and put back into vcc in front of the SDWA add-with-carry:
@@ -1311,9 +1248,14 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
 // lane mask that travels vector -> scalar -> vector costs more than the instructions it moves off the chain; the filing
 // alone with the mask re-made here from the grandchild's increment (v_cmp_ne 0, v205 -- two instructions here for one on the
 // chain): +3 cycles, this shadow has no room left.
-#define GPUAR_A_SHADOW_DEFERRED \
+#define GPUAR_SHADOW_DEFERRED \
             "v_lshl_add_u32 %[oaddr], %[c6], 9, %[collow]\n\t" \
-            GPUAR_LDS_ADD("ds_add_u64 %[oaddr], v[204:205]\n\t")
+            "ds_add_u64 %[oaddr], v[204:205]\n\t"
+// Where a step bumps its register nodes: in its first LDS shadow (rounds 2-5) or in its second (vcc and mj are free there too).
+// The even step keeps them in the first shadow; the odd step -- whose first shadow holds the stream reader's move and read and
+// whose second would otherwise wait -- bumps them in the second (round 6 A/B on uniform 8 GiB: 25.13 -> 24.76 ms; both steps in
+// the second shadow 25.20, only the even step 25.59).  After this both waits of a step are worth 3-6 cycles: the step's time is
+// its instructions' issue time (profiles/r06_decode_step_budget.txt).
 #define GPUAR_REG_NODES \
          /* register nodes += went left: the root by the first decision's mask, of the two depth-1 nodes the one on the path by \
             the second one's -- which of them it is, is settled between the two lane masks by the scalar unit (both were written \
@@ -1324,62 +1266,10 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
             "v_addc_co_u32 %[root], vcc, %[root], 0, %[m0]\n\t" \
             "v_addc_co_u32 %[h0], vcc, %[h0], 0, %[sx]\n\t" \
             "v_addc_co_u32 %[h1], vcc, %[h1], 0, %[mj]\n\t"
-// Where a step bumps its register nodes: in its first LDS shadow (rounds 2-5) or in its second (vcc and mj are free there too).
-// The even step keeps them in the first shadow; the odd step -- whose first shadow holds the stream reader's move and read and
-// whose second would otherwise wait -- bumps them in the second (round 6 A/B on uniform 8 GiB: 25.13 -> 24.76 ms; both steps in
-// the second shadow 25.20, only the even step 25.59).  After this both waits of a step are worth 3-6 cycles: the step's time is
-// its instructions' issue time (profiles/r06_decode_step_budget.txt).
-#ifndef GPUAR_DEC_NODES_PLACE
-#define GPUAR_DEC_NODES_PLACE 1
-#endif
-#define GPUAR_NODES_NOWHERE ""
-#if GPUAR_DEC_NODES_PLACE == 0
-#define GPUAR_NODES_EVEN_EARLY GPUAR_REG_NODES
-#define GPUAR_NODES_EVEN_LATE ""
-#define GPUAR_NODES_ODD_EARLY GPUAR_REG_NODES
-#define GPUAR_NODES_ODD_LATE ""
-#elif GPUAR_DEC_NODES_PLACE == 1
-#define GPUAR_NODES_EVEN_EARLY GPUAR_REG_NODES
-#define GPUAR_NODES_EVEN_LATE ""
-#define GPUAR_NODES_ODD_EARLY ""
-#define GPUAR_NODES_ODD_LATE GPUAR_REG_NODES
-#elif GPUAR_DEC_NODES_PLACE == 2
-#define GPUAR_NODES_EVEN_EARLY ""
-#define GPUAR_NODES_EVEN_LATE GPUAR_REG_NODES
-#define GPUAR_NODES_ODD_EARLY ""
-#define GPUAR_NODES_ODD_LATE GPUAR_REG_NODES
-#elif GPUAR_DEC_NODES_PLACE == 3
-#define GPUAR_NODES_EVEN_EARLY ""
-#define GPUAR_NODES_EVEN_LATE GPUAR_REG_NODES
-#define GPUAR_NODES_ODD_EARLY GPUAR_REG_NODES
-#define GPUAR_NODES_ODD_LATE ""
-#endif
 
 // (the path after the record's first decision stays in `np` -- the two later ones go on in t3 -- so that the address of the
 // half that takes the increments is formed behind read #2, next to the LDS add that uses it, and not on the chain)
-#define GPUAR_MID_WRITEBACK \
-            "v_addc_co_u32 %[t3], %[mj], %[t3], %[t3], %[mc]\n\t" \
-            "v_lshl_add_u32 %[oaddr], %[t3], 10, %[collow]\n\t" \
-            GPUAR_LDS_READ("ds_read2_b64 v[212:215], %[oaddr] offset1:64\n\t") /* READ #2: low record */ \
-            GPUAR_MIN_BEHIND_READ("v_min_u32 %[R], %[R], %[t1]\n\t") \
-         /* ---- the mid half takes its increments by one 64-bit LDS add in the shadow of read #2 */ \
-            "v_lshl_add_u32 %[am], %[np], 9, %[col]\n\t" /* where that half lives: its index is the path up to the record's first decision */ \
-            "v_cndmask_b32 v208, 1, %[k64k1], vcc\n\t" /* +1 on the half's count, +1 for bL/bR if left at the middle decision */ \
-            "v_cndmask_b32 %[t2], 1, %[k64k], vcc\n\t" \
-            "v_cndmask_b32 v209, 0, %[t2], %[mc]\n\t" \
-            GPUAR_LDS_ADD("ds_add_u64 %[am], v[208:209]\n\t")
-#ifdef GPUAR_EXP_NO_WAIT1      /* (timing experiments only: garbage out) */
-#define GPUAR_WAIT1 ""
-#else
-#define GPUAR_WAIT1 "s_waitcnt lgkmcnt(1)\n\t"
-#endif
-#ifdef GPUAR_EXP_NO_WAIT2
-#define GPUAR_WAIT2 ""
-#else
-#define GPUAR_WAIT2 "s_waitcnt lgkmcnt(1)\n\t"
-#endif
-#define GPUAR_BC_MID(WAIT1) \
-            WAIT1 /* read #1 is back (LDS completes in order: at most the write behind it is left) */ \
+#define GPUAR_MID_WALK \
          /* ---- mid record: v200 = aR | bR << 16, v201 = cRR | cRL << 16 (right half), v202 = a | bL << 16, v203 = cLR | cLL << 16 (left half) */ \
             "v_mul_u32_u24_sdwa %[t0], v202, %[rng]" GPUAR_SDWA_W0 \
             "v_sub_co_u32 %[t1], %[ma], %[R], %[t0]\n\t" \
@@ -1393,17 +1283,23 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
             "v_cndmask_b32_sdwa %[t2], %[cc], %[cc], vcc" GPUAR_SDWA_HALVES \
             "v_mul_u32_u24 %[t0], %[t2], %[rng]\n\t" \
             "v_sub_co_u32 %[t1], %[mc], %[R], %[t0]\n\t" \
-            GPUAR_MIN_BEFORE_READ("v_min_u32 %[R], %[R], %[t1]\n\t") \
             "v_addc_co_u32 %[t3], %[mj], %[np], %[np], vcc\n\t" \
-            GPUAR_MID_WRITEBACK
+            "v_addc_co_u32 %[t3], %[mj], %[t3], %[t3], %[mc]\n\t" \
+            "v_lshl_add_u32 %[oaddr], %[t3], 10, %[collow]\n\t" \
+            "ds_read2_b64 v[212:215], %[oaddr] offset1:64\n\t" /* READ #2: low record */ \
+            "v_min_u32 %[R], %[R], %[t1]\n\t" \
+         /* ---- the mid half takes its increments by one 64-bit LDS add in the shadow of read #2 */ \
+            "v_lshl_add_u32 %[am], %[np], 9, %[col]\n\t" /* where that half lives: its index is the path up to the record's first decision */ \
+            "v_cndmask_b32 v208, 1, %[k64k1], vcc\n\t" /* +1 on the half's count, +1 for bL/bR if left at the middle decision */ \
+            "v_cndmask_b32 %[t2], 1, %[k64k], vcc\n\t" \
+            "v_cndmask_b32 v209, 0, %[t2], %[mc]\n\t" \
+            "ds_add_u64 %[am], v[208:209]\n\t"
 
 // OWN_ADDRESS: the address of the step's own low half, formed at once (GPUAR_LOW_ADDRESS_NOW: the last symbol of a loop body)
-// or left to the next step's first shadow (empty; GPUAR_A_SHADOW_DEFERRED)
+// or left to the next step's first shadow (empty; GPUAR_SHADOW_DEFERRED)
 #define GPUAR_LOW_ADDRESS_NOW \
             "v_lshl_add_u32 %[oaddr], %[c6], 9, %[collow]\n\t" /* the low half that takes the increments (in the next step's shadow) */
-#define GPUAR_BC_LOW(OWN_ADDRESS, MUL) GPUAR_BC_LOW_WALK_TEXT(OWN_ADDRESS) GPUAR_BC_LOW_INTERVAL(MUL)
-#define GPUAR_BC_LOW_WALK_TEXT(OWN_ADDRESS) \
-            GPUAR_WAIT2 /* read #2 is back (behind it: the mid half's LDS add, perhaps the stream reader's dword) */ \
+#define GPUAR_LOW_WALK(OWN_ADDRESS) \
          /* ---- low record: v212 = aR | bR << 16, v213 = cRR | cRL << 16 (right half), v214 = a | bL << 16, v215 = cLR | cLL << 16 (left half). \
                  Next to the walk (three decisions on the scaled remainder) the symbol's own COUNT is picked out of the half: \
                  under the chosen side there are `count` symbols (a or aR), `child` of them left of the child node, the \
@@ -1433,7 +1329,7 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
             "v_sub_u32 %[t3], %[ps], %[t2]\n\t" /* the right leaf */ \
             "v_min_u32 %[R], %[R], %[t1]\n\t" \
             "v_cndmask_b32 %[t3], %[t3], %[t2], vcc\n\t" /* cnt(symbol) */
-#define GPUAR_BC_LOW_INTERVAL(MUL) /* MUL: the name of the operand that holds this symbol's reciprocal multiplier */ \
+#define GPUAR_LOW_INTERVAL(MUL) /* MUL: the name of the operand that holds this symbol's reciprocal multiplier */ \
          /* ---- applySymbolRange (:256-299) and the renormalisation (:787-836) */ \
             "v_sub_u32 %[t0], %[R0], %[R]\n\t" /* cumLo * range */ \
             "v_mad_u32_u24 %[t1], %[t3], %[rng], %[t0]\n\t" /* cumHi * range = cumLo * range + cnt * range */ \
@@ -1453,7 +1349,7 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
 // The end of the step: the grandchild's increment sits between the SDWA write of kff and its reader; the last instruction
 // but one files the symbol: all eight complemented path bits = 2 * (the first seven) + the last decision's borrow, written
 // straight into byte J of the output word (SDWA dst_sel, the other bytes preserved) -- no shift-or per symbol.
-#define GPUAR_BC_LOW_END(N) /* N: the name of the operand this step leaves its bit count in ("ne" in an even step, "no" in an odd one) */ \
+#define GPUAR_STEP_END(N) /* N: the name of the operand this step leaves its bit count in ("ne" in an even step, "no" in an odd one) */ \
             "v_cndmask_b32 v205, 0, %[ti], vcc\n\t" \
             "v_lshlrev_b32 %[t2], %[e], %[kff]\n\t" \
             "v_lshrrev_b32 %[t2], 31, %[t2]\n\t" \
@@ -1485,80 +1381,25 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
 // reader 26.4-26.5 ms): the whole reader in the even step's second LDS shadow 25.8; split between the two steps' second shadows
 // 25.8; the even step's subtraction moved to its first shadow 25.6; the odd step's part in ITS first shadow as well 25.2-25.3
 // (kept); everything in first shadows 25.7.  A shadow hides three or four instructions, not ten.
-#define GPUAR_STREAM_PART_A \
+#define GPUAR_STREAM_EVEN_TAKE /* the even step's first shadow */ \
             "v_add_u32 %[pc], %[no], %[ne]\n\t" /* the bits of the two symbols since the last refill: <= 32 */ \
             "v_sub_co_u32 %[raw], %[sb], %[rem], %[pc]\n\t" /* borrow: w0 ran out */ \
             "v_and_b32 %[rem], 31, %[raw]\n\t"
-#define GPUAR_STREAM_PART_B \
+#define GPUAR_STREAM_EVEN_WINDOW /* the even step's second shadow */ \
             "v_perm_b32 %[pa], 0, %[ahead], %[bsw]\n\t" /* big-endian order restored */ \
             "v_cndmask_b32 %[w0], %[w0], %[w1], %[sb]\n\t" \
             "v_cndmask_b32 %[w1], %[w1], %[pa], %[sb]\n\t" \
             "v_alignbit_b32 v216, %[w0], %[w1], %[rem]\n\t" /* the next 32 stream bits */
-#define GPUAR_STREAM_PART_C \
+#define GPUAR_STREAM_ODD_MOVE /* the odd step's first shadow: two LDS operations behind read #1 then, not one */ \
             "v_lshrrev_b32 %[pb], 31, %[raw]\n\t" /* the difference before it was wrapped: negative where w0 ran out */ \
             "v_lshl_add_u32 %[next], %[pb], 8, %[next]\n\t" \
             "v_and_or_b32 %[pc], %[next], %[kf00], %[ring]\n\t" /* ring + 256 * (dword index mod 16) */ \
-            GPUAR_LDS_STREAM_READ("ds_read_b32 %[ahead], %[pc]\n\t")
-#ifndef GPUAR_DEC_STREAM_PLACE
-#define GPUAR_DEC_STREAM_PLACE 6
-#endif
-#define GPUAR_STREAM_ODD_EARLY ""
-#define GPUAR_STREAM_ODD_TEXT ""
-#define GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY GPUAR_WAIT1
-#define GPUAR_WAIT1_GPUAR_STREAM_EVEN_EARLY GPUAR_WAIT1
-#ifdef GPUAR_EXP_NO_STREAM               /* (timing experiments only, garbage out: no stream instruction in any step) */
-#define GPUAR_STREAM_EVEN_EARLY ""
-#define GPUAR_STREAM_EVEN_TEXT ""
-#elif GPUAR_DEC_STREAM_PLACE == 2        /* (A/B) all of it in the even step's second shadow */
-#define GPUAR_STREAM_EVEN_EARLY ""
-#define GPUAR_STREAM_EVEN_TEXT GPUAR_STREAM_PART_A GPUAR_STREAM_PART_B GPUAR_STREAM_PART_C
-#elif GPUAR_DEC_STREAM_PLACE == 4        /* (A/B) the reader's move and the read of `ahead` one step later, in the ODD step's second shadow */
-#define GPUAR_STREAM_EVEN_EARLY ""
-#define GPUAR_STREAM_EVEN_TEXT GPUAR_STREAM_PART_A GPUAR_STREAM_PART_B
-#undef GPUAR_STREAM_ODD_TEXT
-#define GPUAR_STREAM_ODD_TEXT GPUAR_STREAM_PART_C
-#elif GPUAR_DEC_STREAM_PLACE == 5        /* (A/B) as 4, with the subtraction in the even step's first shadow */
-#define GPUAR_STREAM_EVEN_EARLY GPUAR_STREAM_PART_A
-#define GPUAR_STREAM_EVEN_TEXT GPUAR_STREAM_PART_B
-#undef GPUAR_STREAM_ODD_TEXT
-#define GPUAR_STREAM_ODD_TEXT GPUAR_STREAM_PART_C
-#elif GPUAR_DEC_STREAM_PLACE == 6        /* the subtraction in the even step's first shadow, the selects and the window in its second; the odd step's part in ITS first shadow (two LDS operations behind read #1) */
-#define GPUAR_STREAM_EVEN_EARLY GPUAR_STREAM_PART_A
-#define GPUAR_STREAM_EVEN_TEXT GPUAR_STREAM_PART_B
-#undef GPUAR_STREAM_ODD_EARLY
-#define GPUAR_STREAM_ODD_EARLY GPUAR_STREAM_PART_C
-#undef GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY
-#define GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY "s_waitcnt lgkmcnt(2)\n\t"
-#elif GPUAR_DEC_STREAM_PLACE == 10       /* (A/B) as 6, the byte swap in the even step's first shadow as well */
-#define GPUAR_STREAM_EVEN_EARLY GPUAR_STREAM_PART_A "v_perm_b32 %[pa], 0, %[ahead], %[bsw]\n\t"
-#define GPUAR_STREAM_EVEN_TEXT \
-            "v_cndmask_b32 %[w0], %[w0], %[w1], %[sb]\n\t" \
-            "v_cndmask_b32 %[w1], %[w1], %[pa], %[sb]\n\t" \
-            "v_alignbit_b32 v216, %[w0], %[w1], %[rem]\n\t"
-#undef GPUAR_STREAM_ODD_EARLY
-#define GPUAR_STREAM_ODD_EARLY GPUAR_STREAM_PART_C
-#undef GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY
-#define GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY "s_waitcnt lgkmcnt(2)\n\t"
-#elif GPUAR_DEC_STREAM_PLACE == 7        /* (A/B) everything in first shadows */
-#define GPUAR_STREAM_EVEN_EARLY GPUAR_STREAM_PART_A GPUAR_STREAM_PART_B
-#define GPUAR_STREAM_EVEN_TEXT ""
-#undef GPUAR_STREAM_ODD_EARLY
-#define GPUAR_STREAM_ODD_EARLY GPUAR_STREAM_PART_C
-#undef GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY
-#define GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY "s_waitcnt lgkmcnt(2)\n\t"
-#elif GPUAR_DEC_STREAM_PLACE == 9        /* (A/B) the even step's part in its second shadow, the odd step's in its first */
-#define GPUAR_STREAM_EVEN_EARLY ""
-#define GPUAR_STREAM_EVEN_TEXT GPUAR_STREAM_PART_A GPUAR_STREAM_PART_B
-#undef GPUAR_STREAM_ODD_EARLY
-#define GPUAR_STREAM_ODD_EARLY GPUAR_STREAM_PART_C
-#undef GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY
-#define GPUAR_WAIT1_GPUAR_STREAM_ODD_EARLY "s_waitcnt lgkmcnt(2)\n\t"
-#endif
+            "ds_read_b32 %[ahead], %[pc]\n\t"
 
 // lo' : off' = (((lo + dn) : (off - dn)) : window) << n, upper half, with lo's top bit cleared: ONE 64-bit shift moves both
 // (v217 = lo << 16 | off, the window in v216).  What leaves lo at the top falls off the register; (off - dn + 1) << n
 // <= width << n = range' <= 2^16 keeps the lower half inside its 16 bits; bit 31 is the last underflow position
-// (lo' = (a << n) & 0x7FFF) and is cleared in the NEXT step's LDS shadow (GPUAR_A_SHADOW; decode_wave clears it once
+// (lo' = (a << n) & 0x7FFF) and is cleared in the NEXT step's LDS shadow (GPUAR_SHADOW_*; decode_wave clears it once
 // more behind the last step).
 #define GPUAR_OFF_TEXT(N) \
             "v_lshlrev_b64 v[216:217], %[" N "], v[216:217]\n\t"
@@ -1582,35 +1423,29 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
 // J: the byte of its output word the step files its symbol in; MUL, WORD: the NAMES of the operands that hold the symbol's
 // reciprocal multiplier and its output word (a run of eight steps is ONE asm statement, below); the step leaves the number of stream
 // bits it took in "ne" (even steps) or "no" (odd steps): the even step's refill needs both.
-#define GPUAR_N_EVEN "ne"
-#define GPUAR_N_ODD "no"
-#ifdef GPUAR_EXP_NO_SEARCH      /* (timing experiments only, garbage out: the step WITHOUT its symbol search -- no decision, no record read, no
-                                   increment, no register-node update: what every decoder of this format pays per symbol whatever finds the symbol,
-                                   profiles/r06_latency_decoder_prototype.txt) */
-#define GPUAR_STEP_TEXT(SHADOW, PARITY, OWN_ADDRESS, J, MUL, WORD) \
-            GPUAR_HEAD_R0 GPUAR_HEAD_R0_ADD GPUAR_TOTAL_STEP \
-            "v_lshrrev_b32 %[R], 1, %[R0]\n\t" \
-            "v_mov_b32 %[t3], 1\n\t" \
-            "v_mov_b32 %[c7], %[c6]\n\t" \
-            GPUAR_STREAM_##PARITY##_EARLY GPUAR_STREAM_##PARITY##_TEXT GPUAR_BC_LOW_INTERVAL(MUL) GPUAR_BC_LOW_END(GPUAR_N_##PARITY) \
-            GPUAR_FILE_SYMBOL(J, WORD) GPUAR_OFF_TEXT(GPUAR_N_##PARITY)
-#else
-#define GPUAR_STEP_TEXT(SHADOW, PARITY, OWN_ADDRESS, J, MUL, WORD) \
-    GPUAR_A_HEAD SHADOW GPUAR_TOTAL_STEP_EARLY GPUAR_NODES_##PARITY##_EARLY GPUAR_STREAM_##PARITY##_EARLY GPUAR_BC_MID(GPUAR_WAIT1_GPUAR_STREAM_##PARITY##_EARLY) \
-    GPUAR_STREAM_##PARITY##_TEXT GPUAR_NODES_##PARITY##_LATE GPUAR_TOTAL_STEP_LATE GPUAR_BC_LOW(OWN_ADDRESS, MUL) GPUAR_BC_LOW_END(GPUAR_N_##PARITY) \
-    GPUAR_FILE_SYMBOL(J, WORD) GPUAR_OFF_TEXT(GPUAR_N_##PARITY)
-#endif
-#ifdef GPUAR_DEC_NO_DEFER      /* (A/B builds: every step forms its own address, as in rounds 2-4a) */
-#define GPUAR_STEP_FIRST(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_PLAIN, EVEN, GPUAR_LOW_ADDRESS_NOW, J, MUL, WORD)
-#define GPUAR_STEP_EVEN(J, MUL, WORD) GPUAR_STEP_FIRST(J, MUL, WORD)
-#define GPUAR_STEP_ODD(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_PLAIN, ODD, GPUAR_LOW_ADDRESS_NOW, J, MUL, WORD)
-#define GPUAR_STEP_LAST(J, MUL, WORD) GPUAR_STEP_ODD(J, MUL, WORD)
-#else
-#define GPUAR_STEP_FIRST(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_PLAIN, EVEN, , J, MUL, WORD)
-#define GPUAR_STEP_EVEN(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_DEFERRED, EVEN, , J, MUL, WORD)
-#define GPUAR_STEP_ODD(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_DEFERRED, ODD, , J, MUL, WORD)
-#define GPUAR_STEP_LAST(J, MUL, WORD) GPUAR_STEP_TEXT(GPUAR_A_SHADOW_DEFERRED, ODD, GPUAR_LOW_ADDRESS_NOW, J, MUL, WORD)
-#endif
+// The two steps, their pieces in the order they execute.  SHADOW: GPUAR_SHADOW_PLAIN or _DEFERRED; OWN_ADDRESS: GPUAR_LOW_ADDRESS_NOW
+// or empty.  LDS operations complete in order, so "read #N is back" is a wait for all but the operations issued behind it.
+#define GPUAR_STEP_EVEN_TEXT(SHADOW, OWN_ADDRESS, J, MUL, WORD) \
+    GPUAR_STEP_HEAD                                /* depths 0 and 1, READ #1 */ \
+    SHADOW GPUAR_TOTAL_STEP GPUAR_REG_NODES GPUAR_STREAM_EVEN_TAKE \
+    "s_waitcnt lgkmcnt(1)\n\t"                     /* read #1 is back; behind it: the low half's LDS add */ \
+    GPUAR_MID_WALK                                 /* mid walk, READ #2, the mid half's LDS add */ \
+    GPUAR_STREAM_EVEN_WINDOW \
+    "s_waitcnt lgkmcnt(1)\n\t"                     /* read #2 is back; behind it: the mid half's LDS add */ \
+    GPUAR_LOW_WALK(OWN_ADDRESS) GPUAR_LOW_INTERVAL(MUL) GPUAR_STEP_END("ne") GPUAR_FILE_SYMBOL(J, WORD) GPUAR_OFF_TEXT("ne")
+#define GPUAR_STEP_ODD_TEXT(SHADOW, OWN_ADDRESS, J, MUL, WORD) \
+    GPUAR_STEP_HEAD \
+    SHADOW GPUAR_TOTAL_STEP GPUAR_STREAM_ODD_MOVE \
+    "s_waitcnt lgkmcnt(2)\n\t"                     /* read #1 is back; behind it: the low half's LDS add AND the stream reader's dword */ \
+    GPUAR_MID_WALK \
+    GPUAR_REG_NODES \
+    "s_waitcnt lgkmcnt(1)\n\t"                     /* read #2 is back; behind it: the mid half's LDS add */ \
+    GPUAR_LOW_WALK(OWN_ADDRESS) GPUAR_LOW_INTERVAL(MUL) GPUAR_STEP_END("no") GPUAR_FILE_SYMBOL(J, WORD) GPUAR_OFF_TEXT("no")
+// (every step forming its own address, as in rounds 2-4a: 26.64 against 26.42 ms, see GPUAR_SHADOW_DEFERRED)
+#define GPUAR_STEP_FIRST(J, MUL, WORD) GPUAR_STEP_EVEN_TEXT(GPUAR_SHADOW_PLAIN, , J, MUL, WORD)
+#define GPUAR_STEP_EVEN(J, MUL, WORD) GPUAR_STEP_EVEN_TEXT(GPUAR_SHADOW_DEFERRED, , J, MUL, WORD)
+#define GPUAR_STEP_ODD(J, MUL, WORD) GPUAR_STEP_ODD_TEXT(GPUAR_SHADOW_DEFERRED, , J, MUL, WORD)
+#define GPUAR_STEP_LAST(J, MUL, WORD) GPUAR_STEP_ODD_TEXT(GPUAR_SHADOW_DEFERRED, GPUAR_LOW_ADDRESS_NOW, J, MUL, WORD)
 
 // LDS of a decoder workgroup (one wavefront): the 64 models and the 64 stream rings, 40 KiB -> four per CU.
 constexpr uint32_t kRingPieces = 4;                        // 16-byte pieces per lane: 64 bytes of stream
@@ -1651,7 +1486,7 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
     register uint32_t offr asm("v217");        // lo << 16 | (code - lo): v216:v217 is the pair the 64-bit shift works on, and
     offr = dec.off | (dec.lo << 16);           // lower bound and code offset move through the step as ONE register
     // the stream bits the last two symbols took and the reader has not stepped over yet: the even step's and the odd step's, a
-    // register each (GPUAR_STREAM_EVEN_EARLY takes both off `rem` at once)
+    // register each (GPUAR_STREAM_EVEN_TAKE takes both off `rem` at once)
     uint32_t n_even = 0, n_odd = dec.owed_bits;
     uint32_t total_v = 256u;                   // the model's total as a vector register (the same in every lane): GPUAR_TOTAL_STEP
     uint32_t rem_raw = 0;                      // the even step's `rem` before it was wrapped into 0..31: negative where w0 ran out -- the odd step
@@ -1735,36 +1570,16 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
 // knows them as the pinned variables m<SET>0..7) -- where the step's two v_mul_hi_u32 take it from directly.  The
 // loads land before the next phase's s_waitcnt vmcnt(0), one whole run before they are used.  (Rounds 2-3 kept symbol j's
 // multiplier in lane j of ONE register per block of 64 and fetched it with a v_readlane per symbol.)
-// (timing experiments only, garbage out: the ring phase without its wait for the vector memory, without its LDS writes, without
-// the multipliers' loads -- profiles/r06_decode_step_budget.txt, section 3b)
-#ifdef GPUAR_EXP_NO_RING_VMCNT
-#define GPUAR_RING_VMCNT ""
-#else
-#define GPUAR_RING_VMCNT "s_waitcnt vmcnt(0)\n\t"
-#endif
-#ifdef GPUAR_EXP_NO_RING_WRITES
-#define GPUAR_RING_WRITES(TEXT) ""
-#else
-#define GPUAR_RING_WRITES(TEXT) TEXT
-#endif
-#ifdef GPUAR_EXP_NO_RING_MUL
-#define GPUAR_RING_MUL(TEXT) ""
-#else
-#define GPUAR_RING_MUL(TEXT) TEXT
-#endif
 // (the phase is the tail of its run's asm statement -- GPUAR_DECODE_RUN8 --: it shares the run's operands `next`, `ring`, `t2`, `sx`)
-#ifdef GPUAR_EXP_NO_RING        /* (timing experiments only, garbage out: no ring phase at all) */
-#define GPUAR_RING_PHASE_TEXT(TUPLE_LO, TUPLE_HI) ""
-#else
 #define GPUAR_RING_PHASE_TEXT(TUPLE_LO, TUPLE_HI)                                                                    \
             "v_lshrrev_b32 %[rt], 6, %[next]\n\t"                                                                    \
             "v_sub_u32 %[rt], %[fill], %[rt]\n\t"                                                                    \
             "v_cmp_gt_u32 vcc, 49, %[rt]\n\t" /* (first: the scalar unit reads this mask five instructions later) */ \
-            GPUAR_RING_VMCNT                                                                                         \
-            GPUAR_RING_WRITES("ds_write2st64_b32 %[slot], v220, v221 offset1:1\n\t"                                  \
-                              "ds_write2st64_b32 %[slot], v222, v223 offset0:2 offset1:3\n\t")                        \
-            GPUAR_RING_MUL("global_load_dwordx4 " TUPLE_LO ", %[zero], %[mulbase] offset:%[roff]\n\t"                \
-                           "global_load_dwordx4 " TUPLE_HI ", %[zero], %[mulbase] offset:%[roff]+16\n\t")              \
+            "s_waitcnt vmcnt(0)\n\t"                                                                                 \
+            "ds_write2st64_b32 %[slot], v220, v221 offset1:1\n\t"                                                    \
+            "ds_write2st64_b32 %[slot], v222, v223 offset0:2 offset1:3\n\t"                                          \
+            "global_load_dwordx4 " TUPLE_LO ", %[zero], %[mulbase] offset:%[roff]\n\t"                               \
+            "global_load_dwordx4 " TUPLE_HI ", %[zero], %[mulbase] offset:%[roff]+16\n\t"                            \
             "s_and_saveexec_b64 %[sx], vcc\n\t"                                                                      \
             "v_min_u32 %[rt], %[fill], %[lastp]\n\t"                                                                 \
             "global_load_dwordx4 v[220:223], %[rt], %[base]\n\t"                                                     \
@@ -1772,7 +1587,6 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
             "v_lshl_add_u32 %[slot], %[t2], 6, %[ring]\n\t"                                                          \
             "v_add_u32 %[fill], 16, %[fill]\n\t"                                                                     \
             "s_or_b64 exec, exec, %[sx]"
-#endif
 
     // The per-symbol reciprocal multipliers (wave-uniform) reach the symbol step WITHOUT scalar loads and -- since round 4 --
     // without a v_readlane: the ring phase above fetches the eight of the run after next into registers by vector loads
@@ -1826,11 +1640,6 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
 // of its own by name -- rounds 1-3 looped over runs of eight and filed each word into a register array by index (a
 // v_not, an s_set_gpr_idx_on / v_mov / s_set_gpr_idx_off and a scalar add per word, 1.5 issue slots per symbol, plus
 // the loop's own six per eight symbols).
-#ifdef GPUAR_EXP_NO_STORES      /* (timing experiments only: the decoded bytes never leave; a condition the compiler cannot fold) */
-#define GPUAR_EXP_STORES (len_max > 0x7FFFFFF0u)
-#else
-#define GPUAR_EXP_STORES true
-#endif
 #define GPUAR_DECODE_BLOCK                                                                                           \
     {                                                                                                                \
         /* the shift that goes with the multipliers: floor(log2(total)) - 1, the same for all 64 totals of a block */ \
@@ -1852,7 +1661,7 @@ __device__ __forceinline__ void decode_wave(uint8_t *col, uint8_t *ring, const u
             /* complemented, in k0..k7 (the path bits are the COMPLEMENTED symbol bits)                                     */ \
             if (half == 0u) {                                                                                        \
                 k0 = ~w0, k1 = ~w1, k2 = ~w2, k3 = ~w3, k4 = ~w4, k5 = ~w5, k6 = ~w6, k7 = ~w7;                      \
-            } else if (GPUAR_EXP_STORES) {                                                                           \
+            } else {                                                                                                 \
                 uint4 *dst = reinterpret_cast<uint4 *>(out + i);                                                     \
                 dst[0] = make_uint4(k0, k1, k2, k3);                                                                 \
                 dst[1] = make_uint4(k4, k5, k6, k7);                                                                 \
@@ -2131,10 +1940,7 @@ scan_offsets_kernel(const uint8_t *__restrict__ slots, uint32_t n_packets, uint6
 // bench workload, 5.0 TB/s read + write; with a workgroup per packet (measured, uniform / text 8 GiB: 192 threads 3.37 /
 // 2.14 ms, 256: 3.00 / 2.03, 320: 2.90 / 2.15, 384: 2.93 / 2.17, 448: 3.03 / 2.25, 576 = one quad per thread: 3.26 /
 // 2.70) it is 5.76 TB/s = 72 % of the datasheet's 8 TB/s, 93 % of what a plain copy reaches on this part (6.18 TB/s).
-#ifndef GPUAR_GATHER_THREADS
-#define GPUAR_GATHER_THREADS 256
-#endif
-constexpr uint32_t kGatherThreads = GPUAR_GATHER_THREADS;
+constexpr uint32_t kGatherThreads = 256;
 __global__ void __launch_bounds__(kGatherThreads)
 gather_kernel(const uint8_t *__restrict__ slots, const uint64_t *__restrict__ offsets, uint32_t n_packets,
               uint8_t *__restrict__ stream) {
@@ -2718,11 +2524,7 @@ const char *gpuar_hip_error_string(int code) {
     }
 }
 
-#ifdef GPUAR_EXPERIMENT_BUILD
-const char *gpuar_hip_version(void) { return "gpuar-hip 0.2 gfx950 EXPERIMENT BUILD (timing switches: output may be garbage)"; }
-#else
 const char *gpuar_hip_version(void) { return "gpuar-hip 0.2 gfx950"; }
-#endif
 
 int gpuar_hip_abi_version(void) { return GPUAR_HIP_ABI_VERSION; }
 

@@ -579,17 +579,8 @@ struct CoderLane {
 // is a placeholder that lands on the packet's header dword, which finish() overwrites.
 // Pinned against the oracle on the CPU like every other lane program (tests/test_lane_emulation.py).
 // ---------------------------------------------------------------------------
-// Cache policy bits of the coder's dword stores (A/B builds -DGPUAR_STORE_POLICY_ID=1, 2, 3: " nt", " sc1", " sc0 sc1"; profiles/r05_encoder_attribution.txt section 3:
-// none of them brings the L2's write-backs nearer to the bytes written, the default is kept)
-#if !defined(GPUAR_STORE_POLICY_ID) || GPUAR_STORE_POLICY_ID == 0
-#define GPUAR_STORE_POLICY ""
-#elif GPUAR_STORE_POLICY_ID == 1
-#define GPUAR_STORE_POLICY " nt"
-#elif GPUAR_STORE_POLICY_ID == 2
-#define GPUAR_STORE_POLICY " sc1"
-#else
-#define GPUAR_STORE_POLICY " sc0 sc1"
-#endif
+// Cache policy bits on the coder's dword stores (" nt", " sc1", " sc0 sc1"; profiles/r05_encoder_attribution.txt section 3): none
+// of them brings the L2's write-backs nearer to the bytes written, the default is kept
 struct CarryCoderLane {
     uint32_t wl, wh;     // the window w = wh:wl
     uint32_t range;      // hi - lo + 1  (2^14 < range <= 2^16 between symbols)
@@ -684,13 +675,12 @@ struct CarryCoderLane {
             "v_cmp_ge_u32 %[rare], %[cache], %[key]\n\t"                 /* (bits of lanes that do not store stay 0) */
             "v_min_u32 %[ta], %[at], %[last]\n\t"
             "v_perm_b32 %[tw], 0, %[sent], %[sel]\n\t"
-            "global_store_dword %[ta], %[tw], %[base]" GPUAR_STORE_POLICY "\n\t"
+            "global_store_dword %[ta], %[tw], %[base]\n\t"
             "v_bfe_u32 %[wl], %[wl], 0, %[held]\n\t"                     /* the window keeps what is below the dword that left */
             "v_mov_b32 %[wh], 0\n\t"
             "v_add_u32 %[at], 4, %[at]\n\t"
             "v_add_u32 %[held], -32, %[held]\n\t"
             "s_or_b64 exec, exec, %[sx]\n\t"
-#ifndef GPUAR_CARRY_NO_RARE        // (timing experiments only: without the rare path the kernel is WRONG for dwords of 32 ones)
             "s_cmp_eq_u64 %[rare], 0\n\t"
             "s_cbranch_scc1 .Lgpuar_common_%=\n\t"
             "s_mov_b64 %[sx], exec\n\t"
@@ -709,7 +699,7 @@ struct CarryCoderLane {
             "s_and_b64 exec, exec, vcc\n\t"
             "s_cbranch_execz .Lgpuar_filled_%=\n\t"
             "v_min_u32 %[ta], %[at], %[last]\n\t"
-            "global_store_dword %[ta], %[tw], %[base]" GPUAR_STORE_POLICY "\n\t"
+            "global_store_dword %[ta], %[tw], %[base]\n\t"
             "v_add_u32 %[at], 4, %[at]\n\t"
             "v_add_u32 %[nff], -1, %[nff]\n\t"
             "s_branch .Lgpuar_fill_%=\n\t"
@@ -719,7 +709,6 @@ struct CarryCoderLane {
             "v_cndmask_b32 %[key], 0, -1, vcc\n\t"
             "s_mov_b64 exec, %[sx]\n\t"
             ".Lgpuar_common_%=:"
-#endif
             : [wl] "+v"(wl), [wh] "+v"(wh), [at] "+v"(at), [held] "+v"(held), [cache] "+v"(cache), [nff] "+v"(nff), [key] "+v"(key),
               [over] "=&v"(over), [sent] "=&v"(sent), [ta] "=&v"(t_addr), [tw] "=&v"(t_swapped),
               [sx] "=&s"(saved), [rare] "=&s"(rare), [und] "=&s"(undecided)

@@ -106,10 +106,6 @@ def load() -> C.CDLL:
     lib.gpuar_hip_verify_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
-    # a build with timing switches (tools/exp_build.sh -DGPUAR_EXP_...) decodes / encodes garbage by design: it is loaded only from
-    # where the timing tools put it (LIB_PATH pointed there by --lib), never as the product library
-    if b"EXPERIMENT" in lib.gpuar_hip_version() and os.path.abspath(LIB_PATH) == os.path.join(_HERE, "lib", "libgpuar_hip.so"):
-        raise GpuarError(f"{LIB_PATH} is an experiment build ({lib.gpuar_hip_version().decode()}): rebuild the product library with make")
     _lib = lib
     return lib
 

@@ -4,7 +4,7 @@
 // model update would issue -- real multiplies, borrows, DPP all-reduces over 8 lanes, the dependent LDS row read and the row's
 // write-back -- on synthetic counts, timed by the kernel's own clock, one wavefront per SIMD on the whole chip (1024 workgroups
 // with 40 KiB of LDS each), next to the lane-per-packet search's cost taken from the real kernel (a build of decode_slots_kernel
-// WITHOUT its search, -DGPUAR_EXP_NO_SEARCH).  Nothing here decodes anything: it prices the stream.
+// WITHOUT its search: a piece-removal build, retired since and kept in git history).  Nothing here decodes anything: it prices the stream.
 //
 // Model held per packet (8 lanes, lane j of the group):
 //   level 1: P1a, P1b = number of symbols in buckets below 2j, 2j + 1 (16 buckets of 16 symbols), in registers;
