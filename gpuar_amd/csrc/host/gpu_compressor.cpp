@@ -883,6 +883,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
     } catch (...) {
         if (::ftruncate(out_fd, 0) != 0) {}      // a failed job leaves an empty file, not a half-written one
         closeFiles();
+        dropTimes();
         throw;
     }
     io_timer.stop();
@@ -920,6 +921,12 @@ void GPUCompressor::finishTimes(CompressionInfo &info) {
     }
     info.processTime = busiest;
     info.ioTime = std::max(0.0, io_timer.value() - info.processTime);
+}
+
+// A job that throws never reaches finishTimes: the kernel spans its lanes noted so far would stay in their `busy` lists and be
+// counted into the processTime of the next job that reuses the lanes (an object outlives a failed job; the CLI does not).
+void GPUCompressor::dropTimes() {
+    for (DeviceBuffers *b : buffers) b->busy.clear();
 }
 
 // One event per device that every lane of the device measures its kernel intervals against.
@@ -1256,6 +1263,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
     } catch (...) {
         if (::ftruncate(out_fd, 0) != 0) {}      // a failed job leaves an empty file, not a half-written one
         closeFiles();
+        dropTimes();
         throw;
     }
     io_timer.stop();

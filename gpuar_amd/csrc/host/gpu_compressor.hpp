@@ -50,6 +50,7 @@ class GPUCompressor : public Compressor {
     template <typename Work, typename OnFailure>
     void runLanes(Work &&work, OnFailure &&on_failure);
     void finishTimes(CompressionInfo &info);
+    void dropTimes();                          // a failed job's kernel spans are nobody's: not the next job's
     void *epochOf(size_t device_index);
 };
 

@@ -9,7 +9,8 @@ namespace gip {
 class ProgressMonitor {
   public:
     ProgressMonitor() { reset(); }
-    void reset() { currentRatio = 0; quiet = false; }
+    // (every job calls this: it restarts the line and, like the reference's, nothing else -- `quiet` is the caller's setting)
+    void reset() { currentRatio = 0; }
     void setQuiet(bool q) { quiet = q; }
 
     // prints "10%..", "20%.." ... whenever the decile changes (src/progress_monitor.cpp:17-33)
@@ -27,7 +28,7 @@ class ProgressMonitor {
 
   private:
     double currentRatio;
-    bool quiet;
+    bool quiet = false;
 };
 
 }  // namespace gip

@@ -332,7 +332,7 @@ def test_gpu_cli_survives_an_input_cut_short_under_its_mapping(tmp_path):
     short read (src/gpu_compressor.cpp:146-150: "Read input file failed"; decoding: "Invalid file length", :299-307), exit
     code 1, and an empty output file.  GPUAR_TEST_HOLD_AFTER_MAP_MS makes the race deterministic: the CLI sleeps between
     mapping its input and reading it, and the file is cut in that window."""
-    import time
+    import threading
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     src, gip, out = tmp_path / "in.dat", tmp_path / "whole.gip", tmp_path / "out.bin"
@@ -343,18 +343,37 @@ def test_gpu_cli_survives_an_input_cut_short_under_its_mapping(tmp_path):
     env = dict(os.environ, GPUAR_TEST_HOLD_AFTER_MAP_MS="1500")
     for mode, victim, keep, message in (("c", src, 5 << 20, "Read input file failed"), ("d", gip, whole // 3, "Invalid file length")):
         out.write_bytes(b"stale")
-        p = subprocess.Popen([CLI, mode, f"--in={victim}", f"--out={out}", "--batch=2048"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
-                             text=True, env=env)
-        # the CLI says "[gpuar] input mapped" once it has sized and mapped the file, then holds: cut the file THEN, however long
-        # ROCm's start-up took on this box (a fixed sleep raced it)
-        seen = []
-        for _ in range(50):                              # (the HIP runtime or libdrm may say something of their own first)
-            seen.append(p.stderr.readline())
-            if "input mapped" in seen[-1] or not seen[-1]:
-                break
-        assert "input mapped" in seen[-1], (mode, seen)
-        os.truncate(victim, keep)
-        stdout, stderr = p.communicate(timeout=600)
+        # stdout goes to a file (nobody reads it while the job runs: a pipe could fill), stderr is read on a helper thread,
+        # and every wait has a deadline after which the child is killed
+        with open(tmp_path / f"stdout.{mode}", "w+") as stdout_file:
+            p = subprocess.Popen([CLI, mode, f"--in={victim}", f"--out={out}", "--batch=2048"], stdout=stdout_file, stderr=subprocess.PIPE,
+                                 text=True, env=env)
+            # the CLI says "[gpuar] input mapped" once it has sized and mapped the file, then holds: cut the file THEN, however long
+            # ROCm's start-up took on this box (a fixed sleep raced it)
+            seen, mapped = [], threading.Event()
+
+            def read_stderr():
+                for line in p.stderr:                        # (the HIP runtime or libdrm may say something of their own first)
+                    seen.append(line)
+                    if "input mapped" in line:
+                        mapped.set()
+                mapped.set()                                 # end of file: the child is gone, nobody need wait any longer
+
+            reader = threading.Thread(target=read_stderr, daemon=True)
+            reader.start()
+            try:
+                if not mapped.wait(timeout=600):
+                    raise AssertionError((mode, "no word from the child in 600 s", seen))
+                assert any("input mapped" in line for line in seen), (mode, seen)
+                os.truncate(victim, keep)
+                p.wait(timeout=600)
+            finally:
+                if p.poll() is None:
+                    p.kill()
+                    p.wait()
+                reader.join(timeout=60)
+            stdout_file.seek(0)
+            stdout, stderr = stdout_file.read(), "".join(seen)
         assert p.returncode == 1, (mode, p.returncode, stdout[-500:], stderr[-500:])       # not -SIGBUS
         assert message in stdout + stderr, (mode, stdout[-500:], stderr[-500:])
         assert out.stat().st_size == 0
