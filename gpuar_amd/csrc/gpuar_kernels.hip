@@ -23,6 +23,7 @@
 //    reciprocal multipliers as VECTOR operands, eight at a time by loads with a wave-uniform address (no scalar load,
 //    no v_readlane in the loop);
 //  * crc32_kernel: the per-packet CRC-32 of the .gip trailer, computed or verified;
+//  * split_planes_kernel / merge_planes_kernel, planes_tail_kernel: byte-plane splitting of typed data (planes.h);
 //  * compaction (scan + gather), synthetic-stream generators, a plain copy (the measured HBM roof).
 //
 // Bit-exact with the reference: same counts, same integer arithmetic, same
@@ -39,6 +40,7 @@
 
 #include "lane_codec.h"
 #include "crc32.h"
+#include "planes.h"
 
 namespace gpuar {
 
@@ -685,6 +687,7 @@ struct BatchLane {
     const uint8_t *ptr;        // the packet's bytes in its buffer: ptrs[b] + j * 8192
     uint32_t count;            // bytes of the buffer from there on, at most 8192 (0: the packet lies past the buffer's end)
     bool owned;                // some buffer owns the packet and that buffer's pointer is 16-byte aligned
+    uint32_t buffer;           // ... which buffer (when one owns the packet)
 };
 __device__ __forceinline__ BatchLane batch_lane(const uint8_t *const *ptrs, const uint64_t *bytes, const uint64_t *first_packet,
                                                 uint32_t n_buffers, uint64_t packet) {
@@ -694,9 +697,10 @@ __device__ __forceinline__ BatchLane batch_lane(const uint8_t *const *ptrs, cons
         if (first_packet[lo + half] <= packet) lo += half + 1u, n -= half + 1u;
         else n = half;
     }
-    BatchLane r = {nullptr, 0u, false};
+    BatchLane r = {nullptr, 0u, false, 0u};
     if (lo == 0u || packet >= first_packet[lo]) return r;   // in front of the first buffer, or behind the last one's packets
     const uint32_t b = lo - 1u;
+    r.buffer = b;
     const uint64_t at = (packet - first_packet[b]) * kPacket;
     const uint8_t *p = ptrs[b];
     const uint64_t n_bytes = bytes[b];
@@ -718,7 +722,7 @@ encode_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_t *__r
     const uint32_t lane = threadIdx.x & 63u;
     const size_t packet = group * kLanes + lane;
     bool live = packet < n_packets;
-    BatchLane bl = {nullptr, 0u, false};
+    BatchLane bl = {nullptr, 0u, false, 0u};
     if (live) {
         bl = batch_lane(ptrs, bytes, first_packet, n_buffers, packet);
         if (!bl.owned || bl.count == 0u) {
@@ -1144,7 +1148,7 @@ encode_small_batch_kernel(const uint8_t *const *__restrict__ ptrs, const uint64_
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const size_t packet = group * kLanes + lane;
     bool live = packet < n_packets;
-    BatchLane bl = {nullptr, 0u, false};
+    BatchLane bl = {nullptr, 0u, false, 0u};
     if (live) {
         bl = batch_lane(ptrs, bytes, first_packet, n_buffers, packet);
         if (!bl.owned || bl.count == 0u) {
@@ -2194,6 +2198,178 @@ crc32_kernel(CrcArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Byte-plane splitting (planes.h): pure data movement in front of the encoder (split) and behind the decoder
+// (merge), for one buffer or a batch with one element width per buffer.
+//
+// Full groups: one workgroup of 512 threads per packet; the workgroup of a group's FIRST packet moves the whole group
+// (w packets), the others return.  A thread owns one block of 16 elements: 16 w mixed bytes = w quads back to back on the
+// mixed side, one quad of every plane on the other, regrouped in registers by byte permutes (planes_block: v_perm_b32; no
+// LDS).  So the plane side is read or written perfectly coalesced and the mixed side w quads per lane, 16-byte accesses
+// on both.  Every thread holds its loads in registers before the workgroup's barrier and stores behind it: the group is
+// read completely before any of it is written, which is what lets `out` be `in`.
+// The tail of a buffer (n mod G bytes: fewer than w packets) is planes_tail_kernel's, one workgroup per buffer through
+// LDS: by quads in (never beyond the 16-byte piece that holds the buffer's last byte), by dwords and bytes out (never
+// beyond byte n), again all loads before any store.
+// Separate launches, not fused into the codec kernels (their schedules are pinned: DESIGN.md 4.3b).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kPlaneThreads = kPlanePacket / kPlaneBlock;        // 512: a block of 16 elements per thread
+constexpr uint32_t kPlaneGridCap = 1u << 22;                          // workgroups per launch (they stride over the packets)
+
+struct PlanesArgs {
+    const uint8_t *in;                      // one buffer: `in`, `out`, `n_bytes`, `elem` ...
+    uint8_t *out;
+    size_t n_bytes;
+    uint32_t elem;
+    const uint8_t *const *in_ptrs;          // ... or a batch (in_ptrs != nullptr)
+    uint8_t *const *out_ptrs;
+    const uint64_t *bytes;
+    const uint64_t *first_packet;
+    const uint64_t *elem_bytes;
+    uint32_t n_buffers;
+    uint32_t n_packets;
+    uint32_t *status;
+};
+
+// A batch buffer the transform can take: both pointers 16-byte aligned, a width of 1, 2, 4 or 8, and exactly the packets its
+// bytes make (a group is moved as a whole, so a buffer that owns only some of its packets is refused as a whole).
+struct PlanesBuffer {
+    const uint8_t *in;
+    uint8_t *out;
+    uint64_t n_bytes;
+    uint32_t w;                             // 0: unusable
+};
+__device__ __forceinline__ PlanesBuffer planes_buffer(const PlanesArgs &a, uint32_t b) {
+    PlanesBuffer r = {a.in_ptrs[b], a.out_ptrs[b], a.bytes[b], 0u};
+    const uint64_t w = a.elem_bytes[b];
+    const uint64_t owns = a.first_packet[b + 1u] - a.first_packet[b];
+    const bool aligned = ((reinterpret_cast<uintptr_t>(r.in) | reinterpret_cast<uintptr_t>(r.out)) & 15u) == 0u;
+    if (aligned && (w == 1u || w == 2u || w == 4u || w == 8u) && owns == (r.n_bytes + kPacket - 1u) / kPacket) r.w = static_cast<uint32_t>(w);
+    return r;
+}
+
+typedef uint32_t PlanesQuad __attribute__((ext_vector_type(4)));
+
+struct PlanesPerm {
+    __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t sel) const { return __builtin_amdgcn_perm(a, b, sel); }
+};
+
+// one full group at `in` -> `out` (both 16-byte aligned; out == in is fine), the whole workgroup
+template <int W, bool Merge>
+__device__ __forceinline__ void planes_group(const uint8_t *in, uint8_t *out) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    const uint32_t t = threadIdx.x;
+    // mixed side: the thread's 16 elements back to back; plane side: its quad of plane k at k * 8192
+    const uint32_t from_at = Merge ? 16u * t : 16u * W * t, from_step = Merge ? kPlanePacket : 16u;
+    const uint32_t to_at = Merge ? 16u * W * t : 16u * t, to_step = Merge ? 16u : kPlanePacket;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(in + from_at));
+    PlanesQuad q[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) q[k] = src[k * (from_step / 16u)];
+    // the loads have arrived in every thread before any thread stores (in place: another thread's store goes where this one reads)
+#pragma unroll
+    for (int k = 0; k < W; ++k) asm volatile("" : "+v"(q[k]));
+    __syncthreads();
+    uint32_t from[4 * W], to[4 * W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) from[4 * k] = q[k].x, from[4 * k + 1] = q[k].y, from[4 * k + 2] = q[k].z, from[4 * k + 3] = q[k].w;
+    planes_block<W, Merge>(from, to, PlanesPerm());
+    GlobalQuad *dst = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(out + to_at));
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        PlanesQuad v;
+        v.x = to[4 * k], v.y = to[4 * k + 1], v.z = to[4 * k + 2], v.w = to[4 * k + 3];
+        dst[k * (to_step / 16u)] = v;
+    }
+}
+
+template <bool Merge>
+__device__ __forceinline__ void planes_full(const PlanesArgs &a) {
+    for (uint64_t packet = blockIdx.x; packet < a.n_packets; packet += gridDim.x) {
+        const uint8_t *in = a.in;
+        uint8_t *out = a.out;
+        uint64_t n_bytes = a.n_bytes, j = packet;
+        uint32_t w = a.elem;
+        if (a.in_ptrs) {
+            const BatchLane bl = batch_lane(a.in_ptrs, a.bytes, a.first_packet, a.n_buffers, packet);
+            PlanesBuffer pb = {nullptr, nullptr, 0u, 0u};
+            if (bl.owned && bl.count) pb = planes_buffer(a, bl.buffer);
+            if (pb.w == 0u) {
+                if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                continue;
+            }
+            in = pb.in, out = pb.out, n_bytes = pb.n_bytes, w = pb.w;
+            j = packet - a.first_packet[bl.buffer];
+        }
+        w = __builtin_amdgcn_readfirstlane(w);
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(j & (w - 1u)));
+        const uint64_t at = j * kPacket;
+        if (lead != 0u || n_bytes - at < static_cast<uint64_t>(w) * kPacket) continue;      // not a group's first packet, or the tail
+        if (w == 1u && in == out) continue;
+        if (w == 8u) planes_group<8, Merge>(in + at, out + at);
+        else if (w == 4u) planes_group<4, Merge>(in + at, out + at);
+        else if (w == 2u) planes_group<2, Merge>(in + at, out + at);
+        else planes_group<1, Merge>(in + at, out + at);
+    }
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+split_planes_kernel(PlanesArgs a) {
+    planes_full<false>(a);
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+merge_planes_kernel(PlanesArgs a) {
+    planes_full<true>(a);
+}
+
+// the tails: workgroup b on buffer b's last n mod G bytes (the general path of planes.h's definition)
+template <bool Merge>
+__device__ __forceinline__ void planes_tail(const PlanesBuffer &pb, PlanesQuad *lds) {
+    const uint32_t w = pb.w;
+    if (w == 0u || (w == 1u && pb.in == pb.out)) return;
+    const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
+    if (r == 0u) return;
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
+    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) lds[i] = src[i];
+    __syncthreads();
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
+    const uint32_t log_w = 31u - __builtin_clz(w);
+    // output byte o of the tail comes from input byte ...
+    auto source = [&](uint32_t o) -> uint32_t {
+        if (o >= e * w) return o;                                           // the last r mod w bytes (and everything when e = 0)
+        if (!Merge) return (o % e << log_w) + o / e;                        // o = k e + i  <-  i w + k
+        return (o & (w - 1u)) * e + (o >> log_w);                           // o = i w + k  <-  k e + i
+    };
+    uint8_t *out = pb.out + (pb.n_bytes - r);
+    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
+    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) {
+        const uint32_t o = 4u * i;
+        words[i] = bytes[source(o)] | static_cast<uint32_t>(bytes[source(o + 1u)]) << 8 | static_cast<uint32_t>(bytes[source(o + 2u)]) << 16 |
+                   static_cast<uint32_t>(bytes[source(o + 3u)]) << 24;
+    }
+    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
+    if (threadIdx.x < (r & 3u)) last[(r & ~3u) + threadIdx.x] = bytes[source((r & ~3u) + threadIdx.x)];
+}
+
+template <bool Merge>
+__global__ void __launch_bounds__(kPlaneThreads)
+planes_tail_kernel(PlanesArgs a) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    if (!a.in_ptrs) {
+        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
+        planes_tail<Merge>(pb, lds);
+        return;
+    }
+    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
+        planes_tail<Merge>(planes_buffer(a, static_cast<uint32_t>(b)), lds);      // (an unusable buffer with packets was flagged by the kernel above)
+        __syncthreads();                                                          // the next buffer's tail goes into the same LDS
+    }
+}
+
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -2489,6 +2665,96 @@ int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_
     a.first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
     a.status = status;
     return launch_crc32(true, a, stream);
+}
+
+static int launch_planes(bool merge, const gpuar::PlanesArgs &a, size_t n_tails, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t blocks = a.n_packets < gpuar::kPlaneGridCap ? a.n_packets : gpuar::kPlaneGridCap;
+    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
+    if (merge) gpuar::merge_planes_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(a);
+    else gpuar::split_planes_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(a);
+    const int e = check_launch();
+    if (e != GPUAR_OK || tails == 0u) return e;
+    if (merge) gpuar::planes_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(a);
+    else gpuar::planes_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(a);
+    return check_launch();
+}
+
+static int planes_single(bool merge, const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!d_in || !d_out || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_in) || !aligned16(d_out)) return GPUAR_ERR_ALIGNMENT;
+    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out);
+    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
+    if (elem_bytes == 1u && in == out) return GPUAR_OK;
+    gpuar::PlanesArgs a = {};
+    a.in = d_in;
+    a.out = d_out;
+    a.n_bytes = n_bytes;
+    a.elem = elem_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    return launch_planes(merge, a, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+}
+
+static int planes_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                        const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs, uint32_t *d_status,
+                        void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_elem_bytes || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u)) return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::PlanesArgs a = {};
+    a.in_ptrs = d_in_ptrs;
+    a.out_ptrs = d_out_ptrs;
+    a.bytes = d_bytes;
+    a.first_packet = d_first_packet;
+    a.elem_bytes = d_elem_bytes;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.status = status;
+    return launch_planes(merge, a, n_buffers, stream);
+}
+
+int gpuar_hip_split_planes(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return planes_single(false, d_in, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_merge_planes(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return planes_single(true, d_in, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_split_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                 const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                 uint32_t *d_status, void *stream) {
+    return planes_batch(false, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+int gpuar_hip_merge_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                 const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                 uint32_t *d_status, void *stream) {
+    return planes_batch(true, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+static int planes_on_host(bool merge, const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !out) return GPUAR_ERR_ARGUMENT;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
+    if (merge) gpuar::planes_host<true>(in, n_bytes, elem_bytes, out);
+    else gpuar::planes_host<false>(in, n_bytes, elem_bytes, out);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return planes_on_host(false, in, n_bytes, elem_bytes, out);
+}
+
+int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return planes_on_host(true, in, n_bytes, elem_bytes, out);
 }
 
 int gpuar_hip_status(uint32_t *flags) {

@@ -38,11 +38,22 @@ class Compressor {
     FILE *saveFile = nullptr;
     bool writeIndex = false;          // append the packet-offset index trailer (packet_index.hpp)
     bool writeChecksum = false;       // append the trailer with per-packet CRC-32s (version 2), which decompress verifies
+    int planes = 1;                   // compress: split the input into byte planes of elements this wide (../planes.h) and say so in a
+                                      // version-3 trailer, from which decompress learns the width; 1: no transform, no such trailer
 
     // the error a decompress raises for a packet whose decoded bytes do not match the CRC-32 of its trailer
     static std::runtime_error checksumError(size_t packet, uint64_t begin, uint64_t end) {
         return std::runtime_error("Checksum mismatch: packet " + std::to_string(packet) + " (uncompressed bytes " + std::to_string(begin) +
                                   " .. " + std::to_string(end) + ") does not decode to what was compressed");
+    }
+    // a trailer that says the file holds byte planes but cannot be used: going on would hand back the split bytes
+    static std::runtime_error planesTrailerError() {
+        return std::runtime_error("Incorrect file format: the trailer says the file holds byte planes (version 3) but it is damaged, "
+                                  "carries a width other than 2, 4 or 8, or carries flags this gpuar does not know");
+    }
+    static std::runtime_error planesPacketError(size_t packet) {
+        return std::runtime_error("Incorrect file format: packet " + std::to_string(packet) + " of a file of byte planes is not the last one and "
+                                  "does not hold 8192 bytes");
     }
     static void warnMalformedTrailer() {
         std::fprintf(stderr, "Warning: ignoring a malformed checksum trailer: nothing was verified\n");
@@ -68,6 +79,10 @@ class Compressor {
     void setSaveFileName(const std::string &fileName) { saveFileName = fileName; }
     void setWriteIndex(bool on) { writeIndex = on; }
     void setWriteChecksum(bool on) { writeChecksum = on; }
+    void setPlanes(int elem_bytes) {
+        if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) throw std::invalid_argument("planes: the element width is 1, 2, 4 or 8");
+        planes = elem_bytes;
+    }
     virtual CompressionInfo compress(ProgressMonitor *monitor) = 0;
     virtual CompressionInfo decompress(ProgressMonitor *monitor) = 0;
     void closeFiles();

@@ -13,6 +13,7 @@
 
 #include "../crc32.h"
 #include "../lane_codec.h"
+#include "../planes.h"
 #include "file_header.hpp"
 #include "packet_index.hpp"
 
@@ -101,10 +102,14 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
 
     const unsigned nthreads = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
     std::vector<uint8_t> in(kBatchPackets * gpuar::kPacket + 16), slots(kBatchPackets * gpuar::kSlot);
+    // --planes: what is coded is the batch split into byte planes (a batch is a whole number of groups: 4096 packets; only the
+    // file's last one can be shorter, and its tail is the file's tail); the CRCs stay those of the bytes as read
+    static_assert(kBatchPackets % 8 == 0, "a batch starts on a group boundary for every element width");
+    std::vector<uint8_t> split(planes > 1 ? in.size() : 0);
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
     std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
-    const bool trailer = writeIndex || writeChecksum;
+    const bool trailer = writeIndex || writeChecksum || planes > 1;
     try {
         for (;;) {
             io_timer.start();
@@ -113,10 +118,12 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
             if (got == 0) break;
             const size_t np = (got + gpuar::kPacket - 1) / gpuar::kPacket;
             process_timer.start();     // model init + codec only, as src/cpu_compressor.cpp:157-161
+            if (planes > 1) gpuar::planes_host<false>(in.data(), got, static_cast<uint32_t>(planes), split.data());
+            const uint8_t *coded = planes > 1 ? split.data() : in.data();
             for_each_packet(np, nthreads, [&](size_t p) {
                 const size_t off = p * gpuar::kPacket;
                 const uint32_t len = static_cast<uint32_t>(std::min<size_t>(gpuar::kPacket, got - off));
-                clen[p] = static_cast<uint32_t>(encode_one(in.data() + off, len, slots.data() + p * gpuar::kSlot));
+                clen[p] = static_cast<uint32_t>(encode_one(coded + off, len, slots.data() + p * gpuar::kSlot));
                 if (writeChecksum) crc[p] = gpuar::crc32_update(0, in.data() + off, len);
             });
             process_timer.stop();
@@ -133,7 +140,8 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
             monitor->updateProgress(&info);
         }
         io_timer.start();
-        if (trailer) PacketIndex::write(saveFile, all_clens, writeChecksum ? &all_crcs : nullptr);
+        if (planes > 1) PacketIndex::writePlanes(saveFile, all_clens, static_cast<uint32_t>(planes), writeChecksum ? &all_crcs : nullptr);
+        else if (trailer) PacketIndex::write(saveFile, all_clens, writeChecksum ? &all_crcs : nullptr);
         FileHeader header;
         header.setCompressedFileSize(info.compressedFileSize);
         header.setUncompressedFileSize(info.uncompressedFileSize);
@@ -167,10 +175,17 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         const size_t stream_end = streamEnd(info, fileSize);
         std::vector<uint16_t> index;
         std::vector<uint32_t> crcs;              // per packet, from a version-2 trailer: every decoded packet is checked against them
-        const PacketIndex::Found found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
+        // a version-3 trailer first: the packets then hold byte planes of elements `width` bytes wide, merged back below
+        uint32_t width = 1;
+        bool planes_crcs = false;
+        const PacketIndex::Planes split = PacketIndex::findPlanes(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs, width, planes_crcs);
+        if (split == PacketIndex::Planes::unusable) throw planesTrailerError();
+        const bool merging = split == PacketIndex::Planes::ok;
+        PacketIndex::Found found = PacketIndex::Found::none;
+        if (!merging) found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
         if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
-        const bool indexed = found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
-        const bool verify = found == PacketIndex::Found::v2;
+        const bool indexed = merging || found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
+        const bool verify = merging ? planes_crcs : found == PacketIndex::Found::v2;
         size_t first_packet = 0;                 // of the window
         io_timer.stop();
 
@@ -181,6 +196,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         // through the file), then the file is wound back to the end of the last whole packet.
         const unsigned nthreads = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
         std::vector<uint8_t> window(kBatchPackets * gpuar::kSlot + 65536 + 16), out(kBatchPackets * gpuar::kPacket);
+        std::vector<uint8_t> decoded(merging ? out.size() : 0);      // byte planes: a window is decoded here and merged into `out`
         std::vector<size_t> offsets(kBatchPackets + 1);
         std::vector<uint32_t> ulen(kBatchPackets);
         size_t file_pos = FileHeader::HEADER_LENGTH, next_packet = 0;
@@ -191,7 +207,9 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                 offsets[0] = 0;
                 while (next_packet < index.size() && np < kBatchPackets && bytes + index[next_packet] + 16 <= window.size()) {
                     const size_t c = index[next_packet++];
-                    if (c < gpuar::kHdr) throw std::runtime_error("Incorrect file format");
+                    // (byte planes: no packet longer than a slot, so that every window but the last holds kBatchPackets packets,
+                    // a whole number of groups)
+                    if (c < gpuar::kHdr || (merging && c > gpuar::kSlot)) throw std::runtime_error("Incorrect file format");
                     bytes += c;
                     offsets[++np] = bytes;
                 }
@@ -219,10 +237,19 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
             io_timer.stop();
             file_pos += bytes;
             process_timer.start();
+            uint8_t *const plain = merging ? decoded.data() : out.data();
             for_each_packet(np, nthreads, [&](size_t p) {
-                ulen[p] = static_cast<uint32_t>(decode_one(window.data() + offsets[p], window.data() + bytes,
-                                                           out.data() + p * gpuar::kPacket));
+                ulen[p] = static_cast<uint32_t>(decode_one(window.data() + offsets[p], window.data() + bytes, plain + p * gpuar::kPacket));
             });
+            if (merging) {
+                // every packet but the file's last holds 8192 bytes, or the groups are not where the merge takes them to be
+                size_t total = 0;
+                for (size_t p = 0; p < np; ++p) {
+                    if (first_packet + p + 1 < index.size() && ulen[p] != gpuar::kPacket) throw planesPacketError(first_packet + p);
+                    total += ulen[p];
+                }
+                gpuar::planes_host<true>(decoded.data(), total, width, out.data());
+            }
             if (verify) {
                 // the CRC covers the packet's original bytes: all of them 8192 long but the file's last one, which holds 1 .. 8192
                 for (size_t p = 0; p < np; ++p) {

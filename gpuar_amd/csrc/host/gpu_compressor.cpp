@@ -424,6 +424,7 @@ struct GPUCompressor::DeviceBuffers {
     uint32_t *d_status = nullptr;   // this lane's own status word (device): its launches report here, nobody else's do
     uint32_t *d_crc = nullptr;      // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
     uint32_t *h_crc = nullptr;      // pinned, the same
+    uint8_t *d_planes = nullptr;    // cap * 8192 (--planes / a version-3 trailer): the chunk split into byte planes, or merged back
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
     // the lane's pinned pieces and which of them are free
@@ -460,10 +461,16 @@ struct GPUCompressor::DeviceBuffers {
         hip_check(hipMalloc(reinterpret_cast<void **>(&d_crc), crcBytes()), "hipMalloc");
         hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_crc), crcBytes(), hipHostMallocDefault), "hipHostMalloc");
     }
+    // one more buffer of chunk size for a job that splits its input into byte planes or merges them back; the current device is the lane's
+    void allocatePlanes() {
+        if (!d_planes) hip_check(hipMalloc(reinterpret_cast<void **>(&d_planes), cap * kPacket), "hipMalloc");
+    }
     void release() {
         if (!cap) return;
         (void)hipSetDevice(device);
         (void)hipFree(d_plain);
+        if (d_planes) (void)hipFree(d_planes);
+        d_planes = nullptr;
         if (d_slots) (void)hipFree(d_slots);
         (void)hipFree(d_stream);
         (void)hipFree(d_offsets);
@@ -591,11 +598,13 @@ struct GPUCompressor::DeviceBuffers {
     // lane's own stream -- no device-wide synchronisation, no flag shared with another lane
     // `mode`: GPUAR_MODE_* -- which encode kernel (the caller knows whether this launch has the chip to itself)
     // `checksum`: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum) {
+    // `planes` > 1: what is coded is the chunk split into byte planes of elements that wide (d_planes); the CRCs stay the input's
+    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
-        gpuar_check(gpuar_hip_encode_mode(d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
+        if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
+        gpuar_check(gpuar_hip_encode_mode(planes > 1 ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
         if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
@@ -611,10 +620,11 @@ struct GPUCompressor::DeviceBuffers {
     // d_stream[0..n_stream) with h_offsets[0..n_packets] -> d_plain[0..n_packets*8192); returns this chunk's status flags.
     // crcs (n_packets values, or null): the decoded packets -- n_plain bytes back to back -- are verified against them;
     // GPUAR_STATUS_CHECKSUM in the flags then, and the chunk's lowest bad packet in `first_bad`
-    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr) {
+    // `planes` > 1: the n_plain decoded bytes are byte planes, merged into d_planes before they are verified; the result is there
+    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1) {
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
-        uint64_t *d_first_bad = reinterpret_cast<uint64_t *>(d_crc + crcSlots());
+        uint64_t *d_first_bad = crcs ? reinterpret_cast<uint64_t *>(d_crc + crcSlots()) : nullptr;
         if (crcs) {
             std::memcpy(h_crc, crcs, n_packets * sizeof(uint32_t));
             hip_check(hipMemcpyAsync(d_crc, h_crc, n_packets * sizeof(uint32_t), hipMemcpyHostToDevice, stream), "H2D");
@@ -622,7 +632,8 @@ struct GPUCompressor::DeviceBuffers {
         }
         hip_check(hipEventRecord(t0, stream), "event");
         gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
-        if (crcs) gpuar_check(gpuar_hip_verify_crc32(d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
+        if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
+        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         if (crcs) hip_check(hipMemcpyAsync(h_crc + crcSlots(), d_first_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
@@ -663,7 +674,9 @@ void GPUCompressor::releaseBuffers() {
 
 // kLanesPerDevice buffer sets per device, sized for the job at hand: a file of `total_packets` is cut
 // into chunks of at most batchPackets packets, small enough that every lane of every device gets one
-// (whole wavefronts: multiples of 64 packets).  A lane's buffers are allocated when it first gets a
+// (whole wavefronts: multiples of 64 packets -- hence whole groups of byte planes, 2, 4 or 8 packets, whatever --batch says:
+// with chunks that start on group boundaries counted from the file's start, a file of planes does not depend on how it
+// was cut).  A lane's buffers are allocated when it first gets a
 // chunk -- pinned allocations are what a short run of the CLI spends most of its time on.
 void GPUCompressor::ensureBuffers(size_t total_packets, bool compressing) {
     const size_t G = devices.size();
@@ -781,7 +794,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
         // length is set at the end (best effort: a file system without fallocate just grows the file as it goes)
         // (the fallocate system call, not posix_fallocate: where the file system cannot do it, glibc's stand-in would write zeros)
         (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(FileHeader::HEADER_LENGTH + total_packets * kSlot));
-        const bool trailer = writeIndex || writeChecksum;
+        const bool trailer = writeIndex || writeChecksum || planes > 1;
         std::vector<std::vector<uint16_t>> chunk_clens(trailer ? n_chunks : 0);        // for the optional index trailer
         std::vector<std::vector<uint32_t>> chunk_crcs(writeChecksum ? n_chunks : 0);   // and the checksums in it
         std::vector<std::atomic<size_t>> next_of_device(G);
@@ -814,13 +827,14 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (c == 0) trace("compress: its buffers allocated");
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (writeChecksum) b.allocateCrc();
+                            if (planes > 1) b.allocatePlanes();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const uint64_t at = chunk_at[c];
                             const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
                             const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
                             if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
                             uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum);     // (synchronises the lane's stream)
+                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes);     // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(at, n_plain);
                             // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
                             // (src/gpu_compressor.cpp:146-150)
@@ -866,7 +880,8 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
             std::vector<uint32_t> crcs;
             for (const auto &v : chunk_crcs) crcs.insert(crcs.end(), v.begin(), v.end());
             if (std::fseek(saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
-            PacketIndex::write(saveFile, all, writeChecksum ? &crcs : nullptr);
+            if (planes > 1) PacketIndex::writePlanes(saveFile, all, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr);
+            else PacketIndex::write(saveFile, all, writeChecksum ? &crcs : nullptr);
             if (std::fflush(saveFile) != 0) throw std::runtime_error("Write packet index failed");
             file_end = static_cast<uint64_t>(std::ftell(saveFile));
         }
@@ -1053,10 +1068,17 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         // packet lengths from the index trailer when the file has one (packet_index.hpp)
         std::vector<uint16_t> index;
         std::vector<uint32_t> crcs;      // a version-2 trailer's CRC-32s: every decoded chunk is verified against them
-        const PacketIndex::Found found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
+        // a version-3 trailer first: the packets then hold byte planes of elements `width` bytes wide, merged back on the device
+        uint32_t width = 1;
+        bool planes_crcs = false;
+        const PacketIndex::Planes split = PacketIndex::findPlanes(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs, width, planes_crcs);
+        if (split == PacketIndex::Planes::unusable) throw planesTrailerError();
+        const bool merging = split == PacketIndex::Planes::ok;
+        PacketIndex::Found found = PacketIndex::Found::none;
+        if (!merging) found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
         if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
-        const bool indexed = found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
-        const bool verify = found == PacketIndex::Found::v2;
+        const bool indexed = merging || found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
+        const bool verify = merging ? planes_crcs : found == PacketIndex::Found::v2;
 
         ChunkMap map;
         std::thread scanner;
@@ -1160,6 +1182,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             if (!b.cap) b.allocate(b.device, chunkPackets, false);
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (verify) b.allocateCrc();
+                            if (merging) b.allocatePlanes();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
                             const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
@@ -1184,6 +1207,9 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 if (clen < GPUAR_PACKET_HEADER_BYTES || off + clen > n_stream) throw std::runtime_error("Invalid file length");
                                 const size_t ulen = std::min<size_t>(kPacket, pkt[2] | (static_cast<size_t>(pkt[3]) << 8));
                                 all_full = all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
+                                // byte planes: every packet but the file's last holds 8192 bytes, or the groups are not where the merge
+                                // takes them to be (so every chunk but the last is whole groups, and all_full holds)
+                                if (merging && chunk.first_packet + p + 1 < index.size() && ulen != kPacket) throw planesPacketError(chunk.first_packet + p);
                                 produced += ulen;
                                 off += clen;
                             }
@@ -1208,8 +1234,8 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
                             }
                             uint64_t first_bad = 0;
-                            const uint32_t flags = verify ? b.decodeChunk(chunk.n_packets, crcs.data() + chunk.first_packet, static_cast<size_t>(produced), &first_bad)
-                                                          : b.decodeChunk(chunk.n_packets);        // (synchronises the lane's stream)
+                            const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
+                                                                 &first_bad, merging ? static_cast<int>(width) : 1);        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307
@@ -1223,7 +1249,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 throw checksumError(g, begin, std::min<uint64_t>(begin + kPacket, static_cast<uint64_t>(chunk.first_packet) * kPacket + produced));
                             }
                             if (all_full) {
-                                b.drain(writer, c, b.d_plain, static_cast<size_t>(produced), out_at, static_cast<size_t>(produced));
+                                b.drain(writer, c, merging ? b.d_planes : b.d_plain, static_cast<size_t>(produced), out_at, static_cast<size_t>(produced));
                             } else {             // short packets inside the chunk: one piece per packet
                                 uint64_t at = out_at;
                                 for (size_t p = 0; p < chunk.n_packets; ++p) {

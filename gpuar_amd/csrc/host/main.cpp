@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -56,6 +56,8 @@ void usage() {
     std::cout << "--batch       largest chunk of packets a pipeline lane takes at a time (default 65536 = 512 MiB)" << std::endl;
     std::cout << "--index       (compress) append the packet-offset index trailer; decompress uses it when present" << std::endl;
     std::cout << "--checksum    (compress) append the trailer with a CRC-32 per packet (and the index); decompress verifies it when present" << std::endl;
+    std::cout << "--planes      (compress) W = 2, 4 or 8: split the input into byte planes of W-byte elements first (typed data compresses better);" << std::endl;
+    std::cout << "              the file then carries a trailer with W, which decompress needs; 1 = off (default)" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
@@ -65,7 +67,7 @@ int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip";
     bool has_in = false;
-    int device = -1, gpus = 0, threads = 1;
+    int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
         const char *v = nullptr;
@@ -105,6 +107,13 @@ int main(int argc, char **argv) {
         } else if (flag_name_is(argv[i], "threads", &v)) {
             if (!take(&v)) break;
             threads = std::atoi(v);
+        } else if (flag_name_is(argv[i], "planes", &v)) {
+            if (!take(&v)) break;
+            planes = !std::strcmp(v, "1") ? 1 : !std::strcmp(v, "2") ? 2 : !std::strcmp(v, "4") ? 4 : !std::strcmp(v, "8") ? 8 : 0;
+            if (!planes) {
+                std::cerr << "--planes takes 1, 2, 4 or 8: " << v << std::endl;
+                return 2;
+            }
         } else if (flag_name_is(argv[i], "batch", &v)) {
             if (!take(&v)) break;
             batch = std::atol(v);
@@ -145,6 +154,7 @@ int main(int argc, char **argv) {
         }
         compressor->setWriteIndex(index);
         compressor->setWriteChecksum(checksum);
+        compressor->setPlanes(planes);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);
         CompressionInfo info;

@@ -27,6 +27,8 @@ EXPORTS = [
     "gpuar_hip_version", "gpuar_hip_abi_version", "gpuar_hip_generate", "gpuar_hip_copy", "gpuar_hip_clock_samples",
     "gpuar_hip_batch_packet_count", "gpuar_hip_encode_batch", "gpuar_hip_decode_batch", "gpuar_hip_decode_stream_batch",
     "gpuar_hip_crc32", "gpuar_hip_verify_crc32", "gpuar_hip_crc32_batch", "gpuar_hip_verify_crc32_batch",
+    "gpuar_hip_split_planes", "gpuar_hip_merge_planes", "gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch",
+    "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
 ]
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -104,6 +106,15 @@ def load() -> C.CDLL:
     lib.gpuar_hip_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
     lib.gpuar_hip_verify_crc32_batch.restype = C.c_int
     lib.gpuar_hip_verify_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+    for name in ("gpuar_hip_split_planes", "gpuar_hip_merge_planes"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, sz, u32, vp, vp]
+    for name in ("gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    for name in ("gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, sz, u32, vp]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -331,6 +342,69 @@ def verify_crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packet
     _check(load().gpuar_hip_verify_crc32_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
                                                d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status), _stream_handle(stream)),
            "gpuar_hip_verify_crc32_batch")
+
+
+def _planes(name, d_in, elem_bytes, d_out, n_bytes, stream):
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    if d_out is None:
+        d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=d_in.device)[:n]
+    _require_cuda_u8(d_out, "d_out")
+    if d_out.numel() < n:
+        raise GpuarError("d_out too small")
+    _check(getattr(load(), name)(d_in.data_ptr(), n, elem_bytes, d_out.data_ptr(), _stream_handle(stream)), name)
+    return d_out
+
+
+def split_planes(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """Regroup the first `n_bytes` (default: all) bytes of `d_in`, taken as elements of `elem_bytes` bytes (1, 2, 4, 8), into byte
+    planes (gpuar_hip_split_planes; the map is in include/gpuar_hip.h): packet k of every group of elem_bytes packets holds
+    byte k of the group's 8192 elements.  `d_out` may be `d_in`.  Returns d_out."""
+    return _planes("gpuar_hip_split_planes", d_in, elem_bytes, d_out, n_bytes, stream)
+
+
+def merge_planes(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """The inverse of split_planes (gpuar_hip_merge_planes); `d_out` may be `d_in`."""
+    return _planes("gpuar_hip_merge_planes", d_in, elem_bytes, d_out, n_bytes, stream)
+
+
+def _planes_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status):
+    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
+                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
+        _require_u64_desc(t, what, n)
+    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(), n_buffers,
+                                 n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), name)
+
+
+def split_planes_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers: int, n_packets: int, d_out_ptrs, stream=None, d_status=None):
+    """split_planes for every buffer of a batch in one call (gpuar_hip_split_planes_batch; descriptors as for encode_batch, plus
+    one element width per buffer): buffer b goes from d_in_ptrs[b] to d_out_ptrs[b], which may be the same."""
+    _planes_batch("gpuar_hip_split_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
+
+
+def merge_planes_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers: int, n_packets: int, d_out_ptrs, stream=None, d_status=None):
+    """The inverse of split_planes_batch (gpuar_hip_merge_planes_batch)."""
+    _planes_batch("gpuar_hip_merge_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
+
+
+def _planes_host(name, data, elem_bytes):
+    data = bytes(data)
+    out = C.create_string_buffer(len(data))
+    _check(getattr(load(), name)(data, len(data), elem_bytes, out), name)
+    return out.raw
+
+
+def split_planes_host(data, elem_bytes: int) -> bytes:
+    """split_planes of a bytes-like object on the CPU (gpuar_hip_split_planes_host: no device is touched)."""
+    return _planes_host("gpuar_hip_split_planes_host", data, elem_bytes)
+
+
+def merge_planes_host(data, elem_bytes: int) -> bytes:
+    """merge_planes of a bytes-like object on the CPU (gpuar_hip_merge_planes_host)."""
+    return _planes_host("gpuar_hip_merge_planes_host", data, elem_bytes)
 
 
 def status() -> int:

@@ -233,6 +233,43 @@ int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_
                                  const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
                                  const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Byte planes: regrouping typed data in front of the codec.  For elements of elem_bytes = w bytes (2, 4 or 8; 1 = no
+ * transform) a GROUP is G = w * 8192 bytes = w whole packets, counted from the buffer's start, and for a buffer of n bytes
+ *     every full group at base B = g * G:   out[B + k * 8192 + i] = in[B + i * w + k]     0 <= i < 8192, 0 <= k < w
+ *     the tail of r = n mod G bytes at base B = n - r, with e = r div w:
+ *                                           out[B + k * e + i]    = in[B + i * w + k]     0 <= i < e;  the last r mod w
+ *                                           bytes are copied as they are.
+ * That is SPLIT: packet k of a group is byte plane k of its 8192 elements, which one adaptive model codes better than
+ * the mixture.  MERGE is the inverse.  The output has n bytes; packet counts, slots, compaction and
+ * first_packet are untouched, and a chunk that starts on a multiple of 8 packets can be transformed alone.  Separate
+ * launches in front of encode / behind decode; `out` may be `in` (every group is read whole before it is written).
+ * Nothing is read beyond the 16-byte piece that holds a buffer's last byte and nothing written beyond byte n.
+ * ---------------------------------------------------------------------- */
+
+/* One buffer.  elem_bytes outside {1, 2, 4, 8} or (with n_bytes != 0) a null pointer: GPUAR_ERR_ARGUMENT; a pointer that is not
+ * 16-byte aligned: GPUAR_ERR_ALIGNMENT; d_in and d_out overlapping without being equal: GPUAR_ERR_ARGUMENT.  n_bytes == 0,
+ * or elem_bytes == 1 with d_in == d_out, is GPUAR_OK with no launch (elem_bytes == 1 otherwise copies). */
+int gpuar_hip_split_planes(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+int gpuar_hip_merge_planes(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+
+/* A batch (descriptors as for gpuar_hip_encode_batch, with the same host-side checks before any device work): buffer b's
+ * d_bytes[b] bytes at d_in_ptrs[b] go to d_out_ptrs[b] (which may be the same pointer), as elements of d_elem_bytes[b] bytes
+ * (n_buffers u64, 8-byte aligned, like d_out_ptrs).  An unusable descriptor is GPUAR_STATUS_BAD_BATCH in d_status for each of
+ * its packets, by the encoders' rules; here a width outside {1, 2, 4, 8}, a misaligned d_out_ptrs[b] and a buffer whose
+ * first_packet range is not exactly the packets its bytes make count as unusable too, and such a buffer is left untouched. */
+int gpuar_hip_split_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                 const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                 uint32_t *d_status, void *stream);
+int gpuar_hip_merge_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                 const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs,
+                                 uint32_t *d_status, void *stream);
+
+/* Host only: the same maps on host memory, from the same definition (gpuar_amd/csrc/planes.h) -- no device is touched.
+ * `out` may be `in`; any other overlap, a bad width or (with n_bytes != 0) a null pointer is GPUAR_ERR_ARGUMENT. */
+int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
