@@ -17,6 +17,12 @@ coded (hip.split_planes: one launch for the batch, into a temporary buffer -- th
 back, in place in the output tensors, after they are decoded: typed data (bf16, fp32, int64 ...) compresses 7-26 % smaller
 (DESIGN.md 4.6).  The CRCs are those of the ORIGINAL bytes.  Compressed.gip(b) then carries the width in a version-3 trailer
 (`gpuar c --planes=W`), without which a reader would return the regrouped bytes.
+
+With stored="auto" the packets that cannot shrink are not coded at all: one histogram pass (hip.estimate_batch) predicts every
+packet's compressed size, the packets whose estimate is not smaller than their bytes are copied raw into Compressed.raw
+(hip.move_packets) and only the others go through the encoder -- and, in decompress, the decoder.
+estimate(tensors, ...) gives the predicted sizes without compressing anything.  The .gip container has no raw packets:
+Compressed.gip(b) raises for a buffer that holds one.
 """
 from __future__ import annotations
 
@@ -92,13 +98,21 @@ class Compressed:
     (int64, device, n_packets + 1) the packet offsets in it, `first_packet` (host list, n_buffers + 1) which packets
     belong to which buffer, `sizes` the buffers' byte counts, `crc32` (int32, device, n_packets; None unless compressed with
     checksum=True) the CRC-32 of every packet's uncompressed bytes, `planes` (host list, n_buffers; None unless compressed with
-    planes=...) the element width each buffer's bytes were split into byte planes by (1: not split)."""
+    planes=...) the element width each buffer's bytes were split into byte planes by (1: not split).
+
+    Compressed with stored=...: `stored` (uint8, device, n_packets) is 1 for every batch packet that is kept raw, `raw` (uint8,
+    device) holds those packets' bytes in batch order, each at a 16-byte-aligned offset, `raw_offsets` (int64, device,
+    n_stored + 1) where; `stream` and `offsets` (n_coded + 1 entries) then cover the CODED packets only, in batch order.  All
+    three are None otherwise."""
     stream: object
     offsets: object
     first_packet: list
     sizes: list
     crc32: object = None
     planes: list = None
+    stored: object = None
+    raw: object = None
+    raw_offsets: object = None
 
     @property
     def n_buffers(self) -> int:
@@ -113,10 +127,31 @@ class Compressed:
             self._off = self.offsets.cpu().tolist()
         return self._off
 
+    @property
+    def nbytes(self) -> int:
+        """The compressed bytes: the coded packets' stream and the raw packets."""
+        return self.stream.numel() + (self.raw.numel() if self.raw is not None else 0)
+
+    def _coded_range(self, b: int):
+        """Buffer b's packets as a range of `offsets`: its batch packets, or -- with `stored` -- their ranks among the coded ones."""
+        lo, hi = self.first_packet[b], self.first_packet[b + 1]
+        if self.stored is None:
+            return lo, hi
+        if getattr(self, "_rank", None) is None:
+            self._rank = [0]
+            for flag in self.stored.cpu().tolist():
+                self._rank.append(self._rank[-1] + (0 if flag else 1))
+        if self._rank[hi] - self._rank[lo] != hi - lo:
+            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw) packets: it has no packet stream "
+                             "and no .gip form (the container has no raw packets)")
+        return self._rank[lo], self._rank[hi]
+
     def payload(self, b: int):
-        """A view of buffer b's packet stream (the bytes behind the header of its .gip file)."""
+        """A view of buffer b's packet stream (the bytes behind the header of its .gip file).  Raises GpuarError for a buffer that
+        has a stored packet."""
         off = self._offsets_host()
-        return self.stream[off[self.first_packet[b]]:off[self.first_packet[b + 1]]]
+        lo, hi = self._coded_range(b)
+        return self.stream[off[lo]:off[hi]]
 
     def gip(self, b: int) -> bytes:
         """Buffer b as a whole .gip file: what `gpuar c` writes for it (with CRCs: what `gpuar c --checksum` writes; split into
@@ -126,8 +161,9 @@ class Compressed:
         w = self.planes[b] if self.planes is not None else 1
         if self.crc32 is not None or w > 1:
             off = self._offsets_host()
-            lo, hi = self.first_packet[b], self.first_packet[b + 1]
+            lo, hi = self._coded_range(b)
             clens = [off[i + 1] - off[i] for i in range(lo, hi)]
+            lo, hi = self.first_packet[b], self.first_packet[b + 1]
             crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
             out += trailer_v3(clens, w, crcs) if w > 1 else trailer_v2(clens, crcs)
         return out
@@ -172,38 +208,136 @@ def plane_widths(tensors, planes):
     return widths
 
 
-def compress(tensors, mode=None, stream=None, checksum=False, planes=None) -> Compressed:
+def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status):
+    """The batch's descriptors on the device and -- where `widths` asks for it -- its buffers split into byte planes (one launch,
+    into a temporary buffer): (d_ptrs, d_bytes, d_first_packet, d_coded, d_split, the pinned host copy of the descriptors, for the
+    caller to hold while the launches run), d_coded the pointers of the bytes to code."""
+    import torch
+    if widths is not None and any(w != 1 for w in widths):
+        # the split copies of the buffers that are split, back to back (each 16-byte aligned); the others are coded where they are
+        at, split_ptrs = 0, []
+        for p, size, w in zip(ptrs, sizes, widths):
+            split_ptrs.append(at if w != 1 and size else None)
+            at += (size + 15) // 16 * 16 if w != 1 else 0
+        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
+        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
+        (d_ptrs, d_bytes, d_fp, d_elem, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, split_ptrs)
+        H.split_planes_batch(d_ptrs, d_bytes, d_fp, d_elem, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
+        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
+    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
+    return d_ptrs, d_bytes, d_fp, d_ptrs, None, _keep
+
+
+def _packets(d_ptrs, d_bytes, d_fp, n_buffers, n_packets):
+    """Every batch packet as a buffer of its own, built on the device: (buffer index, pointer, bytes) per packet, int64 -- packet
+    j of buffer b is min(8192, bytes[b] - j * 8192) bytes at ptrs[b] + j * 8192."""
+    import torch
+    device = d_ptrs.device
+    counts = d_fp[1:n_buffers + 1] - d_fp[:n_buffers]
+    buf = torch.repeat_interleave(torch.arange(n_buffers, dtype=torch.int64, device=device), counts, output_size=n_packets)
+    at = (torch.arange(n_packets, dtype=torch.int64, device=device) - d_fp[buf]) * H.PACKET
+    return buf, d_ptrs[buf] + at, torch.clamp(d_bytes[buf] - at, max=H.PACKET)
+
+
+def _stored_argument(stored, n_packets):
+    """`stored` as None, "auto" or a list of n_packets bools; anything else raises (before any launch)."""
+    if stored is None or (isinstance(stored, str) and stored == "auto"):
+        return stored
+    if isinstance(stored, str):
+        raise GpuarError(f"stored={stored!r}: None, \"auto\" or one bool per packet")
+    import torch
+    flags = stored.tolist() if isinstance(stored, torch.Tensor) else list(stored)
+    if len(flags) != n_packets:
+        raise GpuarError(f"stored has {len(flags)} entries, the batch {n_packets} packets")
+    return [bool(f) for f in flags]
+
+
+def _partition(d_flags, d_len16):
+    """(n_stored, raw bytes, coded packets, stored packets): the packets of either kind in batch order (a stable sort by the flag;
+    one synchronisation for the two counts)."""
+    import torch
+    n_stored, raw_bytes = torch.stack([d_flags.sum(), (d_len16 * d_flags).sum()]).tolist()
+    order = torch.argsort(d_flags, stable=True)
+    n_coded = d_flags.numel() - n_stored
+    return n_stored, raw_bytes, order[:n_coded], order[n_coded:]
+
+
+def _unit_first_packet(n, device):
+    import torch
+    return torch.arange(n + 1, dtype=torch.int64, device=device)
+
+
+def estimate(tensors, planes=None, stored=None) -> list:
+    """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
+    estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
+    asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
+    split_planes_batch launch if asked for, one estimate_batch launch."""
+    import torch
+    if stored is not None and stored != "auto":
+        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    tensors = list(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    widths = plane_widths(tensors, planes)
+    n = len(sizes)
+    if n_packets == 0:
+        return [0] * n
+    d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
+    d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
+    buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+    if stored == "auto":
+        d_est = torch.where(d_est >= 4 + d_len, d_len, d_est)
+    totals = torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est)
+    _raise_on_status(d_status, "estimate_batch")
+    return totals.tolist()
+
+
+def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
     compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
     every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
     tensor (plane_widths): split each tensor's bytes into byte planes of that element width before coding (one more launch,
     into a temporary buffer that is freed with the slots; widths of 1 are coded as they are).  The widths the kernels take
-    are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH)."""
+    are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).  `stored`: None | "auto" | one bool per batch
+    packet: keep packets raw instead of coding them -- "auto": those whose estimate (hip.estimate_batch, on the split bytes) is
+    not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  See Compressed."""
     import torch
     tensors = list(tensors)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     widths = plane_widths(tensors, planes)
+    stored = _stored_argument(stored, n_packets)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     n = len(sizes)
+    d_stored = d_raw = d_raw_offsets = None
     with torch.cuda.stream(stream) if stream is not None else _nothing():
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
-        d_split = None
-        if widths is not None and any(w != 1 for w in widths):
-            # the split copies of the buffers that are split, back to back (each 16-byte aligned); the others are coded where they are
-            at, split_ptrs = 0, []
-            for p, size, w in zip(ptrs, sizes, widths):
-                split_ptrs.append(at if w != 1 and size else None)
-                at += (size + 15) // 16 * 16 if w != 1 else 0
-            d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
-            split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
-            (d_ptrs, d_bytes, d_fp, d_elem, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, split_ptrs)
-            H.split_planes_batch(d_ptrs, d_bytes, d_fp, d_elem, n, n_packets, d_coded, stream=stream, d_status=d_status)
+        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
+        if stored is None:
+            d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
+            d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
         else:
-            (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
-            d_coded = d_ptrs
-        d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
-        d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
+            # every packet a buffer of its own: the coded ones go to the encoder, the stored ones to the copy, both in batch order
+            _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+            if stored == "auto":
+                d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+                d_flags = (d_est[:n_packets] >= 4 + d_pkt_len).to(torch.int64)
+            else:
+                d_flags = torch.tensor(stored, dtype=torch.int64).to(device)
+            d_len16 = (d_pkt_len + 15) // 16 * 16
+            n_stored, raw_bytes, coded, kept = _partition(d_flags, d_len16)
+            n_coded = n_packets - n_stored
+            d_slots = None
+            d_stream, d_offsets = torch.empty(0, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int64, device=device)
+            if n_coded:
+                d_slots = H.encode_batch(d_pkt_ptr[coded], d_pkt_len[coded], _unit_first_packet(n_coded, device), n_coded, n_coded, stream=stream,
+                                         d_status=d_status, mode=mode, device=device)
+                d_stream, d_offsets = H.compact(d_slots, n_coded, stream=stream)
+            d_raw = torch.zeros(raw_bytes, dtype=torch.uint8, device=device)           # (zeros: the pads behind partial packets)
+            d_raw_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(d_len16[kept], 0)])
+            if n_stored:
+                H.move_packets(d_pkt_ptr[kept], d_raw.data_ptr() + d_raw_offsets[:n_stored], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
+            d_stored = d_flags.to(torch.uint8)
         d_crc = H.crc32_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device) if checksum else None
         _raise_on_status(d_status, "encode_batch")
         # compact() wrote into a buffer of n_packets * 8704 bytes: keep only the compressed bytes (one copy), so that the
@@ -212,7 +346,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None) -> Co
         d_stream = d_stream[:used].clone()
         del d_slots, d_split
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
-                      crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths)
+                      crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
+                      raw_offsets=d_raw_offsets)
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True):
@@ -220,7 +355,8 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
     buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them.  When `c` carries CRCs
     and `verify` is true, the decoded bytes are checked against them (one more launch): a mismatch raises GpuarError naming
     the first buffer and packet that differ.  Buffers that were split into byte planes are merged back in place in `out`
-    after decoding and before verifying: the CRCs are those of the original bytes."""
+    after decoding and before verifying: the CRCs are those of the original bytes.  Packets that were stored raw are copied
+    (one more launch), the others decoded."""
     import torch
     device = c.stream.device
     if out is None:
@@ -234,7 +370,21 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
     with torch.cuda.stream(stream) if stream is not None else _nothing():
         (d_ptrs, d_room, d_fp, d_sizes), _keep = _upload(device, ptrs, room, c.first_packet, c.sizes)
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
-        H.decode_stream_batch(c.stream, c.offsets, d_fp, c.n_buffers, c.n_packets, d_ptrs, d_room, stream=stream, d_status=d_status)
+        if c.stored is None:
+            H.decode_stream_batch(c.stream, c.offsets, d_fp, c.n_buffers, c.n_packets, d_ptrs, d_room, stream=stream, d_status=d_status)
+        elif c.n_packets:
+            # every packet a buffer of its own towards the outputs (its room: the packet's own bytes): the coded ones are decoded,
+            # the stored ones copied
+            _buf, d_pkt_ptr, d_pkt_len = _packets(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets)
+            n_coded = c.offsets.numel() - 1
+            n_stored = c.n_packets - n_coded
+            order = torch.argsort(c.stored, stable=True)
+            coded, kept = order[:n_coded], order[n_coded:]
+            if n_coded:
+                H.decode_stream_batch(c.stream, c.offsets, _unit_first_packet(n_coded, device), n_coded, n_coded, d_pkt_ptr[coded], d_pkt_len[coded],
+                                      stream=stream, d_status=d_status)
+            if n_stored:
+                H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
         if c.planes is not None and any(w != 1 for w in c.planes) and c.n_packets:
             (d_elem,), _keep2 = _upload(device, c.planes)

@@ -41,6 +41,7 @@
 #include "lane_codec.h"
 #include "crc32.h"
 #include "planes.h"
+#include "estimate.h"
 
 namespace gpuar {
 
@@ -2370,6 +2371,155 @@ planes_tail_kernel(PlanesArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Packet size estimate (estimate.h): est[p] = the clen the codec would give packet p, from the packet's byte
+// histogram alone, for one buffer or a batch -- and the copy that moves the packets the estimate says cannot shrink.
+//
+// estimate_kernel has crc32_kernel's shape and reuses its descriptor code (CrcArgs with `crc` as `est`, crc_locate, crc_load):
+// one wavefront per packet, lane l on bytes [128 l, 128 l + 128) as eight 16-byte loads, one workgroup of 16 wavefronts per
+// CU, persistent over the packets.  Each wavefront owns a histogram in LDS: 256 bins of u32, 8 times over -- a lane adds
+// into copy (lane & 7), bin s of copy c at dword 8 s + c, so the eight lanes that read neighbouring bytes never share a
+// counter and a packet of 8192 equal bytes spreads over 8 addresses in 8 banks (4 lanes of a 32-lane half on each) instead
+// of 64 lanes on one.  That is 8 KiB per wavefront, 128 KiB per workgroup.  Nobody but the wavefront touches its histogram,
+// so there is no barrier: LDS operations of one wavefront complete in order.  The wavefront then reads the histogram back as
+// 512 quads (lane l: quads l + 64 k, conflict-free; a quad is four copies of one bin, the neighbouring lane holds the other
+// four), clears it for its next packet, and each lane looks up LF[h] for 4 of the 256 bins in the table built from
+// estimate.h (66 KiB, L2-resident); a wave reduction in u64 follows and lane 0 writes est[p].
+// ---------------------------------------------------------------------------
+__device__ const EstimateTable g_est_table = EstimateTable();
+constexpr uint32_t kEstWaves = 16;
+constexpr uint32_t kEstCopies = 8;
+constexpr uint32_t kEstWaveDwords = 256u * kEstCopies;      // 8 KiB per wavefront
+constexpr uint32_t kEstGroups = 256;                        // one workgroup per CU of an MI355X (128 KiB of LDS each)
+
+__device__ __forceinline__ void est_count(uint32_t *hist, uint32_t w, uint32_t kByte) {      // hist: the lane's copy; kByte static
+    __hip_atomic_fetch_add(hist + (((w >> (8u * kByte)) & 255u) * kEstCopies), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), off), hi = __shfl_xor(static_cast<uint32_t>(v >> 32), off);
+        v += static_cast<uint64_t>(hi) << 32 | lo;
+    }
+    return v;
+}
+
+__global__ void __launch_bounds__(kEstWaves * kLanes)
+estimate_kernel(CrcArgs a) {
+    __shared__ CrcQuad lds[kEstWaves * kEstWaveDwords / 4u];
+    const uint32_t lane = threadIdx.x & 63u;
+    CrcQuad *quads = lds + (threadIdx.x >> 6) * (kEstWaveDwords / 4u);
+    uint32_t *hist = reinterpret_cast<uint32_t *>(quads) + (lane & (kEstCopies - 1u));
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) quads[lane + 64u * k] = CrcQuad(0u);
+    const uint32_t stride = gridDim.x * kEstWaves;
+    for (uint32_t packet = blockIdx.x * kEstWaves + (threadIdx.x >> 6), next; packet < a.n_packets; packet = next) {
+        next = packet + stride;
+        const CrcPacket p = crc_locate(a, packet);
+        if (p.count == 0u) {
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+        } else {
+            CrcQuad q[8];
+            crc_load(q, p, lane);
+            asm volatile("" ::: "memory");                   // the histogram was cleared (by other lanes) in front of these adds
+            if (p.count == kPacket) {                        // wave-uniform
+#pragma unroll
+                for (uint32_t k = 0; k < 8; ++k) {
+                    const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) {
+#pragma unroll
+                        for (uint32_t b = 0; b < 4; ++b) est_count(hist, w[j], b);
+                    }
+                }
+            } else {
+                const uint32_t start = kCrcChunk * lane;
+                const uint32_t have = p.count > start ? (p.count - start < kCrcChunk ? p.count - start : kCrcChunk) : 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < 8; ++k) {
+                    const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) {
+#pragma unroll
+                        for (uint32_t b = 0; b < 4; ++b)
+                            if (16u * k + 4u * j + b < have) est_count(hist, w[j], b);
+                    }
+                }
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // every lane's adds in front of the reads of other lanes' counters
+            // quad l + 64 k: copies 4 (l & 1) .. + 3 of bin (l >> 1) + 32 k; with the neighbouring lane's four that is the bin
+            // both lanes of a pair then hold the pair's 8 bins: the even lane looks up the even k, the odd lane the odd ones
+            using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+            GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+            const bool odd = (lane & 1u) != 0u;
+            uint64_t sum = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < 8; k += 2) {
+                const CrcQuad v0 = quads[lane + 64u * k], v1 = quads[lane + 64u * k + 64u];
+                quads[lane + 64u * k] = CrcQuad(0u);
+                quads[lane + 64u * k + 64u] = CrcQuad(0u);
+                const uint32_t part0 = v0.x + v0.y + v0.z + v0.w, part1 = v1.x + v1.y + v1.z + v1.w;
+                const uint32_t count0 = part0 + __shfl_xor(part0, 1), count1 = part1 + __shfl_xor(part1, 1);
+                sum += lf[odd ? count1 : count0];
+            }
+            sum = wave_sum64(sum);
+            if (lane == 0u) a.crc[packet] = est_clen_from_sum(lf[p.count + 255u], lf[255], sum);
+        }
+        if (next < packet) break;
+    }
+}
+
+// move_packets_kernel: region r is bytes[r] (1 .. 8192) bytes from src[r] to dst[r], both 16-byte aligned -- the packets
+// batch.compress(stored=...) keeps raw.  One workgroup of 512 threads per region, one quad per thread; the region's last,
+// partial quad is loaded whole (nothing beyond the 16-byte piece that holds the last byte) and stored by dwords and bytes
+// (nothing beyond the last byte).  A misaligned pointer or bytes > 8192: BAD_BATCH, the region is skipped.
+constexpr uint32_t kMoveThreads = kPacket / 16u;
+
+struct MoveArgs {
+    const uint8_t *const *src;
+    uint8_t *const *dst;
+    const uint64_t *bytes;
+    uint32_t n_regions;
+    uint32_t *status;
+};
+
+__global__ void __launch_bounds__(kMoveThreads)
+move_packets_kernel(MoveArgs a) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const uint32_t at = 16u * threadIdx.x;
+    for (uint64_t r = blockIdx.x; r < a.n_regions; r += gridDim.x) {
+        const uintptr_t src = reinterpret_cast<uintptr_t>(a.src[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
+        const uint64_t n = a.bytes[r];
+        if (((src | dst) & 15u) != 0u || n > kPacket) {
+            if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        if (at >= n) continue;
+        const uint32_t left = static_cast<uint32_t>(n) - at;
+        const PlanesQuad q = reinterpret_cast<const GlobalQuad *>(src)[threadIdx.x];
+        if (left >= 16u) {
+            reinterpret_cast<GlobalQuad *>(dst)[threadIdx.x] = q;
+        } else {
+            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+            GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
+            GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                if (4u * j + 4u <= left) {
+                    words[j] = w[j];
+                } else {
+#pragma unroll
+                    for (uint32_t b = 0; b < 3; ++b)
+                        if (4u * j + b < left) bytes[4u * j + b] = static_cast<uint8_t>(w[j] >> (8u * b));
+                }
+            }
+        }
+    }
+}
+
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -2755,6 +2905,70 @@ int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem
 
 int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
     return planes_on_host(true, in, n_bytes, elem_bytes, out);
+}
+
+static int launch_estimate(const gpuar::CrcArgs &a, void *stream) {
+    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kEstWaves - 1) / gpuar::kEstWaves;
+    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kEstGroups ? groups : gpuar::kEstGroups);
+    gpuar::estimate_kernel<<<blocks, gpuar::kEstWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_estimate(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, void *stream) {
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the CRC call's checks: same arguments
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::CrcArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.crc = d_est;
+    a.status = status;
+    return launch_estimate(a, stream);
+}
+
+int gpuar_hip_estimate_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                             size_t n_buffers, size_t n_packets, uint32_t *d_est, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::CrcArgs a = {};
+    a.ptrs = d_in_ptrs;
+    a.bytes = d_in_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.crc = d_est;
+    a.status = status;
+    return launch_estimate(a, stream);
+}
+
+int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !est) return GPUAR_ERR_ARGUMENT;
+    gpuar::estimate_host(in, n_bytes, est);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes, size_t n_regions,
+                           uint32_t *d_status, void *stream) {
+    if (n_regions == 0) return GPUAR_OK;
+    if (!d_src_ptrs || !d_dst_ptrs || !d_bytes || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_src_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return GPUAR_ERR_ALIGNMENT;
+    gpuar::MoveArgs a = {};
+    a.src = d_src_ptrs;
+    a.dst = d_dst_ptrs;
+    a.bytes = d_bytes;
+    a.n_regions = static_cast<uint32_t>(n_regions);
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    const uint32_t blocks = a.n_regions < gpuar::kPlaneGridCap ? a.n_regions : gpuar::kPlaneGridCap;
+    gpuar::move_packets_kernel<<<blocks, gpuar::kMoveThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
 }
 
 int gpuar_hip_status(uint32_t *flags) {

@@ -29,6 +29,7 @@ EXPORTS = [
     "gpuar_hip_crc32", "gpuar_hip_verify_crc32", "gpuar_hip_crc32_batch", "gpuar_hip_verify_crc32_batch",
     "gpuar_hip_split_planes", "gpuar_hip_merge_planes", "gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch",
     "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
+    "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
 ]
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -115,6 +116,14 @@ def load() -> C.CDLL:
     for name in ("gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [vp, sz, u32, vp]
+    lib.gpuar_hip_estimate.restype = C.c_int
+    lib.gpuar_hip_estimate.argtypes = [vp, sz, vp, vp]
+    lib.gpuar_hip_estimate_batch.restype = C.c_int
+    lib.gpuar_hip_estimate_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.gpuar_hip_estimate_host.restype = C.c_int
+    lib.gpuar_hip_estimate_host.argtypes = [vp, sz, vp]
+    lib.gpuar_hip_move_packets.restype = C.c_int
+    lib.gpuar_hip_move_packets.argtypes = [vp, vp, vp, sz, vp, vp]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -405,6 +414,59 @@ def split_planes_host(data, elem_bytes: int) -> bytes:
 def merge_planes_host(data, elem_bytes: int) -> bytes:
     """merge_planes of a bytes-like object on the CPU (gpuar_hip_merge_planes_host)."""
     return _planes_host("gpuar_hip_merge_planes_host", data, elem_bytes)
+
+
+def estimate(d_in, n_bytes: int = None, d_est=None, stream=None):
+    """The predicted clen (header included) of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in`, from
+    the packet's byte histogram alone (gpuar_hip_estimate; the definition is in include/gpuar_hip.h).  Returns d_est: int32 CUDA
+    tensor of packet_count(n_bytes) values.  A packet is worth storing raw iff est[p] >= 4 + ulen[p] (stored_rule)."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    npk = packet_count(n)
+    if d_est is None:
+        d_est = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)[:npk]
+    _require_crc(d_est, "d_est", npk)
+    _check(load().gpuar_hip_estimate(d_in.data_ptr(), n, d_est.data_ptr(), _stream_handle(stream)), "gpuar_hip_estimate")
+    return d_est
+
+
+def estimate_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None):
+    """The estimate of every packet of a batch (gpuar_hip_estimate_batch; descriptors as for encode_batch): d_est[p] for batch
+    packet p."""
+    import torch
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_est is None:
+        d_est = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)[:n_packets]
+    _require_crc(d_est, "d_est", n_packets)
+    _check(load().gpuar_hip_estimate_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                           d_est.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_estimate_batch")
+    return d_est
+
+
+def estimate_host(data) -> list:
+    """estimate of a bytes-like object on the CPU (gpuar_hip_estimate_host: no device is touched): one int per packet."""
+    data = bytes(data)
+    est = (C.c_uint32 * max(packet_count(len(data)), 1))()
+    _check(load().gpuar_hip_estimate_host(data, len(data), est), "gpuar_hip_estimate_host")
+    return list(est)[:packet_count(len(data))]
+
+
+def stored_rule(est: int, ulen: int) -> bool:
+    """Whether a packet of `ulen` bytes with estimate `est` is kept raw instead of coded (include/gpuar_hip.h)."""
+    return est >= 4 + ulen
+
+
+def move_packets(d_src_ptrs, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d_status=None):
+    """Copy n_regions regions of d_bytes[r] <= 8192 bytes from d_src_ptrs[r] to d_dst_ptrs[r], all 16-byte aligned
+    (gpuar_hip_move_packets; the three descriptors are 64-bit CUDA tensors)."""
+    for t, name in ((d_src_ptrs, "d_src_ptrs"), (d_dst_ptrs, "d_dst_ptrs"), (d_bytes, "d_bytes")):
+        _require_u64_desc(t, name, n_regions)
+    _check(load().gpuar_hip_move_packets(d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
+                                         _stream_handle(stream)), "gpuar_hip_move_packets")
 
 
 def status() -> int:

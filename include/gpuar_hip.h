@@ -270,6 +270,42 @@ int gpuar_hip_merge_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t
 int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
 int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
 
+/* ------------------------------------------------------------------------
+ * Packet size estimate and raw packets.  The codec's model starts every symbol at count 1, adds 1 per occurrence and never
+ * rescales inside a packet, so a packet's ideal code length depends on its byte histogram h alone.  With
+ *     lg16(k) = floor(2^16 log2 k),   LF[c] = sum of lg16(k) for k = 2 .. c   (LF[0] = LF[1] = 0)
+ *     cost16  = LF[n + 255] - LF[255] - sum over the 256 symbols s of LF[h[s]]
+ * the estimate of a packet of n bytes (1 .. 8192) is
+ *     est = 4 + ((cost16 + 2^19 - 1) >> 19)
+ * (gpuar_amd/csrc/estimate.h: one integer definition for the host and the kernels).  est[p] is the predicted clen of packet p,
+ * its 4-byte header included; against the reference codec's real clen it was within +-1 byte on every packet measured
+ * (INTEGRATION.md).  A packet is worth STORING raw instead of coding iff  est[p] >= 4 + ulen[p]  (ulen[p]: the packet's
+ * uncompressed bytes): its coded form would then be at least 3 bytes longer than the bytes themselves.
+ *
+ * Host-side checks as for the CRC calls, in the same order and before any device work: n_bytes == 0 / n_packets == 0 /
+ * n_regions == 0 is GPUAR_OK with no launch; a null pointer is GPUAR_ERR_ARGUMENT; a data pointer that is not 16-byte
+ * aligned, a d_est not 4-byte, a descriptor array not 8-byte, d_status not 4-byte aligned is GPUAR_ERR_ALIGNMENT.  Nothing
+ * is read beyond the 16-byte-aligned piece of memory that holds a buffer's (a region's) last byte.
+ * ---------------------------------------------------------------------- */
+
+/* est[p] for the gpuar_hip_packet_count(n_bytes) packets of the n_bytes at d_in. */
+int gpuar_hip_estimate(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, void *stream);
+
+/* The same for a batch (descriptors as for gpuar_hip_encode_batch): d_est[p] for batch packet p.  A packet whose descriptor is
+ * unusable is GPUAR_STATUS_BAD_BATCH in d_status, by the encoders' rules, and its d_est[p] is left untouched. */
+int gpuar_hip_estimate_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                             size_t n_buffers, size_t n_packets, uint32_t *d_est, uint32_t *d_status, void *stream);
+
+/* Host only: the same values for host memory, from the same definition -- no device is touched. */
+int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est);
+
+/* Copies n_regions regions: d_bytes[r] bytes (1 .. 8192; 0 moves nothing) from d_src_ptrs[r] to d_dst_ptrs[r], both 16-byte
+ * aligned, the three arrays in device memory and 8-byte aligned.  This is what moves the packets that are stored raw.  Nothing
+ * is written beyond a region's last byte.  A region with a misaligned pointer or more than 8192 bytes is
+ * GPUAR_STATUS_BAD_BATCH in d_status and is skipped: its destination is left untouched. */
+int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes,
+                           size_t n_regions, uint32_t *d_status, void *stream);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
