@@ -23,6 +23,11 @@ packet's compressed size, the packets whose estimate is not smaller than their b
 (hip.move_packets) and only the others go through the encoder -- and, in decompress, the decoder.
 estimate(tensors, ...) gives the predicted sizes without compressing anything.  The .gip container has no raw packets:
 Compressed.gip(b) raises for a buffer that holds one.
+
+With planes="survey" the width of every tensor is chosen by measurement instead of by dtype: survey(tensors) predicts, in one
+launch over the original bytes (hip.survey_planes_batch), what each tensor would compress to at widths 1, 2, 4 and 8, and
+hip.choose_planes picks the smallest width within the estimate's resolution of the best.  That finds the
+element width of typed data held as bytes -- a uint8 view of a checkpoint shard -- which planes="auto" cannot see.
 """
 from __future__ import annotations
 
@@ -194,7 +199,8 @@ def trailer_v3(clens, elem_bytes, crcs=None) -> bytes:
 
 def plane_widths(tensors, planes):
     """The element width per tensor that `planes` asks for: None -> None; "auto" -> each tensor's element_size() where that is
-    2, 4 or 8 and the type is not complex, else 1 (not split); an int -> that width for every tensor; a list -> as given."""
+    2, 4 or 8 and the type is not complex, else 1 (not split); an int -> that width for every tensor; a list -> as given.
+    ("survey" is resolved by survey_widths, which launches; this function never does.)"""
     tensors = list(tensors)
     if planes is None:
         return None
@@ -267,15 +273,50 @@ def _unit_first_packet(n, device):
     return torch.arange(n + 1, dtype=torch.int64, device=device)
 
 
-def estimate(tensors, planes=None, stored=None) -> list:
-    """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
-    estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
-    asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
-    split_planes_batch launch if asked for, one estimate_batch launch."""
+def survey(tensors, stored=None) -> list:
+    """What every tensor would compress to at each byte-plane width, without splitting or encoding anything: per tensor the four
+    predicted totals [T1, T2, T4, T8], T_w = estimate([t], planes=w, stored=stored)[0].  One hip.survey_planes_batch launch over
+    the original bytes and one synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
     import torch
     if stored is not None and stored != "auto":
         raise GpuarError(f"stored={stored!r}: None or \"auto\"")
     tensors = list(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    n = len(sizes)
+    if n_packets == 0:
+        return [[0] * len(H.SURVEY_WIDTHS) for _ in range(n)]
+    d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
+    d_est = H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
+    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
+    if stored == "auto":
+        d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
+    totals = torch.zeros((len(H.SURVEY_WIDTHS), n), dtype=torch.int64, device=device).index_add_(1, buf, d_est)
+    *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
+    if flags:
+        _raise_on_status(d_status, "survey_planes_batch")
+    return [flat[4 * b:4 * b + 4] for b in range(n)]
+
+
+def survey_widths(tensors, stored=None) -> list:
+    """planes="survey": per tensor the width hip.choose_planes picks from survey(tensors, stored) (an empty tensor: 1)."""
+    tensors = list(tensors)
+    _device, _ptrs, _sizes, first_packet, _np = describe(tensors)
+    return [H.choose_planes(totals, first_packet[b + 1] - first_packet[b])
+            for b, totals in enumerate(survey(tensors, stored="auto" if isinstance(stored, str) and stored == "auto" else None))]
+
+
+def estimate(tensors, planes=None, stored=None) -> list:
+    """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
+    estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
+    asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
+    split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front)."""
+    import torch
+    if stored is not None and stored != "auto":
+        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    tensors = list(tensors)
+    if isinstance(planes, str) and planes == "survey":
+        planes = survey_widths(tensors, stored)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     widths = plane_widths(tensors, planes)
     n = len(sizes)
@@ -296,14 +337,19 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
     compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
     every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
-    tensor (plane_widths): split each tensor's bytes into byte planes of that element width before coding (one more launch,
-    into a temporary buffer that is freed with the slots; widths of 1 are coded as they are).  The widths the kernels take
+    tensor (plane_widths) | "survey" (survey_widths: the widths are chosen by a survey of the bytes, one launch and one
+    synchronisation in front, and recorded in Compressed.planes): split each tensor's bytes into byte planes of that element
+    width before coding (one more launch, into a temporary buffer that is freed with the slots; widths of 1 are coded as they are).  The widths the kernels take
     are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).  `stored`: None | "auto" | one bool per batch
     packet: keep packets raw instead of coding them -- "auto": those whose estimate (hip.estimate_batch, on the split bytes) is
     not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  See Compressed."""
     import torch
     tensors = list(tensors)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if isinstance(planes, str) and planes == "survey":
+        stored = _stored_argument(stored, n_packets)
+        with torch.cuda.stream(stream) if stream is not None else _nothing():
+            planes = survey_widths(tensors, stored)
     widths = plane_widths(tensors, planes)
     stored = _stored_argument(stored, n_packets)
     if device is None:

@@ -42,6 +42,7 @@
 #include "crc32.h"
 #include "planes.h"
 #include "estimate.h"
+#include "survey.h"
 
 namespace gpuar {
 
@@ -2520,6 +2521,212 @@ move_packets_kernel(MoveArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Plane-width survey (survey.h): est[j][p] = estimate(split_planes(buffer, 1 << j))[p] for the four widths at
+// once, from one read of the original bytes and without making any split, for one buffer or a batch.
+//
+// One workgroup of 8 wavefronts per SUPERGROUP (8 packets = 65536 bytes of one buffer), persistent over the supergroups, two
+// workgroups resident per CU.  Wavefront e reads eighth e as estimate_kernel reads a packet (lane l: bytes [128 l, 128 l + 128)
+// as eight 16-byte loads) and counts it into the eighth's 8 residue histograms h[e][r], r = byte offset mod 8: bin s of residue
+// r at dword 2048 e + 8 s + r, 8 KiB per wavefront, 64 KiB in all -- u32 counters, because packed u16 increments cost three
+// more vector instructions per byte (4.7) and 64 KiB already fits twice in a CU.  A byte's residue is its position in its
+// 8-byte pair, so one lane's eight adds go to eight histograms; so that the 64 lanes of ONE add do not, every lane rotates its
+// pair by (lane & 7) bytes first (two v_alignbyte_b32 and two selects per 8 bytes): in step t a lane counts its byte
+// (t + lane) & 7, and a packet of equal bytes spreads every add over 8 counters in 8 banks, as estimate_kernel's copies do.
+// Behind a barrier, thread (half, s) sums, for bin s, the 32 counters of its half's four eighths into the bin of 4 packets of
+// each width (for w = 8: its half's four residues, with the other half's eighths), looks the 16 counts up in LF, and 16 wave
+// sums, a 1 KiB exchange and 32 threads give the 32 estimates: one writer each.
+// A buffer's last, short supergroup (1 .. 65535 bytes) takes the general path: each byte is added to the packet histogram it
+// lands in at each width (survey_packet: the tail rule of planes.h), 32 histograms of 256 u32 in the same LDS.  It reads by
+// 16-byte pieces, never beyond the piece that holds the last byte, and is bounded by one supergroup per buffer.
+// In a batch, window u = batch packets [8 u, 8 u + 8) belongs to one workgroup, which takes every supergroup that STARTS there
+// (one for a large buffer, up to eight for short ones).  A buffer the survey cannot take -- misaligned, or not owning exactly
+// the packets its bytes make -- is BAD_BATCH and none of its entries is written; so is a packet nobody owns.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSurveyWaves = 8;                                    // one wavefront per eighth
+constexpr uint32_t kSurveyThreads = kSurveyWaves * kLanes;
+constexpr uint32_t kSurveyEighthDwords = 8u * 256u;                     // 8 residues x 256 bins
+constexpr uint32_t kSurveyGroups = 512;                                 // two workgroups per CU of an MI355X (65 KiB of LDS each)
+
+struct SurveyArgs {
+    const uint8_t *in;                      // one buffer: `in`, `n_bytes` ...
+    size_t n_bytes;
+    const uint8_t *const *ptrs;             // ... or a batch (ptrs != nullptr)
+    const uint64_t *bytes;
+    const uint64_t *first_packet;
+    uint32_t n_buffers;
+    uint32_t n_packets;
+    uint32_t *est;                          // row j at est + j * stride
+    size_t stride;
+    uint32_t *status;
+};
+
+// the 8 bytes {lo, hi} of a lane, rotated by c = lane & 7 bytes: step t counts byte (t + c) & 7 into residue (t + c) & 7, whose
+// histogram (and the wavefront's base) is in slot[t]
+__device__ __forceinline__ void survey_count8(uint32_t *hist, uint32_t lo, uint32_t hi, uint32_t c, const uint32_t (&slot)[8]) {
+    const uint32_t a = __builtin_amdgcn_alignbyte(hi, lo, c & 3u), b = __builtin_amdgcn_alignbyte(lo, hi, c & 3u);
+    const uint32_t first = (c & 4u) ? b : a, second = (c & 4u) ? a : b;
+#pragma unroll
+    for (uint32_t t = 0; t < 4; ++t) {
+        __hip_atomic_fetch_add(hist + (((first >> (8u * t)) & 255u) * 8u + slot[t]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(hist + (((second >> (8u * t)) & 255u) * 8u + slot[4u + t]), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+// one supergroup: `len` bytes (1 .. 65536) at `sg` (16-byte aligned), whose first packet is entry `first` of every row; the whole
+// workgroup, with the histograms clear on entry and on return
+__device__ __forceinline__ void survey_supergroup(const SurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, CrcQuad *lds,
+                                                  uint64_t (*sums)[16]) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, eighths / packets 4 half .. + 3
+    const bool full = len == kSurveyBytes;                                   // workgroup-uniform
+    if (full) {
+        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + wave * kPacket + kCrcChunk * lane));
+        CrcQuad q[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
+        const uint32_t c = lane & 7u;
+        uint32_t slot[8];
+#pragma unroll
+        for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            survey_count8(hist, q[k].x, q[k].y, c, slot);
+            survey_count8(hist, q[k].z, q[k].w, c, slot);
+        }
+    } else {
+        // the general path: packet histogram (j, p) at dword (8 j + p) * 256
+        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg));
+        for (uint32_t i = threadIdx.x; i * 16u < len; i += kSurveyThreads) {
+            const CrcQuad q = src[i];
+            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (uint32_t d = 0; d < 4; ++d) {
+#pragma unroll 1
+                for (uint32_t b = 0; b < 4; ++b) {
+                    const uint32_t o = 16u * i + 4u * d + b, byte = (w[d] >> (8u * b)) & 255u;
+                    if (o >= len) break;
+#pragma unroll
+                    for (uint32_t j = 0; j < kSurveyWidths; ++j)
+                        __hip_atomic_fetch_add(hist + ((j * kSurveyPackets + survey_packet(o, len, j)) * 256u + byte), 1u, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // cnt[4 j + m]: bin s of packet 4 half + m at width 1 << j
+    uint32_t cnt[16];
+    if (full) {
+        CrcQuad lo[4], hi[4], other[4];      // residues 0-3 and 4-7 of the half's own eighths; residues 4 half .. + 3 of the other half's
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) {
+            lo[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u];
+            hi[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u];
+            other[e] = lds[((4u * (1u - half) + e) * kSurveyEighthDwords + 8u * s) / 4u + half];
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) cnt[e] = lo[e].x + lo[e].y + lo[e].z + lo[e].w + hi[e].x + hi[e].y + hi[e].z + hi[e].w;
+#pragma unroll
+        for (uint32_t g = 0; g < 2; ++g) {
+            const CrcQuad t = lo[2 * g] + hi[2 * g] + lo[2 * g + 1] + hi[2 * g + 1];
+            cnt[4 + 2 * g] = t.x + t.z;
+            cnt[4 + 2 * g + 1] = t.y + t.w;
+        }
+        const CrcQuad l4 = lo[0] + lo[1] + lo[2] + lo[3], h4 = hi[0] + hi[1] + hi[2] + hi[3];
+        const CrcQuad w4 = l4 + h4, w8 = (half ? h4 : l4) + other[0] + other[1] + other[2] + other[3];
+        cnt[8] = w4.x, cnt[9] = w4.y, cnt[10] = w4.z, cnt[11] = w4.w;
+        cnt[12] = w8.x, cnt[13] = w8.y, cnt[14] = w8.z, cnt[15] = w8.w;
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) cnt[i] = hist[((i >> 2) * kSurveyPackets + 4u * half + (i & 3u)) * 256u + s];
+    }
+    // 16 wave sums in 17 exchanges instead of 96: every step halves the values a lane carries (it keeps the half its lane bit
+    // names and hands the other half to its partner), so lane l ends with the whole wavefront's sum of value l >> 2
+    uint64_t sum[16];
+#pragma unroll
+    for (uint32_t i = 0; i < 16; ++i) sum[i] = lf[cnt[i]];
+#pragma unroll
+    for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
+        const bool upper = (lane & off) != 0u;
+#pragma unroll
+        for (uint32_t m = 0; m < n; ++m) {
+            const uint64_t keep = upper ? sum[m + n] : sum[m], give = upper ? sum[m] : sum[m + n];
+            const uint32_t lo = __shfl_xor(static_cast<uint32_t>(give), off), hi = __shfl_xor(static_cast<uint32_t>(give >> 32), off);
+            sum[m] = keep + (static_cast<uint64_t>(hi) << 32 | lo);
+        }
+    }
+#pragma unroll
+    for (uint32_t off = 2; off >= 1; off >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(sum[0]), off), hi = __shfl_xor(static_cast<uint32_t>(sum[0] >> 32), off);
+        sum[0] += static_cast<uint64_t>(hi) << 32 | lo;
+    }
+    if ((lane & 3u) == 0u) sums[wave][lane >> 2] = sum[0];
+    __syncthreads();
+    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
+    }
+    if (threadIdx.x < 32u) {
+        const uint32_t i = threadIdx.x & 15u, hh = threadIdx.x >> 4, p = 4u * hh + (i & 3u);
+        if (p * kPacket < len) {
+            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
+            const uint64_t total = sums[4u * hh][i] + sums[4u * hh + 1u][i] + sums[4u * hh + 2u][i] + sums[4u * hh + 3u][i];
+            GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(a.est));
+            est[(i >> 2) * a.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
+        }
+    }
+    __syncthreads();      // the clears and the reads of `sums` in front of the next supergroup
+}
+
+__global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_per_eu(4)))      // two workgroups per CU: 128 VGPRs
+survey_planes_kernel(SurveyArgs a) {
+    __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
+    __shared__ uint64_t sums[kSurveyWaves][16];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
+    __syncthreads();
+    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
+    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
+        uint64_t p = 8ull * u;
+        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
+        while (p < end) {                   // (every value here is the same in all threads)
+            const uint8_t *sg = nullptr;
+            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
+            if (!a.ptrs) {                  // one buffer: the window is the supergroup
+                sg = a.in + p * kPacket;
+                left = a.n_bytes - p * kPacket;
+            } else {
+                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
+                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
+                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    next = p + 1u;
+                } else {
+                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
+                    const uint64_t j = p - lead;
+                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
+                    if (!bl.owned || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
+                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
+                        sg = bl.ptr;
+                        left = n_bytes - j * kPacket;
+                    }
+                }
+            }
+            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
+            if (len != 0u) survey_supergroup(a, sg, len, p, lds, sums);
+            p = next;
+        }
+    }
+}
+
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -2951,6 +3158,58 @@ int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est) {
     gpuar::estimate_host(in, n_bytes, est);
     return GPUAR_OK;
 }
+
+static int launch_survey(const gpuar::SurveyArgs &a, void *stream) {
+    const uint32_t windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
+    const uint32_t blocks = windows < gpuar::kSurveyGroups ? windows : gpuar::kSurveyGroups;
+    gpuar::survey_planes_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_survey_planes(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, size_t est_stride, void *stream) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (est_stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the estimate call's checks
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::SurveyArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.est = d_est;
+    a.stride = est_stride;
+    a.status = status;
+    return launch_survey(a, stream);
+}
+
+int gpuar_hip_survey_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                                  size_t n_buffers, size_t n_packets, uint32_t *d_est, size_t est_stride, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (est_stride < n_packets) return GPUAR_ERR_ARGUMENT;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::SurveyArgs a = {};
+    a.ptrs = d_in_ptrs;
+    a.bytes = d_in_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.est = d_est;
+    a.stride = est_stride;
+    a.status = status;
+    return launch_survey(a, stream);
+}
+
+int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *est, size_t est_stride) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !est || est_stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
+    gpuar::survey_host(in, n_bytes, est, est_stride);
+    return GPUAR_OK;
+}
+
+uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets) { return total ? gpuar::choose_width(total, n_packets) : 1u; }
 
 int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes, size_t n_regions,
                            uint32_t *d_status, void *stream) {

@@ -4,7 +4,9 @@
 #include <unistd.h>
 
 #include <cstdlib>
+#include <vector>
 
+#include "../survey.h"
 #include "gpuar_hip.h"
 
 namespace gip {
@@ -40,6 +42,33 @@ size_t Compressor::getFileSize(FILE *stream) {
     const long end = std::ftell(stream);
     std::fseek(stream, at, SEEK_SET);
     return end < 0 ? 0 : static_cast<size_t>(end);
+}
+
+int Compressor::choosePlanes(unsigned long long total[4]) {
+    const int fd = ::open(openFileName.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("Can not open input file: " + openFileName);
+    std::vector<uint8_t> head(kSurveyPrefix);
+    size_t n = 0;
+    while (n < head.size()) {
+        const ssize_t got = ::pread(fd, head.data() + n, head.size() - n, static_cast<off_t>(n));
+        if (got < 0) {
+            ::close(fd);
+            throw std::runtime_error("Can not read input file: " + openFileName);
+        }
+        if (got == 0) break;
+        n += static_cast<size_t>(got);
+    }
+    ::close(fd);
+    const size_t n_packets = (n + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES;
+    std::vector<uint32_t> est(gpuar::kSurveyWidths * n_packets);
+    gpuar::survey_host(head.data(), n, est.data(), n_packets);
+    uint64_t sums[gpuar::kSurveyWidths] = {};
+    for (uint32_t j = 0; j < gpuar::kSurveyWidths; ++j) {
+        for (size_t p = 0; p < n_packets; ++p) sums[j] += est[j * n_packets + p];
+        total[j] = sums[j];
+    }
+    planes = static_cast<int>(gpuar::choose_width(sums, n_packets));
+    return planes;
 }
 
 void Compressor::closeFiles() {

@@ -83,6 +83,12 @@ class Compressor {
         if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) throw std::invalid_argument("planes: the element width is 1, 2, 4 or 8");
         planes = elem_bytes;
     }
+    // `--planes=auto`: sets the width from the input's own bytes and returns it -- gpuar::choose_width of the totals that
+    // gpuar::survey_host (../survey.h) predicts for the first min(file size, kSurveyPrefix) bytes taken as a buffer of their own,
+    // written to total[4] (widths 1, 2, 4, 8).  On the host, from one pread, before either pipeline starts: the prefix is a
+    // constant, so the file written does not depend on --batch, --gpus, --threads or --host.
+    static constexpr size_t kSurveyPrefix = size_t(16) << 20;
+    int choosePlanes(unsigned long long total[4]);
     virtual CompressionInfo compress(ProgressMonitor *monitor) = 0;
     virtual CompressionInfo decompress(ProgressMonitor *monitor) = 0;
     void closeFiles();

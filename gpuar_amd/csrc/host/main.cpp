@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -57,7 +57,8 @@ void usage() {
     std::cout << "--index       (compress) append the packet-offset index trailer; decompress uses it when present" << std::endl;
     std::cout << "--checksum    (compress) append the trailer with a CRC-32 per packet (and the index); decompress verifies it when present" << std::endl;
     std::cout << "--planes      (compress) W = 2, 4 or 8: split the input into byte planes of W-byte elements first (typed data compresses better);" << std::endl;
-    std::cout << "              the file then carries a trailer with W, which decompress needs; 1 = off (default)" << std::endl;
+    std::cout << "              the file then carries a trailer with W, which decompress needs; 1 = off (default);" << std::endl;
+    std::cout << "              auto: W is chosen from the first 16 MiB of the input (a histogram pass on the host predicts its size at every W)" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
@@ -66,7 +67,7 @@ void usage() {
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip";
-    bool has_in = false;
+    bool has_in = false, planes_auto = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
@@ -109,9 +110,10 @@ int main(int argc, char **argv) {
             threads = std::atoi(v);
         } else if (flag_name_is(argv[i], "planes", &v)) {
             if (!take(&v)) break;
-            planes = !std::strcmp(v, "1") ? 1 : !std::strcmp(v, "2") ? 2 : !std::strcmp(v, "4") ? 4 : !std::strcmp(v, "8") ? 8 : 0;
+            planes_auto = !std::strcmp(v, "auto");
+            planes = planes_auto || !std::strcmp(v, "1") ? 1 : !std::strcmp(v, "2") ? 2 : !std::strcmp(v, "4") ? 4 : !std::strcmp(v, "8") ? 8 : 0;
             if (!planes) {
-                std::cerr << "--planes takes 1, 2, 4 or 8: " << v << std::endl;
+                std::cerr << "--planes takes 1, 2, 4, 8 or auto: " << v << std::endl;
                 return 2;
             }
         } else if (flag_name_is(argv[i], "batch", &v)) {
@@ -159,6 +161,12 @@ int main(int argc, char **argv) {
         compressor->setSaveFileName(out);
         CompressionInfo info;
         if (!decompress) {
+            if (planes_auto) {
+                unsigned long long total[4];
+                const int w = compressor->choosePlanes(total);
+                std::cout << "planes=auto: width " << w << " (predicted bytes at widths 1, 2, 4, 8: " << total[0] << ", " << total[1] << ", "
+                          << total[2] << ", " << total[3] << ")" << std::endl;
+            }
             std::cout << "Start to compress " << in << " to " << out << "." << std::endl;
             info = compressor->compress(&monitor);
         } else {

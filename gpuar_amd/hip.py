@@ -30,7 +30,9 @@ EXPORTS = [
     "gpuar_hip_split_planes", "gpuar_hip_merge_planes", "gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch",
     "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
     "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
+    "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
 ]
+SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
 MODE_ID = {"auto": 0, "throughput": 1, "latency": 2}     # GPUAR_MODE_*
@@ -124,6 +126,14 @@ def load() -> C.CDLL:
     lib.gpuar_hip_estimate_host.argtypes = [vp, sz, vp]
     lib.gpuar_hip_move_packets.restype = C.c_int
     lib.gpuar_hip_move_packets.argtypes = [vp, vp, vp, sz, vp, vp]
+    lib.gpuar_hip_survey_planes.restype = C.c_int
+    lib.gpuar_hip_survey_planes.argtypes = [vp, sz, vp, sz, vp]
+    lib.gpuar_hip_survey_planes_batch.restype = C.c_int
+    lib.gpuar_hip_survey_planes_batch.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp]
+    lib.gpuar_hip_survey_planes_host.restype = C.c_int
+    lib.gpuar_hip_survey_planes_host.argtypes = [vp, sz, vp, sz]
+    lib.gpuar_hip_choose_planes.restype = u32
+    lib.gpuar_hip_choose_planes.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -453,6 +463,66 @@ def estimate_host(data) -> list:
     est = (C.c_uint32 * max(packet_count(len(data)), 1))()
     _check(load().gpuar_hip_estimate_host(data, len(data), est), "gpuar_hip_estimate_host")
     return list(est)[:packet_count(len(data))]
+
+
+def _require_survey(d_est, npk):
+    """A survey's output: a contiguous 4-byte CUDA tensor of shape (4, stride), stride >= npk."""
+    import torch
+    if not (isinstance(d_est, torch.Tensor) and d_est.is_cuda and d_est.element_size() == 4 and d_est.is_contiguous() and d_est.dim() == 2
+            and d_est.shape[0] == len(SURVEY_WIDTHS) and d_est.shape[1] >= npk):
+        raise GpuarError(f"d_est must be a contiguous 32-bit CUDA tensor of shape (4, at least {npk})")
+
+
+def survey_planes(d_in, d_est=None, n_bytes: int = None, stream=None):
+    """The estimate of every packet of the first `n_bytes` (default: all) bytes of `d_in` split into byte planes of width 1, 2, 4
+    and 8, from one read of the bytes and without splitting anything (gpuar_hip_survey_planes): row j of the result is what
+    estimate(split_planes(d_in, SURVEY_WIDTHS[j])) gives.  Returns d_est: int32 CUDA tensor of shape (4, packet_count(n_bytes))
+    (the caller's may be wider: its second dimension is the row stride)."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    npk = packet_count(n)
+    if d_est is None:
+        d_est = torch.empty((len(SURVEY_WIDTHS), npk), dtype=torch.int32, device=d_in.device)
+    _require_survey(d_est, npk)
+    _check(load().gpuar_hip_survey_planes(d_in.data_ptr(), n, d_est.data_ptr(), d_est.shape[1], _stream_handle(stream)), "gpuar_hip_survey_planes")
+    return d_est
+
+
+def survey_planes_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None):
+    """The survey of every buffer of a batch in one launch (gpuar_hip_survey_planes_batch; descriptors as for encode_batch):
+    d_est[j, p] for width SURVEY_WIDTHS[j] and batch packet p."""
+    import torch
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_est is None:
+        d_est = torch.empty((len(SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device or d_ptrs.device)
+    _require_survey(d_est, n_packets)
+    _check(load().gpuar_hip_survey_planes_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                                d_est.data_ptr(), d_est.shape[1], _status_ptr(d_status), _stream_handle(stream)),
+           "gpuar_hip_survey_planes_batch")
+    return d_est
+
+
+def survey_planes_host(data) -> list:
+    """survey_planes of a bytes-like object on the CPU (gpuar_hip_survey_planes_host: no device is touched): four lists, one per
+    width of SURVEY_WIDTHS, of one int per packet."""
+    data = bytes(data)
+    npk = packet_count(len(data))
+    est = (C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))()
+    _check(load().gpuar_hip_survey_planes_host(data, len(data), est, npk), "gpuar_hip_survey_planes_host")
+    return [list(est[j * npk:(j + 1) * npk]) for j in range(len(SURVEY_WIDTHS))]
+
+
+def choose_planes(totals, n_packets: int) -> int:
+    """The width to split by, from the four predicted totals at widths 1, 2, 4, 8 (gpuar_hip_choose_planes): the smallest width
+    whose total is at most the lowest total + n_packets."""
+    totals = [int(t) for t in totals]
+    if len(totals) != len(SURVEY_WIDTHS) or min(totals) < 0:
+        raise GpuarError(f"choose_planes: four non-negative totals, not {totals}")
+    return int(load().gpuar_hip_choose_planes((C.c_uint64 * 4)(*totals), n_packets))
 
 
 def stored_rule(est: int, ulen: int) -> bool:

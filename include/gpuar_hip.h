@@ -306,6 +306,35 @@ int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est);
 int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes,
                            size_t n_regions, uint32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Plane-width survey: what a buffer would compress to at each byte-plane width, from one read of its bytes.  For a buffer of
+ * P packets and j = 0 .. 3 (the widths w = 1, 2, 4, 8),
+ *     d_est[j * est_stride + p]  =  the gpuar_hip_estimate value of packet p of gpuar_hip_split_planes(buffer, w)
+ * for every p < P, by definition (gpuar_amd/csrc/survey.h); no split is made and nothing but d_est is written.  The sum of row
+ * j is the size predicted for width w; gpuar_hip_choose_planes picks a width from the four sums.
+ *
+ * Host-side checks as for gpuar_hip_estimate, in the same order; in addition est_stride must be at least the packet count
+ * (GPUAR_ERR_ARGUMENT).  Nothing is read beyond the 16-byte-aligned piece of memory that holds a buffer's last byte.
+ * ---------------------------------------------------------------------- */
+
+/* The four rows for the n_bytes at d_in. */
+int gpuar_hip_survey_planes(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, size_t est_stride, void *stream);
+
+/* The same for a batch (descriptors as for gpuar_hip_encode_batch): column p of d_est is batch packet p.  A buffer whose pointer
+ * is not 16-byte aligned or that does not own exactly the packets its bytes make is GPUAR_STATUS_BAD_BATCH in d_status, and
+ * its columns are left untouched in all four rows; a packet that no buffer owns likewise. */
+int gpuar_hip_survey_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                                  size_t n_buffers, size_t n_packets, uint32_t *d_est, size_t est_stride, uint32_t *d_status,
+                                  void *stream);
+
+/* Host only: the same values for host memory, from the same definition -- no device is touched. */
+int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *est, size_t est_stride);
+
+/* Host only, pure: the width to split by, from the four predicted totals (bytes at w = 1, 2, 4, 8) of a buffer of n_packets
+ * packets: the SMALLEST w whose total is at most the lowest total + n_packets.  One byte per packet is the estimate's
+ * resolution; on data of element width w every multiple of w ties within it, and the smallest is the cheapest to split. */
+uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
