@@ -170,29 +170,22 @@ class Compressed:
             clens = [off[i + 1] - off[i] for i in range(lo, hi)]
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
             crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
-            out += trailer_v3(clens, w, crcs) if w > 1 else trailer_v2(clens, crcs)
+            out += trailer(clens, w, crcs)
         return out
 
 
-def trailer_v2(clens, crcs) -> bytes:
-    """The .gip trailer version 2: "GIPX" u32 2 u64 n | u16 clen[n] | pad to 4 | u32 crc32[n] | pad to 8 |
-    u64 trailer bytes "XPIG", little-endian."""
+def trailer(clens, elem_bytes=1, crcs=None) -> bytes:
+    """The .gip trailer, little-endian, pads counted from "GIPX": version 3 for a file whose bytes were split
+    into planes of `elem_bytes` > 1, else version 2 when `crcs` are given, else version 1.
+    "GIPX" u32 version u64 n | version 3: u32 elem_bytes u32 flags (bit 0: CRCs present) | u16 clen[n] |
+    with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG"."""
     n = len(clens)
-    body = b"GIPX" + struct.pack("<IQ", 2, n) + struct.pack(f"<{n}H", *clens)
-    body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
-    body += bytes(-len(body) % 8)
-    return body + struct.pack("<Q", len(body) + 12) + b"XPIG"
-
-
-def trailer_v3(clens, elem_bytes, crcs=None) -> bytes:
-    """The .gip trailer version 3 of a file whose bytes were split into planes of `elem_bytes`: "GIPX" u32 3
-    u64 n | u32 elem_bytes | u32 flags (bit 0: CRCs present) | u16 clen[n] | pad to 4 | u32 crc32[n] if flagged | pad to 8 |
-    u64 trailer bytes "XPIG", little-endian, pads counted from "GIPX"."""
-    n = len(clens)
-    body = b"GIPX" + struct.pack("<IQII", 3, n, elem_bytes, 1 if crcs is not None else 0) + struct.pack(f"<{n}H", *clens)
-    body += bytes(-len(body) % 4)
+    body = b"GIPX" + struct.pack("<IQ", 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
+    if elem_bytes > 1:
+        body += struct.pack("<II", elem_bytes, 0 if crcs is None else 1)
+    body += struct.pack(f"<{n}H", *clens)
     if crcs is not None:
-        body += struct.pack(f"<{n}I", *crcs)
+        body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
     body += bytes(-len(body) % 8)
     return body + struct.pack("<Q", len(body) + 12) + b"XPIG"
 

@@ -8,8 +8,11 @@
 #include <cstdio>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 #include "compress_info.hpp"
+#include "file_header.hpp"
+#include "packet_index.hpp"
 #include "progress_monitor.hpp"
 
 namespace gip {
@@ -57,6 +60,33 @@ class Compressor {
     }
     static void warnMalformedTrailer() {
         std::fprintf(stderr, "Warning: ignoring a malformed checksum trailer: nothing was verified\n");
+    }
+
+    // The trailer of the open .gip (packet_index.hpp), empty when there is none a reader may use: one that says version 3 and
+    // cannot be used is an error, one that says version 2 and does not fit a warning.
+    Trailer loadTrailer(size_t stream_end, size_t fileSize) {
+        Trailer trailer;
+        const Trailer::Status status = Trailer::load(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, trailer);
+        if (status == Trailer::Status::unusable) throw planesTrailerError();
+        if (status == Trailer::Status::malformed) warnMalformedTrailer();
+        return trailer;
+    }
+    // compress: whether the options ask for a trailer, and that trailer appended at the current position of the output
+    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1; }
+    void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs) {
+        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr);
+    }
+    static constexpr size_t kPacketBytes = 8192;
+    // What a trailer of `n_packets` packets says of the bytes that packet `packet` of the file holds by its header (`ulen`).
+    // Byte planes: every packet but the file's last holds 8192 bytes, or the groups are not where the merge takes them to be.
+    static void checkPlanesPacket(size_t packet, size_t n_packets, size_t ulen) {
+        if (packet + 1 < n_packets && ulen != kPacketBytes) throw planesPacketError(packet);
+    }
+    // CRCs: they cover the packets' original bytes, all 8192 long but the file's last, which holds 1 .. 8192: a packet that says
+    // otherwise does not decode to them.
+    static void checkChecksumPacket(size_t packet, size_t n_packets, size_t ulen) {
+        const uint64_t begin = static_cast<uint64_t>(packet) * kPacketBytes;
+        if (packet + 1 < n_packets ? ulen != kPacketBytes : ulen == 0) throw checksumError(packet, begin, begin + (ulen < kPacketBytes ? ulen : kPacketBytes));
     }
 
     // where the packets of an open .gip end: the header's size field when it is sane (the reference's

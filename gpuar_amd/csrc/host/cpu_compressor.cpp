@@ -109,7 +109,7 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
     std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
-    const bool trailer = writeIndex || writeChecksum || planes > 1;
+    const bool trailer = wantsTrailer();
     try {
         for (;;) {
             io_timer.start();
@@ -140,8 +140,7 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
             monitor->updateProgress(&info);
         }
         io_timer.start();
-        if (planes > 1) PacketIndex::writePlanes(saveFile, all_clens, static_cast<uint32_t>(planes), writeChecksum ? &all_crcs : nullptr);
-        else if (trailer) PacketIndex::write(saveFile, all_clens, writeChecksum ? &all_crcs : nullptr);
+        saveTrailer(all_clens, all_crcs);
         FileHeader header;
         header.setCompressedFileSize(info.compressedFileSize);
         header.setUncompressedFileSize(info.uncompressedFileSize);
@@ -173,19 +172,11 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
             throw std::runtime_error("Incorrect file format");
         info = header.getInfo(fileSize);
         const size_t stream_end = streamEnd(info, fileSize);
-        std::vector<uint16_t> index;
-        std::vector<uint32_t> crcs;              // per packet, from a version-2 trailer: every decoded packet is checked against them
-        // a version-3 trailer first: the packets then hold byte planes of elements `width` bytes wide, merged back below
-        uint32_t width = 1;
-        bool planes_crcs = false;
-        const PacketIndex::Planes split = PacketIndex::findPlanes(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs, width, planes_crcs);
-        if (split == PacketIndex::Planes::unusable) throw planesTrailerError();
-        const bool merging = split == PacketIndex::Planes::ok;
-        PacketIndex::Found found = PacketIndex::Found::none;
-        if (!merging) found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
-        if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
-        const bool indexed = merging || found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
-        const bool verify = merging ? planes_crcs : found == PacketIndex::Found::v2;
+        // packet lengths, per-packet CRCs (every decoded packet is checked against them) and the width of the byte planes the
+        // packets hold (merged back below), as far as the file's trailer gives them
+        const Trailer trailer = loadTrailer(stream_end, fileSize);
+        const std::vector<uint16_t> &index = trailer.clens;
+        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging();
         size_t first_packet = 0;                 // of the window
         io_timer.stop();
 
@@ -242,22 +233,19 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                 ulen[p] = static_cast<uint32_t>(decode_one(window.data() + offsets[p], window.data() + bytes, plain + p * gpuar::kPacket));
             });
             if (merging) {
-                // every packet but the file's last holds 8192 bytes, or the groups are not where the merge takes them to be
                 size_t total = 0;
                 for (size_t p = 0; p < np; ++p) {
-                    if (first_packet + p + 1 < index.size() && ulen[p] != gpuar::kPacket) throw planesPacketError(first_packet + p);
+                    checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
                     total += ulen[p];
                 }
-                gpuar::planes_host<true>(decoded.data(), total, width, out.data());
+                gpuar::planes_host<true>(decoded.data(), total, trailer.elem_bytes, out.data());
             }
             if (verify) {
-                // the CRC covers the packet's original bytes: all of them 8192 long but the file's last one, which holds 1 .. 8192
                 for (size_t p = 0; p < np; ++p) {
                     const size_t g = first_packet + p;
                     const uint64_t begin = static_cast<uint64_t>(g) * gpuar::kPacket;
-                    if ((g + 1 < crcs.size() ? ulen[p] != gpuar::kPacket : ulen[p] == 0) ||
-                        gpuar::crc32_update(0, out.data() + p * gpuar::kPacket, ulen[p]) != crcs[g])
-                        throw checksumError(g, begin, begin + ulen[p]);
+                    checkChecksumPacket(g, trailer.crcs.size(), ulen[p]);
+                    if (gpuar::crc32_update(0, out.data() + p * gpuar::kPacket, ulen[p]) != trailer.crcs[g]) throw checksumError(g, begin, begin + ulen[p]);
                 }
             }
             first_packet += np;

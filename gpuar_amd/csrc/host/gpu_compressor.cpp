@@ -794,7 +794,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
         // length is set at the end (best effort: a file system without fallocate just grows the file as it goes)
         // (the fallocate system call, not posix_fallocate: where the file system cannot do it, glibc's stand-in would write zeros)
         (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(FileHeader::HEADER_LENGTH + total_packets * kSlot));
-        const bool trailer = writeIndex || writeChecksum || planes > 1;
+        const bool trailer = wantsTrailer();
         std::vector<std::vector<uint16_t>> chunk_clens(trailer ? n_chunks : 0);        // for the optional index trailer
         std::vector<std::vector<uint32_t>> chunk_crcs(writeChecksum ? n_chunks : 0);   // and the checksums in it
         std::vector<std::atomic<size_t>> next_of_device(G);
@@ -880,8 +880,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
             std::vector<uint32_t> crcs;
             for (const auto &v : chunk_crcs) crcs.insert(crcs.end(), v.begin(), v.end());
             if (std::fseek(saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
-            if (planes > 1) PacketIndex::writePlanes(saveFile, all, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr);
-            else PacketIndex::write(saveFile, all, writeChecksum ? &crcs : nullptr);
+            saveTrailer(all, crcs);
             if (std::fflush(saveFile) != 0) throw std::runtime_error("Write packet index failed");
             file_end = static_cast<uint64_t>(std::ftell(saveFile));
         }
@@ -1065,20 +1064,12 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         MappedInput mapped;
         mapped.open(in_fd, fileSize);
         mapped.warmFirstWindow(devices[0]);
-        // packet lengths from the index trailer when the file has one (packet_index.hpp)
-        std::vector<uint16_t> index;
-        std::vector<uint32_t> crcs;      // a version-2 trailer's CRC-32s: every decoded chunk is verified against them
-        // a version-3 trailer first: the packets then hold byte planes of elements `width` bytes wide, merged back on the device
-        uint32_t width = 1;
-        bool planes_crcs = false;
-        const PacketIndex::Planes split = PacketIndex::findPlanes(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs, width, planes_crcs);
-        if (split == PacketIndex::Planes::unusable) throw planesTrailerError();
-        const bool merging = split == PacketIndex::Planes::ok;
-        PacketIndex::Found found = PacketIndex::Found::none;
-        if (!merging) found = PacketIndex::find(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, index, crcs);
-        if (found == PacketIndex::Found::malformed) warnMalformedTrailer();
-        const bool indexed = merging || found == PacketIndex::Found::v1 || found == PacketIndex::Found::v2;
-        const bool verify = merging ? planes_crcs : found == PacketIndex::Found::v2;
+        // packet lengths, per-packet CRCs (every decoded chunk is verified against them) and the width of the byte planes the
+        // packets hold (merged back on the device), as far as the file's trailer gives them (packet_index.hpp)
+        const Trailer trailer = loadTrailer(stream_end, fileSize);
+        const std::vector<uint16_t> &index = trailer.clens;
+        const std::vector<uint32_t> &crcs = trailer.crcs;
+        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging();
 
         ChunkMap map;
         std::thread scanner;
@@ -1205,11 +1196,10 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 const uint8_t *pkt = bytes + off;
                                 const size_t clen = getPacketSize(pkt);
                                 if (clen < GPUAR_PACKET_HEADER_BYTES || off + clen > n_stream) throw std::runtime_error("Invalid file length");
-                                const size_t ulen = std::min<size_t>(kPacket, pkt[2] | (static_cast<size_t>(pkt[3]) << 8));
+                                const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
                                 all_full = all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
-                                // byte planes: every packet but the file's last holds 8192 bytes, or the groups are not where the merge
-                                // takes them to be (so every chunk but the last is whole groups, and all_full holds)
-                                if (merging && chunk.first_packet + p + 1 < index.size() && ulen != kPacket) throw planesPacketError(chunk.first_packet + p);
+                                // (byte planes: so every chunk but the last is whole groups, and all_full holds)
+                                if (merging) checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
                                 produced += ulen;
                                 off += clen;
                             }
@@ -1219,23 +1209,15 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             device_bytes[g] += produced;
                             device_chunks[g] += 1;
                             if (verify) {
-                                // the CRCs cover the packets' original bytes, all 8192 long but the file's last, which holds 1 .. 8192: a
-                                // packet that says otherwise does not decode to them.  (With that, the chunk's `produced` bytes hold
-                                // exactly its n_packets packets, and the verify below covers every one of them: a last packet whose
-                                // ulen had become 0 would otherwise drop out of it.)
-                                for (size_t p = 0; p < chunk.n_packets; ++p) {
-                                    const uint8_t *pkt = bytes + b.h_offsets[p];
-                                    const size_t ulen = pkt[2] | (static_cast<size_t>(pkt[3]) << 8);
-                                    const size_t g = chunk.first_packet + p;
-                                    const uint64_t begin = static_cast<uint64_t>(g) * kPacket;
-                                    if (g + 1 < crcs.size() ? ulen != kPacket : ulen == 0)
-                                        throw checksumError(g, begin, begin + std::min<size_t>(ulen, kPacket));
-                                }
+                                // (With this, the chunk's `produced` bytes hold exactly its n_packets packets, and the verify below covers
+                                // every one of them: a last packet whose ulen had become 0 would otherwise drop out of it.)
+                                for (size_t p = 0; p < chunk.n_packets; ++p)
+                                    checkChecksumPacket(chunk.first_packet + p, crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
                                 if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
                             }
                             uint64_t first_bad = 0;
                             const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
-                                                                 &first_bad, merging ? static_cast<int>(width) : 1);        // (synchronises the lane's stream)
+                                                                 &first_bad, static_cast<int>(trailer.elem_bytes));        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307
@@ -1253,8 +1235,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             } else {             // short packets inside the chunk: one piece per packet
                                 uint64_t at = out_at;
                                 for (size_t p = 0; p < chunk.n_packets; ++p) {
-                                    const uint8_t *pkt = bytes + b.h_offsets[p];
-                                    const size_t ulen = std::min<size_t>(kPacket, pkt[2] | (static_cast<size_t>(pkt[3]) << 8));
+                                    const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(bytes + b.h_offsets[p]));
                                     if (ulen) b.drain(writer, c, b.d_plain + p * kPacket, ulen, at, ulen);
                                     at += ulen;
                                 }

@@ -29,6 +29,10 @@ class GPUCompressor : public Compressor {
     static unsigned short getPacketSize(const uint8_t *packet) {
         return static_cast<unsigned short>(packet[0] | (packet[1] << 8));
     }
+    // ... and the u16 LE count of bytes the packet says it holds, behind it
+    static unsigned short getPacketUlen(const uint8_t *packet) {
+        return static_cast<unsigned short>(packet[2] | (packet[3] << 8));
+    }
 
     // largest chunk a lane takes at a time, in packets (default 65536 = 512 MiB of input = 1024 wavefronts: one launch
     // fills the chip; the pinned staging is independent of it, 64 MiB pieces), kept a multiple of 64 (whole wavefronts);

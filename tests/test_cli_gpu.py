@@ -377,3 +377,34 @@ def test_gpu_cli_survives_an_input_cut_short_under_its_mapping(tmp_path):
         assert p.returncode == 1, (mode, p.returncode, stdout[-500:], stderr[-500:])       # not -SIGBUS
         assert message in stdout + stderr, (mode, stdout[-500:], stderr[-500:])
         assert out.stat().st_size == 0
+
+
+def test_gpu_cli_takes_damaged_trailers_as_the_host_path_does(tmp_path):
+    """Twelve files of the trailer sweep (test_trailer_damage.py) -- every trailer version undamaged, cut off, malformed,
+    unusable and with a CRC that does not match, for a plain and for a planes file of 3 packets -- decoded on the GPU and by
+    --host: the same exit status, the same kind of message and, where the file decodes, the same bytes."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import trailer_ref as T
+    x = T.sweep_input()
+    src, gip = tmp_path / "in.dat", tmp_path / "case.gip"
+    src.write_bytes(x)
+    goods = []
+    for flags in T.FLAGS:
+        r = run("c", "--host", *flags, f"--in={src}", f"--out={gip}")
+        assert r.returncode == 0, r.stderr
+        goods.append(gip.read_bytes())
+    cases = T.cross_cases(x, goods)
+    assert len(cases) == 12
+    assert {T.classify(blob)[0] for _, blob, _ in cases} == {"none", "ok", "malformed", "unusable"}
+    assert {cls.split()[0] for _, _, (_, cls, _) in cases} == {"quiet", "warning", "planes", "checksum"}
+    for what, blob, (code, cls, want) in cases:
+        gip.write_bytes(blob)
+        got = {}
+        for path in (["--host"], []):
+            out = tmp_path / "case.out"
+            out.unlink(missing_ok=True)
+            r = run("d", *path, f"--in={gip}", f"--out={out}")
+            assert r.returncode in (0, 1), (what, path, r.returncode, r.stderr)
+            got[len(path)] = (r.returncode, T.stderr_class(r.returncode, r.stderr), out.read_bytes() if want is not None else None)
+        assert got[0] == got[1] == (code, cls, want), (what, got[0][:2], got[1][:2])

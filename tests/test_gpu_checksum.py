@@ -286,7 +286,7 @@ def test_cli_checksum_on_the_gpu_matches_the_host(H, tmp_path):
 
 def test_gip_is_what_the_cli_writes_with_checksum(H, tmp_path):
     """Compressed.gip(b) of a checksummed batch is byte for byte what `gpuar c --host --checksum` writes for buffer b's bytes
-    (batch.trailer_v2 pinned to the C++ PacketIndex writer), for buffers of one packet, several and none."""
+    (batch.trailer pinned to the C++ Trailer::save), for buffers of one packet, several and none."""
     from gpuar_amd import batch
     sizes = [3 * PACKET + 100, 0, 1, 2 * PACKET, 777]
     ts = [torch.from_numpy(np.resize(LS.packet(1000 + 7 * i), n)).cuda() if n else torch.empty(0, dtype=torch.uint8, device="cuda")
