@@ -28,6 +28,13 @@ With planes="survey" the width of every tensor is chosen by measurement instead 
 launch over the original bytes (hip.survey_planes_batch), what each tensor would compress to at widths 1, 2, 4 and 8, and
 hip.choose_planes picks the smallest width within the estimate's resolution of the best.  That finds the
 element width of typed data held as bytes -- a uint8 view of a checkpoint shard -- which planes="auto" cannot see.
+
+With delta=True (or one bool per tensor) the elements of every group are replaced by their difference to the element in front
+before they are split (hip.split_delta_batch: the same single launch), and summed up again, in place, after they are decoded
+(hip.merge_delta_batch): ordered integers -- offsets, sorted indices, position ids, timestamps, samples -- compress 2-15 x
+smaller, unordered data and floats grow.  The element width is that of `planes` (planes=None: bytes).
+delta="auto" measures: it splits and estimates the batch both ways and filters the tensors for which that is predicted to pay.
+Compressed.gip(b) then carries width and filter in a version-4 trailer (`gpuar c --delta --planes=W`).
 """
 from __future__ import annotations
 
@@ -103,7 +110,9 @@ class Compressed:
     (int64, device, n_packets + 1) the packet offsets in it, `first_packet` (host list, n_buffers + 1) which packets
     belong to which buffer, `sizes` the buffers' byte counts, `crc32` (int32, device, n_packets; None unless compressed with
     checksum=True) the CRC-32 of every packet's uncompressed bytes, `planes` (host list, n_buffers; None unless compressed with
-    planes=...) the element width each buffer's bytes were split into byte planes by (1: not split).
+    planes=...) the element width each buffer's bytes were split into byte planes by (1: not split), `delta` (host list of
+    bools, n_buffers; None unless compressed with delta=...) which buffers went through the delta filter (their `planes`
+    entry is the filter's element width).
 
     Compressed with stored=...: `stored` (uint8, device, n_packets) is 1 for every batch packet that is kept raw, `raw` (uint8,
     device) holds those packets' bytes in batch order, each at a 16-byte-aligned offset, `raw_offsets` (int64, device,
@@ -118,6 +127,7 @@ class Compressed:
     stored: object = None
     raw: object = None
     raw_offsets: object = None
+    delta: list = None
 
     @property
     def n_buffers(self) -> int:
@@ -160,29 +170,31 @@ class Compressed:
 
     def gip(self, b: int) -> bytes:
         """Buffer b as a whole .gip file: what `gpuar c` writes for it (with CRCs: what `gpuar c --checksum` writes; split into
-        planes of width W > 1: what `gpuar c --planes=W` writes)."""
+        planes of width W > 1: what `gpuar c --planes=W` writes; filtered: what `gpuar c --delta --planes=W` writes)."""
         p = self.payload(b)
         out = H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
         w = self.planes[b] if self.planes is not None else 1
-        if self.crc32 is not None or w > 1:
+        filtered = bool(self.delta[b]) if self.delta is not None else False
+        if self.crc32 is not None or w > 1 or filtered:
             off = self._offsets_host()
             lo, hi = self._coded_range(b)
             clens = [off[i + 1] - off[i] for i in range(lo, hi)]
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
             crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
-            out += trailer(clens, w, crcs)
+            out += trailer(clens, w, crcs, delta=filtered)
         return out
 
 
-def trailer(clens, elem_bytes=1, crcs=None) -> bytes:
-    """The .gip trailer, little-endian, pads counted from "GIPX": version 3 for a file whose bytes were split
-    into planes of `elem_bytes` > 1, else version 2 when `crcs` are given, else version 1.
-    "GIPX" u32 version u64 n | version 3: u32 elem_bytes u32 flags (bit 0: CRCs present) | u16 clen[n] |
-    with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG"."""
+def trailer(clens, elem_bytes=1, crcs=None, delta=False) -> bytes:
+    """The .gip trailer, little-endian, pads counted from "GIPX": version 4 for a file whose bytes went through
+    the delta filter at a width of `elem_bytes` (1 too), else version 3 for a file whose bytes were split into planes of
+    `elem_bytes` > 1, else version 2 when `crcs` are given, else version 1.
+    "GIPX" u32 version u64 n | versions 3, 4: u32 elem_bytes u32 flags (bit 0: CRCs present; version 4: bit 1, delta, set) |
+    u16 clen[n] | with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG"."""
     n = len(clens)
-    body = b"GIPX" + struct.pack("<IQ", 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
-    if elem_bytes > 1:
-        body += struct.pack("<II", elem_bytes, 0 if crcs is None else 1)
+    body = b"GIPX" + struct.pack("<IQ", 4 if delta else 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
+    if elem_bytes > 1 or delta:
+        body += struct.pack("<II", elem_bytes, (0 if crcs is None else 1) | (2 if delta else 0))
     body += struct.pack(f"<{n}H", *clens)
     if crcs is not None:
         body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
@@ -207,11 +219,37 @@ def plane_widths(tensors, planes):
     return widths
 
 
-def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status):
+def delta_flags(tensors, delta):
+    """The filter per tensor that `delta` asks for: None -> None; a bool -> that for every tensor; a list -> as given, as bools.
+    ("auto" is resolved by compress and estimate, which launch; this function never does.)"""
+    tensors = list(tensors)
+    if delta is None:
+        return None
+    if isinstance(delta, str):
+        raise GpuarError(f"delta={delta!r}: None, True, False, one bool per tensor or \"auto\"")
+    flags = [bool(delta)] * len(tensors) if isinstance(delta, (bool, int)) else [bool(f) for f in delta]
+    if len(flags) != len(tensors):
+        raise GpuarError(f"delta: {len(flags)} flags for {len(tensors)} tensors")
+    return flags
+
+
+def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None):
     """The batch's descriptors on the device and -- where `widths` asks for it -- its buffers split into byte planes (one launch,
     into a temporary buffer): (d_ptrs, d_bytes, d_first_packet, d_coded, d_split, the pinned host copy of the descriptors, for the
-    caller to hold while the launches run), d_coded the pointers of the bytes to code."""
+    caller to hold while the launches run), d_coded the pointers of the bytes to code.  With `flags` (one bool per buffer, some
+    of them true) the same launch also filters the flagged buffers (hip.split_delta_batch); those get a split copy at any width."""
     import torch
+    if flags is not None and any(flags):
+        at, split_ptrs = 0, []
+        for p, size, w, f in zip(ptrs, sizes, widths, flags):
+            moved = (w != 1 or f) and size
+            split_ptrs.append(at if moved else None)
+            at += (size + 15) // 16 * 16 if moved else 0
+        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
+        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
+        (d_ptrs, d_bytes, d_fp, d_elem, d_filter, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, [int(f) for f in flags], split_ptrs)
+        H.split_delta_batch(d_ptrs, d_bytes, d_fp, d_elem, d_filter, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
+        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
     if widths is not None and any(w != 1 for w in widths):
         # the split copies of the buffers that are split, back to back (each 16-byte aligned); the others are coded where they are
         at, split_ptrs = 0, []
@@ -266,6 +304,39 @@ def _unit_first_packet(n, device):
     return torch.arange(n + 1, dtype=torch.int64, device=device)
 
 
+def _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status):
+    """delta="auto": per buffer, whether the filter is predicted to pay.  The batch is split and estimated twice, without and
+    with the filter (two split launches, two estimate_batch launches, one synchronisation), and a buffer takes the filter iff
+    est_delta + its packets <= est_plain: one byte per packet is the estimate's resolution (as in choose_planes), and a tie
+    goes to no filter."""
+    import torch
+    n = len(sizes)
+    if n_packets == 0:
+        return [False] * n
+    totals = []
+    for flags in (None, [True] * n):
+        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
+        d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device).to(torch.int64)
+        buf, _ptr, _len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+        totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est[:n_packets]))
+        del d_split
+    plain, filtered = torch.stack(totals).tolist()
+    _raise_on_status(d_status, "split_delta_batch")
+    return [first_packet[b + 1] > first_packet[b] and filtered[b] + (first_packet[b + 1] - first_packet[b]) <= plain[b] for b in range(n)]
+
+
+def _filter_arguments(tensors, planes, delta):
+    """(widths, flags or "auto" or None) for compress and estimate: a filter without `planes` works on bytes."""
+    widths = plane_widths(tensors, planes)
+    if delta is None:
+        return widths, None
+    if widths is None:
+        widths = [1] * len(tensors)
+    if isinstance(delta, str) and delta == "auto":
+        return widths, "auto"
+    return widths, delta_flags(tensors, delta)
+
+
 def survey(tensors, stored=None) -> list:
     """What every tensor would compress to at each byte-plane width, without splitting or encoding anything: per tensor the four
     predicted totals [T1, T2, T4, T8], T_w = estimate([t], planes=w, stored=stored)[0].  One hip.survey_planes_batch launch over
@@ -299,11 +370,12 @@ def survey_widths(tensors, stored=None) -> list:
             for b, totals in enumerate(survey(tensors, stored="auto" if isinstance(stored, str) and stored == "auto" else None))]
 
 
-def estimate(tensors, planes=None, stored=None) -> list:
+def estimate(tensors, planes=None, stored=None, delta=None) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
     asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
-    split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front)."""
+    split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front).  `delta`: as
+    compress -- the estimate is that of the filtered, split bytes (delta="auto": of each tensor's better half)."""
     import torch
     if stored is not None and stored != "auto":
         raise GpuarError(f"stored={stored!r}: None or \"auto\"")
@@ -311,12 +383,14 @@ def estimate(tensors, planes=None, stored=None) -> list:
     if isinstance(planes, str) and planes == "survey":
         planes = survey_widths(tensors, stored)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
-    widths = plane_widths(tensors, planes)
+    widths, flags = _filter_arguments(tensors, planes, delta)
     n = len(sizes)
     if n_packets == 0:
         return [0] * n
     d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
+    if flags == "auto":
+        flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
+    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status, flags)
     d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
     buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
     if stored == "auto":
@@ -326,7 +400,7 @@ def estimate(tensors, planes=None, stored=None) -> list:
     return totals.tolist()
 
 
-def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None) -> Compressed:
+def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
     compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
     every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
@@ -335,7 +409,11 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     width before coding (one more launch, into a temporary buffer that is freed with the slots; widths of 1 are coded as they are).  The widths the kernels take
     are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).  `stored`: None | "auto" | one bool per batch
     packet: keep packets raw instead of coding them -- "auto": those whose estimate (hip.estimate_batch, on the split bytes) is
-    not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  See Compressed."""
+    not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  `delta`: None | True |
+    False | one bool per tensor | "auto": replace the elements of the flagged tensors, at the width `planes` gives (planes=None:
+    1), by their differences inside every group, in the launch that splits (hip.split_delta_batch); "auto" flags the tensors
+    for which two more split and two more estimate launches predict a gain (_auto_delta).  None takes exactly the path taken
+    without the keyword.  The CRCs stay those of the original bytes; `stored` sees the filtered, split bytes.  See Compressed."""
     import torch
     tensors = list(tensors)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
@@ -343,7 +421,7 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         stored = _stored_argument(stored, n_packets)
         with torch.cuda.stream(stream) if stream is not None else _nothing():
             planes = survey_widths(tensors, stored)
-    widths = plane_widths(tensors, planes)
+    widths, flags = _filter_arguments(tensors, planes, delta)
     stored = _stored_argument(stored, n_packets)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -351,7 +429,9 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     d_stored = d_raw = d_raw_offsets = None
     with torch.cuda.stream(stream) if stream is not None else _nothing():
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
-        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
+        if flags == "auto":
+            flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
+        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
         if stored is None:
             d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
             d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
@@ -386,7 +466,7 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         del d_slots, d_split
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
                       crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
-                      raw_offsets=d_raw_offsets)
+                      raw_offsets=d_raw_offsets, delta=flags)
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True):
@@ -394,7 +474,8 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
     buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them.  When `c` carries CRCs
     and `verify` is true, the decoded bytes are checked against them (one more launch): a mismatch raises GpuarError naming
     the first buffer and packet that differ.  Buffers that were split into byte planes are merged back in place in `out`
-    after decoding and before verifying: the CRCs are those of the original bytes.  Packets that were stored raw are copied
+    after decoding and before verifying: the CRCs are those of the original bytes; where a buffer went through the delta filter,
+    that launch is hip.merge_delta_batch, which also sums the differences up again.  Packets that were stored raw are copied
     (one more launch), the others decoded."""
     import torch
     device = c.stream.device
@@ -425,7 +506,11 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
             if n_stored:
                 H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
-        if c.planes is not None and any(w != 1 for w in c.planes) and c.n_packets:
+        if c.delta is not None and any(c.delta) and c.n_packets:
+            (d_elem, d_filter), _keep2 = _upload(device, c.planes, [int(f) for f in c.delta])
+            H.merge_delta_batch(d_ptrs, d_sizes, d_fp, d_elem, d_filter, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
+            _raise_on_status(d_status, "merge_delta_batch")
+        elif c.planes is not None and any(w != 1 for w in c.planes) and c.n_packets:
             (d_elem,), _keep2 = _upload(device, c.planes)
             H.merge_planes_batch(d_ptrs, d_sizes, d_fp, d_elem, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
             _raise_on_status(d_status, "merge_planes_batch")

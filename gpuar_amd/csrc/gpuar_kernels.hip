@@ -24,6 +24,8 @@
 //    no v_readlane in the loop);
 //  * crc32_kernel: the per-packet CRC-32 of the .gip trailer, computed or verified;
 //  * split_planes_kernel / merge_planes_kernel, planes_tail_kernel: byte-plane splitting of typed data (planes.h);
+//  * split_delta_kernel / merge_delta_kernel, delta_tail_kernel: the same with an element-wise delta filter fused in (delta.h,
+//    DESIGN.md 4.9);
 //  * compaction (scan + gather), synthetic-stream generators, a plain copy (the measured HBM roof).
 //
 // Bit-exact with the reference: same counts, same integer arithmetic, same
@@ -41,6 +43,7 @@
 #include "lane_codec.h"
 #include "crc32.h"
 #include "planes.h"
+#include "delta.h"
 #include "estimate.h"
 #include "survey.h"
 
@@ -2373,6 +2376,221 @@ planes_tail_kernel(PlanesArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Delta filter (delta.h): split_delta = split_planes of the element-wise differences inside every group,
+// merge_delta its inverse, fused into the byte-plane kernels' shape so that the filter costs no pass over memory of its own.
+//
+// Full groups are planes_group's: 512 threads, 16 elements each, 16-byte accesses on both sides, every load before the
+// barrier and every store behind it.  SPLIT: a thread's predictor is the last element of the thread in front -- a lane shift
+// inside the wavefront, a few bytes of LDS (written before the barrier) across wavefronts, 0 for the group's first element;
+// then delta_block and planes_block.  MERGE: planes_block, the block's local scan (delta_scan_block), an exclusive scan of the
+// 512 block totals (delta_workgroup_scan: lane shifts, then the 8 wave totals through LDS behind one more barrier) and the
+// thread's offset added to its 16 elements.  Modular addition is associative, so the scan order does not matter.
+// A batch carries one more word per buffer, `filter`: 0 takes planes_group (the output is split_planes_batch's), 1 the path
+// above, anything else flags BAD_BATCH and leaves the buffer alone; the choice is uniform over a workgroup.
+// The tail is delta_tail_kernel's, one workgroup per buffer through LDS like planes_tail: a thread takes 16 elements from
+// LDS into registers, filters them, and puts them back in the other layout; then LDS goes out by dwords and bytes.
+// The existing kernels are not touched: callers without the filter keep launching them.
+// ---------------------------------------------------------------------------
+struct DeltaArgs {
+    PlanesArgs p;
+    const uint64_t *filter;                 // a batch: per buffer 0 = planes alone, 1 = delta; one buffer: unused (delta)
+};
+
+template <int W> struct DeltaLane { typedef uint32_t type; };       // what crosses lanes: an element, or a sum of them
+template <> struct DeltaLane<8> { typedef uint64_t type; };
+
+// the exclusive prefix sum of `total` over the workgroup's 512 threads, in thread order, mod 2^32 or 2^64; `waves`: 8 entries
+// of LDS that no thread still reads
+template <typename T>
+__device__ __forceinline__ T delta_workgroup_scan(T total, T *waves) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    T incl = total;
+#pragma unroll
+    for (uint32_t s = 1u; s < 64u; s <<= 1) {
+        const T up = __shfl_up(incl, s);
+        if (lane >= s) incl += up;
+    }
+    if (lane == 63u) waves[wave] = incl;
+    __syncthreads();
+    T front = 0;
+#pragma unroll
+    for (uint32_t k = 0; k + 1u < kPlaneThreads / 64u; ++k) front += k < wave ? waves[k] : static_cast<T>(0);
+    return front + incl - total;
+}
+
+// one full group at `in` -> `out` (both 16-byte aligned; out == in is fine), the whole workgroup; `lds`: 8 entries (split: not
+// those of the group before)
+template <int W, bool Merge>
+__device__ __forceinline__ void delta_group(const uint8_t *in, uint8_t *out, typename DeltaLane<W>::type *lds) {
+    using T = typename DeltaLane<W>::type;
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    const uint32_t t = threadIdx.x;
+    const uint32_t from_at = Merge ? 16u * t : 16u * W * t, from_step = Merge ? kPlanePacket : 16u;
+    const uint32_t to_at = Merge ? 16u * W * t : 16u * t, to_step = Merge ? 16u : kPlanePacket;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(in + from_at));
+    PlanesQuad q[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) q[k] = src[k * (from_step / 16u)];
+#pragma unroll
+    for (int k = 0; k < W; ++k) asm volatile("" : "+v"(q[k]));
+    uint32_t from[4 * W], to[4 * W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) from[4 * k] = q[k].x, from[4 * k + 1] = q[k].y, from[4 * k + 2] = q[k].z, from[4 * k + 3] = q[k].w;
+    if constexpr (!Merge) {
+        T last;                                                         // the thread's last element: the next thread's predictor
+        if constexpr (W == 8) last = static_cast<uint64_t>(from[31]) << 32 | from[30];
+        else last = from[4 * W - 1] >> (32 - 8 * W);
+        if ((t & 63u) == 63u) lds[t >> 6] = last;
+        __syncthreads();
+        T pred = __shfl_up(last, 1u);
+        if ((t & 63u) == 0u) pred = t ? lds[(t >> 6) - 1u] : static_cast<T>(0);
+        delta_block<W>(from, pred);
+        planes_block<W, false>(from, to, PlanesPerm());
+    } else {
+        __syncthreads();
+        planes_block<W, true>(from, to, PlanesPerm());
+        const T total = static_cast<T>(delta_scan_block<W>(to));
+        delta_offset_block<W>(to, delta_workgroup_scan<T>(total, lds));
+    }
+    GlobalQuad *dst = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(out + to_at));
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        PlanesQuad v;
+        v.x = to[4 * k], v.y = to[4 * k + 1], v.z = to[4 * k + 2], v.w = to[4 * k + 3];
+        dst[k * (to_step / 16u)] = v;
+    }
+}
+
+template <bool Merge>
+__device__ __forceinline__ void delta_full(const DeltaArgs &d, uint64_t *lds) {
+    const PlanesArgs &a = d.p;
+    uint32_t turn = 0u;
+    for (uint64_t packet = blockIdx.x; packet < a.n_packets; packet += gridDim.x) {
+        const uint8_t *in = a.in;
+        uint8_t *out = a.out;
+        uint64_t n_bytes = a.n_bytes, j = packet;
+        uint32_t w = a.elem, filter = 1u;
+        if (a.in_ptrs) {
+            const BatchLane bl = batch_lane(a.in_ptrs, a.bytes, a.first_packet, a.n_buffers, packet);
+            PlanesBuffer pb = {nullptr, nullptr, 0u, 0u};
+            uint64_t f = 0u;
+            if (bl.owned && bl.count) pb = planes_buffer(a, bl.buffer), f = d.filter[bl.buffer];
+            if (pb.w == 0u || f > 1u) {
+                if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                continue;
+            }
+            in = pb.in, out = pb.out, n_bytes = pb.n_bytes, w = pb.w, filter = static_cast<uint32_t>(f);
+            j = packet - a.first_packet[bl.buffer];
+        }
+        w = __builtin_amdgcn_readfirstlane(w);
+        filter = __builtin_amdgcn_readfirstlane(filter);
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(j & (w - 1u)));
+        const uint64_t at = j * kPacket;
+        if (lead != 0u || n_bytes - at < static_cast<uint64_t>(w) * kPacket) continue;      // not a group's first packet, or the tail
+        if (filter == 0u) {                                                                 // planes alone: planes_full's path
+            if (w == 1u && in == out) continue;
+            if (w == 8u) planes_group<8, Merge>(in + at, out + at);
+            else if (w == 4u) planes_group<4, Merge>(in + at, out + at);
+            else if (w == 2u) planes_group<2, Merge>(in + at, out + at);
+            else planes_group<1, Merge>(in + at, out + at);
+            continue;
+        }
+        // split has one barrier per group: a wavefront may write the next group's predictors while another still reads this one's
+        uint64_t *mine = lds + 8u * (turn++ & 1u);
+        if (w == 8u) delta_group<8, Merge>(in + at, out + at, mine);
+        else if (w == 4u) delta_group<4, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+        else if (w == 2u) delta_group<2, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+        else delta_group<1, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+    }
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+split_delta_kernel(DeltaArgs d) {
+    __shared__ uint64_t lds[16];
+    delta_full<false>(d, lds);
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+merge_delta_kernel(DeltaArgs d) {
+    __shared__ uint64_t lds[16];
+    delta_full<true>(d, lds);
+}
+
+// the tail of a buffer the filter is on for: e = r div w <= 8191 elements, thread t takes elements 16 t .. 16 t + 15
+template <bool Merge>
+__device__ __forceinline__ void delta_tail(const PlanesBuffer &pb, PlanesQuad *lds, uint64_t *waves) {
+    const uint32_t w = pb.w;
+    const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
+    if (r == 0u) return;
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
+    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) lds[i] = src[i];
+    __syncthreads();
+    uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
+    // element i (< e): its byte k lies at i w + k on the mixed side and at k e + i on the plane side
+    auto element = [&](uint32_t i, bool planes) -> uint64_t {
+        uint64_t v = 0u;
+        if (i < e)
+            for (uint32_t k = 0; k < w; ++k) v |= static_cast<uint64_t>(bytes[planes ? k * e + i : i * w + k]) << (8u * k);
+        return v;
+    };
+    const uint32_t first = 16u * threadIdx.x;
+    uint64_t v[16];
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) v[j] = element(first + j, Merge);
+    if constexpr (!Merge) {
+        const uint64_t pred = first ? element(first - 1u, false) : 0u;
+        __syncthreads();                                                    // every element is in registers before LDS is rewritten
+#pragma unroll
+        for (uint32_t j = 15u; j > 0u; --j) v[j] -= v[j - 1u];
+        v[0] -= pred;
+    } else {
+#pragma unroll
+        for (uint32_t j = 1u; j < 16u; ++j) v[j] += v[j - 1u];              // (elements beyond e count as 0)
+        const uint64_t offset = delta_workgroup_scan<uint64_t>(v[15], waves);      // its barrier: as above
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; ++j) v[j] += offset;
+    }
+    uint32_t again = first;                 // (opaque: the 16 lane masks of the loads above are not kept in scalar registers until here)
+    asm volatile("" : "+v"(again));
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t i = again + j;
+        if (i < e)
+            for (uint32_t k = 0; k < w; ++k) bytes[Merge ? i * w + k : k * e + i] = static_cast<uint8_t>(v[j] >> (8u * k));
+    }
+    __syncthreads();
+    const uint32_t *done = reinterpret_cast<const uint32_t *>(lds);
+    uint8_t *out = pb.out + (pb.n_bytes - r);
+    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
+    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) words[i] = done[i];
+    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
+    if (threadIdx.x < (r & 3u)) last[(r & ~3u) + threadIdx.x] = bytes[(r & ~3u) + threadIdx.x];
+}
+
+template <bool Merge>
+__global__ void __launch_bounds__(kPlaneThreads)
+delta_tail_kernel(DeltaArgs d) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    __shared__ uint64_t waves[kPlaneThreads / 64u];
+    const PlanesArgs &a = d.p;
+    if (!a.in_ptrs) {
+        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
+        delta_tail<Merge>(pb, lds, waves);
+        return;
+    }
+    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
+        const PlanesBuffer pb = planes_buffer(a, static_cast<uint32_t>(b));      // (an unusable buffer with packets was flagged by the kernel above)
+        const uint64_t filter = d.filter[b];
+        if (pb.w != 0u && filter == 1u) delta_tail<Merge>(pb, lds, waves);
+        else if (filter == 0u) planes_tail<Merge>(pb, lds);
+        __syncthreads();                                                         // the next buffer's tail goes into the same LDS
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Packet size estimate (estimate.h): est[p] = the clen the codec would give packet p, from the packet's byte
 // histogram alone, for one buffer or a batch -- and the copy that moves the packets the estimate says cannot shrink.
 //
@@ -3112,6 +3330,120 @@ int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem
 
 int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
     return planes_on_host(true, in, n_bytes, elem_bytes, out);
+}
+
+static int launch_delta(bool merge, const gpuar::DeltaArgs &d, size_t n_tails, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t blocks = d.p.n_packets < gpuar::kPlaneGridCap ? d.p.n_packets : gpuar::kPlaneGridCap;
+    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
+    if (merge) gpuar::merge_delta_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(d);
+    else gpuar::split_delta_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(d);
+    const int e = check_launch();
+    if (e != GPUAR_OK || tails == 0u) return e;
+    if (merge) gpuar::delta_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(d);
+    else gpuar::delta_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(d);
+    return check_launch();
+}
+
+static int delta_single(bool merge, const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!d_in || !d_out || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_in) || !aligned16(d_out)) return GPUAR_ERR_ALIGNMENT;
+    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out);
+    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
+    gpuar::DeltaArgs d = {};                                                                   // (a width of 1 in place is work too)
+    d.p.in = d_in;
+    d.p.out = d_out;
+    d.p.n_bytes = n_bytes;
+    d.p.elem = elem_bytes;
+    d.p.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    return launch_delta(merge, d, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+}
+
+static int delta_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                       const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
+                       uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_elem_bytes || !d_filter || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_filter) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
+        return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::DeltaArgs d = {};
+    d.p.in_ptrs = d_in_ptrs;
+    d.p.out_ptrs = d_out_ptrs;
+    d.p.bytes = d_bytes;
+    d.p.first_packet = d_first_packet;
+    d.p.elem_bytes = d_elem_bytes;
+    d.p.n_buffers = static_cast<uint32_t>(n_buffers);
+    d.p.n_packets = static_cast<uint32_t>(n_packets);
+    d.p.status = status;
+    d.filter = d_filter;
+    return launch_delta(merge, d, n_buffers, stream);
+}
+
+int gpuar_hip_split_delta(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return delta_single(false, d_in, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_merge_delta(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return delta_single(true, d_in, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_split_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
+                                uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return delta_batch(false, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+int gpuar_hip_merge_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
+                                uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return delta_batch(true, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+static int delta_on_host(bool merge, const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !out) return GPUAR_ERR_ARGUMENT;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
+    if (merge) gpuar::merge_delta_host(in, n_bytes, elem_bytes, out);
+    else gpuar::split_delta_host(in, n_bytes, elem_bytes, out);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_split_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return delta_on_host(false, in, n_bytes, elem_bytes, out);
+}
+
+int gpuar_hip_merge_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return delta_on_host(true, in, n_bytes, elem_bytes, out);
+}
+
+// one 16-element block through delta.h's register transforms, as the kernels apply them, on the host (for the tests):
+// mixed: 4 * elem_bytes dwords, in place; undo = 0: delta_block with `carried` as pred; 1: undelta_block with it as offset.
+// *total (may be null) receives undelta_block's total.
+int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, uint64_t carried, uint64_t *total) {
+    if (!mixed || !gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    auto run = [&](auto width) {
+        constexpr int W = decltype(width)::value;
+        uint32_t block[4 * W];
+        memcpy(block, mixed, sizeof block);
+        uint64_t sum = 0;
+        if (undo) sum = gpuar::undelta_block<W>(block, carried);
+        else gpuar::delta_block<W>(block, carried);
+        memcpy(mixed, block, sizeof block);
+        if (total) *total = sum;
+    };
+    if (elem_bytes == 8u) run(std::integral_constant<int, 8>());
+    else if (elem_bytes == 4u) run(std::integral_constant<int, 4>());
+    else if (elem_bytes == 2u) run(std::integral_constant<int, 2>());
+    else run(std::integral_constant<int, 1>());
+    return GPUAR_OK;
 }
 
 static int launch_estimate(const gpuar::CrcArgs &a, void *stream) {

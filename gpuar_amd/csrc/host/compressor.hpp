@@ -43,6 +43,8 @@ class Compressor {
     bool writeChecksum = false;       // append the trailer with per-packet CRC-32s (version 2), which decompress verifies
     int planes = 1;                   // compress: split the input into byte planes of elements this wide (../planes.h) and say so in a
                                       // version-3 trailer, from which decompress learns the width; 1: no transform, no such trailer
+    bool delta = false;               // compress: replace the elements (`planes` bytes wide; 1 too) of every group by their differences
+                                      // before the split (../delta.h) and say so in a version-4 trailer
 
     // the error a decompress raises for a packet whose decoded bytes do not match the CRC-32 of its trailer
     static std::runtime_error checksumError(size_t packet, uint64_t begin, uint64_t end) {
@@ -53,6 +55,11 @@ class Compressor {
     static std::runtime_error planesTrailerError() {
         return std::runtime_error("Incorrect file format: the trailer says the file holds byte planes (version 3) but it is damaged, "
                                   "carries a width other than 2, 4 or 8, or carries flags this gpuar does not know");
+    }
+    // the same for a trailer that says the file went through the delta filter: going on would hand back differences
+    static std::runtime_error deltaTrailerError() {
+        return std::runtime_error("Incorrect file format: the trailer says the file holds delta-filtered elements (version 4) but it is damaged, "
+                                  "carries a width other than 1, 2, 4 or 8, lacks the delta flag, or carries flags this gpuar does not know");
     }
     static std::runtime_error planesPacketError(size_t packet) {
         return std::runtime_error("Incorrect file format: packet " + std::to_string(packet) + " of a file of byte planes is not the last one and "
@@ -68,13 +75,14 @@ class Compressor {
         Trailer trailer;
         const Trailer::Status status = Trailer::load(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, trailer);
         if (status == Trailer::Status::unusable) throw planesTrailerError();
+        if (status == Trailer::Status::unusable_delta) throw deltaTrailerError();
         if (status == Trailer::Status::malformed) warnMalformedTrailer();
         return trailer;
     }
     // compress: whether the options ask for a trailer, and that trailer appended at the current position of the output
-    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1; }
+    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta; }
     void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs) {
-        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr);
+        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta);
     }
     static constexpr size_t kPacketBytes = 8192;
     // What a trailer of `n_packets` packets says of the bytes that packet `packet` of the file holds by its header (`ulen`).
@@ -113,6 +121,7 @@ class Compressor {
         if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) throw std::invalid_argument("planes: the element width is 1, 2, 4 or 8");
         planes = elem_bytes;
     }
+    void setDelta(bool on) { delta = on; }
     // `--planes=auto`: sets the width from the input's own bytes and returns it -- gpuar::choose_width of the totals that
     // gpuar::survey_host (../survey.h) predicts for the first min(file size, kSurveyPrefix) bytes taken as a buffer of their own,
     // written to total[4] (widths 1, 2, 4, 8).  On the host, from one pread, before either pipeline starts: the prefix is a

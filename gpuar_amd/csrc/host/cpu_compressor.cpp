@@ -14,6 +14,7 @@
 #include "../crc32.h"
 #include "../lane_codec.h"
 #include "../planes.h"
+#include "../delta.h"
 #include "file_header.hpp"
 #include "packet_index.hpp"
 
@@ -105,7 +106,9 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     // --planes: what is coded is the batch split into byte planes (a batch is a whole number of groups: 4096 packets; only the
     // file's last one can be shorter, and its tail is the file's tail); the CRCs stay those of the bytes as read
     static_assert(kBatchPackets % 8 == 0, "a batch starts on a group boundary for every element width");
-    std::vector<uint8_t> split(planes > 1 ? in.size() : 0);
+    // --delta: the same with the elements' differences inside every group in front of the split (at a width of 1 too)
+    const bool splitting = planes > 1 || delta;
+    std::vector<uint8_t> split(splitting ? in.size() : 0);
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
     std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
@@ -118,8 +121,9 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
             if (got == 0) break;
             const size_t np = (got + gpuar::kPacket - 1) / gpuar::kPacket;
             process_timer.start();     // model init + codec only, as src/cpu_compressor.cpp:157-161
-            if (planes > 1) gpuar::planes_host<false>(in.data(), got, static_cast<uint32_t>(planes), split.data());
-            const uint8_t *coded = planes > 1 ? split.data() : in.data();
+            if (delta) gpuar::split_delta_host(in.data(), got, static_cast<uint32_t>(planes), split.data());
+            else if (planes > 1) gpuar::planes_host<false>(in.data(), got, static_cast<uint32_t>(planes), split.data());
+            const uint8_t *coded = splitting ? split.data() : in.data();
             for_each_packet(np, nthreads, [&](size_t p) {
                 const size_t off = p * gpuar::kPacket;
                 const uint32_t len = static_cast<uint32_t>(std::min<size_t>(gpuar::kPacket, got - off));
@@ -238,7 +242,8 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                     checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
                     total += ulen[p];
                 }
-                gpuar::planes_host<true>(decoded.data(), total, trailer.elem_bytes, out.data());
+                if (trailer.filtering()) gpuar::merge_delta_host(decoded.data(), total, trailer.elem_bytes, out.data());
+                else gpuar::planes_host<true>(decoded.data(), total, trailer.elem_bytes, out.data());
             }
             if (verify) {
                 for (size_t p = 0; p < np; ++p) {

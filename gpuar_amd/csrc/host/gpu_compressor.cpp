@@ -424,7 +424,7 @@ struct GPUCompressor::DeviceBuffers {
     uint32_t *d_status = nullptr;   // this lane's own status word (device): its launches report here, nobody else's do
     uint32_t *d_crc = nullptr;      // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
     uint32_t *h_crc = nullptr;      // pinned, the same
-    uint8_t *d_planes = nullptr;    // cap * 8192 (--planes / a version-3 trailer): the chunk split into byte planes, or merged back
+    uint8_t *d_planes = nullptr;    // cap * 8192 (--planes, --delta / a version-3 or -4 trailer): the chunk split into byte planes, or merged back
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
     // the lane's pinned pieces and which of them are free
@@ -599,12 +599,14 @@ struct GPUCompressor::DeviceBuffers {
     // `mode`: GPUAR_MODE_* -- which encode kernel (the caller knows whether this launch has the chip to itself)
     // `checksum`: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
     // `planes` > 1: what is coded is the chunk split into byte planes of elements that wide (d_planes); the CRCs stay the input's
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes) {
+    // `delta`: ... of the elements' differences (at a width of 1 too)
+    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
-        if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
-        gpuar_check(gpuar_hip_encode_mode(planes > 1 ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
+        if (delta) gpuar_check(gpuar_hip_split_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_delta");
+        else if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
+        gpuar_check(gpuar_hip_encode_mode(planes > 1 || delta ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
         if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
@@ -621,7 +623,9 @@ struct GPUCompressor::DeviceBuffers {
     // crcs (n_packets values, or null): the decoded packets -- n_plain bytes back to back -- are verified against them;
     // GPUAR_STATUS_CHECKSUM in the flags then, and the chunk's lowest bad packet in `first_bad`
     // `planes` > 1: the n_plain decoded bytes are byte planes, merged into d_planes before they are verified; the result is there
-    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1) {
+    // `delta`: ... of differences, summed up by the merge (at a width of 1 too)
+    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1,
+                         bool delta = false) {
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
         uint64_t *d_first_bad = crcs ? reinterpret_cast<uint64_t *>(d_crc + crcSlots()) : nullptr;
@@ -632,8 +636,9 @@ struct GPUCompressor::DeviceBuffers {
         }
         hip_check(hipEventRecord(t0, stream), "event");
         gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
-        if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
-        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
+        if (delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_delta");
+        else if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
+        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 || delta ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         if (crcs) hip_check(hipMemcpyAsync(h_crc + crcSlots(), d_first_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
@@ -827,14 +832,14 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (c == 0) trace("compress: its buffers allocated");
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (writeChecksum) b.allocateCrc();
-                            if (planes > 1) b.allocatePlanes();
+                            if (planes > 1 || delta) b.allocatePlanes();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const uint64_t at = chunk_at[c];
                             const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
                             const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
                             if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
                             uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes);     // (synchronises the lane's stream)
+                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta);     // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(at, n_plain);
                             // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
                             // (src/gpu_compressor.cpp:146-150)
@@ -1217,7 +1222,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             }
                             uint64_t first_bad = 0;
                             const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
-                                                                 &first_bad, static_cast<int>(trailer.elem_bytes));        // (synchronises the lane's stream)
+                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering());        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307

@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -59,6 +59,9 @@ void usage() {
     std::cout << "--planes      (compress) W = 2, 4 or 8: split the input into byte planes of W-byte elements first (typed data compresses better);" << std::endl;
     std::cout << "              the file then carries a trailer with W, which decompress needs; 1 = off (default);" << std::endl;
     std::cout << "              auto: W is chosen from the first 16 MiB of the input (a histogram pass on the host predicts its size at every W)" << std::endl;
+    std::cout << "--delta       (compress) replace the W-byte integers of the input (W from --planes; alone: bytes) by their differences first:" << std::endl;
+    std::cout << "              ordered integers (offsets, sorted indices, timestamps, samples) compress several times smaller, other data grows;" << std::endl;
+    std::cout << "              the file then carries a trailer that says so, which decompress needs" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
@@ -67,7 +70,7 @@ void usage() {
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip";
-    bool has_in = false, planes_auto = false;
+    bool has_in = false, planes_auto = false, delta = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
@@ -91,6 +94,8 @@ int main(int argc, char **argv) {
             index = true;
         } else if (flag_name_is(argv[i], "checksum", &v)) {
             checksum = true;
+        } else if (flag_name_is(argv[i], "delta", &v)) {
+            delta = true;
         } else if (flag_name_is(argv[i], "nointeractive", &v)) {
         } else if (flag_name_is(argv[i], "in", &v)) {
             if (!take(&v)) break;
@@ -157,6 +162,7 @@ int main(int argc, char **argv) {
         compressor->setWriteIndex(index);
         compressor->setWriteChecksum(checksum);
         compressor->setPlanes(planes);
+        compressor->setDelta(delta);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);
         CompressionInfo info;

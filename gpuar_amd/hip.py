@@ -29,6 +29,8 @@ EXPORTS = [
     "gpuar_hip_crc32", "gpuar_hip_verify_crc32", "gpuar_hip_crc32_batch", "gpuar_hip_verify_crc32_batch",
     "gpuar_hip_split_planes", "gpuar_hip_merge_planes", "gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch",
     "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
+    "gpuar_hip_split_delta", "gpuar_hip_merge_delta", "gpuar_hip_split_delta_batch", "gpuar_hip_merge_delta_batch",
+    "gpuar_hip_split_delta_host", "gpuar_hip_merge_delta_host", "gpuar_hip_delta_block_host",
     "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
     "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
 ]
@@ -118,6 +120,17 @@ def load() -> C.CDLL:
     for name in ("gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [vp, sz, u32, vp]
+    for name in ("gpuar_hip_split_delta", "gpuar_hip_merge_delta"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, sz, u32, vp, vp]
+    for name in ("gpuar_hip_split_delta_batch", "gpuar_hip_merge_delta_batch"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    for name in ("gpuar_hip_split_delta_host", "gpuar_hip_merge_delta_host"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, sz, u32, vp]
+    lib.gpuar_hip_delta_block_host.restype = C.c_int
+    lib.gpuar_hip_delta_block_host.argtypes = [C.POINTER(C.c_uint32), u32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     lib.gpuar_hip_estimate.restype = C.c_int
     lib.gpuar_hip_estimate.argtypes = [vp, sz, vp, vp]
     lib.gpuar_hip_estimate_batch.restype = C.c_int
@@ -424,6 +437,68 @@ def split_planes_host(data, elem_bytes: int) -> bytes:
 def merge_planes_host(data, elem_bytes: int) -> bytes:
     """merge_planes of a bytes-like object on the CPU (gpuar_hip_merge_planes_host)."""
     return _planes_host("gpuar_hip_merge_planes_host", data, elem_bytes)
+
+
+def split_delta(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """split_planes of the element-wise differences (gpuar_hip_split_delta; include/gpuar_hip.h): inside every group of
+    elem_bytes packets the elements, as little-endian unsigned integers of elem_bytes bytes (1, 2, 4, 8), are replaced by their
+    difference to the element in front (mod 2^(8 elem_bytes); the first stays) and then regrouped into byte planes, in one pass.
+    elem_bytes = 1 is a byte delta per packet.  `d_out` may be `d_in`.  Returns d_out."""
+    return _planes("gpuar_hip_split_delta", d_in, elem_bytes, d_out, n_bytes, stream)
+
+
+def merge_delta(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """The inverse of split_delta (gpuar_hip_merge_delta): merge_planes, then the prefix sum inside every group; `d_out` may
+    be `d_in`."""
+    return _planes("gpuar_hip_merge_delta", d_in, elem_bytes, d_out, n_bytes, stream)
+
+
+def _delta_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs, stream, d_status):
+    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
+                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_filter, "d_filter", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
+        _require_u64_desc(t, what, n)
+    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(),
+                                 d_filter.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status),
+                                 _stream_handle(stream)), name)
+
+
+def split_delta_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
+                      d_status=None):
+    """split_planes_batch with a filter per buffer (gpuar_hip_split_delta_batch): d_filter[b] = 0 regroups buffer b as
+    split_planes_batch does, 1 as split_delta; any other value is BAD_BATCH and the buffer is left alone."""
+    _delta_batch("gpuar_hip_split_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs,
+                 stream, d_status)
+
+
+def merge_delta_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
+                      d_status=None):
+    """The inverse of split_delta_batch (gpuar_hip_merge_delta_batch)."""
+    _delta_batch("gpuar_hip_merge_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs,
+                 stream, d_status)
+
+
+def split_delta_host(data, elem_bytes: int) -> bytes:
+    """split_delta of a bytes-like object on the CPU (gpuar_hip_split_delta_host: no device is touched)."""
+    return _planes_host("gpuar_hip_split_delta_host", data, elem_bytes)
+
+
+def merge_delta_host(data, elem_bytes: int) -> bytes:
+    """merge_delta of a bytes-like object on the CPU (gpuar_hip_merge_delta_host)."""
+    return _planes_host("gpuar_hip_merge_delta_host", data, elem_bytes)
+
+
+def delta_block_host(mixed, elem_bytes: int, undo: bool, carried: int):
+    """One block of 16 elements (`mixed`: 4 * elem_bytes dwords) through the kernels' register transform, run on the CPU
+    (gpuar_hip_delta_block_host): undo=False gives delta_block's differences with `carried` as the element in front; undo=True
+    undelta_block's prefix sums plus `carried`.  Returns (dwords, the block's total -- 0 for undo=False)."""
+    mixed = list(mixed)
+    if len(mixed) != 4 * elem_bytes:
+        raise GpuarError(f"delta_block_host: {len(mixed)} dwords for a width of {elem_bytes}")
+    block = (C.c_uint32 * len(mixed))(*mixed)
+    total = C.c_uint64(0)
+    _check(load().gpuar_hip_delta_block_host(block, elem_bytes, 1 if undo else 0, carried & (2 ** 64 - 1), C.byref(total)),
+           "gpuar_hip_delta_block_host")
+    return list(block), total.value
 
 
 def estimate(d_in, n_bytes: int = None, d_est=None, stream=None):

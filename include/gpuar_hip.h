@@ -271,6 +271,41 @@ int gpuar_hip_split_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem
 int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
 
 /* ------------------------------------------------------------------------
+ * Delta filter in front of the byte planes (gpuar_amd/csrc/delta.h).  Inside every group of the byte-plane
+ * layout above (G = w * 8192 bytes), and inside the e = r div w elements of the tail, the elements are read as little-endian
+ * unsigned w-byte integers v[] and replaced by
+ *     d[0] = v[0]      d[i] = v[i] - v[i - 1]   (mod 2^(8 w));      the tail's last r mod w bytes stay as they are.
+ * SPLIT_DELTA is gpuar_hip_split_planes of that, MERGE_DELTA its inverse: gpuar_hip_merge_planes, then the prefix sum inside
+ * every group.  The predictor resets at every group, so groups stay independent of each other.  One fused pass: the same
+ * launches, access rules and overlap rule as the planes calls.  elem_bytes == 1 is a byte delta per packet and does work, in
+ * place too.  Ordered integers (offsets, sorted indices, timestamps, samples) compress 2 - 15 x smaller behind it; unordered
+ * data and floats grow: the filter is for the caller to ask for.
+ * ---------------------------------------------------------------------- */
+
+/* One buffer: arguments and error codes of gpuar_hip_split_planes (n_bytes == 0 is GPUAR_OK with no launch). */
+int gpuar_hip_split_delta(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+int gpuar_hip_merge_delta(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+
+/* A batch: arguments of gpuar_hip_split_planes_batch plus d_filter (n_buffers u64, 8-byte aligned): 0 = byte planes alone
+ * (that buffer's output is gpuar_hip_split_planes_batch's), 1 = delta.  Any other value makes the buffer unusable
+ * (GPUAR_STATUS_BAD_BATCH) and it is left untouched, like the other unusable descriptors. */
+int gpuar_hip_split_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
+                                uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream);
+int gpuar_hip_merge_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
+                                uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream);
+
+/* Host only, from the same definition; rules of gpuar_hip_split_planes_host. */
+int gpuar_hip_split_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+int gpuar_hip_merge_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+
+/* Host only, for tests: the kernels' register transform of one block of 16 elements (mixed: 4 * elem_bytes dwords, in place).
+ * undo == 0: the differences, `carried` being the element in front of the block; undo != 0: the inclusive prefix sums plus
+ * `carried`, and in *total (may be null) the block's sum without it. */
+int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, uint64_t carried, uint64_t *total);
+
+/* ------------------------------------------------------------------------
  * Packet size estimate and raw packets.  The codec's model starts every symbol at count 1, adds 1 per occurrence and never
  * rescales inside a packet, so a packet's ideal code length depends on its byte histogram h alone.  With
  *     lg16(k) = floor(2^16 log2 k),   LF[c] = sum of lg16(k) for k = 2 .. c   (LF[0] = LF[1] = 0)
