@@ -35,6 +35,14 @@ before they are split (hip.split_delta_batch: the same single launch), and summe
 smaller, unordered data and floats grow.  The element width is that of `planes` (planes=None: bytes).
 delta="auto" measures: it splits and estimates the batch both ways and filters the tensors for which that is predicted to pay.
 Compressed.gip(b) then carries width and filter in a version-4 trailer (`gpuar c --delta --planes=W`).
+
+With base=[...] (one tensor of the same byte count, or None, per tensor) every tensor is XORed with its base before it is
+split (hip.split_xor_batch: the same single launch, into the same temporary buffer) and XORed back, in place, after it is
+decoded (hip.merge_xor_batch; decompress needs the same bases).  The next checkpoint of a model is almost the previous one:
+against it a bf16 tensor compresses to 0.06-0.72 of what it does alone, against an unrelated base it grows.
+base_auto=True measures and keeps the bases that are predicted to pay (Compressed.based).  The CRCs are those of the original
+bytes, so a wrong base in decompress is a checksum mismatch.  Compressed.gip(b) carries a version-5 trailer
+(`gpuar c --base=FILE --planes=W`) and needs the CRCs.  A base together with `delta` is refused.
 """
 from __future__ import annotations
 
@@ -112,7 +120,8 @@ class Compressed:
     checksum=True) the CRC-32 of every packet's uncompressed bytes, `planes` (host list, n_buffers; None unless compressed with
     planes=...) the element width each buffer's bytes were split into byte planes by (1: not split), `delta` (host list of
     bools, n_buffers; None unless compressed with delta=...) which buffers went through the delta filter (their `planes`
-    entry is the filter's element width).
+    entry is the filter's element width), `based` (host list of bools, n_buffers; None unless compressed with base=...) which
+    buffers were XORed with their base and need it again in decompress.
 
     Compressed with stored=...: `stored` (uint8, device, n_packets) is 1 for every batch packet that is kept raw, `raw` (uint8,
     device) holds those packets' bytes in batch order, each at a 16-byte-aligned offset, `raw_offsets` (int64, device,
@@ -128,6 +137,7 @@ class Compressed:
     raw: object = None
     raw_offsets: object = None
     delta: list = None
+    based: list = None
 
     @property
     def n_buffers(self) -> int:
@@ -170,31 +180,39 @@ class Compressed:
 
     def gip(self, b: int) -> bytes:
         """Buffer b as a whole .gip file: what `gpuar c` writes for it (with CRCs: what `gpuar c --checksum` writes; split into
-        planes of width W > 1: what `gpuar c --planes=W` writes; filtered: what `gpuar c --delta --planes=W` writes)."""
+        planes of width W > 1: what `gpuar c --planes=W` writes; filtered: what `gpuar c --delta --planes=W` writes; XORed with
+        a base: what `gpuar c --base=FILE --planes=W` writes, which needs the CRCs -- GpuarError without checksum=True)."""
+        xored = bool(self.based[b]) if self.based is not None else False
+        if xored and self.crc32 is None:
+            raise GpuarError(f"buffer {b} was XORed with a base: its .gip form (trailer version 5) needs the CRCs that tell a reader "
+                             "it was given the wrong base -- compress with checksum=True")
         p = self.payload(b)
         out = H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
         w = self.planes[b] if self.planes is not None else 1
         filtered = bool(self.delta[b]) if self.delta is not None else False
-        if self.crc32 is not None or w > 1 or filtered:
+        if self.crc32 is not None or w > 1 or filtered or xored:
             off = self._offsets_host()
             lo, hi = self._coded_range(b)
             clens = [off[i + 1] - off[i] for i in range(lo, hi)]
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
             crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
-            out += trailer(clens, w, crcs, delta=filtered)
+            out += trailer(clens, w, crcs, delta=filtered, base=xored)
         return out
 
 
-def trailer(clens, elem_bytes=1, crcs=None, delta=False) -> bytes:
-    """The .gip trailer, little-endian, pads counted from "GIPX": version 4 for a file whose bytes went through
-    the delta filter at a width of `elem_bytes` (1 too), else version 3 for a file whose bytes were split into planes of
+def trailer(clens, elem_bytes=1, crcs=None, delta=False, base=False) -> bytes:
+    """The .gip trailer, little-endian, pads counted from "GIPX": version 5 for a file whose bytes were XORed with
+    a base and split at a width of `elem_bytes` (1 too; flags bit 2 and bit 0 set: the CRCs are mandatory), else version 4 for a
+    file whose bytes went through the delta filter at a width of `elem_bytes` (1 too), else version 3 for a file whose bytes were split into planes of
     `elem_bytes` > 1, else version 2 when `crcs` are given, else version 1.
     "GIPX" u32 version u64 n | versions 3, 4: u32 elem_bytes u32 flags (bit 0: CRCs present; version 4: bit 1, delta, set) |
     u16 clen[n] | with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG"."""
     n = len(clens)
-    body = b"GIPX" + struct.pack("<IQ", 4 if delta else 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
-    if elem_bytes > 1 or delta:
-        body += struct.pack("<II", elem_bytes, (0 if crcs is None else 1) | (2 if delta else 0))
+    if base and (delta or crcs is None):
+        raise GpuarError("a version-5 trailer (base) carries CRCs and no delta flag")
+    body = b"GIPX" + struct.pack("<IQ", 5 if base else 4 if delta else 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
+    if elem_bytes > 1 or delta or base:
+        body += struct.pack("<II", elem_bytes, (0 if crcs is None else 1) | (2 if delta else 0) | (4 if base else 0))
     body += struct.pack(f"<{n}H", *clens)
     if crcs is not None:
         body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
@@ -233,12 +251,52 @@ def delta_flags(tensors, delta):
     return flags
 
 
-def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None):
+def base_pointers(tensors, base, what="tensors"):
+    """The base per tensor that `base` asks for, as device pointers (0: none): None -> None; a list with one entry per tensor,
+    each None or a contiguous CUDA tensor of exactly the tensor's byte count, on the tensor's device and 16-byte aligned.
+    Anything else raises GpuarError.  (A base of an empty tensor counts as none.)  This function never launches."""
+    tensors = list(tensors)
+    if base is None:
+        return None
+    if not isinstance(base, (list, tuple)):
+        raise GpuarError("base: None or a list with a tensor or None per tensor")
+    if len(base) != len(tensors):
+        raise GpuarError(f"base: {len(base)} entries for {len(tensors)} {what}")
+    ptrs = []
+    for i, (t, b) in enumerate(zip(tensors, base)):
+        if b is None:
+            ptrs.append(0)
+            continue
+        if hasattr(b, "device") and hasattr(t, "device") and b.device != t.device:
+            raise GpuarError(f"base[{i}] is on {b.device}, {what}[{i}] on {t.device}")
+        have, need = _tensor_bytes(b, f"base[{i}]"), _tensor_bytes(t, f"{what}[{i}]")
+        if have != need:
+            raise GpuarError(f"base[{i}] holds {have} bytes, {what}[{i}] {need}: a base has exactly its tensor's bytes")
+        if need and b.data_ptr() % 16:
+            raise GpuarError(f"base[{i}] is not 16-byte aligned (data_ptr() % 16 = {b.data_ptr() % 16}); pass an aligned copy")
+        ptrs.append(b.data_ptr() if need else 0)
+    return ptrs
+
+
+def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None, bases=None):
     """The batch's descriptors on the device and -- where `widths` asks for it -- its buffers split into byte planes (one launch,
     into a temporary buffer): (d_ptrs, d_bytes, d_first_packet, d_coded, d_split, the pinned host copy of the descriptors, for the
     caller to hold while the launches run), d_coded the pointers of the bytes to code.  With `flags` (one bool per buffer, some
-    of them true) the same launch also filters the flagged buffers (hip.split_delta_batch); those get a split copy at any width."""
+    of them true) the same launch also filters the flagged buffers (hip.split_delta_batch); those get a split copy at any width.
+    With `bases` (one pointer per buffer, some of them not 0) the same launch XORs those buffers with their bases
+    (hip.split_xor_batch); they too get a split copy at any width."""
     import torch
+    if bases is not None and any(bases):
+        at, split_ptrs = 0, []
+        for p, size, w, q in zip(ptrs, sizes, widths, bases):
+            moved = (w != 1 or q) and size
+            split_ptrs.append(at if moved else None)
+            at += (size + 15) // 16 * 16 if moved else 0
+        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
+        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
+        (d_ptrs, d_bytes, d_fp, d_elem, d_base, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, bases, split_ptrs)
+        H.split_xor_batch(d_ptrs, d_bytes, d_fp, d_elem, d_base, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
+        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
     if flags is not None and any(flags):
         at, split_ptrs = 0, []
         for p, size, w, f in zip(ptrs, sizes, widths, flags):
@@ -325,6 +383,54 @@ def _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_
     return [first_packet[b + 1] > first_packet[b] and filtered[b] + (first_packet[b + 1] - first_packet[b]) <= plain[b] for b in range(n)]
 
 
+def _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status):
+    """base_auto=True: per buffer, whether its base is predicted to pay, and the batch split accordingly.  The batch is split and
+    estimated twice, without and with the bases -- one split launch and one estimate launch more than the path with fixed bases and
+    stored="auto" takes, and one synchronisation -- and a buffer keeps its base iff est_xor + its packets <= est_plain (the rule
+    of _auto_delta; a tie goes to no base).  Nothing is split a third time: both split copies are kept (twice the temporary
+    memory until the slots are freed) and every buffer is coded from the copy of its choice.  Returns (the choices, what _split
+    returns with d_coded and d_split made of both copies, the chosen copy's per-packet estimates); (all False, None, None)
+    where there is nothing to choose."""
+    import torch
+    n = len(sizes)
+    if n_packets == 0 or not any(bases):
+        return [False] * n, None, None
+    halves, estimates, totals = [], [], []
+    for with_bases in (None, bases):
+        halves.append(_split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, None, with_bases))
+        d_ptrs, d_bytes, d_fp, d_coded = halves[-1][:4]
+        estimates.append(H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)[:n_packets].to(torch.int64))
+        buf, _ptr, _len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+        totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, estimates[-1]))
+    plain, xored = torch.stack(totals).tolist()
+    _raise_on_status(d_status, "split_xor_batch")
+    keep = [bool(bases[b]) and first_packet[b + 1] > first_packet[b] and xored[b] + (first_packet[b + 1] - first_packet[b]) <= plain[b]
+            for b in range(n)]
+    (d_keep,), pinned = _upload(device, [int(k) for k in keep])
+    d_keep = d_keep != 0
+    d_coded = torch.where(d_keep, halves[1][3], halves[0][3])
+    d_est = torch.where(d_keep[buf], estimates[1], estimates[0])
+    return keep, (d_ptrs, d_bytes, d_fp, d_coded, (halves[0][4], halves[1][4]), (halves[0][5], halves[1][5], pinned)), d_est
+
+
+def _check_base(tensors, delta, base, base_auto):
+    """What compress and estimate refuse of `base` and `base_auto`, before anything is launched: a base together with `delta`,
+    base_auto without a base, and whatever base_pointers refuses."""
+    if base is None and base_auto:
+        raise GpuarError("base_auto=True needs base=[...]")
+    if base is not None and delta is not None:
+        raise GpuarError("base together with delta: that combination is not built (DESIGN.md 4.10)")
+    base_pointers(tensors, base)
+
+
+def _base_arguments(tensors, widths, base):
+    """(widths, base pointers or None) for compress and estimate: a base without `planes` works on bytes."""
+    if base is None:
+        return widths, None
+    bases = base_pointers(tensors, base)
+    return (widths if widths is not None else [1] * len(bases)), bases
+
+
 def _filter_arguments(tensors, planes, delta):
     """(widths, flags or "auto" or None) for compress and estimate: a filter without `planes` works on bytes."""
     widths = plane_widths(tensors, planes)
@@ -370,28 +476,38 @@ def survey_widths(tensors, stored=None) -> list:
             for b, totals in enumerate(survey(tensors, stored="auto" if isinstance(stored, str) and stored == "auto" else None))]
 
 
-def estimate(tensors, planes=None, stored=None, delta=None) -> list:
+def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
     asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
     split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front).  `delta`: as
-    compress -- the estimate is that of the filtered, split bytes (delta="auto": of each tensor's better half)."""
+    compress -- the estimate is that of the filtered, split bytes (delta="auto": of each tensor's better half).  `base`,
+    `base_auto`: as compress -- the estimate is that of the XORed, split bytes (base_auto: of each tensor's better half, from
+    _auto_base's two split and two estimate launches alone)."""
     import torch
     if stored is not None and stored != "auto":
         raise GpuarError(f"stored={stored!r}: None or \"auto\"")
     tensors = list(tensors)
+    _check_base(tensors, delta, base, base_auto)
     if isinstance(planes, str) and planes == "survey":
         planes = survey_widths(tensors, stored)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     widths, flags = _filter_arguments(tensors, planes, delta)
+    widths, bases = _base_arguments(tensors, widths, base)
     n = len(sizes)
     if n_packets == 0:
         return [0] * n
     d_status = torch.zeros(1, dtype=torch.int32, device=device)
     if flags == "auto":
         flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
-    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status, flags)
-    d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
+    chosen = d_est = None
+    if bases is not None and base_auto:
+        _choice, chosen, d_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, None, d_status)
+    if chosen is None:
+        chosen = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status, flags, bases)
+    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = chosen
+    if d_est is None:
+        d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
     buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
     if stored == "auto":
         d_est = torch.where(d_est >= 4 + d_len, d_len, d_est)
@@ -400,7 +516,7 @@ def estimate(tensors, planes=None, stored=None, delta=None) -> list:
     return totals.tolist()
 
 
-def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None) -> Compressed:
+def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None, base=None, base_auto=False) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
     compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
     every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
@@ -413,15 +529,24 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     False | one bool per tensor | "auto": replace the elements of the flagged tensors, at the width `planes` gives (planes=None:
     1), by their differences inside every group, in the launch that splits (hip.split_delta_batch); "auto" flags the tensors
     for which two more split and two more estimate launches predict a gain (_auto_delta).  None takes exactly the path taken
-    without the keyword.  The CRCs stay those of the original bytes; `stored` sees the filtered, split bytes.  See Compressed."""
+    without the keyword.  The CRCs stay those of the original bytes; `stored` sees the filtered, split bytes.  `base`: None | a
+    list with, per tensor, None or a contiguous CUDA tensor of exactly the tensor's byte count on its device, 16-byte aligned
+    (base_pointers; anything else raises before any launch, and so does a base together with `delta`): XOR the tensor with it, at
+    the width `planes` gives (planes=None: 1), in the launch that splits (hip.split_xor_batch, into the same temporary buffer:
+    inputs and bases are never modified).  planes="survey" surveys the original bytes.  `base_auto`: keep only the bases for
+    which splitting and estimating the batch both ways predicts a gain (_auto_base: one split and one estimate launch more than
+    fixed bases with stored="auto" take, one synchronisation, both split copies kept and none made a third time);
+    Compressed.based says which.  base=None takes exactly the path taken without the keyword.  See Compressed."""
     import torch
     tensors = list(tensors)
+    _check_base(tensors, delta, base, base_auto)                 # (raises before the survey's launch)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     if isinstance(planes, str) and planes == "survey":
         stored = _stored_argument(stored, n_packets)
         with torch.cuda.stream(stream) if stream is not None else _nothing():
             planes = survey_widths(tensors, stored)
     widths, flags = _filter_arguments(tensors, planes, delta)
+    widths, bases = _base_arguments(tensors, widths, base)
     stored = _stored_argument(stored, n_packets)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -431,7 +556,13 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if flags == "auto":
             flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
-        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
+        chosen = d_chosen_est = None
+        if bases is not None and base_auto:
+            choice, chosen, d_chosen_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status)
+            bases = [q if keep else 0 for q, keep in zip(bases, choice)]
+        if chosen is None:
+            chosen = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags, bases)
+        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = chosen
         if stored is None:
             d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
             d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
@@ -439,7 +570,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
             # every packet a buffer of its own: the coded ones go to the encoder, the stored ones to the copy, both in batch order
             _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
             if stored == "auto":
-                d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+                d_est = d_chosen_est if d_chosen_est is not None else \
+                    H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
                 d_flags = (d_est[:n_packets] >= 4 + d_pkt_len).to(torch.int64)
             else:
                 d_flags = torch.tensor(stored, dtype=torch.int64).to(device)
@@ -466,17 +598,20 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         del d_slots, d_split
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
                       crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
-                      raw_offsets=d_raw_offsets, delta=flags)
+                      raw_offsets=d_raw_offsets, delta=flags, based=[bool(q) for q in bases] if bases is not None else None)
 
 
-def decompress(c: Compressed, out=None, stream=None, verify=True):
+def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
     """Decode every buffer of `c` in one launch.  Returns a list of uint8 tensors, or fills the caller's tensors `out` (one per
     buffer, contiguous CUDA tensors of at least the buffer's bytes, 16-byte aligned) and returns them.  When `c` carries CRCs
     and `verify` is true, the decoded bytes are checked against them (one more launch): a mismatch raises GpuarError naming
     the first buffer and packet that differ.  Buffers that were split into byte planes are merged back in place in `out`
     after decoding and before verifying: the CRCs are those of the original bytes; where a buffer went through the delta filter,
     that launch is hip.merge_delta_batch, which also sums the differences up again.  Packets that were stored raw are copied
-    (one more launch), the others decoded."""
+    (one more launch), the others decoded.  `base`: as in compress; every buffer with c.based[b] needs base[b], the tensor it
+    was compressed against (a missing one, one of another size, device or alignment, or one that overlaps any tensor of `out`
+    raises before any launch; entries of the other buffers are ignored); the merge is then hip.merge_xor_batch.  A base with other contents
+    cannot be told from damage: with CRCs it is reported as the checksum mismatch, without them it goes unnoticed."""
     import torch
     device = c.stream.device
     if out is None:
@@ -487,6 +622,33 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
     for b, (have, need) in enumerate(zip(room, c.sizes)):
         if have < need:
             raise GpuarError(f"out[{b}] holds {have} bytes, buffer {b} needs {need}")
+    bases = None
+    if c.based is not None and any(c.based):
+        # the outputs as intervals by their start, with the furthest end so far: a base overlaps one iff that end lies behind its start
+        spans = sorted((p, p + need, b) for b, (p, need) in enumerate(zip(ptrs, c.sizes)) if need)
+        starts, reach = [s for s, _e, _b in spans], []
+        for _s, e, b in spans:
+            reach.append(max(reach[-1], (e, b)) if reach else (e, b))
+        if not isinstance(base, (list, tuple)) or len(base) != c.n_buffers:
+            raise GpuarError(f"this batch was compressed against bases: decompress needs base=[...] with {c.n_buffers} entries")
+        bases = []
+        for b, (t, need) in enumerate(zip(base, c.sizes)):
+            if not c.based[b] or need == 0:
+                bases.append(0)
+                continue
+            if t is None:
+                raise GpuarError(f"buffer {b} was compressed against a base: base[{b}] is missing")
+            if hasattr(t, "device") and t.device != device:
+                raise GpuarError(f"base[{b}] is on {t.device}, the batch on {device}")
+            have = _tensor_bytes(t, f"base[{b}]")
+            if have != need:
+                raise GpuarError(f"base[{b}] holds {have} bytes, buffer {b} has {need}: a base has exactly its buffer's bytes")
+            if t.data_ptr() % 16:
+                raise GpuarError(f"base[{b}] is not 16-byte aligned (data_ptr() % 16 = {t.data_ptr() % 16}); pass an aligned copy")
+            before = bisect.bisect_left(starts, t.data_ptr() + need)           # the outputs that start in front of the base's end
+            if before and reach[before - 1][0] > t.data_ptr():
+                raise GpuarError(f"base[{b}] overlaps out[{reach[before - 1][1]}]: the merge runs in place in `out` while the bases are read")
+            bases.append(t.data_ptr())
     with torch.cuda.stream(stream) if stream is not None else _nothing():
         (d_ptrs, d_room, d_fp, d_sizes), _keep = _upload(device, ptrs, room, c.first_packet, c.sizes)
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
@@ -506,7 +668,11 @@ def decompress(c: Compressed, out=None, stream=None, verify=True):
             if n_stored:
                 H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
-        if c.delta is not None and any(c.delta) and c.n_packets:
+        if bases is not None and any(bases) and c.n_packets:
+            (d_elem, d_base), _keep2 = _upload(device, c.planes, bases)
+            H.merge_xor_batch(d_ptrs, d_sizes, d_fp, d_elem, d_base, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
+            _raise_on_status(d_status, "merge_xor_batch")
+        elif c.delta is not None and any(c.delta) and c.n_packets:
             (d_elem, d_filter), _keep2 = _upload(device, c.planes, [int(f) for f in c.delta])
             H.merge_delta_batch(d_ptrs, d_sizes, d_fp, d_elem, d_filter, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
             _raise_on_status(d_status, "merge_delta_batch")

@@ -24,6 +24,7 @@
 //    no v_readlane in the loop);
 //  * crc32_kernel: the per-packet CRC-32 of the .gip trailer, computed or verified;
 //  * split_planes_kernel / merge_planes_kernel, planes_tail_kernel: byte-plane splitting of typed data (planes.h);
+//  * split_xor_kernel / merge_xor_kernel, xor_tail_kernel: the same with an XOR against a base buffer fused in (xorbase.h);
 //  * split_delta_kernel / merge_delta_kernel, delta_tail_kernel: the same with an element-wise delta filter fused in (delta.h,
 //    DESIGN.md 4.9);
 //  * compaction (scan + gather), synthetic-stream generators, a plain copy (the measured HBM roof).
@@ -44,6 +45,7 @@
 #include "crc32.h"
 #include "planes.h"
 #include "delta.h"
+#include "xorbase.h"
 #include "estimate.h"
 #include "survey.h"
 
@@ -2591,6 +2593,192 @@ delta_tail_kernel(DeltaArgs d) {
 }
 
 // ---------------------------------------------------------------------------
+// XOR against a base (xorbase.h): split_xor = split_planes of buffer ^ base, merge_xor its inverse, fused into
+// the byte-plane kernels' shape: no second pass over memory and no temporary buffer.
+//
+// Full groups are planes_group's: 512 threads, 16 elements each, 16-byte accesses on both sides, every load -- of the buffer
+// and of the base -- before the barrier and every store behind it.  The base is needed on the MIXED side in both directions (w
+// quads back to back per thread), the side that is slow to read for w >= 4 (neighbouring lanes 16 w bytes apart), so it is read
+// like a plane, perfectly coalesced, and handed to its lanes through one group of LDS around the barrier the shape already has
+// (w = 1: no LDS); one more barrier behind the stores frees the LDS for a workgroup that strides on.  SPLIT XORs the registers
+// in front of planes_block, MERGE behind it.
+// A batch carries one more pointer per buffer, `base_ptrs`: 0 takes planes_group (the output is split_planes_batch's), a
+// 16-byte aligned pointer the path above, a misaligned one flags BAD_BATCH and leaves the buffer alone; the choice is uniform
+// over a workgroup.  A base never overlaps an output: the single-buffer calls check it, a batch's caller sees to it.
+// The tail is xor_tail_kernel's, one workgroup per buffer through LDS like planes_tail: by quads in -- buffer and, for the
+// split, base, XORed on the way into LDS; the merge reads the base by the dwords and last bytes it writes -- so nothing
+// is read beyond the 16-byte piece that holds the last byte and nothing written beyond byte n.
+// The existing kernels are not touched: callers without a base keep launching them.
+// ---------------------------------------------------------------------------
+struct XorArgs {
+    PlanesArgs p;
+    const uint8_t *base;                    // one buffer: its base ...
+    const uint8_t *const *base_ptrs;        // ... a batch: per buffer 0 = planes alone, else the base
+};
+
+// one full group at `in` -> `out` against `base` (all 16-byte aligned; out == in is fine), the whole workgroup; `lds`: room for
+// one group (W > 1)
+template <int W, bool Merge>
+__device__ __forceinline__ void xor_group(const uint8_t *in, const uint8_t *base, uint8_t *out, PlanesQuad *lds) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    const uint32_t t = threadIdx.x;
+    const uint32_t from_at = Merge ? 16u * t : 16u * W * t, from_step = Merge ? kPlanePacket : 16u;
+    const uint32_t to_at = Merge ? 16u * W * t : 16u * t, to_step = Merge ? 16u : kPlanePacket;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(in + from_at));
+    // the base is needed on the mixed side, W quads back to back per thread, but read like a plane: quad k * 512 + t, perfectly
+    // coalesced, and handed to its thread through LDS (W = 1: the two shapes are one)
+    const GlobalQuad *with = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(base + 16u * t));
+    PlanesQuad q[W], b[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) q[k] = src[k * (from_step / 16u)];
+#pragma unroll
+    for (int k = 0; k < W; ++k) b[k] = with[k * kPlaneThreads];
+    // the loads have arrived in every thread before any thread stores (in place: another thread's store goes where this one reads)
+#pragma unroll
+    for (int k = 0; k < W; ++k) asm volatile("" : "+v"(q[k]), "+v"(b[k]));
+    if constexpr (W > 1) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) lds[k * kPlaneThreads + t] = b[k];
+    }
+    __syncthreads();
+    if constexpr (W > 1) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) b[k] = lds[W * t + k];
+    }
+    uint32_t from[4 * W], to[4 * W], mask[4 * W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        from[4 * k] = q[k].x, from[4 * k + 1] = q[k].y, from[4 * k + 2] = q[k].z, from[4 * k + 3] = q[k].w;
+        mask[4 * k] = b[k].x, mask[4 * k + 1] = b[k].y, mask[4 * k + 2] = b[k].z, mask[4 * k + 3] = b[k].w;
+    }
+    if constexpr (!Merge) xor_block<W>(from, mask);
+    planes_block<W, Merge>(from, to, PlanesPerm());
+    if constexpr (Merge) xor_block<W>(to, mask);
+    GlobalQuad *dst = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(out + to_at));
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+        PlanesQuad v;
+        v.x = to[4 * k], v.y = to[4 * k + 1], v.z = to[4 * k + 2], v.w = to[4 * k + 3];
+        dst[k * (to_step / 16u)] = v;
+    }
+    if constexpr (W > 1) __syncthreads();      // a workgroup that strides on puts the next group's base into the same LDS
+}
+
+template <bool Merge>
+__device__ __forceinline__ void xor_full(const XorArgs &x, PlanesQuad *lds) {
+    const PlanesArgs &a = x.p;
+    for (uint64_t packet = blockIdx.x; packet < a.n_packets; packet += gridDim.x) {
+        const uint8_t *in = a.in, *base = x.base;
+        uint8_t *out = a.out;
+        uint64_t n_bytes = a.n_bytes, j = packet;
+        uint32_t w = a.elem;
+        if (a.in_ptrs) {
+            const BatchLane bl = batch_lane(a.in_ptrs, a.bytes, a.first_packet, a.n_buffers, packet);
+            PlanesBuffer pb = {nullptr, nullptr, 0u, 0u};
+            base = nullptr;
+            if (bl.owned && bl.count) pb = planes_buffer(a, bl.buffer), base = x.base_ptrs[bl.buffer];
+            if (pb.w == 0u || (reinterpret_cast<uintptr_t>(base) & 15u) != 0u) {
+                if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                continue;
+            }
+            in = pb.in, out = pb.out, n_bytes = pb.n_bytes, w = pb.w;
+            j = packet - a.first_packet[bl.buffer];
+        }
+        w = __builtin_amdgcn_readfirstlane(w);
+        const uint32_t based = __builtin_amdgcn_readfirstlane(base != nullptr ? 1u : 0u);
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(j & (w - 1u)));
+        const uint64_t at = j * kPacket;
+        if (lead != 0u || n_bytes - at < static_cast<uint64_t>(w) * kPacket) continue;      // not a group's first packet, or the tail
+        if (based == 0u) {                                                                  // planes alone: planes_full's path
+            if (w == 1u && in == out) continue;
+            if (w == 8u) planes_group<8, Merge>(in + at, out + at);
+            else if (w == 4u) planes_group<4, Merge>(in + at, out + at);
+            else if (w == 2u) planes_group<2, Merge>(in + at, out + at);
+            else planes_group<1, Merge>(in + at, out + at);
+            continue;
+        }
+        if (w == 8u) xor_group<8, Merge>(in + at, base + at, out + at, lds);
+        else if (w == 4u) xor_group<4, Merge>(in + at, base + at, out + at, lds);
+        else if (w == 2u) xor_group<2, Merge>(in + at, base + at, out + at, lds);
+        else xor_group<1, Merge>(in + at, base + at, out + at, lds);
+    }
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+split_xor_kernel(XorArgs x) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    xor_full<false>(x, lds);
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+merge_xor_kernel(XorArgs x) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    xor_full<true>(x, lds);
+}
+
+// the tail of a buffer with a base: planes_tail with the XOR on the way into LDS (split) or on the way out of it (merge)
+template <bool Merge>
+__device__ __forceinline__ void xor_tail(const PlanesBuffer &pb, const uint8_t *base, PlanesQuad *lds) {
+    const uint32_t w = pb.w;
+    const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
+    if (r == 0u) return;
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
+    const uintptr_t with = reinterpret_cast<uintptr_t>(base + (pb.n_bytes - r));
+    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) {
+        PlanesQuad v = src[i];
+        if constexpr (!Merge) v ^= reinterpret_cast<const GlobalQuad *>(with)[i];
+        lds[i] = v;
+    }
+    __syncthreads();
+    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
+    const uint32_t log_w = 31u - __builtin_clz(w);
+    // output byte o of the tail comes from input byte ... (planes_tail's map)
+    auto source = [&](uint32_t o) -> uint32_t {
+        if (o >= e * w) return o;                                           // the last r mod w bytes (and everything when e = 0)
+        if (!Merge) return (o % e << log_w) + o / e;                        // o = k e + i  <-  i w + k
+        return (o & (w - 1u)) * e + (o >> log_w);                           // o = i w + k  <-  k e + i
+    };
+    uint8_t *out = pb.out + (pb.n_bytes - r);
+    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
+    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) {
+        const uint32_t o = 4u * i;
+        uint32_t v = bytes[source(o)] | static_cast<uint32_t>(bytes[source(o + 1u)]) << 8 | static_cast<uint32_t>(bytes[source(o + 2u)]) << 16 |
+                     static_cast<uint32_t>(bytes[source(o + 3u)]) << 24;
+        if constexpr (Merge) v ^= reinterpret_cast<const GlobalWord *>(with)[i];
+        words[i] = v;
+    }
+    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
+    if (threadIdx.x < (r & 3u)) {
+        const uint32_t o = (r & ~3u) + threadIdx.x;
+        uint8_t v = bytes[source(o)];
+        if constexpr (Merge) v ^= reinterpret_cast<const GlobalByte *>(with)[o];
+        last[o] = v;
+    }
+}
+
+template <bool Merge>
+__global__ void __launch_bounds__(kPlaneThreads)
+xor_tail_kernel(XorArgs x) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    const PlanesArgs &a = x.p;
+    if (!a.in_ptrs) {
+        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
+        xor_tail<Merge>(pb, x.base, lds);
+        return;
+    }
+    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
+        const PlanesBuffer pb = planes_buffer(a, static_cast<uint32_t>(b));      // (an unusable buffer with packets was flagged by the kernel above)
+        const uint8_t *base = x.base_ptrs[b];
+        if (base == nullptr) planes_tail<Merge>(pb, lds);
+        else if (pb.w != 0u && (reinterpret_cast<uintptr_t>(base) & 15u) == 0u) xor_tail<Merge>(pb, base, lds);
+        __syncthreads();                                                         // the next buffer's tail goes into the same LDS
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Packet size estimate (estimate.h): est[p] = the clen the codec would give packet p, from the packet's byte
 // histogram alone, for one buffer or a batch -- and the copy that moves the packets the estimate says cannot shrink.
 //
@@ -3444,6 +3632,101 @@ int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, u
     else if (elem_bytes == 2u) run(std::integral_constant<int, 2>());
     else run(std::integral_constant<int, 1>());
     return GPUAR_OK;
+}
+
+static int launch_xor(bool merge, const gpuar::XorArgs &x, size_t n_tails, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint32_t blocks = x.p.n_packets < gpuar::kPlaneGridCap ? x.p.n_packets : gpuar::kPlaneGridCap;
+    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
+    if (merge) gpuar::merge_xor_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(x);
+    else gpuar::split_xor_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(x);
+    const int e = check_launch();
+    if (e != GPUAR_OK || tails == 0u) return e;
+    if (merge) gpuar::xor_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(x);
+    else gpuar::xor_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(x);
+    return check_launch();
+}
+
+static int xor_single(bool merge, const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!d_in || !d_out || !d_base || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_in) || !aligned16(d_out) || !aligned16(d_base)) return GPUAR_ERR_ALIGNMENT;
+    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out), base = reinterpret_cast<uintptr_t>(d_base);
+    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
+    if (base < out + n_bytes && out < base + n_bytes) return GPUAR_ERR_ARGUMENT;               // the base is only read
+    gpuar::XorArgs x = {};                                                                     // (a width of 1 in place is work too)
+    x.p.in = d_in;
+    x.p.out = d_out;
+    x.p.n_bytes = n_bytes;
+    x.p.elem = elem_bytes;
+    x.p.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    x.base = d_base;
+    return launch_xor(merge, x, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+}
+
+static int xor_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                     const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                     uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_elem_bytes || !d_base_ptrs || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_base_ptrs) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
+        return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::XorArgs x = {};
+    x.p.in_ptrs = d_in_ptrs;
+    x.p.out_ptrs = d_out_ptrs;
+    x.p.bytes = d_bytes;
+    x.p.first_packet = d_first_packet;
+    x.p.elem_bytes = d_elem_bytes;
+    x.p.n_buffers = static_cast<uint32_t>(n_buffers);
+    x.p.n_packets = static_cast<uint32_t>(n_packets);
+    x.p.status = status;
+    x.base_ptrs = d_base_ptrs;
+    return launch_xor(merge, x, n_buffers, stream);
+}
+
+int gpuar_hip_split_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return xor_single(false, d_in, d_base, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_merge_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
+    return xor_single(true, d_in, d_base, n_bytes, elem_bytes, d_out, stream);
+}
+
+int gpuar_hip_split_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                              const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                              uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return xor_batch(false, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+int gpuar_hip_merge_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                              const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                              uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return xor_batch(true, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, d_status, stream);
+}
+
+static int xor_on_host(bool merge, const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !out || !base) return GPUAR_ERR_ARGUMENT;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out), c = reinterpret_cast<uintptr_t>(base);
+    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
+    if (c < b + n_bytes && b < c + n_bytes) return GPUAR_ERR_ARGUMENT;
+    if (merge) gpuar::merge_xor_host(in, base, n_bytes, elem_bytes, out);
+    else gpuar::split_xor_host(in, base, n_bytes, elem_bytes, out);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_split_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return xor_on_host(false, in, base, n_bytes, elem_bytes, out);
+}
+
+int gpuar_hip_merge_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
+    return xor_on_host(true, in, base, n_bytes, elem_bytes, out);
 }
 
 static int launch_estimate(const gpuar::CrcArgs &a, void *stream) {

@@ -1,6 +1,7 @@
 #include "compressor.hpp"
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cstdlib>
@@ -71,7 +72,28 @@ int Compressor::choosePlanes(unsigned long long total[4]) {
     return planes;
 }
 
+void Compressor::openBase(uint64_t expect, const char *what) {
+    if (delta) throw std::runtime_error("--base together with --delta is not supported");
+    if (baseFd >= 0) ::close(baseFd);
+    baseFd = ::open(baseFileName.c_str(), O_RDONLY);
+    struct stat st;
+    if (baseFd < 0 || ::fstat(baseFd, &st) != 0) throw std::runtime_error("Can not open base file: " + baseFileName);
+    if (static_cast<uint64_t>(st.st_size) != expect)
+        throw std::runtime_error("The base file holds " + std::to_string(st.st_size) + " bytes, " + what + " " + std::to_string(expect) +
+                                 ": --base takes a file of exactly that length");
+}
+
+void Compressor::readBase(uint8_t *dst, size_t n, uint64_t at) {
+    for (size_t done = 0; done < n;) {
+        const ssize_t got = ::pread(baseFd, dst + done, n - done, static_cast<off_t>(at + done));
+        if (got <= 0) throw std::runtime_error("Read base file failed");
+        done += static_cast<size_t>(got);
+    }
+}
+
 void Compressor::closeFiles() {
+    if (baseFd >= 0) ::close(baseFd);
+    baseFd = -1;
     if (saveFile) std::fclose(saveFile);
     if (openFile) std::fclose(openFile);
     saveFile = openFile = nullptr;

@@ -5,6 +5,7 @@
 // no GPU runtime, so `--host` works on a machine without one.
 #pragma once
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -45,6 +46,10 @@ class Compressor {
                                       // version-3 trailer, from which decompress learns the width; 1: no transform, no such trailer
     bool delta = false;               // compress: replace the elements (`planes` bytes wide; 1 too) of every group by their differences
                                       // before the split (../delta.h) and say so in a version-4 trailer
+    std::string baseFileName;         // compress: XOR the input with this file of the same length before the split (../xorbase.h) and say
+                                      // so in a version-5 trailer, with CRCs; decompress: the base a version-5 file needs
+    int baseFd = -1;                  // ... open while a job runs (openBase)
+    bool checksumAsked = false;       // what setWriteChecksum was given: a base turns writeChecksum on by itself
 
     // the error a decompress raises for a packet whose decoded bytes do not match the CRC-32 of its trailer
     static std::runtime_error checksumError(size_t packet, uint64_t begin, uint64_t end) {
@@ -61,6 +66,11 @@ class Compressor {
         return std::runtime_error("Incorrect file format: the trailer says the file holds delta-filtered elements (version 4) but it is damaged, "
                                   "carries a width other than 1, 2, 4 or 8, lacks the delta flag, or carries flags this gpuar does not know");
     }
+    // the same for a trailer that says the file was XORed with a base: going on would hand back the XOR
+    static std::runtime_error baseTrailerError() {
+        return std::runtime_error("Incorrect file format: the trailer says the file was XORed with a base (version 5) but it is damaged, "
+                                  "carries a width other than 1, 2, 4 or 8, lacks the base flag or the checksums, or carries flags this gpuar does not know");
+    }
     static std::runtime_error planesPacketError(size_t packet) {
         return std::runtime_error("Incorrect file format: packet " + std::to_string(packet) + " of a file of byte planes is not the last one and "
                                   "does not hold 8192 bytes");
@@ -70,20 +80,32 @@ class Compressor {
     }
 
     // The trailer of the open .gip (packet_index.hpp), empty when there is none a reader may use: one that says version 3 and
-    // cannot be used is an error, one that says version 2 and does not fit a warning.
+    // cannot be used is an error, one that says version 2 and does not fit a warning.  A version-5 file needs the base it was
+    // compressed against (setBaseFileName), any other file refuses one: both are errors before anything is written.
     Trailer loadTrailer(size_t stream_end, size_t fileSize) {
         Trailer trailer;
         const Trailer::Status status = Trailer::load(openFile, FileHeader::HEADER_LENGTH, stream_end, fileSize, trailer);
         if (status == Trailer::Status::unusable) throw planesTrailerError();
         if (status == Trailer::Status::unusable_delta) throw deltaTrailerError();
+        if (status == Trailer::Status::unusable_base) throw baseTrailerError();
+        if (trailer.based() && !based())
+            throw std::runtime_error("This file was compressed against a base (trailer version 5): pass the same file with --base=FILE");
+        if (!trailer.based() && based())
+            throw std::runtime_error("--base was given, but this file was not compressed against a base (no version-5 trailer)");
         if (status == Trailer::Status::malformed) warnMalformedTrailer();
         return trailer;
     }
     // compress: whether the options ask for a trailer, and that trailer appended at the current position of the output
-    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta; }
+    bool based() const { return !baseFileName.empty(); }
+    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta || based(); }
     void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs) {
-        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta);
+        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta, based());
     }
+    // Opens the base file and checks that it holds exactly `expect` bytes (those of `what`); with the delta filter on it throws:
+    // that combination is not built.  closeFiles() closes it.
+    void openBase(uint64_t expect, const char *what);
+    // base[at .. at + n) -> dst, or throws
+    void readBase(uint8_t *dst, size_t n, uint64_t at);
     static constexpr size_t kPacketBytes = 8192;
     // What a trailer of `n_packets` packets says of the bytes that packet `packet` of the file holds by its header (`ulen`).
     // Byte planes: every packet but the file's last holds 8192 bytes, or the groups are not where the merge takes them to be.
@@ -116,12 +138,20 @@ class Compressor {
     void setOpenFileName(const std::string &fileName) { openFileName = fileName; }
     void setSaveFileName(const std::string &fileName) { saveFileName = fileName; }
     void setWriteIndex(bool on) { writeIndex = on; }
-    void setWriteChecksum(bool on) { writeChecksum = on; }
+    void setWriteChecksum(bool on) {
+        checksumAsked = on;
+        writeChecksum = on || based();
+    }
     void setPlanes(int elem_bytes) {
         if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8) throw std::invalid_argument("planes: the element width is 1, 2, 4 or 8");
         planes = elem_bytes;
     }
     void setDelta(bool on) { delta = on; }
+    // compress: XOR against this file (implies the checksums); decompress: the base of a version-5 file.  Empty: none.
+    void setBaseFileName(const std::string &fileName) {
+        baseFileName = fileName;
+        writeChecksum = checksumAsked || based();
+    }
     // `--planes=auto`: sets the width from the input's own bytes and returns it -- gpuar::choose_width of the totals that
     // gpuar::survey_host (../survey.h) predicts for the first min(file size, kSurveyPrefix) bytes taken as a buffer of their own,
     // written to total[4] (widths 1, 2, 4, 8).  On the host, from one pread, before either pipeline starts: the prefix is a

@@ -15,6 +15,7 @@
 #include "../lane_codec.h"
 #include "../planes.h"
 #include "../delta.h"
+#include "../xorbase.h"
 #include "file_header.hpp"
 #include "packet_index.hpp"
 
@@ -107,21 +108,27 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     // file's last one can be shorter, and its tail is the file's tail); the CRCs stay those of the bytes as read
     static_assert(kBatchPackets % 8 == 0, "a batch starts on a group boundary for every element width");
     // --delta: the same with the elements' differences inside every group in front of the split (at a width of 1 too)
-    const bool splitting = planes > 1 || delta;
-    std::vector<uint8_t> split(splitting ? in.size() : 0);
+    // --base: the same with the XOR against the base's bytes at the same file offsets in front of the split (at a width of 1 too)
+    const bool splitting = planes > 1 || delta || based();
+    std::vector<uint8_t> split(splitting ? in.size() : 0), base(based() ? in.size() : 0);
+    uint64_t file_at = 0;
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
     std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
     const bool trailer = wantsTrailer();
     try {
+        if (based()) openBase(info.uncompressedFileSize, "the input");
         for (;;) {
             io_timer.start();
             const size_t got = std::fread(in.data(), 1, kBatchPackets * gpuar::kPacket, openFile);
+            if (got && based()) readBase(base.data(), got, file_at);
+            file_at += got;
             io_timer.stop();
             if (got == 0) break;
             const size_t np = (got + gpuar::kPacket - 1) / gpuar::kPacket;
             process_timer.start();     // model init + codec only, as src/cpu_compressor.cpp:157-161
-            if (delta) gpuar::split_delta_host(in.data(), got, static_cast<uint32_t>(planes), split.data());
+            if (based()) gpuar::split_xor_host(in.data(), base.data(), got, static_cast<uint32_t>(planes), split.data());
+            else if (delta) gpuar::split_delta_host(in.data(), got, static_cast<uint32_t>(planes), split.data());
             else if (planes > 1) gpuar::planes_host<false>(in.data(), got, static_cast<uint32_t>(planes), split.data());
             const uint8_t *coded = splitting ? split.data() : in.data();
             for_each_packet(np, nthreads, [&](size_t p) {
@@ -192,6 +199,8 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         const unsigned nthreads = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
         std::vector<uint8_t> window(kBatchPackets * gpuar::kSlot + 65536 + 16), out(kBatchPackets * gpuar::kPacket);
         std::vector<uint8_t> decoded(merging ? out.size() : 0);      // byte planes: a window is decoded here and merged into `out`
+        std::vector<uint8_t> base(trailer.based() ? out.size() : 0);  // ... and XORed with these bytes of the base
+        if (trailer.based()) openBase(info.uncompressedFileSize, "the file");
         std::vector<size_t> offsets(kBatchPackets + 1);
         std::vector<uint32_t> ulen(kBatchPackets);
         size_t file_pos = FileHeader::HEADER_LENGTH, next_packet = 0;
@@ -242,7 +251,11 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                     checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
                     total += ulen[p];
                 }
-                if (trailer.filtering()) gpuar::merge_delta_host(decoded.data(), total, trailer.elem_bytes, out.data());
+                if (trailer.based()) {
+                    // (every packet in front of this window holds 8192 bytes: checkPlanesPacket)
+                    readBase(base.data(), total, static_cast<uint64_t>(first_packet) * gpuar::kPacket);
+                    gpuar::merge_xor_host(decoded.data(), base.data(), total, trailer.elem_bytes, out.data());
+                } else if (trailer.filtering()) gpuar::merge_delta_host(decoded.data(), total, trailer.elem_bytes, out.data());
                 else gpuar::planes_host<true>(decoded.data(), total, trailer.elem_bytes, out.data());
             }
             if (verify) {

@@ -425,6 +425,7 @@ struct GPUCompressor::DeviceBuffers {
     uint32_t *d_crc = nullptr;      // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
     uint32_t *h_crc = nullptr;      // pinned, the same
     uint8_t *d_planes = nullptr;    // cap * 8192 (--planes, --delta / a version-3 or -4 trailer): the chunk split into byte planes, or merged back
+    uint8_t *d_base = nullptr;      // cap * 8192 (--base / a version-5 trailer): the base's bytes of the chunk's byte range
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
     // the lane's pinned pieces and which of them are free
@@ -465,10 +466,16 @@ struct GPUCompressor::DeviceBuffers {
     void allocatePlanes() {
         if (!d_planes) hip_check(hipMalloc(reinterpret_cast<void **>(&d_planes), cap * kPacket), "hipMalloc");
     }
+    // and one for the base's bytes of a job that XORs against a base
+    void allocateBase() {
+        if (!d_base) hip_check(hipMalloc(reinterpret_cast<void **>(&d_base), cap * kPacket), "hipMalloc");
+    }
     void release() {
         if (!cap) return;
         (void)hipSetDevice(device);
         (void)hipFree(d_plain);
+        if (d_base) (void)hipFree(d_base);
+        d_base = nullptr;
         if (d_planes) (void)hipFree(d_planes);
         d_planes = nullptr;
         if (d_slots) (void)hipFree(d_slots);
@@ -548,6 +555,11 @@ struct GPUCompressor::DeviceBuffers {
             }
             return true;
         }
+        stage(dst, fd, at, n, error);
+        return false;
+    }
+    // `n` bytes of file `fd` at `at` -> dst (device) by pread into the lane's pinned pieces, each copied on the lane's stream
+    void stage(uint8_t *dst, int fd, uint64_t at, size_t n, const char *error) {
         for (size_t done = 0; done < n;) {
             const size_t k = takePiece();
             const size_t part = std::min(piece_bytes, n - done);
@@ -562,8 +574,11 @@ struct GPUCompressor::DeviceBuffers {
             givePiece(k);
             done += part;
         }
-        return false;
     }
+
+    // `n` bytes of the base file at `at` -> d_base, staged (the CLI is bound by its one writer, so the base does without the
+    // mapped-window machinery)
+    void uploadBase(int fd, uint64_t at, size_t n) { stage(d_base, fd, at, n, "Read base file failed"); }
 
     // src[0..n) (device) -> the writer, piece by piece; `at`: file offset of the first byte (unordered writer).
     // `closes_chunk`: the last piece of these is the chunk's last (the ordered writer then moves on to chunk + 1).
@@ -600,13 +615,15 @@ struct GPUCompressor::DeviceBuffers {
     // `checksum`: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
     // `planes` > 1: what is coded is the chunk split into byte planes of elements that wide (d_planes); the CRCs stay the input's
     // `delta`: ... of the elements' differences (at a width of 1 too)
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta) {
+    // `based`: ... of the chunk XORed with d_base (at a width of 1 too)
+    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta, bool based = false) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
-        if (delta) gpuar_check(gpuar_hip_split_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_delta");
+        if (based) gpuar_check(gpuar_hip_split_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_xor");
+        else if (delta) gpuar_check(gpuar_hip_split_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_delta");
         else if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
-        gpuar_check(gpuar_hip_encode_mode(planes > 1 || delta ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
+        gpuar_check(gpuar_hip_encode_mode(planes > 1 || delta || based ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
         if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
@@ -624,8 +641,9 @@ struct GPUCompressor::DeviceBuffers {
     // GPUAR_STATUS_CHECKSUM in the flags then, and the chunk's lowest bad packet in `first_bad`
     // `planes` > 1: the n_plain decoded bytes are byte planes, merged into d_planes before they are verified; the result is there
     // `delta`: ... of differences, summed up by the merge (at a width of 1 too)
+    // `based`: ... XORed with d_base by the merge (at a width of 1 too)
     uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1,
-                         bool delta = false) {
+                         bool delta = false, bool based = false) {
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
         uint64_t *d_first_bad = crcs ? reinterpret_cast<uint64_t *>(d_crc + crcSlots()) : nullptr;
@@ -636,9 +654,10 @@ struct GPUCompressor::DeviceBuffers {
         }
         hip_check(hipEventRecord(t0, stream), "event");
         gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
-        if (delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_delta");
+        if (based) gpuar_check(gpuar_hip_merge_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_xor");
+        else if (delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_delta");
         else if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
-        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 || delta ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
+        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 || delta || based ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         if (crcs) hip_check(hipMemcpyAsync(h_crc + crcSlots(), d_first_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
@@ -776,6 +795,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
     const int out_fd = fileno(saveFile);
     try {
         info.uncompressedFileSize = getFileSize(openFile);
+        if (based()) openBase(info.uncompressedFileSize, "the input");
         const size_t total_packets = (info.uncompressedFileSize + kPacket - 1) / kPacket;
         ensureBuffers(total_packets, true);
         const size_t G = devices.size();
@@ -832,14 +852,16 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (c == 0) trace("compress: its buffers allocated");
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (writeChecksum) b.allocateCrc();
-                            if (planes > 1 || delta) b.allocatePlanes();
+                            if (planes > 1 || delta || based()) b.allocatePlanes();
+                            if (based()) b.allocateBase();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const uint64_t at = chunk_at[c];
                             const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
                             const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
+                            if (based()) b.uploadBase(baseFd, at, n_plain);      // the same byte range of the base
                             if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
                             uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta);     // (synchronises the lane's stream)
+                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta, based());     // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(at, n_plain);
                             // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
                             // (src/gpu_compressor.cpp:146-150)
@@ -1075,6 +1097,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         const std::vector<uint16_t> &index = trailer.clens;
         const std::vector<uint32_t> &crcs = trailer.crcs;
         const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging();
+        if (trailer.based()) openBase(info.uncompressedFileSize, "the file");
 
         ChunkMap map;
         std::thread scanner;
@@ -1179,6 +1202,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (verify) b.allocateCrc();
                             if (merging) b.allocatePlanes();
+                            if (trailer.based()) b.allocateBase();
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
                             const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
@@ -1220,9 +1244,11 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                     checkChecksumPacket(chunk.first_packet + p, crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
                                 if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
                             }
+                            // (every packet in front of this chunk holds 8192 bytes: checkPlanesPacket)
+                            if (trailer.based()) b.uploadBase(baseFd, static_cast<uint64_t>(chunk.first_packet) * kPacket, static_cast<size_t>(produced));
                             uint64_t first_bad = 0;
                             const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
-                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering());        // (synchronises the lane's stream)
+                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering(), trailer.based());        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307

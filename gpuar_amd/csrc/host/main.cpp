@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta] [--base=FILE] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -62,6 +62,11 @@ void usage() {
     std::cout << "--delta       (compress) replace the W-byte integers of the input (W from --planes; alone: bytes) by their differences first:" << std::endl;
     std::cout << "              ordered integers (offsets, sorted indices, timestamps, samples) compress several times smaller, other data grows;" << std::endl;
     std::cout << "              the file then carries a trailer that says so, which decompress needs" << std::endl;
+    std::cout << "--base        (compress) XOR the input with FILE, of exactly the input's length, first (at the width of --planes; alone: bytes):" << std::endl;
+    std::cout << "              a file that is close to its base (the next checkpoint of a model) compresses several times smaller, an unrelated" << std::endl;
+    std::cout << "              base makes it grow; implies --checksum; not together with --delta; the file then carries a trailer that says so;" << std::endl;
+    std::cout << "              (decompress) the same FILE: required for a file written with --base (a wrong one is a checksum mismatch)," << std::endl;
+    std::cout << "              refused for any other file" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
@@ -69,7 +74,7 @@ void usage() {
 
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
-    std::string in, out = "output.gip";
+    std::string in, out = "output.gip", base;
     bool has_in = false, planes_auto = false, delta = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
@@ -121,6 +126,12 @@ int main(int argc, char **argv) {
                 std::cerr << "--planes takes 1, 2, 4, 8 or auto: " << v << std::endl;
                 return 2;
             }
+        } else if (flag_name_is(argv[i], "base", &v)) {
+            if (!take(&v) || !*v) {
+                std::cerr << "--base takes a file name" << std::endl;
+                return 2;
+            }
+            base = v;
         } else if (flag_name_is(argv[i], "batch", &v)) {
             if (!take(&v)) break;
             batch = std::atol(v);
@@ -132,6 +143,10 @@ int main(int argc, char **argv) {
     if (help) {
         usage();
         return 0;
+    }
+    if (!base.empty() && delta) {
+        std::cerr << "--base and --delta cannot be combined" << std::endl;
+        return 2;
     }
     try {
         if (!has_in) throw std::runtime_error("Please specify the input file name by command: --in filename");
@@ -163,6 +178,7 @@ int main(int argc, char **argv) {
         compressor->setWriteChecksum(checksum);
         compressor->setPlanes(planes);
         compressor->setDelta(delta);
+        compressor->setBaseFileName(base);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);
         CompressionInfo info;

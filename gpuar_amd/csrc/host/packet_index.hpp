@@ -26,6 +26,12 @@
 //     "GIPX"  u32 version = 4  u64 n_packets  |  u32 elem_bytes (1, 2, 4 or 8)  |  u32 flags (bit 0: crc32[] present, bit 1: delta,
 //     others 0)  |  u16 clen[n_packets]  |  zero pad to 4  |  u32 crc32[n_packets] if flagged  |  zero pad to 8  |  u64 trailer_bytes  "XPIG"
 // It is written only when the filter is on, and one that cannot be used is an error too.
+// Version 5 (`--base=FILE`, alone or with `--planes=W`: the input was XORed with a base file of the same length before the split,
+// ../xorbase.h) has version 3's layout; W may be 1 in it, bit 2 of the flags (XOR base) must be set and so must bit 0: the CRCs
+// -- of the ORIGINAL bytes -- are what tells a reader that it was given the wrong base, so they are mandatory:
+//     "GIPX"  u32 version = 5  u64 n_packets  |  u32 elem_bytes (1, 2, 4 or 8)  |  u32 flags = 5 (bit 0: crc32[] present, bit 2: base,
+//     others 0)  |  u16 clen[n_packets]  |  zero pad to 4  |  u32 crc32[n_packets]  |  zero pad to 8  |  u64 trailer_bytes  "XPIG"
+// It is written only with a base, and one that cannot be used is an error too.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -41,12 +47,13 @@ struct Trailer {
     std::vector<uint16_t> clens;      // of every packet
     std::vector<uint32_t> crcs;       // of every packet's original bytes, when has_crcs
     bool has_crcs = false;
-    uint32_t elem_bytes = 1;          // 2, 4 or 8 in version 3, 1 too in version 4: the packets hold byte planes of elements this wide
+    uint32_t elem_bytes = 1;          // 2, 4 or 8 in version 3, 1 too in versions 4 and 5: the packets hold byte planes of elements this wide
 
     bool indexed() const { return version != 0; }        // the packet offsets are the prefix sums of `clens`
     bool verify() const { return has_crcs; }             // every decoded packet is checked against `crcs`
-    bool merging() const { return version == 3 || version == 4; }      // the decoded bytes are merged back from planes of `elem_bytes`
+    bool merging() const { return version == 3 || version == 4 || version == 5; }      // the decoded bytes are merged back from planes of `elem_bytes`
     bool filtering() const { return version == 4; }      // ... and are differences of elements that wide, summed up by the merge
+    bool based() const { return version == 5; }          // ... and are XORed with the base the reader must be given
 
     // offsets from "GIPX": the fixed fields end and the lengths begin at `fixed`, the CRCs (when there are any) begin at `crcs`,
     // and the trailer is `total` bytes long
@@ -55,25 +62,25 @@ struct Trailer {
     };
     static Layout layout(uint32_t version, uint64_t n, bool has_crcs) {
         Layout at;
-        at.fixed = version == 3 || version == 4 ? 24 : 16;
+        at.fixed = version == 3 || version == 4 || version == 5 ? 24 : 16;
         at.crcs = has_crcs ? (at.fixed + 2 * n + 3) / 4 * 4 : at.fixed + 2 * n;
         at.total = (at.crcs + (has_crcs ? 4 * n : 0) + 7) / 8 * 8 + 12;
         return at;
     }
 
-    // appends the trailer at the current position of `f`: version 4 when the packets went through the delta filter, else version 3
+    // appends the trailer at the current position of `f`: version 5 when the packets were XORed with a base (`crcs` is required), else version 4 when the packets went through the delta filter, else version 3
     // when they hold byte planes of elements `elem_bytes` > 1 wide, else version 2 when `crcs` (one per packet) is given, else version 1
     static void save(FILE *f, const std::vector<uint16_t> &clens, uint32_t elem_bytes = 1, const std::vector<uint32_t> *crcs = nullptr,
-                     bool delta = false) {
+                     bool delta = false, bool base = false) {
         const uint64_t n = clens.size();
-        if (crcs && crcs->size() != n) throw std::runtime_error("Write packet index failed");
-        const uint32_t version = delta ? 4 : elem_bytes > 1 ? 3 : crcs ? 2 : 1;
+        if ((crcs && crcs->size() != n) || (base && (!crcs || delta))) throw std::runtime_error("Write packet index failed");
+        const uint32_t version = base ? 5 : delta ? 4 : elem_bytes > 1 ? 3 : crcs ? 2 : 1;
         const Layout at = layout(version, n, crcs != nullptr);
         std::vector<uint8_t> t(at.total, 0);      // the zero pads included
         std::memcpy(t.data(), "GIPX", 4);
         put32(t.data() + 4, version);
         put64(t.data() + 8, n);
-        if (version >= 3) put32(t.data() + 16, elem_bytes), put32(t.data() + 20, (crcs ? 1u : 0u) | (delta ? 2u : 0u));
+        if (version >= 3) put32(t.data() + 16, elem_bytes), put32(t.data() + 20, (crcs ? 1u : 0u) | (delta ? 2u : 0u) | (base ? 4u : 0u));
         for (uint64_t i = 0; i < n; ++i) t[at.fixed + 2 * i] = static_cast<uint8_t>(clens[i]), t[at.fixed + 2 * i + 1] = static_cast<uint8_t>(clens[i] >> 8);
         if (crcs)
             for (uint64_t i = 0; i < n; ++i) put32(t.data() + at.crcs + 4 * i, (*crcs)[i]);
@@ -82,11 +89,12 @@ struct Trailer {
         if (std::fwrite(t.data(), t.size(), 1, f) != 1) throw std::runtime_error("Write packet index failed");
     }
 
-    enum class Status { none, ok, malformed, unusable, unusable_delta };
+    enum class Status { none, ok, malformed, unusable, unusable_delta, unusable_base };
     // Looks for a trailer in [stream_end, file_size) and restores the file position.  ok: `t` is filled.  Otherwise `t` is empty:
     //   unusable   what is there says "GIPX", 3 but its width is not 2, 4 or 8, it carries flags this reader does not know, or its
     //              lengths, its tail or the sum of its clens do not fit: the caller must refuse the file
     //   unusable_delta  the same for "GIPX", 4: a width that is not 1, 2, 4 or 8, the delta flag missing, a flag it does not know
+    //   unusable_base   the same for "GIPX", 5: a width that is not 1, 2, 4 or 8, flags other than base + CRCs
     //   malformed  it says "GIPX", 2 (in 16 bytes) and does not fit in the same way: ignored like any bad trailer, but the caller
     //              can tell the user that nothing was verified
     //   none       anything else, a version 1 that does not fit and versions this reader does not know included
@@ -104,15 +112,17 @@ struct Trailer {
             Status bad;                               // what a trailer of this version is when it does not fit
             if (version == 3) bad = Status::unusable;
             else if (version == 4) bad = Status::unusable_delta;
+            else if (version == 5) bad = Status::unusable_base;
             else if (version == 2 && have >= 16) bad = Status::malformed;
             else if (version == 1) bad = Status::none;
             else return Status::none;
             if (room < layout(version, 0, false).total) return bad;
             const uint64_t n = get64(head + 8);
-            const bool wide = version == 3 || version == 4;
+            const bool wide = version == 3 || version == 4 || version == 5;
             const uint32_t width = wide ? get32(head + 16) : 1u, flags = wide ? get32(head + 20) : version == 2 ? 1u : 0u;
             if (version == 4 && ((width != 1 && width != 2 && width != 4 && width != 8) || (flags & ~1u) != 2u)) return bad;
-            if ((version == 3 && width != 2 && width != 4 && width != 8) || (version != 4 && (flags & ~1u) != 0) || n > room / 2) return bad;
+            if (version == 5 && ((width != 1 && width != 2 && width != 4 && width != 8) || flags != 5u)) return bad;
+            if ((version == 3 && width != 2 && width != 4 && width != 8) || (version != 4 && version != 5 && (flags & ~1u) != 0) || n > room / 2) return bad;
             const Layout at = layout(version, n, flags & 1u);
             if (at.total != room || std::fseek(f, static_cast<long>(file_size - sizeof tail), SEEK_SET) != 0 || std::fread(tail, sizeof tail, 1, f) != 1 ||
                 std::memcmp(tail + 8, "XPIG", 4) != 0 || get64(tail) != room)

@@ -31,6 +31,8 @@ EXPORTS = [
     "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
     "gpuar_hip_split_delta", "gpuar_hip_merge_delta", "gpuar_hip_split_delta_batch", "gpuar_hip_merge_delta_batch",
     "gpuar_hip_split_delta_host", "gpuar_hip_merge_delta_host", "gpuar_hip_delta_block_host",
+    "gpuar_hip_split_xor", "gpuar_hip_merge_xor", "gpuar_hip_split_xor_batch", "gpuar_hip_merge_xor_batch",
+    "gpuar_hip_split_xor_host", "gpuar_hip_merge_xor_host",
     "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
     "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
 ]
@@ -131,6 +133,15 @@ def load() -> C.CDLL:
         getattr(lib, name).argtypes = [vp, sz, u32, vp]
     lib.gpuar_hip_delta_block_host.restype = C.c_int
     lib.gpuar_hip_delta_block_host.argtypes = [C.POINTER(C.c_uint32), u32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+    for name in ("gpuar_hip_split_xor", "gpuar_hip_merge_xor"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, sz, u32, vp, vp]
+    for name in ("gpuar_hip_split_xor_batch", "gpuar_hip_merge_xor_batch"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
+    for name in ("gpuar_hip_split_xor_host", "gpuar_hip_merge_xor_host"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, sz, u32, vp]
     lib.gpuar_hip_estimate.restype = C.c_int
     lib.gpuar_hip_estimate.argtypes = [vp, sz, vp, vp]
     lib.gpuar_hip_estimate_batch.restype = C.c_int
@@ -499,6 +510,80 @@ def delta_block_host(mixed, elem_bytes: int, undo: bool, carried: int):
     _check(load().gpuar_hip_delta_block_host(block, elem_bytes, 1 if undo else 0, carried & (2 ** 64 - 1), C.byref(total)),
            "gpuar_hip_delta_block_host")
     return list(block), total.value
+
+
+def _xor(name, d_in, d_base, elem_bytes, d_out, n_bytes, stream):
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    _require_cuda_u8(d_base, "d_base")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    if n > d_base.numel():
+        raise GpuarError("d_base too small")
+    if d_out is None:
+        d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=d_in.device)[:n]
+    _require_cuda_u8(d_out, "d_out")
+    if d_out.numel() < n:
+        raise GpuarError("d_out too small")
+    _check(getattr(load(), name)(d_in.data_ptr(), d_base.data_ptr(), n, elem_bytes, d_out.data_ptr(), _stream_handle(stream)), name)
+    return d_out
+
+
+def split_xor(d_in, d_base, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """split_planes of d_in ^ d_base (gpuar_hip_split_xor; include/gpuar_hip.h), in one pass: every byte of the first `n_bytes`
+    is XORed with the same byte of the base, then the bytes are regrouped as elements of `elem_bytes` bytes (1, 2, 4, 8);
+    elem_bytes = 1 is a plain XOR.  `d_out` may be `d_in`, never the base.  Returns d_out."""
+    return _xor("gpuar_hip_split_xor", d_in, d_base, elem_bytes, d_out, n_bytes, stream)
+
+
+def merge_xor(d_in, d_base, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
+    """The inverse of split_xor with the same base (gpuar_hip_merge_xor): merge_planes, then the XOR; `d_out` may be `d_in`."""
+    return _xor("gpuar_hip_merge_xor", d_in, d_base, elem_bytes, d_out, n_bytes, stream)
+
+
+def _xor_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, stream, d_status):
+    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
+                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_base_ptrs, "d_base_ptrs", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
+        _require_u64_desc(t, what, n)
+    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(),
+                                 d_base_ptrs.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status),
+                                 _stream_handle(stream)), name)
+
+
+def split_xor_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
+                    d_status=None):
+    """split_planes_batch with a base per buffer (gpuar_hip_split_xor_batch): d_base_ptrs[b] = 0 regroups buffer b as
+    split_planes_batch does, a 16-byte aligned pointer as split_xor against the d_bytes[b] bytes there; a misaligned one is
+    BAD_BATCH and the buffer is left alone."""
+    _xor_batch("gpuar_hip_split_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
+               stream, d_status)
+
+
+def merge_xor_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
+                    d_status=None):
+    """The inverse of split_xor_batch (gpuar_hip_merge_xor_batch)."""
+    _xor_batch("gpuar_hip_merge_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
+               stream, d_status)
+
+
+def _xor_host(name, data, base, elem_bytes):
+    data, base = bytes(data), bytes(base)
+    if len(base) != len(data):
+        raise GpuarError(f"{name}: a base of {len(base)} bytes for {len(data)} bytes")
+    out = C.create_string_buffer(len(data))
+    _check(getattr(load(), name)(data, base, len(data), elem_bytes, out), name)
+    return out.raw
+
+
+def split_xor_host(data, base, elem_bytes: int) -> bytes:
+    """split_xor of two bytes-like objects of one length on the CPU (gpuar_hip_split_xor_host: no device is touched)."""
+    return _xor_host("gpuar_hip_split_xor_host", data, base, elem_bytes)
+
+
+def merge_xor_host(data, base, elem_bytes: int) -> bytes:
+    """merge_xor of two bytes-like objects of one length on the CPU (gpuar_hip_merge_xor_host)."""
+    return _xor_host("gpuar_hip_merge_xor_host", data, base, elem_bytes)
 
 
 def estimate(d_in, n_bytes: int = None, d_est=None, stream=None):

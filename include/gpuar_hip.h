@@ -306,6 +306,38 @@ int gpuar_hip_merge_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_
 int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, uint64_t carried, uint64_t *total);
 
 /* ------------------------------------------------------------------------
+ * XOR against a base in front of the byte planes (gpuar_amd/csrc/xorbase.h).  For a buffer x and a base b of
+ * the same n_bytes, y[i] = x[i] ^ b[i] for every i < n_bytes; SPLIT_XOR is gpuar_hip_split_planes of y, MERGE_XOR is
+ * gpuar_hip_merge_planes followed by the XOR with b.  The XOR covers every byte, the tail's last r mod w included.  One fused
+ * pass: the same launches, access rules and overlap rule as the planes calls; the base is read by the same rules (never beyond
+ * the 16-byte piece that holds its last byte) and never written.  elem_bytes == 1 is a plain XOR and does work, in place too.
+ * A tensor that is close to its base (the next checkpoint of a model) compresses 0.06 - 0.72 of its size behind it; against
+ * an unrelated base it grows: the filter is for the caller to ask for.
+ * Left out: a base together with the delta filter, a base of another length, a base chosen per region of a buffer.
+ * ---------------------------------------------------------------------- */
+
+/* One buffer: arguments and error codes of gpuar_hip_split_planes, in the same order of checks (n_bytes == 0 is GPUAR_OK with
+ * no launch).  A null d_base is GPUAR_ERR_ARGUMENT, a d_base that is not 16-byte aligned GPUAR_ERR_ALIGNMENT, a d_base whose
+ * n_bytes overlap those of d_out (d_out == d_in included) GPUAR_ERR_ARGUMENT. */
+int gpuar_hip_split_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+int gpuar_hip_merge_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream);
+
+/* A batch: arguments of gpuar_hip_split_planes_batch plus d_base_ptrs (n_buffers device pointers, 8-byte aligned): 0 = byte
+ * planes alone (that buffer's output is gpuar_hip_split_planes_batch's), otherwise the buffer's base, d_in_bytes[b] bytes that
+ * overlap no output.  A base pointer that is not 16-byte aligned makes the buffer unusable (GPUAR_STATUS_BAD_BATCH) and it is
+ * left untouched, like the other unusable descriptors. */
+int gpuar_hip_split_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                              const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                              uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream);
+int gpuar_hip_merge_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                              const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                              uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream);
+
+/* Host only, from the same definition; rules of gpuar_hip_split_planes_host, and a null or overlapping base as above. */
+int gpuar_hip_split_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+int gpuar_hip_merge_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out);
+
+/* ------------------------------------------------------------------------
  * Packet size estimate and raw packets.  The codec's model starts every symbol at count 1, adds 1 per occurrence and never
  * rescales inside a packet, so a packet's ideal code length depends on its byte histogram h alone.  With
  *     lg16(k) = floor(2^16 log2 k),   LF[c] = sum of lg16(k) for k = 2 .. c   (LF[0] = LF[1] = 0)
