@@ -36,6 +36,11 @@ smaller, unordered data and floats grow.  The element width is t
 delta="auto" measures: it splits and estimates the batch both ways and filters the tensors for which that is predicted to pay.
 Compressed.gip(b) then carries width and filter in a version-4 trailer (`gpuar c --delta --planes=W`).
 
+delta="survey" makes the decision of delta="auto" without splitting anything: one hip.survey_delta_batch launch over the
+original bytes predicts what every tensor compresses to WITH the filter at the widths in use, survey's launch what it does
+without, and a tensor is filtered on the rule of "auto" (DESIGN.md 4.11).  Together with planes="survey" width and filter are
+chosen together (hip.choose_filter): on position ids held as bytes the plane survey alone picks width 8, the pair (4, filter).
+
 With base=[...] (one tensor of the same byte count, or None, per tensor) every tensor is XORed with its base before it is
 split (hip.split_xor_batch: the same single launch, into the same temporary buffer) and XORed back, in place, after it is
 decoded (hip.merge_xor_batch; decompress needs the same bases).  The next checkpoint of a model is almost the previous one:
@@ -239,12 +244,12 @@ def plane_widths(tensors, planes):
 
 def delta_flags(tensors, delta):
     """The filter per tensor that `delta` asks for: None -> None; a bool -> that for every tensor; a list -> as given, as bools.
-    ("auto" is resolved by compress and estimate, which launch; this function never does.)"""
+    ("auto" and "survey" are resolved by compress and estimate, which launch; this function never does.)"""
     tensors = list(tensors)
     if delta is None:
         return None
     if isinstance(delta, str):
-        raise GpuarError(f"delta={delta!r}: None, True, False, one bool per tensor or \"auto\"")
+        raise GpuarError(f"delta={delta!r}: None, True, False, one bool per tensor, \"auto\" or \"survey\"")
     flags = [bool(delta)] * len(tensors) if isinstance(delta, (bool, int)) else [bool(f) for f in delta]
     if len(flags) != len(tensors):
         raise GpuarError(f"delta: {len(flags)} flags for {len(tensors)} tensors")
@@ -432,14 +437,14 @@ def _base_arguments(tensors, widths, base):
 
 
 def _filter_arguments(tensors, planes, delta):
-    """(widths, flags or "auto" or None) for compress and estimate: a filter without `planes` works on bytes."""
+    """(widths, flags or "auto" or "survey" or None) for compress and estimate: a filter without `planes` works on bytes."""
     widths = plane_widths(tensors, planes)
     if delta is None:
         return widths, None
     if widths is None:
         widths = [1] * len(tensors)
-    if isinstance(delta, str) and delta == "auto":
-        return widths, "auto"
+    if isinstance(delta, str) and delta in ("auto", "survey"):
+        return widths, delta
     return widths, delta_flags(tensors, delta)
 
 
@@ -476,12 +481,88 @@ def survey_widths(tensors, stored=None) -> list:
             for b, totals in enumerate(survey(tensors, stored="auto" if isinstance(stored, str) and stored == "auto" else None))]
 
 
+def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, widths, d_status):
+    """Per buffer the four totals of the plane survey (if `plain`) and of the delta survey at `widths` (if not None; a width
+    that was not asked for: 0): one hip.survey_planes_batch launch, one hip.survey_delta_batch launch, one synchronisation, on the
+    current stream.  stored="auto" counts a packet that would be kept raw as its own bytes.  Raises on any status bit."""
+    import torch
+    n = len(sizes)
+    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
+    rows = []
+    if plain:
+        rows.append(H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device))
+    if widths is not None:
+        d_est = torch.zeros((len(H.SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device)
+        rows.append(H.survey_delta_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_est=d_est, d_status=d_status, device=device, widths=widths))
+    d_est = torch.cat(rows).to(torch.int64)
+    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
+    if stored == "auto":
+        d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
+    totals = torch.zeros((d_est.shape[0], n), dtype=torch.int64, device=device).index_add_(1, buf, d_est)
+    *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
+    if flags:
+        _raise_on_status(d_status, "survey_delta_batch")
+    per = len(flat) // n
+    both = [[flat[per * b + 4 * k:per * b + 4 * k + 4] for b in range(n)] for k in range(per // 4)]
+    return (both[0] if plain else None), (both[-1] if widths is not None else None)
+
+
+def survey_delta(tensors, stored=None, widths=None) -> list:
+    """What every tensor would compress to WITH the delta filter at each byte-plane width, without filtering, splitting or
+    encoding anything: per tensor [D1, D2, D4, D8], D_w = estimate([t], planes=w, delta=True, stored=stored)[0], with None where
+    `widths` (default: all four) does not ask for w.  One hip.survey_delta_batch launch over the original bytes and one
+    synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
+    import torch
+    if stored is not None and stored != "auto":
+        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    widths = tuple(H.SURVEY_WIDTHS if widths is None else widths)
+    H.widths_mask(widths)
+    tensors = list(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if n_packets == 0:
+        return [[0 if w in widths else None for w in H.SURVEY_WIDTHS] for _ in sizes]
+    d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    _plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, False, widths, d_status)
+    return [[t if w in widths else None for w, t in zip(H.SURVEY_WIDTHS, row)] for row in filtered]
+
+
+def _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status):
+    """delta="survey" with the widths fixed: per buffer, whether the filter is predicted to pay at the buffer's width -- the
+    decision of _auto_delta, est_delta + its packets <= est_plain, from the two surveys of the original bytes (the delta survey
+    masked to the widths in use): two launches and one synchronisation, no split and no temporary."""
+    n = len(sizes)
+    if n_packets == 0:
+        return [False] * n
+    if any(w not in H.SURVEY_WIDTHS for w in widths):
+        raise GpuarError(f"delta=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(widths) - set(H.SURVEY_WIDTHS))}")
+    used = sorted({w for w, size in zip(widths, sizes) if size})
+    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, None, True, used, d_status)
+    rows = [H.SURVEY_WIDTHS.index(w) for w in widths]
+    return [first_packet[b + 1] > first_packet[b] and filtered[b][j] + (first_packet[b + 1] - first_packet[b]) <= plain[b][j]
+            for b, j in enumerate(rows)]
+
+
+def survey_choice(tensors, stored=None):
+    """planes="survey" with delta="survey": per tensor the (width, filter) hip.choose_filter picks from both surveys of its bytes
+    (an empty tensor: (1, False)), as (widths, flags).  Two launches and one synchronisation."""
+    import torch
+    tensors = list(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if n_packets == 0:
+        return [1] * len(sizes), [False] * len(sizes)
+    d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, "auto" if isinstance(stored, str) and stored == "auto" else None,
+                                     True, H.SURVEY_WIDTHS, d_status)
+    choices = [H.choose_filter(plain[b], filtered[b], first_packet[b + 1] - first_packet[b]) for b in range(len(sizes))]
+    return [w for w, _f in choices], [f for _w, f in choices]
+
+
 def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
     asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
     split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front).  `delta`: as
-    compress -- the estimate is that of the filtered, split bytes (delta="auto": of each tensor's better half).  `base`,
+    compress -- the estimate is that of the filtered, split bytes (delta="auto", "survey": of each tensor's better half).  `base`,
     `base_auto`: as compress -- the estimate is that of the XORed, split bytes (base_auto: of each tensor's better half, from
     _auto_base's two split and two estimate launches alone)."""
     import torch
@@ -490,7 +571,10 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     tensors = list(tensors)
     _check_base(tensors, delta, base, base_auto)
     if isinstance(planes, str) and planes == "survey":
-        planes = survey_widths(tensors, stored)
+        if isinstance(delta, str) and delta == "survey":
+            planes, delta = survey_choice(tensors, stored)
+        else:
+            planes = survey_widths(tensors, stored)
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     widths, flags = _filter_arguments(tensors, planes, delta)
     widths, bases = _base_arguments(tensors, widths, base)
@@ -500,6 +584,8 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     d_status = torch.zeros(1, dtype=torch.int32, device=device)
     if flags == "auto":
         flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
+    elif flags == "survey":
+        flags = _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status)
     chosen = d_est = None
     if bases is not None and base_auto:
         _choice, chosen, d_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, None, d_status)
@@ -526,9 +612,11 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).  `stored`: None | "auto" | one bool per batch
     packet: keep packets raw instead of coding them -- "auto": those whose estimate (hip.estimate_batch, on the split bytes) is
     not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  `delta`: None | True |
-    False | one bool per tensor | "auto": replace the elements of the flagged tensors, at the width `planes` gives (planes=None:
+    False | one bool per tensor | "auto" | "survey": replace the elements of the flagged tensors, at the width `planes` gives (planes=None:
     1), by their differences inside every group, in the launch that splits (hip.split_delta_batch); "auto" flags the tensors
-    for which two more split and two more estimate launches predict a gain (_auto_delta).  None takes exactly the path taken
+    for which two more split and two more estimate launches predict a gain (_auto_delta); "survey" flags the same tensors from
+    two survey launches over the original bytes and one synchronisation, without a split or a temporary (_survey_delta_flags), and
+    with planes="survey" chooses width and filter together (survey_choice).  None takes exactly the path taken
     without the keyword.  The CRCs stay those of the original bytes; `stored` sees the filtered, split bytes.  `base`: None | a
     list with, per tensor, None or a contiguous CUDA tensor of exactly the tensor's byte count on its device, 16-byte aligned
     (base_pointers; anything else raises before any launch, and so does a base together with `delta`): XOR the tensor with it, at
@@ -544,7 +632,10 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     if isinstance(planes, str) and planes == "survey":
         stored = _stored_argument(stored, n_packets)
         with torch.cuda.stream(stream) if stream is not None else _nothing():
-            planes = survey_widths(tensors, stored)
+            if isinstance(delta, str) and delta == "survey":
+                planes, delta = survey_choice(tensors, stored)
+            else:
+                planes = survey_widths(tensors, stored)
     widths, flags = _filter_arguments(tensors, planes, delta)
     widths, bases = _base_arguments(tensors, widths, base)
     stored = _stored_argument(stored, n_packets)
@@ -556,6 +647,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if flags == "auto":
             flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
+        elif flags == "survey":
+            flags = _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status)
         chosen = d_chosen_est = None
         if bases is not None and base_auto:
             choice, chosen, d_chosen_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status)

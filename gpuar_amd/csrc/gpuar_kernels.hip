@@ -48,6 +48,7 @@
 #include "xorbase.h"
 #include "estimate.h"
 #include "survey.h"
+#include "delta_survey.h"
 
 namespace gpuar {
 
@@ -3133,6 +3134,266 @@ survey_planes_kernel(SurveyArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------
+// Delta survey (delta_survey.h): est[j][p] = estimate(split_delta(buffer, 1 << j))[p] for the widths asked for
+// (widths_mask, uniform over the launch), from one read of the original bytes and without filtering or splitting anything into
+// memory, for one buffer or a batch.  Supergroups, windows, descriptors and BAD_BATCH are survey_planes_kernel's (survey_walk),
+// and so is the workgroup: wavefront e loads eighth e once, lane l bytes [128 l, 128 l + 128) as eight 16-byte loads, and keeps
+// those 32 dwords in registers for all widths.
+// The filtered byte at a position differs per width, so the widths take turns with the one set of counters.  For a width the lane
+// filters its 128 bytes in registers (delta.h's delta_block over 16 elements at a time, with the element in front: the last
+// one of the block before, of the lane before -- two lane shuffles --, for lane 0 the 8 bytes in front of the eighth, loaded
+// once, and 0 where a group starts, e mod w = 0) and counts them into its wavefront's eight residue histograms exactly as the
+// plane survey counts unfiltered bytes: the filter is for data whose differences are constant, so all lanes on one counter is
+// this kernel's typical input and the rotation by (lane & 7) (survey_count8) what keeps it off one bank.  Behind a barrier
+// thread (half, s) sums bin s of this width's packets 4 half .. + 3 (the sums survey.h lists), looks the four counts up in LF;
+// four wave sums in 7 u64 exchanges, a 256-byte exchange and 8 threads give the width's 8 estimates: one writer each.  The counters
+// are cleared behind a second barrier and a third one lets the next width count: three barriers a width.
+// A buffer's last, short supergroup (1 .. 65535 bytes) takes the general path, width by width: a thread takes 8-byte pieces
+// (whole elements at every width, since groups and tails start on multiples of 8192) with the 8 bytes in front, forms the
+// differences (delta_sub; the tail's whole elements only, the predecessor reset where a group or the tail starts) and adds
+// every byte to the packet histogram survey_packet names: 8 histograms of 256 u32 in the same LDS.  It reads nothing in front of
+// the supergroup and nothing beyond the 16-byte piece that holds its last byte, and is bounded by one supergroup per buffer.
+// ---------------------------------------------------------------------------
+struct DeltaSurveyArgs {
+    SurveyArgs s;
+    uint32_t widths_mask;                   // bit j: row j (width 1 << j) is wanted
+};
+
+// survey_planes_kernel's walk over windows and descriptors with the supergroup's work as a parameter: every supergroup that
+// starts in one of this workgroup's windows goes to body(sg, len, first) -- `len` bytes (1 .. 65536) at `sg`, whose first packet
+// is batch packet `first` -- and every unusable descriptor to BAD_BATCH.  (A copy: survey_planes_kernel written over this
+// function compiles to another instruction stream and four registers fewer, and that kernel's code object stays as it is.)
+template <typename Body>
+__device__ __forceinline__ void survey_walk(const SurveyArgs &a, Body body) {
+    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
+    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
+        uint64_t p = 8ull * u;
+        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
+        while (p < end) {                   // (every value here is the same in all threads)
+            const uint8_t *sg = nullptr;
+            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
+            if (!a.ptrs) {                  // one buffer: the window is the supergroup
+                sg = a.in + p * kPacket;
+                left = a.n_bytes - p * kPacket;
+            } else {
+                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
+                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
+                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    next = p + 1u;
+                } else {
+                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
+                    const uint64_t j = p - lead;
+                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
+                    if (!bl.owned || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
+                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
+                        sg = bl.ptr;
+                        left = n_bytes - j * kPacket;
+                    }
+                }
+            }
+            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
+            if (len != 0u) body(sg, len, p);
+            p = next;
+        }
+    }
+}
+
+// the last W-byte element of the 8 bytes {lo, hi}
+template <int W>
+__device__ __forceinline__ uint64_t dsurvey_last(uint32_t lo, uint32_t hi) {
+    if constexpr (W == 8) return static_cast<uint64_t>(hi) << 32 | lo;
+    else if constexpr (W == 4) return hi;
+    else return hi >> (32 - 8 * W);
+}
+
+// the lane's 128 bytes `d` filtered at width W and counted; {front_lo, front_hi}: the 8 bytes in front of them
+template <int W>
+__device__ __forceinline__ void dsurvey_count(uint32_t *hist, const uint32_t (&d)[32], uint32_t front_lo, uint32_t front_hi, bool group_start,
+                                              uint32_t c, const uint32_t (&slot)[8]) {
+    constexpr int D = 4 * W;                // dwords of a block of 16 elements
+    uint64_t pred = group_start ? 0ull : dsurvey_last<W>(front_lo, front_hi);
+#pragma unroll
+    for (int b = 0; b < 32 / D; ++b) {
+        uint32_t m[D];
+#pragma unroll
+        for (int i = 0; i < D; ++i) m[i] = d[D * b + i];
+        delta_block<W>(m, pred);
+        pred = dsurvey_last<W>(d[D * b + D - 2], d[D * b + D - 1]);
+#pragma unroll
+        for (int i = 0; i < D; i += 2) survey_count8(hist, m[i], m[i + 1], c, slot);
+    }
+}
+
+// the general path at width W: the short supergroup's filtered bytes into packet histogram p at dword 256 p
+template <int W, int J>
+__device__ __forceinline__ void dsurvey_short(uint32_t *hist, const uint8_t *sg, uint32_t len) {
+    using GlobalWord = const __attribute__((address_space(1))) uint32_t;
+    GlobalWord *src = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(sg));
+    constexpr uint32_t G = W * kPacket;
+    for (uint32_t i = threadIdx.x; i * 8u < len; i += kSurveyThreads) {
+        const uint32_t o = 8u * i, B = o & ~(G - 1u);
+        const uint32_t whole = (len - B < G ? len - B : G) & ~static_cast<uint32_t>(W - 1);      // the group's or the tail's whole elements
+        const uint32_t lo = src[2u * i], hi = src[2u * i + 1u];
+        uint32_t before = 0, front = 0;      // the dword in front of the piece, and the one in front of that (W = 8): 0 at a reset
+        if (o != B) front = src[2u * i - 1u];
+        if (W == 8 && o != B) before = src[2u * i - 2u];
+        uint32_t f_lo, f_hi;
+        if constexpr (W == 8) {
+            const uint64_t dif = (static_cast<uint64_t>(hi) << 32 | lo) - (static_cast<uint64_t>(front) << 32 | before);
+            f_lo = static_cast<uint32_t>(dif), f_hi = static_cast<uint32_t>(dif >> 32);
+        } else if constexpr (W == 4) {
+            f_lo = delta_sub<W>(lo, front), f_hi = delta_sub<W>(hi, lo);
+        } else {
+            f_lo = delta_sub<W>(lo, lo << (8 * W) | front >> (32 - 8 * W)), f_hi = delta_sub<W>(hi, hi << (8 * W) | lo >> (32 - 8 * W));
+        }
+#pragma unroll 1
+        for (uint32_t b = 0; b < 8u; ++b) {
+            const uint32_t at = o + b;
+            if (at >= len) break;
+            const bool filtered = at - B < whole;      // (else: the tail's last bytes, as they are)
+            const uint32_t word = b < 4u ? (filtered ? f_lo : lo) : (filtered ? f_hi : hi);
+            const uint32_t byte = (word >> (8u * (b & 3u))) & 255u;
+            __hip_atomic_fetch_add(hist + (survey_packet(at, len, J) * 256u + byte), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+}
+
+// bin s of the packets 4 half .. + 3 of a full supergroup at width 1 << J, from the residue histograms
+template <int J>
+__device__ __forceinline__ void dsurvey_bins(const CrcQuad *lds, uint32_t half, uint32_t s, uint32_t (&cnt)[4]) {
+    if constexpr (J == 3) {                 // packet k: residue k of all eighths
+        CrcQuad t = CrcQuad(0u);
+#pragma unroll
+        for (uint32_t e = 0; e < 8; ++e) t += lds[(e * kSurveyEighthDwords + 8u * s) / 4u + half];
+        cnt[0] = t.x, cnt[1] = t.y, cnt[2] = t.z, cnt[3] = t.w;
+    } else {
+        CrcQuad t[4];                       // residues r and r + 4 of the half's own eighths
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e)
+            t[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] + lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u];
+        if constexpr (J == 0) {
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e) cnt[e] = t[e].x + t[e].y + t[e].z + t[e].w;
+        } else if constexpr (J == 1) {
+#pragma unroll
+            for (uint32_t g = 0; g < 2; ++g) {
+                const CrcQuad u = t[2 * g] + t[2 * g + 1];
+                cnt[2 * g] = u.x + u.z;
+                cnt[2 * g + 1] = u.y + u.w;
+            }
+        } else {
+            const CrcQuad u = t[0] + t[1] + t[2] + t[3];
+            cnt[0] = u.x, cnt[1] = u.y, cnt[2] = u.z, cnt[3] = u.w;
+        }
+    }
+}
+
+// one width of one supergroup; the whole workgroup, with the counters clear on entry and on return
+template <int J>
+__device__ __forceinline__ void dsurvey_width(const DeltaSurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, const uint32_t (&d)[32],
+                                              uint32_t front_lo, uint32_t front_hi, CrcQuad *lds, uint64_t (*sums)[4]) {
+    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    constexpr int W = 1 << J;
+    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, packets 4 half .. + 3
+    const bool full = len == kSurveyBytes;                                   // workgroup-uniform
+    if (full) {
+        const uint32_t c = lane & 7u;
+        uint32_t slot[8];
+#pragma unroll
+        for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
+        dsurvey_count<W>(hist, d, front_lo, front_hi, lane == 0u && (wave & (W - 1u)) == 0u, c, slot);
+    } else {
+        dsurvey_short<W, J>(hist, sg, len);
+    }
+    __syncthreads();
+    uint32_t cnt[4];
+    if (full) {
+        dsurvey_bins<J>(lds, half, s, cnt);
+    } else {
+#pragma unroll
+        for (uint32_t m = 0; m < 4; ++m) cnt[m] = hist[(4u * half + m) * 256u + s];
+    }
+    // four wave sums: two steps halve the values a lane carries (as survey_supergroup's), four more sum value lane >> 4 up
+    uint64_t sum[4];
+#pragma unroll
+    for (uint32_t m = 0; m < 4; ++m) sum[m] = lf[cnt[m]];
+#pragma unroll
+    for (uint32_t n = 2, off = 32; n >= 1; n >>= 1, off >>= 1) {
+        const bool upper = (lane & off) != 0u;
+#pragma unroll
+        for (uint32_t m = 0; m < n; ++m) {
+            const uint64_t keep = upper ? sum[m + n] : sum[m], give = upper ? sum[m] : sum[m + n];
+            const uint32_t lo = __shfl_xor(static_cast<uint32_t>(give), off), hi = __shfl_xor(static_cast<uint32_t>(give >> 32), off);
+            sum[m] = keep + (static_cast<uint64_t>(hi) << 32 | lo);
+        }
+    }
+#pragma unroll
+    for (uint32_t off = 8; off >= 1; off >>= 1) {
+        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(sum[0]), off), hi = __shfl_xor(static_cast<uint32_t>(sum[0] >> 32), off);
+        sum[0] += static_cast<uint64_t>(hi) << 32 | lo;
+    }
+    if ((lane & 15u) == 0u) sums[wave][lane >> 4] = sum[0];
+    __syncthreads();
+    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
+    }
+    if (threadIdx.x < 8u) {
+        const uint32_t m = threadIdx.x & 3u, hh = threadIdx.x >> 2, p = 4u * hh + m;
+        if (p * kPacket < len) {
+            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
+            const uint64_t total = sums[4u * hh][m] + sums[4u * hh + 1u][m] + sums[4u * hh + 2u][m] + sums[4u * hh + 3u][m];
+            GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(a.s.est));
+            est[J * a.s.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
+        }
+    }
+    __syncthreads();      // the clears and the reads of `sums` in front of the next width
+}
+
+// one supergroup: `len` bytes (1 .. 65536) at `sg` (16-byte aligned), whose first packet is entry `first` of every row
+__device__ __forceinline__ void dsurvey_supergroup(const DeltaSurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, CrcQuad *lds,
+                                                   uint64_t (*sums)[4]) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    using GlobalWord = const __attribute__((address_space(1))) uint32_t;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint32_t d[32] = {}, front_lo = 0, front_hi = 0;
+    if (len == kSurveyBytes) {                                               // workgroup-uniform
+        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + wave * kPacket + kCrcChunk * lane));
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            const CrcQuad q = src[k];
+            d[4 * k] = q.x, d[4 * k + 1] = q.y, d[4 * k + 2] = q.z, d[4 * k + 3] = q.w;
+        }
+        if (wave != 0u) {                                                    // (nothing is read in front of the supergroup)
+            GlobalWord *front = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(sg + wave * kPacket - 8u));
+            front_lo = front[0], front_hi = front[1];
+        }
+        const uint32_t up_lo = __shfl_up(d[30], 1), up_hi = __shfl_up(d[31], 1);
+        if (lane != 0u) front_lo = up_lo, front_hi = up_hi;
+    }
+    if (a.widths_mask & 1u) dsurvey_width<0>(a, sg, len, first, d, front_lo, front_hi, lds, sums);
+    if (a.widths_mask & 2u) dsurvey_width<1>(a, sg, len, first, d, front_lo, front_hi, lds, sums);
+    if (a.widths_mask & 4u) dsurvey_width<2>(a, sg, len, first, d, front_lo, front_hi, lds, sums);
+    if (a.widths_mask & 8u) dsurvey_width<3>(a, sg, len, first, d, front_lo, front_hi, lds, sums);
+}
+
+__global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_per_eu(4)))      // two workgroups per CU: 128 VGPRs
+survey_delta_kernel(DeltaSurveyArgs a) {
+    __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
+    __shared__ uint64_t sums[kSurveyWaves][4];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
+    __syncthreads();
+    survey_walk(a.s, [&](const uint8_t *sg, uint32_t len, uint64_t first) { dsurvey_supergroup(a, sg, len, first, lds, sums); });
+}
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -3822,6 +4083,66 @@ int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *es
     if (!in || !est || est_stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
     gpuar::survey_host(in, n_bytes, est, est_stride);
     return GPUAR_OK;
+}
+
+static int launch_delta_survey(const gpuar::SurveyArgs &s, uint32_t widths_mask, void *stream) {
+    gpuar::DeltaSurveyArgs a = {s, widths_mask};
+    const uint32_t windows = (s.n_packets >> 3) + ((s.n_packets & 7u) ? 1u : 0u);
+    const uint32_t blocks = windows < gpuar::kSurveyGroups ? windows : gpuar::kSurveyGroups;
+    gpuar::survey_delta_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+static bool delta_survey_mask_ok(uint32_t widths_mask) { return widths_mask != 0u && (widths_mask & ~gpuar::kSurveyAllWidths) == 0u; }
+
+int gpuar_hip_survey_delta(const uint8_t *d_in, size_t n_bytes, uint32_t widths_mask, uint32_t *d_est, size_t est_stride, void *stream) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (est_stride < gpuar_hip_packet_count(n_bytes) || !delta_survey_mask_ok(widths_mask)) return GPUAR_ERR_ARGUMENT;
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the estimate call's checks
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::SurveyArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.est = d_est;
+    a.stride = est_stride;
+    a.status = status;
+    return launch_delta_survey(a, widths_mask, stream);
+}
+
+int gpuar_hip_survey_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet, size_t n_buffers,
+                                 size_t n_packets, uint32_t widths_mask, uint32_t *d_est, size_t est_stride, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (est_stride < n_packets || !delta_survey_mask_ok(widths_mask)) return GPUAR_ERR_ARGUMENT;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::SurveyArgs a = {};
+    a.ptrs = d_in_ptrs;
+    a.bytes = d_in_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.est = d_est;
+    a.stride = est_stride;
+    a.status = status;
+    return launch_delta_survey(a, widths_mask, stream);
+}
+
+int gpuar_hip_survey_delta_host(const uint8_t *in, size_t n_bytes, uint32_t widths_mask, uint32_t *est, size_t est_stride) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !est || est_stride < gpuar_hip_packet_count(n_bytes) || !delta_survey_mask_ok(widths_mask)) return GPUAR_ERR_ARGUMENT;
+    gpuar::delta_survey_host(in, n_bytes, widths_mask, est, est_stride);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_choose_filter(const uint64_t plain[4], const uint64_t filtered[4], uint64_t n_packets, uint32_t *width) {
+    gpuar::FilterChoice c = {1u, false};
+    if (plain && filtered) c = gpuar::choose_filter(plain, filtered, n_packets);
+    if (width) *width = c.width;
+    return c.filter ? 1 : 0;
 }
 
 uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets) { return total ? gpuar::choose_width(total, n_packets) : 1u; }

@@ -7,7 +7,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../survey.h"
+#include "../delta_survey.h"
 #include "gpuar_hip.h"
 
 namespace gip {
@@ -45,7 +45,7 @@ size_t Compressor::getFileSize(FILE *stream) {
     return end < 0 ? 0 : static_cast<size_t>(end);
 }
 
-int Compressor::choosePlanes(unsigned long long total[4]) {
+std::vector<uint8_t> Compressor::readSurveyPrefix() const {
     const int fd = ::open(openFileName.c_str(), O_RDONLY);
     if (fd < 0) throw std::runtime_error("Can not open input file: " + openFileName);
     std::vector<uint8_t> head(kSurveyPrefix);
@@ -60,16 +60,49 @@ int Compressor::choosePlanes(unsigned long long total[4]) {
         n += static_cast<size_t>(got);
     }
     ::close(fd);
-    const size_t n_packets = (n + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES;
-    std::vector<uint32_t> est(gpuar::kSurveyWidths * n_packets);
-    gpuar::survey_host(head.data(), n, est.data(), n_packets);
-    uint64_t sums[gpuar::kSurveyWidths] = {};
+    head.resize(n);
+    return head;
+}
+
+// the four totals of a survey's rows
+static void survey_totals(const std::vector<uint32_t> &est, size_t n_packets, uint64_t sums[4], unsigned long long total[4]) {
     for (uint32_t j = 0; j < gpuar::kSurveyWidths; ++j) {
+        sums[j] = 0;
         for (size_t p = 0; p < n_packets; ++p) sums[j] += est[j * n_packets + p];
         total[j] = sums[j];
     }
+}
+
+int Compressor::choosePlanes(unsigned long long total[4]) {
+    const std::vector<uint8_t> head = readSurveyPrefix();
+    const size_t n_packets = (head.size() + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES;
+    std::vector<uint32_t> est(gpuar::kSurveyWidths * n_packets);
+    gpuar::survey_host(head.data(), head.size(), est.data(), n_packets);
+    uint64_t sums[gpuar::kSurveyWidths];
+    survey_totals(est, n_packets, sums, total);
     planes = static_cast<int>(gpuar::choose_width(sums, n_packets));
     return planes;
+}
+
+bool Compressor::chooseFilter(bool choose_width_too, unsigned long long plain[4], unsigned long long filtered[4]) {
+    if (based()) throw std::runtime_error("--base together with --delta is not supported");
+    const std::vector<uint8_t> head = readSurveyPrefix();
+    const size_t n_packets = (head.size() + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES;
+    std::vector<uint32_t> est(gpuar::kSurveyWidths * n_packets);
+    uint64_t sums_plain[gpuar::kSurveyWidths], sums_filtered[gpuar::kSurveyWidths];
+    gpuar::survey_host(head.data(), head.size(), est.data(), n_packets);
+    survey_totals(est, n_packets, sums_plain, plain);
+    gpuar::delta_survey_host(head.data(), head.size(), gpuar::kSurveyAllWidths, est.data(), n_packets);
+    survey_totals(est, n_packets, sums_filtered, filtered);
+    if (choose_width_too) {
+        const gpuar::FilterChoice c = gpuar::choose_filter(sums_plain, sums_filtered, n_packets);
+        planes = static_cast<int>(c.width);
+        delta = c.filter;
+    } else {
+        const uint32_t j = gpuar::survey_row(static_cast<uint32_t>(planes));
+        delta = n_packets != 0 && sums_filtered[j] + n_packets <= sums_plain[j];
+    }
+    return delta;
 }
 
 void Compressor::openBase(uint64_t expect, const char *what) {

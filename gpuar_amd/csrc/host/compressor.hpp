@@ -51,6 +51,9 @@ class Compressor {
     int baseFd = -1;                  // ... open while a job runs (openBase)
     bool checksumAsked = false;       // what setWriteChecksum was given: a base turns writeChecksum on by itself
 
+    // the first min(file size, kSurveyPrefix) bytes of the input, from one pread: what choosePlanes and chooseFilter survey
+    std::vector<uint8_t> readSurveyPrefix() const;
+
     // the error a decompress raises for a packet whose decoded bytes do not match the CRC-32 of its trailer
     static std::runtime_error checksumError(size_t packet, uint64_t begin, uint64_t end) {
         return std::runtime_error("Checksum mismatch: packet " + std::to_string(packet) + " (uncompressed bytes " + std::to_string(begin) +
@@ -147,6 +150,7 @@ class Compressor {
         planes = elem_bytes;
     }
     void setDelta(bool on) { delta = on; }
+    int getPlanes() const { return planes; }
     // compress: XOR against this file (implies the checksums); decompress: the base of a version-5 file.  Empty: none.
     void setBaseFileName(const std::string &fileName) {
         baseFileName = fileName;
@@ -158,6 +162,12 @@ class Compressor {
     // constant, so the file written does not depend on --batch, --gpus, --threads or --host.
     static constexpr size_t kSurveyPrefix = size_t(16) << 20;
     int choosePlanes(unsigned long long total[4]);
+    // `--delta=auto`: sets the filter -- and with choose_width_too (`--planes=auto` as well) the width -- from the same prefix, and
+    // returns the filter.  plain[4] are the totals of gpuar::survey_host, filtered[4] those of gpuar::delta_survey_host
+    // (../delta_survey.h: the prefix filtered and split at widths 1, 2, 4, 8).  With the width fixed the filter is on iff
+    // filtered[W] + packets <= plain[W], the rule of batch.compress(delta="auto"); with both open it is gpuar::choose_filter.
+    // On the host, before either pipeline starts, as choosePlanes.
+    bool chooseFilter(bool choose_width_too, unsigned long long plain[4], unsigned long long filtered[4]);
     virtual CompressionInfo compress(ProgressMonitor *monitor) = 0;
     virtual CompressionInfo decompress(ProgressMonitor *monitor) = 0;
     void closeFiles();

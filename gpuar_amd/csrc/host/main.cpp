@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta] [--base=FILE] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta[=on|off|auto]] [--base=FILE] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -61,7 +61,9 @@ void usage() {
     std::cout << "              auto: W is chosen from the first 16 MiB of the input (a histogram pass on the host predicts its size at every W)" << std::endl;
     std::cout << "--delta       (compress) replace the W-byte integers of the input (W from --planes; alone: bytes) by their differences first:" << std::endl;
     std::cout << "              ordered integers (offsets, sorted indices, timestamps, samples) compress several times smaller, other data grows;" << std::endl;
-    std::cout << "              the file then carries a trailer that says so, which decompress needs" << std::endl;
+    std::cout << "              the file then carries a trailer that says so, which decompress needs; --delta=on: the same; --delta=off: no filter" << std::endl;
+    std::cout << "              (default); --delta=auto: the filter is chosen from the first 16 MiB of the input (a histogram pass on the host predicts" << std::endl;
+    std::cout << "              the size with and without it) -- at the W of --planes, or together with W where --planes=auto" << std::endl;
     std::cout << "--base        (compress) XOR the input with FILE, of exactly the input's length, first (at the width of --planes; alone: bytes):" << std::endl;
     std::cout << "              a file that is close to its base (the next checkpoint of a model) compresses several times smaller, an unrelated" << std::endl;
     std::cout << "              base makes it grow; implies --checksum; not together with --delta; the file then carries a trailer that says so;" << std::endl;
@@ -75,7 +77,7 @@ void usage() {
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip", base;
-    bool has_in = false, planes_auto = false, delta = false;
+    bool has_in = false, planes_auto = false, delta = false, delta_auto = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
@@ -100,7 +102,12 @@ int main(int argc, char **argv) {
         } else if (flag_name_is(argv[i], "checksum", &v)) {
             checksum = true;
         } else if (flag_name_is(argv[i], "delta", &v)) {
-            delta = true;
+            delta_auto = v && !std::strcmp(v, "auto");
+            delta = !v || !std::strcmp(v, "on") || delta_auto;
+            if (!delta && std::strcmp(v, "off")) {
+                std::cerr << "--delta takes on, off or auto: " << v << std::endl;
+                return 2;
+            }
         } else if (flag_name_is(argv[i], "nointeractive", &v)) {
         } else if (flag_name_is(argv[i], "in", &v)) {
             if (!take(&v)) break;
@@ -177,13 +184,20 @@ int main(int argc, char **argv) {
         compressor->setWriteIndex(index);
         compressor->setWriteChecksum(checksum);
         compressor->setPlanes(planes);
-        compressor->setDelta(delta);
+        compressor->setDelta(delta && !delta_auto);
         compressor->setBaseFileName(base);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);
         CompressionInfo info;
         if (!decompress) {
-            if (planes_auto) {
+            if (delta_auto) {
+                unsigned long long plain[4], filtered[4];
+                const bool on = compressor->chooseFilter(planes_auto, plain, filtered);
+                std::cout << "delta=auto: filter " << (on ? "on" : "off") << ", width " << compressor->getPlanes()
+                          << " (predicted bytes at widths 1, 2, 4, 8 without the filter: " << plain[0] << ", " << plain[1] << ", " << plain[2] << ", "
+                          << plain[3] << "; with it: " << filtered[0] << ", " << filtered[1] << ", " << filtered[2] << ", " << filtered[3] << ")"
+                          << std::endl;
+            } else if (planes_auto) {
                 unsigned long long total[4];
                 const int w = compressor->choosePlanes(total);
                 std::cout << "planes=auto: width " << w << " (predicted bytes at widths 1, 2, 4, 8: " << total[0] << ", " << total[1] << ", "

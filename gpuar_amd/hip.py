@@ -35,6 +35,7 @@ EXPORTS = [
     "gpuar_hip_split_xor_host", "gpuar_hip_merge_xor_host",
     "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
     "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
+    "gpuar_hip_survey_delta", "gpuar_hip_survey_delta_batch", "gpuar_hip_survey_delta_host", "gpuar_hip_choose_filter",
 ]
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
@@ -158,6 +159,14 @@ def load() -> C.CDLL:
     lib.gpuar_hip_survey_planes_host.argtypes = [vp, sz, vp, sz]
     lib.gpuar_hip_choose_planes.restype = u32
     lib.gpuar_hip_choose_planes.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]
+    lib.gpuar_hip_survey_delta.restype = C.c_int
+    lib.gpuar_hip_survey_delta.argtypes = [vp, sz, u32, vp, sz, vp]
+    lib.gpuar_hip_survey_delta_batch.restype = C.c_int
+    lib.gpuar_hip_survey_delta_batch.argtypes = [vp, vp, vp, sz, sz, u32, vp, sz, vp, vp]
+    lib.gpuar_hip_survey_delta_host.restype = C.c_int
+    lib.gpuar_hip_survey_delta_host.argtypes = [vp, sz, u32, vp, sz]
+    lib.gpuar_hip_choose_filter.restype = C.c_int
+    lib.gpuar_hip_choose_filter.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(u32)]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -683,6 +692,77 @@ def choose_planes(totals, n_packets: int) -> int:
     if len(totals) != len(SURVEY_WIDTHS) or min(totals) < 0:
         raise GpuarError(f"choose_planes: four non-negative totals, not {totals}")
     return int(load().gpuar_hip_choose_planes((C.c_uint64 * 4)(*totals), n_packets))
+
+
+def widths_mask(widths) -> int:
+    """The widths_mask of the delta survey: bit j for width SURVEY_WIDTHS[j]; anything but a non-empty set of 1, 2, 4, 8 raises."""
+    widths = list(widths)
+    if not widths or any(w not in SURVEY_WIDTHS for w in widths):
+        raise GpuarError(f"widths={widths}: a non-empty selection of {SURVEY_WIDTHS}")
+    mask = 0
+    for w in widths:
+        mask |= 1 << SURVEY_WIDTHS.index(w)
+    return mask
+
+
+def survey_delta(d_in, d_est=None, n_bytes: int = None, stream=None, widths=SURVEY_WIDTHS):
+    """The estimate of every packet of the first `n_bytes` (default: all) bytes of `d_in` filtered (delta) and split into byte
+    planes of each width of `widths`, from one read of the bytes and without filtering or splitting anything into memory
+    (gpuar_hip_survey_delta): row j of the result is what estimate(split_delta(d_in, SURVEY_WIDTHS[j])) gives.  Returns d_est:
+    int32 CUDA tensor of shape (4, packet_count(n_bytes)) (the caller's may be wider: its second dimension is the row stride);
+    the rows of widths that were not asked for are left as they were."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    mask = widths_mask(widths)
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    npk = packet_count(n)
+    if d_est is None:
+        d_est = torch.empty((len(SURVEY_WIDTHS), npk), dtype=torch.int32, device=d_in.device)
+    _require_survey(d_est, npk)
+    _check(load().gpuar_hip_survey_delta(d_in.data_ptr(), n, mask, d_est.data_ptr(), d_est.shape[1], _stream_handle(stream)), "gpuar_hip_survey_delta")
+    return d_est
+
+
+def survey_delta_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None,
+                       widths=SURVEY_WIDTHS):
+    """The delta survey of every buffer of a batch in one launch (gpuar_hip_survey_delta_batch; descriptors as for encode_batch):
+    d_est[j, p] for every width SURVEY_WIDTHS[j] of `widths` and batch packet p; the other rows are left as they were."""
+    import torch
+    mask = widths_mask(widths)
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_est is None:
+        d_est = torch.empty((len(SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device or d_ptrs.device)
+    _require_survey(d_est, n_packets)
+    _check(load().gpuar_hip_survey_delta_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, mask,
+                                               d_est.data_ptr(), d_est.shape[1], _status_ptr(d_status), _stream_handle(stream)),
+           "gpuar_hip_survey_delta_batch")
+    return d_est
+
+
+def survey_delta_host(data, widths=SURVEY_WIDTHS) -> list:
+    """survey_delta of a bytes-like object on the CPU (gpuar_hip_survey_delta_host: no device is touched): four entries, one per
+    width of SURVEY_WIDTHS -- a list of one int per packet, or None for a width that was not asked for."""
+    data = bytes(data)
+    mask = widths_mask(widths)
+    npk = packet_count(len(data))
+    est = (C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))()
+    _check(load().gpuar_hip_survey_delta_host(data, len(data), mask, est, npk), "gpuar_hip_survey_delta_host")
+    return [list(est[j * npk:(j + 1) * npk]) if mask >> j & 1 else None for j in range(len(SURVEY_WIDTHS))]
+
+
+def choose_filter(plain, filtered, n_packets: int) -> tuple:
+    """(width, filter) from the four totals of the plane survey and the four of the delta survey (gpuar_hip_choose_filter): the
+    filter at the width choose_planes picks from `filtered` iff that total + n_packets is at most the total of the width
+    choose_planes picks from `plain`; else that width and no filter."""
+    plain, filtered = [int(t) for t in plain], [int(t) for t in filtered]
+    if len(plain) != len(SURVEY_WIDTHS) or len(filtered) != len(SURVEY_WIDTHS) or min(plain + filtered) < 0:
+        raise GpuarError(f"choose_filter: two lists of four non-negative totals, not {plain} and {filtered}")
+    width = C.c_uint32(0)
+    on = load().gpuar_hip_choose_filter((C.c_uint64 * 4)(*plain), (C.c_uint64 * 4)(*filtered), n_packets, C.byref(width))
+    return int(width.value), bool(on)
 
 
 def stored_rule(est: int, ulen: int) -> bool:

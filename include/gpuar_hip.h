@@ -402,6 +402,35 @@ int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *es
  * resolution; on data of element width w every multiple of w ties within it, and the smallest is the cheapest to split. */
 uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets);
 
+/* ------------------------------------------------------------------------
+ * Delta survey: what a buffer would compress to WITH the delta filter at each byte-plane width, from one read of its bytes.
+ * For a buffer of P packets and every j = 0 .. 3 (the widths w = 1, 2, 4, 8) whose bit is set in widths_mask,
+ *     d_est[j * est_stride + p]  =  the gpuar_hip_estimate value of packet p of gpuar_hip_split_delta(buffer, w)
+ * for every p < P, by definition (gpuar_amd/csrc/delta_survey.h); nothing is filtered or split into memory, nothing but d_est
+ * is written, and the rows that were not asked for are left untouched.  The input is read once however many rows are asked for.
+ *
+ * Host-side checks as for gpuar_hip_survey_planes, in the same order; in addition widths_mask must be 1 .. 15
+ * (GPUAR_ERR_ARGUMENT).  Nothing is read beyond the 16-byte-aligned piece of memory that holds a buffer's last byte.
+ * ---------------------------------------------------------------------- */
+
+/* The rows asked for, for the n_bytes at d_in. */
+int gpuar_hip_survey_delta(const uint8_t *d_in, size_t n_bytes, uint32_t widths_mask, uint32_t *d_est, size_t est_stride, void *stream);
+
+/* The same for a batch (descriptors as for gpuar_hip_encode_batch): column p of d_est is batch packet p.  Unusable buffers and
+ * packets are GPUAR_STATUS_BAD_BATCH exactly as in gpuar_hip_survey_planes_batch: their columns are left untouched in every row. */
+int gpuar_hip_survey_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                                 size_t n_buffers, size_t n_packets, uint32_t widths_mask, uint32_t *d_est, size_t est_stride,
+                                 uint32_t *d_status, void *stream);
+
+/* Host only: the same values for host memory, from the same definition -- no device is touched. */
+int gpuar_hip_survey_delta_host(const uint8_t *in, size_t n_bytes, uint32_t widths_mask, uint32_t *est, size_t est_stride);
+
+/* Host only, pure: width and filter from the four totals of the plane survey (`plain`) and the four of the delta survey
+ * (`filtered`) of a buffer of n_packets packets.  With wp = gpuar_hip_choose_planes(plain) and wd = gpuar_hip_choose_planes(filtered):
+ * the filter at wd iff filtered[wd] + n_packets <= plain[wp] (it has to win by more than the estimate's resolution of one byte
+ * per packet: a tie goes to no filter, and so does n_packets = 0), else no filter at wp.  Returns 1 (the filter) or 0 and writes the width to *width. */
+int gpuar_hip_choose_filter(const uint64_t plain[4], const uint64_t filtered[4], uint64_t n_packets, uint32_t *width);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
