@@ -3,6 +3,13 @@ launch ORs its flags into its own status word and no other; compaction may run c
 library is usable from one host thread per GPU; the per-device state it keeps -- the fallback status word, the encoder's
 per-CU arrival counters, the clock-sample table -- affects no result).
 
+This module covers the coders and what was built with them: encode (throughput, latency, auto), decode, decode_stream,
+compact, crc32 / verify_crc32, generate, encode_batch / decode_batch / decode_stream_batch / crc32_batch,
+batch.compress(checksum=True) / decompress, the executors' thread-local last error and the fallback status word.  The entry
+points added since -- split_ / merge_planes, _delta and _xor, estimate, survey_planes, survey_delta, their batch forms,
+move_packets, and batch.compress with planes=, delta=, stored=, base= -- are covered in the same way by
+tests/test_gpu_filter_concurrency.py.  The verdict helpers both modules use are in tests/concurrency_checks.py.
+
 Every test works the same way: the serial result of each workload comes first (one launch at a time, synchronised) and is
 pinned against the reference (oracle.encode_stream on 64-packet windows, the oracle's decoder, zlib.crc32); then the same
 workloads run concurrently, and the concurrent result must be byte-equal to the serial one, with every status word
@@ -27,6 +34,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from concurrency_checks import _fail_on, _same, _status, _streams, _words
 from gpuar_amd import synth
 from test_gpu_parity import small_slot_lib  # noqa: F401  (the 1024-byte slot build, a module fixture)
 
@@ -79,10 +87,6 @@ def _release_memory():
     torch.cuda.empty_cache()
 
 
-def _status(k=1):
-    return torch.zeros(k, dtype=torch.int32, device="cuda")
-
-
 def _describe(i, family, mode=None):
     kind, seed, n = WORKLOADS[i]
     m = f" {mode}" if mode else ""
@@ -117,35 +121,8 @@ def _decoded(out, d_in, npk, hole=None):
             & out[n:npk * PACKET].eq(CANARY).all())
 
 
-def _same(a, b):
-    """Device verdict: a and b have the same shape and bytes."""
-    if a.shape != b.shape:
-        return torch.zeros((), dtype=torch.bool, device="cuda")
-    return a.eq(b).all()
-
-
 def _windows(npk):
     return [(a, min(a + 64, npk)) for a in sorted({0, (npk // 2) & ~63, max(npk - 64, 0)})]
-
-
-def _fail_on(verdicts):
-    """verdicts: [(description, device bool)]: one copy to the host; fails naming every check that did not hold."""
-    if not verdicts:
-        return
-    ok = torch.stack([v for _, v in verdicts]).cpu().numpy()
-    wrong = [what for (what, _), good in zip(verdicts, ok) if not good]
-    assert not wrong, f"{len(wrong)} of {len(verdicts)} checks failed: " + "; ".join(wrong[:12])
-
-
-def _words(verdicts, words, expected, what):
-    """Status words against what each launch should report (one verdict each)."""
-    want = torch.tensor(expected, dtype=torch.int32, device=words.device)
-    for j, w in enumerate(what):
-        verdicts.append((f"{w}: status word is not {expected[j]:#x}", words[j].eq(want[j])))
-
-
-def _streams(k):
-    return [torch.cuda.Stream() for _ in range(k)]
 
 
 @pytest.fixture(scope="module")
