@@ -459,7 +459,10 @@ int gpuar_hip_abi_version(void);
 
 /* Synthetic streams of SURVEY.md section 8(d), generated on the device so
  * multi-GiB benchmark inputs never cross PCIe.  kind: 0 uniform, 1 zipf,
- * 2 text.  Fills d_out[0..n) with bytes [offset, offset+n) of the stream. */
+ * 2 text.  Fills d_out[0..n) with bytes [offset, offset+n) of the stream.
+ * d_out must be 8-byte aligned (the kernels store 8 bytes at a time; every allocator's first byte is): GPUAR_ERR_ALIGNMENT
+ * otherwise, before any device work.  `offset` must be a multiple of 8 and `kind` 0 .. 2: GPUAR_ERR_ARGUMENT.  n == 0 is
+ * GPUAR_OK with no launch. */
 int gpuar_hip_generate(int kind, uint64_t seed, uint64_t offset, size_t n, uint8_t *d_out, void *stream);
 
 /* Measurement support: a plain device-to-device copy of n_bytes (a multiple of 16; both pointers 16-byte aligned),
