@@ -48,6 +48,13 @@ against it a bf16 tensor compresses to 0.06-0.72 of what it does alone, against 
 base_auto=True measures and keeps the bases that are predicted to pay (Compressed.based).  The CRCs are those of the original
 bytes, so a wrong base in decompress is a checksum mismatch.  Compressed.gip(b) carries a version-5 trailer
 (`gpuar c --base=FILE --planes=W`) and needs the CRCs.  A base together with `delta` is refused.
+
+With sparse="auto" a packet that is one byte value almost everywhere is neither coded nor kept raw: one more pass
+(hip.sparse_scan_batch) finds every packet's majority byte and counts its exceptions, and the packets whose record -- the byte, the
+count, the exceptions' positions and values: 4 + 3 k bytes -- is smaller than their estimate go into Compressed.sparse
+(hip.sparse_pack) and come back through hip.sparse_unpack.  That is what a base makes of everything that did not
+change since it: compress(tensors, planes="auto", base=[...], sparse="auto") keeps an unchanged packet in 4 bytes where the
+codec cannot go below 210.  Like a raw packet, a sparse one has no .gip form.
 """
 from __future__ import annotations
 
@@ -131,7 +138,12 @@ class Compressed:
     Compressed with stored=...: `stored` (uint8, device, n_packets) is 1 for every batch packet that is kept raw, `raw` (uint8,
     device) holds those packets' bytes in batch order, each at a 16-byte-aligned offset, `raw_offsets` (int64, device,
     n_stored + 1) where; `stream` and `offsets` (n_coded + 1 entries) then cover the CODED packets only, in batch order.  All
-    three are None otherwise."""
+    three are None otherwise.
+
+    Compressed with sparse="auto": `stored` is the packet's kind -- 0 coded, 1 raw, 2 sparse, so that a stable sort by it gives the
+    coded, the raw and the sparse packets, each in batch order --, `sparse` (uint8, device) holds the sparse packets' records
+    (gpuar_amd/csrc/sparse.h) back to back in batch order, `sparse_offsets` (int64, device, n_sparse + 1) where; `raw` and
+    `raw_offsets` are there too (empty without stored=...).  Both are None otherwise."""
     stream: object
     offsets: object
     first_packet: list
@@ -143,6 +155,8 @@ class Compressed:
     raw_offsets: object = None
     delta: list = None
     based: list = None
+    sparse: object = None
+    sparse_offsets: object = None
 
     @property
     def n_buffers(self) -> int:
@@ -159,8 +173,8 @@ class Compressed:
 
     @property
     def nbytes(self) -> int:
-        """The compressed bytes: the coded packets' stream and the raw packets."""
-        return self.stream.numel() + (self.raw.numel() if self.raw is not None else 0)
+        """The compressed bytes: the coded packets' stream, the raw packets and the sparse packets' records."""
+        return self.stream.numel() + (self.raw.numel() if self.raw is not None else 0) + (self.sparse.numel() if self.sparse is not None else 0)
 
     def _coded_range(self, b: int):
         """Buffer b's packets as a range of `offsets`: its batch packets, or -- with `stored` -- their ranks among the coded ones."""
@@ -172,8 +186,8 @@ class Compressed:
             for flag in self.stored.cpu().tolist():
                 self._rank.append(self._rank[-1] + (0 if flag else 1))
         if self._rank[hi] - self._rank[lo] != hi - lo:
-            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw) packets: it has no packet stream "
-                             "and no .gip form (the container has no raw packets)")
+            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw or sparse) packets: it has no packet stream "
+                             "and no .gip form (the container has no raw and no sparse packets)")
         return self._rank[lo], self._rank[hi]
 
     def payload(self, b: int):
@@ -352,14 +366,43 @@ def _stored_argument(stored, n_packets):
     return [bool(f) for f in flags]
 
 
-def _partition(d_flags, d_len16):
-    """(n_stored, raw bytes, coded packets, stored packets): the packets of either kind in batch order (a stable sort by the flag;
-    one synchronisation for the two counts)."""
+def _partition(d_flags, d_len16, d_slen=None):
+    """(n_stored, raw bytes, coded packets, stored packets, n_sparse, sparse bytes, sparse packets): the packets of every kind in
+    batch order (a stable sort by the kind: 0 coded, 1 raw, 2 sparse; one synchronisation for the counts).  d_slen: the bytes of
+    every packet's sparse record; None where no packet is sparse (d_flags is then 0 or 1)."""
     import torch
-    n_stored, raw_bytes = torch.stack([d_flags.sum(), (d_len16 * d_flags).sum()]).tolist()
+    if d_slen is None:
+        n_stored, raw_bytes = torch.stack([d_flags.sum(), (d_len16 * d_flags).sum()]).tolist()
+        n_sparse = sparse_bytes = 0
+    else:
+        d_raw, d_sparse = (d_flags == H.KIND_RAW).to(torch.int64), (d_flags == H.KIND_SPARSE).to(torch.int64)
+        n_stored, raw_bytes, n_sparse, sparse_bytes = torch.stack([d_raw.sum(), (d_len16 * d_raw).sum(), d_sparse.sum(), (d_slen * d_sparse).sum()]).tolist()
     order = torch.argsort(d_flags, stable=True)
-    n_coded = d_flags.numel() - n_stored
-    return n_stored, raw_bytes, order[:n_coded], order[n_coded:]
+    n_coded = d_flags.numel() - n_stored - n_sparse
+    return n_stored, raw_bytes, order[:n_coded], order[n_coded:n_coded + n_stored], n_sparse, sparse_bytes, order[n_coded + n_stored:]
+
+
+def _sparse_argument(sparse, stored):
+    """`sparse` as None or "auto"; anything else raises (before any launch), and so does sparse="auto" beside a list of stored
+    packets: the rule that chooses a packet's kind needs the estimate."""
+    if sparse is None:
+        return None
+    if not (isinstance(sparse, str) and sparse == "auto"):
+        raise GpuarError(f"sparse={sparse!r}: None or \"auto\"")
+    if stored is not None and not (isinstance(stored, str) and stored == "auto"):
+        raise GpuarError("sparse=\"auto\" goes with stored=None or stored=\"auto\", not with a list of stored packets")
+    return sparse
+
+
+def _kinds(d_scan, d_est, d_len, stored_on):
+    """hip.sparse_rule on the device: (kind, sparse record bytes) per packet, int64, from the scan words, the estimates and the
+    packets' lengths."""
+    import torch
+    scan = d_scan.to(torch.int64) & 0xFFFFFFFF
+    d_slen = (4 + 3 * (scan >> 8) + 3) & ~3
+    raw_ok = (d_est >= 4 + d_len) if stored_on else torch.zeros_like(d_len, dtype=torch.bool)
+    is_sparse = (scan != H.SPARSE_NONE) & (d_slen + 1 < d_est) & (~raw_ok | (d_slen < d_len))
+    return torch.where(is_sparse, H.KIND_SPARSE, torch.where(raw_ok, H.KIND_RAW, H.KIND_CODED)), d_slen
 
 
 def _unit_first_packet(n, device):
@@ -557,17 +600,19 @@ def survey_choice(tensors, stored=None):
     return [w for w, _f in choices], [f for _w, f in choices]
 
 
-def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False) -> list:
+def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False, sparse=None) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
     asks for it (as compress), and with stored="auto" counting a packet that would be kept raw as its own bytes.  One
     split_planes_batch launch if asked for, one estimate_batch launch (planes="survey": survey's launch in front).  `delta`: as
     compress -- the estimate is that of the filtered, split bytes (delta="auto", "survey": of each tensor's better half).  `base`,
     `base_auto`: as compress -- the estimate is that of the XORed, split bytes (base_auto: of each tensor's better half, from
-    _auto_base's two split and two estimate launches alone)."""
+    _auto_base's two split and two estimate launches alone).  `sparse`: None | "auto": as compress -- one hip.sparse_scan_batch
+    launch more, and a packet that would be kept sparse counts as its record's bytes."""
     import torch
     if stored is not None and stored != "auto":
         raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    sparse = _sparse_argument(sparse, stored)
     tensors = list(tensors)
     _check_base(tensors, delta, base, base_auto)
     if isinstance(planes, str) and planes == "survey":
@@ -595,14 +640,19 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     if d_est is None:
         d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
     buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
-    if stored == "auto":
+    if sparse == "auto":
+        d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device)
+        d_kind, d_slen = _kinds(d_scan, d_est[:n_packets], d_len, stored == "auto")
+        d_est = torch.where(d_kind == H.KIND_SPARSE, d_slen, torch.where(d_kind == H.KIND_RAW, d_len, d_est[:n_packets]))
+    elif stored == "auto":
         d_est = torch.where(d_est >= 4 + d_len, d_len, d_est)
     totals = torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est)
     _raise_on_status(d_status, "estimate_batch")
     return totals.tolist()
 
 
-def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None, base=None, base_auto=False) -> Compressed:
+def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None, base=None, base_auto=False,
+             sparse=None) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
     compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
     every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
@@ -624,7 +674,12 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     inputs and bases are never modified).  planes="survey" surveys the original bytes.  `base_auto`: keep only the bases for
     which splitting and estimating the batch both ways predicts a gain (_auto_base: one split and one estimate launch more than
     fixed bases with stored="auto" take, one synchronisation, both split copies kept and none made a third time);
-    Compressed.based says which.  base=None takes exactly the path taken without the keyword.  See Compressed."""
+    Compressed.based says which.  base=None takes exactly the path taken without the keyword.  `sparse`: None | "auto" (with
+    stored None or "auto"): keep the packets that are one byte value almost everywhere as that byte and a list of exceptions --
+    one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one hip.sparse_scan_batch launch
+    on the bytes that would be coded, hip.sparse_rule on the device, and the packets go three ways: coded, raw (hip.move_packets)
+    and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.  See
+    Compressed."""
     import torch
     tensors = list(tensors)
     _check_base(tensors, delta, base, base_auto)                 # (raises before the survey's launch)
@@ -639,10 +694,11 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     widths, flags = _filter_arguments(tensors, planes, delta)
     widths, bases = _base_arguments(tensors, widths, base)
     stored = _stored_argument(stored, n_packets)
+    sparse = _sparse_argument(sparse, stored)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     n = len(sizes)
-    d_stored = d_raw = d_raw_offsets = None
+    d_stored = d_raw = d_raw_offsets = d_sparse = d_sparse_offsets = None
     with torch.cuda.stream(stream) if stream is not None else _nothing():
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if flags == "auto":
@@ -656,21 +712,26 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         if chosen is None:
             chosen = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags, bases)
         d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = chosen
-        if stored is None:
+        if stored is None and sparse is None:
             d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
             d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
         else:
             # every packet a buffer of its own: the coded ones go to the encoder, the stored ones to the copy, both in batch order
             _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
-            if stored == "auto":
+            d_slen = None
+            if stored == "auto" or sparse == "auto":
                 d_est = d_chosen_est if d_chosen_est is not None else \
                     H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+            if sparse == "auto":
+                d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+                d_flags, d_slen = _kinds(d_scan, d_est[:n_packets], d_pkt_len, stored == "auto")
+            elif stored == "auto":
                 d_flags = (d_est[:n_packets] >= 4 + d_pkt_len).to(torch.int64)
             else:
                 d_flags = torch.tensor(stored, dtype=torch.int64).to(device)
             d_len16 = (d_pkt_len + 15) // 16 * 16
-            n_stored, raw_bytes, coded, kept = _partition(d_flags, d_len16)
-            n_coded = n_packets - n_stored
+            n_stored, raw_bytes, coded, kept, n_sparse, sparse_bytes, packed = _partition(d_flags, d_len16, d_slen)
+            n_coded = n_packets - n_stored - n_sparse
             d_slots = None
             d_stream, d_offsets = torch.empty(0, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int64, device=device)
             if n_coded:
@@ -681,6 +742,12 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
             d_raw_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(d_len16[kept], 0)])
             if n_stored:
                 H.move_packets(d_pkt_ptr[kept], d_raw.data_ptr() + d_raw_offsets[:n_stored], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
+            if sparse == "auto":
+                d_sparse = torch.empty(sparse_bytes, dtype=torch.uint8, device=device)         # (sparse_pack writes every byte, the pads too)
+                d_sparse_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(d_slen[packed], 0)])
+                if n_sparse:
+                    H.sparse_pack(d_pkt_ptr[packed], d_pkt_len[packed], d_scan[:n_packets][packed], d_sparse.data_ptr() + d_sparse_offsets[:n_sparse],
+                                  n_sparse, stream=stream, d_status=d_status)
             d_stored = d_flags.to(torch.uint8)
         d_crc = H.crc32_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device) if checksum else None
         _raise_on_status(d_status, "encode_batch")
@@ -691,7 +758,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         del d_slots, d_split
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
                       crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
-                      raw_offsets=d_raw_offsets, delta=flags, based=[bool(q) for q in bases] if bases is not None else None)
+                      raw_offsets=d_raw_offsets, delta=flags, based=[bool(q) for q in bases] if bases is not None else None,
+                      sparse=d_sparse, sparse_offsets=d_sparse_offsets)
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
@@ -701,7 +769,8 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
     the first buffer and packet that differ.  Buffers that were split into byte planes are merged back in place in `out`
     after decoding and before verifying: the CRCs are those of the original bytes; where a buffer went through the delta filter,
     that launch is hip.merge_delta_batch, which also sums the differences up again.  Packets that were stored raw are copied
-    (one more launch), the others decoded.  `base`: as in compress; every buffer with c.based[b] needs base[b], the tensor it
+    (one more launch), sparse packets rebuilt from their records (hip.sparse_unpack, one more launch; a record that is not valid
+    raises: BAD_PACKET), the others decoded.  `base`: as in compress; every buffer with c.based[b] needs base[b], the tensor it
     was compressed against (a missing one, one of another size, device or alignment, or one that overlaps any tensor of `out`
     raises before any launch; entries of the other buffers are ignored); the merge is then hip.merge_xor_batch.  A base with other contents
     cannot be told from damage: with CRCs it is reported as the checksum mismatch, without them it goes unnoticed."""
@@ -752,14 +821,18 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
             # the stored ones copied
             _buf, d_pkt_ptr, d_pkt_len = _packets(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets)
             n_coded = c.offsets.numel() - 1
-            n_stored = c.n_packets - n_coded
+            n_sparse = c.sparse_offsets.numel() - 1 if c.sparse_offsets is not None else 0
+            n_stored = c.n_packets - n_coded - n_sparse
             order = torch.argsort(c.stored, stable=True)
-            coded, kept = order[:n_coded], order[n_coded:]
+            coded, kept, packed = order[:n_coded], order[n_coded:n_coded + n_stored], order[n_coded + n_stored:]
             if n_coded:
                 H.decode_stream_batch(c.stream, c.offsets, _unit_first_packet(n_coded, device), n_coded, n_coded, d_pkt_ptr[coded], d_pkt_len[coded],
                                       stream=stream, d_status=d_status)
             if n_stored:
                 H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
+            if n_sparse:
+                H.sparse_unpack(c.sparse.data_ptr() + c.sparse_offsets[:n_sparse], c.sparse_offsets[1:] - c.sparse_offsets[:n_sparse], d_pkt_ptr[packed],
+                                d_pkt_len[packed], n_sparse, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
         if bases is not None and any(bases) and c.n_packets:
             (d_elem, d_base), _keep2 = _upload(device, c.planes, bases)

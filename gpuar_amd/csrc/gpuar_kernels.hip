@@ -49,6 +49,7 @@
 #include "estimate.h"
 #include "survey.h"
 #include "delta_survey.h"
+#include "sparse.h"
 
 namespace gpuar {
 
@@ -2929,6 +2930,255 @@ move_packets_kernel(MoveArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Sparse packets (sparse.h): a packet that is one byte value almost everywhere is kept as that byte and a list
+// of (position, value) exceptions instead of being coded.  Three bandwidth-bound passes, one wavefront per packet, lane l on
+// bytes [128 l, 128 l + 128) as eight 16-byte loads that stay in registers (crc_load; nothing is read beyond the 16-byte piece
+// that holds the packet's last byte, and bytes past the packet's end are masked out of every count).
+//
+// sparse_scan_kernel (one buffer or a batch: CrcArgs with `crc` as `scan`, crc_locate): bit b of the only possible majority
+// byte is 1 iff more than half of the packet's bytes have bit b set -- eight masked popcounts per dword, the eight counts
+// reduced over the wave two to a register --, and a second pass over the registers counts the bytes equal to that candidate.
+// No LDS, no histogram.  Lane 0 writes scan[p].
+//
+// sparse_pack_kernel (regions, as move_packets_kernel): every lane counts its exceptions, an inclusive prefix sum over the wave
+// less its own count gives its first slot (lane order times in-lane order is ascending position), and the total is checked against scan[r] BEFORE
+// anything is written: the slots are then all inside the record's sparse_len(k) bytes.
+//
+// sparse_unpack_kernel (regions): the record is validated and the packet built in the wavefront's own 8 KiB of LDS -- filled,
+// then the exceptions scattered into it (ds byte writes, positions checked against the packet's length first), then read back
+// as quads and stored like move_packets_kernel's.  LDS operations of one wavefront complete in order: no barrier.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kSparseWaves = 4;                        // wavefronts per workgroup, a packet each
+constexpr uint32_t kSparseGroups = 2048;                    // scan: 8 workgroups per CU of an MI355X, persistent over the packets
+constexpr uint32_t kSparseLow = 0x01010101u, kSparseHigh = 0x80808080u;
+
+// the bytes of the dword at byte `at` of the lane's 128 that lie inside the packet (have: how many of the 128 do)
+template <bool Full>
+__device__ __forceinline__ uint32_t sparse_mask(uint32_t at, uint32_t have) {
+    if (Full) return 0xFFFFFFFFu;
+    return at + 4u <= have ? 0xFFFFFFFFu : at < have ? (1u << (8u * (have - at))) - 1u : 0u;
+}
+
+// 0x80 in every byte of x that is zero
+__device__ __forceinline__ uint32_t sparse_zero_bytes(uint32_t x) {
+    return ~(((x & ~kSparseHigh) + ~kSparseHigh) | x) & kSparseHigh;
+}
+
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// the packet's scan word (in every lane)
+template <bool Full>
+__device__ __forceinline__ uint32_t sparse_scan_packet_wave(const CrcQuad (&q)[8], uint32_t count, uint32_t lane) {
+    const uint32_t start = kCrcChunk * lane;
+    const uint32_t have = count > start ? (count - start < kCrcChunk ? count - start : kCrcChunk) : 0u;
+    uint32_t bits[4] = {0u, 0u, 0u, 0u};                    // bits[i]: the counts of bit 2 i (low half) and bit 2 i + 1 (high half)
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t v = w[j] & sparse_mask<Full>(16u * k + 4u * j, have);
+#pragma unroll
+            for (uint32_t i = 0; i < 4; ++i)
+                bits[i] += __popc(v & (kSparseLow << (2u * i))) + (__popc(v & (kSparseLow << (2u * i + 1u))) << 16);
+        }
+    }
+    uint32_t candidate = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t both = wave_sum32(bits[i]);          // (a count is at most 8192: the halves do not meet)
+        candidate |= (2u * (both & 0xFFFFu) > count ? 1u << (2u * i) : 0u) | (2u * (both >> 16) > count ? 2u << (2u * i) : 0u);
+    }
+    uint32_t equal = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) {
+        const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j)
+            equal += __popc(sparse_zero_bytes(w[j] ^ (candidate * kSparseLow)) & sparse_mask<Full>(16u * k + 4u * j, have));
+    }
+    return sparse_scan_word(candidate, wave_sum32(equal), count);
+}
+
+__global__ void __launch_bounds__(kSparseWaves * kLanes)
+sparse_scan_kernel(CrcArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t stride = gridDim.x * kSparseWaves;
+    for (uint32_t packet = blockIdx.x * kSparseWaves + (threadIdx.x >> 6), next; packet < a.n_packets; packet = next) {
+        next = packet + stride;
+        const CrcPacket p = crc_locate(a, packet);
+        if (p.count == 0u) {
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+        } else {
+            CrcQuad q[8];
+            crc_load(q, p, lane);
+            const uint32_t scan = p.count == kPacket ? sparse_scan_packet_wave<true>(q, p.count, lane)       // wave-uniform
+                                                     : sparse_scan_packet_wave<false>(q, p.count, lane);
+            if (lane == 0u) a.crc[packet] = scan;
+        }
+        if (next < packet) break;
+    }
+}
+
+struct SparsePackArgs {
+    const uint8_t *const *src;
+    const uint64_t *bytes;
+    const uint32_t *scan;
+    uint8_t *const *dst;
+    uint32_t n_regions;
+    uint32_t *status;
+};
+
+__global__ void __launch_bounds__(kSparseWaves * kLanes)
+sparse_pack_kernel(SparsePackArgs a) {
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_regions; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+        const uintptr_t src = reinterpret_cast<uintptr_t>(a.src[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
+        const uint64_t n64 = a.bytes[r];
+        const uint32_t scan = a.scan[r];
+        if ((src & 15u) != 0u || (dst & 3u) != 0u || n64 == 0u || n64 > kPacket || scan == kSparseNone) {
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        const uint32_t n = static_cast<uint32_t>(n64), fill = scan & 255u, k = scan >> 8;
+        const CrcPacket p = {reinterpret_cast<const uint8_t *>(src), n};
+        CrcQuad q[8];
+        crc_load(q, p, lane);
+        const uint32_t start = kCrcChunk * lane;
+        const uint32_t have = n > start ? (n - start < kCrcChunk ? n - start : kCrcChunk) : 0u;
+        uint32_t mine = 0;                                   // the lane's exceptions
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                mine += __popc(~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(16u * i + 4u * j, have));
+        }
+        uint32_t upto = mine;                                // inclusive prefix sum over the wave
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t below = __shfl_up(upto, off);
+            if (lane >= off) upto += below;
+        }
+        const uint32_t total = __shfl(upto, 63);
+        if (total != k || 2u * k >= n) {                     // wave-uniform; nothing has been written
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        GlobalHalf *pos = reinterpret_cast<GlobalHalf *>(dst + 4u);
+        GlobalByte *val = reinterpret_cast<GlobalByte *>(dst + 4u + 2u * k);
+        if (lane == 0u) *reinterpret_cast<GlobalWord *>(dst) = sparse_head(fill, k);
+        if (lane < sparse_len(k) - (4u + 3u * k)) val[k + lane] = 0;           // the pad
+        uint32_t slot = upto - mine;                         // slot < k wherever a store below is reached: the same predicate was counted
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t at = 16u * i + 4u * j;
+                const uint32_t differ = ~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(at, have);
+                if (differ != 0u) {
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; ++b) {
+                        if (differ & (0x80u << (8u * b))) {
+                            pos[slot] = static_cast<uint16_t>(start + at + b);
+                            val[slot] = static_cast<uint8_t>(w[j] >> (8u * b));
+                            ++slot;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+struct SparseUnpackArgs {
+    const uint8_t *const *rec;
+    const uint64_t *rec_bytes;
+    uint8_t *const *dst;
+    const uint64_t *bytes;
+    uint32_t n_regions;
+    uint32_t *status;
+};
+
+__global__ void __launch_bounds__(kSparseWaves * kLanes)
+sparse_unpack_kernel(SparseUnpackArgs a) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    __shared__ PlanesQuad lds[kSparseWaves * (kPacket / 16u)];
+    const uint32_t lane = threadIdx.x & 63u;
+    PlanesQuad *quads = lds + (threadIdx.x >> 6) * (kPacket / 16u);          // the wavefront's own packet
+    uint8_t *packet = reinterpret_cast<uint8_t *>(quads);
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_regions; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+        const uintptr_t rec = reinterpret_cast<uintptr_t>(a.rec[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
+        const uint64_t rec_bytes = a.rec_bytes[r], n64 = a.bytes[r];
+        if ((rec & 3u) != 0u || (dst & 15u) != 0u || n64 == 0u || n64 > kPacket) {
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        const uint32_t n = static_cast<uint32_t>(n64);
+        const uint32_t head = rec_bytes >= 4u ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<const GlobalWord *>(rec)) : 0xFFFFFFFFu;
+        if (rec_bytes < 4u || !sparse_head_ok(head, rec_bytes, n)) {         // wave-uniform; nothing behind the head is read
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+            continue;
+        }
+        const uint32_t fill = head & 255u, k = head >> 16;                    // 4 + 3 k <= rec_bytes, 2 k < n
+        const GlobalHalf *pos = reinterpret_cast<const GlobalHalf *>(rec + 4u);
+        const GlobalByte *val = reinterpret_cast<const GlobalByte *>(rec + 4u + 2u * k);
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j)
+            if (16u * (lane + 64u * j) < n) quads[lane + 64u * j] = PlanesQuad(fill * kSparseLow);
+        asm volatile("" ::: "memory");                       // the fill in front of the exceptions, which other lanes write
+        bool bad = false;
+        for (uint32_t i = lane; i < k; i += 64u) {
+            const uint32_t at = pos[i], v = val[i];
+            const bool ascending = i == 0u || pos[i - 1u] < at;
+            if (at < n && v != fill && ascending) packet[at] = static_cast<uint8_t>(v);      // at < n <= 8192: inside the wavefront's LDS
+            else bad = true;
+        }
+        if (__any(bad)) {                                    // the destination is left as it was
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+            continue;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's exceptions in front of the reads of whole quads
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) {
+            const uint32_t at = 16u * (lane + 64u * j);
+            if (at >= n) continue;
+            const uint32_t left = n - at;
+            const PlanesQuad v = quads[lane + 64u * j];
+            if (left >= 16u) {
+                reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = v;
+            } else {                                         // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
+                GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+#pragma unroll
+                for (uint32_t d = 0; d < 4; ++d) {
+                    if (4u * d + 4u <= left) {
+                        words[d] = w[d];
+                    } else {
+#pragma unroll
+                        for (uint32_t b = 0; b < 3; ++b)
+                            if (4u * d + b < left) bytes[4u * d + b] = static_cast<uint8_t>(w[d] >> (8u * b));
+                    }
+                }
+            }
+        }
+        asm volatile("" ::: "memory");                       // these reads in front of the next packet's fill
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Plane-width survey (survey.h): est[j][p] = estimate(split_planes(buffer, 1 << j))[p] for the four widths at
 // once, from one read of the original bytes and without making any split, for one buffer or a batch.
 //
@@ -4164,6 +4414,110 @@ int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_d
     const uint32_t blocks = a.n_regions < gpuar::kPlaneGridCap ? a.n_regions : gpuar::kPlaneGridCap;
     gpuar::move_packets_kernel<<<blocks, gpuar::kMoveThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
+}
+
+uint32_t gpuar_hip_sparse_len(uint32_t k) { return gpuar::sparse_len(k); }
+
+int gpuar_hip_sparse_rule(uint32_t scan, uint32_t est, uint32_t ulen, int stored_on) {
+    return static_cast<int>(gpuar::sparse_kind(scan, est, ulen, stored_on != 0));
+}
+
+static int launch_sparse_scan(const gpuar::CrcArgs &a, void *stream) {
+    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kSparseWaves - 1) / gpuar::kSparseWaves;
+    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kSparseGroups ? groups : gpuar::kSparseGroups);
+    gpuar::sparse_scan_kernel<<<blocks, gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_sparse_scan(const uint8_t *d_in, size_t n_bytes, uint32_t *d_scan, void *stream) {
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_scan, nullptr, nullptr, &status, &launch);     // the estimate call's checks
+    if (e != GPUAR_OK || !launch) return e;
+    gpuar::CrcArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.crc = d_scan;
+    a.status = status;
+    return launch_sparse_scan(a, stream);
+}
+
+int gpuar_hip_sparse_scan_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                                size_t n_buffers, size_t n_packets, uint32_t *d_scan, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    uint32_t *status = nullptr;
+    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_scan, nullptr, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    gpuar::CrcArgs a = {};
+    a.ptrs = d_in_ptrs;
+    a.bytes = d_in_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.crc = d_scan;
+    a.status = status;
+    return launch_sparse_scan(a, stream);
+}
+
+int gpuar_hip_sparse_scan_host(const uint8_t *in, size_t n_bytes, uint32_t *scan) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !scan) return GPUAR_ERR_ARGUMENT;
+    gpuar::sparse_scan_host(in, n_bytes, scan);
+    return GPUAR_OK;
+}
+
+static uint32_t sparse_blocks(uint32_t n_regions) {
+    const uint32_t groups = n_regions / gpuar::kSparseWaves + (n_regions % gpuar::kSparseWaves ? 1u : 0u);
+    return groups < gpuar::kPlaneGridCap ? groups : gpuar::kPlaneGridCap;
+}
+
+int gpuar_hip_sparse_pack(const uint8_t *const *d_src_ptrs, const uint64_t *d_bytes, const uint32_t *d_scan, uint8_t *const *d_dst_ptrs,
+                          size_t n_regions, uint32_t *d_status, void *stream) {
+    if (n_regions == 0) return GPUAR_OK;
+    if (!d_src_ptrs || !d_bytes || !d_scan || !d_dst_ptrs || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_src_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_scan) & 3u) ||
+        (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return GPUAR_ERR_ALIGNMENT;
+    gpuar::SparsePackArgs a = {};
+    a.src = d_src_ptrs;
+    a.bytes = d_bytes;
+    a.scan = d_scan;
+    a.dst = d_dst_ptrs;
+    a.n_regions = static_cast<uint32_t>(n_regions);
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    gpuar::sparse_pack_kernel<<<sparse_blocks(a.n_regions), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_sparse_unpack(const uint8_t *const *d_rec_ptrs, const uint64_t *d_rec_bytes, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes,
+                            size_t n_regions, uint32_t *d_status, void *stream) {
+    if (n_regions == 0) return GPUAR_OK;
+    if (!d_rec_ptrs || !d_rec_bytes || !d_dst_ptrs || !d_bytes || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_rec_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_rec_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) ||
+        (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
+        return GPUAR_ERR_ALIGNMENT;
+    gpuar::SparseUnpackArgs a = {};
+    a.rec = d_rec_ptrs;
+    a.rec_bytes = d_rec_bytes;
+    a.dst = d_dst_ptrs;
+    a.bytes = d_bytes;
+    a.n_regions = static_cast<uint32_t>(n_regions);
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    gpuar::sparse_unpack_kernel<<<sparse_blocks(a.n_regions), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_sparse_pack_host(const uint8_t *in, size_t n_bytes, uint8_t *rec, size_t rec_room, size_t *rec_len) {
+    if (!in || !rec || !rec_len || n_bytes == 0 || n_bytes > gpuar::kSparsePacket) return GPUAR_ERR_ARGUMENT;
+    return gpuar::sparse_pack_host(in, static_cast<uint32_t>(n_bytes), rec, rec_room, rec_len) ? GPUAR_OK : GPUAR_ERR_ARGUMENT;
+}
+
+int gpuar_hip_sparse_unpack_host(const uint8_t *rec, size_t rec_bytes, uint8_t *out, size_t n_bytes) {
+    if (!rec || !out || n_bytes == 0 || n_bytes > gpuar::kSparsePacket) return GPUAR_ERR_ARGUMENT;
+    return gpuar::sparse_unpack_host(rec, rec_bytes, out, static_cast<uint32_t>(n_bytes)) ? GPUAR_OK : GPUAR_ERR_ARGUMENT;
 }
 
 int gpuar_hip_status(uint32_t *flags) {

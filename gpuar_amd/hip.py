@@ -36,6 +36,8 @@ EXPORTS = [
     "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
     "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
     "gpuar_hip_survey_delta", "gpuar_hip_survey_delta_batch", "gpuar_hip_survey_delta_host", "gpuar_hip_choose_filter",
+    "gpuar_hip_sparse_len", "gpuar_hip_sparse_rule", "gpuar_hip_sparse_scan", "gpuar_hip_sparse_scan_batch", "gpuar_hip_sparse_scan_host",
+    "gpuar_hip_sparse_pack", "gpuar_hip_sparse_unpack", "gpuar_hip_sparse_pack_host", "gpuar_hip_sparse_unpack_host",
 ]
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
@@ -167,6 +169,24 @@ def load() -> C.CDLL:
     lib.gpuar_hip_survey_delta_host.argtypes = [vp, sz, u32, vp, sz]
     lib.gpuar_hip_choose_filter.restype = C.c_int
     lib.gpuar_hip_choose_filter.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(u32)]
+    lib.gpuar_hip_sparse_len.restype = u32
+    lib.gpuar_hip_sparse_len.argtypes = [u32]
+    lib.gpuar_hip_sparse_rule.restype = C.c_int
+    lib.gpuar_hip_sparse_rule.argtypes = [u32, u32, u32, C.c_int]
+    lib.gpuar_hip_sparse_scan.restype = C.c_int
+    lib.gpuar_hip_sparse_scan.argtypes = [vp, sz, vp, vp]
+    lib.gpuar_hip_sparse_scan_batch.restype = C.c_int
+    lib.gpuar_hip_sparse_scan_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+    lib.gpuar_hip_sparse_scan_host.restype = C.c_int
+    lib.gpuar_hip_sparse_scan_host.argtypes = [vp, sz, vp]
+    lib.gpuar_hip_sparse_pack.restype = C.c_int
+    lib.gpuar_hip_sparse_pack.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    lib.gpuar_hip_sparse_unpack.restype = C.c_int
+    lib.gpuar_hip_sparse_unpack.argtypes = [vp, vp, vp, vp, sz, vp, vp]
+    lib.gpuar_hip_sparse_pack_host.restype = C.c_int
+    lib.gpuar_hip_sparse_pack_host.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
+    lib.gpuar_hip_sparse_unpack_host.restype = C.c_int
+    lib.gpuar_hip_sparse_unpack_host.argtypes = [vp, sz, vp, sz]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -777,6 +797,99 @@ def move_packets(d_src_ptrs, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d
         _require_u64_desc(t, name, n_regions)
     _check(load().gpuar_hip_move_packets(d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
                                          _stream_handle(stream)), "gpuar_hip_move_packets")
+
+
+SPARSE_NONE = 0xFFFFFFFF             # GPUAR_SPARSE_NONE: a packet without a majority byte
+KIND_CODED, KIND_RAW, KIND_SPARSE = 0, 1, 2      # what gpuar_hip_sparse_rule returns; the values of batch.Compressed.stored
+
+
+def sparse_len(k: int) -> int:
+    """The bytes of a sparse record with k exceptions (gpuar_hip_sparse_len): (4 + 3 k + 3) & ~3."""
+    return int(load().gpuar_hip_sparse_len(k))
+
+
+def sparse_rule(scan: int, est: int, ulen: int, stored_on: bool) -> int:
+    """What a packet of `ulen` bytes with scan word `scan` and estimate `est` is kept as: KIND_CODED, KIND_RAW or KIND_SPARSE
+    (gpuar_hip_sparse_rule; the definition is in include/gpuar_hip.h)."""
+    return int(load().gpuar_hip_sparse_rule(scan & 0xFFFFFFFF, est, ulen, int(bool(stored_on))))
+
+
+def sparse_scan(d_in, n_bytes: int = None, d_scan=None, stream=None):
+    """The scan word of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in` (gpuar_hip_sparse_scan):
+    (k << 8) | f for a packet whose majority byte f leaves k exceptions, SPARSE_NONE (-1 as int32) for one without.  Returns
+    d_scan: int32 CUDA tensor of packet_count(n_bytes) values."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    if n > d_in.numel():
+        raise GpuarError("n_bytes is larger than d_in")
+    npk = packet_count(n)
+    if d_scan is None:
+        d_scan = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)[:npk]
+    _require_crc(d_scan, "d_scan", npk)
+    _check(load().gpuar_hip_sparse_scan(d_in.data_ptr(), n, d_scan.data_ptr(), _stream_handle(stream)), "gpuar_hip_sparse_scan")
+    return d_scan
+
+
+def sparse_scan_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_scan=None, stream=None, d_status=None, device=None):
+    """The scan word of every packet of a batch (gpuar_hip_sparse_scan_batch; descriptors as for encode_batch)."""
+    import torch
+    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
+        _require_u64_desc(t, name, n)
+    if d_scan is None:
+        d_scan = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)[:n_packets]
+    _require_crc(d_scan, "d_scan", n_packets)
+    _check(load().gpuar_hip_sparse_scan_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+                                              d_scan.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_scan_batch")
+    return d_scan
+
+
+def sparse_scan_host(data) -> list:
+    """sparse_scan of a bytes-like object on the CPU (gpuar_hip_sparse_scan_host: no device is touched): one int per packet."""
+    data = bytes(data)
+    scan = (C.c_uint32 * max(packet_count(len(data)), 1))()
+    _check(load().gpuar_hip_sparse_scan_host(data, len(data), scan), "gpuar_hip_sparse_scan_host")
+    return list(scan)[:packet_count(len(data))]
+
+
+def sparse_pack_host(data) -> bytes:
+    """The sparse record of one packet (1 .. 8192 bytes) on the CPU (gpuar_hip_sparse_pack_host); raises for a packet without a
+    majority byte."""
+    data = bytes(data)
+    rec = (C.c_uint8 * (4 + 3 * (PACKET // 2) + 4))()
+    length = C.c_size_t(0)
+    _check(load().gpuar_hip_sparse_pack_host(data, len(data), rec, len(rec), C.byref(length)), "gpuar_hip_sparse_pack_host")
+    return bytes(rec[:length.value])
+
+
+def sparse_unpack_host(rec, n_bytes: int) -> bytes:
+    """The packet of `n_bytes` from its sparse record on the CPU (gpuar_hip_sparse_unpack_host); raises for a record that is
+    not valid."""
+    rec = bytes(rec)
+    out = (C.c_uint8 * max(n_bytes, 1))()
+    _check(load().gpuar_hip_sparse_unpack_host(rec, len(rec), out, n_bytes), "gpuar_hip_sparse_unpack_host")
+    return bytes(out[:n_bytes])
+
+
+def sparse_pack(d_src_ptrs, d_bytes, d_scan, d_dst_ptrs, n_regions: int, stream=None, d_status=None):
+    """Write the sparse records of n_regions packets: d_bytes[r] <= 8192 bytes at d_src_ptrs[r] (16-byte aligned) with the scan
+    word d_scan[r] (int32) into sparse_len(d_scan[r] >> 8) bytes at d_dst_ptrs[r] (4-byte aligned) (gpuar_hip_sparse_pack; the
+    pointers and sizes are 64-bit CUDA tensors)."""
+    for t, name in ((d_src_ptrs, "d_src_ptrs"), (d_bytes, "d_bytes"), (d_dst_ptrs, "d_dst_ptrs")):
+        _require_u64_desc(t, name, n_regions)
+    _require_crc(d_scan, "d_scan", n_regions)
+    _check(load().gpuar_hip_sparse_pack(d_src_ptrs.data_ptr(), d_bytes.data_ptr(), d_scan.data_ptr(), d_dst_ptrs.data_ptr(), n_regions,
+                                        _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_pack")
+
+
+def sparse_unpack(d_rec_ptrs, d_rec_bytes, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d_status=None):
+    """Rebuild n_regions packets of d_bytes[r] <= 8192 bytes at d_dst_ptrs[r] (16-byte aligned) from their records of d_rec_bytes[r]
+    bytes at d_rec_ptrs[r] (4-byte aligned) (gpuar_hip_sparse_unpack; the four descriptors are 64-bit CUDA tensors).  A record that
+    is not valid is STATUS_BAD_PACKET in the status word."""
+    for t, name in ((d_rec_ptrs, "d_rec_ptrs"), (d_rec_bytes, "d_rec_bytes"), (d_dst_ptrs, "d_dst_ptrs"), (d_bytes, "d_bytes")):
+        _require_u64_desc(t, name, n_regions)
+    _check(load().gpuar_hip_sparse_unpack(d_rec_ptrs.data_ptr(), d_rec_bytes.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions,
+                                          _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_unpack")
 
 
 def status() -> int:

@@ -431,6 +431,70 @@ int gpuar_hip_survey_delta_host(const uint8_t *in, size_t n_bytes, uint32_t widt
  * per packet: a tie goes to no filter, and so does n_packets = 0), else no filter at wp.  Returns 1 (the filter) or 0 and writes the width to *width. */
 int gpuar_hip_choose_filter(const uint64_t plain[4], const uint64_t filtered[4], uint64_t n_packets, uint32_t *width);
 
+/* ------------------------------------------------------------------------
+ * Sparse packets: a packet that is one byte value almost everywhere, kept as that byte and a list of exceptions instead of being
+ * coded (gpuar_amd/csrc/sparse.h: one integer definition for the host and the kernels).  The codec cannot code
+ * 8192 equal bytes below 210 bytes; their record here is 4.
+ *     scan  A packet of n bytes (1 .. 8192) has a majority byte f iff 2 count(f) > n; then scan = (k << 8) | f with
+ *           k = n - count(f), else scan = GPUAR_SPARSE_NONE.
+ *     record, little-endian, at a 4-byte-aligned address:
+ *           u8 fill | u8 0 | u16 k | u16 pos[k] | u8 val[k] | zero bytes up to a multiple of 4
+ *           pos strictly ascending and < n, val[i] the byte at pos[i] and != fill; gpuar_hip_sparse_len(k) = (4 + 3 k + 3) & ~3
+ *           bytes, the pad bytes included: a packet has exactly one record.
+ *     A record of rec_bytes for a packet of n bytes is valid iff rec_bytes >= 4, byte 1 is 0, 2 k < n,
+ *           gpuar_hip_sparse_len(k) <= rec_bytes, the positions are strictly ascending and < n and no val[i] equals the fill.
+ *
+ * Host-side checks as for gpuar_hip_estimate and gpuar_hip_move_packets, in the same order and before any device work.  Nothing is
+ * read beyond the 16-byte-aligned piece of memory that holds a packet's last byte, nor beyond a record's rec_bytes.
+ * Left out: the .gip container and the CLI have no sparse packets.
+ * ---------------------------------------------------------------------- */
+#define GPUAR_SPARSE_NONE 0xFFFFFFFFu
+
+/* Host only, pure: the bytes of a record with k exceptions. */
+uint32_t gpuar_hip_sparse_len(uint32_t k);
+
+/* Host only, pure: what to keep a packet of ulen bytes as, from its scan word and its estimate: 0 coded, 1 raw, 2 sparse.  With
+ * s = gpuar_hip_sparse_len(scan >> 8) (infinite for GPUAR_SPARSE_NONE) and raw_ok = stored_on && est >= 4 + ulen:  2 iff
+ * s + 1 < est && (!raw_ok || s < ulen), else 1 iff raw_ok, else 0.  The + 1 is the estimate's resolution; a tie with raw goes to raw. */
+int gpuar_hip_sparse_rule(uint32_t scan, uint32_t est, uint32_t ulen, int stored_on);
+
+/* d_scan[p] for the gpuar_hip_packet_count(n_bytes) packets of the n_bytes at d_in: arguments and checks of gpuar_hip_estimate. */
+int gpuar_hip_sparse_scan(const uint8_t *d_in, size_t n_bytes, uint32_t *d_scan, void *stream);
+
+/* The same for a batch: arguments and checks of gpuar_hip_estimate_batch.  A packet whose descriptor is unusable is
+ * GPUAR_STATUS_BAD_BATCH in d_status and its d_scan[p] is left untouched. */
+int gpuar_hip_sparse_scan_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                                size_t n_buffers, size_t n_packets, uint32_t *d_scan, uint32_t *d_status, void *stream);
+
+/* Host only: the same values for host memory, from the same definition -- no device is touched. */
+int gpuar_hip_sparse_scan_host(const uint8_t *in, size_t n_bytes, uint32_t *scan);
+
+/* Writes the records of n_regions packets: region r is the d_bytes[r] (1 .. 8192) bytes at d_src_ptrs[r] (16-byte aligned) with
+ * the scan word d_scan[r]; its record, exactly gpuar_hip_sparse_len(d_scan[r] >> 8) bytes, goes to d_dst_ptrs[r] (4-byte
+ * aligned) and nothing is written behind it.  The pointer and size arrays are in device memory and 8-byte aligned, d_scan
+ * 4-byte.  A region whose scan word is GPUAR_SPARSE_NONE or is not that of its bytes (another count of exceptions, or a fill
+ * that is no majority), with a misaligned pointer, or of 0 or more than 8192 bytes is GPUAR_STATUS_BAD_BATCH in d_status and
+ * nothing is written for it. */
+int gpuar_hip_sparse_pack(const uint8_t *const *d_src_ptrs, const uint64_t *d_bytes, const uint32_t *d_scan, uint8_t *const *d_dst_ptrs,
+                          size_t n_regions, uint32_t *d_status, void *stream);
+
+/* Rebuilds n_regions packets from their records: region r is the record of d_rec_bytes[r] bytes at d_rec_ptrs[r] (4-byte
+ * aligned); its packet of d_bytes[r] (1 .. 8192) bytes goes to d_dst_ptrs[r] (16-byte aligned).  The four arrays are in device
+ * memory and 8-byte aligned.  A record that is not valid is GPUAR_STATUS_BAD_PACKET in d_status: what the packet's own
+ * d_bytes[r] bytes then hold is unspecified, nothing outside them is written and nothing is read beyond the record.  A
+ * misaligned pointer or a packet of 0 or more than 8192 bytes is GPUAR_STATUS_BAD_BATCH and the region is skipped. */
+int gpuar_hip_sparse_unpack(const uint8_t *const *d_rec_ptrs, const uint64_t *d_rec_bytes, uint8_t *const *d_dst_ptrs,
+                            const uint64_t *d_bytes, size_t n_regions, uint32_t *d_status, void *stream);
+
+/* Host only: the record of the packet in[0 .. n_bytes) (1 .. 8192 bytes) into rec[0 .. rec_room), its length into *rec_len.
+ * GPUAR_ERR_ARGUMENT (nothing written) for a null pointer, another n_bytes, a packet without a majority byte, or a record
+ * longer than rec_room. */
+int gpuar_hip_sparse_pack_host(const uint8_t *in, size_t n_bytes, uint8_t *rec, size_t rec_room, size_t *rec_len);
+
+/* Host only: the packet out[0 .. n_bytes) from the record rec[0 .. rec_bytes).  GPUAR_ERR_ARGUMENT for a null pointer, another
+ * n_bytes, or a record that is not valid (out[0 .. n_bytes) is then unspecified; nothing is read beyond rec_bytes). */
+int gpuar_hip_sparse_unpack_host(const uint8_t *rec, size_t rec_bytes, uint8_t *out, size_t n_bytes);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
