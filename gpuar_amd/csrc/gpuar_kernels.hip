@@ -14,6 +14,8 @@
 //    window with carries, predicated dword stores) and a COURIER that carries the coder's reciprocals from memory into
 //    LDS a phase ahead, so that no working role issues a scalar load.  The roles work one phase (8 symbols) apart and
 //    hand a phase on in place through a three-slot LDS ring, one s_barrier per phase;
+//  * encode_kernel_t16 (throughput, what gpuar_hip_encode launches for large inputs): the same roles with the tree dealt 2 + 5
+//    and the path operands of depths 4-7 read from a 256-byte table in LDS, one 16-byte read per symbol (lane_codec.h, PickTable);
 //  * encode_small_kernel (latency): the same integers cut finer for inputs that cannot fill the chip -- four tree
 //    roles, an interval role, a sink role and a courier, seven wavefronts per 64 packets, phases of 16 symbols;
 //  * decode_*_kernel: one wavefront per 64 packets; the symbol search reads two 16-byte subtree records per symbol
@@ -202,13 +204,14 @@ __device__ __forceinline__ uint32_t byte_tag(uint32_t word, uint32_t kByte) {   
 // every touch of a line is a fetch from memory (rocprofv3 FETCH_SIZE: 3.3x the input with 16-byte
 // pieces and two modelers reading, 1.2-1.8x with 64-byte pieces, 1.01x now that one wavefront reads
 // and takes the whole 128-byte line at a time).
-template <bool kBatch = false>
+// (Model: which depths it walks -- TopModeler<7>, or encode_kernel_t16's TableTopModeler<7>)
+template <bool kBatch = false, typename Model = TopModeler<7>>
 __device__ __forceinline__ void run_top(EncodeLds &lds, const uint8_t *in, uint32_t lane, uint32_t len,
                                         uint32_t len_min, uint32_t n_phases, uint32_t whole_max = 0) {
     constexpr uint32_t kChunkPhases = 8;                       // phases per fetch
     constexpr uint32_t kChunk = kChunkPhases * kPhase;         // 64 symbols = 64 bytes = 4 x 16-byte loads
     constexpr uint32_t kPieces = kChunk / 16u;
-    TopModeler<7> model;
+    Model model;
     uint32_t k = 0, slot = 0;
     {
         const uint32_t first = len ? load16_guarded(in, len).x & 0xFFu : 0u;
@@ -355,9 +358,12 @@ __device__ __forceinline__ void run_top(EncodeLds &lds, const uint8_t *in, uint3
 // The low modeler: one phase behind the top one; input bytes and the top modeler's parts come through LDS, the
 // sums go back to the same slot.  The last symbol of a phase does not know its successor yet (the top modeler is
 // writing it in this very phase), so the node of a phase's first symbol is fetched when the phase begins.
-__device__ __forceinline__ void run_low(EncodeLds &lds, uint32_t lane, uint32_t len, uint32_t len_min, uint32_t n_phases) {
-    LowModeler<7> model;
-    model.open(lds.tree, 2u * lane_column(lane), 0u);          // (the prefetch for symbol 0 is repeated below: harmless)
+// (Model: LowModeler<7>, or encode_kernel_t16's TableLowModeler<7> with `rows`, its pick table in LDS)
+template <typename Model = LowModeler<7>>
+__device__ __forceinline__ void run_low(EncodeLds &lds, uint32_t lane, uint32_t len, uint32_t len_min, uint32_t n_phases,
+                                        const uint8_t *rows = nullptr) {
+    Model model;
+    model.open(lds.tree, 2u * lane_column(lane), 0u, rows);    // (the prefetch for symbol 0 is repeated below: harmless)
     lds_barrier();                                             // phase 0: the top modeler's first
     uint32_t slot = 0, k = 0;
     const uint32_t whole_phases = len_min / kPhase < n_phases ? len_min / kPhase : n_phases;    // (two loops: see the coder's)
@@ -542,6 +548,134 @@ encode_kernel(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict_
             coder.finish(len, overflowed);
             if (overflowed) atomicOr(status, GPUAR_STATUS_SLOT_OVERFLOW);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// encode_kernel_t16: encode_kernel with the TABLE WALK (lane_codec.h, PickTable).  The same four roles by SIMD,
+// ring, barriers, ticket and coder.  The low modeler takes the path operands of depths 4-7 from a 256-byte table in LDS -- one
+// 16-byte read per symbol, its address one bit-field extract of the row tag the low modeler forms anyway -- where encode_kernel
+// shifts and masks once per level; with the levels that cheap the tree is dealt 2 + 5 (top: depths 1-2, depth 0 and the
+// x == 255 term; low: depths 3-7) and the low modeler issues first.  39 936 + 256 bytes of LDS: still four workgroups per CU.
+// Same slots, byte for byte.  What gpuar_hip_encode launches above kSmallGroups groups; encode_kernel stays the batch kernels'
+// twin (GPUAR_MODE_THROUGHPUT).
+// ---------------------------------------------------------------------------
+struct alignas(16) EncodeTableLds {
+    EncodeLds ring;
+    uint32_t picks[16][4];                     // PickTable::row, written once per workgroup before the roles start
+};
+static_assert(sizeof(EncodeTableLds) <= 40960, "four workgroups per CU");
+// Issue priorities (see kPrioTop): the role with the most LDS levels goes first -- here the LOW modeler, five levels to the top
+// one's two (measured both ways, DESIGN.md 4.2: low first 17.31 ms, top first 18.39 on uniform 8 GiB); the coder stays last.
+constexpr int kPrioTableLow = 3, kPrioTableTop = 2;
+
+__global__ void __launch_bounds__(4 * kLanes)
+encode_kernel_t16(const uint8_t *__restrict__ src, size_t size, uint8_t *__restrict__ dst, uint32_t n_packets, uint32_t *__restrict__ status) {
+    __shared__ EncodeTableLds lds_t;
+    EncodeLds &lds = lds_t.ring;
+
+    const size_t group = xcd_contiguous_group(blockIdx.x, gridDim.x);
+    if (group * kLanes >= n_packets) return;                 // grid padding: the whole workgroup, before any barrier
+    const uint32_t lane = threadIdx.x & 63u;
+    // roles by SIMD through the CU's ticket: see encode_kernel
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));        // HW_ID
+    const uint32_t simd = (hw >> 4) & 3u;
+    uint32_t *hello = &lds.sums[0][0][0];                      // (the ring is not in use yet)
+    if (lane == 0) hello[wave] = simd;
+    if (threadIdx.x == 0) {
+        const uint32_t xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11));   // XCC_ID
+        hello[4] = atomicAdd(&g_cu_ticket[((xcc & 7u) << 8) | ((hw >> 8) & 0xFFu)], 1u);
+    }
+    if (wave == 3u) {
+        // the pick table, a dword per lane, by a wavefront that has nothing else to do here: row = x & 15, column = depth - 4,
+        // entry = bit 7 - depth of x | the same bit of x + 1 << 16 (PickTable, lane_codec.h)
+        const uint32_t r = lane >> 2, bit = 3u - (lane & 3u);
+        lds_t.picks[r][lane & 3u] = ((r >> bit) & 1u) | ((((r + 1u) >> bit) & 1u) << 16);
+    }
+    __syncthreads();
+    const uint32_t seen = (1u << hello[0]) | (1u << hello[1]) | (1u << hello[2]) | (1u << hello[3]);
+    const uint32_t by_simd = (simd - hello[4] - 1u) & 3u;
+    const uint32_t role = __builtin_amdgcn_readfirstlane(seen == 0xFu ? by_simd : wave);   // 3 = idle
+    __syncthreads();
+    const size_t packet = group * kLanes + lane;
+    const bool live = packet < n_packets;
+    const size_t start = packet * kPacket;
+    const uint32_t len = live ? static_cast<uint32_t>(size - start < kPacket ? size - start : kPacket) : 0u;
+    const uint32_t len_max = wave_max(len);
+    const uint32_t len_min = wave_max(~len) ^ 0xFFFFFFFFu;
+    const uint32_t n_phases = (len_max + kPhase - 1) / kPhase;
+    const uint8_t *in = src + (live ? start : 0);
+
+    // every role meets n_phases + 2 barriers, as in encode_kernel
+    if (role == 0) {
+        __builtin_amdgcn_s_setprio(kPrioTableTop);
+        run_top<false, TableTopModeler<7>>(lds, in, lane, len, len_min, n_phases);
+    } else if (role == 1) {
+        __builtin_amdgcn_s_setprio(kPrioTableLow);
+        run_low<TableLowModeler<7>>(lds, lane, len, len_min, n_phases, reinterpret_cast<const uint8_t *>(lds_t.picks));
+    } else if (role == 3) {
+        // the courier of the coder's reciprocals (encode_kernel)
+        uint32_t *courier = reinterpret_cast<uint32_t *>(lds.tree + 255u * 128u);
+        const uint32_t *table = reinterpret_cast<const uint32_t *>(g_recip.r);
+        const uint32_t lane16 = lane & 15u;
+        clock_sample(0u, group, lane, 0u);
+        uint32_t carried = table[lane16];                      // the pairs of phase 0
+        for (uint32_t k = 0; k < n_phases + 2u; ++k) {
+            if (lane < 16u) courier[((k + 1u) & 1u) * 16u + lane16] = carried;
+            const uint32_t next_phase = k < n_phases ? k : 0u;
+            carried = table[next_phase * 16u + lane16];
+            lds_barrier();
+        }
+        clock_sample(0u, group, lane, 1u);
+    } else {
+        // the coder, statement for statement encode_kernel's
+        CarryCoderLane coder;
+        coder_open(coder, dst, group, lane);
+        uint32_t slot = 0, k = 0;
+        const uint32_t whole_phases = len_min / kPhase < n_phases ? len_min / kPhase : n_phases;    // phases every lane owns completely
+        for (; k < whole_phases; ++k) {                      // the symbols of phase k, during phase k + 2
+            const uint32_t *in_ring = &lds.sums[slot][0][lane];
+            {
+                uint32_t cums[kPhase];
+#pragma unroll
+                for (uint32_t j = 0; j < kPhase; ++j) cums[j] = in_ring[j * kLanes];
+                Recip rc[kPhase];
+                {
+                    const uint4 *slot = reinterpret_cast<const uint4 *>(lds.tree + 255u * 128u + (k & 1u) * 64u);
+#pragma unroll
+                    for (uint32_t q = 0; q < 4; ++q) {
+                        const uint4 v = slot[q];
+                        rc[2 * q] = {v.x, v.y}, rc[2 * q + 1] = {v.z, v.w};
+                    }
+                }
+                CarryCoderLane::Ahead next = coder.ahead(cums[0], rc[0]);
+#pragma unroll
+                for (uint32_t j = 0; j < kPhase; ++j) {
+                    const CarryCoderLane::Narrowed now = coder.narrow(next);
+                    if (j + 1u < kPhase) next = coder.ahead(cums[j + 1u], rc[j + 1u]);
+                    coder.settle(now);
+                }
+            }
+            slot = next_slot(slot);
+            lds_barrier();
+        }
+        for (; k < n_phases; ++k) {                          // the phases that hold a ragged tail
+            const uint32_t base = k * kPhase;
+            const uint32_t *in_ring = &lds.sums[slot][0][lane];
+            {
+#pragma unroll 1
+                for (uint32_t j = 0; j < kPhase; ++j) {
+                    const uint32_t i = base + j;
+                    if (i >= len_max) break;
+                    const Recip r = g_recip.r[i];
+                    if (i < len) coder.step(in_ring[j * kLanes], r);
+                }
+            }
+            slot = next_slot(slot);
+            lds_barrier();
+        }
+        finish_lane(coder, live, len, status);
     }
 }
 
@@ -3684,7 +3818,7 @@ extern "C" {
 size_t gpuar_hip_packet_count(size_t n_bytes) { return (n_bytes + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES; }
 
 int gpuar_hip_encode_mode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots, uint32_t *d_status, void *stream, int mode) {
-    if (mode != GPUAR_MODE_AUTO && mode != GPUAR_MODE_THROUGHPUT && mode != GPUAR_MODE_LATENCY) return GPUAR_ERR_ARGUMENT;
+    if (mode != GPUAR_MODE_AUTO && mode != GPUAR_MODE_THROUGHPUT && mode != GPUAR_MODE_LATENCY && mode != GPUAR_MODE_TABLE) return GPUAR_ERR_ARGUMENT;
     if (n_bytes == 0) return GPUAR_OK;
     if (!d_in || !d_slots) return GPUAR_ERR_ARGUMENT;
     if (!aligned16(d_in) || !aligned16(d_slots) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
@@ -3703,8 +3837,14 @@ int gpuar_hip_encode_mode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots,
         return check_launch();
     }
     const uint32_t blocks = (groups + 7u) & ~7u;              // see xcd_contiguous_group
-    gpuar::encode_kernel<<<blocks, 4 * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
-        d_in, n_bytes, d_slots, static_cast<uint32_t>(n_packets), status);
+    // Above that switch AUTO takes the table walk (encode_kernel_t16: the same roles, seven vector instructions fewer per symbol);
+    // THROUGHPUT names encode_kernel, the batch kernels' twin, and TABLE the table walk at any size.
+    if (mode == GPUAR_MODE_THROUGHPUT)
+        gpuar::encode_kernel<<<blocks, 4 * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
+            d_in, n_bytes, d_slots, static_cast<uint32_t>(n_packets), status);
+    else
+        gpuar::encode_kernel_t16<<<blocks, 4 * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(
+            d_in, n_bytes, d_slots, static_cast<uint32_t>(n_packets), status);
     return check_launch();
 }
 

@@ -48,6 +48,8 @@
 // the 16-bit field of v that starts at bit (off & 31); (a << (s & 31)) + c -- one instruction each
 #define GPUAR_BFE16(v, off) ([](uint32_t v_, uint32_t o_) { uint32_t r_; asm("v_bfe_u32 %0, %1, %2, 16" : "=v"(r_) : "v"(v_), "v"(o_)); return r_; }((v), (off)))
 #define GPUAR_LSHL_ADD(a, s, c) ([](uint32_t a_, uint32_t s_, uint32_t c_) { uint32_t r_; asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(r_) : "v"(a_), "v"(s_), "v"(c_)); return r_; }((a), (s), (c)))
+// the 8-bit field of v that starts at the constant bit `off`: one instruction (left to itself hipcc shifts and masks)
+#define GPUAR_BFE8_AT(v, off) ([](uint32_t v_) { uint32_t r_; asm("v_bfe_u32 %0, %1, %2, 8" : "=v"(r_) : "v"(v_), "n"(off)); return r_; }((v)))
 // x as a value the compiler cannot see through (keeps it from re-associating the expression x feeds)
 #define GPUAR_OPAQUE_V(x) ([](uint32_t x_) { asm("" : "+v"(x_)); return x_; }((x)))
 // the load that produces q is issued here, before any later store (no wait is implied)
@@ -70,6 +72,7 @@
 #define GPUAR_ALIGNBIT(hi, lo, s) static_cast<uint32_t>(((static_cast<uint64_t>(hi) << 32) | (lo)) >> ((s) & 31u))
 #define GPUAR_BFE16(v, off) (((v) >> ((off) & 31u)) & 0xFFFFu)
 #define GPUAR_LSHL_ADD(a, s, c) (((a) << ((s) & 31u)) + (c))
+#define GPUAR_BFE8_AT(v, off) (((v) >> (off)) & 0xFFu)
 #define GPUAR_PIN_ORDER(x) ((void)0)
 #define GPUAR_PIN_LOAD(q) ((void)0)
 #define GPUAR_OPAQUE_V(x) (x)
@@ -254,6 +257,25 @@ struct InorderModel {
     }
 };
 
+// The path operands of depths 4-7 as a TABLE (the throughput encoder's table walk).  What a level multiplies
+// its node by is pick = b(x) | b(x + 1) << 16, b = bit 7 - depth: a pure function of the symbol, and for depths 4-7 of its
+// low four bits alone -- the low four bits of x + 1 depend on x & 15 only, nothing carries in from above, and x = 255 wraps
+// to 0000, which is what the x == 255 term expects.  Sixteen rows of four ready-made words, 256 bytes: on the GPU one
+// conflict-free row of LDS (row r in banks 4r .. 4r + 3; lanes that want the same row are a broadcast), fetched by ONE
+// 16-byte read per symbol where the four levels shifted and masked four times.  Depths 0-3 cannot come from it: their bit
+// of x + 1 needs the carry out of the low bits.
+constexpr int kPickFirstDepth = 4;
+struct PickTable {
+    uint32_t row[16][4];                               // [x & 15][depth - 4]
+    constexpr PickTable() : row{} {
+        for (uint32_t r = 0; r < 16u; ++r)
+            for (uint32_t d = 0; d < 4u; ++d) row[r][d] = ((r >> (3u - d)) & 1u) | ((((r + 1u) >> (3u - d)) & 1u) << 16);
+    }
+};
+#if !defined(__HIP_DEVICE_COMPILE__)
+static const PickTable kPickTable = PickTable();
+#endif
+
 // One partial modeler owns depths [kFirst, kFirst + kDepths) of the tree (its
 // rows of the shared table are disjoint from the other's), optionally the
 // kHead register-resident depths (0, 1 or 2 of depths 0 and 1) and the x == 255 term (kTail), and
@@ -264,18 +286,28 @@ struct InorderModel {
 // for symbol i, and LDS operations of a wavefront complete in order, so a node
 // shared by both symbols is read with symbol i's increment applied.  The node
 // addresses travel with the prefetched values.
-template <uint32_t kRowShift, int kFirst, int kDepths, int kHead, bool kTail>
+// kTable: the LDS levels at depth >= 4 take their path operands from a PickTable (`rows`: its first byte -- LDS on the GPU,
+// kPickTable on the host), the symbol's row fetched one symbol ahead with its nodes; counts and sums are the same integers.
+template <uint32_t kRowShift, int kFirst, int kDepths, int kHead, bool kTail, bool kTable = false>
 struct PartialModeler {
     InorderModel<kRowShift> tree;
+    const uint8_t *rows;                    // kTable: the pick table (same pointer in every lane of a wavefront)
+    Quad picks;                             // kTable: the row of the NEXT symbol to account
     uint32_t root, half0, half1;            // kHead == 1, 2: depth 0; kHead == 2: depth 1 as well
     uint32_t halves;                        // kHead == 3: depth 1 ALONE in a register, both nodes packed: x < 128 | x >= 128 << 16
     uint32_t left[kDepths];                 // this part's nodes of the NEXT symbol to account
     uint16_t *where[kDepths];
 
     // table: first byte of the shared node table; lane_bits: this lane's byte offset inside a row
-    GPUAR_LANE void open(uint8_t *table, uint32_t lane_bits, uint32_t first_symbol) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    GPUAR_LANE void open(uint8_t *table, uint32_t lane_bits, uint32_t first_symbol, const uint8_t *pick_rows = nullptr) {
+#else
+    GPUAR_LANE void open(uint8_t *table, uint32_t lane_bits, uint32_t first_symbol,
+                         const uint8_t *pick_rows = reinterpret_cast<const uint8_t *>(kPickTable.row)) {
+#endif
         tree.table = table;
         tree.lane_bits = lane_bits;
+        rows = pick_rows;
         // initial counts, own rows only (the other part initialises its own)
 #pragma unroll 1
         for (uint32_t row = 0; row < 255u; ++row) {
@@ -299,6 +331,19 @@ struct PartialModeler {
             where[k] = tree.node(x_tag, kFirst + k);
             left[k] = *where[k];
         }
+        if (kTable) picks = load128(rows + row_offset(x_tag));
+    }
+
+    // Byte offset of a symbol's row of the pick table, (x & 15) * 16, out of its row tag.  On the GPU ONE bit-field extract:
+    // eight bits from bit kRowShift - 4 up are the symbol's low four bits with four zeros below them -- a kTable modeler's
+    // tags are x << kRowShift with NO lane bits in them (InorderModel::tag, the kernels' byte_tag).
+    GPUAR_LANE static uint32_t row_offset(uint32_t x_tag) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        static_assert(!kTable || kRowShift >= 4u, "the row offset is a bit field of the tag");
+        return GPUAR_BFE8_AT(x_tag, (kRowShift >= 4u ? kRowShift - 4u : 0u));
+#else
+        return ((x_tag >> kRowShift) & 15u) << 4;
+#endif
     }
 
     // The path bits of x (low half) and of x + 1 (high half) side by side, kShift bits up: from the symbol itself
@@ -334,6 +379,9 @@ struct PartialModeler {
         // in this part and in the one `onto` came from: the high half is empty and the total can be OR-ed in (two instructions
         // where shift, mask and multiply-add were three)
         if (kTail) acc = GPUAR_OR_WHERE_BIT(z, kShift + 24, total << 16, onto);
+        // the next symbol's row of the pick table: asked for first, so that it is back before that symbol's first node
+        Quad picks_ahead = picks;
+        if (kTable && kAhead) picks_ahead = load128(rows + row_offset(xn));
         if (kHead == 1 || kHead == 2) {
             const uint32_t pick0 = (z >> (kShift + 7)) & 0x10001u;
             acc = GPUAR_MAD24(root, pick0, acc);
@@ -361,7 +409,8 @@ struct PartialModeler {
         }
 #pragma unroll
         for (int k = 0; k < kDepths; ++k) {
-            const uint32_t pick = (z >> (kShift + 7 - (kFirst + k))) & 0x10001u;
+            const bool tabled = kTable && kFirst + k >= kPickFirstDepth;
+            const uint32_t pick = tabled ? picks.w[tabled ? kFirst + k - kPickFirstDepth : 0] : (z >> (kShift + 7 - (kFirst + k))) & 0x10001u;
             const uint32_t l = left[k];
             acc = GPUAR_MAD24(l, pick, acc);
             *where[k] = static_cast<uint16_t>(GPUAR_XOR1_ADD(pick, l));   // +1 where x goes left
@@ -370,6 +419,7 @@ struct PartialModeler {
                 left[k] = *where[k];
             }
         }
+        if (kTable && kAhead) picks = picks_ahead;
         if (kAhead) next_tag = xn;
         return acc;
     }
@@ -396,6 +446,14 @@ using TopModeler = PartialModeler<kRowShift, 1, GPUAR_TOP_DEPTHS, 0, false>;    
 #endif
 template <uint32_t kRowShift>
 using LowModeler = PartialModeler<kRowShift, 1 + GPUAR_TOP_DEPTHS, 7 - GPUAR_TOP_DEPTHS, 1, true>;        // depth 0 (register), the deepest ones and the x == 255 term
+// The table walk's split (encode_kernel_t16; the sweep: DESIGN.md 4.2): 2 + 5.  The top modeler walks depths 1-2 by shift and
+// mask and keeps depth 0 (register) and the x == 255 term; the low one walks depths 3-7, depth 3 by shift and mask, depths 4-7
+// with their path operands out of the pick table.
+constexpr int kTableTopDepths = 2;     // LDS-resident depths the table walk's top modeler takes (1 .. kTableTopDepths)
+template <uint32_t kRowShift>
+using TableTopModeler = PartialModeler<kRowShift, 1, kTableTopDepths, 1, true>;
+template <uint32_t kRowShift>
+using TableLowModeler = PartialModeler<kRowShift, 1 + kTableTopDepths, 7 - kTableTopDepths, 0, false, true>;
 // the last role of the latency kernel's four-way tree: depth 0 (register), depth 7 and the x == 255 term, whatever the split above
 template <uint32_t kRowShift>
 using DeepestModeler = PartialModeler<kRowShift, 7, 1, 1, true>;

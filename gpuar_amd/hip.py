@@ -42,7 +42,7 @@ EXPORTS = [
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
-MODE_ID = {"auto": 0, "throughput": 1, "latency": 2}     # GPUAR_MODE_*
+MODE_ID = {"auto": 0, "throughput": 1, "latency": 2, "table": 3}     # GPUAR_MODE_* ("table": encode() only, the batch encoders refuse it)
 
 _lib = None
 
@@ -194,12 +194,12 @@ def load() -> C.CDLL:
 
 
 def _mode_id(mode, env_var) -> int:
-    """GPUAR_MODE_* for a call: the caller's `mode` ("auto" | "throughput" | "latency"), else the environment variable
+    """GPUAR_MODE_* for a call: the caller's `mode` ("auto" | "throughput" | "latency" | "table"), else the environment variable
     that tests and tools use to pin the encode kernel (GPUAR_ENCODE_MODE; there is no decode mode) -- read HERE, in the
     Python shim, never inside the library --, else auto."""
     name = mode if mode is not None else os.environ.get(env_var, "auto")
     if name not in MODE_ID:
-        raise GpuarError(f"unknown kernel mode {name!r} (auto, throughput, latency)")
+        raise GpuarError(f"unknown kernel mode {name!r} (auto, throughput, latency, table)")
     return MODE_ID[name]
 
 
@@ -237,7 +237,7 @@ def _status_ptr(d_status):
 def encode(d_in, d_slots=None, stream=None, d_status=None, mode=None):
     """Encode the bytes of `d_in` into 8704-byte packet slots (garCompress layout).  `d_status`: this launch's
     own status word (a zeroed 1-element int32 CUDA tensor); None = the device's fallback word (status()).
-    `mode`: "auto" | "throughput" | "latency" (gpuar_hip_encode_mode); None = $GPUAR_ENCODE_MODE, else auto."""
+    `mode`: "auto" | "throughput" | "latency" | "table" (gpuar_hip_encode_mode); None = $GPUAR_ENCODE_MODE, else auto."""
     import torch
     _require_cuda_u8(d_in, "d_in")
     n = d_in.numel()

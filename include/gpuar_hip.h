@@ -122,14 +122,17 @@ int gpuar_hip_encode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots, uint
  *   GPUAR_MODE_LATENCY     a finer cut -- six working wavefronts (and a seventh that carries constants) per
  *                          64 packets -- with a shorter symbol step: faster while the launch cannot fill
  *                          the chip by itself;
+ *   GPUAR_MODE_TABLE       THROUGHPUT's cut with the table walk: the tree dealt 3 + 4 and the path operands of
+ *                          depths 4-7 read from a 256-byte table in LDS (encode_kernel_t16), at any size;
  *   GPUAR_MODE_AUTO        what gpuar_hip_encode does: LATENCY up to 32768 packets (256 MiB of input),
- *                          THROUGHPUT above -- right for a launch that has the chip to itself; a pipeline
+ *                          TABLE above -- right for a launch that has the chip to itself; a pipeline
  *                          that keeps several launches in flight names THROUGHPUT.
  * The choice is an argument, never an environment variable: this library reads no environment.
  * Any other `mode` is GPUAR_ERR_ARGUMENT. */
 #define GPUAR_MODE_AUTO        0
 #define GPUAR_MODE_THROUGHPUT  1
 #define GPUAR_MODE_LATENCY     2
+#define GPUAR_MODE_TABLE       3       /* gpuar_hip_encode_mode only: the batch encoders have no table walk */
 int gpuar_hip_encode_mode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots, uint32_t *d_status, void *stream, int mode);
 
 /* Decode n_packets slots at d_slots into d_out (n_packets*8192 bytes; the
