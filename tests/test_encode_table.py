@@ -3,7 +3,10 @@ tree depths 4-7 come from a 256-byte table instead of a shift and a mask per lev
 byte for byte:
 
   * CPU: the table itself against the shift-and-mask form for every symbol; the host build of the table-walk modelers
-    (tests/encode_table_emulation.cpp) against the modelers the host CLI runs today, the oracle and the golden streams;
+    (tests/encode_table_emulation.cpp) against the modelers the host CLI runs today, the oracle and the golden streams -- in
+    the three forms a lane of the kernel can be in: whole phases, the ragged form (a group that is not full, a packet's
+    tail) and the hand-off between them inside a packet, at every packet length, every shortest length of the wavefront
+    and on the adversarial packet families of tests/test_gpu_parity.py (tests/packet_families.py);
   * code object: the new kernel's resources and per-phase instruction counts, read out of the shipped library the way
     tests/test_codeobj_contract.py reads the pinned kernels';
   * GPU (-m gpu): slots through GPUAR_MODE_TABLE against GPUAR_MODE_THROUGHPUT and the oracle at the shapes where a table
@@ -16,6 +19,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import length_sweep as LS
+import packet_families as PF
 from test_codeobj_contract import VEC, code_object, phase_segments          # noqa: F401  (code_object: the fixture)
 from test_oracle_golden import REFV, case_input, md5
 
@@ -48,8 +53,11 @@ def emu():
     for name in ("emu_current_encode_slots", "emu_table_encode_slots"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [u8p, C.c_size_t, u8p]
-    lib.emu_table_encode_slots_phased.restype = C.c_int
-    lib.emu_table_encode_slots_phased.argtypes = [u8p, C.c_size_t, u8p, C.c_uint32]
+    for name in ("emu_table_encode_slots_phased", "emu_table_encode_slots_ragged"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [u8p, C.c_size_t, u8p, C.c_uint32]
+    lib.emu_table_encode_slots_handoff.restype = C.c_int
+    lib.emu_table_encode_slots_handoff.argtypes = [u8p, C.c_size_t, u8p, C.c_uint32, C.c_uint32]
     return lib
 
 
@@ -84,9 +92,10 @@ def slots_to_stream(slots, npk):
 
 @pytest.mark.parametrize("c", REFV, ids=lambda c: c["name"])
 def test_table_walk_on_the_host_gives_the_golden_streams(emu, port_oracle, c):
-    """The table-walk modelers chained with the existing coder, straight and in the kernel's phases (row tags, a lane's
-    column, the low modeler a phase behind): the slots of today's host modelers byte for byte, the oracle's stream, the
-    golden stream's length, packet lengths, md5 and -- where the bytes are kept -- the bytes."""
+    """The table-walk modelers chained with the existing coder, straight, in the kernel's whole phases (row tags, a lane's
+    column, the low modeler a phase behind) and in its ragged form (every symbol by the top modeler's symbol form and the low
+    one's prime_tag + step_last_tag: a lane of a group that is not full): the slots of today's host modelers byte for byte,
+    the oracle's stream, the golden stream's length, packet lengths, md5 and -- where the bytes are kept -- the bytes."""
     data = np.ascontiguousarray(case_input(c))
     want, npk, ov = emu_slots(emu.emu_current_encode_slots, data)
     got, _, ov2 = emu_slots(emu.emu_table_encode_slots, data)
@@ -94,6 +103,9 @@ def test_table_walk_on_the_host_gives_the_golden_streams(emu, port_oracle, c):
     for lane in (0, 37):
         phased, _, ov3 = emu_slots(emu.emu_table_encode_slots_phased, data, lane)
         assert ov3 == 0 and np.array_equal(phased, want), lane
+    for lane in (0, 63):
+        ragged, _, ov4 = emu_slots(emu.emu_table_encode_slots_ragged, data, lane)
+        assert ov4 == 0 and np.array_equal(ragged, want), lane
     stream = slots_to_stream(got, npk)
     assert np.array_equal(stream, port_oracle.encode_stream(data))
     assert stream.size == c["stream_len"] and md5(stream.tobytes()) == c["stream_md5"]
@@ -116,6 +128,79 @@ def test_table_walk_on_the_host_on_walks_and_runs(emu, port_oracle):
     got, _, ov2 = emu_slots(emu.emu_table_encode_slots_phased, data, 5)
     assert ov == ov2 == 0 and np.array_equal(got, want)
     assert np.array_equal(slots_to_stream(got, npk), port_oracle.encode_stream(data))
+
+
+def mixed_bytes(n, seed):
+    """Bytes of changing statistics: uniform, a small alphabet, long runs -- a packet is 8192 of them."""
+    rng = np.random.default_rng(seed)
+    data = rng.integers(0, 256, n, dtype=np.uint8)
+    third = n // 3
+    data[third:2 * third] = rng.choice(np.array([0x0F, 0x10, 0x7F, 0x80, 0xEF, 0xF0, 0xFF, 0x00], dtype=np.uint8), third)
+    data[2 * third:] = np.repeat(rng.integers(0, 256, (n - 2 * third) // 40 + 1, dtype=np.uint8), 40)[:n - 2 * third]
+    return data
+
+
+def test_whole_phase_and_ragged_forms_at_every_packet_length(emu, port_oracle):
+    """The kernel's two forms on all 8192 packets of tests/length_sweep.py (one per length 1 ... 8192, six source models in
+    turn), each packet a call of its own with the lane's column rotating through all 64: the whole-phase form (whose last
+    phase is a partial one for seven lengths in eight) and the ragged form give the slot of today's host modelers, which is the
+    oracle's packet."""
+    pkts = LS.packets()
+    slot = np.zeros(SLOT, dtype=np.uint8)
+    for i, pkt in enumerate(pkts):
+        want, _, ov = emu_slots(emu.emu_current_encode_slots, pkt)
+        ref = port_oracle.encode_stream(pkt)
+        assert ov == 0 and np.array_equal(want[:ref.size], ref) and not want[ref.size:].any(), pkt.size
+        for fn, lane in ((emu.emu_table_encode_slots_phased, i % 64), (emu.emu_table_encode_slots_ragged, (37 * i + 11) % 64)):
+            slot[:] = 0
+            assert fn(pkt.ctypes.data_as(u8p), pkt.size, slot.ctypes.data_as(u8p), lane) == 0
+            assert np.array_equal(slot, want), (pkt.size, lane, fn.__name__)
+
+
+@pytest.mark.parametrize("kind", ["mixed", "carry"])
+def test_hand_off_from_the_whole_phase_form_at_every_shortest_length(emu, port_oracle, kind):
+    """One 8192-byte packet as a lane of a full group whose shortest lane holds len_min bytes, for every len_min in 0 ... 8192:
+    the top modeler goes over to its symbol form after (len_min / 64) * 8 phases on the nodes its last tag-form step fetched,
+    the low modeler to prime_tag + step_last_tag after len_min / 8 phases -- for most len_min the top is in symbol form while
+    the low one is still in tag form.  Wherever the hand-offs fall, the slot is that of today's host modelers and the oracle's.
+    `carry`: packet 0 of the parity suite's keep-carrying family (0x7F / 0x80 either side of the interval's midpoint)."""
+    pkt = np.ascontiguousarray(mixed_bytes(PACKET, 77) if kind == "mixed" else PF.keep_carrying(2)[:PACKET])
+    assert pkt.size == PACKET
+    want, _, ov = emu_slots(emu.emu_current_encode_slots, pkt)
+    ref = port_oracle.encode_stream(pkt)
+    assert ov == 0 and np.array_equal(want[:ref.size], ref) and not want[ref.size:].any()
+    slot = np.zeros(SLOT, dtype=np.uint8)
+    for len_min in range(PACKET + 1):
+        slot[:] = 0
+        assert emu.emu_table_encode_slots_handoff(pkt.ctypes.data_as(u8p), pkt.size, slot.ctypes.data_as(u8p), len_min % 64, len_min) == 0
+        assert np.array_equal(slot, want), len_min
+
+
+FAMILIES = {
+    "keep_carrying": lambda: PF.keep_carrying(64),
+    "drain_the_window": lambda: PF.drain_the_window(64),
+    "ten_source_models_7": lambda: PF.ten_source_models(7, 64),
+    "ten_source_models_8": lambda: PF.ten_source_models(8, 64),
+}
+HANDOFF_LEN_MINS = (1, 8, 63, 64, 71, 4097, 8128, 8191, 8192)     # around a phase, a chunk, the middle, the last chunk, the end
+
+
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_all_three_forms_on_the_adversarial_packet_families(emu, port_oracle, family):
+    """The first 64 packets of each adversarial family of tests/test_gpu_parity.py (the coder's carry path; models fed bytes
+    they have never seen; ten source models with intervals of width 1-3; the two cut families end in a short packet) through
+    the whole-phase form, the ragged form and the hand-off at shortest lengths around every boundary the kernel has: the slots
+    of today's host modelers, the oracle's stream."""
+    data = np.ascontiguousarray(FAMILIES[family]())
+    want, npk, ov = emu_slots(emu.emu_current_encode_slots, data)
+    assert ov == 0 and npk == 64
+    assert np.array_equal(slots_to_stream(want, npk), port_oracle.encode_stream(data))
+    for lane, fn in ((21, emu.emu_table_encode_slots_phased), (42, emu.emu_table_encode_slots_ragged)):
+        got, _, ov2 = emu_slots(fn, data, lane)
+        assert ov2 == 0 and np.array_equal(got, want), fn.__name__
+    for k, len_min in enumerate(HANDOFF_LEN_MINS):
+        got, _, ov3 = emu_slots(emu.emu_table_encode_slots_handoff, data, (7 * k + 3) % 64, len_min)
+        assert ov3 == 0 and np.array_equal(got, want), len_min
 
 
 # -------------------------------------------------------------------------------------------------------- code object
@@ -208,16 +293,6 @@ def check_against_throughput_and_oracle(H, oracle, data):
 
 
 LAST_LENGTHS = (1, 7, 8, 9, 15, 16, 17, 8191, 8192)
-
-
-def mixed_bytes(n, seed):
-    """Bytes of changing statistics: uniform, a small alphabet, long runs -- a packet is 8192 of them."""
-    rng = np.random.default_rng(seed)
-    data = rng.integers(0, 256, n, dtype=np.uint8)
-    third = n // 3
-    data[third:2 * third] = rng.choice(np.array([0x0F, 0x10, 0x7F, 0x80, 0xEF, 0xF0, 0xFF, 0x00], dtype=np.uint8), third)
-    data[2 * third:] = np.repeat(rng.integers(0, 256, (n - 2 * third) // 40 + 1, dtype=np.uint8), 40)[:n - 2 * third]
-    return data
 
 
 @pytest.mark.gpu

@@ -13,7 +13,8 @@ the device; one copy of the verdicts per test.  Every status word is read and co
 calls without a word report into the fallback word, which must be 0 at the end of each test.
 
 A. Weakest alignment.  All pointer arguments weak at once, then each in turn while the others are 4096-aligned, so a failure
-   names the argument.  Codec (130 packets + 4097 bytes of synth text and uniform: encode in both modes, decode, compact,
+   names the argument.  Codec (130 packets + 4097 bytes of synth text and uniform: encode in its three modes -- throughput, latency and table,
+   the table-walk kernel that auto takes for large inputs --, decode, compact,
    decode_stream with the stream at 4 and at 12 mod 16, the reference-named executors), the batch codec over the lengths of
    length_sweep's layout "last_wave_1_live" (inputs from batch_sweep.scattered_inputs, outputs 16 bytes apart, permuted, none
    32-aligned, the stream at skew 4, descriptor arrays 8- but not 16-aligned), CRC-32 (9 packets + 77 bytes; batch pointers
@@ -34,7 +35,8 @@ C. One buffer of 2^32 + 3 * 65536 + 4097 + 5 bytes (packet 524288 starts at byte
    *_host functions on three windows ([0, 128 KiB), 128 KiB either side of 2^32, the last group with the tail); over the
    whole buffer merge(split(x)) == x and the canary behind n holds.  The codec is not repeated (the 5 GiB tests cover it).
 
-Time, pytest --durations=0 on an MI355X, the module alone: 24 passed in 3.8 s (605 placed launches in parts A and B).
+Time, pytest --durations=0 on an MI355X, the module alone: 24 passed in 3.8 s (605 placed launches in parts A and B; the
+table-mode encode cases added since make it 625).
     0.50 s  setup of test_codec_at_the_weakest_alignment[text] (the arena, the reference encoder on 2 x 1 MiB)
     0.39 s  test_filters_past_4gib[delta-8] (the first of part C: generates and fills the 4 GiB buffer)
     0.29 s  test_codec_at_the_weakest_alignment[text] (the first launches of the process)
@@ -328,7 +330,7 @@ def _codec_cases(H, oracle, kind):
         return Arg("d_out", npk * PACKET, 16, want=out_img)
 
     cases = []
-    for mode in ("throughput", "latency"):
+    for mode in ("throughput", "latency", "table"):
         cases.append(Case(f"encode {mode}, {kind}", [d_in(), d_slots_out(), _status_arg()],
                           lambda v, mode=mode: H.encode(v["d_in"], v["d_slots"], d_status=_i32(v["d_status"]), mode=mode),
                           lines=in_lines("d_in") + slot_lines("d_slots")))

@@ -5,7 +5,8 @@
 2. Compaction: each buffer's subrange of compact() over the batch is its single-buffer stream; batch.gip(b) is its file.
 3. Round trips through both batch decoders into views of one canary-filled arena.
 4. The room check: too little room, or a damaged ulen, is BAD_PACKET and writes nothing past the room.
-5. Bad descriptors: BAD_BATCH, that packet's slot untouched, the other buffers right.
+5. Bad descriptors: BAD_BATCH, that packet's slot untouched, the other buffers right.  The table mode, which only the
+   single-buffer encoder has, is refused as an argument before any launch.
 6. Scale: over 2 GiB in ~2000 buffers (offsets past 4 GiB, several scan tiles).
 7. Two batches on two streams with status words of their own.
 Fixed seeds throughout.
@@ -324,6 +325,43 @@ def test_bad_descriptors(H, mode):
         w = want[j * SLOT:(j + 1) * SLOT]
         clen = int(w[0]) | (int(w[1]) << 8)
         assert torch.equal(slots[(fp[1] + j) * SLOT:(fp[1] + j) * SLOT + clen], w[:clen])
+
+
+def test_batch_encoders_refuse_the_table_mode(H):
+    """GPUAR_MODE_TABLE is gpuar_hip_encode_mode's alone (include/gpuar_hip.h): gpuar_hip_encode_batch returns
+    GPUAR_ERR_ARGUMENT for it before it looks at anything else -- through the argument and through GPUAR_ENCODE_MODE, which
+    tests/test_gpu_parity.py sets to "table" around its single-buffer cases --, nothing is launched: the slots and the
+    caller's status word keep what they held, and the fallback word stays 0."""
+    import os
+    sizes = [10000, PACKET, 3 * PACKET + 5]
+    a = Arena(sizes, seed=17)
+    d_ptrs, d_bytes, d_fp, fp, npk = _desc(H, a.views())
+    slots = torch.full((npk * SLOT,), 0x5A, dtype=torch.uint8, device="cuda")
+    st = torch.full((1,), 0x1234, dtype=torch.int32, device="cuda")
+    assert H.status() == 0
+    with pytest.raises(H.GpuarError, match=r"gpuar_hip_encode_batch.*code -2\)"):
+        H.encode_batch(d_ptrs, d_bytes, d_fp, len(sizes), npk, d_slots=slots, d_status=st, mode="table")
+    old = os.environ.get("GPUAR_ENCODE_MODE")
+    os.environ["GPUAR_ENCODE_MODE"] = "table"
+    try:
+        with pytest.raises(H.GpuarError, match=r"gpuar_hip_encode_batch.*code -2\)"):
+            H.encode_batch(d_ptrs, d_bytes, d_fp, len(sizes), npk, d_slots=slots, d_status=st)
+    finally:
+        if old is None:
+            del os.environ["GPUAR_ENCODE_MODE"]
+        else:
+            os.environ["GPUAR_ENCODE_MODE"] = old
+    assert H.load().gpuar_hip_encode_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_fp.data_ptr(), len(sizes), npk, slots.data_ptr(),
+                                           st.data_ptr(), None, 3) == -2
+    torch.cuda.synchronize()
+    assert int(st.item()) == 0x1234 and bool((slots == 0x5A).all()) and a.gaps_intact()
+    assert H.status() == 0
+    # the same descriptors are fine in a mode the batch encoder has
+    st.zero_()
+    H.encode_batch(d_ptrs, d_bytes, d_fp, len(sizes), npk, d_slots=slots, d_status=st, mode="throughput")
+    torch.cuda.synchronize()
+    assert int(st.item()) == 0
+    _check_slots_equal(H, a.views(), slots, fp, "table")
 
 
 def test_scale_past_4_gib_of_stream_offsets(H):

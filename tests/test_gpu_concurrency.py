@@ -3,7 +3,7 @@ launch ORs its flags into its own status word and no other; compaction may run c
 library is usable from one host thread per GPU; the per-device state it keeps -- the fallback status word, the encoder's
 per-CU arrival counters, the clock-sample table -- affects no result).
 
-This module covers the coders and what was built with them: encode (throughput, latency, auto), decode, decode_stream,
+This module covers the coders and what was built with them: encode (throughput, latency, table, auto), decode, decode_stream,
 compact, crc32 / verify_crc32, generate, encode_batch / decode_batch / decode_stream_batch / crc32_batch,
 batch.compress(checksum=True) / decompress, the executors' thread-local last error and the fallback status word.  The entry
 points added since -- split_ / merge_planes, _delta and _xor, estimate, survey_planes, survey_delta, their batch forms,
@@ -19,6 +19,8 @@ exactly what its own launch should report.  Comparisons run on the device; only 
    zeroed status word, launched back to back and synchronised once at the end.  Sizes: one packet, one ragged wavefront,
    both sides of the auto switch (32768 / 32769 packets), 512 MiB - 1 GiB inputs; uniform, zipf, text and zeros.  The
    encoder's own status word is exercised with the 1024-byte slot build, where random input overflows its slots.
+   encode_kernel and encode_kernel_t16 (the table walk), which deal their roles by the same per-CU ticket counters, run
+   beside each other on two streams.
 2. Mixed co-residency: a >= 1 GiB throughput encode next to decode_slots, decode_stream, compaction and crc32_batch of
    other inputs, the encoder launched first and last, three seeds each.
 3. Host threads: whole chains from eight threads at once; batch.compress / decompress from several threads; the
@@ -34,6 +36,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import packet_families as PF
 from concurrency_checks import _fail_on, _same, _status, _streams, _words
 from gpuar_amd import synth
 from test_gpu_parity import small_slot_lib  # noqa: F401  (the 1024-byte slot build, a module fixture)
@@ -52,7 +55,7 @@ WORKLOADS = [
     ("text", 11, 5000),                              # one packet
     ("zipf", 12, 63 * PACKET + 4321),                # one wavefront, its last lane short
     ("uniform", 13, 32768 * PACKET),                 # the largest input auto sends to the latency kernel
-    ("text", 14, 32768 * PACKET + 77),               # 32769 packets: the smallest it sends to the throughput kernel
+    ("text", 14, 32768 * PACKET + 77),               # 32769 packets: the smallest it sends to the table-walk kernel
     ("zeros", 0, 1024 * MiB),
     ("uniform", 15, 768 * MiB + 3 * PACKET + 17),
     ("zipf", 16, 512 * MiB + 999),
@@ -188,12 +191,12 @@ def serial(H, oracle):
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. stream fan-out, one kernel family at a time
 # ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("mode", ["throughput", "latency", "auto"])
+@pytest.mark.parametrize("mode", ["throughput", "latency", "auto", "table"])
 def test_encode_fan_out(H, serial, mode):
     """encode_mode on eight streams at once.  Serial pass first: each workload alone in this mode must equal the pinned
     slots on their clen bytes.  Concurrent pass into the same buffers (refilled): equal again, so equal to the serial
-    pass.  Several throughput grids (and, in auto, latency grids beside them) share the chip, which changes the order in
-    which workgroups draw their per-CU tickets; the slots must not depend on it."""
+    pass.  Several throughput or table-walk grids (in auto: latency grids beside table-walk ones) share the chip, which
+    changes the order in which workgroups draw their per-CU tickets; the slots must not depend on it."""
     k = len(serial)
     bufs = [torch.full((w["npk"] * SLOT,), 0xEE, dtype=torch.uint8, device="cuda") for w in serial]
     words = _status(2 * k)
@@ -219,6 +222,63 @@ def test_encode_fan_out(H, serial, mode):
     assert H.status() == 0, f"encode {mode}: a launch reported into the fallback word"
 
 
+TWO_KERNEL_N = 130 * PACKET + 4097                   # two full groups and a third of three lanes, the last one short
+
+
+def test_table_and_throughput_kernels_side_by_side(H, oracle):
+    """encode_kernel_t16 (the table walk) on one stream while encode_kernel runs on the other, then swapped: the only place
+    where workgroups of the two kernels draw tickets from the same per-CU arrival counters at once (each kernel deals its
+    wavefronts' roles by SIMD after its ticket, four resident workgroups holding four consecutive ones -- with two kernels
+    on a CU they no longer do).  130 packets + 4097 bytes each of zipf and of the parity suite's keep-carrying packets; every
+    launch's slots equal the same kernel's serial slots and the reference encoder's, both status words are 0 and nothing
+    goes to the fallback word."""
+    inputs = {"zipf": torch.from_numpy(synth.zipf(61, TWO_KERNEL_N)).cuda(),
+              "carry": torch.from_numpy(np.ascontiguousarray(PF.keep_carrying(131)[:TWO_KERNEL_N])).cuda()}
+    npk = H.packet_count(TWO_KERNEL_N)
+    assert npk == 131 and H.status() == 0
+    verdicts = []
+    want, serial_slots = {}, {}
+    for name, d_in in inputs.items():
+        host = d_in.cpu().numpy()
+        stream = oracle.encode_stream(host)
+        ref = np.zeros((npk, SLOT), dtype=np.uint8)
+        at = 0
+        for p in range(npk):
+            c = int(stream[at]) | (int(stream[at + 1]) << 8)
+            ref[p, :c] = stream[at:at + c]
+            at += c
+        assert at == stream.size
+        want[name] = torch.from_numpy(ref).cuda().view(-1)
+        for mode in ("table", "throughput"):
+            word = _status()
+            serial_slots[name, mode] = H.encode(d_in, d_status=word, mode=mode)
+            torch.cuda.synchronize()
+            verdicts.append((f"encode {mode}, {name} {TWO_KERNEL_N} bytes (serial): slots differ from the reference encoder",
+                             _slots_equal(serial_slots[name, mode], want[name], npk)))
+            _words(verdicts, word, [0], [f"encode {mode}, {name} (serial)"])
+    sA, sB = _streams(2)
+    pairs = [(("zipf", "table"), ("carry", "throughput")), (("zipf", "throughput"), ("carry", "table")),
+             (("carry", "table"), ("zipf", "throughput")), (("carry", "throughput"), ("zipf", "table"))]
+    words = _status(2 * len(pairs))
+    what, expected = [], []
+    for r, pair in enumerate(pairs):
+        bufs = [torch.full((npk * SLOT,), 0xEE, dtype=torch.uint8, device="cuda") for _ in pair]
+        torch.cuda.synchronize()
+        for j, ((name, mode), s) in enumerate(zip(pair, (sA, sB))):
+            H.encode(inputs[name], bufs[j], stream=s, d_status=words[2 * r + j:2 * r + j + 1], mode=mode)
+        torch.cuda.synchronize()
+        for j, (name, mode) in enumerate(pair):
+            other = pair[1 - j]
+            tag = f"round {r}, stream {'AB'[j]}: encode {mode}, {name}, beside encode {other[1]}, {other[0]}"
+            verdicts.append((f"{tag}: slots differ from the same kernel's serial slots", _slots_equal(bufs[j], serial_slots[name, mode], npk)))
+            verdicts.append((f"{tag}: slots differ from the reference encoder", _slots_equal(bufs[j], want[name], npk)))
+            what.append(tag)
+            expected.append(0)
+    _words(verdicts, words, expected, what)
+    _fail_on(verdicts)
+    assert H.status() == 0, "a launch reported into the fallback word"
+
+
 SMALL_SLOT = 1024
 SMALL_SLOT_PACKETS = 2048
 
@@ -237,7 +297,7 @@ def _small_slots_defined(got, want, npk):
 def test_encode_status_isolation_with_small_slots(H, oracle, small_slot_lib, how):
     """The encoder's own status word, which the shipped 8704-byte slots never give it a reason to touch: with the 1024-byte
     slot build of tests/test_gpu_parity.py, random bytes overflow every slot and zeros fit.  Eight encodes of 2048
-    packets, alternately overflowing and fitting, the throughput and latency kernels in turn, on eight streams launched
+    packets, alternately overflowing and fitting, the throughput, latency and table-walk kernels in turn, on eight streams launched
     back to back or from eight host threads: SLOT_OVERFLOW lands in exactly the overflowing launches' words, the others
     stay 0, and the slots equal the serial run's (pinned against the reference encoder) on their defined bytes."""
     k = 8
@@ -245,13 +305,13 @@ def test_encode_status_isolation_with_small_slots(H, oracle, small_slot_lib, how
     guard = 4096
     inputs = [H.generate("uniform", 300 + i, n) if i % 2 == 0 else torch.zeros(n, dtype=torch.uint8, device="cuda")
               for i in range(k)]
-    modes = [(1, 2)[(i // 2) % 2] for i in range(k)]                  # GPUAR_MODE_THROUGHPUT / LATENCY, both on each kind
+    modes = [(1, 2, 3)[(i // 2 + i % 2) % 3] for i in range(k)]       # GPUAR_MODE_THROUGHPUT / LATENCY / TABLE, each on both kinds
     slots = [torch.full((SMALL_SLOT_PACKETS * SMALL_SLOT + guard,), CANARY, dtype=torch.uint8, device="cuda") for _ in range(k)]
     words = _status(2 * k)
     expected = [H.STATUS_SLOT_OVERFLOW if i % 2 == 0 else 0 for i in range(k)]
 
     def what(i):
-        return (f"{'thread' if how == 'threads' else 'stream'} {i}: encode_mode {('throughput', 'latency')[modes[i] - 1]} with "
+        return (f"{'thread' if how == 'threads' else 'stream'} {i}: encode_mode {('throughput', 'latency', 'table')[modes[i] - 1]} with "
                 f"1024-byte slots, {('uniform', 'zeros')[i % 2]} {n} bytes ({SMALL_SLOT_PACKETS} packets)")
 
     def launch(i, stream, word):

@@ -2,8 +2,10 @@
 
 1. Every packet length 1 ... 8192 through both decoders (decode_stream and the slot decoder), in lane layouts built to
    drive the decoder's divergent whole-block loop, its handoff to the plain step and its partial last block.
-2. Every tail residue through both encode kernels (throughput and latency mode).
-3. The auto-mode switch between the two encode kernels (32768 / 32769 packets).
+2. Every tail residue through the three encode kernels (throughput: encode_kernel, latency: encode_small_kernel, table:
+   encode_kernel_t16, the table walk).
+3. The auto-mode switch (32768 packets: the latency kernel; 32769: the table-walk kernel encode_kernel_t16) against all
+   three forced modes.
 4. Compaction (scans + gather) against a plain concatenation of synthetic slots.
 5. Every packet length through both batch encoders (throughput and latency mode): each lane its own one-packet buffer,
    the buffers scattered over a canary arena in permuted address order with zero-byte buffers among them, the bytes
@@ -151,7 +153,7 @@ def test_decode_slots_at_every_packet_length(H, sweep, layout, after_clen):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# 2. every tail residue through both encoders
+# 2. every tail residue through the three encoders
 # ---------------------------------------------------------------------------------------------------------------------
 TAILS = sorted(set(range(1, 257)) | set(range(7936, 8192)) | {64 * j + j % 64 for j in range(4, 124)})
 FULL = 63
@@ -163,11 +165,15 @@ def _clen_bytes_equal(d_slots, d_want, d_clens):
     return torch.where(keep, d_slots, 0).eq(torch.where(keep, d_want, 0)).all()
 
 
-@pytest.mark.parametrize("mode", ["throughput", "latency"])
+@pytest.mark.parametrize("mode", ["throughput", "latency", "table"])
 def test_encode_every_tail_residue(H, oracle, sweep, mode):
     """n = 63*8192 + r (one wavefront whose last lane is short) and n = r (one live lane): the last slot equals the
     oracle's encoding of the last packet on its clen bytes, the 63 full packets equal a prefix encoded once, and every
-    case decodes back to its input.  r covers 1 ... 256, 7936 ... 8191 and every residue mod 64 at every depth."""
+    case decodes back to its input.  r covers 1 ... 256, 7936 ... 8191 and every residue mod 64 at every depth.  In the
+    throughput and table kernels the top modeler leaves its whole-phase form after r / 64 chunks and the low modeler and
+    the coder after r / 8 phases, so with 63 full packets in front every residue mod 64 puts the two hand-offs in a
+    different relation; with none the group is not full and the one live lane runs in the ragged form from its first
+    symbol on (host half: tests/test_encode_table.py)."""
     kinds = ("text", "zipf", "uniform")
     prefix = np.concatenate([synth.generate(kinds[k % 3], 40 + k, PACKET) for k in range(FULL)])
     stream = oracle.encode_stream(prefix)
@@ -223,9 +229,10 @@ SMALL_GROUPS_PACKETS = 512 * 64          # gpuar_hip_encode_mode: auto sends up 
 
 @pytest.mark.parametrize("npk", [SMALL_GROUPS_PACKETS, SMALL_GROUPS_PACKETS + 1])
 def test_encode_modes_agree_across_the_auto_boundary(H, oracle, npk):
-    """At 32768 packets auto takes the latency kernel, at 32769 the throughput kernel: auto and both forced modes give
-    the same slots on their clen bytes (compared on the device), 64-packet windows of them equal the oracle, and the
-    slots decode back.  The input mixes three source models packet by packet and ends in a short packet."""
+    """At 32768 packets auto takes the latency kernel, at 32769 the table-walk kernel (encode_kernel_t16): auto and the
+    three forced modes give the same slots on their clen bytes (compared on the device), 64-packet windows of them equal
+    the oracle, and the slots decode back.  The input mixes three source models packet by packet and ends in a short
+    packet."""
     n = (npk - 1) * PACKET + 4321
     d_in = torch.empty(npk * PACKET, dtype=torch.uint8, device="cuda")
     rows = d_in.view(npk, PACKET)
@@ -233,13 +240,13 @@ def test_encode_modes_agree_across_the_auto_boundary(H, oracle, npk):
         rows[k::3] = H.generate(kind, 70 + k, npk * PACKET).view(npk, PACKET)[k::3]
     d_in = d_in[:n]
     out = {}
-    for mode in ("auto", "throughput", "latency"):
+    for mode in ("auto", "throughput", "latency", "table"):
         word = _status()
         out[mode] = H.encode(d_in, mode=mode, d_status=word).view(npk, SLOT)
         torch.cuda.synchronize()
         assert int(word.item()) == 0, (npk, mode)
     d_clens = out["auto"][:, 0].to(torch.int64) | (out["auto"][:, 1].to(torch.int64) << 8)
-    for mode in ("throughput", "latency"):
+    for mode in ("throughput", "latency", "table"):
         assert _clen_bytes_equal(out[mode], out["auto"], d_clens).item(), f"{npk} packets: {mode} differs from auto"
     for first in (0, npk - 64, 32704):
         last = min(first + 65, npk) if first == 32704 else first + 64

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import packet_families as PF
 from gpuar_amd import synth
 from test_oracle_golden import REFV, SURVEY, case_input, md5
 
@@ -48,10 +49,13 @@ def test_the_checker_on_this_box_is_the_reference_codec(oracle):
     assert oracle.kind == "reference" and O.file_sha256(O.REF_LIB_PATH) == O.pinned_checker_sha256()
 
 
-@pytest.fixture(params=["latency", "throughput"])
+@pytest.fixture(params=["latency", "throughput", "table"])
 def encode_mode(request):
-    """gpuar_hip_encode sends small inputs to the five-role latency-mode kernel and large ones to the three-role
-    throughput kernel (GPUAR_ENCODE_MODE pins the choice): the small parity cases run through BOTH kernels."""
+    """gpuar_hip_encode sends small inputs to the five-role latency-mode kernel and large ones to the table walk of the
+    three-role throughput kernel (encode_kernel_t16); encode_kernel, the batch kernels' twin, is reached by
+    GPUAR_MODE_THROUGHPUT alone.  GPUAR_ENCODE_MODE pins the choice: the parity cases run through ALL THREE kernels.  (Only
+    hip.encode and hip.encode_batch read the variable, and no test under this fixture calls the batch encoder, which refuses
+    "table": tests/test_gpu_batch.py::test_batch_encoders_refuse_the_table_mode.)"""
     old = os.environ.get("GPUAR_ENCODE_MODE")
     os.environ["GPUAR_ENCODE_MODE"] = request.param
     yield request.param
@@ -468,7 +472,7 @@ def real_text(min_bytes):
 
 def test_real_text_against_oracle(H, oracle, encode_mode):
     """Real bytes, once (SURVEY.md section 6's third probe row was source text; BASELINE.md section 2 row 3: ratio 0.5717): every
-    other GPU input is synthetic.  >= 32 MiB of this repository's own text through both encode kernels: the whole stream
+    other GPU input is synthetic.  >= 32 MiB of this repository's own text through every encode kernel: the whole stream
     byte-equal to the oracle's, both decoders, the ratio inside the band real source text lands in."""
     data, n_files = real_text(32 << 20)
     assert data.size >= (32 << 20) and n_files > 50
@@ -488,22 +492,9 @@ def test_packets_that_keep_carrying_against_oracle(H, oracle, encode_mode):
     behind a scalar branch in the store region, lane_codec.h) with every lane of a wavefront in a different state of it:
     512 packets of two symbols either side of the interval's midpoint, few-symbol alphabets at every skew, and long
     constant stretches, of ragged lengths; slot for slot against the oracle."""
-    rng = np.random.default_rng(2904)
     npk = 512
-    data = np.zeros(npk * 8192, dtype=np.uint8)
-    for p in range(npk):
-        view = data[p * 8192:(p + 1) * 8192]
-        kind = p % 4
-        if kind == 0:
-            view[:] = np.where(rng.random(8192) < 0.5, 0x7F, 0x80).astype(np.uint8)
-        elif kind == 1:
-            view[:] = rng.choice(np.array([0x7F, 0x80, 0x00, 0xFF], dtype=np.uint8), 8192, p=[0.45, 0.45, 0.05, 0.05])
-        elif kind == 2:
-            view[:] = rng.choice(rng.integers(0, 256, int(rng.integers(2, 6))).astype(np.uint8), 8192)
-        else:
-            view[:] = np.repeat(rng.integers(0, 256, 8192 // 64).astype(np.uint8), 64)
-    n = npk * 8192 - 3001                               # the last packet is a short one
-    data = data[:n]
+    data = PF.keep_carrying(npk)
+    n = data.size
     want, want_len, total = oracle_slots(oracle, data)
     d_slots = H.encode(torch.from_numpy(data).cuda())
     got = d_slots.cpu().numpy().reshape(npk, 8704)
@@ -515,43 +506,15 @@ def test_packets_that_keep_carrying_against_oracle(H, oracle, encode_mode):
     assert H.status() == 0
 
 
-def test_packets_that_drain_the_stream_window_fast_against_oracle(H, oracle):
+def test_packets_that_drain_the_stream_window_fast_against_oracle(H, oracle, encode_mode):
     """The decoder refills its stream window every SECOND symbol and asks for ring pieces by where its reader stands
     (gpuar_kernels.hip, "the stream reader", "the stream ring"): both rest on a symbol taking at most 16 stream bits.  These
     packets make lanes run at the top of that for thousands of symbols while their neighbours idle: a model trained on one
     byte (or on a few) and then fed bytes it has never seen -- 12-13 bits a symbol --, switch points and lengths ragged, next to
     constant packets (0.2 bits a symbol) and uniform ones (8).  Slots against the oracle; both decoders back to the bytes."""
-    rng = np.random.default_rng(6006)
     npk = 192
-    data = np.zeros(npk * 8192, dtype=np.uint8)
-    for p in range(npk):
-        view = data[p * 8192:(p + 1) * 8192]
-        kind = p % 6
-        if kind == 0:                                       # one byte for a while, then every other byte in turn
-            cut = int(rng.integers(512, 7000))
-            view[:cut] = rng.integers(0, 256)
-            view[cut:] = (np.arange(8192 - cut) * 37 + int(rng.integers(0, 256))).astype(np.uint8)
-        elif kind == 1:                                     # a few bytes, then bytes drawn from the unseen rest, then back
-            few = rng.integers(0, 256, 3).astype(np.uint8)
-            a, b = sorted(int(v) for v in rng.integers(256, 7900, 2))
-            view[:] = rng.choice(few, 8192)
-            rest = np.setdiff1d(np.arange(256, dtype=np.uint8), few)
-            view[a:b] = rng.choice(rest, b - a)
-        elif kind == 2:
-            view[:] = rng.integers(0, 256)                  # constant: the slowest reader
-        elif kind == 3:
-            view[:] = rng.integers(0, 256, 8192)            # uniform
-        elif kind == 4:                                     # bursts of rare bytes in a constant packet
-            view[:] = 0x20
-            for _ in range(int(rng.integers(1, 40))):
-                at = int(rng.integers(0, 8100))
-                view[at:at + int(rng.integers(1, 90))] = rng.integers(0, 256, 1)
-        else:                                               # a ramp over all byte values, then a constant tail
-            cut = int(rng.integers(300, 8000))
-            view[:cut] = (np.arange(cut) % 256).astype(np.uint8)
-            view[cut:] = 0xFF
-    n = npk * 8192 - 777
-    data = data[:n]
+    data = PF.drain_the_window(npk)
+    n = data.size
     want, want_len, total = oracle_slots(oracle, data)
     assert 7500 < want_len.max() <= 8704                      # some packets really are long, none outgrows its slot
     d_slots = H.encode(torch.from_numpy(data).cuda())
@@ -571,35 +534,8 @@ def test_round_trips_over_ten_source_models(H, oracle, seed, encode_mode):
     """4096 packets from ten source models -- uniform, few symbols, geometric, runs, ramps, midpoint pairs, a constant with
     1-40 strangers late in the packet (intervals of width 1-3), sorted, one dominant symbol, zipf -- through both decoders;
     every 16th packet's stream against the reference codec."""
-    rng = np.random.default_rng(seed)
     npk = 4096
-    data = np.empty(npk * 8192, dtype=np.uint8)
-    for p in range(npk):
-        v = data[p * 8192:(p + 1) * 8192]
-        m = p % 10
-        if m == 0:
-            v[:] = rng.integers(0, 256, 8192, dtype=np.uint8)
-        elif m == 1:
-            v[:] = rng.integers(0, int(rng.integers(1, 9)), 8192, dtype=np.uint8) * int(rng.integers(1, 32))
-        elif m == 2:
-            v[:] = (rng.geometric(float(rng.uniform(0.02, 0.5)), 8192) % 256).astype(np.uint8)
-        elif m == 3:
-            v[:] = np.repeat(rng.integers(0, 256, 8192 // 32, dtype=np.uint8), 32)
-        elif m == 4:
-            v[:] = (np.arange(8192) * int(rng.integers(1, 255))) % 256
-        elif m == 5:
-            v[:] = rng.choice(np.array([0x7F, 0x80], dtype=np.uint8), 8192)
-        elif m == 6:
-            v[:] = int(rng.integers(0, 256))
-            late = rng.integers(4000, 8192, int(rng.integers(1, 40)))
-            v[late] = rng.integers(0, 256, late.size, dtype=np.uint8)
-        elif m == 7:
-            v[:] = np.sort(rng.integers(0, 256, 8192, dtype=np.uint8))
-        elif m == 8:
-            k = int(rng.integers(2, 6))
-            v[:] = rng.choice(rng.integers(0, 256, k, dtype=np.uint8), 8192, p=np.array([0.97] + [0.03 / (k - 1)] * (k - 1)))
-        else:
-            v[:] = (rng.zipf(1.3, 8192) % 256).astype(np.uint8)
+    data = PF.ten_source_models(seed, npk)
     d_in = torch.from_numpy(data).cuda()
     d_slots = H.encode(d_in)
     assert H.status() == 0
