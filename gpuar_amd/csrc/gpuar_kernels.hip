@@ -2392,6 +2392,9 @@ __device__ __forceinline__ PlanesBuffer planes_buffer(const PlanesArgs &a, uint3
 }
 
 typedef uint32_t PlanesQuad __attribute__((ext_vector_type(4)));
+using PlanesGlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+using PlanesGlobalWord = __attribute__((address_space(1))) uint32_t;
+using PlanesGlobalByte = __attribute__((address_space(1))) uint8_t;
 
 struct PlanesPerm {
     __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t sel) const { return __builtin_amdgcn_perm(a, b, sel); }
@@ -2466,19 +2469,55 @@ merge_planes_kernel(PlanesArgs a) {
     planes_full<true>(a);
 }
 
-// the tails: workgroup b on buffer b's last n mod G bytes (the general path of planes.h's definition)
-template <bool Merge>
-__device__ __forceinline__ void planes_tail(const PlanesBuffer &pb, PlanesQuad *lds) {
+// What a tail kernel does with one buffer: refuse it, move it as planes alone, or filter it -- and `side`, the pointer the XOR
+// reads beside the buffer.  The kernel says it once for a single buffer and per buffer of a batch (a functor of the buffer's
+// index); the tails' loop (filter_tails) acts on it and does not know which filter it serves.
+struct BufferFilter {
+    bool bad;                               // a batch only: the buffer is left alone (the full-group kernel flags BAD_BATCH)
+    uint32_t filtered;                      // 0: planes alone
+    const uint8_t *side;
+};
+constexpr BufferFilter kPlanesAlone = {false, 0u, nullptr};
+struct PlanesAlone {                        // planes_tail_kernel's answers: no buffer is filtered, so no filtered tail is ever asked for
+    __device__ __forceinline__ BufferFilter operator()(uint32_t) const { return kPlanesAlone; }
+    __device__ __forceinline__ void operator()(const PlanesBuffer &, const uint8_t *) const {}
+};
+
+// The tail's frame, shared by the three filters.  tail_load: r bytes at `from` into LDS by quads (never beyond the 16-byte piece
+// that holds the buffer's last byte), XORed with those at `with` on the way where Xor.  tail_store: r bytes to `to` by dwords
+// and the last r mod 4 bytes (never beyond byte n), word(i) giving dword i and byte(o) byte o.
+template <bool Xor>
+__device__ __forceinline__ void tail_load(const uint8_t *from, const uint8_t *with, uint32_t r, PlanesQuad *lds) {
+    const PlanesGlobalQuad *src = reinterpret_cast<const PlanesGlobalQuad *>(reinterpret_cast<uintptr_t>(from));
+    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) {
+        PlanesQuad v = src[i];
+        if constexpr (Xor) v ^= reinterpret_cast<const PlanesGlobalQuad *>(reinterpret_cast<uintptr_t>(with))[i];
+        lds[i] = v;
+    }
+    __syncthreads();
+}
+
+template <typename Word, typename Byte>
+__device__ __forceinline__ void tail_store(uint8_t *to, uint32_t r, Word word, Byte byte) {
+    PlanesGlobalWord *words = reinterpret_cast<PlanesGlobalWord *>(reinterpret_cast<uintptr_t>(to));
+    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) words[i] = word(i);
+    PlanesGlobalByte *last = reinterpret_cast<PlanesGlobalByte *>(reinterpret_cast<uintptr_t>(to));
+    if (threadIdx.x < (r & 3u)) last[(r & ~3u) + threadIdx.x] = byte((r & ~3u) + threadIdx.x);
+}
+
+// the tail of a buffer, its last n mod G bytes (the general path of planes.h's definition); Xor: against `base` (xorbase.h), on
+// the way into LDS for the split -- the base read by quads like the buffer -- and on the way out of it for the merge, which
+// reads the base by the dwords and last bytes it writes
+template <bool Merge, bool Xor>
+__device__ __forceinline__ void planes_tail(const PlanesBuffer &pb, const uint8_t *base, PlanesQuad *lds) {
     const uint32_t w = pb.w;
-    if (w == 0u || (w == 1u && pb.in == pb.out)) return;
+    if constexpr (!Xor) {
+        if (w == 0u || (w == 1u && pb.in == pb.out)) return;
+    }
     const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
     if (r == 0u) return;
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
-    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
-    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) lds[i] = src[i];
-    __syncthreads();
+    const uint8_t *with = Xor ? base + (pb.n_bytes - r) : nullptr;
+    tail_load<Xor && !Merge>(pb.in + (pb.n_bytes - r), with, r, lds);
     const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
     const uint32_t log_w = 31u - __builtin_clz(w);
     // output byte o of the tail comes from input byte ...
@@ -2487,30 +2526,48 @@ __device__ __forceinline__ void planes_tail(const PlanesBuffer &pb, PlanesQuad *
         if (!Merge) return (o % e << log_w) + o / e;                        // o = k e + i  <-  i w + k
         return (o & (w - 1u)) * e + (o >> log_w);                           // o = i w + k  <-  k e + i
     };
-    uint8_t *out = pb.out + (pb.n_bytes - r);
-    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
-    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) {
-        const uint32_t o = 4u * i;
-        words[i] = bytes[source(o)] | static_cast<uint32_t>(bytes[source(o + 1u)]) << 8 | static_cast<uint32_t>(bytes[source(o + 2u)]) << 16 |
-                   static_cast<uint32_t>(bytes[source(o + 3u)]) << 24;
+    tail_store(
+        pb.out + (pb.n_bytes - r), r,
+        [&](uint32_t i) -> uint32_t {
+            const uint32_t o = 4u * i;
+            uint32_t v = bytes[source(o)] | static_cast<uint32_t>(bytes[source(o + 1u)]) << 8 | static_cast<uint32_t>(bytes[source(o + 2u)]) << 16 |
+                         static_cast<uint32_t>(bytes[source(o + 3u)]) << 24;
+            if constexpr (Xor && Merge) v ^= reinterpret_cast<const PlanesGlobalWord *>(reinterpret_cast<uintptr_t>(with))[i];
+            return v;
+        },
+        [&](uint32_t o) -> uint8_t {
+            uint8_t v = bytes[source(o)];
+            if constexpr (Xor && Merge) v ^= reinterpret_cast<const PlanesGlobalByte *>(reinterpret_cast<uintptr_t>(with))[o];
+            return v;
+        });
+}
+
+// The tail kernels' loop: one buffer, or workgroup b on buffer b of a batch with a barrier between buffers.  A buffer that is
+// not filtered takes planes_tail, a filtered one tail(buffer, side); a refused one is left alone (a refused buffer with
+// packets was flagged by the full-group kernel).
+template <bool Merge, typename PerBuffer, typename Tail>
+__device__ __forceinline__ void filter_tails(const PlanesArgs &a, const BufferFilter &single, PerBuffer per_buffer, PlanesQuad *lds, Tail tail) {
+    auto one = [&](const PlanesBuffer &pb, const BufferFilter &f) {
+        if (f.bad) return;
+        if (f.filtered == 0u) planes_tail<Merge, false>(pb, nullptr, lds);
+        else if (pb.w != 0u) tail(pb, f.side);
+    };
+    if (!a.in_ptrs) {
+        one({a.in, a.out, a.n_bytes, a.elem}, single);
+        return;
     }
-    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
-    if (threadIdx.x < (r & 3u)) last[(r & ~3u) + threadIdx.x] = bytes[source((r & ~3u) + threadIdx.x)];
+    const uint64_t n_buffers = a.n_buffers;
+    for (uint64_t b = blockIdx.x; b < n_buffers; b += gridDim.x) {
+        one(planes_buffer(a, static_cast<uint32_t>(b)), per_buffer(static_cast<uint32_t>(b)));
+        __syncthreads();                                                          // the next buffer's tail goes into the same LDS
+    }
 }
 
 template <bool Merge>
 __global__ void __launch_bounds__(kPlaneThreads)
 planes_tail_kernel(PlanesArgs a) {
     __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
-    if (!a.in_ptrs) {
-        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
-        planes_tail<Merge>(pb, lds);
-        return;
-    }
-    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
-        planes_tail<Merge>(planes_buffer(a, static_cast<uint32_t>(b)), lds);      // (an unusable buffer with packets was flagged by the kernel above)
-        __syncthreads();                                                          // the next buffer's tail goes into the same LDS
-    }
+    filter_tails<Merge>(a, kPlanesAlone, PlanesAlone(), lds, PlanesAlone());
 }
 
 // ---------------------------------------------------------------------------
@@ -2527,7 +2584,10 @@ planes_tail_kernel(PlanesArgs a) {
 // above, anything else flags BAD_BATCH and leaves the buffer alone; the choice is uniform over a workgroup.
 // The tail is delta_tail_kernel's, one workgroup per buffer through LDS like planes_tail: a thread takes 16 elements from
 // LDS into registers, filters them, and puts them back in the other layout; then LDS goes out by dwords and bytes.
-// The existing kernels are not touched: callers without the filter keep launching them.
+// Shared with the other filters: the tail's way into LDS and out of it (tail_load, tail_store), the tail kernels' loop over the
+// buffers (filter_tails, which sends a buffer with `filter` 0 to planes_tail) and, on the host, the launcher and the argument
+// checks.  The delta's own: delta_tail's register pass between the two, and the full-group kernels, whose code is their own
+// so that it stays instruction for instruction what DESIGN.md 4.9 measured.
 // ---------------------------------------------------------------------------
 struct DeltaArgs {
     PlanesArgs p;
@@ -2654,18 +2714,22 @@ merge_delta_kernel(DeltaArgs d) {
     delta_full<true>(d, lds);
 }
 
+struct DeltaPerBuffer {
+    const uint64_t *filter;
+    __device__ __forceinline__ BufferFilter operator()(uint32_t b) const {
+        const uint64_t f = filter[b];
+        return {f > 1u, static_cast<uint32_t>(f), nullptr};
+    }
+};
+constexpr BufferFilter kDeltaSingle = {false, 1u, nullptr};
+
 // the tail of a buffer the filter is on for: e = r div w <= 8191 elements, thread t takes elements 16 t .. 16 t + 15
 template <bool Merge>
 __device__ __forceinline__ void delta_tail(const PlanesBuffer &pb, PlanesQuad *lds, uint64_t *waves) {
     const uint32_t w = pb.w;
     const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
     if (r == 0u) return;
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
-    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
-    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) lds[i] = src[i];
-    __syncthreads();
+    tail_load<false>(pb.in + (pb.n_bytes - r), nullptr, r, lds);
     uint8_t *bytes = reinterpret_cast<uint8_t *>(lds);
     // element i (< e): its byte k lies at i w + k on the mixed side and at k e + i on the plane side
     auto element = [&](uint32_t i, bool planes) -> uint64_t {
@@ -2701,11 +2765,8 @@ __device__ __forceinline__ void delta_tail(const PlanesBuffer &pb, PlanesQuad *l
     }
     __syncthreads();
     const uint32_t *done = reinterpret_cast<const uint32_t *>(lds);
-    uint8_t *out = pb.out + (pb.n_bytes - r);
-    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
-    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) words[i] = done[i];
-    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
-    if (threadIdx.x < (r & 3u)) last[(r & ~3u) + threadIdx.x] = bytes[(r & ~3u) + threadIdx.x];
+    tail_store(
+        pb.out + (pb.n_bytes - r), r, [&](uint32_t i) -> uint32_t { return done[i]; }, [&](uint32_t o) -> uint8_t { return bytes[o]; });
 }
 
 template <bool Merge>
@@ -2713,19 +2774,8 @@ __global__ void __launch_bounds__(kPlaneThreads)
 delta_tail_kernel(DeltaArgs d) {
     __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
     __shared__ uint64_t waves[kPlaneThreads / 64u];
-    const PlanesArgs &a = d.p;
-    if (!a.in_ptrs) {
-        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
-        delta_tail<Merge>(pb, lds, waves);
-        return;
-    }
-    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
-        const PlanesBuffer pb = planes_buffer(a, static_cast<uint32_t>(b));      // (an unusable buffer with packets was flagged by the kernel above)
-        const uint64_t filter = d.filter[b];
-        if (pb.w != 0u && filter == 1u) delta_tail<Merge>(pb, lds, waves);
-        else if (filter == 0u) planes_tail<Merge>(pb, lds);
-        __syncthreads();                                                         // the next buffer's tail goes into the same LDS
-    }
+    filter_tails<Merge>(d.p, kDeltaSingle, DeltaPerBuffer{d.filter}, lds,
+                        [&](const PlanesBuffer &pb, const uint8_t *) { delta_tail<Merge>(pb, lds, waves); });
 }
 
 // ---------------------------------------------------------------------------
@@ -2744,7 +2794,9 @@ delta_tail_kernel(DeltaArgs d) {
 // The tail is xor_tail_kernel's, one workgroup per buffer through LDS like planes_tail: by quads in -- buffer and, for the
 // split, base, XORed on the way into LDS; the merge reads the base by the dwords and last bytes it writes -- so nothing
 // is read beyond the 16-byte piece that holds the last byte and nothing written beyond byte n.
-// The existing kernels are not touched: callers without a base keep launching them.
+// Shared with the other filters: the tail itself -- planes_tail with the XOR as its optional part -- the tail kernels' loop over
+// the buffers (filter_tails), and on the host the launcher and the argument checks.  The XOR's own: the full-group kernels, whose
+// code is their own so that it stays instruction for instruction what DESIGN.md 4.10 measured.
 // ---------------------------------------------------------------------------
 struct XorArgs {
     PlanesArgs p;
@@ -2852,66 +2904,20 @@ merge_xor_kernel(XorArgs x) {
     xor_full<true>(x, lds);
 }
 
-// the tail of a buffer with a base: planes_tail with the XOR on the way into LDS (split) or on the way out of it (merge)
-template <bool Merge>
-__device__ __forceinline__ void xor_tail(const PlanesBuffer &pb, const uint8_t *base, PlanesQuad *lds) {
-    const uint32_t w = pb.w;
-    const uint32_t r = static_cast<uint32_t>(pb.n_bytes % (static_cast<uint64_t>(w) * kPlanePacket)), e = r / w;
-    if (r == 0u) return;
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
-    const GlobalQuad *src = reinterpret_cast<const GlobalQuad *>(reinterpret_cast<uintptr_t>(pb.in + (pb.n_bytes - r)));
-    const uintptr_t with = reinterpret_cast<uintptr_t>(base + (pb.n_bytes - r));
-    for (uint32_t i = threadIdx.x; i * 16u < r; i += kPlaneThreads) {
-        PlanesQuad v = src[i];
-        if constexpr (!Merge) v ^= reinterpret_cast<const GlobalQuad *>(with)[i];
-        lds[i] = v;
+struct XorPerBuffer {
+    const uint8_t *const *base_ptrs;
+    __device__ __forceinline__ BufferFilter operator()(uint32_t b) const {
+        const uint8_t *base = base_ptrs[b];
+        return {(reinterpret_cast<uintptr_t>(base) & 15u) != 0u, base != nullptr ? 1u : 0u, base};
     }
-    __syncthreads();
-    const uint8_t *bytes = reinterpret_cast<const uint8_t *>(lds);
-    const uint32_t log_w = 31u - __builtin_clz(w);
-    // output byte o of the tail comes from input byte ... (planes_tail's map)
-    auto source = [&](uint32_t o) -> uint32_t {
-        if (o >= e * w) return o;                                           // the last r mod w bytes (and everything when e = 0)
-        if (!Merge) return (o % e << log_w) + o / e;                        // o = k e + i  <-  i w + k
-        return (o & (w - 1u)) * e + (o >> log_w);                           // o = i w + k  <-  k e + i
-    };
-    uint8_t *out = pb.out + (pb.n_bytes - r);
-    GlobalWord *words = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(out));
-    for (uint32_t i = threadIdx.x; i * 4u + 4u <= r; i += kPlaneThreads) {
-        const uint32_t o = 4u * i;
-        uint32_t v = bytes[source(o)] | static_cast<uint32_t>(bytes[source(o + 1u)]) << 8 | static_cast<uint32_t>(bytes[source(o + 2u)]) << 16 |
-                     static_cast<uint32_t>(bytes[source(o + 3u)]) << 24;
-        if constexpr (Merge) v ^= reinterpret_cast<const GlobalWord *>(with)[i];
-        words[i] = v;
-    }
-    GlobalByte *last = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(out));
-    if (threadIdx.x < (r & 3u)) {
-        const uint32_t o = (r & ~3u) + threadIdx.x;
-        uint8_t v = bytes[source(o)];
-        if constexpr (Merge) v ^= reinterpret_cast<const GlobalByte *>(with)[o];
-        last[o] = v;
-    }
-}
+};
 
 template <bool Merge>
 __global__ void __launch_bounds__(kPlaneThreads)
 xor_tail_kernel(XorArgs x) {
     __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
-    const PlanesArgs &a = x.p;
-    if (!a.in_ptrs) {
-        const PlanesBuffer pb = {a.in, a.out, a.n_bytes, a.elem};
-        xor_tail<Merge>(pb, x.base, lds);
-        return;
-    }
-    for (uint64_t b = blockIdx.x; b < a.n_buffers; b += gridDim.x) {
-        const PlanesBuffer pb = planes_buffer(a, static_cast<uint32_t>(b));      // (an unusable buffer with packets was flagged by the kernel above)
-        const uint8_t *base = x.base_ptrs[b];
-        if (base == nullptr) planes_tail<Merge>(pb, lds);
-        else if (pb.w != 0u && (reinterpret_cast<uintptr_t>(base) & 15u) == 0u) xor_tail<Merge>(pb, base, lds);
-        __syncthreads();                                                         // the next buffer's tail goes into the same LDS
-    }
+    filter_tails<Merge>(x.p, {false, 1u, x.base}, XorPerBuffer{x.base_ptrs}, lds,
+                        [&](const PlanesBuffer &pb, const uint8_t *base) { planes_tail<Merge, true>(pb, base, lds); });
 }
 
 // ---------------------------------------------------------------------------
@@ -3811,6 +3817,36 @@ uint32_t *status_word(uint32_t *d_status) {
     return static_cast<uint32_t *>(p);
 }
 
+// The filters' launches (byte planes, delta, XOR against a base): the full-group kernel over the packets, then the tail kernel
+// over the buffers that have a tail.  `args` is what the filter's kernels take, `p` the PlanesArgs inside it.
+template <typename Args>
+struct FilterKernels {
+    void (*split)(Args);
+    void (*merge)(Args);
+    void (*split_tail)(Args);
+    void (*merge_tail)(Args);
+};
+const FilterKernels<gpuar::PlanesArgs> kPlanesKernels = {gpuar::split_planes_kernel, gpuar::merge_planes_kernel,
+                                                                gpuar::planes_tail_kernel<false>, gpuar::planes_tail_kernel<true>};
+const FilterKernels<gpuar::DeltaArgs> kDeltaKernels = {gpuar::split_delta_kernel, gpuar::merge_delta_kernel,
+                                                              gpuar::delta_tail_kernel<false>, gpuar::delta_tail_kernel<true>};
+const FilterKernels<gpuar::XorArgs> kXorKernels = {gpuar::split_xor_kernel, gpuar::merge_xor_kernel,
+                                                          gpuar::xor_tail_kernel<false>, gpuar::xor_tail_kernel<true>};
+
+template <typename Args>
+int launch_filter(const FilterKernels<Args> &kernels, bool merge, const Args &args, const gpuar::PlanesArgs &p, void *stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // a batch: any buffer may have a tail; one buffer: it has one or not
+    const size_t n_tails = p.in_ptrs ? p.n_buffers : (p.n_bytes % (static_cast<size_t>(p.elem) * GPUAR_PACKET_BYTES) ? 1u : 0u);
+    const uint32_t blocks = p.n_packets < gpuar::kPlaneGridCap ? p.n_packets : gpuar::kPlaneGridCap;
+    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
+    (merge ? kernels.merge : kernels.split)<<<blocks, gpuar::kPlaneThreads, 0, s>>>(args);
+    const int e = check_launch();
+    if (e != GPUAR_OK || tails == 0u) return e;
+    (merge ? kernels.merge_tail : kernels.split_tail)<<<tails, gpuar::kPlaneThreads, 0, s>>>(args);
+    return check_launch();
+}
+
 }  // namespace
 
 extern "C" {
@@ -4081,55 +4117,82 @@ int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_
     return launch_crc32(true, a, stream);
 }
 
-static int launch_planes(bool merge, const gpuar::PlanesArgs &a, size_t n_tails, void *stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t blocks = a.n_packets < gpuar::kPlaneGridCap ? a.n_packets : gpuar::kPlaneGridCap;
-    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
-    if (merge) gpuar::merge_planes_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(a);
-    else gpuar::split_planes_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(a);
-    const int e = check_launch();
-    if (e != GPUAR_OK || tails == 0u) return e;
-    if (merge) gpuar::planes_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(a);
-    else gpuar::planes_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(a);
-    return check_launch();
+static bool ranges_meet(uintptr_t a, uintptr_t b, size_t n_bytes) { return a < b + n_bytes && b < a + n_bytes; }
+
+// The checks of a single-buffer filter call, on the device or (on_host: no packet limit, no alignment) on the host, in the order
+// the calls have always made them; `based`: the call takes a base, which is only read.  *work: there is something to do.
+static int filter_checks(bool on_host, const uint8_t *in, bool based, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes,
+                         const uint8_t *out, bool *work) {
+    *work = false;
+    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !out || (based && !base)) return GPUAR_ERR_ARGUMENT;
+    if (!on_host && gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (!on_host && (!aligned16(in) || !aligned16(out) || (based && !aligned16(base)))) return GPUAR_ERR_ALIGNMENT;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
+    if (a != b && ranges_meet(a, b, n_bytes)) return GPUAR_ERR_ARGUMENT;                        // in place or apart, nothing in between
+    if (based && ranges_meet(reinterpret_cast<uintptr_t>(base), b, n_bytes)) return GPUAR_ERR_ARGUMENT;
+    *work = true;
+    return GPUAR_OK;
+}
+
+// one buffer on the device: the checks, then the PlanesArgs of its launch
+static int single_arguments(const uint8_t *d_in, bool based, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out,
+                            gpuar::PlanesArgs *p, bool *launch) {
+    const int e = filter_checks(false, d_in, based, d_base, n_bytes, elem_bytes, d_out, launch);
+    if (e != GPUAR_OK || !*launch) return e;
+    p->in = d_in;
+    p->out = d_out;
+    p->n_bytes = n_bytes;
+    p->elem = elem_bytes;
+    p->n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    return GPUAR_OK;
+}
+
+// a batch: the checks of its descriptors -- `d_extra` is the one that delta (filter) and XOR (base_ptrs) add, `extra` whether the
+// call has one -- then the PlanesArgs of its launch
+static int batch_filter_arguments(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                  const uint64_t *d_elem_bytes, bool extra, const void *d_extra, size_t n_buffers, size_t n_packets,
+                                  uint8_t *const *d_out_ptrs, uint32_t *d_status, gpuar::PlanesArgs *p, bool *launch) {
+    *launch = false;
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_elem_bytes || (extra && !d_extra) || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (extra && (reinterpret_cast<uintptr_t>(d_extra) & 7u)) ||
+        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
+        return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    p->in_ptrs = d_in_ptrs;
+    p->out_ptrs = d_out_ptrs;
+    p->bytes = d_bytes;
+    p->first_packet = d_first_packet;
+    p->elem_bytes = d_elem_bytes;
+    p->n_buffers = static_cast<uint32_t>(n_buffers);
+    p->n_packets = static_cast<uint32_t>(n_packets);
+    p->status = status;
+    *launch = true;
+    return GPUAR_OK;
 }
 
 static int planes_single(bool merge, const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!d_in || !d_out || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_in) || !aligned16(d_out)) return GPUAR_ERR_ALIGNMENT;
-    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out);
-    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
-    if (elem_bytes == 1u && in == out) return GPUAR_OK;
     gpuar::PlanesArgs a = {};
-    a.in = d_in;
-    a.out = d_out;
-    a.n_bytes = n_bytes;
-    a.elem = elem_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
-    return launch_planes(merge, a, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+    bool launch = false;
+    const int e = single_arguments(d_in, false, nullptr, n_bytes, elem_bytes, d_out, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    if (elem_bytes == 1u && d_in == d_out) return GPUAR_OK;                     // planes alone: a width of 1 in place is nothing
+    return launch_filter(kPlanesKernels, merge, a, a, stream);
 }
 
 static int planes_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
                         const uint64_t *d_elem_bytes, size_t n_buffers, size_t n_packets, uint8_t *const *d_out_ptrs, uint32_t *d_status,
                         void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    if (!d_elem_bytes || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u)) return GPUAR_ERR_ALIGNMENT;
-    uint32_t *status = nullptr;
-    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
-    if (e != GPUAR_OK) return e;
     gpuar::PlanesArgs a = {};
-    a.in_ptrs = d_in_ptrs;
-    a.out_ptrs = d_out_ptrs;
-    a.bytes = d_bytes;
-    a.first_packet = d_first_packet;
-    a.elem_bytes = d_elem_bytes;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
-    a.status = status;
-    return launch_planes(merge, a, n_buffers, stream);
+    bool launch = false;
+    const int e = batch_filter_arguments(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, false, nullptr, n_buffers, n_packets, d_out_ptrs,
+                                         d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    return launch_filter(kPlanesKernels, merge, a, a, stream);
 }
 
 int gpuar_hip_split_planes(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
@@ -4153,11 +4216,9 @@ int gpuar_hip_merge_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t
 }
 
 static int planes_on_host(bool merge, const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!in || !out) return GPUAR_ERR_ARGUMENT;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
-    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
+    bool work = false;
+    const int e = filter_checks(true, in, false, nullptr, n_bytes, elem_bytes, out, &work);
+    if (e != GPUAR_OK || !work) return e;
     if (merge) gpuar::planes_host<true>(in, n_bytes, elem_bytes, out);
     else gpuar::planes_host<false>(in, n_bytes, elem_bytes, out);
     return GPUAR_OK;
@@ -4171,57 +4232,24 @@ int gpuar_hip_merge_planes_host(const uint8_t *in, size_t n_bytes, uint32_t elem
     return planes_on_host(true, in, n_bytes, elem_bytes, out);
 }
 
-static int launch_delta(bool merge, const gpuar::DeltaArgs &d, size_t n_tails, void *stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t blocks = d.p.n_packets < gpuar::kPlaneGridCap ? d.p.n_packets : gpuar::kPlaneGridCap;
-    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
-    if (merge) gpuar::merge_delta_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(d);
-    else gpuar::split_delta_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(d);
-    const int e = check_launch();
-    if (e != GPUAR_OK || tails == 0u) return e;
-    if (merge) gpuar::delta_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(d);
-    else gpuar::delta_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(d);
-    return check_launch();
-}
-
 static int delta_single(bool merge, const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!d_in || !d_out || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_in) || !aligned16(d_out)) return GPUAR_ERR_ALIGNMENT;
-    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out);
-    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
-    gpuar::DeltaArgs d = {};                                                                   // (a width of 1 in place is work too)
-    d.p.in = d_in;
-    d.p.out = d_out;
-    d.p.n_bytes = n_bytes;
-    d.p.elem = elem_bytes;
-    d.p.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
-    return launch_delta(merge, d, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+    gpuar::DeltaArgs d = {};
+    bool launch = false;
+    const int e = single_arguments(d_in, false, nullptr, n_bytes, elem_bytes, d_out, &d.p, &launch);      // (a width of 1 in place is work too)
+    if (e != GPUAR_OK || !launch) return e;
+    return launch_filter(kDeltaKernels, merge, d, d.p, stream);
 }
 
 static int delta_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
                        const uint64_t *d_elem_bytes, const uint64_t *d_filter, size_t n_buffers, size_t n_packets,
                        uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    if (!d_elem_bytes || !d_filter || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_filter) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
-        return GPUAR_ERR_ALIGNMENT;
-    uint32_t *status = nullptr;
-    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
-    if (e != GPUAR_OK) return e;
     gpuar::DeltaArgs d = {};
-    d.p.in_ptrs = d_in_ptrs;
-    d.p.out_ptrs = d_out_ptrs;
-    d.p.bytes = d_bytes;
-    d.p.first_packet = d_first_packet;
-    d.p.elem_bytes = d_elem_bytes;
-    d.p.n_buffers = static_cast<uint32_t>(n_buffers);
-    d.p.n_packets = static_cast<uint32_t>(n_packets);
-    d.p.status = status;
+    bool launch = false;
+    const int e = batch_filter_arguments(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, true, d_filter, n_buffers, n_packets, d_out_ptrs,
+                                         d_status, &d.p, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     d.filter = d_filter;
-    return launch_delta(merge, d, n_buffers, stream);
+    return launch_filter(kDeltaKernels, merge, d, d.p, stream);
 }
 
 int gpuar_hip_split_delta(const uint8_t *d_in, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
@@ -4245,11 +4273,9 @@ int gpuar_hip_merge_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t 
 }
 
 static int delta_on_host(bool merge, const uint8_t *in, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!in || !out) return GPUAR_ERR_ARGUMENT;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
-    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
+    bool work = false;
+    const int e = filter_checks(true, in, false, nullptr, n_bytes, elem_bytes, out, &work);
+    if (e != GPUAR_OK || !work) return e;
     if (merge) gpuar::merge_delta_host(in, n_bytes, elem_bytes, out);
     else gpuar::split_delta_host(in, n_bytes, elem_bytes, out);
     return GPUAR_OK;
@@ -4263,81 +4289,25 @@ int gpuar_hip_merge_delta_host(const uint8_t *in, size_t n_bytes, uint32_t elem_
     return delta_on_host(true, in, n_bytes, elem_bytes, out);
 }
 
-// one 16-element block through delta.h's register transforms, as the kernels apply them, on the host (for the tests):
-// mixed: 4 * elem_bytes dwords, in place; undo = 0: delta_block with `carried` as pred; 1: undelta_block with it as offset.
-// *total (may be null) receives undelta_block's total.
-int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, uint64_t carried, uint64_t *total) {
-    if (!mixed || !gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    auto run = [&](auto width) {
-        constexpr int W = decltype(width)::value;
-        uint32_t block[4 * W];
-        memcpy(block, mixed, sizeof block);
-        uint64_t sum = 0;
-        if (undo) sum = gpuar::undelta_block<W>(block, carried);
-        else gpuar::delta_block<W>(block, carried);
-        memcpy(mixed, block, sizeof block);
-        if (total) *total = sum;
-    };
-    if (elem_bytes == 8u) run(std::integral_constant<int, 8>());
-    else if (elem_bytes == 4u) run(std::integral_constant<int, 4>());
-    else if (elem_bytes == 2u) run(std::integral_constant<int, 2>());
-    else run(std::integral_constant<int, 1>());
-    return GPUAR_OK;
-}
-
-static int launch_xor(bool merge, const gpuar::XorArgs &x, size_t n_tails, void *stream) {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const uint32_t blocks = x.p.n_packets < gpuar::kPlaneGridCap ? x.p.n_packets : gpuar::kPlaneGridCap;
-    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
-    if (merge) gpuar::merge_xor_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(x);
-    else gpuar::split_xor_kernel<<<blocks, gpuar::kPlaneThreads, 0, s>>>(x);
-    const int e = check_launch();
-    if (e != GPUAR_OK || tails == 0u) return e;
-    if (merge) gpuar::xor_tail_kernel<true><<<tails, gpuar::kPlaneThreads, 0, s>>>(x);
-    else gpuar::xor_tail_kernel<false><<<tails, gpuar::kPlaneThreads, 0, s>>>(x);
-    return check_launch();
-}
-
 static int xor_single(bool merge, const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!d_in || !d_out || !d_base || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_in) || !aligned16(d_out) || !aligned16(d_base)) return GPUAR_ERR_ALIGNMENT;
-    const uintptr_t in = reinterpret_cast<uintptr_t>(d_in), out = reinterpret_cast<uintptr_t>(d_out), base = reinterpret_cast<uintptr_t>(d_base);
-    if (in != out && in < out + n_bytes && out < in + n_bytes) return GPUAR_ERR_ARGUMENT;      // in place or apart, nothing in between
-    if (base < out + n_bytes && out < base + n_bytes) return GPUAR_ERR_ARGUMENT;               // the base is only read
-    gpuar::XorArgs x = {};                                                                     // (a width of 1 in place is work too)
-    x.p.in = d_in;
-    x.p.out = d_out;
-    x.p.n_bytes = n_bytes;
-    x.p.elem = elem_bytes;
-    x.p.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    gpuar::XorArgs x = {};
+    bool launch = false;
+    const int e = single_arguments(d_in, true, d_base, n_bytes, elem_bytes, d_out, &x.p, &launch);      // (a width of 1 in place is work too)
+    if (e != GPUAR_OK || !launch) return e;
     x.base = d_base;
-    return launch_xor(merge, x, n_bytes % (static_cast<size_t>(elem_bytes) * GPUAR_PACKET_BYTES) ? 1u : 0u, stream);
+    return launch_filter(kXorKernels, merge, x, x.p, stream);
 }
 
 static int xor_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
                      const uint64_t *d_elem_bytes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
                      uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    if (!d_elem_bytes || !d_base_ptrs || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_base_ptrs) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
-        return GPUAR_ERR_ALIGNMENT;
-    uint32_t *status = nullptr;
-    const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
-    if (e != GPUAR_OK) return e;
     gpuar::XorArgs x = {};
-    x.p.in_ptrs = d_in_ptrs;
-    x.p.out_ptrs = d_out_ptrs;
-    x.p.bytes = d_bytes;
-    x.p.first_packet = d_first_packet;
-    x.p.elem_bytes = d_elem_bytes;
-    x.p.n_buffers = static_cast<uint32_t>(n_buffers);
-    x.p.n_packets = static_cast<uint32_t>(n_packets);
-    x.p.status = status;
+    bool launch = false;
+    const int e = batch_filter_arguments(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, true, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
+                                         d_status, &x.p, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     x.base_ptrs = d_base_ptrs;
-    return launch_xor(merge, x, n_buffers, stream);
+    return launch_filter(kXorKernels, merge, x, x.p, stream);
 }
 
 int gpuar_hip_split_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t elem_bytes, uint8_t *d_out, void *stream) {
@@ -4361,12 +4331,9 @@ int gpuar_hip_merge_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d
 }
 
 static int xor_on_host(bool merge, const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
-    if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!in || !out || !base) return GPUAR_ERR_ARGUMENT;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out), c = reinterpret_cast<uintptr_t>(base);
-    if (a != b && a < b + n_bytes && b < a + n_bytes) return GPUAR_ERR_ARGUMENT;
-    if (c < b + n_bytes && b < c + n_bytes) return GPUAR_ERR_ARGUMENT;
+    bool work = false;
+    const int e = filter_checks(true, in, true, base, n_bytes, elem_bytes, out, &work);
+    if (e != GPUAR_OK || !work) return e;
     if (merge) gpuar::merge_xor_host(in, base, n_bytes, elem_bytes, out);
     else gpuar::split_xor_host(in, base, n_bytes, elem_bytes, out);
     return GPUAR_OK;
@@ -4378,6 +4345,28 @@ int gpuar_hip_split_xor_host(const uint8_t *in, const uint8_t *base, size_t n_by
 
 int gpuar_hip_merge_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
     return xor_on_host(true, in, base, n_bytes, elem_bytes, out);
+}
+
+// one 16-element block through delta.h's register transforms, as the kernels apply them, on the host (for the tests):
+// mixed: 4 * elem_bytes dwords, in place; undo = 0: delta_block with `carried` as pred; 1: undelta_block with it as offset.
+// *total (may be null) receives undelta_block's total.
+int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, uint64_t carried, uint64_t *total) {
+    if (!mixed || !gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
+    auto run = [&](auto width) {
+        constexpr int W = decltype(width)::value;
+        uint32_t block[4 * W];
+        memcpy(block, mixed, sizeof block);
+        uint64_t sum = 0;
+        if (undo) sum = gpuar::undelta_block<W>(block, carried);
+        else gpuar::delta_block<W>(block, carried);
+        memcpy(mixed, block, sizeof block);
+        if (total) *total = sum;
+    };
+    if (elem_bytes == 8u) run(std::integral_constant<int, 8>());
+    else if (elem_bytes == 4u) run(std::integral_constant<int, 4>());
+    else if (elem_bytes == 2u) run(std::integral_constant<int, 2>());
+    else run(std::integral_constant<int, 1>());
+    return GPUAR_OK;
 }
 
 static int launch_estimate(const gpuar::CrcArgs &a, void *stream) {
