@@ -143,7 +143,10 @@ class Compressed:
     Compressed with sparse="auto": `stored` is the packet's kind -- 0 coded, 1 raw, 2 sparse, so that a stable sort by it gives the
     coded, the raw and the sparse packets, each in batch order --, `sparse` (uint8, device) holds the sparse packets' records
     (gpuar_amd/csrc/sparse.h) back to back in batch order, `sparse_offsets` (int64, device, n_sparse + 1) where; `raw` and
-    `raw_offsets` are there too (empty without stored=...).  Both are None otherwise."""
+    `raw_offsets` are there too (empty without stored=...).  Both are None otherwise.
+
+    `kinds_rule`: (stored == "auto", sparse == "auto") where the packets' kinds were chosen by hip.sparse_rule -- what
+    gip(b, kinds=True) needs to know: such a buffer has a version-6 file, one with a list of stored packets has none."""
     stream: object
     offsets: object
     first_packet: list
@@ -157,6 +160,7 @@ class Compressed:
     based: list = None
     sparse: object = None
     sparse_offsets: object = None
+    kinds_rule: tuple = None
 
     @property
     def n_buffers(self) -> int:
@@ -197,14 +201,53 @@ class Compressed:
         lo, hi = self._coded_range(b)
         return self.stream[off[lo]:off[hi]]
 
-    def gip(self, b: int) -> bytes:
+    def _kinds_packets(self, b: int):
+        """(packet stream, clens, kinds) of buffer b with every packet in its stream form (gpuar_amd/csrc/kinds.h): the coded
+        packets as they are, the raw and the sparse ones behind a 4-byte header put in front of them here, on the host."""
+        lo, hi = self.first_packet[b], self.first_packet[b + 1]
+        kinds = self.stored.cpu().tolist()
+        rank = [0, 0, 0]                                   # how many packets of each kind stand in front of packet lo
+        for k in kinds[:lo]:
+            rank[k] += 1
+        off = self._offsets_host()
+        raw = self.raw.cpu().numpy().tobytes() if self.raw is not None else b""
+        raw_off = self.raw_offsets.cpu().tolist() if self.raw_offsets is not None else [0]
+        rec = self.sparse.cpu().numpy().tobytes() if self.sparse is not None else b""
+        rec_off = self.sparse_offsets.cpu().tolist() if self.sparse_offsets is not None else [0]
+        coded = self.stream.cpu().numpy().tobytes()
+        packets = []
+        for i, k in enumerate(kinds[lo:hi]):
+            ulen, r = min(H.PACKET, self.sizes[b] - i * H.PACKET), rank[k]
+            if k == H.KIND_CODED:
+                packets.append(coded[off[r]:off[r + 1]])
+            elif k == H.KIND_RAW:
+                packets.append(struct.pack("<HH", 4 + ulen, ulen) + raw[raw_off[r]:raw_off[r] + ulen])
+            else:
+                packets.append(struct.pack("<HH", 4 + rec_off[r + 1] - rec_off[r], ulen) + rec[rec_off[r]:rec_off[r + 1]])
+            rank[k] += 1
+        return b"".join(packets), [len(p) for p in packets], kinds[lo:hi]
+
+    def gip(self, b: int, kinds: bool = False) -> bytes:
         """Buffer b as a whole .gip file: what `gpuar c` writes for it (with CRCs: what `gpuar c --checksum` writes; split into
         planes of width W > 1: what `gpuar c --planes=W` writes; filtered: what `gpuar c --delta --planes=W` writes; XORed with
-        a base: what `gpuar c --base=FILE --planes=W` writes, which needs the CRCs -- GpuarError without checksum=True)."""
+        a base: what `gpuar c --base=FILE --planes=W` writes, which needs the CRCs -- GpuarError without checksum=True).
+        `kinds`: for a batch compressed with stored="auto" and / or sparse="auto", the file `gpuar c` writes with --stored=auto
+        and / or --sparse=auto beside those flags -- every packet behind its 4-byte header, a version-6 trailer that says which is
+        which; GpuarError for any other batch (a list of stored packets has no file form).  Without it a buffer that holds a
+        raw or sparse packet raises, as ever."""
         xored = bool(self.based[b]) if self.based is not None else False
         if xored and self.crc32 is None:
             raise GpuarError(f"buffer {b} was XORed with a base: its .gip form (trailer version 5) needs the CRCs that tell a reader "
                              "it was given the wrong base -- compress with checksum=True")
+        if kinds:
+            if self.kinds_rule is None or self.stored is None:
+                raise GpuarError("gip(kinds=True) is the file of a batch compressed with stored=\"auto\" and / or sparse=\"auto\"")
+            payload, clens, which = self._kinds_packets(b)
+            lo, hi = self.first_packet[b], self.first_packet[b + 1]
+            crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
+            return H.gip_header(self.sizes[b], len(payload)) + payload + trailer(
+                clens, self.planes[b] if self.planes is not None else 1, crcs, delta=bool(self.delta[b]) if self.delta is not None else False,
+                base=xored, kinds=which)
         p = self.payload(b)
         out = H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
         w = self.planes[b] if self.planes is not None else 1
@@ -219,22 +262,28 @@ class Compressed:
         return out
 
 
-def trailer(clens, elem_bytes=1, crcs=None, delta=False, base=False) -> bytes:
+def trailer(clens, elem_bytes=1, crcs=None, delta=False, base=False, kinds=None) -> bytes:
     """The .gip trailer, little-endian, pads counted from "GIPX": version 5 for a file whose bytes were XORed with
     a base and split at a width of `elem_bytes` (1 too; flags bit 2 and bit 0 set: the CRCs are mandatory), else version 4 for a
     file whose bytes went through the delta filter at a width of `elem_bytes` (1 too), else version 3 for a file whose bytes were split into planes of
     `elem_bytes` > 1, else version 2 when `crcs` are given, else version 1.
     "GIPX" u32 version u64 n | versions 3, 4: u32 elem_bytes u32 flags (bit 0: CRCs present; version 4: bit 1, delta, set) |
-    u16 clen[n] | with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG"."""
+    u16 clen[n] | with CRCs: pad to 4 u32 crc32[n] | pad to 8 | u64 trailer bytes "XPIG".
+    `kinds` (one of 0 coded, 1 raw, 2 sparse per packet): version 6, which has version 3's fields whatever the rest says, bit 3
+    of the flags set beside those above, and u8 kind[n] behind the CRCs (behind the pad to 4 where there are none)."""
     n = len(clens)
     if base and (delta or crcs is None):
         raise GpuarError("a version-5 trailer (base) carries CRCs and no delta flag")
-    body = b"GIPX" + struct.pack("<IQ", 5 if base else 4 if delta else 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
-    if elem_bytes > 1 or delta or base:
-        body += struct.pack("<II", elem_bytes, (0 if crcs is None else 1) | (2 if delta else 0) | (4 if base else 0))
+    if kinds is not None and (len(kinds) != n or any(k not in (0, 1, 2) for k in kinds)):
+        raise GpuarError("a version-6 trailer carries one kind (0, 1 or 2) per packet")
+    body = b"GIPX" + struct.pack("<IQ", 6 if kinds is not None else 5 if base else 4 if delta else 3 if elem_bytes > 1 else 1 if crcs is None else 2, n)
+    if elem_bytes > 1 or delta or base or kinds is not None:
+        body += struct.pack("<II", elem_bytes, (0 if crcs is None else 1) | (2 if delta else 0) | (4 if base else 0) | (0 if kinds is None else 8))
     body += struct.pack(f"<{n}H", *clens)
     if crcs is not None:
         body += bytes(-len(body) % 4) + struct.pack(f"<{n}I", *crcs)
+    if kinds is not None:
+        body += bytes(-len(body) % 4) + bytes(kinds)
     body += bytes(-len(body) % 8)
     return body + struct.pack("<Q", len(body) + 12) + b"XPIG"
 
@@ -759,7 +808,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
                       crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
                       raw_offsets=d_raw_offsets, delta=flags, based=[bool(q) for q in bases] if bases is not None else None,
-                      sparse=d_sparse, sparse_offsets=d_sparse_offsets)
+                      sparse=d_sparse, sparse_offsets=d_sparse_offsets,
+                      kinds_rule=(stored == "auto", sparse == "auto") if isinstance(stored, str) or sparse == "auto" else None)
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):

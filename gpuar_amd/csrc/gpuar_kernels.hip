@@ -52,6 +52,7 @@
 #include "survey.h"
 #include "delta_survey.h"
 #include "sparse.h"
+#include "kinds.h"
 
 namespace gpuar {
 
@@ -3319,6 +3320,273 @@ sparse_unpack_kernel(SparseUnpackArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// Raw and sparse packets in a packet stream (kinds.h): every packet keeps its 4-byte header, so a file's
+// stream is still walked by `off += clen` and compacted by gpuar_hip_compact.  Two bandwidth-bound passes over ALL packets of
+// one buffer (a pipeline chunk), one wavefront per packet, persistent; a coded packet's wavefront returns at once.
+//
+// kinds_store_kernel runs behind the encoder, which has filled every slot: it applies sparse_kind to est[p] and scan[p]
+// (scan null: sparse off), writes kind[p], and overwrites the slot of a raw packet with header + bytes (the lane's 128 bytes in
+// registers as crc_load leaves them, stored to slot + 4 by 4-byte-aligned quads; the last partial quad by dwords and bytes) and
+// the slot of a sparse packet with header + record (count, prefix sum and stores as sparse_pack_kernel: the same predicate over
+// the same registers, the total compared with scan >> 8 and the record's length with the slot BEFORE anything is written).  A
+// scan word that is not that of the bytes: BAD_BATCH, the slot stays the encoder's, kind[p] = 0 -- the stream is still valid.
+//
+// kinds_expand_kernel takes packet p of kind 1 or 2 out of a compacted stream, at any byte alignment, to out + 8192 p (16-byte
+// aligned): the header is checked against offsets[p + 1] - offsets[p] and the packet's bytes in n_bytes first (kinds.h); raw
+// bytes go by destination-aligned 16-byte stores fed from unaligned loads (as gather_kernel), the last partial quad by dwords
+// and bytes; a sparse packet is built in the wavefront's own 8 KiB of LDS as sparse_unpack_kernel builds it.  Nothing before
+// offsets[p] or from offsets[p + 1] on is read, nothing outside the packet's bytes is written.
+// ---------------------------------------------------------------------------
+typedef uint32_t KindsQuad4 __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at a 4-byte-aligned address
+typedef uint32_t KindsQuad1 __attribute__((ext_vector_type(4), aligned(1)));      // ... and at any address
+typedef uint32_t KindsWord1 __attribute__((aligned(1)));
+typedef uint16_t KindsHalf1 __attribute__((aligned(1)));
+
+struct KindsStoreArgs {
+    const uint8_t *in;
+    size_t n_bytes;
+    const uint32_t *est;
+    const uint32_t *scan;                   // null: sparse is off
+    uint32_t stored_on;
+    uint8_t *slots;
+    uint8_t *kind;
+    uint32_t n_packets;
+    uint32_t *status;
+};
+
+__global__ void __launch_bounds__(kSparseWaves * kLanes)
+kinds_store_kernel(KindsStoreArgs a) {
+    using GlobalQuad4 = __attribute__((address_space(1))) KindsQuad4;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    const uint32_t lane = threadIdx.x & 63u;
+    GlobalByte *kinds = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_packets; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+        const size_t first = static_cast<size_t>(r) * kPacket;
+        const uint32_t n = a.n_bytes - first < kPacket ? static_cast<uint32_t>(a.n_bytes - first) : kPacket;
+        const uint32_t est = __builtin_amdgcn_readfirstlane(a.est[r]);
+        const uint32_t scan = a.scan ? __builtin_amdgcn_readfirstlane(a.scan[r]) : kSparseNone;
+        const uint32_t kind = sparse_kind(scan, est, n, a.stored_on != 0u);         // wave-uniform
+        if (kind == kSparseCoded) {                          // the slot is the encoder's
+            if (lane == 0u) kinds[r] = static_cast<uint8_t>(kSparseCoded);
+            continue;
+        }
+        const uintptr_t slot = reinterpret_cast<uintptr_t>(a.slots) + static_cast<size_t>(r) * kSlot;
+        const CrcPacket p = {a.in + first, n};
+        CrcQuad q[8];
+        crc_load(q, p, lane);
+        const uint32_t start = kCrcChunk * lane;
+        const uint32_t have = n > start ? (n - start < kCrcChunk ? n - start : kCrcChunk) : 0u;
+        if (kind == kSparseRaw) {                            // 4 + n <= 8196 bytes of the slot
+            if (lane == 0u) {
+                *reinterpret_cast<GlobalWord *>(slot) = kinds_header(kinds_raw_clen(n), n);
+                kinds[r] = static_cast<uint8_t>(kSparseRaw);
+            }
+            const uintptr_t dst = slot + kKindsHeader + start;
+#pragma unroll
+            for (uint32_t i = 0; i < 8; ++i) {
+                const uint32_t at = 16u * i;
+                if (at >= have) continue;
+                const uint32_t left = have - at;
+                if (left >= 16u) {
+                    *reinterpret_cast<GlobalQuad4 *>(dst + at) = q[i];
+                } else {                                     // the packet's last, partial quad: nothing behind byte n
+                    const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+                    GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
+                    GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+#pragma unroll
+                    for (uint32_t j = 0; j < 4; ++j) {
+                        if (4u * j + 4u <= left) {
+                            words[j] = w[j];
+                        } else {
+#pragma unroll
+                            for (uint32_t b = 0; b < 3; ++b)
+                                if (4u * j + b < left) bytes[4u * j + b] = static_cast<uint8_t>(w[j] >> (8u * b));
+                        }
+                    }
+                }
+            }
+            continue;
+        }
+        const uint32_t fill = scan & 255u, k = scan >> 8;   // (sparse_kind took the word: it is not kSparseNone)
+        uint32_t mine = 0;                                   // the lane's exceptions
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j)
+                mine += __popc(~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(16u * i + 4u * j, have));
+        }
+        uint32_t upto = mine;                                // inclusive prefix sum over the wave
+#pragma unroll
+        for (uint32_t off = 1; off < 64u; off <<= 1) {
+            const uint32_t below = __shfl_up(upto, off);
+            if (lane >= off) upto += below;
+        }
+        const uint32_t total = __shfl(upto, 63);
+        if (total != k || 2u * k >= n || kinds_sparse_clen(k) > kSlot) {      // wave-uniform; nothing has been written to the slot
+            if (lane == 0u) {
+                atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                kinds[r] = static_cast<uint8_t>(kSparseCoded);
+            }
+            continue;
+        }
+        GlobalHalf *pos = reinterpret_cast<GlobalHalf *>(slot + kKindsHeader + 4u);
+        GlobalByte *val = reinterpret_cast<GlobalByte *>(slot + kKindsHeader + 4u + 2u * k);
+        if (lane == 0u) {
+            *reinterpret_cast<GlobalWord *>(slot) = kinds_header(kinds_sparse_clen(k), n);
+            *reinterpret_cast<GlobalWord *>(slot + kKindsHeader) = sparse_head(fill, k);
+            kinds[r] = static_cast<uint8_t>(kSparseSparse);
+        }
+        if (lane < sparse_len(k) - (4u + 3u * k)) val[k + lane] = 0;           // the pad
+        uint32_t at_slot = upto - mine;                      // < k wherever a store below is reached: the same predicate was counted
+#pragma unroll
+        for (uint32_t i = 0; i < 8; ++i) {
+            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+            for (uint32_t j = 0; j < 4; ++j) {
+                const uint32_t at = 16u * i + 4u * j;
+                const uint32_t differ = ~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(at, have);
+                if (differ != 0u) {
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; ++b) {
+                        if (differ & (0x80u << (8u * b))) {
+                            pos[at_slot] = static_cast<uint16_t>(start + at + b);
+                            val[at_slot] = static_cast<uint8_t>(w[j] >> (8u * b));
+                            ++at_slot;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+struct KindsExpandArgs {
+    const uint8_t *stream;
+    const uint64_t *offsets;
+    const uint8_t *kind;
+    uint32_t n_packets;
+    uint8_t *out;
+    size_t n_bytes;
+    uint32_t *status;
+};
+
+__global__ void __launch_bounds__(kSparseWaves * kLanes)
+kinds_expand_kernel(KindsExpandArgs a) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    using LooseQuad = const __attribute__((address_space(1))) KindsQuad1;
+    using LooseWord = const __attribute__((address_space(1))) KindsWord1;
+    using LooseHalf = const __attribute__((address_space(1))) KindsHalf1;
+    __shared__ PlanesQuad lds[kSparseWaves * (kPacket / 16u)];
+    const uint32_t lane = threadIdx.x & 63u;
+    PlanesQuad *quads = lds + (threadIdx.x >> 6) * (kPacket / 16u);          // the wavefront's own packet
+    uint8_t *packet = reinterpret_cast<uint8_t *>(quads);
+    const GlobalByte *kinds = reinterpret_cast<const GlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
+    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_packets; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+        const uint32_t kind = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(kinds[r]));
+        if (kind == kSparseCoded) continue;                  // the decoder's
+        const size_t first = static_cast<size_t>(r) * kPacket;
+        const uint32_t n = a.n_bytes - first < kPacket ? static_cast<uint32_t>(a.n_bytes - first) : kPacket;
+        const uint64_t off = a.offsets[r], end = a.offsets[r + 1u];
+        const uint64_t pkt_bytes = end - off;
+        if (kind > kSparseSparse || end < off || pkt_bytes < kKindsHeader || pkt_bytes > kSlot) {        // wave-uniform; nothing of the stream is read
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+            continue;
+        }
+        const uintptr_t src = reinterpret_cast<uintptr_t>(a.stream) + off, dst = reinterpret_cast<uintptr_t>(a.out) + first;
+        const uint32_t header = __builtin_amdgcn_readfirstlane(*reinterpret_cast<LooseWord *>(src));
+        if (kind == kSparseRaw) {
+            if (!kinds_raw_ok(header, pkt_bytes, n)) {       // the destination is left as it was
+                if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+                continue;
+            }
+            const uintptr_t body = src + kKindsHeader;       // n bytes: up to offsets[r + 1]
+#pragma unroll
+            for (uint32_t j = 0; j < 8; ++j) {
+                const uint32_t at = 16u * (lane + 64u * j);
+                if (at >= n) continue;
+                const uint32_t left = n - at;
+                if (left >= 16u) {
+                    const PlanesQuad whole = *reinterpret_cast<LooseQuad *>(body + at);
+                    reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = whole;
+                } else {                                     // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
+                    GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
+                    GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+#pragma unroll
+                    for (uint32_t d = 0; d < 4; ++d) {
+                        if (4u * d + 4u <= left) {
+                            words[d] = *reinterpret_cast<LooseWord *>(body + at + 4u * d);
+                        } else {
+#pragma unroll
+                            for (uint32_t b = 0; b < 3; ++b)
+                                if (4u * d + b < left) bytes[4u * d + b] = *reinterpret_cast<const GlobalByte *>(body + at + 4u * d + b);
+                        }
+                    }
+                }
+            }
+            continue;
+        }
+        const uintptr_t rec = src + kKindsHeader;
+        const uint64_t rec_bytes = pkt_bytes - kKindsHeader;
+        const uint32_t head = kinds_header_ok(header, pkt_bytes, n) && rec_bytes >= 4u
+                                  ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<LooseWord *>(rec)) : 0xFFFFFFFFu;
+        if (!kinds_header_ok(header, pkt_bytes, n) || rec_bytes < 4u || !sparse_head_ok(head, rec_bytes, n)) {      // wave-uniform; nothing behind the head is read
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+            continue;
+        }
+        const uint32_t fill = head & 255u, k = head >> 16;                    // 4 + 3 k <= rec_bytes, 2 k < n
+        LooseHalf *pos = reinterpret_cast<LooseHalf *>(rec + 4u);
+        const GlobalByte *val = reinterpret_cast<const GlobalByte *>(rec + 4u + 2u * k);
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j)
+            if (16u * (lane + 64u * j) < n) quads[lane + 64u * j] = PlanesQuad(fill * kSparseLow);
+        asm volatile("" ::: "memory");                       // the fill in front of the exceptions, which other lanes write
+        bool bad = false;
+        for (uint32_t i = lane; i < k; i += 64u) {
+            const uint32_t at = pos[i], v = val[i];
+            const bool ascending = i == 0u || pos[i - 1u] < at;
+            if (at < n && v != fill && ascending) packet[at] = static_cast<uint8_t>(v);      // at < n <= 8192: inside the wavefront's LDS
+            else bad = true;
+        }
+        if (__any(bad)) {                                    // the destination is left as it was
+            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
+            asm volatile("" ::: "memory");
+            continue;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's exceptions in front of the reads of whole quads
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) {
+            const uint32_t at = 16u * (lane + 64u * j);
+            if (at >= n) continue;
+            const uint32_t left = n - at;
+            const PlanesQuad v = quads[lane + 64u * j];
+            if (left >= 16u) {
+                reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = v;
+            } else {                                         // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
+                GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+#pragma unroll
+                for (uint32_t d = 0; d < 4; ++d) {
+                    if (4u * d + 4u <= left) {
+                        words[d] = w[d];
+                    } else {
+#pragma unroll
+                        for (uint32_t b = 0; b < 3; ++b)
+                            if (4u * d + b < left) bytes[4u * d + b] = static_cast<uint8_t>(w[d] >> (8u * b));
+                    }
+                }
+            }
+        }
+        asm volatile("" ::: "memory");                       // these reads in front of the next packet's fill
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Plane-width survey (survey.h): est[j][p] = estimate(split_planes(buffer, 1 << j))[p] for the four widths at
 // once, from one read of the original bytes and without making any split, for one buffer or a batch.
 //
@@ -4647,6 +4915,68 @@ int gpuar_hip_sparse_pack_host(const uint8_t *in, size_t n_bytes, uint8_t *rec, 
 int gpuar_hip_sparse_unpack_host(const uint8_t *rec, size_t rec_bytes, uint8_t *out, size_t n_bytes) {
     if (!rec || !out || n_bytes == 0 || n_bytes > gpuar::kSparsePacket) return GPUAR_ERR_ARGUMENT;
     return gpuar::sparse_unpack_host(rec, rec_bytes, out, static_cast<uint32_t>(n_bytes)) ? GPUAR_OK : GPUAR_ERR_ARGUMENT;
+}
+
+static uint32_t kinds_blocks(uint32_t n_packets) {
+    const uint32_t groups = n_packets / gpuar::kSparseWaves + (n_packets % gpuar::kSparseWaves ? 1u : 0u);
+    return groups < gpuar::kSparseGroups ? groups : gpuar::kSparseGroups;
+}
+
+int gpuar_hip_kinds_store(const uint8_t *d_in, size_t n_bytes, const uint32_t *d_est, const uint32_t *d_scan, int stored_on, uint8_t *d_slots,
+                          uint8_t *d_kind, uint32_t *d_status, void *stream) {
+    uint32_t *status = nullptr;
+    bool launch = false;
+    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, d_status, &status, &launch);     // the estimate call's checks
+    if (e != GPUAR_OK || !launch) return e;
+    if (!d_slots || !d_kind) return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_slots) || (reinterpret_cast<uintptr_t>(d_scan) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    gpuar::KindsStoreArgs a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.est = d_est;
+    a.scan = d_scan;
+    a.stored_on = stored_on != 0 ? 1u : 0u;
+    a.slots = d_slots;
+    a.kind = d_kind;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.status = status;
+    gpuar::kinds_store_kernel<<<kinds_blocks(a.n_packets), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_kinds_expand(const uint8_t *d_stream, const uint64_t *d_offsets, const uint8_t *d_kind, size_t n_packets, uint8_t *d_out,
+                           size_t n_bytes, uint32_t *d_status, void *stream) {
+    if (n_packets == 0) return GPUAR_OK;
+    if (!d_stream || !d_offsets || !d_kind || !d_out || n_packets > 0xFFFFFFFFull || gpuar_hip_packet_count(n_bytes) != n_packets)
+        return GPUAR_ERR_ARGUMENT;
+    if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    gpuar::KindsExpandArgs a = {};
+    a.stream = d_stream;
+    a.offsets = d_offsets;
+    a.kind = d_kind;
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.out = d_out;
+    a.n_bytes = n_bytes;
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    gpuar::kinds_expand_kernel<<<kinds_blocks(a.n_packets), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+int gpuar_hip_kinds_store_host(const uint8_t *in, size_t n_bytes, int stored_on, int sparse_on, uint8_t *pkt, size_t room, uint32_t *kind,
+                               size_t *clen) {
+    if (!in || !kind || !clen || n_bytes == 0 || n_bytes > gpuar::kKindsPacket || (!pkt && room)) return GPUAR_ERR_ARGUMENT;
+    uint32_t len = 0;
+    const uint32_t k = gpuar::kinds_store_packet(in, static_cast<uint32_t>(n_bytes), stored_on != 0, sparse_on != 0, pkt, room, &len);
+    if (k == ~0u) return GPUAR_ERR_ARGUMENT;
+    *kind = k;
+    *clen = len;
+    return GPUAR_OK;
+}
+
+int gpuar_hip_kinds_expand_host(const uint8_t *pkt, size_t pkt_bytes, uint32_t kind, uint8_t *out, size_t n_bytes) {
+    if (!pkt || !out || n_bytes == 0 || n_bytes > gpuar::kKindsPacket) return GPUAR_ERR_ARGUMENT;
+    return gpuar::kinds_expand_packet(pkt, pkt_bytes, kind, out, static_cast<uint32_t>(n_bytes)) ? GPUAR_OK : GPUAR_ERR_ARGUMENT;
 }
 
 int gpuar_hip_status(uint32_t *flags) {

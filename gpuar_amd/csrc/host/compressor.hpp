@@ -50,6 +50,9 @@ class Compressor {
                                       // so in a version-5 trailer, with CRCs; decompress: the base a version-5 file needs
     int baseFd = -1;                  // ... open while a job runs (openBase)
     bool checksumAsked = false;       // what setWriteChecksum was given: a base turns writeChecksum on by itself
+    bool stored = false;              // compress (`--stored=auto`): a packet whose estimate says it does not shrink is kept raw, and
+    bool sparse = false;              // (`--sparse=auto`) one that is a single byte value almost everywhere as that byte and its exceptions
+                                      // (../kinds.h); either says so in a version-6 trailer, whatever the packets turn out to be
 
     // the first min(file size, kSurveyPrefix) bytes of the input, from one pread: what choosePlanes and chooseFilter survey
     std::vector<uint8_t> readSurveyPrefix() const;
@@ -74,6 +77,11 @@ class Compressor {
         return std::runtime_error("Incorrect file format: the trailer says the file was XORed with a base (version 5) but it is damaged, "
                                   "carries a width other than 1, 2, 4 or 8, lacks the base flag or the checksums, or carries flags this gpuar does not know");
     }
+    // the same for a trailer that says which packets are raw or sparse: going on would feed raw bytes to the decoder
+    static std::runtime_error kindsTrailerError() {
+        return std::runtime_error("Incorrect file format: the trailer says the file holds raw or sparse packets (version 6) but it is damaged, "
+                                  "carries a width other than 1, 2, 4 or 8, a packet kind above 2, lacks the kinds flag, or carries flags this gpuar does not know");
+    }
     static std::runtime_error planesPacketError(size_t packet) {
         return std::runtime_error("Incorrect file format: packet " + std::to_string(packet) + " of a file of byte planes is not the last one and "
                                   "does not hold 8192 bytes");
@@ -91,8 +99,9 @@ class Compressor {
         if (status == Trailer::Status::unusable) throw planesTrailerError();
         if (status == Trailer::Status::unusable_delta) throw deltaTrailerError();
         if (status == Trailer::Status::unusable_base) throw baseTrailerError();
+        if (status == Trailer::Status::unusable_kinds) throw kindsTrailerError();
         if (trailer.based() && !based())
-            throw std::runtime_error("This file was compressed against a base (trailer version 5): pass the same file with --base=FILE");
+            throw std::runtime_error("This file was compressed against a base (trailer version " + std::to_string(trailer.version) + "): pass the same file with --base=FILE");
         if (!trailer.based() && based())
             throw std::runtime_error("--base was given, but this file was not compressed against a base (no version-5 trailer)");
         if (status == Trailer::Status::malformed) warnMalformedTrailer();
@@ -100,9 +109,12 @@ class Compressor {
     }
     // compress: whether the options ask for a trailer, and that trailer appended at the current position of the output
     bool based() const { return !baseFileName.empty(); }
-    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta || based(); }
-    void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs) {
-        if (wantsTrailer()) Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta, based());
+    bool mixed() const { return stored || sparse; }
+    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta || based() || mixed(); }
+    // `kinds`: of every packet, read only where mixed()
+    void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs, const std::vector<uint8_t> &kinds) {
+        if (wantsTrailer())
+            Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta, based(), mixed() ? &kinds : nullptr);
     }
     // Opens the base file and checks that it holds exactly `expect` bytes (those of `what`); with the delta filter on it throws:
     // that combination is not built.  closeFiles() closes it.
@@ -150,6 +162,8 @@ class Compressor {
         planes = elem_bytes;
     }
     void setDelta(bool on) { delta = on; }
+    void setStored(bool on) { stored = on; }
+    void setSparse(bool on) { sparse = on; }
     int getPlanes() const { return planes; }
     // compress: XOR against this file (implies the checksums); decompress: the base of a version-5 file.  Empty: none.
     void setBaseFileName(const std::string &fileName) {

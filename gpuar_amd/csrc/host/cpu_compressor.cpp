@@ -11,11 +11,14 @@
 #include <thread>
 #include <vector>
 
+#include <unistd.h>
+
 #include "../crc32.h"
 #include "../lane_codec.h"
 #include "../planes.h"
 #include "../delta.h"
 #include "../xorbase.h"
+#include "../kinds.h"
 #include "file_header.hpp"
 #include "packet_index.hpp"
 
@@ -115,6 +118,7 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
     std::vector<uint32_t> all_crcs;                    // for the optional checksum trailer
+    std::vector<uint8_t> kind(kBatchPackets), all_kinds;      // --stored / --sparse: what every packet is kept as (version-6 trailer)
     const bool trailer = wantsTrailer();
     try {
         if (based()) openBase(info.uncompressedFileSize, "the input");
@@ -134,7 +138,14 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
             for_each_packet(np, nthreads, [&](size_t p) {
                 const size_t off = p * gpuar::kPacket;
                 const uint32_t len = static_cast<uint32_t>(std::min<size_t>(gpuar::kPacket, got - off));
-                clen[p] = static_cast<uint32_t>(encode_one(coded + off, len, slots.data() + p * gpuar::kSlot));
+                // --stored=auto / --sparse=auto: the rule of ../kinds.h over the bytes that are coded; a raw or sparse packet is
+                // its own stream form in the slot (what the GPU pipeline overwrites the encoder's packet with), a coded one as ever
+                uint32_t kept = 0;
+                if (mixed()) {
+                    kind[p] = static_cast<uint8_t>(gpuar::kinds_store_packet(coded + off, len, stored, sparse, slots.data() + p * gpuar::kSlot, gpuar::kSlot, &kept));
+                    if (kind[p] > gpuar::kSparseSparse) throw std::runtime_error("a packet outgrew its 8704-byte slot");
+                }
+                clen[p] = kept ? kept : static_cast<uint32_t>(encode_one(coded + off, len, slots.data() + p * gpuar::kSlot));
                 if (writeChecksum) crc[p] = gpuar::crc32_update(0, in.data() + off, len);
             });
             process_timer.stop();
@@ -145,13 +156,14 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
                 info.compressedFileSize += clen[p];
                 if (trailer) all_clens.push_back(static_cast<uint16_t>(clen[p]));
                 if (writeChecksum) all_crcs.push_back(crc[p]);
+                if (mixed()) all_kinds.push_back(kind[p]);
             }
             io_timer.stop();
             info.processedUncompressedSize += got;
             monitor->updateProgress(&info);
         }
         io_timer.start();
-        saveTrailer(all_clens, all_crcs);
+        saveTrailer(all_clens, all_crcs, all_kinds);
         FileHeader header;
         header.setCompressedFileSize(info.compressedFileSize);
         header.setUncompressedFileSize(info.uncompressedFileSize);
@@ -178,6 +190,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
     openFiles();
     FileHeader header;
     const size_t fileSize = getFileSize(openFile);
+    bool mixed_file = false;                     // a version-6 file: a failed job leaves an empty output, as the GPU pipeline does
     try {
         if (std::fread(header.getData(), FileHeader::HEADER_LENGTH, 1, openFile) != 1 || !header.checkHeaderVersion())
             throw std::runtime_error("Incorrect file format");
@@ -187,7 +200,8 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         // packets hold (merged back below), as far as the file's trailer gives them
         const Trailer trailer = loadTrailer(stream_end, fileSize);
         const std::vector<uint16_t> &index = trailer.clens;
-        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging();
+        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging(), mixed = trailer.mixed();
+        mixed_file = mixed;
         size_t first_packet = 0;                 // of the window
         io_timer.stop();
 
@@ -213,7 +227,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                     const size_t c = index[next_packet++];
                     // (byte planes: no packet longer than a slot, so that every window but the last holds kBatchPackets packets,
                     // a whole number of groups)
-                    if (c < gpuar::kHdr || (merging && c > gpuar::kSlot)) throw std::runtime_error("Incorrect file format");
+                    if (c < gpuar::kHdr || ((merging || mixed) && c > gpuar::kSlot)) throw std::runtime_error("Incorrect file format");
                     bytes += c;
                     offsets[++np] = bytes;
                 }
@@ -243,8 +257,21 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
             process_timer.start();
             uint8_t *const plain = merging ? decoded.data() : out.data();
             for_each_packet(np, nthreads, [&](size_t p) {
-                ulen[p] = static_cast<uint32_t>(decode_one(window.data() + offsets[p], window.data() + bytes, plain + p * gpuar::kPacket));
+                const uint8_t *pkt = window.data() + offsets[p];
+                const uint32_t kind = mixed ? trailer.kinds[first_packet + p] : gpuar::kSparseCoded;
+                if (kind == gpuar::kSparseCoded) {
+                    ulen[p] = static_cast<uint32_t>(decode_one(pkt, window.data() + bytes, plain + p * gpuar::kPacket));
+                } else {                                   // raw or sparse (../kinds.h): the header is checked, the decoder never sees it
+                    const uint32_t n = pkt[2] | static_cast<uint32_t>(pkt[3]) << 8;
+                    if (!gpuar::kinds_expand_packet(pkt, offsets[p + 1] - offsets[p], kind, plain + p * gpuar::kPacket, n))
+                        throw std::runtime_error("Incorrect file format (malformed " + std::string(kind == gpuar::kSparseRaw ? "raw" : "sparse") + " packet " +
+                                                 std::to_string(first_packet + p) + ")");
+                    ulen[p] = n;
+                }
             });
+            // (raw and sparse packets: every packet but the file's last holds 8192 bytes, as the GPU pipeline requires of such a file)
+            if (mixed)
+                for (size_t p = 0; p < np; ++p) checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
             if (merging) {
                 size_t total = 0;
                 for (size_t p = 0; p < np; ++p) {
@@ -282,6 +309,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         closeFiles();
         io_timer.stop();
     } catch (...) {
+        if (mixed_file && saveFile && (std::fflush(saveFile) != 0 || ::ftruncate(fileno(saveFile), 0) != 0)) {}
         closeFiles();
         throw;
     }

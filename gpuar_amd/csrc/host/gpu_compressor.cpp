@@ -426,6 +426,12 @@ struct GPUCompressor::DeviceBuffers {
     uint32_t *h_crc = nullptr;      // pinned, the same
     uint8_t *d_planes = nullptr;    // cap * 8192 (--planes, --delta / a version-3 or -4 trailer): the chunk split into byte planes, or merged back
     uint8_t *d_base = nullptr;      // cap * 8192 (--base / a version-5 trailer): the base's bytes of the chunk's byte range
+    uint32_t *d_est = nullptr;      // cap estimates and cap scan words (--stored / --sparse): what the kind of every packet is decided from
+    uint32_t *d_scan = nullptr;
+    uint8_t *d_kind = nullptr;      // cap packet kinds (--stored / --sparse, a version-6 trailer)
+    uint8_t *h_kind = nullptr;      // pinned, the same
+    uint64_t *d_desc = nullptr;     // 4 * (cap + 1): a version-6 chunk's coded packets as a batch of one-packet buffers (decodeChunk)
+    uint64_t *h_desc = nullptr;     // pinned, the same
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
     // the lane's pinned pieces and which of them are free
@@ -470,10 +476,36 @@ struct GPUCompressor::DeviceBuffers {
     void allocateBase() {
         if (!d_base) hip_check(hipMalloc(reinterpret_cast<void **>(&d_base), cap * kPacket), "hipMalloc");
     }
+    // room for a chunk's packet kinds: only for a job that writes or reads raw and sparse packets (compress --stored / --sparse,
+    // with the estimates and scan words they are decided from; decompress of a file with a version-6 trailer, with the
+    // descriptors of its coded packets); the current device is the lane's
+    void allocateKinds(bool compressing) {
+        if (!d_kind) {
+            hip_check(hipMalloc(reinterpret_cast<void **>(&d_kind), cap), "hipMalloc");
+            hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_kind), cap, hipHostMallocDefault), "hipHostMalloc");
+        }
+        // (an object's lanes outlive a job: the next one may go the other way)
+        if (compressing && !d_est) {
+            hip_check(hipMalloc(reinterpret_cast<void **>(&d_est), cap * sizeof(uint32_t)), "hipMalloc");
+            hip_check(hipMalloc(reinterpret_cast<void **>(&d_scan), cap * sizeof(uint32_t)), "hipMalloc");
+        } else if (!compressing && !d_desc) {
+            hip_check(hipMalloc(reinterpret_cast<void **>(&d_desc), 4 * (cap + 1) * sizeof(uint64_t)), "hipMalloc");
+            hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_desc), 4 * (cap + 1) * sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc");
+        }
+    }
     void release() {
         if (!cap) return;
         (void)hipSetDevice(device);
         (void)hipFree(d_plain);
+        if (d_kind) (void)hipFree(d_kind);
+        if (h_kind) (void)hipHostFree(h_kind);
+        if (d_est) (void)hipFree(d_est);
+        if (d_scan) (void)hipFree(d_scan);
+        if (d_desc) (void)hipFree(d_desc);
+        if (h_desc) (void)hipHostFree(h_desc);
+        d_kind = h_kind = nullptr;
+        d_est = d_scan = nullptr;
+        d_desc = h_desc = nullptr;
         if (d_base) (void)hipFree(d_base);
         d_base = nullptr;
         if (d_planes) (void)hipFree(d_planes);
@@ -616,20 +648,31 @@ struct GPUCompressor::DeviceBuffers {
     // `planes` > 1: what is coded is the chunk split into byte planes of elements that wide (d_planes); the CRCs stay the input's
     // `delta`: ... of the elements' differences (at a width of 1 too)
     // `based`: ... of the chunk XORed with d_base (at a width of 1 too)
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta, bool based = false) {
+    // `stored` / `sparse`: behind the encoder, the packets the rule of ../kinds.h keeps raw or sparse overwrite their slots (every packet
+    // is coded first: the CLI is bound by the file system, not by the encoder); the kinds go to h_kind[0..n_packets)
+    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta, bool based = false, bool stored = false,
+                       bool sparse = false) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
         if (based) gpuar_check(gpuar_hip_split_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_xor");
         else if (delta) gpuar_check(gpuar_hip_split_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_delta");
         else if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
-        gpuar_check(gpuar_hip_encode_mode(planes > 1 || delta || based ? d_planes : d_plain, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
+        const uint8_t *coded = planes > 1 || delta || based ? d_planes : d_plain;
+        gpuar_check(gpuar_hip_encode_mode(coded, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
+        if (stored || sparse) {
+            gpuar_check(gpuar_hip_estimate(coded, n_plain, d_est, stream), "gpuar_hip_estimate");
+            if (sparse) gpuar_check(gpuar_hip_sparse_scan(coded, n_plain, d_scan, stream), "gpuar_hip_sparse_scan");
+            gpuar_check(gpuar_hip_kinds_store(coded, n_plain, d_est, sparse ? d_scan : nullptr, stored ? 1 : 0, d_slots, d_kind, d_status, stream),
+                        "gpuar_hip_kinds_store");
+        }
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
         if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets, d_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         if (checksum) hip_check(hipMemcpyAsync(h_crc, d_crc, n_packets * sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        if (stored || sparse) hip_check(hipMemcpyAsync(h_kind, d_kind, n_packets, hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipStreamSynchronize(stream), "sync");
         flags = *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1);
         noteBusy();
@@ -642,8 +685,11 @@ struct GPUCompressor::DeviceBuffers {
     // `planes` > 1: the n_plain decoded bytes are byte planes, merged into d_planes before they are verified; the result is there
     // `delta`: ... of differences, summed up by the merge (at a width of 1 too)
     // `based`: ... XORed with d_base by the merge (at a width of 1 too)
+    // `kinds` (n_packets values, or null: every packet is coded): the chunk of a version-6 file, whose packets all hold 8192 bytes but
+    // the last.  Its coded packets are decoded as a batch of one-packet buffers (raw bytes are never fed to the decoder; a chunk
+    // without a coded packet launches no decoder), then one launch takes the raw and sparse ones out of the stream
     uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1,
-                         bool delta = false, bool based = false) {
+                         bool delta = false, bool based = false, const uint8_t *kinds = nullptr) {
         hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
         uint64_t *d_first_bad = crcs ? reinterpret_cast<uint64_t *>(d_crc + crcSlots()) : nullptr;
@@ -653,7 +699,30 @@ struct GPUCompressor::DeviceBuffers {
             hip_check(hipMemsetAsync(d_first_bad, 0xFF, sizeof(uint64_t), stream), "memset");
         }
         hip_check(hipEventRecord(t0, stream), "event");
-        gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
+        if (kinds) {
+            uint64_t *out_ptrs = h_desc, *out_bytes = h_desc + (cap + 1), *first = h_desc + 2 * (cap + 1), *coded_at = h_desc + 3 * (cap + 1);
+            size_t n_coded = 0;
+            for (size_t p = 0; p < n_packets; ++p) {
+                if (kinds[p] != 0) continue;
+                out_ptrs[n_coded] = reinterpret_cast<uint64_t>(d_plain + p * kPacket);
+                out_bytes[n_coded] = std::min<uint64_t>(kPacket, n_plain - p * kPacket);
+                first[n_coded] = n_coded;
+                coded_at[n_coded++] = h_offsets[p];
+            }
+            first[n_coded] = n_coded;
+            coded_at[n_coded] = h_offsets[n_packets];
+            std::memcpy(h_kind, kinds, n_packets);
+            hip_check(hipMemcpyAsync(d_kind, h_kind, n_packets, hipMemcpyHostToDevice, stream), "H2D");
+            if (n_coded) {
+                hip_check(hipMemcpyAsync(d_desc, h_desc, 4 * (cap + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
+                gpuar_check(gpuar_hip_decode_stream_batch(d_stream, d_desc + 3 * (cap + 1), d_desc + 2 * (cap + 1), n_coded, n_coded,
+                                                          reinterpret_cast<uint8_t *const *>(d_desc), d_desc + (cap + 1), d_status, stream),
+                            "gpuar_hip_decode_stream_batch");
+            }
+            gpuar_check(gpuar_hip_kinds_expand(d_stream, d_offsets, d_kind, n_packets, d_plain, n_plain, d_status, stream), "gpuar_hip_kinds_expand");
+        } else {
+            gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
+        }
         if (based) gpuar_check(gpuar_hip_merge_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_xor");
         else if (delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_delta");
         else if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
@@ -822,6 +891,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
         const bool trailer = wantsTrailer();
         std::vector<std::vector<uint16_t>> chunk_clens(trailer ? n_chunks : 0);        // for the optional index trailer
         std::vector<std::vector<uint32_t>> chunk_crcs(writeChecksum ? n_chunks : 0);   // and the checksums in it
+        std::vector<std::vector<uint8_t>> chunk_kinds(mixed() ? n_chunks : 0);         // and the packet kinds (--stored / --sparse)
         std::vector<std::atomic<size_t>> next_of_device(G);
         for (auto &n : next_of_device) n = 0;
         std::vector<std::atomic<uint64_t>> device_bytes(G), device_chunks(G);      // what each device coded (GPUAR_TRACE)
@@ -854,6 +924,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (writeChecksum) b.allocateCrc();
                             if (planes > 1 || delta || based()) b.allocatePlanes();
                             if (based()) b.allocateBase();
+                            if (mixed()) b.allocateKinds(true);
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const uint64_t at = chunk_at[c];
                             const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
@@ -861,7 +932,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (based()) b.uploadBase(baseFd, at, n_plain);      // the same byte range of the base
                             if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
                             uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta, based());     // (synchronises the lane's stream)
+                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta, based(), stored, sparse);     // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(at, n_plain);
                             // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
                             // (src/gpu_compressor.cpp:146-150)
@@ -870,8 +941,11 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
                             if (flags & GPUAR_STATUS_SLOT_OVERFLOW)
                                 throw std::runtime_error("a packet outgrew its 8704-byte slot (input bytes " + std::to_string(at) + " .. " +
                                                          std::to_string(at + n_plain) + ")");
+                            // (the scan words are computed from the very bytes: this cannot happen, and the file would still be valid)
+                            if (flags & GPUAR_STATUS_BAD_BATCH) throw std::runtime_error("Fail to execute kernel code: gpuar_hip_kinds_store: inconsistent scan");
                             const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
                             if (writeChecksum) chunk_crcs[c].assign(b.h_crc, b.h_crc + n_packets);
+                            if (mixed()) chunk_kinds[c].assign(b.h_kind, b.h_kind + n_packets);
                             if (trailer) {
                                 chunk_clens[c].resize(n_packets);
                                 for (size_t p = 0; p < n_packets; ++p) chunk_clens[c][p] = static_cast<uint16_t>(b.h_offsets[p + 1] - b.h_offsets[p]);
@@ -907,7 +981,9 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
             std::vector<uint32_t> crcs;
             for (const auto &v : chunk_crcs) crcs.insert(crcs.end(), v.begin(), v.end());
             if (std::fseek(saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
-            saveTrailer(all, crcs);
+            std::vector<uint8_t> kinds;
+            for (const auto &v : chunk_kinds) kinds.insert(kinds.end(), v.begin(), v.end());
+            saveTrailer(all, crcs, kinds);
             if (std::fflush(saveFile) != 0) throw std::runtime_error("Write packet index failed");
             file_end = static_cast<uint64_t>(std::ftell(saveFile));
         }
@@ -1096,7 +1172,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         const Trailer trailer = loadTrailer(stream_end, fileSize);
         const std::vector<uint16_t> &index = trailer.clens;
         const std::vector<uint32_t> &crcs = trailer.crcs;
-        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging();
+        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging(), mixed = trailer.mixed();
         if (trailer.based()) openBase(info.uncompressedFileSize, "the file");
 
         ChunkMap map;
@@ -1203,6 +1279,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             if (verify) b.allocateCrc();
                             if (merging) b.allocatePlanes();
                             if (trailer.based()) b.allocateBase();
+                            if (mixed) b.allocateKinds(false);
                             b.epoch = static_cast<hipEvent_t>(epochOf(g));
                             const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
                             const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
@@ -1229,11 +1306,20 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 all_full = all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
                                 // (byte planes: so every chunk but the last is whole groups, and all_full holds)
                                 if (merging) checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
+                                // (raw and sparse packets: the same, so that packet p of the chunk goes to byte 8192 p of it; a raw
+                                // packet is its header and its bytes)
+                                if (mixed) {
+                                    checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
+                                    if (trailer.kinds[chunk.first_packet + p] == 1 && clen != GPUAR_PACKET_HEADER_BYTES + getPacketUlen(pkt))
+                                        throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
+                                                                 " and " + std::to_string(chunk.end) + ")");
+                                }
                                 produced += ulen;
                                 off += clen;
                             }
                             if (off != n_stream) throw std::runtime_error("Invalid file length");
                             b.h_offsets[chunk.n_packets] = off;
+                            if (mixed && (produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
                             const uint64_t out_at = place.take(c, produced);
                             device_bytes[g] += produced;
                             device_chunks[g] += 1;
@@ -1248,7 +1334,8 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             if (trailer.based()) b.uploadBase(baseFd, static_cast<uint64_t>(chunk.first_packet) * kPacket, static_cast<size_t>(produced));
                             uint64_t first_bad = 0;
                             const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
-                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering(), trailer.based());        // (synchronises the lane's stream)
+                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering(), trailer.based(),
+                                                                 mixed ? trailer.kinds.data() + chunk.first_packet : nullptr);        // (synchronises the lane's stream)
                             if (from_mapping) mapped.release(chunk.begin, n_stream);
                             // the file was cut short under the mapping (what was read behind its new end are zeros,
                             // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307

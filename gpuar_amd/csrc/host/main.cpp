@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta[=on|off|auto]] [--base=FILE] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta[=on|off|auto]] [--base=FILE] [--stored[=auto|off]] [--sparse[=auto|off]] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -69,6 +69,12 @@ void usage() {
     std::cout << "              base makes it grow; implies --checksum; not together with --delta; the file then carries a trailer that says so;" << std::endl;
     std::cout << "              (decompress) the same FILE: required for a file written with --base (a wrong one is a checksum mismatch)," << std::endl;
     std::cout << "              refused for any other file" << std::endl;
+    std::cout << "--stored      (compress) --stored or --stored=auto: a packet that the coder cannot shrink (its estimate says so: mantissa planes," << std::endl;
+    std::cout << "              data that is already compressed) is kept raw behind its 4-byte header; --stored=off: every packet is coded (default)" << std::endl;
+    std::cout << "--sparse      (compress) --sparse or --sparse=auto: a packet that is one byte value almost everywhere (what --base makes of" << std::endl;
+    std::cout << "              everything that did not change) is kept as that byte and its exceptions: 8 bytes instead of 210 for an unchanged" << std::endl;
+    std::cout << "              packet; --sparse=off: no such packets (default).  Either option: the file carries a trailer that says which packet is" << std::endl;
+    std::cout << "              which, and decompress needs no flag to read it" << std::endl;
     std::cout << "--nointeractive no interactive mode" << std::endl;
 }
 
@@ -77,7 +83,7 @@ void usage() {
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip", base;
-    bool has_in = false, planes_auto = false, delta = false, delta_auto = false;
+    bool has_in = false, planes_auto = false, delta = false, delta_auto = false, stored = false, sparse = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
@@ -108,6 +114,14 @@ int main(int argc, char **argv) {
                 std::cerr << "--delta takes on, off or auto: " << v << std::endl;
                 return 2;
             }
+        } else if (flag_name_is(argv[i], "stored", &v) || flag_name_is(argv[i], "sparse", &v)) {
+            const bool is_stored = flag_name_is(argv[i], "stored", &v);
+            const bool on = !v || !std::strcmp(v, "auto");
+            if (!on && std::strcmp(v, "off")) {
+                std::cerr << (is_stored ? "--stored" : "--sparse") << " takes auto or off: " << v << std::endl;
+                return 2;
+            }
+            (is_stored ? stored : sparse) = on;
         } else if (flag_name_is(argv[i], "nointeractive", &v)) {
         } else if (flag_name_is(argv[i], "in", &v)) {
             if (!take(&v)) break;
@@ -185,6 +199,8 @@ int main(int argc, char **argv) {
         compressor->setWriteChecksum(checksum);
         compressor->setPlanes(planes);
         compressor->setDelta(delta && !delta_auto);
+        compressor->setStored(stored);
+        compressor->setSparse(sparse);
         compressor->setBaseFileName(base);
         compressor->setOpenFileName(in);
         compressor->setSaveFileName(out);

@@ -38,6 +38,7 @@ EXPORTS = [
     "gpuar_hip_survey_delta", "gpuar_hip_survey_delta_batch", "gpuar_hip_survey_delta_host", "gpuar_hip_choose_filter",
     "gpuar_hip_sparse_len", "gpuar_hip_sparse_rule", "gpuar_hip_sparse_scan", "gpuar_hip_sparse_scan_batch", "gpuar_hip_sparse_scan_host",
     "gpuar_hip_sparse_pack", "gpuar_hip_sparse_unpack", "gpuar_hip_sparse_pack_host", "gpuar_hip_sparse_unpack_host",
+    "gpuar_hip_kinds_store", "gpuar_hip_kinds_expand", "gpuar_hip_kinds_store_host", "gpuar_hip_kinds_expand_host",
 ]
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
@@ -187,6 +188,14 @@ def load() -> C.CDLL:
     lib.gpuar_hip_sparse_pack_host.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
     lib.gpuar_hip_sparse_unpack_host.restype = C.c_int
     lib.gpuar_hip_sparse_unpack_host.argtypes = [vp, sz, vp, sz]
+    lib.gpuar_hip_kinds_store.restype = C.c_int
+    lib.gpuar_hip_kinds_store.argtypes = [vp, sz, vp, vp, C.c_int, vp, vp, vp, vp]
+    lib.gpuar_hip_kinds_expand.restype = C.c_int
+    lib.gpuar_hip_kinds_expand.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
+    lib.gpuar_hip_kinds_store_host.restype = C.c_int
+    lib.gpuar_hip_kinds_store_host.argtypes = [vp, sz, C.c_int, C.c_int, vp, sz, C.POINTER(u32), C.POINTER(sz)]
+    lib.gpuar_hip_kinds_expand_host.restype = C.c_int
+    lib.gpuar_hip_kinds_expand_host.argtypes = [vp, sz, u32, vp, sz]
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -890,6 +899,67 @@ def sparse_unpack(d_rec_ptrs, d_rec_bytes, d_dst_ptrs, d_bytes, n_regions: int, 
         _require_u64_desc(t, name, n_regions)
     _check(load().gpuar_hip_sparse_unpack(d_rec_ptrs.data_ptr(), d_rec_bytes.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions,
                                           _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_unpack")
+
+
+def kinds_store_host(data, stored: bool, sparse: bool):
+    """One packet (1 .. 8192 bytes) in its stream form on the CPU (gpuar_hip_kinds_store_host; gpuar_amd/csrc/kinds.h): (kind,
+    packet) with the packet -- 4-byte header, then the bytes or the sparse record -- as bytes, or b"" for KIND_CODED (the
+    encoder's packet stands)."""
+    data = bytes(data)
+    pkt = (C.c_uint8 * SLOT)()
+    kind, clen = C.c_uint32(0), C.c_size_t(0)
+    _check(load().gpuar_hip_kinds_store_host(data, len(data), int(bool(stored)), int(bool(sparse)), pkt, len(pkt), C.byref(kind), C.byref(clen)),
+           "gpuar_hip_kinds_store_host")
+    return int(kind.value), bytes(pkt[:clen.value])
+
+
+def kinds_expand_host(pkt, kind: int, n_bytes: int) -> bytes:
+    """The `n_bytes` of a raw (KIND_RAW) or sparse (KIND_SPARSE) packet in its stream form on the CPU
+    (gpuar_hip_kinds_expand_host); raises for any other kind and for a packet that is not valid."""
+    pkt = bytes(pkt)
+    out = (C.c_uint8 * max(n_bytes, 1))()
+    _check(load().gpuar_hip_kinds_expand_host(pkt, len(pkt), kind, out, n_bytes), "gpuar_hip_kinds_expand_host")
+    return bytes(out[:n_bytes])
+
+
+def kinds_store(d_in, d_est, d_scan, stored: bool, d_slots, n_bytes: int = None, d_kind=None, stream=None, d_status=None):
+    """Behind encode() on the same stream: the kind of every packet of the first `n_bytes` (default: all) bytes of `d_in` from
+    d_est (estimate) and d_scan (sparse_scan; None: sparse is off) into d_kind (uint8 CUDA tensor, one per packet; allocated when
+    None), and the slots of the raw and sparse packets overwritten with their stream form (gpuar_hip_kinds_store).  A scan word
+    that is not that of the packet's bytes is STATUS_BAD_BATCH: the slot stays the encoder's and the kind 0.  Returns d_kind."""
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    _require_cuda_u8(d_slots, "d_slots")
+    n = d_in.numel() if n_bytes is None else n_bytes
+    n_packets = packet_count(n)
+    if n > d_in.numel() or d_slots.numel() < n_packets * SLOT:
+        raise GpuarError("d_in or d_slots is too small")
+    _require_crc(d_est, "d_est", n_packets)
+    if d_scan is not None:
+        _require_crc(d_scan, "d_scan", n_packets)
+    if d_kind is None:
+        d_kind = torch.empty(n_packets, dtype=torch.uint8, device=d_in.device)
+    _require_cuda_u8(d_kind, "d_kind")
+    if d_kind.numel() < n_packets:
+        raise GpuarError("d_kind is too small")
+    _check(load().gpuar_hip_kinds_store(d_in.data_ptr(), n, d_est.data_ptr(), d_scan.data_ptr() if d_scan is not None else None, int(bool(stored)),
+                                        d_slots.data_ptr(), d_kind.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_kinds_store")
+    return d_kind
+
+
+def kinds_expand(d_stream, d_offsets, d_kind, n_packets: int, d_out, n_bytes: int, stream=None, d_status=None):
+    """Take the raw and sparse packets out of a compacted stream: packet p of kind d_kind[p] = 1 or 2 at d_stream + d_offsets[p]
+    (any alignment) to d_out + 8192 p; coded packets (kind 0) are skipped (gpuar_hip_kinds_expand).  n_bytes: the bytes of the whole
+    output, packet_count(n_bytes) == n_packets.  A packet that is not valid, or a kind above 2, is STATUS_BAD_PACKET."""
+    _require_cuda_u8(d_stream, "d_stream")
+    _require_cuda_u8(d_kind, "d_kind")
+    _require_cuda_u8(d_out, "d_out")
+    _require_u64_desc(d_offsets, "d_offsets", n_packets + 1)
+    if d_kind.numel() < n_packets or d_out.numel() < n_bytes:
+        raise GpuarError("d_kind or d_out is too small")
+    _check(load().gpuar_hip_kinds_expand(d_stream.data_ptr(), d_offsets.data_ptr(), d_kind.data_ptr(), n_packets, d_out.data_ptr(), n_bytes,
+                                         _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_kinds_expand")
+    return d_out
 
 
 def status() -> int:

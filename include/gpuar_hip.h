@@ -449,7 +449,7 @@ int gpuar_hip_choose_filter(const uint64_t plain[4], const uint64_t filtered[4],
  *
  * Host-side checks as for gpuar_hip_estimate and gpuar_hip_move_packets, in the same order and before any device work.  Nothing is
  * read beyond the 16-byte-aligned piece of memory that holds a packet's last byte, nor beyond a record's rec_bytes.
- * Left out: the .gip container and the CLI have no sparse packets.
+ * In a .gip file a sparse packet is its record behind the packet's 4-byte header (below: raw and sparse packets in a stream).
  * ---------------------------------------------------------------------- */
 #define GPUAR_SPARSE_NONE 0xFFFFFFFFu
 
@@ -497,6 +497,54 @@ int gpuar_hip_sparse_pack_host(const uint8_t *in, size_t n_bytes, uint8_t *rec, 
 /* Host only: the packet out[0 .. n_bytes) from the record rec[0 .. rec_bytes).  GPUAR_ERR_ARGUMENT for a null pointer, another
  * n_bytes, or a record that is not valid (out[0 .. n_bytes) is then unspecified; nothing is read beyond rec_bytes). */
 int gpuar_hip_sparse_unpack_host(const uint8_t *rec, size_t rec_bytes, uint8_t *out, size_t n_bytes);
+
+/* ------------------------------------------------------------------------
+ * Raw and sparse packets in a packet stream (gpuar_amd/csrc/kinds.h: one integer definition for the host and the kernels;
+ * DESIGN.md 4.13).  In a stream -- the slots gpuar_hip_encode fills, what gpuar_hip_compact makes of them, a .gip file -- a packet
+ * of any kind starts with the 4-byte header of a coded one, u16 clen (these 4 bytes included) | u16 ulen:
+ *     kind 0 coded    the bitstream                                 clen as ever
+ *     kind 1 raw      the packet's ulen bytes                       clen = 4 + ulen  (<= 8196)
+ *     kind 2 sparse   the record above, pads included               clen = 4 + gpuar_hip_sparse_len(k)
+ * so `off += clen` walks the stream, every packet fits its 8704-byte slot and gpuar_hip_compact works unchanged.  The kind is
+ * gpuar_hip_sparse_rule(scan, est, ulen, stored_on), scan = GPUAR_SPARSE_NONE where sparse is off: what batch.compress applies
+ * (not re-tuned for the 4 header bytes: at the tie a sparse packet may be up to 3 bytes longer than its coded form).  Which
+ * packet is which is kept beside the stream, one byte per packet (the version-6 trailer of a .gip file).
+ * Left out: counting kinds in the surveys, one read for scan and estimate, skipping the encode of non-coded packets.
+ * ---------------------------------------------------------------------- */
+
+/* Behind gpuar_hip_encode* on the same stream, over the gpuar_hip_packet_count(n_bytes) packets of the n_bytes at d_in (the bytes
+ * that were coded; 16-byte aligned) and their slots at d_slots (16-byte aligned): writes d_kind[p] (one byte per packet) from
+ * d_est[p] (gpuar_hip_estimate) and d_scan[p] (gpuar_hip_sparse_scan; NULL: sparse is off) and overwrites the slot of a raw
+ * packet with header + bytes and of a sparse packet with header + record.  A coded packet's slot is not touched, and nothing
+ * is written beyond slot + clen.  A scan word that is not that of the packet's bytes (another count of exceptions, a fill that
+ * is no majority) is GPUAR_STATUS_BAD_BATCH in d_status: the slot stays the encoder's and d_kind[p] = 0, so the stream is
+ * still a valid one.  Host-side checks as for gpuar_hip_estimate, then d_slots and d_kind (NULL: GPUAR_ERR_ARGUMENT) and the
+ * alignment of d_slots (16) and d_scan (4).  Nothing is read beyond the 16-byte piece that holds the buffer's last byte. */
+int gpuar_hip_kinds_store(const uint8_t *d_in, size_t n_bytes, const uint32_t *d_est, const uint32_t *d_scan, int stored_on,
+                          uint8_t *d_slots, uint8_t *d_kind, uint32_t *d_status, void *stream);
+
+/* Takes the raw and sparse packets out of a compacted stream: packet p of kind d_kind[p] = 1 or 2 at d_stream + d_offsets[p]
+ * (any alignment; d_offsets: n_packets + 1 values, 8-byte aligned) goes to d_out + p * 8192 (d_out 16-byte aligned), n_bytes
+ * being the bytes of the whole output: gpuar_hip_packet_count(n_bytes) == n_packets, or GPUAR_ERR_ARGUMENT.  Packets of kind 0
+ * are the decoder's and are skipped.  The header is checked first: clen == d_offsets[p + 1] - d_offsets[p], ulen == the bytes
+ * packet p has in n_bytes, raw: clen == 4 + ulen, sparse: a valid record.  A packet that fails, or a kind above 2, is
+ * GPUAR_STATUS_BAD_PACKET in d_status: a raw packet's destination is left as it was, a sparse packet's own bytes are
+ * unspecified; nothing outside the packet's bytes is written, and nothing before d_offsets[p] or from d_offsets[p + 1] on is
+ * read. */
+int gpuar_hip_kinds_expand(const uint8_t *d_stream, const uint64_t *d_offsets, const uint8_t *d_kind, size_t n_packets, uint8_t *d_out,
+                           size_t n_bytes, uint32_t *d_status, void *stream);
+
+/* Host only: ONE packet in[0 .. n_bytes) (1 .. 8192 bytes) in its stream form.  *kind is what the rule gives with the two
+ * options; for a raw or sparse packet pkt[0 .. *clen) is written; for a coded one nothing is written and *clen = 0 (the
+ * encoder's packet stands).  GPUAR_ERR_ARGUMENT (nothing written) for a null pointer, another n_bytes, or a packet longer
+ * than room. */
+int gpuar_hip_kinds_store_host(const uint8_t *in, size_t n_bytes, int stored_on, int sparse_on, uint8_t *pkt, size_t room, uint32_t *kind,
+                               size_t *clen);
+
+/* Host only: the packet out[0 .. n_bytes) from the raw (kind 1) or sparse (kind 2) packet pkt[0 .. pkt_bytes).
+ * GPUAR_ERR_ARGUMENT for a null pointer, another n_bytes, any other kind, or a packet that is not valid (a raw packet's out is
+ * then untouched, a sparse packet's out[0 .. n_bytes) unspecified; nothing is read beyond pkt_bytes). */
+int gpuar_hip_kinds_expand_host(const uint8_t *pkt, size_t pkt_bytes, uint32_t kind, uint8_t *out, size_t n_bytes);
 
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
