@@ -35,6 +35,7 @@
 // bitstream.  No MFMA: this is integer, bit-serial
 // work bounded by VALU issue and LDS operations, not by HBM.
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <mutex>
 #include <stdint.h>
 #include <stdio.h>
@@ -4069,7 +4070,43 @@ namespace {
 
 thread_local int t_last_error = GPUAR_OK;
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+constexpr size_t kMaxCount = 0xFFFFFFFFull;            // packets, buffers or regions of one call: the kernels count in 32 bits
+
+// The alignment test of every pointer argument: data, slots and outputs 16, descriptor arrays and 64-bit words 8, 32-bit words and
+// records 4.  A null pointer passes: whether it may be null is another test.
+inline bool misaligned(const void *p, uintptr_t align) { return (reinterpret_cast<uintptr_t>(p) & (align - 1u)) != 0; }
+
+// The grid of every kernel that strides over its work: one workgroup for every `per` items, `cap` at most.
+constexpr uint32_t capped_blocks(uint64_t n, uint32_t per, uint32_t cap) {
+    const uint64_t groups = n / per + (n % per ? 1u : 0u);
+    return static_cast<uint32_t>(groups < cap ? groups : cap);
+}
+
+// The same rule in the other spellings a launch may carry, in the width each kernel counts in: the compiler holds capped_blocks to
+// them at the edges of every (per, cap) in use.
+constexpr uint32_t blocks_added(uint64_t n, uint32_t per, uint32_t cap) {                  // CRC, estimate, sparse scan
+    const size_t groups = (static_cast<size_t>(n) + per - 1) / per;
+    return static_cast<uint32_t>(groups < cap ? groups : cap);
+}
+constexpr uint32_t blocks_shifted(uint64_t n, uint32_t, uint32_t cap) {                    // the surveys: windows of 8 packets
+    const uint32_t windows = (static_cast<uint32_t>(n) >> 3) + ((static_cast<uint32_t>(n) & 7u) ? 1u : 0u);
+    return windows < cap ? windows : cap;
+}
+constexpr uint32_t blocks_divided(uint64_t n, uint32_t per, uint32_t cap) {                // sparse pack / unpack, kinds; per = 1: filters, move
+    const uint32_t groups = static_cast<uint32_t>(n) / per + (static_cast<uint32_t>(n) % per ? 1u : 0u);
+    return groups < cap ? groups : cap;
+}
+constexpr bool same_blocks(uint32_t (*old)(uint64_t, uint32_t, uint32_t), uint32_t per, uint32_t cap) {
+    const uint64_t edge = static_cast<uint64_t>(cap) * per;
+    for (const uint64_t n : {uint64_t{0}, uint64_t{1}, uint64_t{per} - 1, uint64_t{per}, uint64_t{per} + 1, edge, edge + 1})
+        if (capped_blocks(n, per, cap) != old(n, per, cap)) return false;
+    return true;
+}
+static_assert(same_blocks(blocks_added, gpuar::kCrcWaves, gpuar::kCrcGroups) && same_blocks(blocks_added, gpuar::kEstWaves, gpuar::kEstGroups) &&
+              same_blocks(blocks_shifted, 8u, gpuar::kSurveyGroups) && same_blocks(blocks_added, gpuar::kSparseWaves, gpuar::kSparseGroups) &&
+              same_blocks(blocks_divided, gpuar::kSparseWaves, gpuar::kSparseGroups) &&
+              same_blocks(blocks_divided, gpuar::kSparseWaves, gpuar::kPlaneGridCap) && same_blocks(blocks_divided, 1u, gpuar::kPlaneGridCap),
+              "capped_blocks is not the grid of one of the launches");
 
 int check_launch() {
     const hipError_t e = hipGetLastError();
@@ -4106,12 +4143,110 @@ int launch_filter(const FilterKernels<Args> &kernels, bool merge, const Args &ar
     hipStream_t s = static_cast<hipStream_t>(stream);
     // a batch: any buffer may have a tail; one buffer: it has one or not
     const size_t n_tails = p.in_ptrs ? p.n_buffers : (p.n_bytes % (static_cast<size_t>(p.elem) * GPUAR_PACKET_BYTES) ? 1u : 0u);
-    const uint32_t blocks = p.n_packets < gpuar::kPlaneGridCap ? p.n_packets : gpuar::kPlaneGridCap;
-    const uint32_t tails = static_cast<uint32_t>(n_tails < gpuar::kPlaneGridCap ? n_tails : gpuar::kPlaneGridCap);
-    (merge ? kernels.merge : kernels.split)<<<blocks, gpuar::kPlaneThreads, 0, s>>>(args);
+    const uint32_t tails = capped_blocks(n_tails, 1u, gpuar::kPlaneGridCap);
+    (merge ? kernels.merge : kernels.split)<<<capped_blocks(p.n_packets, 1u, gpuar::kPlaneGridCap), gpuar::kPlaneThreads, 0, s>>>(args);
     const int e = check_launch();
     if (e != GPUAR_OK || tails == 0u) return e;
     (merge ? kernels.merge_tail : kernels.split_tail)<<<tails, gpuar::kPlaneThreads, 0, s>>>(args);
+    return check_launch();
+}
+
+// the host-side checks every batch call makes before any device work; d_packets (the slots or the stream) must be aligned to
+// packets_align bytes; *status_out: where the launch reports
+int batch_arguments(const void *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                    const void *d_packets, uintptr_t packets_align, uint32_t *d_status, uint32_t **status_out) {
+    if (!d_ptrs || !d_bytes || !d_first_packet || !d_packets) return GPUAR_ERR_ARGUMENT;
+    if (n_packets > kMaxCount || n_buffers > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_ptrs, 8) || misaligned(d_bytes, 8) || misaligned(d_first_packet, 8) || misaligned(d_status, 4) ||
+        misaligned(d_packets, packets_align))
+        return GPUAR_ERR_ALIGNMENT;
+    *status_out = status_word(d_status);
+    return *status_out ? GPUAR_OK : GPUAR_ERR_NO_DEVICE;
+}
+
+// The source of a per-packet kernel, in the fields every such kernel's arguments (CrcArgs, SurveyArgs, KindsStoreArgs) name alike:
+// one buffer ...
+template <typename Args>
+Args buffer_source(const uint8_t *d_in, size_t n_bytes, uint32_t *status) {
+    Args a = {};
+    a.in = d_in;
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.status = status;
+    return a;
+}
+
+// ... or a batch
+template <typename Args>
+Args batch_source(const uint8_t *const *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
+                  uint32_t *status) {
+    Args a = {};
+    a.ptrs = d_ptrs;
+    a.bytes = d_bytes;
+    a.first_packet = d_first_packet;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.status = status;
+    return a;
+}
+
+// The checks of a per-packet call on one buffer that takes one array of 32-bit words (d_words: CRCs, estimates, scan words) and
+// maybe a 64-bit word (d_word64), in the order include/gpuar_hip.h gives: nothing to do; `own_ok`, the test of the call's own
+// values (the surveys' stride and mask); null pointers and the packet count; alignments; the status word.  *a: the call's source,
+// once *launch says there is something to launch.
+template <typename Args>
+int packet_checks(bool own_ok, const uint8_t *d_data, size_t n_bytes, const uint32_t *d_words, const uint64_t *d_word64, uint32_t *d_status,
+                  Args *a, bool *launch) {
+    *launch = false;
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!own_ok || !d_data || !d_words || gpuar_hip_packet_count(n_bytes) > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_data, 16) || misaligned(d_words, 4) || misaligned(d_word64, 8) || misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = status_word(d_status);
+    if (!status) return GPUAR_ERR_NO_DEVICE;
+    *a = buffer_source<Args>(d_data, n_bytes, status);
+    *launch = true;
+    return GPUAR_OK;
+}
+
+// The same on a batch: d_words (4) and d_word64 (8) in front of batch_arguments' checks, where the buffers' pointer array stands in
+// for the packets (8-byte aligned).
+template <typename Args>
+int packet_batch_checks(bool own_ok, const uint8_t *const *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers,
+                        size_t n_packets, const uint32_t *d_words, const uint64_t *d_word64, uint32_t *d_status, Args *a, bool *launch) {
+    *launch = false;
+    if (n_packets == 0) return GPUAR_OK;
+    if (!own_ok || !d_words || !d_ptrs || !d_bytes || !d_first_packet || n_packets > kMaxCount || n_buffers > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_words, 4) || misaligned(d_word64, 8)) return GPUAR_ERR_ALIGNMENT;
+    uint32_t *status = nullptr;
+    const int e = batch_arguments(d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_ptrs, 8u, d_status, &status);
+    if (e != GPUAR_OK) return e;
+    *a = batch_source<Args>(d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, status);
+    *launch = true;
+    return GPUAR_OK;
+}
+
+// The frame of a per-region call (move_packets, sparse_pack, sparse_unpack): `a` with the call's pointers in place, which are also
+// listed by alignment -- d_arrays8: the descriptor arrays, d_arrays4: arrays of 32-bit words.  Nothing to do; a null array or too
+// many regions; a misaligned array or status word; the status word; one workgroup for every `per` regions.
+template <typename Args>
+int region_call(void (*kernel)(Args), uint32_t per, uint32_t threads, Args a, std::initializer_list<const void *> d_arrays8,
+                std::initializer_list<const void *> d_arrays4, size_t n_regions, uint32_t *d_status, void *stream) {
+    if (n_regions == 0) return GPUAR_OK;
+    bool missing = n_regions > kMaxCount, skewed = misaligned(d_status, 4);
+    for (const void *p : d_arrays8) {
+        missing |= !p;
+        skewed |= misaligned(p, 8);
+    }
+    for (const void *p : d_arrays4) {
+        missing |= !p;
+        skewed |= misaligned(p, 4);
+    }
+    if (missing) return GPUAR_ERR_ARGUMENT;
+    if (skewed) return GPUAR_ERR_ALIGNMENT;
+    a.n_regions = static_cast<uint32_t>(n_regions);
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    kernel<<<capped_blocks(a.n_regions, per, gpuar::kPlaneGridCap), threads, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }
 
@@ -4125,11 +4260,11 @@ int gpuar_hip_encode_mode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots,
     if (mode != GPUAR_MODE_AUTO && mode != GPUAR_MODE_THROUGHPUT && mode != GPUAR_MODE_LATENCY && mode != GPUAR_MODE_TABLE) return GPUAR_ERR_ARGUMENT;
     if (n_bytes == 0) return GPUAR_OK;
     if (!d_in || !d_slots) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_in) || !aligned16(d_slots) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_in, 16) || misaligned(d_slots, 16) || misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
     uint32_t *status = status_word(d_status);
     if (!status) return GPUAR_ERR_NO_DEVICE;
     const size_t n_packets = gpuar_hip_packet_count(n_bytes);
-    if (n_packets > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
+    if (n_packets > kMaxCount) return GPUAR_ERR_ARGUMENT;
     const uint32_t groups = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
     // Small inputs cannot fill the chip and take as long as one packet: left to itself (GPUAR_MODE_AUTO) such a launch
     // goes to the latency-mode kernel (six working roles and a courier, a shorter step).  The slots are the same bytes either way; the
@@ -4159,8 +4294,8 @@ int gpuar_hip_encode(const uint8_t *d_in, size_t n_bytes, uint8_t *d_slots, uint
 // n_bytes: how much of d_slots may be read (n_packets * 8704, or less when the last slot is a partial one)
 static int launch_decode_slots(const uint8_t *d_slots, size_t n_packets, size_t n_bytes, uint8_t *d_out, uint32_t *d_status, void *stream) {
     if (n_packets == 0) return GPUAR_OK;
-    if (!d_slots || !d_out || n_packets > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_slots) || !aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    if (!d_slots || !d_out || n_packets > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_slots, 16) || misaligned(d_out, 16) || misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
     uint32_t *status = status_word(d_status);
     if (!status) return GPUAR_ERR_NO_DEVICE;
     const uint32_t blocks = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
@@ -4181,8 +4316,7 @@ int gpuar_hip_compact(const uint8_t *d_slots, size_t n_packets, uint8_t *d_strea
         return e == hipSuccess ? GPUAR_OK : static_cast<int>(e);
     }
     if (!d_slots || !d_stream) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_slots) || (reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_stream) & 7u))
-        return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_slots, 16) || misaligned(d_offsets, 8) || misaligned(d_stream, 8)) return GPUAR_ERR_ALIGNMENT;
     // the gather launches one workgroup per packet, and gridDim.x * blockDim.x must stay below 2^32 threads: 16.7 M packets
     // = 128 GiB of input per call with 256-thread workgroups (a device holds 288 GB; the CLI compacts 512 MiB chunks)
     if (n_packets * static_cast<size_t>(gpuar::kGatherThreads) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
@@ -4202,8 +4336,8 @@ int gpuar_hip_compact(const uint8_t *d_slots, size_t n_packets, uint8_t *d_strea
 int gpuar_hip_decode_stream(const uint8_t *d_stream, const uint64_t *d_offsets, size_t n_packets,
                             uint8_t *d_out, uint32_t *d_status, void *stream) {
     if (n_packets == 0) return GPUAR_OK;
-    if (!d_stream || !d_offsets || !d_out || n_packets > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_stream) & 3u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    if (!d_stream || !d_offsets || !d_out || n_packets > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_out, 16) || misaligned(d_stream, 4) || misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
     uint32_t *status = status_word(d_status);
     if (!status) return GPUAR_ERR_NO_DEVICE;
     const uint32_t blocks = static_cast<uint32_t>((n_packets + gpuar::kLanes - 1) / gpuar::kLanes);
@@ -4221,20 +4355,6 @@ size_t gpuar_hip_batch_packet_count(const uint64_t *bytes, size_t n_buffers, uin
     }
     if (first_packet) first_packet[n_buffers] = total;
     return total;
-}
-
-// the host-side checks every batch call makes before any device work; d_packets (the slots or the stream) must be aligned to
-// packets_align bytes; *status_out: where the launch reports
-static int batch_arguments(const void *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers,
-                           size_t n_packets, const void *d_packets, uintptr_t packets_align, uint32_t *d_status, uint32_t **status_out) {
-    if (!d_ptrs || !d_bytes || !d_first_packet || !d_packets) return GPUAR_ERR_ARGUMENT;
-    if (n_packets > 0xFFFFFFFFull || n_buffers > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_first_packet) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_packets) & (packets_align - 1u)))
-        return GPUAR_ERR_ALIGNMENT;
-    *status_out = status_word(d_status);
-    return *status_out ? GPUAR_OK : GPUAR_ERR_NO_DEVICE;
 }
 
 int gpuar_hip_encode_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
@@ -4275,7 +4395,7 @@ int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_off
                                   const uint64_t *d_out_bytes, uint32_t *d_status, void *stream) {
     if (n_packets == 0) return GPUAR_OK;
     if (!d_offsets) return GPUAR_ERR_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(d_offsets) & 7u) return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_offsets, 8)) return GPUAR_ERR_ALIGNMENT;
     uint32_t *status = nullptr;
     const int e = batch_arguments(d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_stream, 4u, d_status, &status);
     if (e != GPUAR_OK) return e;
@@ -4286,102 +4406,52 @@ int gpuar_hip_decode_stream_batch(const uint8_t *d_stream, const uint64_t *d_off
 }
 
 static int launch_crc32(bool verify, const gpuar::CrcArgs &a, void *stream) {
-    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kCrcWaves - 1) / gpuar::kCrcWaves;
-    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kCrcGroups ? groups : gpuar::kCrcGroups);
+    const uint32_t blocks = capped_blocks(a.n_packets, gpuar::kCrcWaves, gpuar::kCrcGroups);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (verify) gpuar::crc32_kernel<true><<<blocks, gpuar::kCrcWaves * gpuar::kLanes, 0, s>>>(a);
     else gpuar::crc32_kernel<false><<<blocks, gpuar::kCrcWaves * gpuar::kLanes, 0, s>>>(a);
     return check_launch();
 }
 
-// the single-buffer calls' checks; n_bytes == 0 is GPUAR_OK with no launch (*launch = false)
-static int crc32_arguments(const uint8_t *d_data, size_t n_bytes, const uint32_t *d_crc, const uint64_t *d_first_bad, uint32_t *d_status,
-                           uint32_t **status_out, bool *launch) {
-    *launch = false;
-    if (n_bytes == 0) return GPUAR_OK;
-    if (!d_data || !d_crc || gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_data) || (reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_first_bad) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_status) & 3u))
-        return GPUAR_ERR_ALIGNMENT;
-    *status_out = status_word(d_status);
-    if (!*status_out) return GPUAR_ERR_NO_DEVICE;
-    *launch = true;
-    return GPUAR_OK;
-}
-
 int gpuar_hip_crc32(const uint8_t *d_in, size_t n_bytes, uint32_t *d_crc, void *stream) {
-    uint32_t *status = nullptr;
+    gpuar::CrcArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_crc, nullptr, nullptr, &status, &launch);
+    const int e = packet_checks(true, d_in, n_bytes, d_crc, nullptr, nullptr, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::CrcArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
     a.crc = d_crc;
-    a.status = status;
     return launch_crc32(false, a, stream);
 }
 
 int gpuar_hip_verify_crc32(const uint8_t *d_out, size_t n_bytes, const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status,
                            void *stream) {
-    uint32_t *status = nullptr;
+    gpuar::CrcArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_out, n_bytes, d_crc, d_first_bad, d_status, &status, &launch);
+    const int e = packet_checks(true, d_out, n_bytes, d_crc, d_first_bad, d_status, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::CrcArgs a = {};
-    a.in = d_out;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
     a.crc = const_cast<uint32_t *>(d_crc);
     a.first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
-    a.status = status;
     return launch_crc32(true, a, stream);
-}
-
-// the batch calls' checks: batch_arguments' (the buffers' pointer array stands in for the packets, 8-byte aligned), then
-// d_crc (4) and d_first_bad (8)
-static int crc32_batch_arguments(const uint8_t *const *d_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet, size_t n_buffers,
-                                 size_t n_packets, const uint32_t *d_crc, const uint64_t *d_first_bad, uint32_t *d_status,
-                                 uint32_t **status_out) {
-    if (!d_crc || !d_ptrs || !d_bytes || !d_first_packet || n_packets > 0xFFFFFFFFull || n_buffers > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_crc) & 3u) || (reinterpret_cast<uintptr_t>(d_first_bad) & 7u)) return GPUAR_ERR_ALIGNMENT;
-    return batch_arguments(d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_ptrs, 8u, d_status, status_out);
 }
 
 int gpuar_hip_crc32_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
                           size_t n_buffers, size_t n_packets, uint32_t *d_crc, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_crc, nullptr, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::CrcArgs a = {};
-    a.ptrs = d_in_ptrs;
-    a.bytes = d_in_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
+    gpuar::CrcArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(true, d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_crc, nullptr, d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     a.crc = d_crc;
-    a.status = status;
     return launch_crc32(false, a, stream);
 }
 
 int gpuar_hip_verify_crc32_batch(const uint8_t *const *d_out_ptrs, const uint64_t *d_out_bytes,
                                  const uint64_t *d_first_packet, size_t n_buffers, size_t n_packets,
                                  const uint32_t *d_crc, uint64_t *d_first_bad, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_crc, d_first_bad, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::CrcArgs a = {};
-    a.ptrs = d_out_ptrs;
-    a.bytes = d_out_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
+    gpuar::CrcArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(true, d_out_ptrs, d_out_bytes, d_first_packet, n_buffers, n_packets, d_crc, d_first_bad, d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     a.crc = const_cast<uint32_t *>(d_crc);
     a.first_bad = reinterpret_cast<unsigned long long *>(d_first_bad);
-    a.status = status;
     return launch_crc32(true, a, stream);
 }
 
@@ -4395,8 +4465,8 @@ static int filter_checks(bool on_host, const uint8_t *in, bool based, const uint
     if (!gpuar::planes_width_ok(elem_bytes)) return GPUAR_ERR_ARGUMENT;
     if (n_bytes == 0) return GPUAR_OK;
     if (!in || !out || (based && !base)) return GPUAR_ERR_ARGUMENT;
-    if (!on_host && gpuar_hip_packet_count(n_bytes) > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if (!on_host && (!aligned16(in) || !aligned16(out) || (based && !aligned16(base)))) return GPUAR_ERR_ALIGNMENT;
+    if (!on_host && gpuar_hip_packet_count(n_bytes) > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    if (!on_host && (misaligned(in, 16) || misaligned(out, 16) || (based && misaligned(base, 16)))) return GPUAR_ERR_ALIGNMENT;
     const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out);
     if (a != b && ranges_meet(a, b, n_bytes)) return GPUAR_ERR_ARGUMENT;                        // in place or apart, nothing in between
     if (based && ranges_meet(reinterpret_cast<uintptr_t>(base), b, n_bytes)) return GPUAR_ERR_ARGUMENT;
@@ -4425,9 +4495,7 @@ static int batch_filter_arguments(const uint8_t *const *d_in_ptrs, const uint64_
     *launch = false;
     if (n_packets == 0) return GPUAR_OK;
     if (!d_elem_bytes || (extra && !d_extra) || !d_out_ptrs) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_elem_bytes) & 7u) || (extra && (reinterpret_cast<uintptr_t>(d_extra) & 7u)) ||
-        (reinterpret_cast<uintptr_t>(d_out_ptrs) & 7u))
-        return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_elem_bytes, 8) || (extra && misaligned(d_extra, 8)) || misaligned(d_out_ptrs, 8)) return GPUAR_ERR_ALIGNMENT;
     uint32_t *status = nullptr;
     const int e = batch_arguments(d_in_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_in_ptrs, 8u, d_status, &status);
     if (e != GPUAR_OK) return e;
@@ -4638,40 +4706,27 @@ int gpuar_hip_delta_block_host(uint32_t *mixed, uint32_t elem_bytes, int undo, u
 }
 
 static int launch_estimate(const gpuar::CrcArgs &a, void *stream) {
-    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kEstWaves - 1) / gpuar::kEstWaves;
-    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kEstGroups ? groups : gpuar::kEstGroups);
+    const uint32_t blocks = capped_blocks(a.n_packets, gpuar::kEstWaves, gpuar::kEstGroups);
     gpuar::estimate_kernel<<<blocks, gpuar::kEstWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }
 
 int gpuar_hip_estimate(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, void *stream) {
-    uint32_t *status = nullptr;
+    gpuar::CrcArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the CRC call's checks: same arguments
+    const int e = packet_checks(true, d_in, n_bytes, d_est, nullptr, nullptr, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::CrcArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
     a.crc = d_est;
-    a.status = status;
     return launch_estimate(a, stream);
 }
 
 int gpuar_hip_estimate_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
                              size_t n_buffers, size_t n_packets, uint32_t *d_est, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::CrcArgs a = {};
-    a.ptrs = d_in_ptrs;
-    a.bytes = d_in_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
+    gpuar::CrcArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(true, d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     a.crc = d_est;
-    a.status = status;
     return launch_estimate(a, stream);
 }
 
@@ -4682,47 +4737,33 @@ int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est) {
     return GPUAR_OK;
 }
 
-static int launch_survey(const gpuar::SurveyArgs &a, void *stream) {
-    const uint32_t windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
-    const uint32_t blocks = windows < gpuar::kSurveyGroups ? windows : gpuar::kSurveyGroups;
-    gpuar::survey_planes_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+// both surveys, into the rows at d_est: delta_mask 0 is the plane survey, anything else the delta survey of those widths
+static int launch_survey(gpuar::SurveyArgs a, uint32_t *d_est, size_t est_stride, uint32_t delta_mask, void *stream) {
+    a.est = d_est;
+    a.stride = est_stride;
+    const uint32_t blocks = capped_blocks(a.n_packets, 8u, gpuar::kSurveyGroups);       // a window of 8 packets at a time
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (delta_mask) gpuar::survey_delta_kernel<<<blocks, gpuar::kSurveyThreads, 0, s>>>(gpuar::DeltaSurveyArgs{a, delta_mask});
+    else gpuar::survey_planes_kernel<<<blocks, gpuar::kSurveyThreads, 0, s>>>(a);
     return check_launch();
 }
 
 int gpuar_hip_survey_planes(const uint8_t *d_in, size_t n_bytes, uint32_t *d_est, size_t est_stride, void *stream) {
-    if (n_bytes == 0) return GPUAR_OK;
-    if (est_stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
-    uint32_t *status = nullptr;
+    gpuar::SurveyArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the estimate call's checks
+    const int e = packet_checks(est_stride >= gpuar_hip_packet_count(n_bytes), d_in, n_bytes, d_est, nullptr, nullptr, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::SurveyArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
-    a.est = d_est;
-    a.stride = est_stride;
-    a.status = status;
-    return launch_survey(a, stream);
+    return launch_survey(a, d_est, est_stride, 0u, stream);
 }
 
 int gpuar_hip_survey_planes_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
                                   size_t n_buffers, size_t n_packets, uint32_t *d_est, size_t est_stride, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    if (est_stride < n_packets) return GPUAR_ERR_ARGUMENT;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::SurveyArgs a = {};
-    a.ptrs = d_in_ptrs;
-    a.bytes = d_in_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
-    a.est = d_est;
-    a.stride = est_stride;
-    a.status = status;
-    return launch_survey(a, stream);
+    gpuar::SurveyArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(est_stride >= n_packets, d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status,
+                                      &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    return launch_survey(a, d_est, est_stride, 0u, stream);
 }
 
 int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *est, size_t est_stride) {
@@ -4732,50 +4773,25 @@ int gpuar_hip_survey_planes_host(const uint8_t *in, size_t n_bytes, uint32_t *es
     return GPUAR_OK;
 }
 
-static int launch_delta_survey(const gpuar::SurveyArgs &s, uint32_t widths_mask, void *stream) {
-    gpuar::DeltaSurveyArgs a = {s, widths_mask};
-    const uint32_t windows = (s.n_packets >> 3) + ((s.n_packets & 7u) ? 1u : 0u);
-    const uint32_t blocks = windows < gpuar::kSurveyGroups ? windows : gpuar::kSurveyGroups;
-    gpuar::survey_delta_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
-    return check_launch();
-}
-
 static bool delta_survey_mask_ok(uint32_t widths_mask) { return widths_mask != 0u && (widths_mask & ~gpuar::kSurveyAllWidths) == 0u; }
 
 int gpuar_hip_survey_delta(const uint8_t *d_in, size_t n_bytes, uint32_t widths_mask, uint32_t *d_est, size_t est_stride, void *stream) {
-    if (n_bytes == 0) return GPUAR_OK;
-    if (est_stride < gpuar_hip_packet_count(n_bytes) || !delta_survey_mask_ok(widths_mask)) return GPUAR_ERR_ARGUMENT;
-    uint32_t *status = nullptr;
+    gpuar::SurveyArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, nullptr, &status, &launch);      // the estimate call's checks
+    const int e = packet_checks(est_stride >= gpuar_hip_packet_count(n_bytes) && delta_survey_mask_ok(widths_mask), d_in, n_bytes, d_est, nullptr,
+                                nullptr, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::SurveyArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
-    a.est = d_est;
-    a.stride = est_stride;
-    a.status = status;
-    return launch_delta_survey(a, widths_mask, stream);
+    return launch_survey(a, d_est, est_stride, widths_mask, stream);
 }
 
 int gpuar_hip_survey_delta_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet, size_t n_buffers,
                                  size_t n_packets, uint32_t widths_mask, uint32_t *d_est, size_t est_stride, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    if (est_stride < n_packets || !delta_survey_mask_ok(widths_mask)) return GPUAR_ERR_ARGUMENT;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_est, nullptr, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::SurveyArgs a = {};
-    a.ptrs = d_in_ptrs;
-    a.bytes = d_in_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
-    a.est = d_est;
-    a.stride = est_stride;
-    a.status = status;
-    return launch_delta_survey(a, widths_mask, stream);
+    gpuar::SurveyArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(est_stride >= n_packets && delta_survey_mask_ok(widths_mask), d_in_ptrs, d_in_bytes, d_first_packet, n_buffers,
+                                      n_packets, d_est, nullptr, d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    return launch_survey(a, d_est, est_stride, widths_mask, stream);
 }
 
 int gpuar_hip_survey_delta_host(const uint8_t *in, size_t n_bytes, uint32_t widths_mask, uint32_t *est, size_t est_stride) {
@@ -4796,21 +4812,11 @@ uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets) { 
 
 int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes, size_t n_regions,
                            uint32_t *d_status, void *stream) {
-    if (n_regions == 0) return GPUAR_OK;
-    if (!d_src_ptrs || !d_dst_ptrs || !d_bytes || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_src_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
-        return GPUAR_ERR_ALIGNMENT;
     gpuar::MoveArgs a = {};
     a.src = d_src_ptrs;
     a.dst = d_dst_ptrs;
     a.bytes = d_bytes;
-    a.n_regions = static_cast<uint32_t>(n_regions);
-    a.status = status_word(d_status);
-    if (!a.status) return GPUAR_ERR_NO_DEVICE;
-    const uint32_t blocks = a.n_regions < gpuar::kPlaneGridCap ? a.n_regions : gpuar::kPlaneGridCap;
-    gpuar::move_packets_kernel<<<blocks, gpuar::kMoveThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
-    return check_launch();
+    return region_call(gpuar::move_packets_kernel, 1u, gpuar::kMoveThreads, a, {d_src_ptrs, d_dst_ptrs, d_bytes}, {}, n_regions, d_status, stream);
 }
 
 uint32_t gpuar_hip_sparse_len(uint32_t k) { return gpuar::sparse_len(k); }
@@ -4820,40 +4826,27 @@ int gpuar_hip_sparse_rule(uint32_t scan, uint32_t est, uint32_t ulen, int stored
 }
 
 static int launch_sparse_scan(const gpuar::CrcArgs &a, void *stream) {
-    const size_t groups = (static_cast<size_t>(a.n_packets) + gpuar::kSparseWaves - 1) / gpuar::kSparseWaves;
-    const uint32_t blocks = static_cast<uint32_t>(groups < gpuar::kSparseGroups ? groups : gpuar::kSparseGroups);
+    const uint32_t blocks = capped_blocks(a.n_packets, gpuar::kSparseWaves, gpuar::kSparseGroups);
     gpuar::sparse_scan_kernel<<<blocks, gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }
 
 int gpuar_hip_sparse_scan(const uint8_t *d_in, size_t n_bytes, uint32_t *d_scan, void *stream) {
-    uint32_t *status = nullptr;
+    gpuar::CrcArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_scan, nullptr, nullptr, &status, &launch);     // the estimate call's checks
+    const int e = packet_checks(true, d_in, n_bytes, d_scan, nullptr, nullptr, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
-    gpuar::CrcArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
     a.crc = d_scan;
-    a.status = status;
     return launch_sparse_scan(a, stream);
 }
 
 int gpuar_hip_sparse_scan_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
                                 size_t n_buffers, size_t n_packets, uint32_t *d_scan, uint32_t *d_status, void *stream) {
-    if (n_packets == 0) return GPUAR_OK;
-    uint32_t *status = nullptr;
-    const int e = crc32_batch_arguments(d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_scan, nullptr, d_status, &status);
-    if (e != GPUAR_OK) return e;
-    gpuar::CrcArgs a = {};
-    a.ptrs = d_in_ptrs;
-    a.bytes = d_in_bytes;
-    a.first_packet = d_first_packet;
-    a.n_buffers = static_cast<uint32_t>(n_buffers);
-    a.n_packets = static_cast<uint32_t>(n_packets);
+    gpuar::CrcArgs a;
+    bool launch = false;
+    const int e = packet_batch_checks(true, d_in_ptrs, d_in_bytes, d_first_packet, n_buffers, n_packets, d_scan, nullptr, d_status, &a, &launch);
+    if (e != GPUAR_OK || !launch) return e;
     a.crc = d_scan;
-    a.status = status;
     return launch_sparse_scan(a, stream);
 }
 
@@ -4864,47 +4857,26 @@ int gpuar_hip_sparse_scan_host(const uint8_t *in, size_t n_bytes, uint32_t *scan
     return GPUAR_OK;
 }
 
-static uint32_t sparse_blocks(uint32_t n_regions) {
-    const uint32_t groups = n_regions / gpuar::kSparseWaves + (n_regions % gpuar::kSparseWaves ? 1u : 0u);
-    return groups < gpuar::kPlaneGridCap ? groups : gpuar::kPlaneGridCap;
-}
-
 int gpuar_hip_sparse_pack(const uint8_t *const *d_src_ptrs, const uint64_t *d_bytes, const uint32_t *d_scan, uint8_t *const *d_dst_ptrs,
                           size_t n_regions, uint32_t *d_status, void *stream) {
-    if (n_regions == 0) return GPUAR_OK;
-    if (!d_src_ptrs || !d_bytes || !d_scan || !d_dst_ptrs || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_src_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_scan) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
-        return GPUAR_ERR_ALIGNMENT;
     gpuar::SparsePackArgs a = {};
     a.src = d_src_ptrs;
     a.bytes = d_bytes;
     a.scan = d_scan;
     a.dst = d_dst_ptrs;
-    a.n_regions = static_cast<uint32_t>(n_regions);
-    a.status = status_word(d_status);
-    if (!a.status) return GPUAR_ERR_NO_DEVICE;
-    gpuar::sparse_pack_kernel<<<sparse_blocks(a.n_regions), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
-    return check_launch();
+    return region_call(gpuar::sparse_pack_kernel, gpuar::kSparseWaves, gpuar::kSparseWaves * gpuar::kLanes, a, {d_src_ptrs, d_bytes, d_dst_ptrs},
+                       {d_scan}, n_regions, d_status, stream);
 }
 
 int gpuar_hip_sparse_unpack(const uint8_t *const *d_rec_ptrs, const uint64_t *d_rec_bytes, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes,
                             size_t n_regions, uint32_t *d_status, void *stream) {
-    if (n_regions == 0) return GPUAR_OK;
-    if (!d_rec_ptrs || !d_rec_bytes || !d_dst_ptrs || !d_bytes || n_regions > 0xFFFFFFFFull) return GPUAR_ERR_ARGUMENT;
-    if ((reinterpret_cast<uintptr_t>(d_rec_ptrs) & 7u) || (reinterpret_cast<uintptr_t>(d_rec_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_dst_ptrs) & 7u) ||
-        (reinterpret_cast<uintptr_t>(d_bytes) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u))
-        return GPUAR_ERR_ALIGNMENT;
     gpuar::SparseUnpackArgs a = {};
     a.rec = d_rec_ptrs;
     a.rec_bytes = d_rec_bytes;
     a.dst = d_dst_ptrs;
     a.bytes = d_bytes;
-    a.n_regions = static_cast<uint32_t>(n_regions);
-    a.status = status_word(d_status);
-    if (!a.status) return GPUAR_ERR_NO_DEVICE;
-    gpuar::sparse_unpack_kernel<<<sparse_blocks(a.n_regions), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
-    return check_launch();
+    return region_call(gpuar::sparse_unpack_kernel, gpuar::kSparseWaves, gpuar::kSparseWaves * gpuar::kLanes, a,
+                       {d_rec_ptrs, d_rec_bytes, d_dst_ptrs, d_bytes}, {}, n_regions, d_status, stream);
 }
 
 int gpuar_hip_sparse_pack_host(const uint8_t *in, size_t n_bytes, uint8_t *rec, size_t rec_room, size_t *rec_len) {
@@ -4917,39 +4889,30 @@ int gpuar_hip_sparse_unpack_host(const uint8_t *rec, size_t rec_bytes, uint8_t *
     return gpuar::sparse_unpack_host(rec, rec_bytes, out, static_cast<uint32_t>(n_bytes)) ? GPUAR_OK : GPUAR_ERR_ARGUMENT;
 }
 
-static uint32_t kinds_blocks(uint32_t n_packets) {
-    const uint32_t groups = n_packets / gpuar::kSparseWaves + (n_packets % gpuar::kSparseWaves ? 1u : 0u);
-    return groups < gpuar::kSparseGroups ? groups : gpuar::kSparseGroups;
-}
-
 int gpuar_hip_kinds_store(const uint8_t *d_in, size_t n_bytes, const uint32_t *d_est, const uint32_t *d_scan, int stored_on, uint8_t *d_slots,
                           uint8_t *d_kind, uint32_t *d_status, void *stream) {
-    uint32_t *status = nullptr;
+    gpuar::KindsStoreArgs a;
     bool launch = false;
-    const int e = crc32_arguments(d_in, n_bytes, d_est, nullptr, d_status, &status, &launch);     // the estimate call's checks
+    const int e = packet_checks(true, d_in, n_bytes, d_est, nullptr, d_status, &a, &launch);
     if (e != GPUAR_OK || !launch) return e;
     if (!d_slots || !d_kind) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_slots) || (reinterpret_cast<uintptr_t>(d_scan) & 3u)) return GPUAR_ERR_ALIGNMENT;
-    gpuar::KindsStoreArgs a = {};
-    a.in = d_in;
-    a.n_bytes = n_bytes;
+    if (misaligned(d_slots, 16) || misaligned(d_scan, 4)) return GPUAR_ERR_ALIGNMENT;
     a.est = d_est;
     a.scan = d_scan;
     a.stored_on = stored_on != 0 ? 1u : 0u;
     a.slots = d_slots;
     a.kind = d_kind;
-    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
-    a.status = status;
-    gpuar::kinds_store_kernel<<<kinds_blocks(a.n_packets), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    const uint32_t blocks = capped_blocks(a.n_packets, gpuar::kSparseWaves, gpuar::kSparseGroups);
+    gpuar::kinds_store_kernel<<<blocks, gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }
 
 int gpuar_hip_kinds_expand(const uint8_t *d_stream, const uint64_t *d_offsets, const uint8_t *d_kind, size_t n_packets, uint8_t *d_out,
                            size_t n_bytes, uint32_t *d_status, void *stream) {
     if (n_packets == 0) return GPUAR_OK;
-    if (!d_stream || !d_offsets || !d_kind || !d_out || n_packets > 0xFFFFFFFFull || gpuar_hip_packet_count(n_bytes) != n_packets)
+    if (!d_stream || !d_offsets || !d_kind || !d_out || n_packets > kMaxCount || gpuar_hip_packet_count(n_bytes) != n_packets)
         return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_out) || (reinterpret_cast<uintptr_t>(d_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_status) & 3u)) return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_out, 16) || misaligned(d_offsets, 8) || misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
     gpuar::KindsExpandArgs a = {};
     a.stream = d_stream;
     a.offsets = d_offsets;
@@ -4959,7 +4922,8 @@ int gpuar_hip_kinds_expand(const uint8_t *d_stream, const uint64_t *d_offsets, c
     a.n_bytes = n_bytes;
     a.status = status_word(d_status);
     if (!a.status) return GPUAR_ERR_NO_DEVICE;
-    gpuar::kinds_expand_kernel<<<kinds_blocks(a.n_packets), gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
+    const uint32_t blocks = capped_blocks(a.n_packets, gpuar::kSparseWaves, gpuar::kSparseGroups);
+    gpuar::kinds_expand_kernel<<<blocks, gpuar::kSparseWaves * gpuar::kLanes, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }
 
@@ -5019,7 +4983,7 @@ int gpuar_hip_abi_version(void) { return GPUAR_HIP_ABI_VERSION; }
 int gpuar_hip_generate(int kind, uint64_t seed, uint64_t offset, size_t n, uint8_t *d_out, void *stream) {
     if (n == 0) return GPUAR_OK;
     if (!d_out || (offset & 7u) || kind < 0 || kind > 2) return GPUAR_ERR_ARGUMENT;
-    if (reinterpret_cast<uintptr_t>(d_out) & 7u) return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_out, 8)) return GPUAR_ERR_ALIGNMENT;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t groups = (n + 7) / 8;
     const uint32_t blocks = static_cast<uint32_t>((groups + 255) / 256);
@@ -5045,7 +5009,7 @@ int gpuar_hip_generate(int kind, uint64_t seed, uint64_t offset, size_t n, uint8
 int gpuar_hip_copy(const uint8_t *d_src, uint8_t *d_dst, size_t n_bytes, void *stream) {
     if (n_bytes == 0) return GPUAR_OK;
     if (!d_src || !d_dst || (n_bytes & 15u)) return GPUAR_ERR_ARGUMENT;
-    if (!aligned16(d_src) || !aligned16(d_dst)) return GPUAR_ERR_ALIGNMENT;
+    if (misaligned(d_src, 16) || misaligned(d_dst, 16)) return GPUAR_ERR_ALIGNMENT;
     const size_t n_quads = n_bytes / 16u;
     const size_t want = (n_quads + 255u) / 256u;                    // one quad per thread
     // HIP rejects a launch once gridDim.x * blockDim.x reaches 2^32 threads: 64 GiB less one tile for this kernel (bench.py

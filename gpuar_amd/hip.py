@@ -20,26 +20,82 @@ KIND_ID = {"uniform": 0, "zipf": 1, "text": 2}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgpuar_hip.so")
-EXPORTS = [
-    "initConstantRange", "garCompressExecutor", "garDecompressExecutor",
-    "gpuar_hip_packet_count", "gpuar_hip_encode", "gpuar_hip_encode_mode", "gpuar_hip_decode", "gpuar_hip_compact",
-    "gpuar_hip_decode_stream", "gpuar_hip_status", "gpuar_hip_last_error", "gpuar_hip_error_string",
-    "gpuar_hip_version", "gpuar_hip_abi_version", "gpuar_hip_generate", "gpuar_hip_copy", "gpuar_hip_clock_samples",
-    "gpuar_hip_batch_packet_count", "gpuar_hip_encode_batch", "gpuar_hip_decode_batch", "gpuar_hip_decode_stream_batch",
-    "gpuar_hip_crc32", "gpuar_hip_verify_crc32", "gpuar_hip_crc32_batch", "gpuar_hip_verify_crc32_batch",
-    "gpuar_hip_split_planes", "gpuar_hip_merge_planes", "gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch",
-    "gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host",
-    "gpuar_hip_split_delta", "gpuar_hip_merge_delta", "gpuar_hip_split_delta_batch", "gpuar_hip_merge_delta_batch",
-    "gpuar_hip_split_delta_host", "gpuar_hip_merge_delta_host", "gpuar_hip_delta_block_host",
-    "gpuar_hip_split_xor", "gpuar_hip_merge_xor", "gpuar_hip_split_xor_batch", "gpuar_hip_merge_xor_batch",
-    "gpuar_hip_split_xor_host", "gpuar_hip_merge_xor_host",
-    "gpuar_hip_estimate", "gpuar_hip_estimate_batch", "gpuar_hip_estimate_host", "gpuar_hip_move_packets",
-    "gpuar_hip_survey_planes", "gpuar_hip_survey_planes_batch", "gpuar_hip_survey_planes_host", "gpuar_hip_choose_planes",
-    "gpuar_hip_survey_delta", "gpuar_hip_survey_delta_batch", "gpuar_hip_survey_delta_host", "gpuar_hip_choose_filter",
-    "gpuar_hip_sparse_len", "gpuar_hip_sparse_rule", "gpuar_hip_sparse_scan", "gpuar_hip_sparse_scan_batch", "gpuar_hip_sparse_scan_host",
-    "gpuar_hip_sparse_pack", "gpuar_hip_sparse_unpack", "gpuar_hip_sparse_pack_host", "gpuar_hip_sparse_unpack_host",
-    "gpuar_hip_kinds_store", "gpuar_hip_kinds_expand", "gpuar_hip_kinds_store_host", "gpuar_hip_kinds_expand_host",
-]
+
+_int, _vp, _sz, _u32, _u64, _str = C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint64, C.c_char_p
+_pu32, _pu64, _psz = C.POINTER(_u32), C.POINTER(_u64), C.POINTER(_sz)
+_BATCH = [_vp, _vp, _vp, _sz, _sz]   # the descriptors of a batch: pointers, bytes, first_packet, n_buffers, n_packets
+
+
+def _both(stem, restype, argtypes):
+    """the split and the merge call of one filter: one prototype"""
+    return {f"gpuar_hip_split_{stem}": (restype, argtypes), f"gpuar_hip_merge_{stem}": (restype, argtypes)}
+
+
+# Every export of the library with its (restype, argtypes): the prototypes of include/gpuar_hip.h, each once.  d_status and stream
+# are the two _vp at the end of the calls that take them.
+SIGNATURES = {
+    "initConstantRange": (None, []),
+    "garCompressExecutor": (None, [_vp, _sz, _vp, _u32]),
+    "garDecompressExecutor": (None, [_vp, _sz, _vp, _u32]),
+    "gpuar_hip_packet_count": (_sz, [_sz]),
+    "gpuar_hip_encode": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "gpuar_hip_encode_mode": (_int, [_vp, _sz, _vp, _vp, _vp, _int]),
+    "gpuar_hip_decode": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "gpuar_hip_compact": (_int, [_vp, _sz, _vp, _vp, _vp]),
+    "gpuar_hip_decode_stream": (_int, [_vp, _vp, _sz, _vp, _vp, _vp]),
+    "gpuar_hip_status": (_int, [_pu32]),
+    "gpuar_hip_last_error": (_int, []),
+    "gpuar_hip_error_string": (_str, [_int]),
+    "gpuar_hip_version": (_str, []),
+    "gpuar_hip_abi_version": (_int, []),
+    "gpuar_hip_generate": (_int, [_int, _u64, _u64, _sz, _vp, _vp]),
+    "gpuar_hip_copy": (_int, [_vp, _vp, _sz, _vp]),
+    "gpuar_hip_clock_samples": (_int, [_int, _pu64, _int]),
+    "gpuar_hip_batch_packet_count": (_sz, [_pu64, _sz, _pu64]),
+    "gpuar_hip_encode_batch": (_int, [*_BATCH, _vp, _vp, _vp, _int]),
+    "gpuar_hip_decode_batch": (_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_decode_stream_batch": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_crc32": (_int, [_vp, _sz, _vp, _vp]),
+    "gpuar_hip_verify_crc32": (_int, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_crc32_batch": (_int, [*_BATCH, _vp, _vp, _vp]),
+    "gpuar_hip_verify_crc32_batch": (_int, [*_BATCH, _vp, _vp, _vp, _vp]),
+    **_both("planes", _int, [_vp, _sz, _u32, _vp, _vp]),
+    **_both("planes_batch", _int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    **_both("planes_host", _int, [_vp, _sz, _u32, _vp]),
+    **_both("delta", _int, [_vp, _sz, _u32, _vp, _vp]),
+    **_both("delta_batch", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    **_both("delta_host", _int, [_vp, _sz, _u32, _vp]),
+    "gpuar_hip_delta_block_host": (_int, [_pu32, _u32, _int, _u64, _pu64]),
+    **_both("xor", _int, [_vp, _vp, _sz, _u32, _vp, _vp]),
+    **_both("xor_batch", _int, [_vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    **_both("xor_host", _int, [_vp, _vp, _sz, _u32, _vp]),
+    "gpuar_hip_estimate": (_int, [_vp, _sz, _vp, _vp]),
+    "gpuar_hip_estimate_batch": (_int, [*_BATCH, _vp, _vp, _vp]),
+    "gpuar_hip_estimate_host": (_int, [_vp, _sz, _vp]),
+    "gpuar_hip_move_packets": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_survey_planes": (_int, [_vp, _sz, _vp, _sz, _vp]),
+    "gpuar_hip_survey_planes_batch": (_int, [*_BATCH, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_survey_planes_host": (_int, [_vp, _sz, _vp, _sz]),
+    "gpuar_hip_choose_planes": (_u32, [_pu64, _u64]),
+    "gpuar_hip_survey_delta": (_int, [_vp, _sz, _u32, _vp, _sz, _vp]),
+    "gpuar_hip_survey_delta_batch": (_int, [*_BATCH, _u32, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_survey_delta_host": (_int, [_vp, _sz, _u32, _vp, _sz]),
+    "gpuar_hip_choose_filter": (_int, [_pu64, _pu64, _u64, _pu32]),
+    "gpuar_hip_sparse_len": (_u32, [_u32]),
+    "gpuar_hip_sparse_rule": (_int, [_u32, _u32, _u32, _int]),
+    "gpuar_hip_sparse_scan": (_int, [_vp, _sz, _vp, _vp]),
+    "gpuar_hip_sparse_scan_batch": (_int, [*_BATCH, _vp, _vp, _vp]),
+    "gpuar_hip_sparse_scan_host": (_int, [_vp, _sz, _vp]),
+    "gpuar_hip_sparse_pack": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_sparse_unpack": (_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_sparse_pack_host": (_int, [_vp, _sz, _vp, _sz, _psz]),
+    "gpuar_hip_sparse_unpack_host": (_int, [_vp, _sz, _vp, _sz]),
+    "gpuar_hip_kinds_store": (_int, [_vp, _sz, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_kinds_expand": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_kinds_store_host": (_int, [_vp, _sz, _int, _int, _vp, _sz, _pu32, _psz]),
+    "gpuar_hip_kinds_expand_host": (_int, [_vp, _sz, _u32, _vp, _sz]),
+}
+EXPORTS = list(SIGNATURES)
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -62,140 +118,12 @@ def load() -> C.CDLL:
                          "(hipcc --offload-arch=gfx950); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
     # a library built from older sources lacks newer exports: say "rebuild" instead of dying with an AttributeError half-way
-    # through the declarations below
+    # through the signatures
     missing = [name for name in EXPORTS if not hasattr(lib, name)]
     if missing:
         raise GpuarError(f"{LIB_PATH} lacks {missing}: it was built from older sources -- rebuild the library")
-    vp, sz, u32 = C.c_void_p, C.c_size_t, C.c_uint32
-    lib.initConstantRange.restype = None
-    lib.initConstantRange.argtypes = []
-    lib.garCompressExecutor.restype = None
-    lib.garCompressExecutor.argtypes = [vp, sz, vp, u32]
-    lib.garDecompressExecutor.restype = None
-    lib.garDecompressExecutor.argtypes = [vp, sz, vp, u32]
-    lib.gpuar_hip_packet_count.restype = sz
-    lib.gpuar_hip_packet_count.argtypes = [sz]
-    lib.gpuar_hip_encode.restype = C.c_int
-    lib.gpuar_hip_encode.argtypes = [vp, sz, vp, vp, vp]
-    lib.gpuar_hip_encode_mode.restype = C.c_int
-    lib.gpuar_hip_encode_mode.argtypes = [vp, sz, vp, vp, vp, C.c_int]
-    lib.gpuar_hip_decode.restype = C.c_int
-    lib.gpuar_hip_decode.argtypes = [vp, sz, vp, vp, vp]
-    lib.gpuar_hip_compact.restype = C.c_int
-    lib.gpuar_hip_compact.argtypes = [vp, sz, vp, vp, vp]
-    lib.gpuar_hip_decode_stream.restype = C.c_int
-    lib.gpuar_hip_decode_stream.argtypes = [vp, vp, sz, vp, vp, vp]
-    lib.gpuar_hip_status.restype = C.c_int
-    lib.gpuar_hip_status.argtypes = [C.POINTER(C.c_uint32)]
-    lib.gpuar_hip_last_error.restype = C.c_int
-    lib.gpuar_hip_last_error.argtypes = []
-    lib.gpuar_hip_error_string.restype = C.c_char_p
-    lib.gpuar_hip_error_string.argtypes = [C.c_int]
-    lib.gpuar_hip_version.restype = C.c_char_p
-    lib.gpuar_hip_version.argtypes = []
-    lib.gpuar_hip_abi_version.restype = C.c_int
-    lib.gpuar_hip_abi_version.argtypes = []
-    lib.gpuar_hip_generate.restype = C.c_int
-    lib.gpuar_hip_generate.argtypes = [C.c_int, C.c_uint64, C.c_uint64, sz, vp, vp]
-    lib.gpuar_hip_copy.restype = C.c_int
-    lib.gpuar_hip_copy.argtypes = [vp, vp, sz, vp]
-    lib.gpuar_hip_clock_samples.restype = C.c_int
-    lib.gpuar_hip_clock_samples.argtypes = [C.c_int, C.POINTER(C.c_uint64), C.c_int]
-    lib.gpuar_hip_batch_packet_count.restype = sz
-    lib.gpuar_hip_batch_packet_count.argtypes = [C.POINTER(C.c_uint64), sz, C.POINTER(C.c_uint64)]
-    lib.gpuar_hip_encode_batch.restype = C.c_int
-    lib.gpuar_hip_encode_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, C.c_int]
-    lib.gpuar_hip_decode_batch.restype = C.c_int
-    lib.gpuar_hip_decode_batch.argtypes = [vp, vp, sz, sz, vp, vp, vp, vp]
-    lib.gpuar_hip_decode_stream_batch.restype = C.c_int
-    lib.gpuar_hip_decode_stream_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
-    lib.gpuar_hip_crc32.restype = C.c_int
-    lib.gpuar_hip_crc32.argtypes = [vp, sz, vp, vp]
-    lib.gpuar_hip_verify_crc32.restype = C.c_int
-    lib.gpuar_hip_verify_crc32.argtypes = [vp, sz, vp, vp, vp, vp]
-    lib.gpuar_hip_crc32_batch.restype = C.c_int
-    lib.gpuar_hip_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
-    lib.gpuar_hip_verify_crc32_batch.restype = C.c_int
-    lib.gpuar_hip_verify_crc32_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
-    for name in ("gpuar_hip_split_planes", "gpuar_hip_merge_planes"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, sz, u32, vp, vp]
-    for name in ("gpuar_hip_split_planes_batch", "gpuar_hip_merge_planes_batch"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp]
-    for name in ("gpuar_hip_split_planes_host", "gpuar_hip_merge_planes_host"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, sz, u32, vp]
-    for name in ("gpuar_hip_split_delta", "gpuar_hip_merge_delta"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, sz, u32, vp, vp]
-    for name in ("gpuar_hip_split_delta_batch", "gpuar_hip_merge_delta_batch"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
-    for name in ("gpuar_hip_split_delta_host", "gpuar_hip_merge_delta_host"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, sz, u32, vp]
-    lib.gpuar_hip_delta_block_host.restype = C.c_int
-    lib.gpuar_hip_delta_block_host.argtypes = [C.POINTER(C.c_uint32), u32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
-    for name in ("gpuar_hip_split_xor", "gpuar_hip_merge_xor"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, sz, u32, vp, vp]
-    for name in ("gpuar_hip_split_xor_batch", "gpuar_hip_merge_xor_batch"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
-    for name in ("gpuar_hip_split_xor_host", "gpuar_hip_merge_xor_host"):
-        getattr(lib, name).restype = C.c_int
-        getattr(lib, name).argtypes = [vp, vp, sz, u32, vp]
-    lib.gpuar_hip_estimate.restype = C.c_int
-    lib.gpuar_hip_estimate.argtypes = [vp, sz, vp, vp]
-    lib.gpuar_hip_estimate_batch.restype = C.c_int
-    lib.gpuar_hip_estimate_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
-    lib.gpuar_hip_estimate_host.restype = C.c_int
-    lib.gpuar_hip_estimate_host.argtypes = [vp, sz, vp]
-    lib.gpuar_hip_move_packets.restype = C.c_int
-    lib.gpuar_hip_move_packets.argtypes = [vp, vp, vp, sz, vp, vp]
-    lib.gpuar_hip_survey_planes.restype = C.c_int
-    lib.gpuar_hip_survey_planes.argtypes = [vp, sz, vp, sz, vp]
-    lib.gpuar_hip_survey_planes_batch.restype = C.c_int
-    lib.gpuar_hip_survey_planes_batch.argtypes = [vp, vp, vp, sz, sz, vp, sz, vp, vp]
-    lib.gpuar_hip_survey_planes_host.restype = C.c_int
-    lib.gpuar_hip_survey_planes_host.argtypes = [vp, sz, vp, sz]
-    lib.gpuar_hip_choose_planes.restype = u32
-    lib.gpuar_hip_choose_planes.argtypes = [C.POINTER(C.c_uint64), C.c_uint64]
-    lib.gpuar_hip_survey_delta.restype = C.c_int
-    lib.gpuar_hip_survey_delta.argtypes = [vp, sz, u32, vp, sz, vp]
-    lib.gpuar_hip_survey_delta_batch.restype = C.c_int
-    lib.gpuar_hip_survey_delta_batch.argtypes = [vp, vp, vp, sz, sz, u32, vp, sz, vp, vp]
-    lib.gpuar_hip_survey_delta_host.restype = C.c_int
-    lib.gpuar_hip_survey_delta_host.argtypes = [vp, sz, u32, vp, sz]
-    lib.gpuar_hip_choose_filter.restype = C.c_int
-    lib.gpuar_hip_choose_filter.argtypes = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint64, C.POINTER(u32)]
-    lib.gpuar_hip_sparse_len.restype = u32
-    lib.gpuar_hip_sparse_len.argtypes = [u32]
-    lib.gpuar_hip_sparse_rule.restype = C.c_int
-    lib.gpuar_hip_sparse_rule.argtypes = [u32, u32, u32, C.c_int]
-    lib.gpuar_hip_sparse_scan.restype = C.c_int
-    lib.gpuar_hip_sparse_scan.argtypes = [vp, sz, vp, vp]
-    lib.gpuar_hip_sparse_scan_batch.restype = C.c_int
-    lib.gpuar_hip_sparse_scan_batch.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
-    lib.gpuar_hip_sparse_scan_host.restype = C.c_int
-    lib.gpuar_hip_sparse_scan_host.argtypes = [vp, sz, vp]
-    lib.gpuar_hip_sparse_pack.restype = C.c_int
-    lib.gpuar_hip_sparse_pack.argtypes = [vp, vp, vp, vp, sz, vp, vp]
-    lib.gpuar_hip_sparse_unpack.restype = C.c_int
-    lib.gpuar_hip_sparse_unpack.argtypes = [vp, vp, vp, vp, sz, vp, vp]
-    lib.gpuar_hip_sparse_pack_host.restype = C.c_int
-    lib.gpuar_hip_sparse_pack_host.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
-    lib.gpuar_hip_sparse_unpack_host.restype = C.c_int
-    lib.gpuar_hip_sparse_unpack_host.argtypes = [vp, sz, vp, sz]
-    lib.gpuar_hip_kinds_store.restype = C.c_int
-    lib.gpuar_hip_kinds_store.argtypes = [vp, sz, vp, vp, C.c_int, vp, vp, vp, vp]
-    lib.gpuar_hip_kinds_expand.restype = C.c_int
-    lib.gpuar_hip_kinds_expand.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp]
-    lib.gpuar_hip_kinds_store_host.restype = C.c_int
-    lib.gpuar_hip_kinds_store_host.argtypes = [vp, sz, C.c_int, C.c_int, vp, sz, C.POINTER(u32), C.POINTER(sz)]
-    lib.gpuar_hip_kinds_expand_host.restype = C.c_int
-    lib.gpuar_hip_kinds_expand_host.argtypes = [vp, sz, u32, vp, sz]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
     _lib = lib
@@ -215,6 +143,11 @@ def _mode_id(mode, env_var) -> int:
 def _check(code: int, what: str) -> None:
     if code != 0:
         raise GpuarError(f"{what}: {load().gpuar_hip_error_string(code).decode()} (code {code})")
+
+
+def _call(name: str, *args) -> None:
+    """One call of an export that returns a code; anything but 0 raises with the export's name."""
+    _check(getattr(load(), name)(*args), name)
 
 
 def _stream_handle(stream=None) -> int:
@@ -243,6 +176,14 @@ def _status_ptr(d_status):
     return d_status.data_ptr()
 
 
+def _span(t, n_bytes, name="d_in"):
+    """(n, its packet count): the bytes of the uint8 tensor `t` a call works on -- the first n_bytes, by default all."""
+    n = t.numel() if n_bytes is None else n_bytes
+    if n > t.numel():
+        raise GpuarError(f"n_bytes is larger than {name}")
+    return n, packet_count(n)
+
+
 def encode(d_in, d_slots=None, stream=None, d_status=None, mode=None):
     """Encode the bytes of `d_in` into 8704-byte packet slots (garCompress layout).  `d_status`: this launch's
     own status word (a zeroed 1-element int32 CUDA tensor); None = the device's fallback word (status()).
@@ -256,8 +197,8 @@ def encode(d_in, d_slots=None, stream=None, d_status=None, mode=None):
     _require_cuda_u8(d_slots, "d_slots")
     if d_slots.numel() < npk * SLOT:
         raise GpuarError("d_slots too small")
-    _check(load().gpuar_hip_encode_mode(d_in.data_ptr(), n, d_slots.data_ptr(), _status_ptr(d_status), _stream_handle(stream),
-                                        _mode_id(mode, "GPUAR_ENCODE_MODE")), "gpuar_hip_encode_mode")
+    _call("gpuar_hip_encode_mode", d_in.data_ptr(), n, d_slots.data_ptr(), _status_ptr(d_status), _stream_handle(stream),
+          _mode_id(mode, "GPUAR_ENCODE_MODE"))
     return d_slots
 
 
@@ -272,7 +213,7 @@ def decode(d_slots, n_packets: int, d_out=None, stream=None, d_status=None):
     _require_cuda_u8(d_out, "d_out")
     if d_out.numel() < n_packets * PACKET:
         raise GpuarError("d_out too small")
-    _check(load().gpuar_hip_decode(d_slots.data_ptr(), n_packets, d_out.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_decode")
+    _call("gpuar_hip_decode", d_slots.data_ptr(), n_packets, d_out.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
     return d_out
 
 
@@ -284,8 +225,7 @@ def compact(d_slots, n_packets: int, d_stream=None, d_offsets=None, stream=None)
         d_stream = torch.empty(max(n_packets, 1) * SLOT, dtype=torch.uint8, device=d_slots.device)
     if d_offsets is None:
         d_offsets = torch.empty(n_packets + 1, dtype=torch.int64, device=d_slots.device)
-    _check(load().gpuar_hip_compact(d_slots.data_ptr(), n_packets, d_stream.data_ptr(), d_offsets.data_ptr(),
-                                    _stream_handle(stream)), "gpuar_hip_compact")
+    _call("gpuar_hip_compact", d_slots.data_ptr(), n_packets, d_stream.data_ptr(), d_offsets.data_ptr(), _stream_handle(stream))
     return d_stream, d_offsets
 
 
@@ -294,8 +234,8 @@ def decode_stream(d_stream, d_offsets, n_packets: int, d_out=None, stream=None, 
     _require_cuda_u8(d_stream, "d_stream")
     if d_out is None:
         d_out = torch.empty(max(n_packets, 1) * PACKET, dtype=torch.uint8, device=d_stream.device)
-    _check(load().gpuar_hip_decode_stream(d_stream.data_ptr(), d_offsets.data_ptr(), n_packets, d_out.data_ptr(),
-                                          _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_decode_stream")
+    _call("gpuar_hip_decode_stream", d_stream.data_ptr(), d_offsets.data_ptr(), n_packets, d_out.data_ptr(), _status_ptr(d_status),
+          _stream_handle(stream))
     return d_out
 
 
@@ -315,21 +255,26 @@ def _require_u64_desc(t, name, n):
         raise GpuarError(f"{name} must be a contiguous 64-bit CUDA tensor of at least {n} entries")
 
 
+def _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers, ptrs="d_ptrs", more=()):
+    """The descriptors of a batch call: the pointers (named `ptrs`), d_bytes, d_first_packet, then `more`: (tensor, name) of n_buffers entries."""
+    for t, name, n in ((d_ptrs, ptrs, n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
+                       *((t, name, n_buffers) for t, name in more)):
+        _require_u64_desc(t, name, n)
+
+
 def encode_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_slots=None, stream=None, d_status=None, mode=None,
                  device=None):
     """Encode a batch of buffers into n_packets slots (gpuar_hip_encode_batch).  d_ptrs / d_bytes / d_first_packet: device
     descriptor tensors (int64: buffer addresses, byte counts, n_buffers + 1 first packets).  `mode` as for encode()."""
     import torch
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
+    _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers)
     if d_slots is None:
         d_slots = torch.empty(max(n_packets, 1) * SLOT, dtype=torch.uint8, device=device or d_ptrs.device)
     _require_cuda_u8(d_slots, "d_slots")
     if d_slots.numel() < n_packets * SLOT:
         raise GpuarError("d_slots too small")
-    _check(load().gpuar_hip_encode_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                         d_slots.data_ptr(), _status_ptr(d_status), _stream_handle(stream),
-                                         _mode_id(mode, "GPUAR_ENCODE_MODE")), "gpuar_hip_encode_batch")
+    _call("gpuar_hip_encode_batch", d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, d_slots.data_ptr(),
+          _status_ptr(d_status), _stream_handle(stream), _mode_id(mode, "GPUAR_ENCODE_MODE"))
     return d_slots
 
 
@@ -340,8 +285,8 @@ def decode_batch(d_slots, d_first_packet, n_buffers: int, n_packets: int, d_out_
         raise GpuarError("d_slots too small")
     for t, name, n in ((d_out_ptrs, "d_out_ptrs", n_buffers), (d_out_bytes, "d_out_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
         _require_u64_desc(t, name, n)
-    _check(load().gpuar_hip_decode_batch(d_slots.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(),
-                                         d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_decode_batch")
+    _call("gpuar_hip_decode_batch", d_slots.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(),
+          d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
 
 
 def decode_stream_batch(d_stream, d_offsets, d_first_packet, n_buffers: int, n_packets: int, d_out_ptrs, d_out_bytes, stream=None,
@@ -351,9 +296,8 @@ def decode_stream_batch(d_stream, d_offsets, d_first_packet, n_buffers: int, n_p
     for t, name, n in ((d_offsets, "d_offsets", n_packets + 1), (d_out_ptrs, "d_out_ptrs", n_buffers), (d_out_bytes, "d_out_bytes", n_buffers),
                        (d_first_packet, "d_first_packet", n_buffers + 1)):
         _require_u64_desc(t, name, n)
-    _check(load().gpuar_hip_decode_stream_batch(d_stream.data_ptr(), d_offsets.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                                d_out_ptrs.data_ptr(), d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream)),
-           "gpuar_hip_decode_stream_batch")
+    _call("gpuar_hip_decode_stream_batch", d_stream.data_ptr(), d_offsets.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+          d_out_ptrs.data_ptr(), d_out_bytes.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
 
 
 def _require_crc(t, name, n):
@@ -361,6 +305,42 @@ def _require_crc(t, name, n):
     import torch
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.element_size() == 4 and t.is_contiguous() and t.numel() >= n):
         raise GpuarError(f"{name} must be a contiguous 32-bit CUDA tensor of at least {n} entries")
+
+
+def _words(d_words, name, n, device, whole=False):
+    """A call's result of n 32-bit words: the caller's tensor, or a new int32 one (`whole`: not cut to n where n is 0)."""
+    import torch
+    if d_words is None:
+        d_words = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        d_words = d_words if whole else d_words[:n]
+    _require_crc(d_words, name, n)
+    return d_words
+
+
+def _words_single(export, d_in, n_bytes, d_words, name, stream, whole=False):
+    """The calls that give one 32-bit word per packet of one buffer (CRC, estimate, scan word): one prototype.  Returns d_words."""
+    _require_cuda_u8(d_in, "d_in")
+    n, npk = _span(d_in, n_bytes)
+    d_words = _words(d_words, name, npk, d_in.device, whole)
+    _call(export, d_in.data_ptr(), n, d_words.data_ptr(), _stream_handle(stream))
+    return d_words
+
+
+def _words_batch(export, d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_words, name, stream, d_status, device, whole=False):
+    """The batch calls that give one 32-bit word per packet (CRC, estimate, scan word): one prototype.  Returns d_words."""
+    _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers)
+    d_words = _words(d_words, name, n_packets, device or d_ptrs.device, whole)
+    _call(export, d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, d_words.data_ptr(),
+          _status_ptr(d_status), _stream_handle(stream))
+    return d_words
+
+
+def _words_host(name, data):
+    """The host twins that give one 32-bit word per packet (estimate, scan word): a list of ints."""
+    data = bytes(data)
+    words = (C.c_uint32 * max(packet_count(len(data)), 1))()
+    _call(name, data, len(data), words)
+    return list(words)[:packet_count(len(data))]
 
 
 def _first_bad_ptr(d_first_bad):
@@ -375,17 +355,7 @@ def _first_bad_ptr(d_first_bad):
 def crc32(d_in, n_bytes: int = None, d_crc=None, stream=None):
     """The CRC-32 (zlib.crc32) of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in`
     (gpuar_hip_crc32).  Returns d_crc: int32 CUDA tensor of packet_count(n_bytes) values (the uint32 bits; & 0xFFFFFFFF)."""
-    import torch
-    _require_cuda_u8(d_in, "d_in")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    npk = packet_count(n)
-    if d_crc is None:
-        d_crc = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)
-    _require_crc(d_crc, "d_crc", npk)
-    _check(load().gpuar_hip_crc32(d_in.data_ptr(), n, d_crc.data_ptr(), _stream_handle(stream)), "gpuar_hip_crc32")
-    return d_crc
+    return _words_single("gpuar_hip_crc32", d_in, n_bytes, d_crc, "d_crc", stream, whole=True)
 
 
 def verify_crc32(d_out, d_crc, n_bytes: int = None, d_first_bad=None, d_status=None, stream=None):
@@ -393,50 +363,42 @@ def verify_crc32(d_out, d_crc, n_bytes: int = None, d_first_bad=None, d_status=N
     a mismatch ORs STATUS_CHECKSUM into d_status (None: the fallback word) and takes the minimum of the packet index and
     d_first_bad (a 1-element int64 CUDA tensor the caller set to -1, i.e. UINT64_MAX), when given."""
     _require_cuda_u8(d_out, "d_out")
-    n = d_out.numel() if n_bytes is None else n_bytes
-    if n > d_out.numel():
-        raise GpuarError("n_bytes is larger than d_out")
-    _require_crc(d_crc, "d_crc", packet_count(n))
-    _check(load().gpuar_hip_verify_crc32(d_out.data_ptr(), n, d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status),
-                                         _stream_handle(stream)), "gpuar_hip_verify_crc32")
+    n, npk = _span(d_out, n_bytes, "d_out")
+    _require_crc(d_crc, "d_crc", npk)
+    _call("gpuar_hip_verify_crc32", d_out.data_ptr(), n, d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status),
+          _stream_handle(stream))
 
 
 def crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_crc=None, stream=None, d_status=None, device=None):
     """The CRC-32 of every packet of a batch (gpuar_hip_crc32_batch; descriptors as for encode_batch): d_crc[p] for batch packet p."""
-    import torch
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
-    if d_crc is None:
-        d_crc = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)
-    _require_crc(d_crc, "d_crc", n_packets)
-    _check(load().gpuar_hip_crc32_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                        d_crc.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_crc32_batch")
-    return d_crc
+    return _words_batch("gpuar_hip_crc32_batch", d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_crc, "d_crc", stream, d_status, device,
+                        whole=True)
 
 
 def verify_crc32_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_crc, d_first_bad=None, stream=None, d_status=None):
     """Verify a batch's decoded buffers against d_crc (gpuar_hip_verify_crc32_batch): d_bytes holds each buffer's ORIGINAL size;
     d_first_bad receives the lowest failing batch packet."""
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
+    _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers)
     _require_crc(d_crc, "d_crc", n_packets)
-    _check(load().gpuar_hip_verify_crc32_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                               d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status), _stream_handle(stream)),
-           "gpuar_hip_verify_crc32_batch")
+    _call("gpuar_hip_verify_crc32_batch", d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
+          d_crc.data_ptr(), _first_bad_ptr(d_first_bad), _status_ptr(d_status), _stream_handle(stream))
 
 
-def _planes(name, d_in, elem_bytes, d_out, n_bytes, stream):
+def _planes(name, d_in, elem_bytes, d_out, n_bytes, stream, *d_base):
+    """One filter call on one buffer: planes and delta, and (with the one d_base) XOR.  Returns d_out."""
     import torch
     _require_cuda_u8(d_in, "d_in")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
+    for base in d_base:
+        _require_cuda_u8(base, "d_base")
+    n, _npk = _span(d_in, n_bytes)
+    if any(n > base.numel() for base in d_base):
+        raise GpuarError("d_base too small")
     if d_out is None:
         d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=d_in.device)[:n]
     _require_cuda_u8(d_out, "d_out")
     if d_out.numel() < n:
         raise GpuarError("d_out too small")
-    _check(getattr(load(), name)(d_in.data_ptr(), n, elem_bytes, d_out.data_ptr(), _stream_handle(stream)), name)
+    _call(name, d_in.data_ptr(), *(base.data_ptr() for base in d_base), n, elem_bytes, d_out.data_ptr(), _stream_handle(stream))
     return d_out
 
 
@@ -452,29 +414,28 @@ def merge_planes(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=
     return _planes("gpuar_hip_merge_planes", d_in, elem_bytes, d_out, n_bytes, stream)
 
 
-def _planes_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status):
-    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
-                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
-        _require_u64_desc(t, what, n)
-    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(), n_buffers,
-                                 n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), name)
+def _filter_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status, *extra):
+    """One filter call on a batch; `extra`: the (tensor, name) that delta (d_filter) and XOR (d_base_ptrs) add behind d_elem_bytes."""
+    _require_batch(d_in_ptrs, d_bytes, d_first_packet, n_buffers, "d_in_ptrs", ((d_elem_bytes, "d_elem_bytes"), *extra, (d_out_ptrs, "d_out_ptrs")))
+    _call(name, d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(), *(t.data_ptr() for t, _what in extra),
+          n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
 
 
 def split_planes_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers: int, n_packets: int, d_out_ptrs, stream=None, d_status=None):
     """split_planes for every buffer of a batch in one call (gpuar_hip_split_planes_batch; descriptors as for encode_batch, plus
     one element width per buffer): buffer b goes from d_in_ptrs[b] to d_out_ptrs[b], which may be the same."""
-    _planes_batch("gpuar_hip_split_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
+    _filter_batch("gpuar_hip_split_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
 
 
 def merge_planes_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers: int, n_packets: int, d_out_ptrs, stream=None, d_status=None):
     """The inverse of split_planes_batch (gpuar_hip_merge_planes_batch)."""
-    _planes_batch("gpuar_hip_merge_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
+    _filter_batch("gpuar_hip_merge_planes_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status)
 
 
 def _planes_host(name, data, elem_bytes):
     data = bytes(data)
     out = C.create_string_buffer(len(data))
-    _check(getattr(load(), name)(data, len(data), elem_bytes, out), name)
+    _call(name, data, len(data), elem_bytes, out)
     return out.raw
 
 
@@ -502,28 +463,19 @@ def merge_delta(d_in, elem_bytes: int, d_out=None, n_bytes: int = None, stream=N
     return _planes("gpuar_hip_merge_delta", d_in, elem_bytes, d_out, n_bytes, stream)
 
 
-def _delta_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs, stream, d_status):
-    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
-                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_filter, "d_filter", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
-        _require_u64_desc(t, what, n)
-    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(),
-                                 d_filter.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status),
-                                 _stream_handle(stream)), name)
-
-
 def split_delta_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
                       d_status=None):
     """split_planes_batch with a filter per buffer (gpuar_hip_split_delta_batch): d_filter[b] = 0 regroups buffer b as
     split_planes_batch does, 1 as split_delta; any other value is BAD_BATCH and the buffer is left alone."""
-    _delta_batch("gpuar_hip_split_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs,
-                 stream, d_status)
+    _filter_batch("gpuar_hip_split_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status,
+                  (d_filter, "d_filter"))
 
 
 def merge_delta_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
                       d_status=None):
     """The inverse of split_delta_batch (gpuar_hip_merge_delta_batch)."""
-    _delta_batch("gpuar_hip_merge_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_filter, n_buffers, n_packets, d_out_ptrs,
-                 stream, d_status)
+    _filter_batch("gpuar_hip_merge_delta_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status,
+                  (d_filter, "d_filter"))
 
 
 def split_delta_host(data, elem_bytes: int) -> bytes:
@@ -545,48 +497,20 @@ def delta_block_host(mixed, elem_bytes: int, undo: bool, carried: int):
         raise GpuarError(f"delta_block_host: {len(mixed)} dwords for a width of {elem_bytes}")
     block = (C.c_uint32 * len(mixed))(*mixed)
     total = C.c_uint64(0)
-    _check(load().gpuar_hip_delta_block_host(block, elem_bytes, 1 if undo else 0, carried & (2 ** 64 - 1), C.byref(total)),
-           "gpuar_hip_delta_block_host")
+    _call("gpuar_hip_delta_block_host", block, elem_bytes, 1 if undo else 0, carried & (2 ** 64 - 1), C.byref(total))
     return list(block), total.value
-
-
-def _xor(name, d_in, d_base, elem_bytes, d_out, n_bytes, stream):
-    import torch
-    _require_cuda_u8(d_in, "d_in")
-    _require_cuda_u8(d_base, "d_base")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    if n > d_base.numel():
-        raise GpuarError("d_base too small")
-    if d_out is None:
-        d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=d_in.device)[:n]
-    _require_cuda_u8(d_out, "d_out")
-    if d_out.numel() < n:
-        raise GpuarError("d_out too small")
-    _check(getattr(load(), name)(d_in.data_ptr(), d_base.data_ptr(), n, elem_bytes, d_out.data_ptr(), _stream_handle(stream)), name)
-    return d_out
 
 
 def split_xor(d_in, d_base, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
     """split_planes of d_in ^ d_base (gpuar_hip_split_xor; include/gpuar_hip.h), in one pass: every byte of the first `n_bytes`
     is XORed with the same byte of the base, then the bytes are regrouped as elements of `elem_bytes` bytes (1, 2, 4, 8);
     elem_bytes = 1 is a plain XOR.  `d_out` may be `d_in`, never the base.  Returns d_out."""
-    return _xor("gpuar_hip_split_xor", d_in, d_base, elem_bytes, d_out, n_bytes, stream)
+    return _planes("gpuar_hip_split_xor", d_in, elem_bytes, d_out, n_bytes, stream, d_base)
 
 
 def merge_xor(d_in, d_base, elem_bytes: int, d_out=None, n_bytes: int = None, stream=None):
     """The inverse of split_xor with the same base (gpuar_hip_merge_xor): merge_planes, then the XOR; `d_out` may be `d_in`."""
-    return _xor("gpuar_hip_merge_xor", d_in, d_base, elem_bytes, d_out, n_bytes, stream)
-
-
-def _xor_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, stream, d_status):
-    for t, what, n in ((d_in_ptrs, "d_in_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1),
-                       (d_elem_bytes, "d_elem_bytes", n_buffers), (d_base_ptrs, "d_base_ptrs", n_buffers), (d_out_ptrs, "d_out_ptrs", n_buffers)):
-        _require_u64_desc(t, what, n)
-    _check(getattr(load(), name)(d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_elem_bytes.data_ptr(),
-                                 d_base_ptrs.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status),
-                                 _stream_handle(stream)), name)
+    return _planes("gpuar_hip_merge_xor", d_in, elem_bytes, d_out, n_bytes, stream, d_base)
 
 
 def split_xor_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
@@ -594,15 +518,15 @@ def split_xor_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptr
     """split_planes_batch with a base per buffer (gpuar_hip_split_xor_batch): d_base_ptrs[b] = 0 regroups buffer b as
     split_planes_batch does, a 16-byte aligned pointer as split_xor against the d_bytes[b] bytes there; a misaligned one is
     BAD_BATCH and the buffer is left alone."""
-    _xor_batch("gpuar_hip_split_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
-               stream, d_status)
+    _filter_batch("gpuar_hip_split_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status,
+                  (d_base_ptrs, "d_base_ptrs"))
 
 
 def merge_xor_batch(d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs, stream=None,
                     d_status=None):
     """The inverse of split_xor_batch (gpuar_hip_merge_xor_batch)."""
-    _xor_batch("gpuar_hip_merge_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
-               stream, d_status)
+    _filter_batch("gpuar_hip_merge_xor_batch", d_in_ptrs, d_bytes, d_first_packet, d_elem_bytes, n_buffers, n_packets, d_out_ptrs, stream, d_status,
+                  (d_base_ptrs, "d_base_ptrs"))
 
 
 def _xor_host(name, data, base, elem_bytes):
@@ -610,7 +534,7 @@ def _xor_host(name, data, base, elem_bytes):
     if len(base) != len(data):
         raise GpuarError(f"{name}: a base of {len(base)} bytes for {len(data)} bytes")
     out = C.create_string_buffer(len(data))
-    _check(getattr(load(), name)(data, base, len(data), elem_bytes, out), name)
+    _call(name, data, base, len(data), elem_bytes, out)
     return out.raw
 
 
@@ -628,47 +552,55 @@ def estimate(d_in, n_bytes: int = None, d_est=None, stream=None):
     """The predicted clen (header included) of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in`, from
     the packet's byte histogram alone (gpuar_hip_estimate; the definition is in include/gpuar_hip.h).  Returns d_est: int32 CUDA
     tensor of packet_count(n_bytes) values.  A packet is worth storing raw iff est[p] >= 4 + ulen[p] (stored_rule)."""
-    import torch
-    _require_cuda_u8(d_in, "d_in")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    npk = packet_count(n)
-    if d_est is None:
-        d_est = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)[:npk]
-    _require_crc(d_est, "d_est", npk)
-    _check(load().gpuar_hip_estimate(d_in.data_ptr(), n, d_est.data_ptr(), _stream_handle(stream)), "gpuar_hip_estimate")
-    return d_est
+    return _words_single("gpuar_hip_estimate", d_in, n_bytes, d_est, "d_est", stream)
 
 
 def estimate_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None):
     """The estimate of every packet of a batch (gpuar_hip_estimate_batch; descriptors as for encode_batch): d_est[p] for batch
     packet p."""
-    import torch
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
-    if d_est is None:
-        d_est = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)[:n_packets]
-    _require_crc(d_est, "d_est", n_packets)
-    _check(load().gpuar_hip_estimate_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                           d_est.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_estimate_batch")
-    return d_est
+    return _words_batch("gpuar_hip_estimate_batch", d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_est, "d_est", stream, d_status, device)
 
 
 def estimate_host(data) -> list:
     """estimate of a bytes-like object on the CPU (gpuar_hip_estimate_host: no device is touched): one int per packet."""
-    data = bytes(data)
-    est = (C.c_uint32 * max(packet_count(len(data)), 1))()
-    _check(load().gpuar_hip_estimate_host(data, len(data), est), "gpuar_hip_estimate_host")
-    return list(est)[:packet_count(len(data))]
+    return _words_host("gpuar_hip_estimate_host", data)
 
 
-def _require_survey(d_est, npk):
-    """A survey's output: a contiguous 4-byte CUDA tensor of shape (4, stride), stride >= npk."""
+def _survey_rows(d_est, npk, device):
+    """A survey's output of shape (4, stride), stride >= npk: the caller's contiguous 4-byte CUDA tensor, or a new int32 one of (4, npk)."""
     import torch
+    if d_est is None:
+        d_est = torch.empty((len(SURVEY_WIDTHS), npk), dtype=torch.int32, device=device)
     if not (isinstance(d_est, torch.Tensor) and d_est.is_cuda and d_est.element_size() == 4 and d_est.is_contiguous() and d_est.dim() == 2
             and d_est.shape[0] == len(SURVEY_WIDTHS) and d_est.shape[1] >= npk):
         raise GpuarError(f"d_est must be a contiguous 32-bit CUDA tensor of shape (4, at least {npk})")
+    return d_est
+
+
+def _survey(name, d_in, d_est, n_bytes, stream, *mask):
+    """Either survey of one buffer; `mask`: the delta survey's widths_mask.  Returns d_est."""
+    n, npk = _span(d_in, n_bytes)
+    d_est = _survey_rows(d_est, npk, d_in.device)
+    _call(name, d_in.data_ptr(), n, *mask, d_est.data_ptr(), d_est.shape[1], _stream_handle(stream))
+    return d_est
+
+
+def _survey_batch(name, d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_est, stream, d_status, device, *mask):
+    """Either survey of a batch.  Returns d_est."""
+    _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers)
+    d_est = _survey_rows(d_est, n_packets, device or d_ptrs.device)
+    _call(name, d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, *mask, d_est.data_ptr(), d_est.shape[1],
+          _status_ptr(d_status), _stream_handle(stream))
+    return d_est
+
+
+def _survey_host(name, data, *mask):
+    """Either survey on the CPU: four lists, one per width of SURVEY_WIDTHS, of one int per packet."""
+    data = bytes(data)
+    npk = packet_count(len(data))
+    est = (C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))()
+    _call(name, data, len(data), *mask, est, npk)
+    return [list(est[j * npk:(j + 1) * npk]) for j in range(len(SURVEY_WIDTHS))]
 
 
 def survey_planes(d_in, d_est=None, n_bytes: int = None, stream=None):
@@ -676,42 +608,20 @@ def survey_planes(d_in, d_est=None, n_bytes: int = None, stream=None):
     and 8, from one read of the bytes and without splitting anything (gpuar_hip_survey_planes): row j of the result is what
     estimate(split_planes(d_in, SURVEY_WIDTHS[j])) gives.  Returns d_est: int32 CUDA tensor of shape (4, packet_count(n_bytes))
     (the caller's may be wider: its second dimension is the row stride)."""
-    import torch
     _require_cuda_u8(d_in, "d_in")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    npk = packet_count(n)
-    if d_est is None:
-        d_est = torch.empty((len(SURVEY_WIDTHS), npk), dtype=torch.int32, device=d_in.device)
-    _require_survey(d_est, npk)
-    _check(load().gpuar_hip_survey_planes(d_in.data_ptr(), n, d_est.data_ptr(), d_est.shape[1], _stream_handle(stream)), "gpuar_hip_survey_planes")
-    return d_est
+    return _survey("gpuar_hip_survey_planes", d_in, d_est, n_bytes, stream)
 
 
 def survey_planes_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None):
     """The survey of every buffer of a batch in one launch (gpuar_hip_survey_planes_batch; descriptors as for encode_batch):
     d_est[j, p] for width SURVEY_WIDTHS[j] and batch packet p."""
-    import torch
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
-    if d_est is None:
-        d_est = torch.empty((len(SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device or d_ptrs.device)
-    _require_survey(d_est, n_packets)
-    _check(load().gpuar_hip_survey_planes_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                                d_est.data_ptr(), d_est.shape[1], _status_ptr(d_status), _stream_handle(stream)),
-           "gpuar_hip_survey_planes_batch")
-    return d_est
+    return _survey_batch("gpuar_hip_survey_planes_batch", d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_est, stream, d_status, device)
 
 
 def survey_planes_host(data) -> list:
     """survey_planes of a bytes-like object on the CPU (gpuar_hip_survey_planes_host: no device is touched): four lists, one per
     width of SURVEY_WIDTHS, of one int per packet."""
-    data = bytes(data)
-    npk = packet_count(len(data))
-    est = (C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))()
-    _check(load().gpuar_hip_survey_planes_host(data, len(data), est, npk), "gpuar_hip_survey_planes_host")
-    return [list(est[j * npk:(j + 1) * npk]) for j in range(len(SURVEY_WIDTHS))]
+    return _survey_host("gpuar_hip_survey_planes_host", data)
 
 
 def choose_planes(totals, n_packets: int) -> int:
@@ -740,35 +650,16 @@ def survey_delta(d_in, d_est=None, n_bytes: int = None, stream=None, widths=SURV
     (gpuar_hip_survey_delta): row j of the result is what estimate(split_delta(d_in, SURVEY_WIDTHS[j])) gives.  Returns d_est:
     int32 CUDA tensor of shape (4, packet_count(n_bytes)) (the caller's may be wider: its second dimension is the row stride);
     the rows of widths that were not asked for are left as they were."""
-    import torch
     _require_cuda_u8(d_in, "d_in")
-    mask = widths_mask(widths)
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    npk = packet_count(n)
-    if d_est is None:
-        d_est = torch.empty((len(SURVEY_WIDTHS), npk), dtype=torch.int32, device=d_in.device)
-    _require_survey(d_est, npk)
-    _check(load().gpuar_hip_survey_delta(d_in.data_ptr(), n, mask, d_est.data_ptr(), d_est.shape[1], _stream_handle(stream)), "gpuar_hip_survey_delta")
-    return d_est
+    return _survey("gpuar_hip_survey_delta", d_in, d_est, n_bytes, stream, widths_mask(widths))
 
 
 def survey_delta_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_est=None, stream=None, d_status=None, device=None,
                        widths=SURVEY_WIDTHS):
     """The delta survey of every buffer of a batch in one launch (gpuar_hip_survey_delta_batch; descriptors as for encode_batch):
     d_est[j, p] for every width SURVEY_WIDTHS[j] of `widths` and batch packet p; the other rows are left as they were."""
-    import torch
-    mask = widths_mask(widths)
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
-    if d_est is None:
-        d_est = torch.empty((len(SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device or d_ptrs.device)
-    _require_survey(d_est, n_packets)
-    _check(load().gpuar_hip_survey_delta_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets, mask,
-                                               d_est.data_ptr(), d_est.shape[1], _status_ptr(d_status), _stream_handle(stream)),
-           "gpuar_hip_survey_delta_batch")
-    return d_est
+    return _survey_batch("gpuar_hip_survey_delta_batch", d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_est, stream, d_status, device,
+                         widths_mask(widths))
 
 
 def survey_delta_host(data, widths=SURVEY_WIDTHS) -> list:
@@ -776,10 +667,8 @@ def survey_delta_host(data, widths=SURVEY_WIDTHS) -> list:
     width of SURVEY_WIDTHS -- a list of one int per packet, or None for a width that was not asked for."""
     data = bytes(data)
     mask = widths_mask(widths)
-    npk = packet_count(len(data))
-    est = (C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))()
-    _check(load().gpuar_hip_survey_delta_host(data, len(data), mask, est, npk), "gpuar_hip_survey_delta_host")
-    return [list(est[j * npk:(j + 1) * npk]) if mask >> j & 1 else None for j in range(len(SURVEY_WIDTHS))]
+    rows = _survey_host("gpuar_hip_survey_delta_host", data, mask)
+    return [row if mask >> j & 1 else None for j, row in enumerate(rows)]
 
 
 def choose_filter(plain, filtered, n_packets: int) -> tuple:
@@ -804,8 +693,8 @@ def move_packets(d_src_ptrs, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d
     (gpuar_hip_move_packets; the three descriptors are 64-bit CUDA tensors)."""
     for t, name in ((d_src_ptrs, "d_src_ptrs"), (d_dst_ptrs, "d_dst_ptrs"), (d_bytes, "d_bytes")):
         _require_u64_desc(t, name, n_regions)
-    _check(load().gpuar_hip_move_packets(d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
-                                         _stream_handle(stream)), "gpuar_hip_move_packets")
+    _call("gpuar_hip_move_packets", d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
+          _stream_handle(stream))
 
 
 SPARSE_NONE = 0xFFFFFFFF             # GPUAR_SPARSE_NONE: a packet without a majority byte
@@ -827,38 +716,18 @@ def sparse_scan(d_in, n_bytes: int = None, d_scan=None, stream=None):
     """The scan word of every 8192-byte packet of the first `n_bytes` (default: all) bytes of `d_in` (gpuar_hip_sparse_scan):
     (k << 8) | f for a packet whose majority byte f leaves k exceptions, SPARSE_NONE (-1 as int32) for one without.  Returns
     d_scan: int32 CUDA tensor of packet_count(n_bytes) values."""
-    import torch
-    _require_cuda_u8(d_in, "d_in")
-    n = d_in.numel() if n_bytes is None else n_bytes
-    if n > d_in.numel():
-        raise GpuarError("n_bytes is larger than d_in")
-    npk = packet_count(n)
-    if d_scan is None:
-        d_scan = torch.empty(max(npk, 1), dtype=torch.int32, device=d_in.device)[:npk]
-    _require_crc(d_scan, "d_scan", npk)
-    _check(load().gpuar_hip_sparse_scan(d_in.data_ptr(), n, d_scan.data_ptr(), _stream_handle(stream)), "gpuar_hip_sparse_scan")
-    return d_scan
+    return _words_single("gpuar_hip_sparse_scan", d_in, n_bytes, d_scan, "d_scan", stream)
 
 
 def sparse_scan_batch(d_ptrs, d_bytes, d_first_packet, n_buffers: int, n_packets: int, d_scan=None, stream=None, d_status=None, device=None):
     """The scan word of every packet of a batch (gpuar_hip_sparse_scan_batch; descriptors as for encode_batch)."""
-    import torch
-    for t, name, n in ((d_ptrs, "d_ptrs", n_buffers), (d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1)):
-        _require_u64_desc(t, name, n)
-    if d_scan is None:
-        d_scan = torch.empty(max(n_packets, 1), dtype=torch.int32, device=device or d_ptrs.device)[:n_packets]
-    _require_crc(d_scan, "d_scan", n_packets)
-    _check(load().gpuar_hip_sparse_scan_batch(d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), n_buffers, n_packets,
-                                              d_scan.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_scan_batch")
-    return d_scan
+    return _words_batch("gpuar_hip_sparse_scan_batch", d_ptrs, d_bytes, d_first_packet, n_buffers, n_packets, d_scan, "d_scan", stream, d_status,
+                        device)
 
 
 def sparse_scan_host(data) -> list:
     """sparse_scan of a bytes-like object on the CPU (gpuar_hip_sparse_scan_host: no device is touched): one int per packet."""
-    data = bytes(data)
-    scan = (C.c_uint32 * max(packet_count(len(data)), 1))()
-    _check(load().gpuar_hip_sparse_scan_host(data, len(data), scan), "gpuar_hip_sparse_scan_host")
-    return list(scan)[:packet_count(len(data))]
+    return _words_host("gpuar_hip_sparse_scan_host", data)
 
 
 def sparse_pack_host(data) -> bytes:
@@ -867,7 +736,7 @@ def sparse_pack_host(data) -> bytes:
     data = bytes(data)
     rec = (C.c_uint8 * (4 + 3 * (PACKET // 2) + 4))()
     length = C.c_size_t(0)
-    _check(load().gpuar_hip_sparse_pack_host(data, len(data), rec, len(rec), C.byref(length)), "gpuar_hip_sparse_pack_host")
+    _call("gpuar_hip_sparse_pack_host", data, len(data), rec, len(rec), C.byref(length))
     return bytes(rec[:length.value])
 
 
@@ -876,7 +745,7 @@ def sparse_unpack_host(rec, n_bytes: int) -> bytes:
     not valid."""
     rec = bytes(rec)
     out = (C.c_uint8 * max(n_bytes, 1))()
-    _check(load().gpuar_hip_sparse_unpack_host(rec, len(rec), out, n_bytes), "gpuar_hip_sparse_unpack_host")
+    _call("gpuar_hip_sparse_unpack_host", rec, len(rec), out, n_bytes)
     return bytes(out[:n_bytes])
 
 
@@ -887,8 +756,8 @@ def sparse_pack(d_src_ptrs, d_bytes, d_scan, d_dst_ptrs, n_regions: int, stream=
     for t, name in ((d_src_ptrs, "d_src_ptrs"), (d_bytes, "d_bytes"), (d_dst_ptrs, "d_dst_ptrs")):
         _require_u64_desc(t, name, n_regions)
     _require_crc(d_scan, "d_scan", n_regions)
-    _check(load().gpuar_hip_sparse_pack(d_src_ptrs.data_ptr(), d_bytes.data_ptr(), d_scan.data_ptr(), d_dst_ptrs.data_ptr(), n_regions,
-                                        _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_pack")
+    _call("gpuar_hip_sparse_pack", d_src_ptrs.data_ptr(), d_bytes.data_ptr(), d_scan.data_ptr(), d_dst_ptrs.data_ptr(), n_regions,
+          _status_ptr(d_status), _stream_handle(stream))
 
 
 def sparse_unpack(d_rec_ptrs, d_rec_bytes, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d_status=None):
@@ -897,8 +766,8 @@ def sparse_unpack(d_rec_ptrs, d_rec_bytes, d_dst_ptrs, d_bytes, n_regions: int, 
     is not valid is STATUS_BAD_PACKET in the status word."""
     for t, name in ((d_rec_ptrs, "d_rec_ptrs"), (d_rec_bytes, "d_rec_bytes"), (d_dst_ptrs, "d_dst_ptrs"), (d_bytes, "d_bytes")):
         _require_u64_desc(t, name, n_regions)
-    _check(load().gpuar_hip_sparse_unpack(d_rec_ptrs.data_ptr(), d_rec_bytes.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions,
-                                          _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_sparse_unpack")
+    _call("gpuar_hip_sparse_unpack", d_rec_ptrs.data_ptr(), d_rec_bytes.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions,
+          _status_ptr(d_status), _stream_handle(stream))
 
 
 def kinds_store_host(data, stored: bool, sparse: bool):
@@ -908,8 +777,7 @@ def kinds_store_host(data, stored: bool, sparse: bool):
     data = bytes(data)
     pkt = (C.c_uint8 * SLOT)()
     kind, clen = C.c_uint32(0), C.c_size_t(0)
-    _check(load().gpuar_hip_kinds_store_host(data, len(data), int(bool(stored)), int(bool(sparse)), pkt, len(pkt), C.byref(kind), C.byref(clen)),
-           "gpuar_hip_kinds_store_host")
+    _call("gpuar_hip_kinds_store_host", data, len(data), int(bool(stored)), int(bool(sparse)), pkt, len(pkt), C.byref(kind), C.byref(clen))
     return int(kind.value), bytes(pkt[:clen.value])
 
 
@@ -918,7 +786,7 @@ def kinds_expand_host(pkt, kind: int, n_bytes: int) -> bytes:
     (gpuar_hip_kinds_expand_host); raises for any other kind and for a packet that is not valid."""
     pkt = bytes(pkt)
     out = (C.c_uint8 * max(n_bytes, 1))()
-    _check(load().gpuar_hip_kinds_expand_host(pkt, len(pkt), kind, out, n_bytes), "gpuar_hip_kinds_expand_host")
+    _call("gpuar_hip_kinds_expand_host", pkt, len(pkt), kind, out, n_bytes)
     return bytes(out[:n_bytes])
 
 
@@ -942,8 +810,8 @@ def kinds_store(d_in, d_est, d_scan, stored: bool, d_slots, n_bytes: int = None,
     _require_cuda_u8(d_kind, "d_kind")
     if d_kind.numel() < n_packets:
         raise GpuarError("d_kind is too small")
-    _check(load().gpuar_hip_kinds_store(d_in.data_ptr(), n, d_est.data_ptr(), d_scan.data_ptr() if d_scan is not None else None, int(bool(stored)),
-                                        d_slots.data_ptr(), d_kind.data_ptr(), _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_kinds_store")
+    _call("gpuar_hip_kinds_store", d_in.data_ptr(), n, d_est.data_ptr(), d_scan.data_ptr() if d_scan is not None else None, int(bool(stored)),
+          d_slots.data_ptr(), d_kind.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
     return d_kind
 
 
@@ -957,8 +825,8 @@ def kinds_expand(d_stream, d_offsets, d_kind, n_packets: int, d_out, n_bytes: in
     _require_u64_desc(d_offsets, "d_offsets", n_packets + 1)
     if d_kind.numel() < n_packets or d_out.numel() < n_bytes:
         raise GpuarError("d_kind or d_out is too small")
-    _check(load().gpuar_hip_kinds_expand(d_stream.data_ptr(), d_offsets.data_ptr(), d_kind.data_ptr(), n_packets, d_out.data_ptr(), n_bytes,
-                                         _status_ptr(d_status), _stream_handle(stream)), "gpuar_hip_kinds_expand")
+    _call("gpuar_hip_kinds_expand", d_stream.data_ptr(), d_offsets.data_ptr(), d_kind.data_ptr(), n_packets, d_out.data_ptr(), n_bytes,
+          _status_ptr(d_status), _stream_handle(stream))
     return d_out
 
 
@@ -967,7 +835,7 @@ def status() -> int:
     reported (synchronises the device).  The read and the clear are one atomic exchange on the device: every bit a
     launch ORs into the word is reported by exactly one status() call, even while other threads launch into it."""
     flags = C.c_uint32(0)
-    _check(load().gpuar_hip_status(C.byref(flags)), "gpuar_hip_status")
+    _call("gpuar_hip_status", C.byref(flags))
     return int(flags.value)
 
 
@@ -979,8 +847,7 @@ def generate(kind: str, seed: int, n: int, offset: int = 0, device="cuda", out=N
     if kind == "zeros":
         out[:n].zero_()
         return out
-    _check(load().gpuar_hip_generate(KIND_ID[kind], seed & 0xFFFFFFFFFFFFFFFF, offset, n, out.data_ptr(),
-                                     _stream_handle(stream)), "gpuar_hip_generate")
+    _call("gpuar_hip_generate", KIND_ID[kind], seed & 0xFFFFFFFFFFFFFFFF, offset, n, out.data_ptr(), _stream_handle(stream))
     return out
 
 
@@ -991,7 +858,7 @@ def device_copy(d_src, d_dst, n_bytes: int = None, stream=None):
     n = d_src.numel() if n_bytes is None else n_bytes
     if d_dst.numel() < n or d_src.numel() < n:
         raise GpuarError("copy: buffer too small")
-    _check(load().gpuar_hip_copy(d_src.data_ptr(), d_dst.data_ptr(), n, _stream_handle(stream)), "gpuar_hip_copy")
+    _call("gpuar_hip_copy", d_src.data_ptr(), d_dst.data_ptr(), n, _stream_handle(stream))
     return d_dst
 
 
@@ -1012,7 +879,7 @@ def shader_clock_mhz(which: str, reset: bool = True):
     ("decode") ran, from the samples their workgroups left (gpuar_hip_clock_samples): (MHz, number of samples), or
     (None, 0) when no sampled workgroup has run to its end since the last reset.  Synchronises the device."""
     buf = (C.c_uint64 * (4 * CLOCK_SLOTS))()
-    _check(load().gpuar_hip_clock_samples({"encode": 0, "decode": 1}[which], buf, 1 if reset else 0), "gpuar_hip_clock_samples")
+    _call("gpuar_hip_clock_samples", {"encode": 0, "decode": 1}[which], buf, 1 if reset else 0)
     shader = real = n = 0
     for i in range(CLOCK_SLOTS):
         s0, r0, s1, r1 = buf[4 * i:4 * i + 4]
