@@ -21,8 +21,10 @@ back, in place in the output tensors, after they are decoded: typed data (bf16, 
 With stored="auto" the packets that cannot shrink are not coded at all: one histogram pass (hip.estimate_batch) predicts every
 packet's compressed size, the packets whose estimate is not smaller than their bytes are copied raw into Compressed.raw
 (hip.move_packets) and only the others go through the encoder -- and, in decompress, the decoder.
-estimate(tensors, ...) gives the predicted sizes without compressing anything.  The .gip container has no raw packets:
-Compressed.gip(b) raises for a buffer that holds one.
+estimate(tensors, ...) gives the predicted sizes without compressing anything.  In a .gip file a raw packet stands behind a 4-byte
+header and a version-6 trailer says which packets are raw: Compressed.gip(b, kinds=True) writes that file for a
+batch compressed with stored="auto"; without kinds=True a buffer that holds a raw packet raises, and so does a batch compressed
+with a list of stored packets, which has no file form.
 
 With planes="survey" the width of every tensor is chosen by measurement instead of by dtype: survey(tensors) predicts, in one
 launch over the original bytes (hip.survey_planes_batch), what each tensor would compress to at widths 1, 2, 4 and 8, and
@@ -54,7 +56,16 @@ With sparse="auto" a packet that is one byte value almost everywhere is neither 
 count, the exceptions' positions and values: 4 + 3 k bytes -- is smaller than their estimate go into Compressed.sparse
 (hip.sparse_pack) and come back through hip.sparse_unpack.  That is what a base makes of everything that did not
 change since it: compress(tensors, planes="auto", base=[...], sparse="auto") keeps an unchanged packet in 4 bytes where the
-codec cannot go below 210.  Like a raw packet, a sparse one has no .gip form.
+codec cannot go below 210.  Like a raw packet, a sparse one goes into a version-6 file: Compressed.gip(b, kinds=True).
+
+from_gip(files) is the way back: a list of .gip files -- what Compressed.gip or `gpuar c` wrote, any trailer version or none, as
+bytes, arrays or paths -- becomes one Compressed, one buffer per file, and decompress decodes them all in one launch.  The files
+are read and checked on the host by the CLI's own reader (read_gip: hip.gip_read_host, no GPU), their streams go to the device in
+one copy, and where a file is version 6 one hip.move_bytes launch takes the interleaved coded, raw and sparse packets apart into
+`stream`, `raw` and `sparse`.
+
+    blobs = [c.gip(b) for b in range(c.n_buffers)]
+    outs = batch.decompress(batch.from_gip(blobs))
 """
 from __future__ import annotations
 
@@ -175,6 +186,19 @@ class Compressed:
             self._off = self.offsets.cpu().tolist()
         return self._off
 
+    def _host_copy(self, name):
+        """The host copy of the device field `name`, made on first use and kept (as _offsets_host keeps the offsets): gip(b) for
+        every buffer of the batch then costs one copy of the batch, not one per file.  `stream`, `raw`, `sparse`: bytes; the
+        others: a list of ints; a field that is None: the empty one.  The fields are not written after compress."""
+        kept = self.__dict__.setdefault("_host_copies", {})
+        if name not in kept:
+            t = getattr(self, name)
+            if name in ("stream", "raw", "sparse"):
+                kept[name] = t.cpu().numpy().tobytes() if t is not None else b""
+            else:
+                kept[name] = t.cpu().tolist() if t is not None else [0]
+        return kept[name]
+
     @property
     def nbytes(self) -> int:
         """The compressed bytes: the coded packets' stream, the raw packets and the sparse packets' records."""
@@ -190,8 +214,8 @@ class Compressed:
             for flag in self.stored.cpu().tolist():
                 self._rank.append(self._rank[-1] + (0 if flag else 1))
         if self._rank[hi] - self._rank[lo] != hi - lo:
-            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw or sparse) packets: it has no packet stream "
-                             "and no .gip form (the container has no raw and no sparse packets)")
+            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw or sparse) packets: it has no packet stream of "
+                             "coded packets alone; its .gip form is the version-6 file, gip(b, kinds=True), where the kinds came from the rule")
         return self._rank[lo], self._rank[hi]
 
     def payload(self, b: int):
@@ -205,16 +229,14 @@ class Compressed:
         """(packet stream, clens, kinds) of buffer b with every packet in its stream form (gpuar_amd/csrc/kinds.h): the coded
         packets as they are, the raw and the sparse ones behind a 4-byte header put in front of them here, on the host."""
         lo, hi = self.first_packet[b], self.first_packet[b + 1]
-        kinds = self.stored.cpu().tolist()
+        kinds = self._host_copy("stored")
         rank = [0, 0, 0]                                   # how many packets of each kind stand in front of packet lo
         for k in kinds[:lo]:
             rank[k] += 1
         off = self._offsets_host()
-        raw = self.raw.cpu().numpy().tobytes() if self.raw is not None else b""
-        raw_off = self.raw_offsets.cpu().tolist() if self.raw_offsets is not None else [0]
-        rec = self.sparse.cpu().numpy().tobytes() if self.sparse is not None else b""
-        rec_off = self.sparse_offsets.cpu().tolist() if self.sparse_offsets is not None else [0]
-        coded = self.stream.cpu().numpy().tobytes()
+        raw, raw_off = self._host_copy("raw"), self._host_copy("raw_offsets")
+        rec, rec_off = self._host_copy("sparse"), self._host_copy("sparse_offsets")
+        coded = self._host_copy("stream")
         packets = []
         for i, k in enumerate(kinds[lo:hi]):
             ulen, r = min(H.PACKET, self.sizes[b] - i * H.PACKET), rank[k]
@@ -244,20 +266,20 @@ class Compressed:
                 raise GpuarError("gip(kinds=True) is the file of a batch compressed with stored=\"auto\" and / or sparse=\"auto\"")
             payload, clens, which = self._kinds_packets(b)
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
-            crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
+            crcs = [v & 0xFFFFFFFF for v in self._host_copy("crc32")[lo:hi]] if self.crc32 is not None else None
             return H.gip_header(self.sizes[b], len(payload)) + payload + trailer(
                 clens, self.planes[b] if self.planes is not None else 1, crcs, delta=bool(self.delta[b]) if self.delta is not None else False,
                 base=xored, kinds=which)
-        p = self.payload(b)
-        out = H.gip_header(self.sizes[b], p.numel()) + bytes(p.cpu().numpy().tobytes())
+        off = self._offsets_host()
+        lo, hi = self._coded_range(b)                      # (raises for a buffer that holds a stored packet, as payload(b) does)
+        p = self._host_copy("stream")[off[lo]:off[hi]]
+        out = H.gip_header(self.sizes[b], len(p)) + p
         w = self.planes[b] if self.planes is not None else 1
         filtered = bool(self.delta[b]) if self.delta is not None else False
         if self.crc32 is not None or w > 1 or filtered or xored:
-            off = self._offsets_host()
-            lo, hi = self._coded_range(b)
             clens = [off[i + 1] - off[i] for i in range(lo, hi)]
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
-            crcs = [v & 0xFFFFFFFF for v in self.crc32[lo:hi].cpu().tolist()] if self.crc32 is not None else None
+            crcs = [v & 0xFFFFFFFF for v in self._host_copy("crc32")[lo:hi]] if self.crc32 is not None else None
             out += trailer(clens, w, crcs, delta=filtered, base=xored)
         return out
 
@@ -286,6 +308,198 @@ def trailer(clens, elem_bytes=1, crcs=None, delta=False, base=False, kinds=None)
         body += bytes(-len(body) % 4) + bytes(kinds)
     body += bytes(-len(body) % 8)
     return body + struct.pack("<Q", len(body) + 12) + b"XPIG"
+
+
+@dataclass
+class GipFile:
+    """A .gip file in memory as the CLI's reader sees it (read_gip): `uncompressed` bytes in `n_packets` packets, whose stream is
+    bytes [stream_begin, stream_end) of the file (`stream`: a numpy view of them, no copy); the usable trailer's `version` (0: none),
+    `elem_bytes` (1 where nothing says) and `flags` (bit 0 CRCs, bit 1 delta, bit 2 base, bit 3 kinds); per packet `clens`
+    (uint16; from the trailer, else from walking the headers), `crcs` (uint32; None without them) and `kinds` (uint8; None unless
+    version 6).  Every packet's header has been checked against these (include/gpuar_hip.h)."""
+    uncompressed: int
+    stream_begin: int
+    stream_end: int
+    version: int
+    elem_bytes: int
+    flags: int
+    clens: object
+    crcs: object
+    kinds: object
+    stream: object
+
+    @property
+    def n_packets(self) -> int:
+        return len(self.clens)
+
+    @property
+    def delta(self) -> bool:
+        return self.version in (4, 6) and bool(self.flags & 2)
+
+    @property
+    def based(self) -> bool:
+        return self.version in (5, 6) and bool(self.flags & 4)
+
+
+def read_gip(blob, what="the file") -> GipFile:
+    """A whole .gip file -- bytes, bytearray, memoryview, a numpy or CPU torch uint8 array -- read on the host by the CLI's own
+    reader (hip.gip_read_host: FileHeader::getInfo, Trailer::load and a check of every packet header; no GPU).  Any version
+    `gpuar c` or Compressed.gip writes, and files without a trailer, reference-written ones included.  Raises GpuarError naming
+    `what`, the defect and where it is: a short or foreign header, a compressed size beyond the file, a trailer of version 3 .. 6
+    that cannot be used, a packet count, clen, ulen or kind that does not fit, a raw or sparse packet whose header does not fit
+    its form.  The exceptions inside a sparse record and the bits of a coded packet are decompress's to judge."""
+    arr = H._host_bytes(blob)
+    info, clens, crcs, kinds = H.gip_read_host(arr, what)
+    return GipFile(uncompressed=info[0], stream_begin=info[1], stream_end=info[2], version=info[3], elem_bytes=info[5], flags=info[6],
+                   clens=clens, crcs=crcs, kinds=kinds, stream=arr[info[1]:info[2]])
+
+
+def _gip_entry(entry, i):
+    """files[i] of from_gip as (bytes-like or array, its name in messages); a path is read whole."""
+    import os
+    import numpy as np
+    import torch
+    if isinstance(entry, (str, os.PathLike)):
+        try:
+            return np.fromfile(entry, dtype=np.uint8), f"files[{i}] ({os.fspath(entry)})"
+        except OSError as e:
+            raise GpuarError(f"files[{i}] ({os.fspath(entry)}): {e}") from None
+    if isinstance(entry, (bytes, bytearray, memoryview)) or (isinstance(entry, np.ndarray) and entry.dtype == np.uint8) or \
+            (isinstance(entry, torch.Tensor) and not entry.is_cuda and entry.dtype == torch.uint8):
+        return entry, f"files[{i}]"
+    raise GpuarError(f"files[{i}] is a {type(entry).__name__}: a .gip file is bytes, a bytearray, a memoryview, a numpy or CPU torch uint8 "
+                     "array, or a path")
+
+
+def _upload_rows(device, *rows):
+    """_upload for numpy rows: the int64 arrays as ONE pinned tensor and one copy, returned split back into device rows."""
+    import numpy as np
+    import torch
+    flat = np.concatenate([np.asarray(r, dtype=np.int64) for r in rows] + [np.zeros(1, dtype=np.int64)])
+    host = torch.from_numpy(flat).pin_memory()
+    dev = host.to(device, non_blocking=True)
+    out, at = [], 0
+    for r in rows:
+        out.append(dev[at:at + len(r)])
+        at += len(r)
+    return out, host
+
+
+def _gip_parse(files):
+    """from_gip's host step: every file of the list read and checked (read_gip), and the list checked as a whole; no GPU."""
+    if not isinstance(files, (list, tuple)):
+        raise GpuarError("files: a list of .gip files (bytes-like objects, uint8 arrays or paths)")
+    parsed = []
+    for i, entry in enumerate(files):
+        blob, what = _gip_entry(entry, i)
+        parsed.append(read_gip(blob, what))
+    with_crcs = [g.crcs is not None for g in parsed]
+    if any(with_crcs):
+        for i, g in enumerate(parsed):
+            if g.crcs is None and g.n_packets:
+                raise GpuarError(f"files[{i}] carries no CRCs, files[{with_crcs.index(True)}] does: a batch has them for every packet or "
+                                 "for none (Compressed.crc32)")
+    return parsed
+
+
+def _gip_upload(parsed, total, device):
+    """from_gip's upload: the files' packet streams (`total` bytes) back to back in one pinned tensor and on the device after one
+    copy, on the current stream: (the device tensor, the pinned one for the caller to hold)."""
+    import torch
+    staging = torch.empty(max(total, 1), dtype=torch.uint8).pin_memory()
+    at, host = 0, staging.numpy()
+    for g in parsed:
+        host[at:at + g.stream.size] = g.stream
+        at += g.stream.size
+    return staging.to(device, non_blocking=True)[:total], staging
+
+
+def from_gip(files, device=None, stream=None) -> Compressed:
+    """The .gip files of `files` (a list; each bytes / bytearray / memoryview / a numpy or CPU torch uint8 array, or a path) as one
+    Compressed, one buffer per file in list order: what Compressed.gip and `gpuar c` write, read back -- decompress(from_gip(...),
+    base=[...]) then decodes a directory of files in one launch.  Every file is read and checked on the host first (read_gip);
+    nothing is launched for a list with a bad file, for one where some files carry CRCs and others (with packets) do not
+    (Compressed.crc32 is all or nothing), or for an entry of another type: GpuarError naming the file.
+
+    The files' packet streams go back to back into one pinned buffer and to the device in one copy.  Where no file is version 6
+    that copy IS `stream`.  Otherwise the packets -- coded, raw and sparse, interleaved at byte alignment -- are taken apart by
+    ONE hip.move_bytes launch over region lists built on the device: a coded packet whole to its place in `stream`, a raw one's
+    ulen bytes behind its header to its 16-byte-aligned slot of `raw`, a sparse one's record to its place in `sparse`; the status
+    word is checked afterwards.
+
+    The fields are those compress returns for the options the files record: `planes` is None where every file says width 1, no
+    filter and no base (else a list), `delta` None where no file is filtered, `based` None where none has a base, `crc32` None
+    where none has CRCs.  With a version-6 file in the list `stored`, `raw`, `raw_offsets`, `sparse` and `sparse_offsets` are all
+    there (kind 0 for the packets of the other files; empty where no packet is of the kind) and `kinds_rule` is (a raw packet is
+    there, a sparse one is) -- a file does not say which options wrote it; else they are None."""
+    import torch
+    parsed = _gip_parse(files)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.stream(stream) if stream is not None else _nothing():
+        d_up, _staging = _gip_upload(parsed, sum(g.stream.size for g in parsed), device)
+        return _gip_assemble(parsed, d_up, device, stream)
+
+
+def _gip_assemble(parsed, d_up, device, stream):
+    """from_gip's device step, on the current stream (`stream`, where one was given): the Compressed of the files `parsed` whose
+    packet streams stand back to back in `d_up` -- the per-packet tables in one small copy, then the offsets; with a version-6 file
+    the region lists and the one hip.move_bytes launch, and the status word checked."""
+    import numpy as np
+    import torch
+    with_crcs = [g.crcs is not None for g in parsed]
+    sizes = [g.uncompressed for g in parsed]
+    first_packet, n_packets = H.batch_packet_count(sizes)
+    mixed = any(g.version == 6 for g in parsed)
+    u16, u8 = np.zeros(0, dtype=np.uint16), np.zeros(0, dtype=np.uint8)
+    clens = np.concatenate([g.clens for g in parsed] + [u16]).astype(np.int64)
+    widths = [g.elem_bytes for g in parsed]
+    flags, bases = [g.delta for g in parsed], [g.based for g in parsed]
+    d_stored = d_raw = d_raw_offsets = d_sparse = d_sparse_offsets = None
+    rows = [clens]
+    if any(with_crcs):
+        rows.append(np.concatenate([g.crcs for g in parsed if g.crcs is not None]).view(np.int32))
+    if mixed:
+        kinds = np.concatenate([g.kinds if g.kinds is not None else np.zeros(g.n_packets, dtype=np.uint8) for g in parsed] + [u8]).astype(np.int64)
+        ulens = np.concatenate([np.minimum(H.PACKET, size - H.PACKET * np.arange(g.n_packets, dtype=np.int64)) for g, size in zip(parsed, sizes)]
+                               + [np.zeros(0, dtype=np.int64)])
+        rows += [kinds, ulens]
+    d_rows, _keep = _upload_rows(device, *rows)
+    d_clen = d_rows[0]
+    d_crc = d_rows[1].to(torch.int32) if any(with_crcs) else None
+    zero = torch.zeros(1, dtype=torch.int64, device=device)
+    if not mixed:
+        d_stream, d_offsets = d_up, torch.cat([zero, torch.cumsum(d_clen, 0)])
+    else:
+        d_kind, d_ulen = d_rows[-2], d_rows[-1]
+        is_coded, is_raw = kinds == H.KIND_CODED, kinds == H.KIND_RAW
+        n_coded, n_stored = int(is_coded.sum()), int(is_raw.sum())
+        len16 = (ulens + 15) // 16 * 16
+        d_stream = torch.empty(int(clens[is_coded].sum()), dtype=torch.uint8, device=device)
+        d_raw = torch.zeros(int(len16[is_raw].sum()), dtype=torch.uint8, device=device)          # (zeros: the pads behind partial packets)
+        d_sparse = torch.empty(int((clens - 4)[~is_coded & ~is_raw].sum()), dtype=torch.uint8, device=device)
+        # the three region lists, on the device: per packet where it stands in the upload, what of it moves, and to where
+        coded, raw = d_kind == H.KIND_CODED, d_kind == H.KIND_RAW
+        d_len16, d_rec = (d_ulen + 15) // 16 * 16, d_clen - 4
+        part = [torch.where(coded, d_clen, 0), torch.where(raw, d_len16, 0), torch.where(coded | raw, 0, d_rec)]
+        place = [torch.cumsum(p, 0) - p for p in part]
+        d_src = d_up.data_ptr() + (torch.cumsum(d_clen, 0) - d_clen) + torch.where(coded, 0, 4)
+        d_dst = torch.where(coded, d_stream.data_ptr() + place[0], torch.where(raw, d_raw.data_ptr() + place[1], d_sparse.data_ptr() + place[2]))
+        d_bytes = torch.where(coded, d_clen, torch.where(raw, d_ulen, d_rec))
+        d_status = torch.zeros(1, dtype=torch.int32, device=device)
+        if n_packets:
+            H.move_bytes(d_src, d_dst, d_bytes, n_packets, stream=stream, d_status=d_status)
+        order = torch.argsort(d_kind, stable=True)
+        d_offsets = torch.cat([zero, torch.cumsum(d_clen[order[:n_coded]], 0)])
+        d_raw_offsets = torch.cat([zero, torch.cumsum(d_len16[order[n_coded:n_coded + n_stored]], 0)])
+        d_sparse_offsets = torch.cat([zero, torch.cumsum(d_rec[order[n_coded + n_stored:]], 0)])
+        d_stored = d_kind.to(torch.uint8)
+        _raise_on_status(d_status, "move_bytes")           # (.item() waits for this stream: the upload is done with too)
+    plain = all(w == 1 for w in widths) and not any(flags) and not any(bases)
+    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes, crc32=d_crc,
+                      planes=None if plain else widths, stored=d_stored, raw=d_raw, raw_offsets=d_raw_offsets,
+                      delta=flags if any(flags) else None, based=bases if any(bases) else None, sparse=d_sparse,
+                      sparse_offsets=d_sparse_offsets,
+                      kinds_rule=(bool(n_stored), bool(n_packets - n_coded - n_stored)) if mixed else None)
 
 
 def plane_widths(tensors, planes):

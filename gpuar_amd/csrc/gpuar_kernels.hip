@@ -43,6 +43,7 @@
 #include <string.h>
 
 #include "gpuar_hip.h"
+#include "gpuar_hip_gip.h"
 
 #include "lane_codec.h"
 #include "crc32.h"
@@ -3587,6 +3588,44 @@ kinds_expand_kernel(KindsExpandArgs a) {
     }
 }
 
+// move_bytes_kernel: region r is bytes[r] (1 .. 8704; 0 moves nothing) bytes from src[r] to dst[r], both at ANY
+// byte alignment -- the packets of a version-6 .gip stream taken apart into the three regions of a batch.Compressed.  The shape is
+// gather_kernel's, with its workgroup of 256 threads (the size gather_kernel's own sweep chose for regions of this length): the
+// bytes up to dst's first 16-byte boundary (head, 0 .. 15) and those behind its last (tail, 0 .. 15) go by single bytes from 32
+// lanes of the last wavefront, the quads between by destination-aligned 16-byte stores fed from byte-exact unaligned loads: three
+// rounds at most.  Every load lies in [src, src + bytes) and every store in [dst, dst + bytes): destinations may stand back to
+// back at byte grain.  A null pointer or bytes > 8704: BAD_BATCH, the region is skipped.
+constexpr uint32_t kMoveBytesThreads = 256;
+
+__global__ void __launch_bounds__(kMoveBytesThreads)
+move_bytes_kernel(MoveArgs a) {
+    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
+    using GlobalByte = __attribute__((address_space(1))) uint8_t;
+    using LooseQuad = const __attribute__((address_space(1))) KindsQuad1;
+    for (uint64_t r = blockIdx.x; r < a.n_regions; r += gridDim.x) {
+        const uintptr_t src = reinterpret_cast<uintptr_t>(a.src[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
+        const uint64_t n = a.bytes[r];
+        if (src == 0u || dst == 0u || n > kSlot) {           // uniform over the workgroup; nothing is read or written
+            if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        const uint32_t len = static_cast<uint32_t>(n);
+        uint32_t head = static_cast<uint32_t>((16u - (dst & 15u)) & 15u);
+        if (head > len) head = len;
+        const uint32_t body = (len - head) & ~15u;           // head + body <= len: whole quads of dst, all inside the region
+        const uint32_t tail = len - head - body;
+        for (uint32_t at = threadIdx.x * 16u; at < body; at += kMoveBytesThreads * 16u) {
+            const PlanesQuad whole = *reinterpret_cast<LooseQuad *>(src + head + at);
+            *reinterpret_cast<GlobalQuad *>(dst + head + at) = whole;
+        }
+        // the ragged ends: of the last wavefront's upper half, lanes 0 .. 15 take the head and lanes 16 .. 31 the tail
+        const uint32_t spare = threadIdx.x - (kMoveBytesThreads - 32u);
+        if (spare < head) *reinterpret_cast<GlobalByte *>(dst + spare) = *reinterpret_cast<const GlobalByte *>(src + spare);
+        else if (spare >= 16u && spare - 16u < tail)
+            *reinterpret_cast<GlobalByte *>(dst + head + body + spare - 16u) = *reinterpret_cast<const GlobalByte *>(src + head + body + spare - 16u);
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Plane-width survey (survey.h): est[j][p] = estimate(split_planes(buffer, 1 << j))[p] for the four widths at
 // once, from one read of the original bytes and without making any split, for one buffer or a batch.
@@ -4817,6 +4856,15 @@ int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_d
     a.dst = d_dst_ptrs;
     a.bytes = d_bytes;
     return region_call(gpuar::move_packets_kernel, 1u, gpuar::kMoveThreads, a, {d_src_ptrs, d_dst_ptrs, d_bytes}, {}, n_regions, d_status, stream);
+}
+
+int gpuar_hip_move_bytes(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes, size_t n_regions,
+                         uint32_t *d_status, void *stream) {
+    gpuar::MoveArgs a = {};
+    a.src = d_src_ptrs;
+    a.dst = d_dst_ptrs;
+    a.bytes = d_bytes;
+    return region_call(gpuar::move_bytes_kernel, 1u, gpuar::kMoveBytesThreads, a, {d_src_ptrs, d_dst_ptrs, d_bytes}, {}, n_regions, d_status, stream);
 }
 
 uint32_t gpuar_hip_sparse_len(uint32_t k) { return gpuar::sparse_len(k); }

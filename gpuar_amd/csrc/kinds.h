@@ -22,7 +22,7 @@
 //
 // Left out on purpose: counting kinds in the two surveys and in --planes=auto / --delta=auto (they predict coded sizes);
 // one read for scan and estimate together; skipping the encode of packets that end up non-coded in the CLI (it is bound by
-// the file system); reading version-6 files back into a batch.Compressed.
+// the file system).  (Reading version-6 files back into a batch.Compressed is batch.from_gip)
 #ifndef GPUAR_KINDS_H
 #define GPUAR_KINDS_H
 

@@ -94,8 +94,16 @@ SIGNATURES = {
     "gpuar_hip_kinds_expand": (_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "gpuar_hip_kinds_store_host": (_int, [_vp, _sz, _int, _int, _vp, _sz, _pu32, _psz]),
     "gpuar_hip_kinds_expand_host": (_int, [_vp, _sz, _u32, _vp, _sz]),
+    "gpuar_hip_gip_read_host": (_int, [_vp, _sz, _pu64]),
+    "gpuar_hip_gip_tables_host": (_int, [_vp, _sz, _vp, _vp, _vp, _sz]),
 }
 EXPORTS = list(SIGNATURES)
+# The device calls declared in include/gpuar_hip_gip.h: a table of their own, because the tables that pin gpuar_hip.h are closed
+# (INTEGRATION.md 3).  load() declares them beside SIGNATURES.
+GIP_SIGNATURES = {
+    "gpuar_hip_move_bytes": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+}
+GIP_INFO_WORDS = 10                  # GPUAR_GIP_INFO_WORDS
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
 ABI_VERSION = 2                      # GPUAR_HIP_ABI_VERSION of the header these bindings were written against
@@ -119,10 +127,10 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     # a library built from older sources lacks newer exports: say "rebuild" instead of dying with an AttributeError half-way
     # through the signatures
-    missing = [name for name in EXPORTS if not hasattr(lib, name)]
+    missing = [name for name in (*EXPORTS, *GIP_SIGNATURES) if not hasattr(lib, name)]
     if missing:
         raise GpuarError(f"{LIB_PATH} lacks {missing}: it was built from older sources -- rebuild the library")
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *GIP_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
@@ -695,6 +703,73 @@ def move_packets(d_src_ptrs, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d
         _require_u64_desc(t, name, n_regions)
     _call("gpuar_hip_move_packets", d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
           _stream_handle(stream))
+
+
+def move_bytes(d_src_ptrs, d_dst_ptrs, d_bytes, n_regions: int, stream=None, d_status=None):
+    """Copy n_regions regions of d_bytes[r] <= 8704 bytes from d_src_ptrs[r] to d_dst_ptrs[r], both at any byte alignment
+    (gpuar_hip_move_bytes, include/gpuar_hip_gip.h; the three descriptors are 64-bit CUDA tensors).  Nothing outside a region is
+    read or written: destinations may stand back to back.  A null pointer or a longer region is STATUS_BAD_BATCH."""
+    for t, name in ((d_src_ptrs, "d_src_ptrs"), (d_dst_ptrs, "d_dst_ptrs"), (d_bytes, "d_bytes")):
+        _require_u64_desc(t, name, n_regions)
+    _call("gpuar_hip_move_bytes", d_src_ptrs.data_ptr(), d_dst_ptrs.data_ptr(), d_bytes.data_ptr(), n_regions, _status_ptr(d_status),
+          _stream_handle(stream))
+
+
+# what gpuar_hip_gip_read_host / gpuar_hip_gip_tables_host return for a file they refuse (GPUAR_GIP_*): the sentence, with
+# {p} the packet and {at} the file offset the defect was found at, {v} the trailer version and {n} the file's bytes
+GIP_DEFECTS = {
+    1: "{n} bytes are fewer than the 20 of a .gip header",
+    2: "bytes 0 .. 2 are not the version 0.1.0 of a .gip header",
+    3: "the header's compressed size (bytes 12 .. 19) is below 20 or beyond the file's {n} bytes",
+    4: "the trailer at offset {at} says version {v} but cannot be used: it is damaged, or carries a width, a flag or a packet kind "
+       "(above 2) this reader does not know -- not a file to read without it",
+    5: "{p} packets (counted up to offset {at}) are not what the header's uncompressed size needs",
+    6: "the packet stream ends inside packet {p} at offset {at}",
+    7: "packet {p} at offset {at}: a clen below 4 or above 8704",
+    8: "packet {p} at offset {at}: the header's clen is not the trailer's",
+    9: "packet {p} at offset {at}: ulen is not the bytes the packet has in the file",
+    10: "packet {p} at offset {at}: a kind above 2",
+    11: "packet {p} at offset {at}: a raw packet whose clen is not 4 + ulen",
+    12: "packet {p} at offset {at}: a sparse packet whose record head is not valid for its clen and ulen",
+    13: "the packets' lengths end at offset {at}, not where the stream ends",
+}
+
+
+def _host_bytes(blob):
+    """A bytes-like object (or a numpy / CPU torch uint8 array) as a contiguous read-only numpy uint8 view, without a copy."""
+    import numpy as np
+    if hasattr(blob, "numpy") and not isinstance(blob, np.ndarray):      # a CPU torch tensor
+        blob = blob.numpy()
+    arr = blob if isinstance(blob, np.ndarray) else np.frombuffer(blob, dtype=np.uint8)
+    if arr.dtype != np.uint8 or arr.ndim != 1 or not arr.flags.c_contiguous:
+        raise GpuarError("a .gip file in memory is a contiguous one-dimensional array of uint8")
+    return arr
+
+
+def gip_read_host(blob, what="the file"):
+    """(info, clens, crcs or None, kinds or None) of a whole .gip file in memory, from the CLI's own reader
+    (gpuar_hip_gip_read_host, gpuar_hip_gip_tables_host: no device is touched): info as include/gpuar_hip.h lists it, the tables
+    as numpy arrays (uint16, uint32, uint8); crcs where the trailer has them, kinds where it is version 6.  Raises GpuarError
+    naming `what`, the defect and where it is."""
+    import numpy as np
+    arr = _host_bytes(blob)
+    lib = load()
+    info = (C.c_uint64 * GIP_INFO_WORDS)()
+    nothing = C.create_string_buffer(1)                        # (an empty blob has no address: it is refused as too short, not as null)
+    ptr = arr.ctypes.data if arr.size else C.addressof(nothing)
+
+    def refuse(code):
+        if code in GIP_DEFECTS:
+            raise GpuarError(f"{what}: " + GIP_DEFECTS[code].format(p=info[8], at=info[9], v=info[3], n=arr.size))
+        _check(code, f"{what}: gpuar_hip_gip_read_host")
+    refuse(lib.gpuar_hip_gip_read_host(ptr, arr.size, info))
+    n = int(info[4])
+    clens = np.zeros(n, dtype=np.uint16)
+    crcs = np.zeros(n, dtype=np.uint32) if info[6] & 1 else None
+    kinds = np.zeros(n, dtype=np.uint8) if info[3] == 6 else None
+    refuse(lib.gpuar_hip_gip_tables_host(ptr, arr.size, clens.ctypes.data, crcs.ctypes.data if crcs is not None else None,
+                                         kinds.ctypes.data if kinds is not None else None, n))
+    return [int(v) for v in info], clens, crcs, kinds
 
 
 SPARSE_NONE = 0xFFFFFFFF             # GPUAR_SPARSE_NONE: a packet without a majority byte

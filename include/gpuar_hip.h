@@ -546,6 +546,45 @@ int gpuar_hip_kinds_store_host(const uint8_t *in, size_t n_bytes, int stored_on,
  * then untouched, a sparse packet's out[0 .. n_bytes) unspecified; nothing is read beyond pkt_bytes). */
 int gpuar_hip_kinds_expand_host(const uint8_t *pkt, size_t pkt_bytes, uint32_t kind, uint8_t *out, size_t n_bytes);
 
+/* ------------------------------------------------------------------------
+ * Host only: a whole .gip file in memory, read by the CLI's own reader (FileHeader::getInfo, Trailer::load of
+ * gpuar_amd/csrc/host) and checked packet by packet -- what batch.read_gip and batch.from_gip stand on (the
+ * device call that goes with them is in gpuar_hip_gip.h).  No device is touched.
+ *
+ * info[] (GPUAR_GIP_INFO_WORDS values) is filled as far as the reader got:
+ *     [0] uncompressed bytes (a reference-written header's garbage upper bytes dropped, as getInfo drops them)
+ *     [1] where the packet stream begins in the file (20)   [2] where it ends
+ *     [3] the usable trailer's version, 0 where there is none (an unusable version 1, a malformed version 2 and unknown
+ *         versions included, as in the CLI); with GPUAR_GIP_TRAILER the version the unusable trailer claims (3 .. 6)
+ *     [4] packets   [5] elem_bytes (1 without a trailer that says)   [6] the trailer's flags (bit 0: CRCs, bit 1: delta, bit 2:
+ *         base, bit 3: kinds; version 2: 1)   [7] Trailer::Status as a number (0 none, 1 ok, 2 malformed, 3 .. 6 unusable)
+ *     [8] the packet and [9] the file offset a defect was found at (0 where it has none)
+ * The lengths come from the trailer, and without a usable one from walking the headers; EVERY packet's header is then checked
+ * against them.  Returns GPUAR_OK, GPUAR_ERR_ARGUMENT (a null pointer) or the first defect met, in this order:
+ * ---------------------------------------------------------------------- */
+#define GPUAR_GIP_INFO_WORDS 10
+#define GPUAR_GIP_SHORT    1   /* fewer than 20 bytes                                                                    */
+#define GPUAR_GIP_VERSION  2   /* bytes 0 .. 2 are not 0.1.0                                                              */
+#define GPUAR_GIP_SIZE     3   /* the header's compressed size is below 20 or beyond the file                             */
+#define GPUAR_GIP_TRAILER  4   /* a trailer that says version 3 .. 6 and cannot be used: not a file to read without it    */
+#define GPUAR_GIP_COUNT    5   /* the packets are not the ceil(uncompressed / 8192) the header's size needs               */
+#define GPUAR_GIP_CUT      6   /* the stream ends inside packet [8] (its header included)                                 */
+#define GPUAR_GIP_CLEN     7   /* packet [8]: clen below 4 or above 8704                                                  */
+#define GPUAR_GIP_TABLE    8   /* packet [8]: the header's clen is not the trailer's                                      */
+#define GPUAR_GIP_ULEN     9   /* packet [8]: ulen is not the bytes it has in the file (8192; the last one the rest)      */
+#define GPUAR_GIP_KIND    10   /* packet [8]: a kind above 2                                                              */
+#define GPUAR_GIP_RAW     11   /* packet [8]: raw and clen != 4 + ulen                                                    */
+#define GPUAR_GIP_SPARSE  12   /* packet [8]: sparse and the record's head fails sparse_head_ok, or clen != 4 + sparse_len(k) */
+#define GPUAR_GIP_SUM     13   /* the lengths do not sum to the stream                                                    */
+int gpuar_hip_gip_read_host(const uint8_t *file, size_t file_bytes, uint64_t info[GPUAR_GIP_INFO_WORDS]);
+
+/* The per-packet tables of the same file: clen[n_packets], and where the pointer is not null crc[n_packets] (the trailer's
+ * CRC-32s; GPUAR_ERR_ARGUMENT where it has none) and kind[n_packets] (version 6: the trailer's; else zeros).  n_packets must be
+ * info[4].  The same checks are made again and the same code returned; the arrays are written only with GPUAR_OK.  What is NOT
+ * checked here: the exceptions of a sparse record (gpuar_hip_sparse_unpack: GPUAR_STATUS_BAD_PACKET) and the inside of a coded
+ * packet (the decoder and the CRCs). */
+int gpuar_hip_gip_tables_host(const uint8_t *file, size_t file_bytes, uint16_t *clen, uint32_t *crc, uint8_t *kind, size_t n_packets);
+
 /* Reads and clears the FALLBACK status word of the current device: what
  * launches without a `d_status` of their own reported (the reference-named
  * executors above).  Synchronises the whole device -- meant for that
