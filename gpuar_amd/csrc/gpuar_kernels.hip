@@ -2255,6 +2255,12 @@ __device__ __forceinline__ void crc_load(CrcQuad (&q)[8], const CrcPacket &p, ui
     }
 }
 
+// how many of the lane's 128 bytes lie inside a packet of `count` bytes
+__device__ __forceinline__ uint32_t lane_have(uint32_t count, uint32_t lane) {
+    const uint32_t start = kCrcChunk * lane;
+    return count > start ? (count - start < kCrcChunk ? count - start : kCrcChunk) : 0u;
+}
+
 // one slicing-by-4 step; tab: the lane's copy (dword x * 32 of table t at t * 8192)
 __device__ __forceinline__ uint32_t crc_word(const uint32_t *tab, uint32_t c, uint32_t w) {
     c ^= w;
@@ -2288,7 +2294,7 @@ __device__ __forceinline__ uint32_t crc_packet(const uint32_t *tab, const CrcQua
         for (uint32_t i = 0; i < 32; ++i) s ^= col[i] & (0u - ((c >> i) & 1u));
         c = s;
     } else {
-        const uint32_t start = kCrcChunk * lane;
+        const uint32_t start = kCrcChunk * lane;      // (lane_have, written out: through the function crc32_kernel gains an instruction)
         const uint32_t have = count > start ? (count - start < kCrcChunk ? count - start : kCrcChunk) : 0u;
 #pragma unroll
         for (uint32_t k = 0; k < 8; ++k) {
@@ -2397,7 +2403,17 @@ __device__ __forceinline__ PlanesBuffer planes_buffer(const PlanesArgs &a, uint3
 typedef uint32_t PlanesQuad __attribute__((ext_vector_type(4)));
 using PlanesGlobalQuad = __attribute__((address_space(1))) PlanesQuad;
 using PlanesGlobalWord = __attribute__((address_space(1))) uint32_t;
+using PlanesGlobalHalf = __attribute__((address_space(1))) uint16_t;
 using PlanesGlobalByte = __attribute__((address_space(1))) uint8_t;
+// ... and what is read at less than its own alignment: out of a slot (4-byte aligned) or a compacted stream (any byte)
+typedef uint32_t KindsQuad4 __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at a 4-byte-aligned address
+typedef uint32_t KindsQuad1 __attribute__((ext_vector_type(4), aligned(1)));      // ... and at any address
+typedef uint32_t KindsWord1 __attribute__((aligned(1)));
+typedef uint16_t KindsHalf1 __attribute__((aligned(1)));
+using GlobalQuad4 = __attribute__((address_space(1))) KindsQuad4;
+using LooseQuad = const __attribute__((address_space(1))) KindsQuad1;
+using LooseWord = const __attribute__((address_space(1))) KindsWord1;
+using LooseHalf = const __attribute__((address_space(1))) KindsHalf1;
 
 struct PlanesPerm {
     __device__ __forceinline__ uint32_t operator()(uint32_t a, uint32_t b, uint32_t sel) const { return __builtin_amdgcn_perm(a, b, sel); }
@@ -2986,8 +3002,7 @@ estimate_kernel(CrcArgs a) {
                     }
                 }
             } else {
-                const uint32_t start = kCrcChunk * lane;
-                const uint32_t have = p.count > start ? (p.count - start < kCrcChunk ? p.count - start : kCrcChunk) : 0u;
+                const uint32_t have = lane_have(p.count, lane);
 #pragma unroll
                 for (uint32_t k = 0; k < 8; ++k) {
                     const uint32_t w[4] = {q[k].x, q[k].y, q[k].z, q[k].w};
@@ -3036,11 +3051,26 @@ struct MoveArgs {
     uint32_t *status;
 };
 
+// A packet's last, partial quad: bytes [0, left) of q, left = 1 .. 15, to `to` (4-byte aligned) by dwords and bytes -- nothing
+// behind byte `left` is written.  The one copy for every kernel that stores a packet from registers.
+__device__ __forceinline__ void store_partial_quad(uintptr_t to, const PlanesQuad &q, uint32_t left) {
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+    PlanesGlobalWord *words = reinterpret_cast<PlanesGlobalWord *>(to);
+    PlanesGlobalByte *bytes = reinterpret_cast<PlanesGlobalByte *>(to);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+        if (4u * j + 4u <= left) {
+            words[j] = w[j];
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 3; ++b)
+                if (4u * j + b < left) bytes[4u * j + b] = static_cast<uint8_t>(w[j] >> (8u * b));
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kMoveThreads)
 move_packets_kernel(MoveArgs a) {
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
     const uint32_t at = 16u * threadIdx.x;
     for (uint64_t r = blockIdx.x; r < a.n_regions; r += gridDim.x) {
         const uintptr_t src = reinterpret_cast<uintptr_t>(a.src[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
@@ -3051,24 +3081,9 @@ move_packets_kernel(MoveArgs a) {
         }
         if (at >= n) continue;
         const uint32_t left = static_cast<uint32_t>(n) - at;
-        const PlanesQuad q = reinterpret_cast<const GlobalQuad *>(src)[threadIdx.x];
-        if (left >= 16u) {
-            reinterpret_cast<GlobalQuad *>(dst)[threadIdx.x] = q;
-        } else {
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-            GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
-            GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                if (4u * j + 4u <= left) {
-                    words[j] = w[j];
-                } else {
-#pragma unroll
-                    for (uint32_t b = 0; b < 3; ++b)
-                        if (4u * j + b < left) bytes[4u * j + b] = static_cast<uint8_t>(w[j] >> (8u * b));
-                }
-            }
-        }
+        const PlanesQuad q = reinterpret_cast<const PlanesGlobalQuad *>(src)[threadIdx.x];
+        if (left >= 16u) reinterpret_cast<PlanesGlobalQuad *>(dst)[threadIdx.x] = q;
+        else store_partial_quad(dst + at, q, left);
     }
 }
 
@@ -3083,13 +3098,15 @@ move_packets_kernel(MoveArgs a) {
 // reduced over the wave two to a register --, and a second pass over the registers counts the bytes equal to that candidate.
 // No LDS, no histogram.  Lane 0 writes scan[p].
 //
-// sparse_pack_kernel (regions, as move_packets_kernel): every lane counts its exceptions, an inclusive prefix sum over the wave
-// less its own count gives its first slot (lane order times in-lane order is ascending position), and the total is checked against scan[r] BEFORE
-// anything is written: the slots are then all inside the record's sparse_len(k) bytes.
+// sparse_pack_kernel (regions, as move_packets_kernel) is sparse_count, the check, the head, sparse_emit: the count gives the
+// wave's total and the lane's first slot, and the total is checked against scan[r] BEFORE anything is written: the slots are
+// then all inside the record's sparse_len(k) bytes.
 //
-// sparse_unpack_kernel (regions): the record is validated and the packet built in the wavefront's own 8 KiB of LDS -- filled,
-// then the exceptions scattered into it (ds byte writes, positions checked against the packet's length first), then read back
-// as quads and stored like move_packets_kernel's.  LDS operations of one wavefront complete in order: no barrier.
+// sparse_unpack_kernel (regions) validates the record's head and hands it to sparse_build, which builds the packet in the
+// wavefront's own 8 KiB of LDS and stores it like move_packets_kernel's.
+//
+// sparse_build and store_partial_quad are also what kinds_expand_kernel (below) does with a sparse packet, so each check on a
+// damaged record exists once; kinds_store_kernel shares sparse_differ and store_partial_quad and keeps the writer's text.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kSparseWaves = 4;                        // wavefronts per workgroup, a packet each
 constexpr uint32_t kSparseGroups = 2048;                    // scan: 8 workgroups per CU of an MI355X, persistent over the packets
@@ -3116,8 +3133,7 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
 // the packet's scan word (in every lane)
 template <bool Full>
 __device__ __forceinline__ uint32_t sparse_scan_packet_wave(const CrcQuad (&q)[8], uint32_t count, uint32_t lane) {
-    const uint32_t start = kCrcChunk * lane;
-    const uint32_t have = count > start ? (count - start < kCrcChunk ? count - start : kCrcChunk) : 0u;
+    const uint32_t have = lane_have(count, lane);
     uint32_t bits[4] = {0u, 0u, 0u, 0u};                    // bits[i]: the counts of bit 2 i (low half) and bit 2 i + 1 (high half)
 #pragma unroll
     for (uint32_t k = 0; k < 8; ++k) {
@@ -3176,13 +3192,70 @@ struct SparsePackArgs {
     uint32_t *status;
 };
 
+// one wavefront per item (a region, a packet), persistent: `for (uint64_t r = wave_item(); r < n; r += wave_items())`
+__device__ __forceinline__ uint64_t wave_item() { return static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); }
+__device__ __forceinline__ uint64_t wave_items() { return static_cast<uint64_t>(gridDim.x) * kSparseWaves; }
+
+// 0x80 in every byte of dword w, at byte `at` of the lane's 128, that lies inside the packet and is not the fill: an exception.
+// The one predicate behind the count and the stores of a record.
+__device__ __forceinline__ uint32_t sparse_differ(uint32_t w, uint32_t fill, uint32_t at, uint32_t have) {
+    return ~sparse_zero_bytes(w ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(at, have);
+}
+
+// The record writer, first half: the packet's exceptions counted over the wave (the total, in every lane) and `slot`, the
+// lane's first slot in the record -- an inclusive prefix sum less the lane's own count, so that lane order times in-lane order
+// is ascending position.  Nothing is written: the caller checks the total against the scan word, and what else it has to,
+// before it calls sparse_emit.
+__device__ __forceinline__ uint32_t sparse_count(const CrcQuad (&q)[8], uint32_t fill, uint32_t have, uint32_t lane, uint32_t &slot) {
+    uint32_t mine = 0;                                       // the lane's exceptions
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) {
+        const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) mine += __popc(sparse_differ(w[j], fill, 16u * i + 4u * j, have));
+    }
+    uint32_t upto = mine;                                    // inclusive prefix sum over the wave
+#pragma unroll
+    for (uint32_t off = 1; off < 64u; off <<= 1) {
+        const uint32_t below = __shfl_up(upto, off);
+        if (lane >= off) upto += below;
+    }
+    slot = upto - mine;
+    return __shfl(upto, 63);
+}
+
+// ... second half: behind the record's head at `rec` (4-byte aligned; the head itself is the caller's), pos[k], val[k] and the
+// pad up to sparse_len(k).  k is sparse_count's total and slot its slot: every store below is then to a slot below k, the same
+// predicate having been counted.
+__device__ __forceinline__ void sparse_emit(uintptr_t rec, const CrcQuad (&q)[8], uint32_t fill, uint32_t k, uint32_t have, uint32_t lane, uint32_t slot) {
+    PlanesGlobalHalf *pos = reinterpret_cast<PlanesGlobalHalf *>(rec + 4u);
+    PlanesGlobalByte *val = reinterpret_cast<PlanesGlobalByte *>(rec + 4u + 2u * k);
+    if (lane < sparse_len(k) - (4u + 3u * k)) val[k + lane] = 0;               // the pad
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) {
+        const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
+#pragma unroll
+        for (uint32_t j = 0; j < 4; ++j) {
+            const uint32_t at = 16u * i + 4u * j;
+            const uint32_t differ = sparse_differ(w[j], fill, at, have);
+            if (differ != 0u) {
+#pragma unroll
+                for (uint32_t b = 0; b < 4; ++b) {
+                    if (differ & (0x80u << (8u * b))) {
+                        pos[slot] = static_cast<uint16_t>(kCrcChunk * lane + at + b);
+                        val[slot] = static_cast<uint8_t>(w[j] >> (8u * b));
+                        ++slot;
+                    }
+                }
+            }
+        }
+    }
+}
+
 __global__ void __launch_bounds__(kSparseWaves * kLanes)
 sparse_pack_kernel(SparsePackArgs a) {
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
     const uint32_t lane = threadIdx.x & 63u;
-    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_regions; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+    for (uint64_t r = wave_item(); r < a.n_regions; r += wave_items()) {
         const uintptr_t src = reinterpret_cast<uintptr_t>(a.src[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
         const uint64_t n64 = a.bytes[r];
         const uint32_t scan = a.scan[r];
@@ -3194,51 +3267,15 @@ sparse_pack_kernel(SparsePackArgs a) {
         const CrcPacket p = {reinterpret_cast<const uint8_t *>(src), n};
         CrcQuad q[8];
         crc_load(q, p, lane);
-        const uint32_t start = kCrcChunk * lane;
-        const uint32_t have = n > start ? (n - start < kCrcChunk ? n - start : kCrcChunk) : 0u;
-        uint32_t mine = 0;                                   // the lane's exceptions
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                mine += __popc(~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(16u * i + 4u * j, have));
-        }
-        uint32_t upto = mine;                                // inclusive prefix sum over the wave
-#pragma unroll
-        for (uint32_t off = 1; off < 64u; off <<= 1) {
-            const uint32_t below = __shfl_up(upto, off);
-            if (lane >= off) upto += below;
-        }
-        const uint32_t total = __shfl(upto, 63);
+        const uint32_t have = lane_have(n, lane);
+        uint32_t slot;
+        const uint32_t total = sparse_count(q, fill, have, lane, slot);
         if (total != k || 2u * k >= n) {                     // wave-uniform; nothing has been written
             if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
             continue;
         }
-        GlobalHalf *pos = reinterpret_cast<GlobalHalf *>(dst + 4u);
-        GlobalByte *val = reinterpret_cast<GlobalByte *>(dst + 4u + 2u * k);
-        if (lane == 0u) *reinterpret_cast<GlobalWord *>(dst) = sparse_head(fill, k);
-        if (lane < sparse_len(k) - (4u + 3u * k)) val[k + lane] = 0;           // the pad
-        uint32_t slot = upto - mine;                         // slot < k wherever a store below is reached: the same predicate was counted
-#pragma unroll
-        for (uint32_t i = 0; i < 8; ++i) {
-            const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                const uint32_t at = 16u * i + 4u * j;
-                const uint32_t differ = ~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(at, have);
-                if (differ != 0u) {
-#pragma unroll
-                    for (uint32_t b = 0; b < 4; ++b) {
-                        if (differ & (0x80u << (8u * b))) {
-                            pos[slot] = static_cast<uint16_t>(start + at + b);
-                            val[slot] = static_cast<uint8_t>(w[j] >> (8u * b));
-                            ++slot;
-                        }
-                    }
-                }
-            }
-        }
+        if (lane == 0u) *reinterpret_cast<PlanesGlobalWord *>(dst) = sparse_head(fill, k);
+        sparse_emit(dst, q, fill, k, have, lane, slot);
     }
 }
 
@@ -3251,17 +3288,57 @@ struct SparseUnpackArgs {
     uint32_t *status;
 };
 
+// The packet builder: the n bytes (1 .. 8192) of the record at `rec` to dst (16-byte aligned), through `quads`, the wavefront's
+// own 8 KiB of LDS.  The caller has checked the record's head (sparse_head_ok: 4 + 3 k <= rec_bytes, 2 k < n); Loose says how
+// the positions are read: aligned u16 (false: sparse_unpack_kernel) or at any byte (true: kinds_expand_kernel).  The packet is filled by
+// quads, the exceptions are scattered into it -- every position checked against n, the value against the fill and the position
+// against the one in front BEFORE the LDS byte is written: no address is formed from an unchecked position --, and it is read
+// back as quads and stored like move_packets_kernel's.  A record that fails a check is BAD_PACKET, its destination left as it
+// was.  LDS operations of one wavefront complete in order: no barrier.
+template <bool Loose>
+__device__ __forceinline__ void sparse_build(PlanesQuad *quads, uintptr_t rec, uint32_t head, uint32_t n, uintptr_t dst, uint32_t lane, uint32_t *status) {
+    const uint32_t fill = head & 255u, k = head >> 16;
+    uint8_t *packet = reinterpret_cast<uint8_t *>(quads);
+    // pos[i] under either type (a bool, not the pointer's type: a typedef's alignment does not travel through a template argument)
+    const PlanesGlobalHalf *tight = reinterpret_cast<const PlanesGlobalHalf *>(rec + 4u);
+    LooseHalf *loose = reinterpret_cast<LooseHalf *>(rec + 4u);
+    const PlanesGlobalByte *val = reinterpret_cast<const PlanesGlobalByte *>(rec + 4u + 2u * k);
+#pragma unroll
+    for (uint32_t j = 0; j < 8; ++j)
+        if (16u * (lane + 64u * j) < n) quads[lane + 64u * j] = PlanesQuad(fill * kSparseLow);
+    asm volatile("" ::: "memory");                           // the fill in front of the exceptions, which other lanes write
+    bool bad = false;
+    for (uint32_t i = lane; i < k; i += 64u) {
+        const uint32_t at = Loose ? loose[i] : tight[i], v = val[i];
+        const bool ascending = i == 0u || (Loose ? loose[i - 1u] : tight[i - 1u]) < at;
+        if (at < n && v != fill && ascending) packet[at] = static_cast<uint8_t>(v);          // at < n <= 8192: inside the wavefront's LDS
+        else bad = true;
+    }
+    if (__any(bad)) {                                        // wave-uniform
+        if (lane == 0u) atomicOr(status, GPUAR_STATUS_BAD_PACKET);
+    } else {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's exceptions in front of the reads of whole quads
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) {
+            const uint32_t at = 16u * (lane + 64u * j);
+            if (at >= n) continue;
+            const PlanesQuad v = quads[lane + 64u * j];
+            if (n - at >= 16u) reinterpret_cast<PlanesGlobalQuad *>(dst)[lane + 64u * j] = v;
+            else store_partial_quad(dst + at, v, n - at);
+        }
+    }
+    // On both paths: what this packet did to the LDS in front of the next packet's fill.  A refused record leaves bytes that
+    // other lanes scattered; the compiler keeps those stores ahead of the fill anyway (a byte store may alias it), so on that path
+    // the barrier costs nothing and only says what is relied on -- one exit, one barrier, rather than one kernel with and one without.
+    asm volatile("" ::: "memory");
+}
+
 __global__ void __launch_bounds__(kSparseWaves * kLanes)
 sparse_unpack_kernel(SparseUnpackArgs a) {
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
     __shared__ PlanesQuad lds[kSparseWaves * (kPacket / 16u)];
     const uint32_t lane = threadIdx.x & 63u;
     PlanesQuad *quads = lds + (threadIdx.x >> 6) * (kPacket / 16u);          // the wavefront's own packet
-    uint8_t *packet = reinterpret_cast<uint8_t *>(quads);
-    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_regions; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+    for (uint64_t r = wave_item(); r < a.n_regions; r += wave_items()) {
         const uintptr_t rec = reinterpret_cast<uintptr_t>(a.rec[r]), dst = reinterpret_cast<uintptr_t>(a.dst[r]);
         const uint64_t rec_bytes = a.rec_bytes[r], n64 = a.bytes[r];
         if ((rec & 3u) != 0u || (dst & 15u) != 0u || n64 == 0u || n64 > kPacket) {
@@ -3269,55 +3346,12 @@ sparse_unpack_kernel(SparseUnpackArgs a) {
             continue;
         }
         const uint32_t n = static_cast<uint32_t>(n64);
-        const uint32_t head = rec_bytes >= 4u ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<const GlobalWord *>(rec)) : 0xFFFFFFFFu;
+        const uint32_t head = rec_bytes >= 4u ? __builtin_amdgcn_readfirstlane(*reinterpret_cast<const PlanesGlobalWord *>(rec)) : 0xFFFFFFFFu;
         if (rec_bytes < 4u || !sparse_head_ok(head, rec_bytes, n)) {         // wave-uniform; nothing behind the head is read
             if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
             continue;
         }
-        const uint32_t fill = head & 255u, k = head >> 16;                    // 4 + 3 k <= rec_bytes, 2 k < n
-        const GlobalHalf *pos = reinterpret_cast<const GlobalHalf *>(rec + 4u);
-        const GlobalByte *val = reinterpret_cast<const GlobalByte *>(rec + 4u + 2u * k);
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j)
-            if (16u * (lane + 64u * j) < n) quads[lane + 64u * j] = PlanesQuad(fill * kSparseLow);
-        asm volatile("" ::: "memory");                       // the fill in front of the exceptions, which other lanes write
-        bool bad = false;
-        for (uint32_t i = lane; i < k; i += 64u) {
-            const uint32_t at = pos[i], v = val[i];
-            const bool ascending = i == 0u || pos[i - 1u] < at;
-            if (at < n && v != fill && ascending) packet[at] = static_cast<uint8_t>(v);      // at < n <= 8192: inside the wavefront's LDS
-            else bad = true;
-        }
-        if (__any(bad)) {                                    // the destination is left as it was
-            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
-            continue;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's exceptions in front of the reads of whole quads
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t at = 16u * (lane + 64u * j);
-            if (at >= n) continue;
-            const uint32_t left = n - at;
-            const PlanesQuad v = quads[lane + 64u * j];
-            if (left >= 16u) {
-                reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = v;
-            } else {                                         // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
-                GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
-#pragma unroll
-                for (uint32_t d = 0; d < 4; ++d) {
-                    if (4u * d + 4u <= left) {
-                        words[d] = w[d];
-                    } else {
-#pragma unroll
-                        for (uint32_t b = 0; b < 3; ++b)
-                            if (4u * d + b < left) bytes[4u * d + b] = static_cast<uint8_t>(w[d] >> (8u * b));
-                    }
-                }
-            }
-        }
-        asm volatile("" ::: "memory");                       // these reads in front of the next packet's fill
+        sparse_build<false>(quads, rec, head, n, dst, lane, a.status);
     }
 }
 
@@ -3328,22 +3362,18 @@ sparse_unpack_kernel(SparseUnpackArgs a) {
 //
 // kinds_store_kernel runs behind the encoder, which has filled every slot: it applies sparse_kind to est[p] and scan[p]
 // (scan null: sparse off), writes kind[p], and overwrites the slot of a raw packet with header + bytes (the lane's 128 bytes in
-// registers as crc_load leaves them, stored to slot + 4 by 4-byte-aligned quads; the last partial quad by dwords and bytes) and
-// the slot of a sparse packet with header + record (count, prefix sum and stores as sparse_pack_kernel: the same predicate over
-// the same registers, the total compared with scan >> 8 and the record's length with the slot BEFORE anything is written).  A
+// registers as crc_load leaves them, stored to slot + 4 by 4-byte-aligned quads; the last partial quad by store_partial_quad)
+// and the slot of a sparse packet with header + record: count, prefix sum and stores as sparse_count and sparse_emit have them
+// (the same sparse_differ over the same registers), the total compared with scan >> 8 and the record's length with the slot
+// BEFORE anything is written.  The kernel keeps that text as a copy of its own, for a measured reason: see in front of it.  A
 // scan word that is not that of the bytes: BAD_BATCH, the slot stays the encoder's, kind[p] = 0 -- the stream is still valid.
 //
 // kinds_expand_kernel takes packet p of kind 1 or 2 out of a compacted stream, at any byte alignment, to out + 8192 p (16-byte
 // aligned): the header is checked against offsets[p + 1] - offsets[p] and the packet's bytes in n_bytes first (kinds.h); raw
 // bytes go by destination-aligned 16-byte stores fed from unaligned loads (as gather_kernel), the last partial quad by dwords
-// and bytes; a sparse packet is built in the wavefront's own 8 KiB of LDS as sparse_unpack_kernel builds it.  Nothing before
-// offsets[p] or from offsets[p + 1] on is read, nothing outside the packet's bytes is written.
+// and bytes loaded one by one; a sparse packet is sparse_unpack_kernel's own sparse_build, with the positions read at any byte.
+// Nothing before offsets[p] or from offsets[p + 1] on is read, nothing outside the packet's bytes is written.
 // ---------------------------------------------------------------------------
-typedef uint32_t KindsQuad4 __attribute__((ext_vector_type(4), aligned(4)));      // 16 bytes at a 4-byte-aligned address
-typedef uint32_t KindsQuad1 __attribute__((ext_vector_type(4), aligned(1)));      // ... and at any address
-typedef uint32_t KindsWord1 __attribute__((aligned(1)));
-typedef uint16_t KindsHalf1 __attribute__((aligned(1)));
-
 struct KindsStoreArgs {
     const uint8_t *in;
     size_t n_bytes;
@@ -3358,13 +3388,9 @@ struct KindsStoreArgs {
 
 __global__ void __launch_bounds__(kSparseWaves * kLanes)
 kinds_store_kernel(KindsStoreArgs a) {
-    using GlobalQuad4 = __attribute__((address_space(1))) KindsQuad4;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalHalf = __attribute__((address_space(1))) uint16_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
     const uint32_t lane = threadIdx.x & 63u;
-    GlobalByte *kinds = reinterpret_cast<GlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
-    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_packets; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+    PlanesGlobalByte *kinds = reinterpret_cast<PlanesGlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
+    for (uint64_t r = wave_item(); r < a.n_packets; r += wave_items()) {
         const size_t first = static_cast<size_t>(r) * kPacket;
         const uint32_t n = a.n_bytes - first < kPacket ? static_cast<uint32_t>(a.n_bytes - first) : kPacket;
         const uint32_t est = __builtin_amdgcn_readfirstlane(a.est[r]);
@@ -3378,47 +3404,33 @@ kinds_store_kernel(KindsStoreArgs a) {
         const CrcPacket p = {a.in + first, n};
         CrcQuad q[8];
         crc_load(q, p, lane);
-        const uint32_t start = kCrcChunk * lane;
-        const uint32_t have = n > start ? (n - start < kCrcChunk ? n - start : kCrcChunk) : 0u;
+        const uint32_t have = lane_have(n, lane);
         if (kind == kSparseRaw) {                            // 4 + n <= 8196 bytes of the slot
             if (lane == 0u) {
-                *reinterpret_cast<GlobalWord *>(slot) = kinds_header(kinds_raw_clen(n), n);
+                *reinterpret_cast<PlanesGlobalWord *>(slot) = kinds_header(kinds_raw_clen(n), n);
                 kinds[r] = static_cast<uint8_t>(kSparseRaw);
             }
-            const uintptr_t dst = slot + kKindsHeader + start;
+            const uintptr_t dst = slot + kKindsHeader + kCrcChunk * lane;
 #pragma unroll
             for (uint32_t i = 0; i < 8; ++i) {
                 const uint32_t at = 16u * i;
                 if (at >= have) continue;
-                const uint32_t left = have - at;
-                if (left >= 16u) {
-                    *reinterpret_cast<GlobalQuad4 *>(dst + at) = q[i];
-                } else {                                     // the packet's last, partial quad: nothing behind byte n
-                    const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
-                    GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
-                    GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
-#pragma unroll
-                    for (uint32_t j = 0; j < 4; ++j) {
-                        if (4u * j + 4u <= left) {
-                            words[j] = w[j];
-                        } else {
-#pragma unroll
-                            for (uint32_t b = 0; b < 3; ++b)
-                                if (4u * j + b < left) bytes[4u * j + b] = static_cast<uint8_t>(w[j] >> (8u * b));
-                        }
-                    }
-                }
+                if (have - at >= 16u) *reinterpret_cast<GlobalQuad4 *>(dst + at) = q[i];
+                else store_partial_quad(dst + at, q[i], have - at);
             }
             continue;
         }
         const uint32_t fill = scan & 255u, k = scan >> 8;   // (sparse_kind took the word: it is not kSparseNone)
+        // sparse_count and, behind the check, sparse_emit, written out.  Through the two functions the kernel
+        // needs 168 vector registers instead of 248, a third wavefront fits a SIMD, and the RAW path above then takes 7.5 ms
+        // instead of 4.8 on 8 GiB of raw packets: its stores, 16 bytes per lane at a stride of 128, get slower with more of them
+        // in flight.  Capping the occupancy by attribute costs 250 registers.  When the raw path has another layout, call them.
         uint32_t mine = 0;                                   // the lane's exceptions
 #pragma unroll
         for (uint32_t i = 0; i < 8; ++i) {
             const uint32_t w[4] = {q[i].x, q[i].y, q[i].z, q[i].w};
 #pragma unroll
-            for (uint32_t j = 0; j < 4; ++j)
-                mine += __popc(~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(16u * i + 4u * j, have));
+            for (uint32_t j = 0; j < 4; ++j) mine += __popc(sparse_differ(w[j], fill, 16u * i + 4u * j, have));
         }
         uint32_t upto = mine;                                // inclusive prefix sum over the wave
 #pragma unroll
@@ -3434,13 +3446,13 @@ kinds_store_kernel(KindsStoreArgs a) {
             }
             continue;
         }
-        GlobalHalf *pos = reinterpret_cast<GlobalHalf *>(slot + kKindsHeader + 4u);
-        GlobalByte *val = reinterpret_cast<GlobalByte *>(slot + kKindsHeader + 4u + 2u * k);
         if (lane == 0u) {
-            *reinterpret_cast<GlobalWord *>(slot) = kinds_header(kinds_sparse_clen(k), n);
-            *reinterpret_cast<GlobalWord *>(slot + kKindsHeader) = sparse_head(fill, k);
+            *reinterpret_cast<PlanesGlobalWord *>(slot) = kinds_header(kinds_sparse_clen(k), n);
+            *reinterpret_cast<PlanesGlobalWord *>(slot + kKindsHeader) = sparse_head(fill, k);
             kinds[r] = static_cast<uint8_t>(kSparseSparse);
         }
+        PlanesGlobalHalf *pos = reinterpret_cast<PlanesGlobalHalf *>(slot + kKindsHeader + 4u);
+        PlanesGlobalByte *val = reinterpret_cast<PlanesGlobalByte *>(slot + kKindsHeader + 4u + 2u * k);
         if (lane < sparse_len(k) - (4u + 3u * k)) val[k + lane] = 0;           // the pad
         uint32_t at_slot = upto - mine;                      // < k wherever a store below is reached: the same predicate was counted
 #pragma unroll
@@ -3449,12 +3461,12 @@ kinds_store_kernel(KindsStoreArgs a) {
 #pragma unroll
             for (uint32_t j = 0; j < 4; ++j) {
                 const uint32_t at = 16u * i + 4u * j;
-                const uint32_t differ = ~sparse_zero_bytes(w[j] ^ (fill * kSparseLow)) & kSparseHigh & sparse_mask<false>(at, have);
+                const uint32_t differ = sparse_differ(w[j], fill, at, have);
                 if (differ != 0u) {
 #pragma unroll
                     for (uint32_t b = 0; b < 4; ++b) {
                         if (differ & (0x80u << (8u * b))) {
-                            pos[at_slot] = static_cast<uint16_t>(start + at + b);
+                            pos[at_slot] = static_cast<uint16_t>(kCrcChunk * lane + at + b);
                             val[at_slot] = static_cast<uint8_t>(w[j] >> (8u * b));
                             ++at_slot;
                         }
@@ -3477,18 +3489,11 @@ struct KindsExpandArgs {
 
 __global__ void __launch_bounds__(kSparseWaves * kLanes)
 kinds_expand_kernel(KindsExpandArgs a) {
-    using GlobalQuad = __attribute__((address_space(1))) PlanesQuad;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    using GlobalByte = __attribute__((address_space(1))) uint8_t;
-    using LooseQuad = const __attribute__((address_space(1))) KindsQuad1;
-    using LooseWord = const __attribute__((address_space(1))) KindsWord1;
-    using LooseHalf = const __attribute__((address_space(1))) KindsHalf1;
     __shared__ PlanesQuad lds[kSparseWaves * (kPacket / 16u)];
     const uint32_t lane = threadIdx.x & 63u;
     PlanesQuad *quads = lds + (threadIdx.x >> 6) * (kPacket / 16u);          // the wavefront's own packet
-    uint8_t *packet = reinterpret_cast<uint8_t *>(quads);
-    const GlobalByte *kinds = reinterpret_cast<const GlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
-    for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * kSparseWaves + (threadIdx.x >> 6); r < a.n_packets; r += static_cast<uint64_t>(gridDim.x) * kSparseWaves) {
+    const PlanesGlobalByte *kinds = reinterpret_cast<const PlanesGlobalByte *>(reinterpret_cast<uintptr_t>(a.kind));
+    for (uint64_t r = wave_item(); r < a.n_packets; r += wave_items()) {
         const uint32_t kind = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(kinds[r]));
         if (kind == kSparseCoded) continue;                  // the decoder's
         const size_t first = static_cast<size_t>(r) * kPacket;
@@ -3514,10 +3519,12 @@ kinds_expand_kernel(KindsExpandArgs a) {
                 const uint32_t left = n - at;
                 if (left >= 16u) {
                     const PlanesQuad whole = *reinterpret_cast<LooseQuad *>(body + at);
-                    reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = whole;
-                } else {                                     // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
-                    GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
-                    GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
+                    reinterpret_cast<PlanesGlobalQuad *>(dst)[lane + 64u * j] = whole;
+                } else {
+                    // store_partial_quad's shape, kept apart from it: that one takes the whole quad in registers, and a 16-byte load
+                    // here would read from offsets[r + 1] on.  Each dword and byte is loaded only where it is stored.
+                    PlanesGlobalWord *words = reinterpret_cast<PlanesGlobalWord *>(dst + at);
+                    PlanesGlobalByte *bytes = reinterpret_cast<PlanesGlobalByte *>(dst + at);
 #pragma unroll
                     for (uint32_t d = 0; d < 4; ++d) {
                         if (4u * d + 4u <= left) {
@@ -3525,7 +3532,7 @@ kinds_expand_kernel(KindsExpandArgs a) {
                         } else {
 #pragma unroll
                             for (uint32_t b = 0; b < 3; ++b)
-                                if (4u * d + b < left) bytes[4u * d + b] = *reinterpret_cast<const GlobalByte *>(body + at + 4u * d + b);
+                                if (4u * d + b < left) bytes[4u * d + b] = *reinterpret_cast<const PlanesGlobalByte *>(body + at + 4u * d + b);
                         }
                     }
                 }
@@ -3540,51 +3547,7 @@ kinds_expand_kernel(KindsExpandArgs a) {
             if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
             continue;
         }
-        const uint32_t fill = head & 255u, k = head >> 16;                    // 4 + 3 k <= rec_bytes, 2 k < n
-        LooseHalf *pos = reinterpret_cast<LooseHalf *>(rec + 4u);
-        const GlobalByte *val = reinterpret_cast<const GlobalByte *>(rec + 4u + 2u * k);
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j)
-            if (16u * (lane + 64u * j) < n) quads[lane + 64u * j] = PlanesQuad(fill * kSparseLow);
-        asm volatile("" ::: "memory");                       // the fill in front of the exceptions, which other lanes write
-        bool bad = false;
-        for (uint32_t i = lane; i < k; i += 64u) {
-            const uint32_t at = pos[i], v = val[i];
-            const bool ascending = i == 0u || pos[i - 1u] < at;
-            if (at < n && v != fill && ascending) packet[at] = static_cast<uint8_t>(v);      // at < n <= 8192: inside the wavefront's LDS
-            else bad = true;
-        }
-        if (__any(bad)) {                                    // the destination is left as it was
-            if (lane == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_PACKET);
-            asm volatile("" ::: "memory");
-            continue;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every lane's exceptions in front of the reads of whole quads
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) {
-            const uint32_t at = 16u * (lane + 64u * j);
-            if (at >= n) continue;
-            const uint32_t left = n - at;
-            const PlanesQuad v = quads[lane + 64u * j];
-            if (left >= 16u) {
-                reinterpret_cast<GlobalQuad *>(dst)[lane + 64u * j] = v;
-            } else {                                         // the packet's last, partial quad: by dwords and bytes, nothing behind byte n
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                GlobalWord *words = reinterpret_cast<GlobalWord *>(dst + at);
-                GlobalByte *bytes = reinterpret_cast<GlobalByte *>(dst + at);
-#pragma unroll
-                for (uint32_t d = 0; d < 4; ++d) {
-                    if (4u * d + 4u <= left) {
-                        words[d] = w[d];
-                    } else {
-#pragma unroll
-                        for (uint32_t b = 0; b < 3; ++b)
-                            if (4u * d + b < left) bytes[4u * d + b] = static_cast<uint8_t>(w[d] >> (8u * b));
-                    }
-                }
-            }
-        }
-        asm volatile("" ::: "memory");                       // these reads in front of the next packet's fill
+        sparse_build<true>(quads, rec, head, n, dst, lane, a.status);
     }
 }
 

@@ -10,7 +10,7 @@ WAVES = 4                                    # kSparseWaves: wavefronts per work
 # kernel -> (LDS bytes per workgroup, vector registers measured, scalar registers measured)
 FACTS = {
     "sparse_scan_kernel": (0, 95, 74),
-    "sparse_pack_kernel": (0, 170, 72),
+    "sparse_pack_kernel": (0, 168, 72),
     "sparse_unpack_kernel": (WAVES * 8192, 52, 74),
 }
 
