@@ -1,6 +1,6 @@
-"""Verdict helpers of the concurrency tests (tests/test_gpu_concurrency.py, tests/test_gpu_filter_concurrency.py; not a test
-module): comparisons that stay on the device, one copy to the host per test that names every check that did not hold, status
-words against what each launch should report, and the non-blocking streams the launches go to.  torch is imported where it
+"""Verdict helpers of the concurrency tests (tests/test_gpu_concurrency.py, tests/test_gpu_filter_concurrency.py,
+tests/test_gpu_packet_forms_concurrency.py; not a test module): comparisons that stay on the device, one copy to the host per
+test that names every check that did not hold, status words against what each launch should report, and the non-blocking streams the launches go to.  torch is imported where it
 is used, so that importing this module needs no GPU."""
 
 

@@ -1,6 +1,8 @@
-"""Where the buffers lie and how far into a buffer a kernel works: every entry point of include/gpuar_hip.h at the weakest
-pointer alignment its contract allows, with the address line 2^32 (where a pointer's low word carries into its high word)
-inside each of its buffers in turn, and -- the filter, CRC, estimate and survey kernels -- at offsets past 2^32 inside one buffer.
+"""Where the buffers lie and how far into a buffer a kernel works: every entry point of include/gpuar_hip.h and of
+include/gpuar_hip_gip.h at the weakest pointer alignment its contract allows, with the address line 2^32 (where a pointer's low
+word carries into its high word) inside each of its buffers in turn, and -- the filter, CRC, estimate, survey, scan and kinds
+kernels and move_bytes -- at offsets past 2^32 inside one buffer; and the kernels that keep 8192 wavefronts resident on three
+packets per wavefront.
 The other GPU modules vary packet lengths, contents and concurrency and hand over the first byte of a fresh allocation.
 
 Every buffer of parts A and B is a slice of ONE arena of 2^32 + 128 MiB bytes, which therefore holds a multiple of 2^32 with
@@ -22,34 +24,65 @@ A. Weakest alignment.  All pointer arguments weak at once, then each in turn whi
    bytes), estimate and both surveys (d_est 4-weak, odd stride P + 1, mask 15 and the single width 8), move_packets (1, 15, 16,
    17, 8191, 8192 bytes), generate and gpuar_hip_copy.  generate's d_out must be 8-byte aligned (its kernels store 8 bytes at a
    time): at offsets 1 and 4 it returns GPUAR_ERR_ALIGNMENT and writes nothing, which the header now says.
+   The packet forms (sections 8 - 12; each section's docstring names the fault class it would catch): sparse_scan (9 packets +
+   77 bytes: zeros, exceptions at bytes 0, 127, 128 and n - 1, count(f) at n / 2 and n / 2 + 1, uniform, text, 128 exceptions in
+   one lane, one in every lane, a short last packet; d_scan 4-weak) and sparse_scan_batch (buffers 16-weak and not packet-aligned,
+   descriptors as for the batch CRC); sparse_pack / sparse_unpack (regions of 1, 2, 3, 15, 16, 17, 129, 8191 and 8192 bytes with
+   k = 0, 1, 64 over every lane, 128 in one lane and the largest k a small n allows; packets at 16 mod 32, the records back to
+   back from an address that is 4 mod 8 with canaries only behind the last, expected from sparse_pack_host and
+   sparse_unpack_host); kinds_store (stored on / off x d_scan given / NULL over raw, sparse and coded packets and a short last
+   one of each non-coded kind; slots of canaries behind a made-up header, d_kind byte-weak); kinds_expand (a stream built from
+   kinds_store_host's packets between kind-0 packets of odd lengths, raw and sparse packets starting at every residue mod 16,
+   the stream byte-weak and at 1 and 15 mod 16); move_bytes (regions of 0, 1, 15, 16, 17, 31, 33, 4097 and 8704 bytes, sources
+   at mixed residues, destinations back to back at byte grain, the blocks at five more residue pairs).
 B. The same shapes and references with the line inside one pointer argument at a time, the others weak elsewhere: in the
    middle of a packet of the second wavefront group, inside a slot's coded bytes, inside the compacted stream, the offsets
    array, a survey's rows, a filter's tail, the XOR base; and with a packet / slot / group boundary exactly on the line.  (A
    boundary on the line makes the start a multiple of the unit, 8192 or 512 bytes for slots: those placements cannot be weak
    as well and assert the boundary instead.)  Batch calls: one buffer straddles; in a second layout one buffer ends exactly
-   at the line and the next begins at it.
+   at the line and the next begins at it.  The packet forms: the line inside a record's pos[], exactly between pos[] and
+   val[], on a record's start; inside a raw slot's body, a sparse record in a slot, on a slot boundary; in a stream inside a raw
+   body, inside a sparse record and two bytes into a packet's header; inside d_kind, d_scan, d_offsets; and for move_bytes where
+   a destination's head bytes end, inside its body, where its tail bytes begin, at its first byte and one byte behind its
+   last, and the same for a source (the line is a multiple of 16: inside a destination it is always a quad boundary).
 C. One buffer of 2^32 + 3 * 65536 + 4097 + 5 bytes (packet 524288 starts at byte 2^32), generated on the device, three
    windows overwritten with sorted 64-bit integers (so the delta filter's borrows run through every byte): split / merge of
    planes (w = 8, 2), delta (w = 8) and xor (w = 8, in place, against a base of the same size that is freed right after), crc32
    and verify_crc32 with one byte flipped at 2^32 + 5 (first_bad = 524288), estimate and both surveys.  Compared against the
    *_host functions on three windows ([0, 128 KiB), 128 KiB either side of 2^32, the last group with the tail); over the
    whole buffer merge(split(x)) == x and the canary behind n holds.  The codec is not repeated (the 5 GiB tests cover it).
+   The packet forms: a second buffer of the same size of UNIFORM bytes (every whole packet raw) with four windows of 16 mixed
+   packets -- at packet 0, at packet 493 448 where the slot offset r * 8704 passes 2^32, at packet 524 288 where r * 8192 does,
+   and the last 16 with the short last packet -- through estimate, sparse_scan, kinds_store, compact and kinds_expand on one
+   stream: the windows against the host twins, every scan word, kind, slot and output packet of the whole buffer on the
+   device, the stream longer than 2^32 (asserted; at most 200 packets are not raw) and the packet that holds stream byte 2^32
+   by itself.  move_bytes: one launch of 4096 regions from behind offset 2^32 of the first buffer to back-to-back destinations
+   across offset 2^32 of another allocation, every residue pair, against numpy.
+D. 3 * 8192 + 5 packets: sparse_scan, kinds_store and kinds_expand keep 8192 wavefronts resident, so each takes three packets
+   (five take four) and kinds_expand builds them in the same 8 KiB of LDS: sparse, raw, coded and DAMAGED packets in orders
+   chosen so that what one leaves behind would show in the next; BAD_PACKET / BAD_BATCH exactly when a defect is present.
 
-Time, pytest --durations=0 on an MI355X, the module alone: 24 passed in 3.8 s (605 placed launches in parts A and B; the
-table-mode encode cases added since make it 625).
-    0.50 s  setup of test_codec_at_the_weakest_alignment[text] (the arena, the reference encoder on 2 x 1 MiB)
-    0.39 s  test_filters_past_4gib[delta-8] (the first of part C: generates and fills the 4 GiB buffer)
-    0.29 s  test_codec_at_the_weakest_alignment[text] (the first launches of the process)
+Time, pytest --durations=0 on an MI355X, the module alone: 40 passed in 3.9 s (625 placed launches in parts A and B for the
+older entry points, 151 for the packet forms).
+    0.49 s  setup of test_codec_at_the_weakest_alignment[text] (the arena, the reference encoder on 2 x 1 MiB)
+    0.46 s  test_kinds_pipeline_past_4gib (4 GiB generated, 4.25 GiB of slots filled, five launches, four passes of comparisons)
+    0.32 s  test_codec_at_the_weakest_alignment[text] (the first launches of the process)
     0.10 s  setup of test_batch_codec_at_the_weakest_alignment (321 reference packets)
-    0.06 s  test_codec_across_the_address_line[text], [uniform]
-    0.04 s  test_codec_at_the_weakest_alignment[uniform], test_batch_codec_at_the_weakest_alignment, test_xor_in_place_past_4gib
-    0.03 s  test_batch_codec_across_the_address_line
-    0.02 s  test_filters_past_4gib[planes-8], test_filters_across_the_address_line[xor]
-    0.01 s  test_filters_past_4gib[planes-2], test_estimate_and_surveys_past_4gib, test_crc32_at_the_weakest_alignment, the other
-            filter tests; every remaining test and setup is under 0.005 s.
-No shape had to shrink: no case of parts A and B comes near 5 s.  Memory: 4.1 GiB for the arena, at most 8.5 GiB more during
-part C.  Fixed seeds throughout.
+    0.07 s  test_kinds_expand_second_trip[damaged], test_codec_across_the_address_line[text], [uniform]
+    0.05 s  test_codec_at_the_weakest_alignment[uniform]
+    0.04 s  test_xor_in_place_past_4gib, test_batch_codec_at_the_weakest_alignment
+    0.03 s  test_batch_codec_across_the_address_line, test_filters_past_4gib[delta-8]
+    0.02 s  test_filters_past_4gib[planes-8], test_kinds_expand_second_trip[intact], test_filters_across_the_address_line[xor],
+            test_move_bytes_past_4gib
+    0.01 s  the tests of sections 9 - 11, test_filters_past_4gib[planes-2], test_estimate_and_surveys_past_4gib,
+            test_crc32_at_the_weakest_alignment, the other filter tests; every remaining test and setup is under 0.005 s
+            (test_sparse_scan_and_kinds_store_second_trip, the scan and move_bytes sections among them).
+No shape had to shrink: no case comes near 5 s.  Memory: 4.1 GiB for the arena; on top of it at most 8.5 GiB during the filter
+tests of part C (its buffer and one more of that size) and, by the sizes allocated, 16.3 GiB during the kinds pipeline (part
+C's buffer, which the module keeps, 4.0 GiB of uniform bytes, 4.25 GiB of slots and 4.0 GiB of stream; the slots are freed
+before the 4.0 GiB output is made), 8.0 GiB during test_move_bytes_past_4gib and 4.9 GiB in part D.  Fixed seeds throughout.
 """
+import struct
 import zlib
 
 import numpy as np
@@ -57,7 +90,9 @@ import pytest
 
 import address_edges as AE
 import batch_sweep as BS
+import kinds_ref as K
 import length_sweep as LS
+import sparse_ref as S
 from concurrency_checks import _fail_on, _same
 from gpuar_amd import synth
 
@@ -736,6 +771,365 @@ def test_move_generate_copy_across_the_address_line(H, A, small_cases):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 8. sparse_scan and sparse_scan_batch
+# ---------------------------------------------------------------------------------------------------------------------
+FORMS_N = 9 * PACKET + 77
+FORMS_NPK = 10
+
+
+_filled = S._packet                                          # (n, fill, where): n bytes of `fill` with exceptions at `where`, none of them the fill
+
+
+def _every_lane(n):
+    """One position in each 128-byte lane of a packet of n bytes."""
+    lanes = np.arange((n + 127) // 128)
+    at = lanes * 128 + (lanes * 37) % 128
+    return at[at < n]
+
+
+def _form_packets(rng, last):
+    """Nine whole packets -- zeros; fill 0x80 with exceptions at bytes 0, 127, 128 and n - 1; count(f) exactly n / 2 (no majority)
+    and n / 2 + 1; uniform; text; 128 exceptions in one lane; one in every lane; 100 spread out -- and `last`, the short one."""
+    return [np.zeros(PACKET, dtype=np.uint8), _filled(PACKET, 0x80, [0, 127, 128, PACKET - 1]),
+            _filled(PACKET, 0x00, np.arange(PACKET // 2) * 2), _filled(PACKET, 0xFF, np.arange(PACKET // 2 - 1) * 2 + 1),
+            rng.integers(0, 256, PACKET, dtype=np.uint8), np.frombuffer(K.TEXT[:PACKET], dtype=np.uint8).copy(),
+            _filled(PACKET, 0xFF, np.arange(128) + 3 * 128), _filled(PACKET, 0x80, _every_lane(PACKET)),
+            _filled(PACKET, 0x00, np.arange(100) * 81 + 7), last]
+
+
+def _put(v, **columns):
+    """Writes 64-bit descriptor columns into the placed arrays of the same names."""
+    for name, col in columns.items():
+        assert v[name].data_ptr() % 8 == 0
+        _i64(v[name]).copy_(torch.tensor([int(c) for c in col], dtype=torch.int64))
+
+
+def _scan_cases(H):
+    """Would catch: a packet address formed in 32 bits or from the wrong base (the line inside a packet and on a packet
+    boundary), a d_scan store wider than its word (d_scan 4-weak, the canary behind d_scan[npk]), a short last packet's bytes
+    past its end counted, a batch buffer located from a pointer read as two halves (buffers ending and beginning on the line)."""
+    rng = np.random.default_rng([SEED, 12])
+    n, npk = FORMS_N, FORMS_NPK
+    pkts = _form_packets(rng, _filled(77, 0x80, [0, 76]))
+    host = np.concatenate(pkts)
+    assert host.size == n
+    want = np.array(H.sparse_scan_host(host.tobytes()), dtype=np.uint32)
+    assert want.tolist() == [S.scan(x) for x in pkts] and want[2] == S.NONE and want[3] == ((PACKET // 2 - 1) << 8 | 0xFF) and want[4] == S.NONE
+    cases = [Case("sparse_scan", [Arg("d_in", n, 16, init=host), Arg("d_scan", 4 * npk, 4, want=want)],
+                  lambda v: H.sparse_scan(v["d_in"], n_bytes=n, d_scan=_i32(v["d_scan"])),
+                  lines=[("d_in", ("in", 4 * PACKET + 100)), ("d_in", ("on", 4 * PACKET)), ("d_in", ("in", n - 40)), ("d_scan", ("in", 20))])]
+    sizes = [0, 1, PACKET, PACKET + 1, 77, 3 * PACKET + 5, 16, 2 * PACKET + 8176, n]
+    datas = [np.concatenate([pkts[(b + j) % 9] for j in range(s // PACKET + 1)])[:s] for b, s in enumerate(sizes)]
+    fp, total_pk = H.batch_packet_count(sizes)
+    want = np.concatenate([np.array(H.sparse_scan_host(d.tobytes()), dtype=np.uint32) for d in datas if d.size])
+    assert want.size == total_pk
+    for join in (None, (7, 5)):
+        offs, total = AE.scattered(sizes, 15, align=16, gap=16, join=join)
+        bufs = [(o, s, (s + PACKET - 1) // PACKET) for o, s in zip(offs, sizes)]
+        img = _block_image(offs, datas, total)
+        tag = "" if join is None else ", one buffer ends where the next begins"
+        on = ("on", offs[8] + AE.weak(4 * PACKET + 100, 16)) if join is None else ("on", offs[5])
+
+        def scan_batch(v, bufs=bufs, join=join, offs=offs):
+            k = _fill_desc(v, bufs, v["block"], weak=(16, None if join is None else v["block"].data_ptr() + offs[join[1]]))
+            assert join is not None or all(p % PACKET for p in BS.columns(bufs, v["block"].data_ptr())[0]), "a buffer is packet-aligned"
+            H.sparse_scan_batch(_i64(v["d_ptrs"]), _i64(v["d_bytes"]), _i64(v["d_fp"]), k, total_pk, d_scan=_i32(v["d_scan"]), d_status=_i32(v["d_status"]))
+
+        cases.append(Case(f"sparse_scan_batch{tag}", [Arg("block", total, 32, init=img, block=True), Arg("d_scan", 4 * total_pk, 4, want=want)] +
+                          _desc_args(len(bufs)) + [_status_arg()], scan_batch, lines=[("block", on)],
+                          moving=["d_scan", "d_ptrs", "d_bytes", "d_fp"] if join is None else []))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def scan_cases(H):
+    return _scan_cases(H)
+
+
+def test_sparse_scan_at_the_weakest_alignment(H, A, scan_cases):
+    _part_a(H, A, scan_cases)
+
+
+def test_sparse_scan_across_the_address_line(H, A, scan_cases):
+    _part_b(H, A, scan_cases)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 9. sparse_pack and sparse_unpack
+# ---------------------------------------------------------------------------------------------------------------------
+def _record_cases(H):
+    """Packets at ptr % 32 == 16; their records back to back at 4-byte grain in one buffer that starts at ptr % 8 == 4 (a
+    record's length is 4 or 0 mod 8, so the starts take both residues: asserted), canaries only behind the last: a pad that is
+    a byte too long lands in the next record's head and shows.  Would catch: pos[] stored as dwords or val[] through pos's
+    pointer type (2-byte and 1-byte stores at an address that is only 4-aligned), rec + 4 + 2 k formed in 32 bits (the line
+    inside pos[], exactly between pos[] and val[], a record starting on it), descriptor arrays or d_scan read 16 bytes at a time."""
+    regions = [(1, 0x00, []), (2, 0x80, []), (3, 0xFF, [1]), (15, 0x00, np.arange(7) * 2), (16, 0x80, [15]), (17, 0xFF, np.arange(8) * 2 + 1),
+               (129, 0x00, [0, 127, 128]), (129, 0x80, np.arange(64) * 2), (8191, 0xFF, _every_lane(8191)), (PACKET, 0x00, np.arange(128) + 3 * 128),
+               (PACKET, 0x80, []), (PACKET, 0xFF, [PACKET - 1]), (8191, 0x00, [0]), (PACKET, 0x80, _every_lane(PACKET))]
+    pkts = [_filled(*r) for r in regions]
+    sizes = [x.size for x in pkts]
+    k = len(pkts)
+    scans = [S.scan(x) for x in pkts]
+    assert [s >> 8 for s in scans] == [0, 0, 1, 7, 1, 8, 3, 64, 64, 128, 0, 1, 1, 64] and all(2 * (s >> 8) < n for s, n in zip(scans, sizes))
+    assert sorted(set(sizes)) == [1, 2, 3, 15, 16, 17, 129, 8191, 8192]
+    recs = [np.frombuffer(H.sparse_pack_host(x.tobytes()), dtype=np.uint8) for x in pkts]
+    assert all(r.tobytes() == S.pack(x) and r.size == S.sparse_len(s >> 8) for r, x, s in zip(recs, pkts, scans))
+    back = [np.frombuffer(H.sparse_unpack_host(r.tobytes(), n), dtype=np.uint8) for r, n in zip(recs, sizes)]
+    assert all(np.array_equal(b, x) for b, x in zip(back, pkts))
+    rec_offs = np.concatenate([[0], np.cumsum([r.size for r in recs])]).astype(np.int64)
+    rec_total, rec_offs = int(rec_offs[-1]), [int(o) for o in rec_offs[:-1]]
+    assert {(4 + o) % 8 for o in rec_offs} == {0, 4}
+    rec_img = np.concatenate(recs)
+    src_offs, src_total = AE.scattered(sizes, 13, align=16, gap=16)
+    dst_offs, dst_total = AE.scattered(sizes, 14, align=16, gap=16)
+    lanes, one_lane, full = 13, 9, 10                        # k = 64 over every lane, k = 128 in one lane, a whole packet with k = 0
+    rec_lines = [("recs", ("on", rec_offs[lanes] + 4 + 2 * 10)), ("recs", ("on", rec_offs[lanes] + 4 + 2 * 64)), ("recs", ("on", rec_offs[lanes])),
+                 ("recs", ("on", rec_offs[one_lane] + 4 + 2 * 128 + 40)), ("recs", ("on", rec_offs[1]))]
+    assert all(at % 4 == 0 and 0 < at < rec_total for _n, (_how, at) in rec_lines)
+
+    def pack(v):
+        src, dst = [v["src"].data_ptr() + o for o in src_offs], [v["recs"].data_ptr() + o for o in rec_offs]
+        assert all(p % 32 == 16 for p in src) and all(p % 4 == 0 for p in dst) and v["d_scan"].data_ptr() % 4 == 0
+        _put(v, d_src_ptrs=src, d_bytes=sizes, d_dst_ptrs=dst)
+        H.sparse_pack(_i64(v["d_src_ptrs"]), _i64(v["d_bytes"]), _i32(v["d_scan"]), _i64(v["d_dst_ptrs"]), k, d_status=_i32(v["d_status"]))
+
+    def unpack(v):
+        rec, dst = [v["recs"].data_ptr() + o for o in rec_offs], [v["dst"].data_ptr() + o for o in dst_offs]
+        assert all(p % 32 == 16 for p in dst) and all(p % 4 == 0 for p in rec)
+        _put(v, d_rec_ptrs=rec, d_rec_bytes=[r.size for r in recs], d_dst_ptrs=dst, d_bytes=sizes)
+        H.sparse_unpack(_i64(v["d_rec_ptrs"]), _i64(v["d_rec_bytes"]), _i64(v["d_dst_ptrs"]), _i64(v["d_bytes"]), k, d_status=_i32(v["d_status"]))
+
+    desc = lambda *names: [Arg(name, 8 * k, 8, check=False) for name in names]
+    in_packet = lambda name, offs: [(name, ("on", offs[full] + 4112)), (name, ("on", offs[lanes] + 16))]
+    return [Case(f"sparse_pack, {k} regions of 1 .. 8192 bytes, k = 0 .. 128",
+                 [Arg("src", src_total, 32, init=_block_image(src_offs, pkts, src_total), block=True), Arg("recs", rec_total, 4, want=rec_img),
+                  Arg("d_scan", 4 * k, 4, init=np.array(scans, dtype=np.uint32))] + desc("d_src_ptrs", "d_bytes", "d_dst_ptrs") + [_status_arg()],
+                 pack, lines=rec_lines + in_packet("src", src_offs), moving=["recs", "d_scan", "d_src_ptrs", "d_bytes", "d_dst_ptrs", "d_status"]),
+            Case(f"sparse_unpack, {k} records",
+                 [Arg("recs", rec_total, 4, init=rec_img), Arg("dst", dst_total, 32, want=_block_image(dst_offs, back, dst_total), block=True)] +
+                 desc("d_rec_ptrs", "d_rec_bytes", "d_dst_ptrs", "d_bytes") + [_status_arg()],
+                 unpack, lines=rec_lines + in_packet("dst", dst_offs), moving=["recs", "d_rec_ptrs", "d_rec_bytes", "d_dst_ptrs", "d_bytes", "d_status"])]
+
+
+@pytest.fixture(scope="module")
+def record_cases(H):
+    return _record_cases(H)
+
+
+def test_sparse_records_at_the_weakest_alignment(H, A, record_cases):
+    _part_a(H, A, record_cases)
+
+
+def test_sparse_records_across_the_address_line(H, A, record_cases):
+    _part_b(H, A, record_cases)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 10. kinds_store
+# ---------------------------------------------------------------------------------------------------------------------
+def _made_up_header(p, ulen):
+    """What stands in a slot before kinds_store: a header nobody wrote (clen 4 .. 254), in front of canaries."""
+    return np.frombuffer(struct.pack("<HH", 4 + (37 * p) % 251, ulen), dtype=np.uint8)
+
+
+def _store_cases(H):
+    """Slots of canaries with a made-up header each; a coded packet's slot must come back untouched in all 8704 bytes, a raw or
+    sparse one holds kinds_store_host's bytes and canaries from clen on.  Would catch: slot + 4 stored with 16-byte-aligned
+    stores (they would land at slot or slot + 16), d_kind written as a word (byte-weak, a canary behind kind[npk]), d_est or
+    d_scan read as quads, slots + r * 8704 or in + r * 8192 formed in 32 bits (the line inside a raw body, inside a sparse
+    record, on a slot boundary, inside d_in and d_kind)."""
+    rng = np.random.default_rng([SEED, 16])
+    n, npk = FORMS_N, FORMS_NPK
+    text = np.frombuffer(K.TEXT[:77], dtype=np.uint8).copy()
+    cases = []
+    for stored, scanned, last, last_kind in ((True, True, _filled(77, 0x80, [0, 76]), K.SPARSE), (True, False, rng.integers(0, 256, 77, dtype=np.uint8), K.RAW),
+                                             (False, True, np.zeros(77, dtype=np.uint8), K.SPARSE), (False, False, text, K.CODED)):
+        pkts = _form_packets(rng, last)
+        host = np.concatenate(pkts)
+        raw = host.tobytes()
+        est = np.array(H.estimate_host(raw), dtype=np.uint32)
+        scan = np.array(H.sparse_scan_host(raw), dtype=np.uint32)
+        before = np.full((npk, SLOT), CANARY, dtype=np.uint8)
+        for p, x in enumerate(pkts):
+            before[p, :4] = _made_up_header(p, x.size)
+        after, kinds = before.copy(), []
+        for p, x in enumerate(pkts):
+            kind, pkt = H.kinds_store_host(x.tobytes(), stored, scanned)
+            assert kind == H.sparse_rule(int(scan[p]) if scanned else S.NONE, int(est[p]), x.size, stored) == K.kind_of(x, stored, scanned)
+            assert (kind == K.CODED) == (pkt == b"") and len(pkt) <= SLOT
+            after[p, :len(pkt)] = np.frombuffer(pkt, dtype=np.uint8)
+            kinds.append(kind)
+        assert set(kinds) == {K.CODED} | ({K.RAW} if stored else set()) | ({K.SPARSE} if scanned else set()) and kinds[-1] == last_kind, kinds
+        lines = [("d_slots", ("on", 4 * SLOT)), ("d_in", ("in", 4 * PACKET + 100)), ("d_in", ("on", 4 * PACKET)), ("d_in", ("in", n - 40)),
+                 ("d_kind", ("in", 5))]
+        if stored:
+            p_raw = kinds.index(K.RAW)
+            lines.append(("d_slots", ("in", p_raw * SLOT + 5000)))
+        if scanned:
+            p_sp = max((p for p in range(npk) if kinds[p] == K.SPARSE), key=lambda p: int(after[p, 0]) | int(after[p, 1]) << 8)
+            assert (int(after[p_sp, 0]) | int(after[p_sp, 1]) << 8) >= 8 + 160, "no sparse record long enough to hold the line"
+            lines.append(("d_slots", ("in", p_sp * SLOT + 8 + 100)))
+
+        def store(v, stored=stored, scanned=scanned):
+            H.kinds_store(v["d_in"], _i32(v["d_est"]), _i32(v["d_scan"]) if scanned else None, stored, v["d_slots"], n_bytes=n, d_kind=v["d_kind"],
+                          d_status=_i32(v["d_status"]))
+
+        args = [Arg("d_in", n, 16, init=host), Arg("d_est", 4 * npk, 4, init=est)] + ([Arg("d_scan", 4 * npk, 4, init=scan)] if scanned else []) + \
+               [Arg("d_slots", npk * SLOT, 16, init=before, want=after), Arg("d_kind", npk, 1, want=np.array(kinds, dtype=np.uint8)), _status_arg()]
+        cases.append(Case(f"kinds_store, stored {'on' if stored else 'off'}, d_scan {'given' if scanned else 'NULL'}, kinds {kinds}", args, store, lines=lines))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def store_cases(H):
+    return _store_cases(H)
+
+
+def test_kinds_store_at_the_weakest_alignment(H, A, store_cases):
+    _part_a(H, A, store_cases)
+
+
+def test_kinds_store_across_the_address_line(H, A, store_cases):
+    _part_b(H, A, store_cases)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 11. kinds_expand
+# ---------------------------------------------------------------------------------------------------------------------
+def _filler(length):
+    """A coded packet of `length` bytes as far as anybody but the decoder can tell: its header and bytes nobody reads."""
+    return struct.pack("<HH", length, PACKET) + bytes([0xC3]) * (length - 4)
+
+
+def _expand_cases(H):
+    """A compacted stream built on the host: kinds_store_host's raw and sparse packets, each behind a made-up kind-0 packet of
+    an odd length chosen so that the raw and the sparse packets start at every residue mod 16 (asserted), and a short last
+    packet.  A kind-0 packet's 8192 output bytes stay canaries, the stream comes back unchanged.  Would catch: the header or
+    pos[] read through an aligned type (stream byte-weak, at 1 and 15 mod 16 too; the header two bytes either side of the
+    line), stream + offsets[r] or out + r * 8192 formed in 32 bits, a raw tail read from offsets[p + 1] on, d_offsets read as
+    quads (8-weak, the line inside it), d_kind read as words."""
+    packets = dict(K.packets())
+    rng = np.random.default_rng([SEED, 17])
+    raws = [packets[f"uniform_n{PACKET}"], rng.integers(0, 256, PACKET, dtype=np.uint8)]
+    sparses = [x for name, x in sorted(packets.items()) if x.size == PACKET and K.kind_of(x, False, True) == K.SPARSE]
+    assert len(sparses) > 20
+    cases = []
+    for turn, last in enumerate(("ends_n4095", "uniform_n4095")):
+        stream_packets, kinds, plain, at, starts = [], [], [], 0, {K.RAW: set(), K.SPARSE: set()}
+        for i in range(32):                                  # a filler, then a raw or a sparse packet that starts at residue i % 16
+            x = raws[(i + turn) % 2] if i < 16 else sparses[(i + 7 * turn) % len(sparses)]
+            kind, pkt = H.kinds_store_host(x.tobytes(), i < 16, i >= 16)
+            assert kind == (K.RAW if i < 16 else K.SPARSE) and (kind, pkt) == K.store(x, i < 16, i >= 16)
+            length = 4 + 13 * i + turn
+            length += (i % 16 - (at + length)) % 16
+            stream_packets += [_filler(length), pkt]
+            at += length
+            starts[kind].add(at % 16)
+            at += len(pkt)
+            kinds += [K.CODED, kind]
+            plain += [None, x]
+        assert starts[K.RAW] == starts[K.SPARSE] == set(range(16))
+        x = packets[last]
+        kind, pkt = H.kinds_store_host(x.tobytes(), True, True)
+        if kind == K.CODED:
+            kind, pkt = K.RAW, struct.pack("<HH", 4 + x.size, x.size) + x.tobytes()
+        stream_packets.append(pkt)
+        kinds.append(kind)
+        plain.append(x)
+        npk = len(kinds)
+        n_bytes = (npk - 1) * PACKET + x.size
+        offs = np.concatenate([[0], np.cumsum([len(p) for p in stream_packets])]).astype(np.int64)
+        stream = np.frombuffer(b"".join(stream_packets), dtype=np.uint8).copy()
+        out = np.full(n_bytes, CANARY, dtype=np.uint8)
+        for p, x in enumerate(plain):
+            if x is not None:
+                assert H.kinds_expand_host(stream_packets[p], kinds[p], x.size) == x.tobytes()
+                out[p * PACKET:p * PACKET + x.size] = x
+        p_raw, p_sp = 2 * 9 + 1, max(range(33, 64, 2), key=lambda p: len(stream_packets[p]))
+        assert kinds[p_raw] == K.RAW and kinds[p_sp] == K.SPARSE and len(stream_packets[p_sp]) > 8 + 160
+        lines = [("d_stream", ("on", int(offs[p_raw]) + 4 + 3001)), ("d_stream", ("on", int(offs[p_raw]) + 2)), ("d_stream", ("on", int(offs[p_sp]) + 2)),
+                 ("d_stream", ("on", int(offs[p_sp]) + 8 + 51)), ("d_stream", ("on", int(offs[npk - 1]) + 2)),
+                 ("d_out", ("in", p_sp * PACKET + 4096)), ("d_out", ("in", p_raw * PACKET + 100)), ("d_out", ("on", p_raw * PACKET)),
+                 ("d_out", ("on", p_sp * PACKET)), ("d_out", ("in", n_bytes - 40)), ("d_offsets", ("in", 8 * 30))]
+
+        def expand(v, npk=npk, n_bytes=n_bytes):
+            H.kinds_expand(v["d_stream"], _i64(v["d_offsets"]), v["d_kind"], npk, v["d_out"], n_bytes, d_status=_i32(v["d_status"]))
+
+        cases.append(Case(f"kinds_expand, {npk} packets, the last one {last}",
+                          [Arg("d_stream", stream.size, 1, init=stream), Arg("d_offsets", 8 * (npk + 1), 8, init=offs),
+                           Arg("d_kind", npk, 1, init=np.array(kinds, dtype=np.uint8)), Arg("d_out", n_bytes, 16, want=out), _status_arg()],
+                          expand, lines=lines,
+                          extra=[({"d_stream": ("skew", 16, r)}, f"d_stream at {r} mod 16") for r in (1, 15)]))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def expand_cases(H):
+    return _expand_cases(H)
+
+
+def test_kinds_expand_at_the_weakest_alignment(H, A, expand_cases):
+    _part_a(H, A, expand_cases)
+
+
+def test_kinds_expand_across_the_address_line(H, A, expand_cases):
+    _part_b(H, A, expand_cases)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 12. move_bytes
+# ---------------------------------------------------------------------------------------------------------------------
+def _move_bytes_cases(H):
+    """Regions of 1 .. 8704 bytes and one of 0, twice over: the sources at mixed residues mod 16, the destinations back to back
+    at byte grain in one block, so a store that leaves its region lands in a neighbour or in the canaries around the block.
+    The line is a multiple of 16, so inside a destination it is always a boundary between 16-byte pieces: it is put where the
+    head bytes end (3 bytes in), between two quads of the body, where the tail bytes begin, at the region's first byte and one
+    byte behind its last; inside a source it falls in the middle of an unaligned 16-byte load.  Would catch: src + head + at or
+    the tail's address formed in 32 bits, a whole-quad store over a ragged end, descriptor arrays read as quads."""
+    rng = np.random.default_rng([SEED, 18])
+    sizes = [1, 15, 16, 17, 31, 0, 33, 4097, SLOT]
+    sizes = sizes + sizes[::-1]
+    datas = [rng.integers(0, 256, s, dtype=np.uint8) for s in sizes]
+    k = len(sizes)
+    dst_offs = [21 + int(o) for o in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
+    dst_total = dst_offs[-1] + sizes[-1] + 27
+    src_offs, at = [], 7
+    for i, s in enumerate(sizes):
+        src_offs.append(at)
+        at += s + 16 + (5 * i + 3) % 16
+    src_total = at + 16
+    assert len({o % 16 for o in src_offs}) >= 8 and len({o % 16 for o in dst_offs}) >= 5
+    r = sizes.index(4097)
+    lines = [("dst", ("on", dst_offs[r] + at)) for at in (3, 2051, 4083, 0, 4097)] + [("src", ("on", src_offs[r] + at)) for at in (2056, 0, 4097)] + \
+            [("dst", ("on", dst_offs[8] + 5000)), ("src", ("on", src_offs[8] + 8699))]
+
+    def move(v):
+        _put(v, d_src_ptrs=[v["src"].data_ptr() + o for o in src_offs], d_dst_ptrs=[v["dst"].data_ptr() + o for o in dst_offs], d_bytes=sizes)
+        H.move_bytes(_i64(v["d_src_ptrs"]), _i64(v["d_dst_ptrs"]), _i64(v["d_bytes"]), k, d_status=_i32(v["d_status"]))
+
+    args = [Arg("src", src_total, 1, init=_block_image(src_offs, datas, src_total), block=True),
+            Arg("dst", dst_total, 1, want=_block_image(dst_offs, datas, dst_total), block=True),
+            Arg("d_src_ptrs", 8 * k, 8, check=False), Arg("d_dst_ptrs", 8 * k, 8, check=False), Arg("d_bytes", 8 * k, 8, check=False), _status_arg()]
+    skews = ((0, 0), (9, 2), (15, 15), (3, 12), (6, 7))       # with the destinations' own offsets, 5 .. 9 mod 16: every residue
+    return [Case(f"move_bytes, regions of {sizes[:9]} bytes and back", args, move, lines=lines,
+                 moving=["d_src_ptrs", "d_dst_ptrs", "d_bytes", "d_status"],
+                 extra=[({"src": ("skew", 16, rs), "dst": ("skew", 16, rd)}, f"src at {rs} and dst at {rd} mod 16") for rs, rd in skews])]
+
+
+@pytest.fixture(scope="module")
+def move_bytes_cases(H):
+    return _move_bytes_cases(H)
+
+
+def test_move_bytes_at_the_weakest_alignment(H, A, move_bytes_cases):
+    _part_a(H, A, move_bytes_cases)
+
+
+def test_move_bytes_across_the_address_line(H, A, move_bytes_cases):
+    _part_b(H, A, move_bytes_cases)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # C. offsets past 2^32 inside one buffer
 # ---------------------------------------------------------------------------------------------------------------------
 TAIL = BIG % GROUP                                           # 4102 bytes behind the last whole group of w = 8
@@ -886,3 +1280,346 @@ def test_xor_in_place_past_4gib(H, big):
     assert _canary_holds(x), "written behind byte n"
     assert H.status() == 0
     del y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# C, continued: estimate -> sparse_scan -> kinds_store -> compact -> kinds_expand past 2^32, and move_bytes
+# ---------------------------------------------------------------------------------------------------------------------
+BIG_NPK = (BIG + PACKET - 1) // PACKET                       # 524313
+BIG_LAST = BIG - (BIG_NPK - 1) * PACKET                      # 4102
+SLOT_CROSSING = (AE.LINE + SLOT - 1) // SLOT                 # 493448: the first packet whose slot starts past byte 2^32 of d_slots
+KW = 16                                                      # packets in a window
+KINDS_WINDOWS = (0, SLOT_CROSSING - KW // 2, AE.LINE // PACKET - KW // 2, BIG_NPK - KW)
+ROWS = 8192                                                  # packets per device comparison
+
+
+def _window_mix(rng, w):
+    """The 16 packets of window w: zeros, fills with k = 1 .. 100 exceptions, text (coded) and uniform (raw), in an order that
+    depends on the window; the last window ends with a fill whose short form is the buffer's last packet."""
+    text = np.frombuffer(K.TEXT[:PACKET], dtype=np.uint8)
+    fills = lambda f, k: _filled(PACKET, f, np.arange(k) * (PACKET // 101) + 5 + w)
+    mix = [np.zeros(PACKET, dtype=np.uint8), fills(0x80, 1), text.copy(), rng.integers(0, 256, PACKET, dtype=np.uint8), fills(0x00, 2), fills(0xFF, 17),
+           np.roll(text, 3 + w), fills(0x00, 64), rng.integers(0, 256, PACKET, dtype=np.uint8), fills(0x80, 100), np.full(PACKET, 0xFF, dtype=np.uint8),
+           np.roll(text, 100), fills(0xFF, 33), rng.integers(0, 256, PACKET, dtype=np.uint8), fills(0x00, 99), np.roll(text, 7)]
+    mix = mix[w:] + mix[:w]
+    if w == 3:
+        j = next(j for j, q in enumerate(mix) if not q.any())
+        mix[j], mix[-1] = mix[-1], mix[j][:BIG_LAST]
+    return mix
+
+
+def _made_up_slots(npk, last):
+    """npk slots of canaries behind a made-up header (clen 4 + p % 251, the packet's ulen), and 4096 canaries behind them."""
+    slots = torch.full((npk * SLOT + 4096,), CANARY, dtype=torch.uint8, device="cuda")
+    rows = slots[:npk * SLOT].view(npk, SLOT)
+    rows[:, 0] = (4 + torch.arange(npk, device="cuda") % 251).to(torch.uint8)
+    rows[:, 1] = 0
+    rows[:, 2] = 0
+    rows[:, 3] = PACKET >> 8
+    rows[npk - 1, 2] = last & 255
+    rows[npk - 1, 3] = last >> 8
+    return slots, rows
+
+
+def _all_equal(t, value):
+    """Device verdict: every byte of t is `value`, 256 MiB at a time."""
+    ok = torch.ones((), dtype=torch.bool, device="cuda")
+    for at in range(0, t.numel(), CHUNK):
+        ok = ok & t[at:at + CHUNK].eq(value).all()
+    return ok
+
+
+def test_kinds_pipeline_past_4gib(H, A):
+    """estimate, sparse_scan, kinds_store (stored on, d_scan given), compact and kinds_expand on one stream over 524 313 packets
+    of uniform bytes -- every whole one raw: its estimate is 8249 .. 8265 against the threshold 8196 -- with four windows of 16
+    mixed packets: at packet 0, where the slot offset r * 8704 passes 2^32 (packet 493 448), where the input offset r * 8192
+    does (524 288), and the last 16 with the short last packet.  The slots start as canaries behind a made-up header of clen
+    4 + p % 251, so the untouched (coded) packets of window 0 make later stream offsets odd, and with at most 200 packets that
+    are not raw the stream itself passes 2^32 (asserted).  Would catch: a 32-bit product in slots + r * 8704, in + r * 8192,
+    out + r * 8192 or stream + offsets[r] -- each writes a wrong but in-bounds place, so every slot, every kind and every
+    output packet of the whole buffer is compared on the device --, and a scan loop whose 32-bit packet index goes wrong."""
+    npk = BIG_NPK
+    assert H.packet_count(BIG) == npk and (SLOT_CROSSING - 1) * SLOT < AE.LINE <= SLOT_CROSSING * SLOT
+    x = _alloc_big()
+    H.generate("uniform", 33, BIG, out=x)
+    rng = np.random.default_rng([SEED, 19])
+    wins = []
+    for w, first in enumerate(KINDS_WINDOWS):
+        pkts = _window_mix(rng, w)
+        data = np.concatenate(pkts)
+        assert first * PACKET + data.size <= BIG and (w < 3 or first * PACKET + data.size == BIG)
+        x[first * PACKET:first * PACKET + data.size].copy_(_u8(data))
+        wins.append((first, pkts))
+    in_window = torch.zeros(npk, dtype=torch.bool, device="cuda")
+    for first, _pkts in wins:
+        in_window[first:first + KW] = True
+    slots, rows = _made_up_slots(npk, BIG_LAST)
+    room = npk * (4 + PACKET) + 4096
+    d_stream = torch.full((room,), CANARY, dtype=torch.uint8, device="cuda")
+    A.reset()
+    d_est, d_scan, d_kind = _i32(A.put(4 * npk, 4)), _i32(A.put(4 * npk, 4)), A.put(npk, 1)
+    d_offsets, word = _i64(A.put(8 * (npk + 1), 8)), _i32(A.put(4, 4))
+    word.zero_()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    H.estimate(x, n_bytes=BIG, d_est=d_est, stream=s)
+    H.sparse_scan(x, n_bytes=BIG, d_scan=d_scan, stream=s)
+    H.kinds_store(x, d_est, d_scan, True, slots[:npk * SLOT], n_bytes=BIG, d_kind=d_kind, stream=s, d_status=word)
+    H.compact(slots[:npk * SLOT], npk, d_stream, d_offsets, stream=s)
+    s.synchronize()
+
+    # the windows against the host twins
+    got_scan, got_kind = d_scan.cpu().numpy().view(np.uint32), d_kind.cpu().numpy()
+    host_kind = {}
+    for first, pkts in wins:
+        raw = np.concatenate(pkts).tobytes()
+        scan_host, est_host = H.sparse_scan_host(raw), H.estimate_host(raw)
+        assert got_scan[first:first + KW].tolist() == scan_host, f"scan words of packets {first} .. {first + KW - 1} differ from sparse_scan_host"
+        want_kind = [H.sparse_rule(sc, e, q.size, True) for sc, e, q in zip(scan_host, est_host, pkts)]
+        assert got_kind[first:first + KW].tolist() == want_kind, f"kinds of packets {first} .. {first + KW - 1} differ from sparse_rule"
+        got_slots = rows[first:first + KW].cpu().numpy()
+        for j, q in enumerate(pkts):
+            kind, pkt = H.kinds_store_host(q.tobytes(), True, True)
+            assert kind == want_kind[j]
+            want = np.full(SLOT, CANARY, dtype=np.uint8)
+            want[:4] = np.frombuffer(struct.pack("<HH", 4 + (first + j) % 251, q.size), dtype=np.uint8)
+            want[:len(pkt)] = np.frombuffer(pkt, dtype=np.uint8)
+            assert np.array_equal(got_slots[j], want), f"slot {first + j} (kind {kind}) differs from kinds_store_host or its canaries behind clen are gone"
+            host_kind[first + j] = kind
+        assert set(want_kind) == {K.CODED, K.RAW, K.SPARSE}
+    not_raw = int(d_kind.ne(K.RAW).sum().item())
+    assert 0 < not_raw == sum(k != K.RAW for k in host_kind.values()) <= 200, f"{not_raw} packets are not raw: the stream need not pass 2^32"
+
+    # the whole buffer on the device
+    verdicts = [("a scan word outside the windows is not NONE", (d_scan.eq(-1) | in_window).all()),
+                ("a packet outside the windows is not raw", (d_kind.eq(K.RAW) | in_window).all())]
+    header = torch.tensor([(4 + PACKET) & 255, (4 + PACKET) >> 8, 0, PACKET >> 8], dtype=torch.uint8, device="cuda")
+    ok = torch.ones((), dtype=torch.bool, device="cuda")
+    for lo in range(0, npk - 1, ROWS):
+        hi = min(lo + ROWS, npk - 1)
+        r, xs = rows[lo:hi], x[lo * PACKET:hi * PACKET].view(-1, PACKET)
+        good = r[:, :4].eq(header).all(1) & r[:, 4:4 + PACKET].eq(xs).all(1) & r[:, 4 + PACKET:].eq(CANARY).all(1)
+        ok = ok & (good | in_window[lo:hi]).all()
+    verdicts.append(("a slot outside the windows is not header(8196, 8192), the packet's bytes, canaries", ok))
+    verdicts.append(("written behind the last slot", slots[npk * SLOT:].eq(CANARY).all()))
+    offs = d_offsets.cpu().numpy()
+    total = int(offs[-1])
+    assert total > 1 << 32, f"the stream has {total} bytes: it does not pass 2^32"
+    assert total == int((rows[:, 0].to(torch.int64) | rows[:, 1].to(torch.int64) << 8).sum().item()), "offsets[-1] is not the sum of the clens"
+    verdicts.append(("written behind the stream", d_stream[total:].eq(CANARY).all()))
+    _fail_on(verdicts)
+    del r, xs, rows, slots
+    torch.cuda.empty_cache()
+
+    out = torch.full((BIG + 4096,), CANARY, dtype=torch.uint8, device="cuda")
+    s.wait_stream(torch.cuda.current_stream())
+    H.kinds_expand(d_stream, d_offsets, d_kind, npk, out, BIG, stream=s, d_status=word)
+    s.synchronize()
+    ok = torch.ones((), dtype=torch.bool, device="cuda")
+    for lo in range(0, npk - 1, ROWS):
+        hi = min(lo + ROWS, npk - 1)
+        o, xs = out[lo * PACKET:hi * PACKET].view(-1, PACKET), x[lo * PACKET:hi * PACKET].view(-1, PACKET)
+        ok = ok & torch.where(d_kind[lo:hi].ne(K.CODED), o.eq(xs).all(1), o.eq(CANARY).all(1)).all()
+    tail = out[(npk - 1) * PACKET:BIG]
+    assert host_kind[npk - 1] != K.CODED
+    verdicts = [("an output packet is not the input's (kind 1, 2) or not canaries (kind 0)", ok),
+                ("the short last packet is not the input's", _same(tail, x[(npk - 1) * PACKET:BIG])),
+                ("written behind n_bytes", out[BIG:].eq(CANARY).all()), ("the input changed or was written behind", x[BIG:].eq(CANARY).all()),
+                ("the status word is not 0", word.eq(0).all()), A.guards("the kinds pipeline past 4 GiB")]
+    at = int(np.searchsorted(offs, 1 << 32, side="right")) - 1
+    assert offs[at] <= 1 << 32 < offs[at + 1] and got_kind[at] == K.RAW, f"packet {at} holds stream byte 2^32 and is of kind {got_kind[at]}"
+    verdicts += [(f"packet {at}, which holds stream byte 2^32: its output differs", _same(out[at * PACKET:(at + 1) * PACKET], x[at * PACKET:(at + 1) * PACKET])),
+                 (f"packet {at}: its bytes in the stream differ", _same(d_stream[int(offs[at]) + 4:int(offs[at + 1])], x[at * PACKET:(at + 1) * PACKET]))]
+    _fail_on(verdicts)
+    assert H.status() == 0
+    del out, d_stream, x, o, xs, tail
+
+
+def test_move_bytes_past_4gib(H, A, big):
+    """One launch of 4096 regions of 1 .. 8704 bytes whose sources lie behind offset 2^32 of part C's buffer and whose
+    destinations stand back to back, at byte grain, across offset 2^32 of a second allocation, with every pair of residues
+    mod 16 (asserted).  Expected: numpy over the region list; everything else in the second allocation stays canaries."""
+    x, wins = big["x"], big["wins"]
+    tail = np.concatenate([wins[1][2 * GROUP:], wins[2]])
+    assert tail.size == BIG - AE.LINE
+    rng = np.random.default_rng([SEED, 20])
+    n = 4096
+    sizes = np.concatenate([[1, 15, 16, 17, 31, 33, 4097, SLOT], rng.integers(1, SLOT + 1, n - 8)])[rng.permutation(n)].astype(np.int64)
+    total = int(sizes.sum())
+    start = AE.LINE - total // 2 + 3
+    dst = start + np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    assert dst[0] < AE.LINE < dst[-1]
+    turn, src = [0] * 16, np.zeros(n, dtype=np.int64)
+    for i in range(n):
+        res = turn[dst[i] % 16] % 16
+        turn[dst[i] % 16] += 1
+        src[i] = int(rng.integers(0, tail.size - sizes[i] - 16)) // 16 * 16 + res
+    assert len({(int(a) % 16, int(b) % 16) for a, b in zip(src, dst)}) == 256 and (src + sizes <= tail.size).all()
+    want = np.full(total + 2 * 4096, CANARY, dtype=np.uint8)
+    for a, b, m in zip(src, dst - start + 4096, sizes):
+        want[b:b + m] = tail[a:a + m]
+    d = torch.full((AE.LINE + total + 8192,), CANARY, dtype=torch.uint8, device="cuda")
+    A.reset()
+    d_src, d_dst, d_bytes, word = _i64(A.put(8 * n, 8)), _i64(A.put(8 * n, 8)), _i64(A.put(8 * n, 8)), _i32(A.put(4, 4))
+    d_src.copy_(torch.from_numpy(src + AE.LINE + x.data_ptr()))
+    d_dst.copy_(torch.from_numpy(dst + d.data_ptr()))
+    d_bytes.copy_(torch.from_numpy(sizes))
+    word.zero_()
+    H.move_bytes(d_src, d_dst, d_bytes, n, d_status=word)
+    lo, hi = start - 4096, start + total + 4096
+    _fail_on([("the destinations differ from numpy's, or a byte next to them changed", _same(d[lo:hi], _u8(want))),
+              ("written in front of the destinations", _all_equal(d[:lo], CANARY)), ("written behind the destinations", _all_equal(d[hi:], CANARY)),
+              ("the sources changed", _same(x[AE.LINE:BIG], _u8(tail))), ("the status word is not 0", word.eq(0).all()),
+              A.guards("move_bytes past 4 GiB")])
+    assert _canary_holds(x) and H.status() == 0
+    del d
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# D. the second and third trip of a wavefront: sparse_scan, kinds_store and kinds_expand over 3 * 8192 + 5 packets
+# ---------------------------------------------------------------------------------------------------------------------
+WAVES = 2048 * 4                                             # the persistent grid: 2048 workgroups of 4 wavefronts, a packet each
+TRIPS_NPK = 3 * WAVES + 5
+TRIPS_LAST = 77
+TRIPS_N = (TRIPS_NPK - 1) * PACKET + TRIPS_LAST
+
+
+def _sparse_packet(H, x):
+    """x as a kind-2 packet of a stream, whatever the rule would make of it."""
+    rec = H.sparse_pack_host(x.tobytes())
+    return struct.pack("<HH", 4 + len(rec), x.size) + rec
+
+
+def _patched(pkt, at, data):
+    pkt = bytearray(pkt)
+    pkt[at:at + len(data)] = data
+    return bytes(pkt)
+
+
+@pytest.mark.parametrize("damage", [True, False], ids=["damaged", "intact"])
+def test_kinds_expand_second_trip(H, damage):
+    """Wavefront w of kinds_expand's 8192 takes packets w, w + 8192 and w + 16384 (w < 5: a fourth) and builds every sparse one
+    in the same 8 KiB of LDS.  What a packet leaves there must not show in the next: by w % 6 a wavefront meets 100 exceptions,
+    then fill 0xFF with none, then a raw packet; a DAMAGED record -- positions not ascending at index 70 (the first turn of 64
+    lanes has scattered its bytes), a value equal to the fill, a position >= n --, then a good packet with another fill and two
+    exceptions; raw, kind 0 and sparse in other orders; and wavefront 4 a damaged full packet in front of the buffer's short last
+    one.  Every packet that is not damaged must be exact (its template is pinned against kinds_expand_host), kind-0 packets stay
+    canaries, the stream is unchanged, and BAD_PACKET is set exactly when a damaged packet is present.  Would catch: a missing
+    ordering between one packet's scatter or read-back and the next packet's fill, a fill that covers only the next packet's
+    bytes where the read-back covers more, a loop stride that is not the grid's."""
+    rng = np.random.default_rng([SEED, 21])
+    sp100 = _filled(PACKET, 0x00, np.arange(100) * 81 + 7)
+    ff, two = np.full(PACKET, 0xFF, dtype=np.uint8), _filled(PACKET, 0x55, [9, 4000])
+    uniform, text = rng.integers(0, 256, PACKET, dtype=np.uint8), np.frombuffer(K.TEXT[:PACKET], dtype=np.uint8).copy()
+    last = _filled(TRIPS_LAST, 0x80, [0, TRIPS_LAST - 1])
+    good = _sparse_packet(H, sp100)
+    pos, val = 8, 8 + 2 * 100                                 # where pos[] and val[] begin in the packet
+    bad = [_patched(good, pos + 2 * 70, good[pos + 2 * 69:pos + 2 * 70]), _patched(good, val + 70, b"\x00"), _patched(good, pos + 2 * 99, struct.pack("<H", PACKET))]
+    for pkt in bad:
+        assert K.expand(pkt, K.SPARSE, PACKET) is None and K.expand(good, K.SPARSE, PACKET) is not None
+    raw_of = lambda q: struct.pack("<HH", 4 + q.size, q.size) + q.tobytes()
+    # (bytes or None for canaries, kind, packet, damaged)
+    T = [(sp100, K.SPARSE, good, False), (ff, K.SPARSE, _sparse_packet(H, ff), False), (uniform, K.RAW, raw_of(uniform), False),
+         (text, K.RAW, raw_of(text), False), (None, K.CODED, _filler(4 + 13), False), (two, K.SPARSE, _sparse_packet(H, two), False)] + \
+        [(sp100, K.SPARSE, pkt if damage else good, damage) for pkt in bad] + [(last, K.SPARSE, _sparse_packet(H, last), False)]
+    for q, kind, pkt, damaged in T:
+        if q is not None and not damaged:
+            assert H.kinds_expand_host(pkt, kind, q.size) == q.tobytes()
+    SP100, FF, RAW, TEXT, CODED, TWO, BAD_A, BAD_B, BAD_C, LAST = range(10)
+    by_class = [(SP100, FF, RAW), (BAD_A, TWO, FF), (RAW, SP100, TWO), (BAD_B, FF, SP100), (CODED, BAD_C, TWO), (TEXT, CODED, SP100)]
+    npk = TRIPS_NPK
+    idx = np.array([by_class[(p % WAVES) % 6][p // WAVES] if p < 3 * WAVES else (TWO, SP100, FF, RAW, LAST)[p - 3 * WAVES] for p in range(npk)])
+    idx[2 * WAVES + 4] = BAD_A                               # wavefront 4: a damaged full packet, then the short last one
+    assert (idx[4::WAVES] == [CODED, BAD_C, BAD_A, LAST]).all()
+    lens = np.array([len(t[2]) for t in T])
+    offs = np.concatenate([[0], np.cumsum(lens[idx])]).astype(np.int64)
+    stream = np.frombuffer(b"".join(T[t][2] for t in idx), dtype=np.uint8).copy()
+    assert stream.size == offs[-1] and len({int(o) % 16 for o in offs}) == 16
+    images = np.full((len(T), PACKET), CANARY, dtype=np.uint8)
+    for t, (q, _kind, _pkt, _damaged) in enumerate(T):
+        if q is not None:
+            images[t, :q.size] = q
+    d_idx = torch.from_numpy(idx).cuda()
+    want = _u8(images).view(len(T), PACKET)[d_idx].view(-1)    # (the last packet's row: its 77 bytes, then canaries)
+    skip = torch.tensor([t[3] for t in T], device="cuda")[d_idx]
+    d_stream = torch.full((stream.size + GUARD,), CANARY, dtype=torch.uint8, device="cuda")
+    d_stream[:stream.size] = _u8(stream)
+    before = d_stream.clone()
+    d_offsets = torch.from_numpy(offs).cuda()
+    d_kind = torch.tensor([t[1] for t in T], dtype=torch.uint8, device="cuda")[d_idx]
+    out = torch.full((npk * PACKET,), CANARY, dtype=torch.uint8, device="cuda")
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    H.kinds_expand(d_stream, d_offsets, d_kind, npk, out, TRIPS_N, d_status=word)
+    same = out.view(npk, PACKET).eq(want.view(npk, PACKET)).all(1)
+    n_bad = int(np.isin(idx, (BAD_A, BAD_B, BAD_C)).sum())
+    assert n_bad > WAVES // 3 and int(skip.sum().item()) == (n_bad if damage else 0)
+    _fail_on([("a packet that is not damaged differs from its template, a kind-0 packet is not canaries, or bytes behind the short last packet changed",
+               (same | skip).all()),
+              ("the stream changed", _same(d_stream, before)),
+              (f"the status word is not {H.STATUS_BAD_PACKET if damage else 0:#x}", word.eq(H.STATUS_BAD_PACKET if damage else 0).all())])
+    assert H.status() == 0
+
+
+@pytest.mark.parametrize("defect", [True, False], ids=["wrong_scan_words", "right_scan_words"])
+def test_sparse_scan_and_kinds_store_second_trip(H, defect):
+    """The same for sparse_scan and kinds_store (stored on, d_scan given): each of their 8192 wavefronts takes three packets of
+    the 3 * 8192 + 5, by w % 6 sparse, raw and coded ones in changing order.  The scan words are compared with the templates'
+    (sparse_scan_host), the kinds with sparse_rule, every slot with kinds_store_host's bytes behind canaries and a made-up
+    header.  With `defect`, the scan words of first-trip packets disagree with their bytes (a count that is one too many; a
+    fill that is no majority): BAD_BATCH, kind 0, the slot untouched, and the good packets behind them in the same wavefront
+    are stored as ever.  Would catch: state carried from one trip to the next (the prefix sum, the registers of a skipped
+    packet), `continue` paths that skip the stride, a loop stride that is not the grid's."""
+    rng = np.random.default_rng([SEED, 22])
+    text = np.frombuffer(K.TEXT[:PACKET], dtype=np.uint8).copy()
+    T = [_filled(PACKET, 0x00, np.arange(100) * 81 + 7), np.full(PACKET, 0xFF, dtype=np.uint8), rng.integers(0, 256, PACKET, dtype=np.uint8), text,
+         _filled(PACKET, 0x55, [9, 4000]), np.zeros(PACKET, dtype=np.uint8), _filled(TRIPS_LAST, 0x80, [0, TRIPS_LAST - 1])]
+    SP100, FF, RAW, TEXT, TWO, ZEROS, LAST = range(7)
+    by_class = [(SP100, FF, RAW), (TWO, RAW, SP100), (RAW, SP100, TWO), (TWO, TEXT, FF), (TEXT, ZEROS, RAW), (FF, TWO, TEXT)]
+    npk = TRIPS_NPK
+    idx = np.array([by_class[(p % WAVES) % 6][p // WAVES] if p < 3 * WAVES else (TWO, SP100, FF, RAW, LAST)[p - 3 * WAVES] for p in range(npk)])
+    scan_t = [H.sparse_scan_host(q.tobytes())[0] for q in T]
+    est_t = [H.estimate_host(q.tobytes())[0] for q in T]
+    kind_t, slot_t = [], np.full((len(T), SLOT), CANARY, dtype=np.uint8)
+    for t, q in enumerate(T):
+        kind, pkt = H.kinds_store_host(q.tobytes(), True, True)
+        assert kind == H.sparse_rule(scan_t[t], est_t[t], q.size, True)
+        slot_t[t, :len(pkt)] = np.frombuffer(pkt, dtype=np.uint8)
+        kind_t.append(kind)
+    assert [kind_t[t] for t in (SP100, FF, RAW, TEXT, TWO, ZEROS, LAST)] == [K.SPARSE, K.SPARSE, K.RAW, K.CODED, K.SPARSE, K.SPARSE, K.SPARSE]
+    images = np.full((len(T), PACKET), CANARY, dtype=np.uint8)
+    for t, q in enumerate(T):
+        images[t, :q.size] = q
+    d_idx = torch.from_numpy(idx).cuda()
+    x = _u8(images).view(len(T), PACKET)[d_idx].view(-1)
+    scans = np.array(scan_t, dtype=np.uint32)[idx]
+    kinds = np.array(kind_t, dtype=np.uint8)[idx]
+    wrong = np.zeros(npk, dtype=bool)
+    if defect:
+        first = np.arange(WAVES)
+        one_more, no_majority = first[first % 6 == 1], first[first % 6 == 3]
+        assert (idx[one_more] == TWO).all() and (idx[no_majority] == TWO).all()
+        scans[one_more] = (3 << 8) | 0x55
+        scans[no_majority] = (2 << 8) | 0x56
+        wrong[one_more] = wrong[no_majority] = True
+        kinds[wrong] = K.CODED
+    d_est = torch.from_numpy(np.array(est_t, dtype=np.uint32)[idx].view(np.int32)).cuda()
+    d_scan_in = torch.from_numpy(scans.view(np.int32)).cuda()
+    got_scan = torch.full((npk + 64,), -0x5A5A5A5B, dtype=torch.int32, device="cuda")
+    H.sparse_scan(x, n_bytes=TRIPS_N, d_scan=got_scan[:npk])
+    slots, rows = _made_up_slots(npk, TRIPS_LAST)
+    untouched = rows.clone()
+    d_kind = torch.full((npk + 64,), CANARY, dtype=torch.uint8, device="cuda")
+    word = torch.zeros(1, dtype=torch.int32, device="cuda")
+    H.kinds_store(x, d_est, d_scan_in, True, slots[:npk * SLOT], n_bytes=TRIPS_N, d_kind=d_kind[:npk], d_status=word)
+    d_kinds = torch.from_numpy(kinds).cuda()
+    want = torch.where(d_kinds.eq(K.CODED)[:, None], untouched, _u8(slot_t).view(len(T), SLOT)[d_idx])
+    true_scans = torch.from_numpy(np.array(scan_t, dtype=np.uint32)[idx].view(np.int32)).cuda()
+    _fail_on([("a scan word differs from sparse_scan_host's", _same(got_scan[:npk], true_scans)),
+              ("written behind d_scan[npk]", got_scan[npk:].eq(-0x5A5A5A5B).all()),
+              ("a kind differs from sparse_rule's (0 for a packet whose scan word is wrong)", _same(d_kind[:npk], d_kinds)),
+              ("written behind d_kind[npk]", d_kind[npk:].eq(CANARY).all()),
+              ("a slot differs: a coded packet's or a refused one's is not untouched, a raw or sparse one's is not kinds_store_host's bytes and canaries",
+               rows.eq(want).all()),
+              ("written behind the last slot", slots[npk * SLOT:].eq(CANARY).all()),
+              (f"the status word is not {H.STATUS_BAD_BATCH if defect else 0:#x}", word.eq(H.STATUS_BAD_BATCH if defect else 0).all())])
+    assert H.status() == 0
