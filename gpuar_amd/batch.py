@@ -72,9 +72,15 @@ from __future__ import annotations
 import bisect
 import struct
 from dataclasses import dataclass
+from typing import NamedTuple
 
 from . import hip as H
 from .hip import GpuarError
+
+
+def _is(value, word):
+    """`value` is the string `word` (and no list, array or tensor that `==` would compare element by element)"""
+    return isinstance(value, str) and value == word
 
 
 def _tensor_bytes(t, name):
@@ -109,10 +115,15 @@ def describe(tensors, what="tensors"):
 
 
 def _upload(device, *rows):
-    """The descriptor rows (lists of ints) as ONE int64 device tensor (one copy), returned split back into rows."""
+    """The descriptor rows (lists of ints below 2^64 -- from 2^63 on they wrap, as pointers do -- or numpy integer arrays) as ONE int64
+    device tensor (one pinned tensor, one copy), returned split back into rows, with the pinned tensor for the caller to hold."""
+    import numpy as np
     import torch
-    flat = [v if v < (1 << 63) else v - (1 << 64) for row in rows for v in row]
-    host = torch.tensor(flat or [0], dtype=torch.int64).pin_memory() if torch.cuda.is_available() else torch.tensor(flat or [0], dtype=torch.int64)
+    flat = np.concatenate([r.astype(np.int64, copy=False) if isinstance(r, np.ndarray) else np.array(r, dtype=np.uint64).view(np.int64) for r in rows]
+                          + [np.zeros(1, dtype=np.int64)])
+    host = torch.from_numpy(flat)
+    if torch.cuda.is_available():
+        host = host.pin_memory()
     dev = host.to(device, non_blocking=True)
     out, at = [], 0
     for row in rows:
@@ -121,9 +132,17 @@ def _upload(device, *rows):
     return out, host
 
 
-def _nothing():
+def _offsets(lengths):
+    """[0, lengths[0], lengths[0] + lengths[1], ...] (int64, on the lengths' device): where pieces of these lengths stand back to back."""
+    import torch
+    return torch.cat([torch.zeros(1, dtype=torch.int64, device=lengths.device), torch.cumsum(lengths, 0)])
+
+
+def _on(stream):
+    """the context in which torch's own work goes to `stream` (None: to the current one)"""
     import contextlib
-    return contextlib.nullcontext()
+    import torch
+    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
 
 
 def _raise_on_status(d_status, what):
@@ -182,12 +201,10 @@ class Compressed:
         return self.first_packet[-1]
 
     def _offsets_host(self):
-        if getattr(self, "_off", None) is None:
-            self._off = self.offsets.cpu().tolist()
-        return self._off
+        return self._host_copy("offsets")
 
     def _host_copy(self, name):
-        """The host copy of the device field `name`, made on first use and kept (as _offsets_host keeps the offsets): gip(b) for
+        """The host copy of the device field `name`, made on first use and kept (_offsets_host: that of the offsets): gip(b) for
         every buffer of the batch then costs one copy of the batch, not one per file.  `stream`, `raw`, `sparse`: bytes; the
         others: a list of ints; a field that is None: the empty one.  The fields are not written after compress."""
         kept = self.__dict__.setdefault("_host_copies", {})
@@ -209,14 +226,21 @@ class Compressed:
         lo, hi = self.first_packet[b], self.first_packet[b + 1]
         if self.stored is None:
             return lo, hi
-        if getattr(self, "_rank", None) is None:
-            self._rank = [0]
-            for flag in self.stored.cpu().tolist():
-                self._rank.append(self._rank[-1] + (0 if flag else 1))
-        if self._rank[hi] - self._rank[lo] != hi - lo:
-            raise GpuarError(f"buffer {b} has {hi - lo - (self._rank[hi] - self._rank[lo])} stored (raw or sparse) packets: it has no packet stream of "
+        rank = self._ranks()[H.KIND_CODED]
+        if rank[hi] - rank[lo] != hi - lo:
+            raise GpuarError(f"buffer {b} has {hi - lo - (rank[hi] - rank[lo])} stored (raw or sparse) packets: it has no packet stream of "
                              "coded packets alone; its .gip form is the version-6 file, gip(b, kinds=True), where the kinds came from the rule")
-        return self._rank[lo], self._rank[hi]
+        return rank[lo], rank[hi]
+
+    def _ranks(self):
+        """Per kind k (0 coded, 1 raw, 2 sparse) a list of n_packets + 1 entries: how many packets of kind k stand in front of batch
+        packet p -- packet p's place in `offsets`, `raw_offsets` or `sparse_offsets`.  Made on first use and kept."""
+        if getattr(self, "_rank", None) is None:
+            self._rank = [[0], [0], [0]]
+            for kind in self._host_copy("stored"):
+                for k, row in enumerate(self._rank):
+                    row.append(row[-1] + (k == kind))
+        return self._rank
 
     def payload(self, b: int):
         """A view of buffer b's packet stream (the bytes behind the header of its .gip file).  Raises GpuarError for a buffer that
@@ -230,9 +254,7 @@ class Compressed:
         packets as they are, the raw and the sparse ones behind a 4-byte header put in front of them here, on the host."""
         lo, hi = self.first_packet[b], self.first_packet[b + 1]
         kinds = self._host_copy("stored")
-        rank = [0, 0, 0]                                   # how many packets of each kind stand in front of packet lo
-        for k in kinds[:lo]:
-            rank[k] += 1
+        rank = [row[lo] for row in self._ranks()]          # how many packets of each kind stand in front of packet lo
         off = self._offsets_host()
         raw, raw_off = self._host_copy("raw"), self._host_copy("raw_offsets")
         rec, rec_off = self._host_copy("sparse"), self._host_copy("sparse_offsets")
@@ -265,22 +287,17 @@ class Compressed:
             if self.kinds_rule is None or self.stored is None:
                 raise GpuarError("gip(kinds=True) is the file of a batch compressed with stored=\"auto\" and / or sparse=\"auto\"")
             payload, clens, which = self._kinds_packets(b)
-            lo, hi = self.first_packet[b], self.first_packet[b + 1]
-            crcs = [v & 0xFFFFFFFF for v in self._host_copy("crc32")[lo:hi]] if self.crc32 is not None else None
-            return H.gip_header(self.sizes[b], len(payload)) + payload + trailer(
-                clens, self.planes[b] if self.planes is not None else 1, crcs, delta=bool(self.delta[b]) if self.delta is not None else False,
-                base=xored, kinds=which)
-        off = self._offsets_host()
-        lo, hi = self._coded_range(b)                      # (raises for a buffer that holds a stored packet, as payload(b) does)
-        p = self._host_copy("stream")[off[lo]:off[hi]]
-        out = H.gip_header(self.sizes[b], len(p)) + p
+        else:
+            off = self._offsets_host()
+            lo, hi = self._coded_range(b)                  # (raises for a buffer that holds a stored packet, as payload(b) does)
+            payload, clens, which = self._host_copy("stream")[off[lo]:off[hi]], [off[i + 1] - off[i] for i in range(lo, hi)], None
+        out = H.gip_header(self.sizes[b], len(payload)) + payload
         w = self.planes[b] if self.planes is not None else 1
         filtered = bool(self.delta[b]) if self.delta is not None else False
-        if self.crc32 is not None or w > 1 or filtered or xored:
-            clens = [off[i + 1] - off[i] for i in range(lo, hi)]
+        if which is not None or self.crc32 is not None or w > 1 or filtered or xored:
             lo, hi = self.first_packet[b], self.first_packet[b + 1]
             crcs = [v & 0xFFFFFFFF for v in self._host_copy("crc32")[lo:hi]] if self.crc32 is not None else None
-            out += trailer(clens, w, crcs, delta=filtered, base=xored)
+            out += trailer(clens, w, crcs, delta=filtered, base=xored, kinds=which)
         return out
 
 
@@ -371,20 +388,6 @@ def _gip_entry(entry, i):
                      "array, or a path")
 
 
-def _upload_rows(device, *rows):
-    """_upload for numpy rows: the int64 arrays as ONE pinned tensor and one copy, returned split back into device rows."""
-    import numpy as np
-    import torch
-    flat = np.concatenate([np.asarray(r, dtype=np.int64) for r in rows] + [np.zeros(1, dtype=np.int64)])
-    host = torch.from_numpy(flat).pin_memory()
-    dev = host.to(device, non_blocking=True)
-    out, at = [], 0
-    for r in rows:
-        out.append(dev[at:at + len(r)])
-        at += len(r)
-    return out, host
-
-
 def _gip_parse(files):
     """from_gip's host step: every file of the list read and checked (read_gip), and the list checked as a whole; no GPU."""
     if not isinstance(files, (list, tuple)):
@@ -435,7 +438,7 @@ def from_gip(files, device=None, stream=None) -> Compressed:
     import torch
     parsed = _gip_parse(files)
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    with torch.cuda.stream(stream) if stream is not None else _nothing():
+    with _on(stream):
         d_up, _staging = _gip_upload(parsed, sum(g.stream.size for g in parsed), device)
         return _gip_assemble(parsed, d_up, device, stream)
 
@@ -463,12 +466,11 @@ def _gip_assemble(parsed, d_up, device, stream):
         ulens = np.concatenate([np.minimum(H.PACKET, size - H.PACKET * np.arange(g.n_packets, dtype=np.int64)) for g, size in zip(parsed, sizes)]
                                + [np.zeros(0, dtype=np.int64)])
         rows += [kinds, ulens]
-    d_rows, _keep = _upload_rows(device, *rows)
+    d_rows, _keep = _upload(device, *rows)
     d_clen = d_rows[0]
     d_crc = d_rows[1].to(torch.int32) if any(with_crcs) else None
-    zero = torch.zeros(1, dtype=torch.int64, device=device)
     if not mixed:
-        d_stream, d_offsets = d_up, torch.cat([zero, torch.cumsum(d_clen, 0)])
+        d_stream, d_offsets = d_up, _offsets(d_clen)
     else:
         d_kind, d_ulen = d_rows[-2], d_rows[-1]
         is_coded, is_raw = kinds == H.KIND_CODED, kinds == H.KIND_RAW
@@ -488,10 +490,8 @@ def _gip_assemble(parsed, d_up, device, stream):
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if n_packets:
             H.move_bytes(d_src, d_dst, d_bytes, n_packets, stream=stream, d_status=d_status)
-        order = torch.argsort(d_kind, stable=True)
-        d_offsets = torch.cat([zero, torch.cumsum(d_clen[order[:n_coded]], 0)])
-        d_raw_offsets = torch.cat([zero, torch.cumsum(d_len16[order[n_coded:n_coded + n_stored]], 0)])
-        d_sparse_offsets = torch.cat([zero, torch.cumsum(d_rec[order[n_coded + n_stored:]], 0)])
+        in_stream, in_raw, in_sparse = _by_kind(d_kind, n_coded, n_stored)
+        d_offsets, d_raw_offsets, d_sparse_offsets = _offsets(d_clen[in_stream]), _offsets(d_len16[in_raw]), _offsets(d_rec[in_sparse])
         d_stored = d_kind.to(torch.uint8)
         _raise_on_status(d_status, "move_bytes")           # (.item() waits for this stream: the upload is done with too)
     plain = all(w == 1 for w in widths) and not any(flags) and not any(bases)
@@ -544,65 +544,83 @@ def base_pointers(tensors, base, what="tensors"):
         raise GpuarError("base: None or a list with a tensor or None per tensor")
     if len(base) != len(tensors):
         raise GpuarError(f"base: {len(base)} entries for {len(tensors)} {what}")
-    ptrs = []
-    for i, (t, b) in enumerate(zip(tensors, base)):
-        if b is None:
-            ptrs.append(0)
-            continue
-        if hasattr(b, "device") and hasattr(t, "device") and b.device != t.device:
-            raise GpuarError(f"base[{i}] is on {b.device}, {what}[{i}] on {t.device}")
-        have, need = _tensor_bytes(b, f"base[{i}]"), _tensor_bytes(t, f"{what}[{i}]")
-        if have != need:
-            raise GpuarError(f"base[{i}] holds {have} bytes, {what}[{i}] {need}: a base has exactly its tensor's bytes")
-        if need and b.data_ptr() % 16:
-            raise GpuarError(f"base[{i}] is not 16-byte aligned (data_ptr() % 16 = {b.data_ptr() % 16}); pass an aligned copy")
-        ptrs.append(b.data_ptr() if need else 0)
-    return ptrs
+    return [0 if b is None else
+            _base_pointer(b, i, getattr(t, "device", None), f"{what}[{i}]", lambda: _tensor_bytes(t, f"{what}[{i}]"), f"{what}[{i}]", "tensor")
+            for i, (t, b) in enumerate(zip(tensors, base))]
+
+
+def _base_pointer(t, i, device, where, need, whose, noun):
+    """The device pointer of base[i] = `t` (0 where it has no bytes) after the checks every base gets, in compress and in decompress:
+    on `device` (where that is known), a contiguous CUDA tensor of exactly need() bytes, 16-byte aligned.  `where`, `whose` and `noun`
+    name what it belongs to in the messages."""
+    if hasattr(t, "device") and device is not None and t.device != device:
+        raise GpuarError(f"base[{i}] is on {t.device}, {where} on {device}")
+    have, need = _tensor_bytes(t, f"base[{i}]"), need()
+    if have != need:
+        raise GpuarError(f"base[{i}] holds {have} bytes, {whose} {need}: a base has exactly its {noun}'s bytes")
+    if need and t.data_ptr() % 16:
+        raise GpuarError(f"base[{i}] is not 16-byte aligned (data_ptr() % 16 = {t.data_ptr() % 16}); pass an aligned copy")
+    return t.data_ptr() if need else 0
+
+
+# The filters in front of the coder, in the order in which they win: (hip's split function, hip's merge function, the descriptor rows
+# the two take behind the widths; None: the batch has nothing for this filter to do).  Entry b of such a row is 0 iff buffer b is not filtered.
+_FILTERS = (
+    ("split_xor_batch", "merge_xor_batch", lambda widths, flags, bases: [list(bases)] if bases is not None and any(bases) else None),
+    ("split_delta_batch", "merge_delta_batch", lambda widths, flags, bases: [[int(f) for f in flags]] if flags is not None and any(flags) else None),
+    ("split_planes_batch", "merge_planes_batch", lambda widths, flags, bases: [] if widths is not None and any(w != 1 for w in widths) else None),
+)
+
+
+def _filter(widths, flags, bases):
+    """(split function's name, merge function's name, extra descriptor rows) of the filter this batch takes -- a base over the delta
+    filter over planes alone --; None where nothing is split."""
+    for split, merge, rows in _FILTERS:
+        extra = rows(widths, flags, bases)
+        if extra is not None:
+            return split, merge, extra
+    return None
+
+
+class _Split(NamedTuple):
+    """What _split returns: the descriptors on the device, d_coded the pointers of the bytes to code, d_split the temporary buffer the split
+    copies stand in (None: nothing was split), keep the pinned host copy of the descriptors, for the caller to hold while the launches run."""
+    d_ptrs: object
+    d_bytes: object
+    d_fp: object
+    d_coded: object
+    d_split: object
+    keep: object
+
+
+def _split_layout(sizes, widths, extra):
+    """(bytes, per buffer its offset or None): the split copies of the buffers that are split or filtered, back to back (each 16-byte
+    aligned); the others (None) are coded where they are."""
+    at, places = 0, []
+    for b, (size, w) in enumerate(zip(sizes, widths)):
+        moved = (w != 1 or any(row[b] for row in extra)) and size
+        places.append(at if moved else None)
+        at += (size + 15) // 16 * 16 if moved else 0
+    return at, places
 
 
 def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None, bases=None):
     """The batch's descriptors on the device and -- where `widths` asks for it -- its buffers split into byte planes (one launch,
-    into a temporary buffer): (d_ptrs, d_bytes, d_first_packet, d_coded, d_split, the pinned host copy of the descriptors, for the
-    caller to hold while the launches run), d_coded the pointers of the bytes to code.  With `flags` (one bool per buffer, some
-    of them true) the same launch also filters the flagged buffers (hip.split_delta_batch); those get a split copy at any width.
-    With `bases` (one pointer per buffer, some of them not 0) the same launch XORs those buffers with their bases
-    (hip.split_xor_batch); they too get a split copy at any width."""
+    into a temporary buffer): a _Split.  With `flags` (one bool per buffer, some of them true) the same launch also filters the
+    flagged buffers (hip.split_delta_batch); those get a split copy at any width.  With `bases` (one pointer per buffer, some of them
+    not 0) the same launch XORs those buffers with their bases (hip.split_xor_batch); they too get a split copy at any width."""
     import torch
-    if bases is not None and any(bases):
-        at, split_ptrs = 0, []
-        for p, size, w, q in zip(ptrs, sizes, widths, bases):
-            moved = (w != 1 or q) and size
-            split_ptrs.append(at if moved else None)
-            at += (size + 15) // 16 * 16 if moved else 0
-        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
-        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
-        (d_ptrs, d_bytes, d_fp, d_elem, d_base, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, bases, split_ptrs)
-        H.split_xor_batch(d_ptrs, d_bytes, d_fp, d_elem, d_base, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
-        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
-    if flags is not None and any(flags):
-        at, split_ptrs = 0, []
-        for p, size, w, f in zip(ptrs, sizes, widths, flags):
-            moved = (w != 1 or f) and size
-            split_ptrs.append(at if moved else None)
-            at += (size + 15) // 16 * 16 if moved else 0
-        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
-        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
-        (d_ptrs, d_bytes, d_fp, d_elem, d_filter, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, [int(f) for f in flags], split_ptrs)
-        H.split_delta_batch(d_ptrs, d_bytes, d_fp, d_elem, d_filter, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
-        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
-    if widths is not None and any(w != 1 for w in widths):
-        # the split copies of the buffers that are split, back to back (each 16-byte aligned); the others are coded where they are
-        at, split_ptrs = 0, []
-        for p, size, w in zip(ptrs, sizes, widths):
-            split_ptrs.append(at if w != 1 and size else None)
-            at += (size + 15) // 16 * 16 if w != 1 else 0
-        d_split = torch.empty(max(at, 16), dtype=torch.uint8, device=device)
-        split_ptrs = [p if q is None else d_split.data_ptr() + q for p, q in zip(ptrs, split_ptrs)]
-        (d_ptrs, d_bytes, d_fp, d_elem, d_coded), _keep = _upload(device, ptrs, sizes, first_packet, widths, split_ptrs)
-        H.split_planes_batch(d_ptrs, d_bytes, d_fp, d_elem, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
-        return d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep
-    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
-    return d_ptrs, d_bytes, d_fp, d_ptrs, None, _keep
+    found = _filter(widths, flags, bases)
+    if found is None:
+        (d_ptrs, d_bytes, d_fp), keep = _upload(device, ptrs, sizes, first_packet)
+        return _Split(d_ptrs, d_bytes, d_fp, d_ptrs, None, keep)
+    split, _merge, extra = found
+    total, places = _split_layout(sizes, widths, extra)
+    d_split = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+    coded = [p if at is None else d_split.data_ptr() + at for p, at in zip(ptrs, places)]
+    (d_ptrs, d_bytes, d_fp, d_elem, *d_extra, d_coded), keep = _upload(device, ptrs, sizes, first_packet, widths, *extra, coded)
+    getattr(H, split)(d_ptrs, d_bytes, d_fp, d_elem, *d_extra, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
+    return _Split(d_ptrs, d_bytes, d_fp, d_coded, d_split, keep)
 
 
 def _packets(d_ptrs, d_bytes, d_fp, n_buffers, n_packets):
@@ -616,9 +634,16 @@ def _packets(d_ptrs, d_bytes, d_fp, n_buffers, n_packets):
     return buf, d_ptrs[buf] + at, torch.clamp(d_bytes[buf] - at, max=H.PACKET)
 
 
+def _stored_auto(stored):
+    """`stored` for the functions that take None or "auto" and no list of packets; anything else raises (before any launch)."""
+    if stored is not None and stored != "auto":
+        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    return stored
+
+
 def _stored_argument(stored, n_packets):
     """`stored` as None, "auto" or a list of n_packets bools; anything else raises (before any launch)."""
-    if stored is None or (isinstance(stored, str) and stored == "auto"):
+    if stored is None or _is(stored, "auto"):
         return stored
     if isinstance(stored, str):
         raise GpuarError(f"stored={stored!r}: None, \"auto\" or one bool per packet")
@@ -629,9 +654,17 @@ def _stored_argument(stored, n_packets):
     return [bool(f) for f in flags]
 
 
+def _by_kind(d_kind, n_coded, n_stored):
+    """The batch packets that are coded, raw and sparse, each in batch order: a stable sort by the kind (0 coded, 1 raw, 2 sparse; any
+    integer type) cut at the counts, which the caller has on the host.  No synchronisation."""
+    import torch
+    order = torch.argsort(d_kind, stable=True)
+    return order[:n_coded], order[n_coded:n_coded + n_stored], order[n_coded + n_stored:]
+
+
 def _partition(d_flags, d_len16, d_slen=None):
     """(n_stored, raw bytes, coded packets, stored packets, n_sparse, sparse bytes, sparse packets): the packets of every kind in
-    batch order (a stable sort by the kind: 0 coded, 1 raw, 2 sparse; one synchronisation for the counts).  d_slen: the bytes of
+    batch order (_by_kind; one synchronisation for the counts).  d_slen: the bytes of
     every packet's sparse record; None where no packet is sparse (d_flags is then 0 or 1)."""
     import torch
     if d_slen is None:
@@ -640,9 +673,8 @@ def _partition(d_flags, d_len16, d_slen=None):
     else:
         d_raw, d_sparse = (d_flags == H.KIND_RAW).to(torch.int64), (d_flags == H.KIND_SPARSE).to(torch.int64)
         n_stored, raw_bytes, n_sparse, sparse_bytes = torch.stack([d_raw.sum(), (d_len16 * d_raw).sum(), d_sparse.sum(), (d_slen * d_sparse).sum()]).tolist()
-    order = torch.argsort(d_flags, stable=True)
-    n_coded = d_flags.numel() - n_stored - n_sparse
-    return n_stored, raw_bytes, order[:n_coded], order[n_coded:n_coded + n_stored], n_sparse, sparse_bytes, order[n_coded + n_stored:]
+    coded, kept, packed = _by_kind(d_flags, d_flags.numel() - n_stored - n_sparse, n_stored)
+    return n_stored, raw_bytes, coded, kept, n_sparse, sparse_bytes, packed
 
 
 def _sparse_argument(sparse, stored):
@@ -650,9 +682,9 @@ def _sparse_argument(sparse, stored):
     packets: the rule that chooses a packet's kind needs the estimate."""
     if sparse is None:
         return None
-    if not (isinstance(sparse, str) and sparse == "auto"):
+    if not _is(sparse, "auto"):
         raise GpuarError(f"sparse={sparse!r}: None or \"auto\"")
-    if stored is not None and not (isinstance(stored, str) and stored == "auto"):
+    if stored is not None and not _is(stored, "auto"):
         raise GpuarError("sparse=\"auto\" goes with stored=None or stored=\"auto\", not with a list of stored packets")
     return sparse
 
@@ -684,14 +716,20 @@ def _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_
         return [False] * n
     totals = []
     for flags in (None, [True] * n):
-        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
-        d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device).to(torch.int64)
-        buf, _ptr, _len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+        s = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
+        d_est = H.estimate_batch(s.d_coded, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=d_status, device=device).to(torch.int64)
+        buf, _ptr, _len = _packets(s.d_coded, s.d_bytes, s.d_fp, n, n_packets)
         totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est[:n_packets]))
-        del d_split
+        del s                                              # (the split copy: freed in front of the next)
     plain, filtered = torch.stack(totals).tolist()
     _raise_on_status(d_status, "split_delta_batch")
-    return [first_packet[b + 1] > first_packet[b] and filtered[b] + (first_packet[b + 1] - first_packet[b]) <= plain[b] for b in range(n)]
+    return [_pays(first_packet, b, filtered[b], plain[b]) for b in range(n)]
+
+
+def _pays(first_packet, b, est_with, est_without):
+    """The rule of delta="auto", delta="survey" and base_auto for buffer b: est_with + its packets <= est_without, and it has packets."""
+    packets = first_packet[b + 1] - first_packet[b]
+    return packets > 0 and est_with + packets <= est_without
 
 
 def _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status):
@@ -708,75 +746,97 @@ def _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stre
         return [False] * n, None, None
     halves, estimates, totals = [], [], []
     for with_bases in (None, bases):
-        halves.append(_split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, None, with_bases))
-        d_ptrs, d_bytes, d_fp, d_coded = halves[-1][:4]
-        estimates.append(H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)[:n_packets].to(torch.int64))
-        buf, _ptr, _len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+        s = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, None, with_bases)
+        halves.append(s)
+        estimates.append(H.estimate_batch(s.d_coded, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)[:n_packets].to(torch.int64))
+        buf, _ptr, _len = _packets(s.d_coded, s.d_bytes, s.d_fp, n, n_packets)
         totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, estimates[-1]))
     plain, xored = torch.stack(totals).tolist()
     _raise_on_status(d_status, "split_xor_batch")
-    keep = [bool(bases[b]) and first_packet[b + 1] > first_packet[b] and xored[b] + (first_packet[b + 1] - first_packet[b]) <= plain[b]
-            for b in range(n)]
+    keep = [bool(bases[b]) and _pays(first_packet, b, xored[b], plain[b]) for b in range(n)]
     (d_keep,), pinned = _upload(device, [int(k) for k in keep])
     d_keep = d_keep != 0
-    d_coded = torch.where(d_keep, halves[1][3], halves[0][3])
+    without, with_ = halves
+    d_coded = torch.where(d_keep, with_.d_coded, without.d_coded)
     d_est = torch.where(d_keep[buf], estimates[1], estimates[0])
-    return keep, (d_ptrs, d_bytes, d_fp, d_coded, (halves[0][4], halves[1][4]), (halves[0][5], halves[1][5], pinned)), d_est
+    return keep, _Split(s.d_ptrs, s.d_bytes, s.d_fp, d_coded, (without.d_split, with_.d_split), (without.keep, with_.keep, pinned)), d_est
 
 
-def _check_base(tensors, delta, base, base_auto):
-    """What compress and estimate refuse of `base` and `base_auto`, before anything is launched: a base together with `delta`,
-    base_auto without a base, and whatever base_pointers refuses."""
+class _Batch(NamedTuple):
+    """What _arguments makes of a call's tensors and keywords: describe's five, the width per buffer (None: no planes, filter or base),
+    the filter flags (None, one bool per buffer, or "auto" / "survey" for _prepare to resolve) and the base pointers (None: no base).
+    Behind _prepare also the _Split, the per-packet estimates of the bytes to code where _auto_base made them already (else None) and
+    the status word of every launch so far."""
+    device: object
+    ptrs: list
+    sizes: list
+    first_packet: list
+    n_packets: int
+    widths: list
+    flags: object
+    bases: list
+    split: _Split = None
+    d_est: object = None
+    d_status: object = None
+
+
+def _arguments(tensors, planes, stored, delta, base, base_auto, stream) -> _Batch:
+    """The host step compress and estimate share: what both refuse of base, tensors, planes and delta, in this order and before any
+    launch -- base_auto without a base, a base beside `delta`, whatever base_pointers, describe, plane_widths and delta_flags refuse --,
+    and planes="survey" resolved: the one step here that launches, on `stream`, with a `stored` that no caller takes refused in front
+    of it.  A filter or a base without `planes` works on bytes (width 1)."""
+    import torch
     if base is None and base_auto:
         raise GpuarError("base_auto=True needs base=[...]")
     if base is not None and delta is not None:
         raise GpuarError("base together with delta: that combination is not built (DESIGN.md 4.10)")
-    base_pointers(tensors, base)
-
-
-def _base_arguments(tensors, widths, base):
-    """(widths, base pointers or None) for compress and estimate: a base without `planes` works on bytes."""
-    if base is None:
-        return widths, None
     bases = base_pointers(tensors, base)
-    return (widths if widths is not None else [1] * len(bases)), bases
-
-
-def _filter_arguments(tensors, planes, delta):
-    """(widths, flags or "auto" or "survey" or None) for compress and estimate: a filter without `planes` works on bytes."""
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if _is(planes, "survey"):
+        stored = _stored_argument(stored, n_packets)
+        with _on(stream):
+            if _is(delta, "survey"):
+                planes, delta = survey_choice(tensors, stored)
+            else:
+                planes = survey_widths(tensors, stored)
     widths = plane_widths(tensors, planes)
-    if delta is None:
-        return widths, None
-    if widths is None:
+    if widths is None and (delta is not None or bases is not None):
         widths = [1] * len(tensors)
-    if isinstance(delta, str) and delta in ("auto", "survey"):
-        return widths, delta
-    return widths, delta_flags(tensors, delta)
+    flags = delta if isinstance(delta, str) and delta in ("auto", "survey") else delta_flags(tensors, delta)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return _Batch(device, ptrs, sizes, first_packet, n_packets, widths, flags, bases)
+
+
+def _prepare(a: _Batch, base_auto, stream) -> _Batch:
+    """The device step compress and estimate share, on the current stream (`stream`, where the caller is in its context): `a` with
+    delta="auto" / "survey" and base_auto resolved by measurement (flags, bases: lists or None) and with the batch split -- by
+    _auto_base where that has split it both ways, else by one _split."""
+    import torch
+    d_status = torch.zeros(1, dtype=torch.int32, device=a.device)
+    flags, bases, split, d_est = a.flags, a.bases, None, None
+    if flags == "auto":
+        flags = _auto_delta(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status)
+    elif flags == "survey":
+        flags = _survey_delta_flags(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, d_status)
+    if bases is not None and base_auto:
+        choice, split, d_est = _auto_base(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, bases, stream, d_status)
+        bases = [q if keep else 0 for q, keep in zip(bases, choice)]
+    if split is None:
+        split = _split(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status, flags, bases)
+    return a._replace(flags=flags, bases=bases, split=split, d_est=d_est, d_status=d_status)
 
 
 def survey(tensors, stored=None) -> list:
     """What every tensor would compress to at each byte-plane width, without splitting or encoding anything: per tensor the four
     predicted totals [T1, T2, T4, T8], T_w = estimate([t], planes=w, stored=stored)[0].  One hip.survey_planes_batch launch over
     the original bytes and one synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
-    import torch
-    if stored is not None and stored != "auto":
-        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
-    tensors = list(tensors)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
-    n = len(sizes)
+    stored = _stored_auto(stored)
+    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
     if n_packets == 0:
-        return [[0] * len(H.SURVEY_WIDTHS) for _ in range(n)]
-    d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
-    d_est = H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
-    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
-    if stored == "auto":
-        d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
-    totals = torch.zeros((len(H.SURVEY_WIDTHS), n), dtype=torch.int64, device=device).index_add_(1, buf, d_est)
-    *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
-    if flags:
-        _raise_on_status(d_status, "survey_planes_batch")
-    return [flat[4 * b:4 * b + 4] for b in range(n)]
+        return [[0] * len(H.SURVEY_WIDTHS) for _ in sizes]
+    plain, _filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, True, None, "survey_planes_batch")
+    return plain
 
 
 def survey_widths(tensors, stored=None) -> list:
@@ -784,15 +844,18 @@ def survey_widths(tensors, stored=None) -> list:
     tensors = list(tensors)
     _device, _ptrs, _sizes, first_packet, _np = describe(tensors)
     return [H.choose_planes(totals, first_packet[b + 1] - first_packet[b])
-            for b, totals in enumerate(survey(tensors, stored="auto" if isinstance(stored, str) and stored == "auto" else None))]
+            for b, totals in enumerate(survey(tensors, stored="auto" if _is(stored, "auto") else None))]
 
 
-def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, widths, d_status):
+def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, widths, what, d_status=None):
     """Per buffer the four totals of the plane survey (if `plain`) and of the delta survey at `widths` (if not None; a width
     that was not asked for: 0): one hip.survey_planes_batch launch, one hip.survey_delta_batch launch, one synchronisation, on the
-    current stream.  stored="auto" counts a packet that would be kept raw as its own bytes.  Raises on any status bit."""
+    current stream.  stored="auto" (any other value: as None) counts a packet that would be kept raw as its own bytes.  Raises on any
+    status bit, naming `what`; d_status: the caller's status word, where it has one."""
     import torch
     n = len(sizes)
+    if d_status is None:
+        d_status = torch.zeros(1, dtype=torch.int32, device=device)
     (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
     rows = []
     if plain:
@@ -800,14 +863,14 @@ def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, 
     if widths is not None:
         d_est = torch.zeros((len(H.SURVEY_WIDTHS), n_packets), dtype=torch.int32, device=device)
         rows.append(H.survey_delta_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_est=d_est, d_status=d_status, device=device, widths=widths))
-    d_est = torch.cat(rows).to(torch.int64)
+    d_est = (rows[0] if len(rows) == 1 else torch.cat(rows)).to(torch.int64)
     buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
-    if stored == "auto":
+    if _is(stored, "auto"):
         d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
     totals = torch.zeros((d_est.shape[0], n), dtype=torch.int64, device=device).index_add_(1, buf, d_est)
     *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
     if flags:
-        _raise_on_status(d_status, "survey_delta_batch")
+        _raise_on_status(d_status, what)
     per = len(flat) // n
     both = [[flat[per * b + 4 * k:per * b + 4 * k + 4] for b in range(n)] for k in range(per // 4)]
     return (both[0] if plain else None), (both[-1] if widths is not None else None)
@@ -818,17 +881,13 @@ def survey_delta(tensors, stored=None, widths=None) -> list:
     encoding anything: per tensor [D1, D2, D4, D8], D_w = estimate([t], planes=w, delta=True, stored=stored)[0], with None where
     `widths` (default: all four) does not ask for w.  One hip.survey_delta_batch launch over the original bytes and one
     synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
-    import torch
-    if stored is not None and stored != "auto":
-        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    stored = _stored_auto(stored)
     widths = tuple(H.SURVEY_WIDTHS if widths is None else widths)
     H.widths_mask(widths)
-    tensors = list(tensors)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
     if n_packets == 0:
         return [[0 if w in widths else None for w in H.SURVEY_WIDTHS] for _ in sizes]
-    d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    _plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, False, widths, d_status)
+    _plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, False, widths, "survey_delta_batch")
     return [[t if w in widths else None for w, t in zip(H.SURVEY_WIDTHS, row)] for row in filtered]
 
 
@@ -842,23 +901,18 @@ def _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_
     if any(w not in H.SURVEY_WIDTHS for w in widths):
         raise GpuarError(f"delta=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(widths) - set(H.SURVEY_WIDTHS))}")
     used = sorted({w for w, size in zip(widths, sizes) if size})
-    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, None, True, used, d_status)
+    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, None, True, used, "survey_delta_batch", d_status)
     rows = [H.SURVEY_WIDTHS.index(w) for w in widths]
-    return [first_packet[b + 1] > first_packet[b] and filtered[b][j] + (first_packet[b + 1] - first_packet[b]) <= plain[b][j]
-            for b, j in enumerate(rows)]
+    return [_pays(first_packet, b, filtered[b][j], plain[b][j]) for b, j in enumerate(rows)]
 
 
 def survey_choice(tensors, stored=None):
     """planes="survey" with delta="survey": per tensor the (width, filter) hip.choose_filter picks from both surveys of its bytes
     (an empty tensor: (1, False)), as (widths, flags).  Two launches and one synchronisation."""
-    import torch
-    tensors = list(tensors)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
     if n_packets == 0:
         return [1] * len(sizes), [False] * len(sizes)
-    d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, "auto" if isinstance(stored, str) and stored == "auto" else None,
-                                     True, H.SURVEY_WIDTHS, d_status)
+    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, True, H.SURVEY_WIDTHS, "survey_delta_batch")
     choices = [H.choose_filter(plain[b], filtered[b], first_packet[b + 1] - first_packet[b]) for b in range(len(sizes))]
     return [w for w, _f in choices], [f for _w, f in choices]
 
@@ -873,33 +927,14 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     _auto_base's two split and two estimate launches alone).  `sparse`: None | "auto": as compress -- one hip.sparse_scan_batch
     launch more, and a packet that would be kept sparse counts as its record's bytes."""
     import torch
-    if stored is not None and stored != "auto":
-        raise GpuarError(f"stored={stored!r}: None or \"auto\"")
+    stored = _stored_auto(stored)                                # (no list of stored packets: compress alone takes one)
     sparse = _sparse_argument(sparse, stored)
-    tensors = list(tensors)
-    _check_base(tensors, delta, base, base_auto)
-    if isinstance(planes, str) and planes == "survey":
-        if isinstance(delta, str) and delta == "survey":
-            planes, delta = survey_choice(tensors, stored)
-        else:
-            planes = survey_widths(tensors, stored)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
-    widths, flags = _filter_arguments(tensors, planes, delta)
-    widths, bases = _base_arguments(tensors, widths, base)
-    n = len(sizes)
+    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, None)
+    device, n, n_packets = a.device, len(a.sizes), a.n_packets
     if n_packets == 0:
         return [0] * n
-    d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    if flags == "auto":
-        flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status)
-    elif flags == "survey":
-        flags = _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status)
-    chosen = d_est = None
-    if bases is not None and base_auto:
-        _choice, chosen, d_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, None, d_status)
-    if chosen is None:
-        chosen = _split(device, ptrs, sizes, first_packet, n_packets, widths, None, d_status, flags, bases)
-    d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = chosen
+    a = _prepare(a, base_auto, None)
+    d_status, d_est, d_coded, d_bytes, d_fp = a.d_status, a.d_est, a.split.d_coded, a.split.d_bytes, a.split.d_fp
     if d_est is None:
         d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
     buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
@@ -944,37 +979,14 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.  See
     Compressed."""
     import torch
-    tensors = list(tensors)
-    _check_base(tensors, delta, base, base_auto)                 # (raises before the survey's launch)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
-    if isinstance(planes, str) and planes == "survey":
-        stored = _stored_argument(stored, n_packets)
-        with torch.cuda.stream(stream) if stream is not None else _nothing():
-            if isinstance(delta, str) and delta == "survey":
-                planes, delta = survey_choice(tensors, stored)
-            else:
-                planes = survey_widths(tensors, stored)
-    widths, flags = _filter_arguments(tensors, planes, delta)
-    widths, bases = _base_arguments(tensors, widths, base)
-    stored = _stored_argument(stored, n_packets)
+    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, stream)
+    device, n, n_packets = a.device, len(a.sizes), a.n_packets
+    stored = _stored_argument(stored, n_packets)                 # (a list of stored packets too: estimate takes none)
     sparse = _sparse_argument(sparse, stored)
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    n = len(sizes)
     d_stored = d_raw = d_raw_offsets = d_sparse = d_sparse_offsets = None
-    with torch.cuda.stream(stream) if stream is not None else _nothing():
-        d_status = torch.zeros(1, dtype=torch.int32, device=device)
-        if flags == "auto":
-            flags = _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status)
-        elif flags == "survey":
-            flags = _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status)
-        chosen = d_chosen_est = None
-        if bases is not None and base_auto:
-            choice, chosen, d_chosen_est = _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status)
-            bases = [q if keep else 0 for q, keep in zip(bases, choice)]
-        if chosen is None:
-            chosen = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags, bases)
-        d_ptrs, d_bytes, d_fp, d_coded, d_split, _keep = chosen
+    with _on(stream):
+        a = _prepare(a, base_auto, stream)
+        d_status, d_ptrs, d_bytes, d_fp, d_coded = a.d_status, a.split.d_ptrs, a.split.d_bytes, a.split.d_fp, a.split.d_coded
         if stored is None and sparse is None:
             d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
             d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
@@ -983,7 +995,7 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
             _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
             d_slen = None
             if stored == "auto" or sparse == "auto":
-                d_est = d_chosen_est if d_chosen_est is not None else \
+                d_est = a.d_est if a.d_est is not None else \
                     H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
             if sparse == "auto":
                 d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
@@ -995,19 +1007,18 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
             d_len16 = (d_pkt_len + 15) // 16 * 16
             n_stored, raw_bytes, coded, kept, n_sparse, sparse_bytes, packed = _partition(d_flags, d_len16, d_slen)
             n_coded = n_packets - n_stored - n_sparse
-            d_slots = None
             d_stream, d_offsets = torch.empty(0, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int64, device=device)
             if n_coded:
                 d_slots = H.encode_batch(d_pkt_ptr[coded], d_pkt_len[coded], _unit_first_packet(n_coded, device), n_coded, n_coded, stream=stream,
                                          d_status=d_status, mode=mode, device=device)
                 d_stream, d_offsets = H.compact(d_slots, n_coded, stream=stream)
             d_raw = torch.zeros(raw_bytes, dtype=torch.uint8, device=device)           # (zeros: the pads behind partial packets)
-            d_raw_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(d_len16[kept], 0)])
+            d_raw_offsets = _offsets(d_len16[kept])
             if n_stored:
                 H.move_packets(d_pkt_ptr[kept], d_raw.data_ptr() + d_raw_offsets[:n_stored], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
             if sparse == "auto":
                 d_sparse = torch.empty(sparse_bytes, dtype=torch.uint8, device=device)         # (sparse_pack writes every byte, the pads too)
-                d_sparse_offsets = torch.cat([torch.zeros(1, dtype=torch.int64, device=device), torch.cumsum(d_slen[packed], 0)])
+                d_sparse_offsets = _offsets(d_slen[packed])
                 if n_sparse:
                     H.sparse_pack(d_pkt_ptr[packed], d_pkt_len[packed], d_scan[:n_packets][packed], d_sparse.data_ptr() + d_sparse_offsets[:n_sparse],
                                   n_sparse, stream=stream, d_status=d_status)
@@ -1018,10 +1029,10 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
         # result takes what it compressed to, not ~1.06 x the input
         used = int(d_offsets[-1].item())
         d_stream = d_stream[:used].clone()
-        del d_slots, d_split
-    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=first_packet, sizes=sizes,
-                      crc32=d_crc[:n_packets] if d_crc is not None else None, planes=widths, stored=d_stored, raw=d_raw,
-                      raw_offsets=d_raw_offsets, delta=flags, based=[bool(q) for q in bases] if bases is not None else None,
+    # (the slots and the split copies were held until here; they are freed on return)
+    return Compressed(stream=d_stream, offsets=d_offsets, first_packet=a.first_packet, sizes=a.sizes,
+                      crc32=d_crc[:n_packets] if d_crc is not None else None, planes=a.widths, stored=d_stored, raw=d_raw,
+                      raw_offsets=d_raw_offsets, delta=a.flags, based=[bool(q) for q in a.bases] if a.bases is not None else None,
                       sparse=d_sparse, sparse_offsets=d_sparse_offsets,
                       kinds_rule=(stored == "auto", sparse == "auto") if isinstance(stored, str) or sparse == "auto" else None)
 
@@ -1064,18 +1075,12 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
                 continue
             if t is None:
                 raise GpuarError(f"buffer {b} was compressed against a base: base[{b}] is missing")
-            if hasattr(t, "device") and t.device != device:
-                raise GpuarError(f"base[{b}] is on {t.device}, the batch on {device}")
-            have = _tensor_bytes(t, f"base[{b}]")
-            if have != need:
-                raise GpuarError(f"base[{b}] holds {have} bytes, buffer {b} has {need}: a base has exactly its buffer's bytes")
-            if t.data_ptr() % 16:
-                raise GpuarError(f"base[{b}] is not 16-byte aligned (data_ptr() % 16 = {t.data_ptr() % 16}); pass an aligned copy")
-            before = bisect.bisect_left(starts, t.data_ptr() + need)           # the outputs that start in front of the base's end
-            if before and reach[before - 1][0] > t.data_ptr():
+            at = _base_pointer(t, b, device, "the batch", lambda: need, f"buffer {b} has", "buffer")
+            before = bisect.bisect_left(starts, at + need)                     # the outputs that start in front of the base's end
+            if before and reach[before - 1][0] > at:
                 raise GpuarError(f"base[{b}] overlaps out[{reach[before - 1][1]}]: the merge runs in place in `out` while the bases are read")
-            bases.append(t.data_ptr())
-    with torch.cuda.stream(stream) if stream is not None else _nothing():
+            bases.append(at)
+    with _on(stream):
         (d_ptrs, d_room, d_fp, d_sizes), _keep = _upload(device, ptrs, room, c.first_packet, c.sizes)
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if c.stored is None:
@@ -1087,8 +1092,7 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
             n_coded = c.offsets.numel() - 1
             n_sparse = c.sparse_offsets.numel() - 1 if c.sparse_offsets is not None else 0
             n_stored = c.n_packets - n_coded - n_sparse
-            order = torch.argsort(c.stored, stable=True)
-            coded, kept, packed = order[:n_coded], order[n_coded:n_coded + n_stored], order[n_coded + n_stored:]
+            coded, kept, packed = _by_kind(c.stored, n_coded, n_stored)
             if n_coded:
                 H.decode_stream_batch(c.stream, c.offsets, _unit_first_packet(n_coded, device), n_coded, n_coded, d_pkt_ptr[coded], d_pkt_len[coded],
                                       stream=stream, d_status=d_status)
@@ -1098,18 +1102,12 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
                 H.sparse_unpack(c.sparse.data_ptr() + c.sparse_offsets[:n_sparse], c.sparse_offsets[1:] - c.sparse_offsets[:n_sparse], d_pkt_ptr[packed],
                                 d_pkt_len[packed], n_sparse, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
-        if bases is not None and any(bases) and c.n_packets:
-            (d_elem, d_base), _keep2 = _upload(device, c.planes, bases)
-            H.merge_xor_batch(d_ptrs, d_sizes, d_fp, d_elem, d_base, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
-            _raise_on_status(d_status, "merge_xor_batch")
-        elif c.delta is not None and any(c.delta) and c.n_packets:
-            (d_elem, d_filter), _keep2 = _upload(device, c.planes, [int(f) for f in c.delta])
-            H.merge_delta_batch(d_ptrs, d_sizes, d_fp, d_elem, d_filter, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
-            _raise_on_status(d_status, "merge_delta_batch")
-        elif c.planes is not None and any(w != 1 for w in c.planes) and c.n_packets:
-            (d_elem,), _keep2 = _upload(device, c.planes)
-            H.merge_planes_batch(d_ptrs, d_sizes, d_fp, d_elem, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
-            _raise_on_status(d_status, "merge_planes_batch")
+        found = _filter(c.planes, c.delta, bases) if c.n_packets else None
+        if found is not None:
+            _split_name, merge, extra = found
+            (d_elem, *d_extra), _keep2 = _upload(device, c.planes, *extra)
+            getattr(H, merge)(d_ptrs, d_sizes, d_fp, d_elem, *d_extra, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
+            _raise_on_status(d_status, merge)
         if c.crc32 is not None and verify and c.n_packets:
             d_first_bad = torch.full((1,), -1, dtype=torch.int64, device=device)
             H.verify_crc32_batch(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets, c.crc32, d_first_bad, stream=stream, d_status=d_status)

@@ -353,7 +353,8 @@ class _FakeLaunches:
     def split(self, device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None, bases=None):
         other = int(bool((flags is not None and any(flags)) or (bases is not None and any(bases))))
         d_coded = _i64([2 * b + other for b in range(len(sizes))])               # (which copy: the estimate below looks at it)
-        return _i64(ptrs), _i64(sizes), _i64(first_packet), d_coded, None, None
+        from gpuar_amd import batch
+        return batch._Split(_i64(ptrs), _i64(sizes), _i64(first_packet), d_coded, None, None)
 
     def estimate_batch(self, d_coded, d_bytes, d_fp, n, n_packets, stream=None, d_status=None, device=None):
         import torch

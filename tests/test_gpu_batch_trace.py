@@ -1,0 +1,189 @@
+"""The sequence of launches, staged uploads and synchronising reads that batch.py makes, pinned for every one of the 175 valid option
+combinations of tests/test_gpu_batch_matrix.py: the speed of that layer is this sequence, so a change of batch.py that keeps it keeps
+the speed, and one that adds a launch, a pinned upload or a wait shows up here and not in a timing.
+
+On the batch of 14 tensors of tests/batch_model.py (test_gpu_batch_matrix's Uploaded; no new inputs), with checksum, stream and mode
+as ROTATION gives them, the test records what is called inside
+    compress
+    estimate                          (not for a list of stored packets, which estimate does not take)
+    decompress(verify=True)
+    from_gip of the buffers' gip(b, kinds=...) files, where every buffer has a file (kinds: where the kinds came from the rule)
+in order: every call of a function of batch.H that takes a stream -- the ones that launch or copy -- as its name and its n_buffers /
+n_packets / n_regions; every torch.Tensor.item, .tolist and .cpu on a CUDA tensor (the synchronising reads); every
+torch.Tensor.pin_memory (the staged uploads).  What the test itself calls between those four is not recorded.
+
+The expected traces are tests/golden/batch_call_trace.json, every distinct trace once with the (combination, call) pairs that have it.
+The file was written by this module run as a script,
+    python tests/test_gpu_batch_trace.py --write
+against the batch.py of the commit in front of the one that made batch.py one split, one upload, one partition and one prepare step:
+it is the record of that commit's behaviour and is never rewritten from later code (its first key says so).
+
+The recording runs in a process of its own (this module as a script, --record FILE) and the test compares what it wrote: a process
+that has wrapped torch.Tensor's methods, uploaded the batch a second time and driven 610 calls over one more stream leaves the
+streams of the pool in another state than it found them, and the stream-order tests of tests/test_gpu_packet_forms_concurrency.py,
+which run later in the same pytest process, then find their control launch serialised behind their producer.  The child starts,
+imports torch and records in about 5 s."""
+import contextlib
+import inspect
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from test_gpu_batch_matrix import ROTATION, VALID, Uploaded  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "batch_call_trace.json")
+WRITTEN_FROM = ("the batch.py of the commit in front of 'batch.py: one split, one upload, one partition, one prepare step' "
+                "(python tests/test_gpu_batch_trace.py --write); never from later code")
+COUNTS = ("n_buffers", "n_packets", "n_regions")
+READS = ("item", "tolist", "cpu")
+
+
+class Recorder:
+    """the calls made while `during` is open, in order"""
+
+    def __init__(self):
+        self.trace = None
+
+    @contextlib.contextmanager
+    def during(self):
+        self.trace = []
+        try:
+            yield self.trace
+        finally:
+            self.trace = None
+
+    def launch(self, name, fn):
+        signature = inspect.signature(fn)
+
+        def wrapped(*args, **kwargs):
+            if self.trace is not None:
+                given = signature.bind(*args, **kwargs).arguments
+                self.trace.append(" ".join([name] + [str(int(given[k])) for k in COUNTS if k in given]))
+            return fn(*args, **kwargs)
+        return wrapped
+
+    def method(self, name, fn, cuda_only):
+        def wrapped(tensor, *args, **kwargs):
+            if self.trace is not None and (tensor.is_cuda or not cuda_only):
+                self.trace.append("." + name)
+            return fn(tensor, *args, **kwargs)
+        return wrapped
+
+
+def install(monkeypatch, batch):
+    """every function of batch.H that takes a stream, and the four tensor methods, wrapped until `monkeypatch` undoes it"""
+    rec = Recorder()
+    for name, fn in sorted(vars(batch.H).items()):
+        if inspect.isfunction(fn) and not name.startswith("_") and "stream" in inspect.signature(fn).parameters:
+            monkeypatch.setattr(batch.H, name, rec.launch(name, fn))
+    for name in READS:
+        monkeypatch.setattr(torch.Tensor, name, rec.method(name, getattr(torch.Tensor, name), True))
+    monkeypatch.setattr(torch.Tensor, "pin_memory", rec.method("pin_memory", torch.Tensor.pin_memory, False))
+    return rec
+
+
+def traces_of(batch, rec, T, combo):
+    """{call: trace} of one combination"""
+    checksum, side, mode, _caller_first = ROTATION[combo]
+    stream = T.side if side else None
+    kw = T.keywords(combo)
+    out = {}
+    with rec.during() as trace:
+        c = batch.compress(T.tensors, mode=mode, stream=stream, checksum=checksum, **kw)
+    out["compress"] = trace
+    if stream is not None:
+        stream.synchronize()
+    if combo[2] != "list":
+        with rec.during() as trace:
+            batch.estimate(T.tensors, **kw)
+        out["estimate"] = trace
+    with rec.during() as trace:
+        batch.decompress(c, stream=stream, verify=True, base=T.bases if "base" in kw else None)
+    out["decompress"] = trace
+    if stream is not None:
+        stream.synchronize()
+    try:
+        files = [c.gip(b, kinds=c.kinds_rule is not None) for b in range(c.n_buffers)]
+    except batch.GpuarError:
+        files = None                                           # (a list of stored packets, or a base without the CRCs)
+    if files is not None:
+        with rec.during() as trace:
+            batch.from_gip(files, stream=stream)
+        out["from_gip"] = trace
+        if stream is not None:
+            stream.synchronize()
+    return out
+
+
+def all_traces(monkeypatch):
+    """{"planes-filter-stored-sparse:call": trace} over the 175 combinations"""
+    from gpuar_amd import batch
+    batch.H.load()
+    T = Uploaded()
+    rec = install(monkeypatch, batch)
+    got = {}
+    for combo in VALID:
+        for call, trace in traces_of(batch, rec, T, combo).items():
+            got["-".join(combo) + ":" + call] = trace
+    T.unchanged()
+    assert batch.H.status() == 0
+    return got
+
+
+def grouped(got):
+    """every distinct trace once, with the calls that have it"""
+    by_trace = {}
+    for key, trace in got.items():
+        by_trace.setdefault(";".join(trace), []).append(key)
+    return [{"calls": keys, "trace": trace} for trace, keys in sorted(by_trace.items(), key=lambda kv: kv[1][0])]
+
+
+def test_every_combination_makes_the_recorded_launches_uploads_and_reads(tmp_path):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    with open(GOLDEN) as f:
+        golden = json.load(f)
+    assert list(golden)[0] == "written from" and golden["written from"] == WRITTEN_FROM
+    want = {key: entry["trace"].split(";") if entry["trace"] else [] for entry in golden["traces"] for key in entry["calls"]}
+    assert len(want) == sum(len(entry["calls"]) for entry in golden["traces"])
+    assert len({key.split(":")[0] for key in want}) == len(VALID) == 175
+    recorded = tmp_path / "traces.json"
+    child = subprocess.run([sys.executable, os.path.abspath(__file__), "--record", str(recorded)], capture_output=True, text=True, timeout=300)
+    assert child.returncode == 0, (child.returncode, child.stdout[-2000:], child.stderr[-4000:])
+    with open(recorded) as f:
+        got = json.load(f)
+    assert sorted(got) == sorted(want)
+    for key in want:
+        assert got[key] == want[key], key
+    # the recording is not vacuous: every kind of event is there; estimate for all but the 35 combinations with a stored list; a file
+    # of every buffer for all but those 35 and the 20 of the other 140 that have a base and, by the rotation, no CRCs
+    events = {e.split()[0] for trace in got.values() for e in trace}
+    assert {".item", ".tolist", ".pin_memory", "encode_batch", "decode_stream_batch", "move_bytes", "estimate_batch"} <= events
+    assert sum(key.endswith(":estimate") for key in got) == 140 and sum(key.endswith(":from_gip") for key in got) == 120
+
+
+if __name__ == "__main__":
+    if sys.argv[1:] != ["--write"] and not (len(sys.argv) == 3 and sys.argv[1] == "--record"):
+        sys.exit("usage: python tests/test_gpu_batch_trace.py --record FILE   (what the test compares), or --write   (the golden file, "
+                 "against the commit it records; see the docstring)")
+    with pytest.MonkeyPatch.context() as patch:
+        traces = all_traces(patch)
+    if sys.argv[1] == "--record":
+        with open(sys.argv[2], "w") as f:
+            json.dump(traces, f)
+    else:
+        with open(GOLDEN, "w") as f:
+            json.dump({"written from": WRITTEN_FROM, "traces": grouped(traces)}, f, separators=(",", ":"))
+            f.write("\n")
+        print(f"{GOLDEN}: {len(traces)} calls, {len({';'.join(t) for t in traces.values()})} distinct traces, {os.path.getsize(GOLDEN)} bytes")
