@@ -873,6 +873,8 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
         for (uint64_t at = 0; at < info.uncompressedFileSize; at += rampPackets(chunk_at.size() - 1, chunkPackets) * kPacket) chunk_at.push_back(at);
         const size_t n_chunks = chunk_at.size();
         chunk_at.push_back(info.uncompressedFileSize);
+        for (size_t c = 0; c < n_chunks && c < 8; ++c)      // (GPUAR_TRACE: the ramp, and where the chunks behind it start)
+            trace(("compress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>((chunk_at[c + 1] - chunk_at[c] + kPacket - 1) / kPacket));
         // The latency-mode encode kernel is faster only for a launch that has the chip to itself (include/gpuar_hip.h):
         // a job of one chunk.  With several chunks the lanes of a device keep three launches in flight (the ramped first
         // chunks are small enough for GPUAR_MODE_AUTO to pick the latency kernel), so the pipeline names the kernel itself.
@@ -1106,10 +1108,13 @@ struct ChunkMap {
 // returns the total before chunk c's own n bytes; it is called before the chunk's kernels, so nobody waits for it long.
 class OrderedOffsets {
   public:
-    uint64_t take(size_t chunk, uint64_t bytes) {
+    // `check` runs once it is the chunk's turn; if it throws, the turn is never passed on, and the chunks behind wait until abort()
+    template <typename Check>
+    uint64_t take(size_t chunk, uint64_t bytes, Check &&check) {
         std::unique_lock<std::mutex> hold(lock);
         turn.wait(hold, [&] { return aborted || next == chunk; });
         if (aborted) throw std::runtime_error("pipeline stopped");
+        check();
         const uint64_t mine = total;
         total += bytes;
         ++next;
@@ -1274,6 +1279,7 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                             const size_t c = g + G * next_of_device[g].fetch_add(1);
                             ChunkMap::Chunk chunk;
                             if (failure.stop || !map.get(c, chunk)) break;
+                            if (c < 8) trace(("decompress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>(chunk.n_packets));
                             if (!b.cap) b.allocate(b.device, chunkPackets, false);
                             hip_check(hipSetDevice(b.device), "hipSetDevice");
                             if (verify) b.allocateCrc();
@@ -1304,32 +1310,48 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
                                 if (clen < GPUAR_PACKET_HEADER_BYTES || off + clen > n_stream) throw std::runtime_error("Invalid file length");
                                 const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
                                 all_full = all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
-                                // (byte planes: so every chunk but the last is whole groups, and all_full holds)
-                                if (merging) checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
-                                // (raw and sparse packets: the same, so that packet p of the chunk goes to byte 8192 p of it; a raw
-                                // packet is its header and its bytes)
-                                if (mixed) {
-                                    checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
-                                    if (trailer.kinds[chunk.first_packet + p] == 1 && clen != GPUAR_PACKET_HEADER_BYTES + getPacketUlen(pkt))
-                                        throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
-                                                                 " and " + std::to_string(chunk.end) + ")");
-                                }
                                 produced += ulen;
                                 off += clen;
                             }
                             if (off != n_stream) throw std::runtime_error("Invalid file length");
                             b.h_offsets[chunk.n_packets] = off;
-                            if (mixed && (produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
-                            const uint64_t out_at = place.take(c, produced);
+                            // What the trailer forbids the packets to say of themselves.  Checked in the chunk's turn (place.take), after
+                            // every chunk in front of it has passed: of several such packets in a file the FIRST is the one refused and
+                            // named, as --host does it, whichever lane gets to its chunk first.
+                            const auto refuse = [&] {
+                                for (size_t p = 0; p < chunk.n_packets; ++p) {
+                                    const uint8_t *pkt = bytes + b.h_offsets[p];
+                                    const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
+                                    // (a packet that says it holds more than 8192 bytes is malformed, which the decoder would say
+                                    // too -- but only after a CRC trailer had it called a checksum mismatch below; --host calls it
+                                    // malformed under every trailer)
+                                    if (getPacketUlen(pkt) > kPacket)
+                                        throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
+                                                                 " and " + std::to_string(chunk.end) + ")");
+                                    // (byte planes: so every chunk but the last is whole groups, and all_full holds)
+                                    if (merging) checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
+                                    // (raw and sparse packets: the same, so that packet p of the chunk goes to byte 8192 p of it; a raw
+                                    // packet is its header and its bytes)
+                                    if (mixed) {
+                                        checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
+                                        if (trailer.kinds[chunk.first_packet + p] == 1 &&
+                                            b.h_offsets[p + 1] - b.h_offsets[p] != GPUAR_PACKET_HEADER_BYTES + getPacketUlen(pkt))
+                                            throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
+                                                                     " and " + std::to_string(chunk.end) + ")");
+                                    }
+                                }
+                                if (mixed && (produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
+                                if (verify) {
+                                    // (With this, the chunk's `produced` bytes hold exactly its n_packets packets, and the verify below covers
+                                    // every one of them: a last packet whose ulen had become 0 would otherwise drop out of it.)
+                                    for (size_t p = 0; p < chunk.n_packets; ++p)
+                                        checkChecksumPacket(chunk.first_packet + p, crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
+                                    if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
+                                }
+                            };
+                            const uint64_t out_at = place.take(c, produced, refuse);
                             device_bytes[g] += produced;
                             device_chunks[g] += 1;
-                            if (verify) {
-                                // (With this, the chunk's `produced` bytes hold exactly its n_packets packets, and the verify below covers
-                                // every one of them: a last packet whose ulen had become 0 would otherwise drop out of it.)
-                                for (size_t p = 0; p < chunk.n_packets; ++p)
-                                    checkChecksumPacket(chunk.first_packet + p, crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
-                                if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
-                            }
                             // (every packet in front of this chunk holds 8192 bytes: checkPlanesPacket)
                             if (trailer.based()) b.uploadBase(baseFd, static_cast<uint64_t>(chunk.first_packet) * kPacket, static_cast<size_t>(produced));
                             uint64_t first_bad = 0;
