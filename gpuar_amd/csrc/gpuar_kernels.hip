@@ -2366,7 +2366,7 @@ crc32_kernel(CrcArgs a) {
 // Separate launches, not fused into the codec kernels (their schedules are pinned: DESIGN.md 4.3b).
 // ---------------------------------------------------------------------------
 constexpr uint32_t kPlaneThreads = kPlanePacket / kPlaneBlock;        // 512: a block of 16 elements per thread
-constexpr uint32_t kPlaneGridCap = 1u << 22;                          // workgroups per launch (they stride over the packets)
+constexpr uint32_t kPlaneGridCap = GPUAR_PLANE_GRID_CAP;              // workgroups per launch (they stride over the packets): planes.h; the launch code alone reads it
 
 struct PlanesArgs {
     const uint8_t *in;                      // one buffer: `in`, `out`, `n_bytes`, `elem` ...

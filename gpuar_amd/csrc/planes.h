@@ -29,6 +29,12 @@
 #define GPUAR_PLANES_FN inline
 #endif
 
+// The most workgroups a launch of the filter, move and sparse pack / unpack kernels gets (gpuar_kernels.hip: kPlaneGridCap, read by
+// the launch code alone -- the kernels stride over their items by gridDim.x, whatever it is).
+#ifndef GPUAR_PLANE_GRID_CAP                 /* only tests/grid_cap_build.py ever overrides it (to 3: every workgroup strides on, many times) */
+#define GPUAR_PLANE_GRID_CAP (1u << 22)
+#endif
+
 namespace gpuar {
 
 constexpr uint32_t kPlanePacket = 8192;      // bytes per packet: one plane of a full group

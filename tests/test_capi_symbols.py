@@ -119,7 +119,7 @@ def test_the_kernel_sources_hold_one_path_and_no_wrong_output_switch():
     def text(*parts):
         return open(os.path.join(ROOT, *parts)).read()
     conditional = re.compile(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$", re.M)
-    sources = {name: text("gpuar_amd", "csrc", name) for name in ("gpuar_kernels.hip", "lane_codec.h", "crc32.h", "Makefile")}
+    sources = {name: text("gpuar_amd", "csrc", name) for name in ("gpuar_kernels.hip", "lane_codec.h", "crc32.h", "planes.h", "Makefile")}
     sources["exp_build.sh"] = text("tools", "exp_build.sh")
     sources["hip.py"] = text("gpuar_amd", "hip.py")
     assert conditional.findall(sources["gpuar_kernels.hip"]) == []
@@ -130,6 +130,7 @@ def test_the_kernel_sources_hold_one_path_and_no_wrong_output_switch():
     allowed = {
         "lane_codec.h": {"GPUAR_LANE_CODEC_H", "__HIP_DEVICE_COMPILE__", "__HIPCC__", "GPUAR_TOP_DEPTHS", "GPUAR_TOP_D1_REGS"},
         "crc32.h": {"GPUAR_CRC32_H", "__HIP_DEVICE_COMPILE__", "__HIPCC__"},
+        "planes.h": {"GPUAR_PLANES_H", "__HIPCC__", "GPUAR_PLANE_GRID_CAP"},    # the cap: host launch code only (tests/test_grid_cap_host.py)
     }
     for name, names in allowed.items():
         conditions = conditional.findall(sources[name])

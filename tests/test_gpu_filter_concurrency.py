@@ -36,8 +36,8 @@ goes round the chip two to four times and eight of them contend for it).
    move_packets and crc32_batch, the encoder enqueued first or last.
 5. batch.compress / decompress from six threads, each with its own stream and one keyword family.
 
-Not covered: the grid-stride loops of the plane, delta, XOR and move kernels start at 2^22 workgroups (32 GiB, or four million
-buffers) and stay untested; tensors on a device that is not the current one.  Fixed seeds throughout.
+Not covered here: the grid-stride loops of the plane, delta, XOR and move kernels start at 2^22 workgroups (32 GiB, or four million
+buffers); tests/test_gpu_grid_cap.py runs their later passes on a build whose cap is 3.  Tensors on a device that is not the current one.  Fixed seeds throughout.
 """
 import math
 import threading

@@ -44,8 +44,9 @@ Would catch: a launch on the NULL or the current stream (1), a status word share
 fallback word beside the launch's own (2, 3), LDS or register state that survives a wavefront's trip when the chip is shared (2,
 4), torch temporaries of _partition or of from_gip's region lists made on one stream and used on another (5).
 
-Not covered: the region kernels (sparse_pack, sparse_unpack, move_bytes) take a region per wavefront or workgroup and their
-grid-stride loops start at 2^22 workgroups, which stay untested, as the filter module says of move_packets; tensors on a device
+Not covered here: the region kernels (sparse_pack, sparse_unpack, move_bytes) take a region per wavefront or workgroup and their
+grid-stride loops start at 2^22 workgroups; tests/test_gpu_grid_cap.py runs their later passes on a build whose cap is 3, as it
+does for move_packets and the filters.  Tensors on a device
 that is not the current one; from_gip from paths (the files are bytes in memory here).  Fixed seeds throughout.
 
 Time, pytest --durations=0 on an MI355X, the module alone: 11 passed in 3.2 s.  One producer link (a 256 MiB device_copy) ran
