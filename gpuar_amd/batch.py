@@ -47,7 +47,10 @@ With base=[...] (one tensor of the same byte count, or None, per tensor) every t
 split (hip.split_xor_batch: the same single launch, into the same temporary buffer) and XORed back, in place, after it is
 decoded (hip.merge_xor_batch; decompress needs the same bases).  The next checkpoint of a model is almost the previous one:
 against it a bf16 tensor compresses to 0.06-0.72 of what it does alone, against an unrelated base it grows.
-base_auto=True measures and keeps the bases that are predicted to pay (Compressed.based).  The CRCs are those of the original
+base_auto=True measures and keeps the bases that are predicted to pay (Compressed.based); base_auto="survey" keeps the same ones
+from two survey launches over the original bytes (hip.survey_xor_batch: the estimate and the scan word of every packet of the XORed,
+split bytes at the four widths, without making them) and splits once, and with planes="survey" chooses width and base together;
+survey_xor gives those totals to a caller of its own.  The CRCs are those of the original
 bytes, so a wrong base in decompress is a checksum mismatch.  Compressed.gip(b) carries a version-5 trailer
 (`gpuar c --base=FILE --planes=W`) and needs the CRCs.  A base together with `delta` is refused.
 
@@ -778,25 +781,32 @@ class _Batch(NamedTuple):
     split: _Split = None
     d_est: object = None
     d_status: object = None
+    base_chosen: bool = False               # base_auto="survey" was resolved with the widths (planes="survey"): `bases` are the kept ones
 
 
-def _arguments(tensors, planes, stored, delta, base, base_auto, stream) -> _Batch:
+def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=None) -> _Batch:
     """The host step compress and estimate share: what both refuse of base, tensors, planes and delta, in this order and before any
     launch -- base_auto without a base, a base beside `delta`, whatever base_pointers, describe, plane_widths and delta_flags refuse --,
     and planes="survey" resolved: the one step here that launches, on `stream`, with a `stored` that no caller takes refused in front
-    of it.  A filter or a base without `planes` works on bytes (width 1)."""
+    of it.  A filter or a base without `planes` works on bytes (width 1).  With base_auto="survey" the same step chooses width and
+    base together (survey_base_choice; `sparse` is what its totals count)."""
     import torch
     if base is None and base_auto:
         raise GpuarError("base_auto=True needs base=[...]")
+    if isinstance(base_auto, str) and base_auto != "survey":
+        raise GpuarError(f"base_auto={base_auto!r}: False, True or \"survey\"")
     if base is not None and delta is not None:
         raise GpuarError("base together with delta: that combination is not built (DESIGN.md 4.10)")
-    bases = base_pointers(tensors, base)
+    bases, base_chosen = base_pointers(tensors, base), False
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
     if _is(planes, "survey"):
         stored = _stored_argument(stored, n_packets)
         with _on(stream):
             if _is(delta, "survey"):
                 planes, delta = survey_choice(tensors, stored)
+            elif _is(base_auto, "survey"):
+                planes, kept = survey_base_choice(tensors, base, stored if _is(stored, "auto") else None, sparse if _is(sparse, "auto") else None)
+                bases, base_chosen = [q if keep else 0 for q, keep in zip(bases, kept)], True
             else:
                 planes = survey_widths(tensors, stored)
     widths = plane_widths(tensors, planes)
@@ -805,7 +815,7 @@ def _arguments(tensors, planes, stored, delta, base, base_auto, stream) -> _Batc
     flags = delta if isinstance(delta, str) and delta in ("auto", "survey") else delta_flags(tensors, delta)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    return _Batch(device, ptrs, sizes, first_packet, n_packets, widths, flags, bases)
+    return _Batch(device, ptrs, sizes, first_packet, n_packets, widths, flags, bases, base_chosen=base_chosen)
 
 
 def _prepare(a: _Batch, base_auto, stream) -> _Batch:
@@ -819,7 +829,11 @@ def _prepare(a: _Batch, base_auto, stream) -> _Batch:
         flags = _auto_delta(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status)
     elif flags == "survey":
         flags = _survey_delta_flags(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, d_status)
-    if bases is not None and base_auto:
+    if bases is not None and _is(base_auto, "survey"):
+        if not a.base_chosen:
+            choice = _survey_base_keep(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, bases, d_status)
+            bases = [q if keep else 0 for q, keep in zip(bases, choice)]
+    elif bases is not None and base_auto:
         choice, split, d_est = _auto_base(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, bases, stream, d_status)
         bases = [q if keep else 0 for q, keep in zip(bases, choice)]
     if split is None:
@@ -867,13 +881,21 @@ def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, 
     buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
     if _is(stored, "auto"):
         d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
-    totals = torch.zeros((d_est.shape[0], n), dtype=torch.int64, device=device).index_add_(1, buf, d_est)
+    both = _totals_per_buffer(d_est, buf, n, d_status, what)
+    return (both[0] if plain else None), (both[-1] if widths is not None else None)
+
+
+def _totals_per_buffer(d_est, buf, n, d_status, what):
+    """The surveys' one synchronisation: d_est (4 k rows of one int64 per batch packet, k surveys one under the other) summed over
+    the packets of each of the n buffers (buf: every packet's buffer), as [survey][buffer][four totals]; raises on any status bit,
+    naming `what`."""
+    import torch
+    totals = torch.zeros((d_est.shape[0], n), dtype=torch.int64, device=d_est.device).index_add_(1, buf, d_est)
     *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
     if flags:
         _raise_on_status(d_status, what)
     per = len(flat) // n
-    both = [[flat[per * b + 4 * k:per * b + 4 * k + 4] for b in range(n)] for k in range(per // 4)]
-    return (both[0] if plain else None), (both[-1] if widths is not None else None)
+    return [[flat[per * b + 4 * k:per * b + 4 * k + 4] for b in range(n)] for k in range(per // 4)]
 
 
 def survey_delta(tensors, stored=None, widths=None) -> list:
@@ -917,6 +939,97 @@ def survey_choice(tensors, stored=None):
     return [w for w, _f in choices], [f for _w, f in choices]
 
 
+def _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, plain, what, d_status=None):
+    """Per buffer the four totals of the XOR survey against `bases` (one pointer per buffer, 0: none) and, if `plain`, the four of
+    the bytes as they are: (plain or None, xored).  One hip.survey_xor_batch launch, for `plain` one launch more -- hip.survey_planes_batch,
+    or, where sparse packets count, the XOR survey with base pointers of 0, which also gives scan words --, one synchronisation, on
+    the current stream.  stored="auto" and sparse="auto" (any other value: as None) count every packet as _kinds' rule would keep
+    it at that width: its record, its own bytes or its estimate.  Raises on any status bit, naming `what`."""
+    import torch
+    n = len(sizes)
+    if d_status is None:
+        d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    count_sparse, stored_on = _is(sparse, "auto"), _is(stored, "auto")
+    (d_ptrs, d_bytes, d_fp, d_bases, d_none), _keep = _upload(device, ptrs, sizes, first_packet, list(bases), [0] * n)
+    want_scan = None if count_sparse else False
+    sides = []
+    if plain and count_sparse:
+        sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_none, n, n_packets, d_status=d_status, device=device))
+    elif plain:
+        sides.append((H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device), None))
+    sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_bases, n, n_packets, d_scan=want_scan, d_status=d_status, device=device))
+    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
+    rows = []
+    for d_est, d_scan in sides:
+        d_est = d_est[:, :n_packets].to(torch.int64)
+        if count_sparse:
+            d_kind, d_slen = _kinds(d_scan[:, :n_packets], d_est, d_len, stored_on)
+            d_est = torch.where(d_kind == H.KIND_SPARSE, d_slen, torch.where(d_kind == H.KIND_RAW, d_len.expand_as(d_est), d_est))
+        elif stored_on:
+            d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
+        rows.append(d_est)
+    both = _totals_per_buffer(torch.cat(rows), buf, n, d_status, what)
+    return (both[0] if plain else None), both[-1]
+
+
+def _survey_xor_arguments(tensors, base, stored, sparse):
+    """What survey_xor and survey_xor_widths refuse, before any launch, and the batch's description with its base pointers"""
+    tensors = list(tensors)
+    stored = _stored_auto(stored)
+    sparse = _sparse_argument(sparse, stored)
+    if base is None:
+        raise GpuarError("survey_xor needs base=[...]")
+    bases = base_pointers(tensors, base)
+    return describe(tensors), bases, stored, sparse
+
+
+def survey_xor(tensors, base, stored=None, sparse=None) -> list:
+    """What every tensor would compress to XORed against its base at each byte-plane width, without XORing, splitting or encoding
+    anything: per tensor [X1, X2, X4, X8], X_w = estimate([t], planes=w, base=[b], stored=stored, sparse=sparse)[0]; a tensor whose
+    base is None gets its plain totals.  One hip.survey_xor_batch launch over the original bytes and the bases, and one
+    synchronisation; _kinds' rule is applied per width on the device, from the survey's est and scan rows."""
+    (device, ptrs, sizes, first_packet, n_packets), bases, stored, sparse = _survey_xor_arguments(tensors, base, stored, sparse)
+    if n_packets == 0:
+        return [[0] * len(H.SURVEY_WIDTHS) for _ in sizes]
+    _plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, False, "survey_xor_batch")
+    return xored
+
+
+def survey_xor_widths(tensors, base, stored=None, sparse=None) -> list:
+    """For a caller who keeps the bases: per tensor the width hip.choose_planes picks from survey_xor's totals -- the width of the
+    bytes that are coded, not of the original ones (an empty tensor: 1)."""
+    tensors = list(tensors)
+    _device, _ptrs, _sizes, first_packet, _np = describe(tensors)
+    return [H.choose_planes(totals, first_packet[b + 1] - first_packet[b]) for b, totals in enumerate(survey_xor(tensors, base, stored, sparse))]
+
+
+def _survey_base_keep(device, ptrs, sizes, first_packet, n_packets, widths, bases, d_status):
+    """base_auto="survey" with the widths fixed: per buffer, whether its base is predicted to pay at the buffer's width -- the
+    decision of _auto_base, est_xor + its packets <= est_plain on coded estimates, from the plane survey and the XOR survey of the
+    original bytes: two launches and one synchronisation, no split and no temporary."""
+    n = len(sizes)
+    if n_packets == 0 or not any(bases):
+        return [False] * n
+    if any(w not in H.SURVEY_WIDTHS for w in widths):
+        raise GpuarError(f"base_auto=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(widths) - set(H.SURVEY_WIDTHS))}")
+    plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, None, None, True, "survey_xor_batch", d_status)
+    rows = [H.SURVEY_WIDTHS.index(w) for w in widths]
+    return [bool(bases[b]) and _pays(first_packet, b, xored[b][j], plain[b][j]) for b, j in enumerate(rows)]
+
+
+def survey_base_choice(tensors, base, stored=None, sparse=None):
+    """planes="survey" with base_auto="survey": per tensor the (width, base kept) hip.choose_filter picks from the totals of its
+    bytes as they are and XORed against its base (an empty tensor or one without a base: its plain width, no base), as (widths,
+    kept).  Two launches and one synchronisation; with sparse="auto" both sides count sparse packets."""
+    (device, ptrs, sizes, first_packet, n_packets), bases, stored, sparse = _survey_xor_arguments(tensors, base, stored, sparse)
+    if n_packets == 0:
+        return [1] * len(sizes), [False] * len(sizes)
+    plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, True, "survey_xor_batch")
+    choices = [H.choose_filter(plain[b], xored[b], first_packet[b + 1] - first_packet[b]) if bases[b] else
+               (H.choose_planes(plain[b], first_packet[b + 1] - first_packet[b]), False) for b in range(len(sizes))]
+    return [w for w, _k in choices], [k for _w, k in choices]
+
+
 def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False, sparse=None) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
@@ -929,7 +1042,7 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     import torch
     stored = _stored_auto(stored)                                # (no list of stored packets: compress alone takes one)
     sparse = _sparse_argument(sparse, stored)
-    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, None)
+    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, None, sparse)
     device, n, n_packets = a.device, len(a.sizes), a.n_packets
     if n_packets == 0:
         return [0] * n
@@ -972,14 +1085,17 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     inputs and bases are never modified).  planes="survey" surveys the original bytes.  `base_auto`: keep only the bases for
     which splitting and estimating the batch both ways predicts a gain (_auto_base: one split and one estimate launch more than
     fixed bases with stored="auto" take, one synchronisation, both split copies kept and none made a third time);
-    Compressed.based says which.  base=None takes exactly the path taken without the keyword.  `sparse`: None | "auto" (with
+    Compressed.based says which.  base_auto="survey" keeps the same bases from one hip.survey_planes_batch and one
+    hip.survey_xor_batch launch over the original bytes and one synchronisation, and then splits once: one temporary of the batch's
+    size instead of two (_survey_base_keep); with planes="survey" it chooses width and base together, on the bytes that would be
+    coded (survey_base_choice), and records both in Compressed.planes and Compressed.based.  base=None takes exactly the path taken without the keyword.  `sparse`: None | "auto" (with
     stored None or "auto"): keep the packets that are one byte value almost everywhere as that byte and a list of exceptions --
     one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one hip.sparse_scan_batch launch
     on the bytes that would be coded, hip.sparse_rule on the device, and the packets go three ways: coded, raw (hip.move_packets)
     and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.  See
     Compressed."""
     import torch
-    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, stream)
+    a = _arguments(list(tensors), planes, stored, delta, base, base_auto, stream, sparse)
     device, n, n_packets = a.device, len(a.sizes), a.n_packets
     stored = _stored_argument(stored, n_packets)                 # (a list of stored packets too: estimate takes none)
     sparse = _sparse_argument(sparse, stored)

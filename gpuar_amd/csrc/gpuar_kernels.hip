@@ -44,6 +44,7 @@
 
 #include "gpuar_hip.h"
 #include "gpuar_hip_gip.h"
+#include "gpuar_hip_xsurvey.h"
 
 #include "lane_codec.h"
 #include "crc32.h"
@@ -53,6 +54,7 @@
 #include "estimate.h"
 #include "survey.h"
 #include "delta_survey.h"
+#include "xor_survey.h"
 #include "sparse.h"
 #include "kinds.h"
 
@@ -4055,6 +4057,243 @@ survey_delta_kernel(DeltaSurveyArgs a) {
     __syncthreads();
     survey_walk(a.s, [&](const uint8_t *sg, uint32_t len, uint64_t first) { dsurvey_supergroup(a, sg, len, first, lds, sums); });
 }
+
+// ---------------------------------------------------------------------------
+// XOR-base survey (xor_survey.h): est[j][p] = estimate(split_xor(buffer, base, 1 << j))[p] and scan[j][p] =
+// sparse_scan(split_xor(buffer, base, 1 << j))[p] for the four widths at once, from one read of the buffer and one of its base and
+// without XORing or splitting anything into memory, for one buffer or a batch.  XOR commutes with the regrouping, so this is the
+// plane survey of buffer ^ base: supergroups, windows, the workgroup, the residue histograms and the sums behind the barrier are
+// survey_planes_kernel's.  Wavefront e loads eighth e of the buffer and of the base, lane l bytes [128 l, 128 l + 128) of each as
+// eight 16-byte loads, XORs them in registers and counts the result with survey_count8: a tensor equal to its base is all zeros,
+// all lanes on one bin, which is what the rotation by (lane & 7) is for.
+// Behind the barrier thread (half, s) forms survey_supergroup's 16 counts of bin s.  The estimates leave through the sum exchange;
+// the scan words through a second reduction of the same shape over 32-bit keys (xor_scan_key: count << 8 | s) by MAXIMUM --
+// a packet's majority byte, if it has one, is its fullest bin -- with an exchange of 8 x 16 words and one writer per entry.
+// A short supergroup takes the general path, with the base read by the same 16-byte pieces and the same two reductions.
+// Either output may be missing (null): its reduction is skipped and nothing of it is written.
+// In a batch a base pointer of 0 means "no base": the buffer's rows are the plane survey's, with scan rows beside them.  A base
+// pointer that is not 16-byte aligned makes its buffer BAD_BATCH, as a misaligned buffer is: none of its entries is written.
+// ---------------------------------------------------------------------------
+struct XorSurveyArgs {
+    SurveyArgs s;                           // s.est may be null
+    const uint8_t *base;                    // one buffer: its base ...
+    const uint8_t *const *bases;            // ... or a batch: one pointer per buffer, 0: no base
+    uint32_t *scan;                         // row j at scan + j * s.stride; may be null
+};
+
+// survey_walk with the base beside the buffer: body(sg, bs, len, first), bs the base's bytes of the supergroup or null.  (A copy,
+// as survey_walk is: the other surveys' code objects stay as they are.)
+template <typename Body>
+__device__ __forceinline__ void xsurvey_walk(const XorSurveyArgs &x, Body body) {
+    const SurveyArgs &a = x.s;
+    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
+    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
+        uint64_t p = 8ull * u;
+        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
+        while (p < end) {                   // (every value here is the same in all threads)
+            const uint8_t *sg = nullptr, *bs = nullptr;
+            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
+            if (!a.ptrs) {                  // one buffer: the window is the supergroup
+                sg = a.in + p * kPacket;
+                bs = x.base + p * kPacket;
+                left = a.n_bytes - p * kPacket;
+            } else {
+                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
+                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
+                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    next = p + 1u;
+                } else {
+                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
+                    const uint8_t *base = x.bases[bl.buffer];
+                    const uint64_t j = p - lead;
+                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
+                    if (!bl.owned || (reinterpret_cast<uintptr_t>(base) & 15u) != 0u || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
+                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
+                        sg = bl.ptr;
+                        bs = base ? base + j * kPacket : nullptr;
+                        left = n_bytes - j * kPacket;
+                    }
+                }
+            }
+            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
+            if (len != 0u) body(sg, bs, len, p);
+            p = next;
+        }
+    }
+}
+
+// one supergroup: `len` bytes (1 .. 65536) at `sg` and, unless null, at `bs` (both 16-byte aligned), whose first packet is entry
+// `first` of every row; the whole workgroup, with the histograms clear on entry and on return
+__device__ __forceinline__ void xsurvey_supergroup(const XorSurveyArgs &x, const uint8_t *sg, const uint8_t *bs, uint32_t len, uint64_t first,
+                                                   CrcQuad *lds, uint64_t (*sums)[16], uint32_t (*keys)[16]) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, eighths / packets 4 half .. + 3
+    const bool full = len == kSurveyBytes, based = bs != nullptr;            // workgroup-uniform
+    if (full) {
+        const uint32_t at = wave * kPacket + kCrcChunk * lane;
+        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + at));
+        CrcQuad q[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
+        if (based) {
+            GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs + at));
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) {
+                const CrcQuad b = bsrc[k];
+                q[k].x ^= b.x, q[k].y ^= b.y, q[k].z ^= b.z, q[k].w ^= b.w;
+            }
+        }
+        const uint32_t c = lane & 7u;
+        uint32_t slot[8];
+#pragma unroll
+        for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            survey_count8(hist, q[k].x, q[k].y, c, slot);
+            survey_count8(hist, q[k].z, q[k].w, c, slot);
+        }
+    } else {
+        // the general path: packet histogram (j, p) at dword (8 j + p) * 256
+        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg));
+        GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs));
+        for (uint32_t i = threadIdx.x; i * 16u < len; i += kSurveyThreads) {
+            const CrcQuad q = src[i];
+            uint32_t w[4] = {q.x, q.y, q.z, q.w};
+            if (based) {
+                const CrcQuad b = bsrc[i];
+                w[0] ^= b.x, w[1] ^= b.y, w[2] ^= b.z, w[3] ^= b.w;
+            }
+#pragma unroll
+            for (uint32_t d = 0; d < 4; ++d) {
+#pragma unroll 1
+                for (uint32_t b = 0; b < 4; ++b) {
+                    const uint32_t o = 16u * i + 4u * d + b, byte = (w[d] >> (8u * b)) & 255u;
+                    if (o >= len) break;
+#pragma unroll
+                    for (uint32_t j = 0; j < kSurveyWidths; ++j)
+                        __hip_atomic_fetch_add(hist + ((j * kSurveyPackets + survey_packet(o, len, j)) * 256u + byte), 1u, __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // cnt[4 j + m]: bin s of packet 4 half + m at width 1 << j
+    uint32_t cnt[16];
+    if (full) {
+        CrcQuad lo[4], hi[4], other[4];      // residues 0-3 and 4-7 of the half's own eighths; residues 4 half .. + 3 of the other half's
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) {
+            lo[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u];
+            hi[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u];
+            other[e] = lds[((4u * (1u - half) + e) * kSurveyEighthDwords + 8u * s) / 4u + half];
+        }
+#pragma unroll
+        for (uint32_t e = 0; e < 4; ++e) cnt[e] = lo[e].x + lo[e].y + lo[e].z + lo[e].w + hi[e].x + hi[e].y + hi[e].z + hi[e].w;
+#pragma unroll
+        for (uint32_t g = 0; g < 2; ++g) {
+            const CrcQuad t = lo[2 * g] + hi[2 * g] + lo[2 * g + 1] + hi[2 * g + 1];
+            cnt[4 + 2 * g] = t.x + t.z;
+            cnt[4 + 2 * g + 1] = t.y + t.w;
+        }
+        const CrcQuad l4 = lo[0] + lo[1] + lo[2] + lo[3], h4 = hi[0] + hi[1] + hi[2] + hi[3];
+        const CrcQuad w4 = l4 + h4, w8 = (half ? h4 : l4) + other[0] + other[1] + other[2] + other[3];
+        cnt[8] = w4.x, cnt[9] = w4.y, cnt[10] = w4.z, cnt[11] = w4.w;
+        cnt[12] = w8.x, cnt[13] = w8.y, cnt[14] = w8.z, cnt[15] = w8.w;
+    } else {
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) cnt[i] = hist[((i >> 2) * kSurveyPackets + 4u * half + (i & 3u)) * 256u + s];
+    }
+    // the scan words: 16 wave maxima of the keys, by survey_supergroup's halving pattern -- every step halves the values a lane
+    // carries, so lane l ends with the whole wavefront's maximum of value l >> 2
+    if (x.scan) {
+        uint32_t key[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) key[i] = xor_scan_key(cnt[i], s);
+#pragma unroll
+        for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
+            const bool upper = (lane & off) != 0u;
+#pragma unroll
+            for (uint32_t m = 0; m < n; ++m) {
+                const uint32_t keep = upper ? key[m + n] : key[m], give = upper ? key[m] : key[m + n];
+                const uint32_t got = __shfl_xor(give, off);
+                key[m] = keep > got ? keep : got;
+            }
+        }
+#pragma unroll
+        for (uint32_t off = 2; off >= 1; off >>= 1) {
+            const uint32_t got = __shfl_xor(key[0], off);
+            key[0] = key[0] > got ? key[0] : got;
+        }
+        if ((lane & 3u) == 0u) keys[wave][lane >> 2] = key[0];
+    }
+    // the estimates: 16 wave sums, as survey_supergroup's
+    if (x.s.est) {
+        uint64_t sum[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) sum[i] = lf[cnt[i]];
+#pragma unroll
+        for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
+            const bool upper = (lane & off) != 0u;
+#pragma unroll
+            for (uint32_t m = 0; m < n; ++m) {
+                const uint64_t keep = upper ? sum[m + n] : sum[m], give = upper ? sum[m] : sum[m + n];
+                const uint32_t lo = __shfl_xor(static_cast<uint32_t>(give), off), hi = __shfl_xor(static_cast<uint32_t>(give >> 32), off);
+                sum[m] = keep + (static_cast<uint64_t>(hi) << 32 | lo);
+            }
+        }
+#pragma unroll
+        for (uint32_t off = 2; off >= 1; off >>= 1) {
+            const uint32_t lo = __shfl_xor(static_cast<uint32_t>(sum[0]), off), hi = __shfl_xor(static_cast<uint32_t>(sum[0] >> 32), off);
+            sum[0] += static_cast<uint64_t>(hi) << 32 | lo;
+        }
+        if ((lane & 3u) == 0u) sums[wave][lane >> 2] = sum[0];
+    }
+    __syncthreads();
+    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
+        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
+    }
+    if (threadIdx.x < 32u) {
+        const uint32_t i = threadIdx.x & 15u, hh = threadIdx.x >> 4, p = 4u * hh + (i & 3u);
+        if (p * kPacket < len) {
+            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
+            if (x.s.est) {
+                const uint64_t total = sums[4u * hh][i] + sums[4u * hh + 1u][i] + sums[4u * hh + 2u][i] + sums[4u * hh + 3u][i];
+                GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(x.s.est));
+                est[(i >> 2) * x.s.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
+            }
+            if (x.scan) {
+                const uint32_t k01 = keys[4u * hh][i] > keys[4u * hh + 1u][i] ? keys[4u * hh][i] : keys[4u * hh + 1u][i];
+                const uint32_t k23 = keys[4u * hh + 2u][i] > keys[4u * hh + 3u][i] ? keys[4u * hh + 2u][i] : keys[4u * hh + 3u][i];
+                GlobalWord *scan = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(x.scan));
+                scan[(i >> 2) * x.s.stride + first + p] = xor_scan_word(k01 > k23 ? k01 : k23, count);
+            }
+        }
+    }
+    __syncthreads();      // the clears and the reads of both exchanges in front of the next supergroup
+}
+
+__global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_per_eu(4)))      // two workgroups per CU: 128 VGPRs
+survey_xor_kernel(XorSurveyArgs a) {
+    __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
+    __shared__ uint64_t sums[kSurveyWaves][16];
+    __shared__ uint32_t keys[kSurveyWaves][16];
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
+    __syncthreads();
+    xsurvey_walk(a, [&](const uint8_t *sg, const uint8_t *bs, uint32_t len, uint64_t first) {
+        xsurvey_supergroup(a, sg, bs, len, first, lds, sums, keys);
+    });
+}
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -4811,6 +5050,63 @@ int gpuar_hip_choose_filter(const uint64_t plain[4], const uint64_t filtered[4],
 }
 
 uint32_t gpuar_hip_choose_planes(const uint64_t total[4], uint64_t n_packets) { return total ? gpuar::choose_width(total, n_packets) : 1u; }
+
+// the XOR-base survey (include/gpuar_hip_xsurvey.h): `a` with its source, base and status in place
+static int launch_survey_xor(gpuar::XorSurveyArgs a, uint32_t *d_est, uint32_t *d_scan, size_t stride, void *stream) {
+    a.s.est = d_est;
+    a.s.stride = stride;
+    a.scan = d_scan;
+    const uint32_t blocks = capped_blocks(a.s.n_packets, 8u, gpuar::kSurveyGroups);     // a window of 8 packets at a time
+    gpuar::survey_xor_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+// What the XOR survey's calls add to the plane survey's checks: the base (or the array of base pointers) is there and one output
+// at least (else ARGUMENT); the base and the scan rows are aligned (else ALIGNMENT; the est rows, or the scan rows where there are
+// none, go through packet_checks as the plane survey's d_est does).
+static int xsurvey_pointers(const void *base, uintptr_t base_align, const uint32_t *d_est, const uint32_t *d_scan) {
+    if (!base || (!d_est && !d_scan)) return GPUAR_ERR_ARGUMENT;
+    return misaligned(base, base_align) || misaligned(d_scan, 4) ? GPUAR_ERR_ALIGNMENT : GPUAR_OK;
+}
+
+// ... in the header's order: nothing to do, every ARGUMENT defect, every ALIGNMENT defect, then the status word.  `own`: what
+// xsurvey_pointers said (its ARGUMENT went into own_ok), `e`: what the plane survey's checks said.
+static int xsurvey_order(int own, int e, bool launch) {
+    if ((e == GPUAR_OK && !launch) || e == GPUAR_ERR_ARGUMENT || e == GPUAR_ERR_ALIGNMENT) return e;
+    return own != GPUAR_OK ? own : e;
+}
+
+int gpuar_hip_survey_xor(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, uint32_t *d_est, uint32_t *d_scan, size_t stride,
+                         void *stream) {
+    gpuar::XorSurveyArgs a = {};
+    bool launch = false;
+    const int own = xsurvey_pointers(d_base, 16u, d_est, d_scan);
+    const int e = xsurvey_order(own, packet_checks(stride >= gpuar_hip_packet_count(n_bytes) && own != GPUAR_ERR_ARGUMENT, d_in, n_bytes,
+                                                   d_est ? d_est : d_scan, nullptr, nullptr, &a.s, &launch), launch);
+    if (e != GPUAR_OK || !launch) return e;
+    a.base = d_base;
+    return launch_survey_xor(a, d_est, d_scan, stride, stream);
+}
+
+int gpuar_hip_survey_xor_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_in_bytes, const uint64_t *d_first_packet,
+                               const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets, uint32_t *d_est, uint32_t *d_scan,
+                               size_t stride, uint32_t *d_status, void *stream) {
+    gpuar::XorSurveyArgs a = {};
+    bool launch = false;
+    const int own = xsurvey_pointers(d_base_ptrs, 8u, d_est, d_scan);
+    const int e = xsurvey_order(own, packet_batch_checks(stride >= n_packets && own != GPUAR_ERR_ARGUMENT, d_in_ptrs, d_in_bytes, d_first_packet,
+                                                         n_buffers, n_packets, d_est ? d_est : d_scan, nullptr, d_status, &a.s, &launch), launch);
+    if (e != GPUAR_OK || !launch) return e;
+    a.bases = d_base_ptrs;
+    return launch_survey_xor(a, d_est, d_scan, stride, stream);
+}
+
+int gpuar_hip_survey_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t *est, uint32_t *scan, size_t stride) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!in || !base || (!est && !scan) || stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
+    gpuar::xor_survey_host(in, base, n_bytes, est, scan, stride);
+    return GPUAR_OK;
+}
 
 int gpuar_hip_move_packets(const uint8_t *const *d_src_ptrs, uint8_t *const *d_dst_ptrs, const uint64_t *d_bytes, size_t n_regions,
                            uint32_t *d_status, void *stream) {

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../delta_survey.h"
+#include "../xor_survey.h"
 #include "gpuar_hip.h"
 
 namespace gip {
@@ -103,6 +104,36 @@ bool Compressor::chooseFilter(bool choose_width_too, unsigned long long plain[4]
         delta = n_packets != 0 && sums_filtered[j] + n_packets <= sums_plain[j];
     }
     return delta;
+}
+
+bool Compressor::chooseBase(bool choose_width_too, unsigned long long plain[4], unsigned long long xored[4]) {
+    if (!based()) throw std::runtime_error("--base-auto needs --base=FILE");
+    const std::vector<uint8_t> head = readSurveyPrefix();
+    struct stat st;
+    if (::stat(openFileName.c_str(), &st) != 0) throw std::runtime_error("Can not open input file: " + openFileName);
+    openBase(static_cast<uint64_t>(st.st_size), "the input");
+    std::vector<uint8_t> base(head.size());
+    if (!base.empty()) readBase(base.data(), base.size(), 0);
+    ::close(baseFd);
+    baseFd = -1;
+    const size_t n_packets = (head.size() + GPUAR_PACKET_BYTES - 1) / GPUAR_PACKET_BYTES;
+    std::vector<uint32_t> est(gpuar::kSurveyWidths * n_packets);
+    uint64_t sums_plain[gpuar::kSurveyWidths], sums_xored[gpuar::kSurveyWidths];
+    gpuar::survey_host(head.data(), head.size(), est.data(), n_packets);
+    survey_totals(est, n_packets, sums_plain, plain);
+    gpuar::xor_survey_host(head.data(), base.data(), head.size(), est.data(), nullptr, n_packets);
+    survey_totals(est, n_packets, sums_xored, xored);
+    bool keep = false;
+    if (choose_width_too) {
+        const gpuar::FilterChoice c = gpuar::choose_filter(sums_plain, sums_xored, n_packets);
+        planes = static_cast<int>(c.width);
+        keep = c.filter;
+    } else {
+        const uint32_t j = gpuar::survey_row(static_cast<uint32_t>(planes));
+        keep = n_packets != 0 && sums_xored[j] + n_packets <= sums_plain[j];
+    }
+    if (!keep) setBaseFileName("");
+    return keep;
 }
 
 void Compressor::openBase(uint64_t expect, const char *what) {

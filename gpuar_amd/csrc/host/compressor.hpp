@@ -182,6 +182,14 @@ class Compressor {
     // filtered[W] + packets <= plain[W], the rule of batch.compress(delta="auto"); with both open it is gpuar::choose_filter.
     // On the host, before either pipeline starts, as choosePlanes.
     bool chooseFilter(bool choose_width_too, unsigned long long plain[4], unsigned long long filtered[4]);
+    // `--base-auto`: keeps or drops the base -- and with choose_width_too (`--planes=auto` as well) sets the width -- from the same
+    // prefix of the input and the same byte range of the base, and returns whether the base is kept.  plain[4] are the totals of
+    // gpuar::survey_host, xored[4] those of gpuar::xor_survey_host (../xor_survey.h: the prefix XORed with the base and split at
+    // widths 1, 2, 4, 8).  With the width fixed the base is kept iff xored[W] + packets <= plain[W], the rule of
+    // batch.compress(base_auto=...); with both open it is gpuar::choose_filter with the base in the filter's place.  A dropped base
+    // is forgotten (setBaseFileName("")): the file is that of no --base at all, the implied checksums included.  The base must have
+    // the input's length, kept or not.  On the host, before either pipeline starts, as choosePlanes.
+    bool chooseBase(bool choose_width_too, unsigned long long plain[4], unsigned long long xored[4]);
     virtual CompressionInfo compress(ProgressMonitor *monitor) = 0;
     virtual CompressionInfo decompress(ProgressMonitor *monitor) = 0;
     void closeFiles();

@@ -1,6 +1,6 @@
 // main.cpp -- the `gpuar` command line (flags and output text of src/main.cpp:59-205).
 //
-//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta[=on|off|auto]] [--base=FILE] [--stored[=auto|off]] [--sparse[=auto|off]] [--nointeractive] [--help]
+//   gpuar c|d --in=F --out=G [--host] [--device=N] [--gpus=K] [--threads=T] [--batch=P] [--index] [--checksum] [--planes=W|auto] [--delta[=on|off|auto]] [--base=FILE [--base-auto]] [--stored[=auto|off]] [--sparse[=auto|off]] [--nointeractive] [--help]
 //
 // Differences from the reference, all on the error side: `--in F` and `--in=F`
 // are both accepted on purpose (the reference's `--in F` works by accident of
@@ -69,6 +69,9 @@ void usage() {
     std::cout << "              base makes it grow; implies --checksum; not together with --delta; the file then carries a trailer that says so;" << std::endl;
     std::cout << "              (decompress) the same FILE: required for a file written with --base (a wrong one is a checksum mismatch)," << std::endl;
     std::cout << "              refused for any other file" << std::endl;
+    std::cout << "--base-auto   (compress, with --base=FILE) keep the base only if it is predicted to pay: the first 16 MiB of the input and of FILE are" << std::endl;
+    std::cout << "              surveyed on the host as they are and XORed -- at the W of --planes, or together with W where --planes=auto, and W is" << std::endl;
+    std::cout << "              then that of the bytes that get coded; a dropped base leaves the file of no --base at all" << std::endl;
     std::cout << "--stored      (compress) --stored or --stored=auto: a packet that the coder cannot shrink (its estimate says so: mantissa planes," << std::endl;
     std::cout << "              data that is already compressed) is kept raw behind its 4-byte header; --stored=off: every packet is coded (default)" << std::endl;
     std::cout << "--sparse      (compress) --sparse or --sparse=auto: a packet that is one byte value almost everywhere (what --base makes of" << std::endl;
@@ -83,7 +86,7 @@ void usage() {
 int main(int argc, char **argv) {
     bool decompress = false, host = false, help = argc <= 1, index = false, checksum = false;
     std::string in, out = "output.gip", base;
-    bool has_in = false, planes_auto = false, delta = false, delta_auto = false, stored = false, sparse = false;
+    bool has_in = false, planes_auto = false, delta = false, delta_auto = false, stored = false, sparse = false, base_auto = false;
     int device = -1, gpus = 0, threads = 1, planes = 1;
     long batch = 0;
     for (int i = 1; i < argc; ++i) {
@@ -147,6 +150,8 @@ int main(int argc, char **argv) {
                 std::cerr << "--planes takes 1, 2, 4, 8 or auto: " << v << std::endl;
                 return 2;
             }
+        } else if (flag_name_is(argv[i], "base-auto", &v)) {
+            base_auto = true;
         } else if (flag_name_is(argv[i], "base", &v)) {
             if (!take(&v) || !*v) {
                 std::cerr << "--base takes a file name" << std::endl;
@@ -167,6 +172,10 @@ int main(int argc, char **argv) {
     }
     if (!base.empty() && delta) {
         std::cerr << "--base and --delta cannot be combined" << std::endl;
+        return 2;
+    }
+    if (base_auto && (base.empty() || decompress)) {
+        std::cerr << "--base-auto goes with c and --base=FILE" << std::endl;
         return 2;
     }
     try {
@@ -213,6 +222,12 @@ int main(int argc, char **argv) {
                           << " (predicted bytes at widths 1, 2, 4, 8 without the filter: " << plain[0] << ", " << plain[1] << ", " << plain[2] << ", "
                           << plain[3] << "; with it: " << filtered[0] << ", " << filtered[1] << ", " << filtered[2] << ", " << filtered[3] << ")"
                           << std::endl;
+            } else if (base_auto) {
+                unsigned long long plain[4], xored[4];
+                const bool kept = compressor->chooseBase(planes_auto, plain, xored);
+                std::cout << "base-auto: base " << (kept ? "kept" : "dropped") << ", width " << compressor->getPlanes()
+                          << " (predicted bytes at widths 1, 2, 4, 8 without the base: " << plain[0] << ", " << plain[1] << ", " << plain[2] << ", "
+                          << plain[3] << "; against it: " << xored[0] << ", " << xored[1] << ", " << xored[2] << ", " << xored[3] << ")" << std::endl;
             } else if (planes_auto) {
                 unsigned long long total[4];
                 const int w = compressor->choosePlanes(total);

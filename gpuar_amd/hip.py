@@ -103,6 +103,12 @@ EXPORTS = list(SIGNATURES)
 GIP_SIGNATURES = {
     "gpuar_hip_move_bytes": (_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
 }
+# The XOR-base survey, declared in include/gpuar_hip_xsurvey.h: a third table for the same reason (tests/test_capi_xsurvey_host.py).
+XSURVEY_SIGNATURES = {
+    "gpuar_hip_survey_xor": (_int, [_vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "gpuar_hip_survey_xor_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "gpuar_hip_survey_xor_host": (_int, [_vp, _vp, _sz, _vp, _vp, _sz]),
+}
 GIP_INFO_WORDS = 10                  # GPUAR_GIP_INFO_WORDS
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
@@ -127,10 +133,10 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     # a library built from older sources lacks newer exports: say "rebuild" instead of dying with an AttributeError half-way
     # through the signatures
-    missing = [name for name in (*EXPORTS, *GIP_SIGNATURES) if not hasattr(lib, name)]
+    missing = [name for name in (*EXPORTS, *GIP_SIGNATURES, *XSURVEY_SIGNATURES) if not hasattr(lib, name)]
     if missing:
         raise GpuarError(f"{LIB_PATH} lacks {missing}: it was built from older sources -- rebuild the library")
-    for name, (restype, argtypes) in (*SIGNATURES.items(), *GIP_SIGNATURES.items()):
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *GIP_SIGNATURES.items(), *XSURVEY_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
@@ -689,6 +695,65 @@ def choose_filter(plain, filtered, n_packets: int) -> tuple:
     width = C.c_uint32(0)
     on = load().gpuar_hip_choose_filter((C.c_uint64 * 4)(*plain), (C.c_uint64 * 4)(*filtered), n_packets, C.byref(width))
     return int(width.value), bool(on)
+
+
+def _xsurvey_rows(d_est, d_scan, npk, device):
+    """The two outputs of the XOR survey, each as _survey_rows takes it (None: a new tensor) or False for "not asked"; both of one
+    row stride.  Returns the tensors (None for one not asked) and the stride."""
+    if d_est is False and d_scan is False:
+        raise GpuarError("survey_xor: d_est and d_scan cannot both be left out")
+    d_est = None if d_est is False else _survey_rows(d_est, npk, device)
+    d_scan = None if d_scan is False else _survey_rows(d_scan, npk, device)
+    if d_est is not None and d_scan is not None and d_est.shape[1] != d_scan.shape[1]:
+        raise GpuarError(f"d_est and d_scan must have one row stride, not {d_est.shape[1]} and {d_scan.shape[1]}")
+    return d_est, d_scan, (d_est if d_est is not None else d_scan).shape[1]
+
+
+def _ptr_or_null(t):
+    return None if t is None else t.data_ptr()
+
+
+def survey_xor(d_in, d_base, d_est=None, d_scan=None, n_bytes: int = None, stream=None):
+    """The estimate and the sparse scan word of every packet of the first `n_bytes` (default: all) bytes of `d_in` XORed with
+    `d_base` and split into byte planes of width 1, 2, 4 and 8, from one read of both and without XORing or splitting anything into
+    memory (gpuar_hip_survey_xor): row j of d_est is what estimate(split_xor(d_in, d_base, SURVEY_WIDTHS[j])) gives, row j of d_scan
+    what sparse_scan of it gives.  Returns (d_est, d_scan): int32 CUDA tensors of shape (4, packet_count(n_bytes)) (the caller's
+    may be wider: their second dimension is the row stride, the same for both).  False for d_est or d_scan leaves that output out
+    (None is returned in its place); not both."""
+    _require_cuda_u8(d_in, "d_in")
+    _require_cuda_u8(d_base, "d_base")
+    n, npk = _span(d_in, n_bytes)
+    if n > d_base.numel():
+        raise GpuarError("n_bytes is larger than d_base")
+    d_est, d_scan, stride = _xsurvey_rows(d_est, d_scan, npk, d_in.device)
+    _call("gpuar_hip_survey_xor", d_in.data_ptr(), d_base.data_ptr(), n, _ptr_or_null(d_est), _ptr_or_null(d_scan), stride, _stream_handle(stream))
+    return d_est, d_scan
+
+
+def survey_xor_batch(d_ptrs, d_bytes, d_first_packet, d_base_ptrs, n_buffers: int, n_packets: int, d_est=None, d_scan=None, stream=None,
+                     d_status=None, device=None):
+    """The XOR survey of every buffer of a batch in one launch (gpuar_hip_survey_xor_batch; descriptors as for encode_batch, and
+    d_base_ptrs: one base address per buffer, 0 for "no base" -- that buffer's rows are the plane survey's): d_est[j, p] and
+    d_scan[j, p] for width SURVEY_WIDTHS[j] and batch packet p.  Outputs as for survey_xor."""
+    _require_batch(d_ptrs, d_bytes, d_first_packet, n_buffers, more=((d_base_ptrs, "d_base_ptrs"),))
+    d_est, d_scan, stride = _xsurvey_rows(d_est, d_scan, n_packets, device or d_ptrs.device)
+    _call("gpuar_hip_survey_xor_batch", d_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_base_ptrs.data_ptr(), n_buffers,
+          n_packets, _ptr_or_null(d_est), _ptr_or_null(d_scan), stride, _status_ptr(d_status), _stream_handle(stream))
+    return d_est, d_scan
+
+
+def survey_xor_host(data, base, est: bool = True, scan: bool = True) -> tuple:
+    """survey_xor of two bytes-like objects of one length on the CPU (gpuar_hip_survey_xor_host: no device is touched): (est, scan),
+    each four lists, one per width of SURVEY_WIDTHS, of one int per packet -- or None where est / scan is False."""
+    data, base = bytes(data), bytes(base)
+    if len(data) != len(base):
+        raise GpuarError(f"survey_xor_host: {len(data)} bytes against a base of {len(base)}")
+    if not est and not scan:
+        raise GpuarError("survey_xor_host: est and scan cannot both be left out")
+    npk = packet_count(len(data))
+    words = [(C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))() if on else None for on in (est, scan)]
+    _call("gpuar_hip_survey_xor_host", data, base, len(data), words[0], words[1], npk)
+    return tuple(None if w is None else [list(w[j * npk:(j + 1) * npk]) for j in range(len(SURVEY_WIDTHS))] for w in words)
 
 
 def stored_rule(est: int, ulen: int) -> bool:
