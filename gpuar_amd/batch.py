@@ -786,7 +786,7 @@ class _Batch(NamedTuple):
 
 def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=None) -> _Batch:
     """The host step compress and estimate share: what both refuse of base, tensors, planes and delta, in this order and before any
-    launch -- base_auto without a base, a base beside `delta`, whatever base_pointers, describe, plane_widths and delta_flags refuse --,
+    launch -- base_auto without a base, a base_auto that is a string other than "survey", a base beside `delta`, whatever base_pointers, describe, plane_widths and delta_flags refuse --,
     and planes="survey" resolved: the one step here that launches, on `stream`, with a `stored` that no caller takes refused in front
     of it.  A filter or a base without `planes` works on bytes (width 1).  With base_auto="survey" the same step chooses width and
     base together (survey_base_choice; `sparse` is what its totals count)."""
@@ -1087,7 +1087,8 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     fixed bases with stored="auto" take, one synchronisation, both split copies kept and none made a third time);
     Compressed.based says which.  base_auto="survey" keeps the same bases from one hip.survey_planes_batch and one
     hip.survey_xor_batch launch over the original bytes and one synchronisation, and then splits once: one temporary of the batch's
-    size instead of two (_survey_base_keep); with planes="survey" it chooses width and base together, on the bytes that would be
+    size instead of two (_survey_base_keep; a width the surveys do not have, any but 1, 2, 4 and 8, raises before any launch, as with
+    delta="survey", where base_auto=True gets BAD_BATCH from the split); with planes="survey" it chooses width and base together, on the bytes that would be
     coded (survey_base_choice), and records both in Compressed.planes and Compressed.based.  base=None takes exactly the path taken without the keyword.  `sparse`: None | "auto" (with
     stored None or "auto"): keep the packets that are one byte value almost everywhere as that byte and a list of exceptions --
     one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one hip.sparse_scan_batch launch

@@ -5,7 +5,8 @@ The model needs numpy, the numpy definitions of the filters (planes_ref, delta_r
 trailer_ref / delta_ref / xor_ref, zlib.crc32, the host library's estimate (hip.estimate_host) and the oracle's codec; no device and
 no torch.  Where batch.py measures (planes="survey", delta="auto" / "survey", base_auto) the model decides by definition: it splits
 with numpy, estimates the split bytes and applies the rule, restated here (choose_planes, choose_filter) and pinned against the C
-functions by tests/test_batch_model_host.py.
+functions by tests/test_batch_model_host.py.  base_auto="survey" is decided the same way, from the split bytes' estimates and
+scan words and never from the XOR survey (hip.survey_xor_host), which is what batch.py decides from.
 
 Everything that depends only on a layout -- (buffer, width, none | delta | base) -- is made once and shared by every combination
 that uses it: the split bytes, the per-packet estimates and scan words and the oracle's packets."""
@@ -138,6 +139,28 @@ def _totals(ests, lens, replace):
     return sum(n if replace and e >= 4 + n else e for e, n in zip(ests, lens))
 
 
+def _kept_total(lay, replace, count_sparse):
+    """a layout's predicted bytes with every packet counted as it would be kept: under sparse="auto" by sparse_ref.rule -- a sparse
+    packet as its record, a raw one as its bytes --, under stored="auto" alone a packet whose estimate is not below 4 + its bytes as
+    its bytes, else its estimate"""
+    if not count_sparse:
+        return _totals(lay.est, lay.lens, replace)
+    total = 0
+    for s, e, n in zip(lay.scan, lay.est, lay.lens):
+        kind = S.rule(s, e, n, replace)
+        total += S.sparse_len(s >> 8) if kind == SPARSE else n if kind == RAW else e
+    return total
+
+
+def survey_base_totals(arrays, base, b, replace=False, count_sparse=False):
+    """(plain, xored) of buffer b for base_auto="survey" beside planes="survey": the four totals of its bytes split at widths 1, 2, 4
+    and 8 as they are and XORed with its base (None without one), every packet counted as it would be kept (_kept_total)"""
+    plain = [_kept_total(layout(arrays[b], w, "none"), replace, count_sparse) for w in WIDTHS]
+    if base is None or base[b] is None or not _raw(arrays[b]).size:
+        return plain, None
+    return plain, [_kept_total(layout(arrays[b], w, "base", base[b]), replace, count_sparse) for w in WIDTHS]
+
+
 def _resolve(arrays, dtypes, planes, delta, base, base_auto, stored, sparse):
     """(the buffers' bytes, their packet counts, widths or None, flags or None, based or None, the layout every buffer is coded from,
     the kind of every batch packet or None) -- every choice batch.py measures for, made by definition"""
@@ -148,6 +171,8 @@ def _resolve(arrays, dtypes, planes, delta, base, base_auto, stored, sparse):
     n_packets = sum(counts)
     if base is None and base_auto:
         raise Refused("base_auto without base")
+    if isinstance(base_auto, str) and base_auto != "survey":
+        raise Refused("base_auto is a string other than \"survey\"")
     if base is not None and delta is not None:
         raise Refused("base with delta")
     if stored is not None and not isinstance(stored, str) and len(stored) != n_packets:
@@ -160,8 +185,14 @@ def _resolve(arrays, dtypes, planes, delta, base, base_auto, stored, sparse):
         lay = layout(arrays[b], w, how)
         return _totals(lay.est, lay.lens, False), _totals(lay.est, lay.lens, replace)
 
-    flags = None
-    if isinstance(planes, str) and planes == "survey":
+    flags = based = None
+    if isinstance(planes, str) and planes == "survey" and base is not None and isinstance(base_auto, str):
+        # width and base together: choose_filter with the base in the filter's place, on totals that count raw and sparse packets
+        both = [survey_base_totals(arrays, base, b, replace, sparse is not None) for b in range(n)]
+        choice = [(choose_planes(plain, counts[b]), False) if xored is None else choose_filter(plain, xored, counts[b])
+                  for b, (plain, xored) in enumerate(both)]
+        widths, based = [w for w, _k in choice], [k for _w, k in choice]
+    elif isinstance(planes, str) and planes == "survey":
         plain = [[total(b, w, "none")[1] for w in WIDTHS] for b in range(n)]
         if isinstance(delta, str) and delta == "survey":
             filtered = [[total(b, w, "delta")[1] for w in WIDTHS] for b in range(n)]
@@ -184,10 +215,9 @@ def _resolve(arrays, dtypes, planes, delta, base, base_auto, stored, sparse):
             flags = [filter_pays(total(b, widths[b], "delta")[0], total(b, widths[b], "none")[0], counts[b]) for b in range(n)]
         else:
             flags = [bool(delta)] * n if isinstance(delta, (bool, int)) else [bool(f) for f in delta]
-    based = None
-    if base is not None:
+    if base is not None and based is None:
         based = [q is not None and xs[b].size > 0 for b, q in enumerate(base)]
-        if base_auto:
+        if base_auto:                                           # (True and "survey" at fixed widths: one rule, on coded estimates)
             based = [based[b] and filter_pays(sum(layout(arrays[b], widths[b], "base", base[b]).est), total(b, widths[b], "none")[0], counts[b])
                      for b in range(n)]
     lays = []
@@ -390,6 +420,7 @@ FILTER_AXIS = {                                                     # the keywor
     "delta_survey": {"delta": "survey"},
     "base": {"base": BASES},
     "base_auto": {"base": BASES, "base_auto": True},
+    "base_survey": {"base": BASES, "base_auto": "survey"},
 }
 STORED_AXIS = {"none": None, "auto": "auto", "list": [p % 3 == 0 for p in range(N_PACKETS)]}
 SPARSE_AXIS = {"none": None, "auto": "auto"}
@@ -397,7 +428,7 @@ assert sorted(set(PLANES_AXIS["list"])) == [1, 2, 4, 8] and len(set(DELTA_LIST))
 
 
 def combinations():
-    """every (planes, filter, stored, sparse) by name, 210 of them"""
+    """every (planes, filter, stored, sparse) by name, 240 of them"""
     return [(p, f, s, q) for p in PLANES_AXIS for f in FILTER_AXIS for s in STORED_AXIS for q in SPARSE_AXIS]
 
 
@@ -413,7 +444,7 @@ def is_refused(combo):
 # raw; "still" (the tensor equal to its base, zeros, nothing) has under `base` only sparse packets with sparse="auto" and only coded
 # ones without; "rough" (uniform bytes, text, one byte) has no sparse packet.
 SUBSETS = {"calm": [6, 8, 9], "still": [3, 8, 9], "rough": [5, 6, 10]}
-SUBSET_COMBOS = [("auto", f, s, q) for f in ("delta", "base") for s in ("none", "auto") for q in ("none", "auto")]
+SUBSET_COMBOS = [("auto", f, s, q) for f in ("delta", "base", "base_survey") for s in ("none", "auto") for q in ("none", "auto")]
 
 
 def keywords(combo, subset=None):

@@ -1,13 +1,18 @@
-"""The host model of batch.py (tests/batch_model.py) on the CPU, over the whole option matrix: planes x filter x stored x sparse, 210
-combinations of which 35 are refused by contract.  Every valid combination goes through model_compress and back through
+"""The host model of batch.py (tests/batch_model.py) on the CPU, over the whole option matrix: planes x filter x stored x sparse, 240
+combinations of which 40 are refused by contract.  Every valid combination goes through model_compress and back through
 model_decompress; the conditions that keep tests/test_gpu_batch_matrix.py from being vacuous -- every kind of packet, every choice
 taken both ways, an empty kind -- are asserted on the model alone; the model's restatements of choose_planes and choose_filter are
 pinned against the C functions; and the parts of batch.py that are device-free torch (_kinds, _partition, and the decisions of
 _auto_delta and _auto_base with the launches replaced by the model's estimates) run on CPU tensors against the model.
 
-Wall time of the module: 6 s on one core (19 tests), 3 s of it importing torch in the first test that needs it.  The 350
-model_compress / model_decompress pairs (with and without CRCs) take under 2 s: 118 layouts are split, estimated, scanned and encoded
-once each for all of them."""
+Wall time of the module: 6 s on one core (21 tests), 3 s of it importing torch in the first test that needs it.  The 400
+model_compress / model_decompress pairs (with and without CRCs) take under 2 s: 124 layouts are split, estimated, scanned and encoded
+once each for all of them.
+
+base_auto="survey" is the eighth value of the filter axis.  At fixed widths its model is base_auto=True's, field by field; beside
+planes="survey" it is a rule of its own -- width and base together, on totals that count raw and sparse packets -- whose totals
+and choices for the three tensors with a base are written out here (CODED_TOTALS, KEPT_TOTALS) and differ from base_auto=True's in
+the widths of two of them."""
 import itertools
 import os
 
@@ -51,11 +56,11 @@ def valid(M):
 
 # ---- the matrix --------------------------------------------------------------------------------------------------------
 
-def test_the_matrix_is_175_valid_combinations_and_35_refused_ones(M):
+def test_the_matrix_is_200_valid_combinations_and_40_refused_ones(M):
     combos = M.combinations()
-    assert len(combos) == len(set(combos)) == 5 * 7 * 3 * 2 == 210
+    assert len(combos) == len(set(combos)) == 5 * 8 * 3 * 2 == 240
     refused = [c for c in combos if M.is_refused(c)]
-    assert len(refused) == 35 and len(valid(M)) == 175
+    assert len(refused) == 40 and len(valid(M)) == 200
     assert {(p, f) for p, f, _s, _q in refused} == set(itertools.product(M.PLANES_AXIS, M.FILTER_AXIS))
     for c in refused:
         with pytest.raises(M.Refused):
@@ -64,6 +69,14 @@ def test_the_matrix_is_175_valid_combinations_and_35_refused_ones(M):
         M.model(c, False)                                      # (raises for none of them)
     with pytest.raises(M.Refused):
         M.model_compress(M.ARRAYS, M.DTYPES, base_auto=True)
+    for base_auto in ("survey", "auto"):                       # without a base; a string other than "survey", as batch.py refuses it
+        with pytest.raises(M.Refused):
+            M.model_compress(M.ARRAYS, M.DTYPES, base_auto=base_auto)
+    with pytest.raises(M.Refused):
+        M.model_compress(M.ARRAYS, M.DTYPES, base=M.BASES, base_auto="auto")
+    for base_auto in (True, "survey"):
+        with pytest.raises(M.Refused):
+            M.model_compress(M.ARRAYS, M.DTYPES, base=M.BASES, base_auto=base_auto, delta=True)
     for delta in (True, False, M.DELTA_LIST, "auto", "survey"):
         with pytest.raises(M.Refused):
             M.model_compress(M.ARRAYS, M.DTYPES, base=M.BASES, delta=delta)
@@ -101,7 +114,7 @@ def test_every_valid_combination_goes_there_and_back(M, planes):
             assert (m.stored is None) == (c[2] == "none" and c[3] == "none") and (m.sparse is None) == (c[3] == "none")
             assert (m.raw is None) == (m.stored is None) and (m.stored is None or len(m.stored) == M.N_PACKETS)
         n += 1
-    assert n == 35
+    assert n == 40
 
 
 def test_estimate_is_the_size_where_no_packet_is_coded_and_bounds_it_elsewhere(M):
@@ -162,6 +175,84 @@ def test_base_auto_keeps_the_bases_that_pay(M):
             m = M.model((p, "base_auto", s, "none"), False)
             assert m.based == [b in (2, 3) for b in range(len(M.ARRAYS))], (p, s)
             assert M.model((p, "base", s, "none"), False).based == [b in (2, 3, 4) for b in range(len(M.ARRAYS))]
+
+
+def test_base_survey_at_fixed_widths_is_base_auto_field_by_field(M):
+    """base_auto="survey" beside None, "auto", a width or a list of widths keeps the bases base_auto=True keeps, by the same rule on
+    coded estimates: the two models are equal in every field and coded from the same layouts."""
+    n = 0
+    for c in valid(M):
+        if c[1] != "base_survey" or c[0] == "survey":
+            continue
+        for checksum in (False, True):
+            m, a = M.model(c, checksum), M.model((c[0], "base_auto") + c[2:], checksum)
+            assert sorted(vars(m)) == sorted(vars(a))
+            for field in vars(a):
+                if field == "layouts":
+                    assert all(x is y for x, y in zip(m.layouts, a.layouts)), c
+                else:
+                    assert getattr(m, field) == getattr(a, field), (c, field)
+        assert m.based == [b in (2, 3) for b in range(len(M.ARRAYS))], c
+        n += 1
+    assert n == 4 * 5
+
+
+# base_auto="survey" beside planes="survey", for the three tensors of the batch that have a base: the totals [T1, T2, T4, T8] of
+# the bytes as they are and XORed, 7, 3 and 3 packets, and what choose_filter makes of them.  Coded totals (no stored, no sparse;
+# a list of stored packets counts as None): tensors 2 and 3 are within one byte a packet of their lowest XORed total at every
+# width, so the smallest width wins, where the plain bytes alone (and so planes="survey" beside base_auto=True) say 2.
+CODED_TOTALS = {
+    2: ([38795, 33646, 35366, 38115], [1372, 1370, 1370, 1371], (1, True)),
+    3: ([12976, 11267, 12982, 12986], [462, 462, 462, 462], (1, True)),
+    4: ([19337, 17620, 18986, 19255], [19905, 18254, 19572, 19829], (2, False)),
+}
+# Counting moves totals and no choice.  stored="auto": the raw packets are low-byte planes at widths 2 and 4, plain and against
+# the unrelated base.  sparse="auto": an unchanged packet is a 4-byte record and one with a few changed elements a short one, so
+# the XORed side falls to 160 .. 164 bytes for tensor 2 (7 packets: all within the margin, width 1) and 12 for tensor 3; no
+# packet of the plain side or of tensor 4 is sparse.  (stored, sparse): (plain, xored) where they differ from CODED_TOTALS.
+KEPT_TOTALS = {
+    ("auto", "none"): {2: ([38795, 33530, 35284, 38115], None), 3: ([12976, 11226, 12982, 12986], None),
+                       4: ([19337, 17583, 18986, 19255], [19905, 18192, 19572, 19829])},
+    ("none", "auto"): {2: (None, [164, 160, 164, 160]), 3: (None, [12, 12, 12, 12]), 4: (None, None)},
+    ("auto", "auto"): {2: ([38795, 33530, 35284, 38115], [164, 160, 164, 160]), 3: ([12976, 11226, 12982, 12986], [12, 12, 12, 12]),
+                       4: ([19337, 17583, 18986, 19255], [19905, 18192, 19572, 19829])},
+}
+
+
+def test_base_survey_beside_the_plane_survey_chooses_width_and_base_together(H, M):
+    for b, (plain, xored, choice) in CODED_TOTALS.items():
+        packets = M.packets_of(M.SIZES[b])
+        assert M.survey_base_totals(M.ARRAYS, M.BASES, b) == (plain, xored), b
+        assert M.choose_filter(plain, xored, packets) == H.choose_filter(plain, xored, packets) == choice, b
+        # the survey the device decides from gives the same coded totals: its est rows are the layouts' estimates
+        est, _scan = H.survey_xor_host(M._raw(M.ARRAYS[b]).tobytes(), M.BASES[b].tobytes())
+        assert [sum(row) for row in est] == xored, b
+    assert [M.choose_planes(CODED_TOTALS[b][0], M.packets_of(M.SIZES[b])) for b in (2, 3, 4)] == [2, 2, 2]
+    n = 0
+    for s in M.STORED_AXIS:
+        for q in M.SPARSE_AXIS:
+            c = ("survey", "base_survey", s, q)
+            if M.is_refused(c):
+                continue
+            for b, (plain, xored, choice) in CODED_TOTALS.items():
+                moved = KEPT_TOTALS.get((s, q), {}).get(b, (None, None))
+                want = (moved[0] or plain, moved[1] or xored)
+                got = M.survey_base_totals(M.ARRAYS, M.BASES, b, s == "auto", q == "auto")
+                packets = M.packets_of(M.SIZES[b])
+                assert got == want, (c, b)
+                assert M.choose_filter(*got, packets) == H.choose_filter(*got, packets) == choice, (c, b)
+            m, a = M.model(c, False), M.model(("survey", "base_auto", s, q), False)
+            assert [(m.planes[b], m.based[b]) for b in (2, 3, 4)] == [(1, True), (1, True), (2, False)], c
+            assert [(a.planes[b], a.based[b]) for b in (2, 3, 4)] == [(2, True), (2, True), (2, False)], c
+            # a tensor without a base: choose_planes of plain totals that count sparse packets too, which planes="survey" alone
+            # does not; on this batch that moves no width
+            others = [b for b in range(len(M.ARRAYS)) if b not in CODED_TOTALS]
+            assert [m.planes[b] for b in others] == [a.planes[b] for b in others] and not any(m.based[b] for b in others), c
+            assert m.layouts[2] is M.layout(M.ARRAYS[2], 1, "base", M.BASES[2]) and m.layouts[4] is M.layout(M.ARRAYS[4], 2, "none")
+            n += 1
+    assert n == 5
+    # the whole joint rule once more by hand: no base, no packets
+    assert M.survey_base_totals(M.ARRAYS, M.BASES, 9) == ([0] * 4, None) and M.survey_base_totals(M.ARRAYS, M.BASES, 0)[1] is None
 
 
 def test_the_plane_survey_finds_widths_that_auto_cannot_see(M):
@@ -308,7 +399,7 @@ def test_kinds_is_the_rule_on_the_table_and_on_every_packet_of_the_matrix(H, M):
         assert kind.tolist() == m.stored, c
         assert all(v == S.sparse_len(s >> 8) for v, s in zip(slen.tolist(), scan) if s != S.NONE), c
         n += len(scan)
-    assert n == 70 * M.N_PACKETS
+    assert n == 80 * M.N_PACKETS
 
 
 def _check_partition(batch, m, lens, scan):
@@ -332,7 +423,7 @@ def test_partition_gives_the_models_ranks(H, M):
         if m.stored is not None:
             _check_partition(batch, m, [v for lay in m.layouts for v in lay.lens], [s for lay in m.layouts for s in lay.scan])
             n += 1
-    assert n == 140
+    assert n == 160
     empty = set()
     for part in M.SUBSETS:
         for c in M.SUBSET_COMBOS:

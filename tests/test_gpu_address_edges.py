@@ -21,7 +21,12 @@ A. Weakest alignment.  All pointer arguments weak at once, then each in turn whi
    length_sweep's layout "last_wave_1_live" (inputs from batch_sweep.scattered_inputs, outputs 16 bytes apart, permuted, none
    32-aligned, the stream at skew 4, descriptor arrays 8- but not 16-aligned), CRC-32 (9 packets + 77 bytes; batch pointers
    16-weak, not packet-aligned), the filters (planes, delta, xor; w = 1, 2, 4, 8; out of place and in place; 3 * 65536 + 4097 + 5
-   bytes), estimate and both surveys (d_est 4-weak, odd stride P + 1, mask 15 and the single width 8), move_packets (1, 15, 16,
+   bytes), estimate and both surveys (d_est 4-weak, odd stride P + 1, mask 15 and the single width 8), the XOR survey (the same
+   20 packets against a base that equals them but for the first half of every third half-packet; d_in and d_base 16-weak, d_est
+   and d_scan each 4-weak at the odd stride; both outputs, the est rows alone, the scan rows alone, the output that was not asked
+   for keeping every canary; expected from survey_xor_host) and its batch form (buffers of 65536 + 8192 + 1, 3 * 8192 + 77, 17,
+   0 and 65536 bytes, the second and the fourth with base pointer 0, buffers and bases in two blocks in different permuted
+   address orders, 16-weak and not packet-aligned, the four descriptor arrays 8- but not 16-aligned), move_packets (1, 15, 16,
    17, 8191, 8192 bytes), generate and gpuar_hip_copy.  generate's d_out must be 8-byte aligned (its kernels store 8 bytes at a
    time): at offsets 1 and 4 it returns GPUAR_ERR_ALIGNMENT and writes nothing, which the header now says.
    The packet forms (sections 8 - 12; each section's docstring names the fault class it would catch): sparse_scan (9 packets +
@@ -37,10 +42,13 @@ A. Weakest alignment.  All pointer arguments weak at once, then each in turn whi
    at mixed residues, destinations back to back at byte grain, the blocks at five more residue pairs).
 B. The same shapes and references with the line inside one pointer argument at a time, the others weak elsewhere: in the
    middle of a packet of the second wavefront group, inside a slot's coded bytes, inside the compacted stream, the offsets
-   array, a survey's rows, a filter's tail, the XOR base; and with a packet / slot / group boundary exactly on the line.  (A
+   array, a survey's rows, a filter's tail, the XOR base; for the XOR survey inside a lane's 128-byte piece of a full
+   supergroup, on a supergroup boundary and in the ragged tail of the base and of the buffer, in row 0 and on the word of the
+   stride gap of the est rows and of the scan rows, inside the array of base pointers; and with a packet / slot / group boundary exactly on the line.  (A
    boundary on the line makes the start a multiple of the unit, 8192 or 512 bytes for slots: those placements cannot be weak
    as well and assert the boundary instead.)  Batch calls: one buffer straddles; in a second layout one buffer ends exactly
-   at the line and the next begins at it.  The packet forms: the line inside a record's pos[], exactly between pos[] and
+   at the line and the next begins at it (the XOR survey's batch: one BASE straddles, and one base ends at the line where the
+   next begins; a base that ends on the line is a multiple of 16 bytes long, here 65536).  The packet forms: the line inside a record's pos[], exactly between pos[] and
    val[], on a record's start; inside a raw slot's body, a sparse record in a slot, on a slot boundary; in a stream inside a raw
    body, inside a sparse record and two bytes into a packet's header; inside d_kind, d_scan, d_offsets; and for move_bytes where
    a destination's head bytes end, inside its body, where its tail bytes begin, at its first byte and one byte behind its
@@ -62,8 +70,8 @@ D. 3 * 8192 + 5 packets: sparse_scan, kinds_store and kinds_expand keep 8192 wav
    (five take four) and kinds_expand builds them in the same 8 KiB of LDS: sparse, raw, coded and DAMAGED packets in orders
    chosen so that what one leaves behind would show in the next; BAD_PACKET / BAD_BATCH exactly when a defect is present.
 
-Time, pytest --durations=0 on an MI355X, the module alone: 40 passed in 3.9 s (625 placed launches in parts A and B for the
-older entry points, 151 for the packet forms).
+Time, pytest --durations=0 on an MI355X, the module alone: 42 passed in 4.0 s (625 placed launches in parts A and B for the
+older entry points, 151 for the packet forms, 59 for the XOR survey).
     0.49 s  setup of test_codec_at_the_weakest_alignment[text] (the arena, the reference encoder on 2 x 1 MiB)
     0.46 s  test_kinds_pipeline_past_4gib (4 GiB generated, 4.25 GiB of slots filled, five launches, four passes of comparisons)
     0.32 s  test_codec_at_the_weakest_alignment[text] (the first launches of the process)
@@ -74,7 +82,9 @@ older entry points, 151 for the packet forms).
     0.03 s  test_batch_codec_across_the_address_line, test_filters_past_4gib[delta-8]
     0.02 s  test_filters_past_4gib[planes-8], test_kinds_expand_second_trip[intact], test_filters_across_the_address_line[xor],
             test_move_bytes_past_4gib
-    0.01 s  the tests of sections 9 - 11, test_filters_past_4gib[planes-2], test_estimate_and_surveys_past_4gib,
+    0.01 s  test_xor_survey_at_the_weakest_alignment (24 placed launches), test_xor_survey_across_the_address_line (35; their
+            setup, the host twin on six buffers, is under 0.005 s),
+            the tests of sections 9 - 11, test_filters_past_4gib[planes-2], test_estimate_and_surveys_past_4gib,
             test_crc32_at_the_weakest_alignment, the other filter tests; every remaining test and setup is under 0.005 s
             (test_sparse_scan_and_kinds_store_second_trip, the scan and move_bytes sections among them).
 No shape had to shrink: no case comes near 5 s.  Memory: 4.1 GiB for the arena; on top of it at most 8.5 GiB during the filter
@@ -669,11 +679,12 @@ def _rows_image(rows, npk, stride):
     return img
 
 
-def _rows(v, stride):
-    return _i32(v["d_est"]).view(4, stride)
+def _rows(v, stride, name="d_est"):
+    return _i32(v[name]).view(4, stride)
 
 
-def _survey_cases(H):
+def _survey_input(H):
+    """(n, packets, row stride, bytes): the section's one-buffer input"""
     rng = np.random.default_rng([SEED, 6])
     n = 2 * GROUP + 3 * PACKET + 4097 + 5
     npk = H.packet_count(n)                                    # 20 packets: two supergroups and a ragged third
@@ -681,6 +692,11 @@ def _survey_cases(H):
     assert stride % 2 == 1
     x = np.cumsum(rng.integers(0, 1 << 12, n // 4 + 1, dtype=np.uint32), dtype=np.uint32).view(np.uint8)[:n].copy()
     x[GROUP:GROUP + 3 * PACKET] = rng.integers(0, 256, 3 * PACKET, dtype=np.uint8)
+    return n, npk, stride, x
+
+
+def _survey_cases(H):
+    n, npk, stride, x = _survey_input(H)
     raw = x.tobytes()
     in_lines = [("d_in", ("in", 9 * PACKET + 100)), ("d_in", ("on", GROUP)), ("d_in", ("in", n - 2000))]
     est_lines = [("d_est", ("in", 4 * stride + 40)), ("d_est", ("in", 4 * (2 * stride + 3)))]
@@ -706,6 +722,115 @@ def test_estimate_and_surveys_at_the_weakest_alignment(H, A, survey_cases):
 
 def test_estimate_and_surveys_across_the_address_line(H, A, survey_cases):
     _part_b(H, A, survey_cases)
+
+
+def _survey_base(x, seed):
+    """tests/test_gpu_xor_survey.py::_base_of: independent uniform bytes in the first half of every third half-packet, x elsewhere,
+    so that full and short supergroups each hold packets whose XOR is all zeros, half zeros and neither"""
+    b = x.copy()
+    pick = (np.arange(x.size) // (PACKET // 2)) % 3 == 0
+    b[pick] = np.random.default_rng([SEED, seed]).integers(0, 256, x.size, dtype=np.uint8)[pick]
+    return b
+
+
+def _joined_bases(sizes, seed, a, b):
+    """AE.scattered, but bases a and b stand behind the others, b exactly where a ends.  sizes[a] is a multiple of 32 (a base that
+    ends on the line and is 16-byte aligned has no other length here), so neither start is weak: a's is a multiple of 32, and the
+    caller puts b's on the line."""
+    assert sizes[a] and sizes[a] % 32 == 0 and sizes[b]
+    offs, total = AE.scattered(sizes, seed, align=16, gap=16)
+    offs[a] = (total + 31) // 32 * 32 + 32
+    offs[b] = offs[a] + sizes[a]
+    return offs, AE.weak(offs[b] + sizes[b] + 16, 16) + 16
+
+
+def _xor_survey_cases(H):
+    """The XOR survey is the first survey that reads two inputs in step, has a second output and, in a batch, an array of base
+    pointers in which 0 is a value.  Would catch: the base's address formed from the buffer's high word or in 32 bits (the line
+    inside a lane's 128-byte piece of the base, on a supergroup boundary of it, in its ragged tail -- and the same for the buffer
+    while the base lies elsewhere), a store to the scan rows through the est rows' pointer or stride (each output 4-weak on its
+    own, the line in row 0 and in the stride gap of each), a store to an output that was not asked for (it keeps every canary),
+    a 16-byte load of a base that is only 16-aligned taken wider, a batch base located from a pointer read as two halves or from
+    a 16-byte load of the 8-aligned pointer array (the line inside that array, a base that straddles the line, one that ends on it
+    and the next that begins there), and a base pointer of 0 dereferenced."""
+    n, npk, stride, x = _survey_input(H)
+    base = _survey_base(x, 16)
+    est, scan = H.survey_xor_host(x.tobytes(), base.tobytes())
+    # packets that equal their base (scan word 0), that differ from it in half their bytes and, at the wider widths, in other
+    # shares: in the full supergroups and in the ragged one
+    for lo, hi in ((0, 16), (16, npk)):
+        assert 0 in scan[0][lo:hi] and any(v >> 8 > 4000 for v in scan[0][lo:hi]) and len({tuple(r[p] for r in scan) for p in range(lo, hi)}) >= 3
+    est_img, scan_img = _rows_image(est, npk, stride), _rows_image(scan, npk, stride)
+    lane = GROUP + 3 * PACKET + 37 * 128 + 48                  # inside lane 37's piece of packet 3 of the second supergroup
+    data_lines = lambda name: [(name, ("in", lane)), (name, ("on", GROUP)), (name, ("in", n - 2000))]
+    row_lines = lambda name: [(name, ("in", 40)), (name, ("in", 4 * (stride + npk)))]         # in row 0; on the gap word behind row 1
+    cases = []
+    for tag, want_est, want_scan in (("both outputs", True, True), ("the est rows alone", True, False), ("the scan rows alone", False, True)):
+        def call(v, want_est=want_est, want_scan=want_scan):
+            got = H.survey_xor(v["d_in"], v["d_base"], d_est=_rows(v, stride) if want_est else False,
+                               d_scan=_rows(v, stride, "d_scan") if want_scan else False, n_bytes=n)
+            assert (got[0] is None) == (not want_est) and (got[1] is None) == (not want_scan)
+
+        args = [Arg("d_in", n, 16, init=x), Arg("d_base", n, 16, init=base), Arg("d_est", 16 * stride, 4, want=est_img if want_est else None),
+                Arg("d_scan", 16 * stride, 4, want=scan_img if want_scan else None)]
+        cases.append(Case(f"survey_xor, {tag}, odd stride", args, call,
+                          lines=data_lines("d_base") + data_lines("d_in") + row_lines("d_est") + row_lines("d_scan")))
+    # the batch form: five buffers and their bases in two blocks, each in its own permuted address order
+    sizes = [GROUP + PACKET + 1, 3 * PACKET + 77, 17, 0, GROUP]
+    based = [True, False, True, False, True]
+    rng = np.random.default_rng([SEED, 17])
+    datas = [np.cumsum(rng.integers(0, 1 << 12, s // 4 + 1, dtype=np.uint32), dtype=np.uint32).view(np.uint8)[:s].copy() for s in sizes]
+    bases = [_survey_base(d, 18 + b) for b, d in enumerate(datas)]
+    fp, total_pk = H.batch_packet_count(sizes)
+    bstride = total_pk + 2
+    assert total_pk == 23 and bstride % 2 == 1
+    rows = [[[], [], [], []], [[], [], [], []]]
+    for d, q, on in zip(datas, bases, based):
+        got = H.survey_xor_host(d.tobytes(), (q if on else np.zeros_like(d)).tobytes())                 # (no base: against zeros)
+        for which in (0, 1):
+            for j in range(4):
+                rows[which][j] += got[which][j]
+    best_img, bscan_img = _rows_image(rows[0], total_pk, bstride), _rows_image(rows[1], total_pk, bstride)
+    offs, total = AE.scattered(sizes, 21, align=16, gap=16)
+    img = _block_image(offs, datas, total)
+    for join in (None, (4, 0)):
+        boffs, btotal = AE.scattered(sizes, 22, align=16, gap=16) if join is None else _joined_bases(sizes, 22, *join)
+        bimg = _block_image(boffs, [q if on else q[:0] for q, on in zip(bases, based)], btotal)      # (a base that is not used is not there)
+        tag = ", base 0 straddles" if join is None else f", base {join[0]} ends where base {join[1]} begins"
+        inside = AE.weak(3 * PACKET + 37 * 128 + 40, 16)       # inside a lane's piece of the first supergroup of buffer 0 / base 0
+        on = ("on", boffs[0] + inside) if join is None else ("on", boffs[0])
+
+        def call(v, boffs=boffs, join=join):
+            ptrs = [v["block"].data_ptr() + o if s else 0 for o, s in zip(offs, sizes)]
+            bptrs = [v["bases"].data_ptr() + o if f and s else 0 for o, s, f in zip(boffs, sizes, based)]
+            assert all(p == 0 or (p % 32 == 16 and p % PACKET) for p in ptrs), "a buffer is not 16-weak, or is packet-aligned"
+            strong = [] if join is None else [bptrs[i] for i in join]
+            assert all(p == 0 or p % 32 == 16 or p in strong for p in bptrs), "a base is not 16-weak"
+            assert join is None or bptrs[join[0]] + sizes[join[0]] == bptrs[join[1]]
+            _put(v, d_ptrs=ptrs, d_bytes=sizes, d_fp=fp, d_base_ptrs=bptrs)
+            H.survey_xor_batch(_i64(v["d_ptrs"]), _i64(v["d_bytes"]), _i64(v["d_fp"]), _i64(v["d_base_ptrs"]), len(sizes), total_pk,
+                               d_est=_rows(v, bstride), d_scan=_rows(v, bstride, "d_scan"), d_status=_i32(v["d_status"]))
+
+        args = [Arg("block", total, 32, init=img, block=True), Arg("bases", btotal, 32, init=bimg, block=True),
+                Arg("d_est", 16 * bstride, 4, want=best_img), Arg("d_scan", 16 * bstride, 4, want=bscan_img)] + _desc_args(len(sizes)) + \
+               [Arg("d_base_ptrs", 8 * len(sizes), 8, check=False), _status_arg()]
+        cases.append(Case(f"survey_xor_batch{tag}", args, call,
+                          lines=[("bases", on), ("d_base_ptrs", ("in", 24))] + ([("block", ("on", offs[0] + inside))] if join is None else []),
+                          moving=["d_est", "d_scan", "d_ptrs", "d_bytes", "d_fp", "d_base_ptrs", "d_status"] if join is None else []))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def xor_survey_cases(H):
+    return _xor_survey_cases(H)
+
+
+def test_xor_survey_at_the_weakest_alignment(H, A, xor_survey_cases):
+    _part_a(H, A, xor_survey_cases)
+
+
+def test_xor_survey_across_the_address_line(H, A, xor_survey_cases):
+    _part_b(H, A, xor_survey_cases)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

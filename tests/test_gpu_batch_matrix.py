@@ -1,5 +1,5 @@
 """batch.compress / estimate / decompress on the MI355X over the whole option matrix, against the host model of
-tests/batch_model.py: planes x filter (35 tests) x the five valid (stored, sparse) pairs inside each -- the 175 valid combinations
+tests/batch_model.py: planes x filter (40 tests) x the five valid (stored, sparse) pairs inside each -- the 200 valid combinations
 tests/test_batch_model_host.py counts, on the batch of 14 tensors it describes, uploaded once.  Every comparison is byte for byte.
 
 For every combination: every field of Compressed against model_compress (the None-ness too: `stored`, `raw`, `sparse` and their
@@ -19,16 +19,24 @@ so that every value of each of them meets every value of every axis and of each 
 (test_the_rotation_covers_every_pair).  Three parts of the batch (batch_model.SUBSETS) add what the whole batch cannot have: a call
 with stored="auto" and no raw packet, one with no coded packet at all, one with sparse="auto" and no sparse packet.
 
-compress calls compared against the model, field by field: 175 (the matrix) + 24 (the parts) + 41 (the valid call behind every
-refused one) + 1 (damage) = 241.
+The filter axis ends at base_auto="survey" (base_survey).  At fixed widths it must give what base_auto=True gives from other
+launches; beside planes="survey" it is a decision of its own (width and base together, batch.survey_base_choice), which the model
+makes by definition and which codes tensors 2 and 3 of the batch from another layout than base_auto=True does
+(tests/test_batch_model_host.py has the totals).
 
-Time, pytest --durations=0 on an MI355X, the module alone: 46 passed in 5.1 s (of which 2 s import torch and collect).
-    0.98 s  test_every_field_estimate_decompress_and_gip_equal_the_model[none-none] (the first launches of the process and the
+compress calls compared against the model, field by field: 200 (the matrix) + 36 (the parts) + 52 (the valid call behind every
+refused one: 40 + 9 + 1 + 2) + 1 (damage) = 289.
+
+Time, pytest --durations=0 on an MI355X, with tests/test_gpu_batch_trace.py and tests/test_gpu_xor_survey_batch.py behind it: 65
+passed in 9.5 s (of which 2 s import torch and collect, and 3.6 s the trace module's child process); this module's 53 tests:
+    1.00 s  test_every_field_estimate_decompress_and_gip_equal_the_model[none-none] (the first launches of the process and the
             first layouts of the model), 0.34 s its setup (the upload)
-    0.04 .. 0.06 s  each of the other 34 tests of the matrix (5 compress, 4 estimate, 10 decompress and 70 gip calls each, and
-            the model of its five combinations) and of the three parts of the batch
+    0.04 .. 0.06 s  each of the other 39 tests of the matrix (5 compress, 4 estimate, 10 decompress and 70 gip calls each, and
+            the model of its five combinations), the five base_survey ones at 0.04 s among them
+    0.06 .. 0.08 s  each of the three parts of the batch (12 combinations each)
     0.03 s  test_damage_is_reported_at_the_packet_the_model_gets_wrong_first
-    0.01 .. 0.02 s  each of the six refusal tests; everything else is under 0.005 s.
+    0.01 .. 0.02 s  each of the six older refusal tests and test_base_survey_beside_a_width_the_surveys_do_not_have;
+            test_base_auto_of_another_string_is_refused_before_any_launch and everything else is under 0.005 s.
 """
 import dataclasses
 
@@ -197,10 +205,10 @@ def run(H, T, combo, subset=None):
 # ---- the matrix --------------------------------------------------------------------------------------------------------
 
 def test_the_rotation_covers_every_pair():
-    assert len(VALID) == 175 and len(PAIRS) == 35
+    assert len(VALID) == 200 and len(PAIRS) == 40
     rows = [c + tuple(str(v) for v in ROTATION[c]) for c in VALID]
     values = [sorted({r[i] for r in rows}) for i in range(8)]
-    assert [len(v) for v in values] == [5, 7, 3, 2, 2, 2, 3, 2]
+    assert [len(v) for v in values] == [5, 8, 3, 2, 2, 2, 3, 2]
     for i in range(4, 8):                                      # a rotating keyword ...
         for j in range(8):                                     # ... against every axis and every other rotating keyword
             if i != j:
@@ -254,8 +262,11 @@ def test_sparse_beside_a_stored_list_is_refused_and_the_next_call_is_right(H, T,
 def test_base_beside_delta_and_base_auto_without_base_are_refused(H, T):
     from gpuar_amd import batch
     calls = [dict(base=T.bases, delta=delta) for delta in (True, False, M.DELTA_LIST, "auto", "survey")] + [dict(base_auto=True)]
+    calls += [dict(base=T.bases, delta=True, base_auto="survey"), dict(base=T.bases, delta="survey", base_auto="survey"), dict(base_auto="survey")]
     follows = [("auto", "base", "auto", "auto"), ("auto", "delta", "auto", "auto"), ("survey", "base_auto", "auto", "none"),
-               ("list", "delta_auto", "none", "auto"), ("2", "delta_survey", "list", "none"), ("none", "none", "none", "none")]
+               ("list", "delta_auto", "none", "auto"), ("2", "delta_survey", "list", "none"), ("none", "none", "none", "none"),
+               ("survey", "base_survey", "auto", "auto"), ("2", "base_survey", "none", "auto"), ("survey", "base_survey", "list", "none")]
+    assert len(calls) == len(follows) == 9
     for kw, follow in zip(calls, follows):
         with pytest.raises(H.GpuarError, match="base"):
             batch.compress(T.tensors, planes="auto", **kw)
@@ -263,6 +274,64 @@ def test_base_beside_delta_and_base_auto_without_base_are_refused(H, T):
             batch.estimate(T.tensors, planes="auto", **kw)
         checksum = ROTATION[follow][0]
         compare(batch.compress(T.tensors, checksum=checksum, **T.keywords(follow)), M.model(follow, checksum), ("after", sorted(kw)))
+    T.unchanged()
+    assert H.status() == 0
+
+
+def launches_of(monkeypatch, batch):
+    """the names of the functions of batch.H that take a stream -- the ones that launch or copy -- as they are called from here on"""
+    import inspect
+    seen = []
+    for name, fn in sorted(vars(batch.H).items()):
+        if inspect.isfunction(fn) and not name.startswith("_") and "stream" in inspect.signature(fn).parameters:
+            def wrapped(*args, _name=name, _fn=fn, **kwargs):
+                seen.append(_name)
+                return _fn(*args, **kwargs)
+            monkeypatch.setattr(batch.H, name, wrapped)
+    return seen
+
+
+def test_base_auto_of_another_string_is_refused_before_any_launch(H, T, monkeypatch):
+    """base_auto="auto" is no spelling of anything (delta="auto" is): GpuarError that names the values, from compress and estimate,
+    beside every value of `planes` -- planes="survey", which would launch first, too -- and with nothing launched."""
+    from gpuar_amd import batch
+    seen = launches_of(monkeypatch, batch)
+    for planes in M.PLANES_AXIS.values():
+        for call in (batch.compress, batch.estimate):
+            with pytest.raises(H.GpuarError, match=r'base_auto=\'auto\': False, True or "survey"'):
+                call(T.tensors, planes=planes, base=T.bases, base_auto="auto", stored="auto", sparse="auto")
+    with pytest.raises(H.GpuarError, match="base_auto"):
+        batch.compress(T.tensors, planes="survey", base_auto="auto")              # (without a base: that refusal comes first)
+    assert seen == [], seen
+    follow = ("survey", "base_survey", "none", "auto")
+    checksum = ROTATION[follow][0]
+    compare(batch.compress(T.tensors, checksum=checksum, **T.keywords(follow)), M.model(follow, checksum), ("after", "base_auto='auto'"))
+    assert "survey_xor_batch" in seen and "encode_batch" in seen
+    T.unchanged()
+    assert H.status() == 0
+
+
+def test_base_survey_beside_a_width_the_surveys_do_not_have(H, T, monkeypatch):
+    """base_auto="survey" decides from the surveys' rows, which are those of widths 1, 2, 4 and 8: beside planes=3, or a list with a
+    3 in it, compress and estimate raise GpuarError that names the width, before any launch -- where base_auto=True, which splits,
+    gets BAD_BATCH from the device for the same width.  The call behind each is right."""
+    from gpuar_amd import batch
+    seen = launches_of(monkeypatch, batch)
+    listed = [3 if b == 3 else w for b, w in enumerate(M.PLANES_AXIS["list"])]
+    for planes in (3, listed):
+        for call in (batch.compress, batch.estimate):
+            with pytest.raises(H.GpuarError, match=r'base_auto="survey": the widths are \(1, 2, 4, 8\), not \[3\]'):
+                call(T.tensors, planes=planes, base=T.bases, base_auto="survey")
+    assert seen == [], seen
+    follow = ("list", "base_survey", "auto", "none")
+    checksum = ROTATION[follow][0]
+    compare(batch.compress(T.tensors, checksum=checksum, **T.keywords(follow)), M.model(follow, checksum), ("after", "planes=3"))
+    assert seen.count("survey_planes_batch") == 1 and seen.count("survey_xor_batch") == 1 and seen.count("split_xor_batch") == 1, seen
+    with pytest.raises(H.GpuarError, match="BAD_BATCH"):
+        batch.compress(T.tensors, planes=3, base=T.bases, base_auto=True)
+    follow = ("survey", "base_survey", "auto", "auto")
+    checksum = ROTATION[follow][0]
+    compare(batch.compress(T.tensors, checksum=checksum, **T.keywords(follow)), M.model(follow, checksum), ("after", "BAD_BATCH"))
     T.unchanged()
     assert H.status() == 0
 

@@ -1,4 +1,4 @@
-"""The sequence of launches, staged uploads and synchronising reads that batch.py makes, pinned for every one of the 175 valid option
+"""The sequence of launches, staged uploads and synchronising reads that batch.py makes, pinned for every one of the 200 valid option
 combinations of tests/test_gpu_batch_matrix.py: the speed of that layer is this sequence, so a change of batch.py that keeps it keeps
 the speed, and one that adds a launch, a pinned upload or a wait shows up here and not in a timing.
 
@@ -16,7 +16,12 @@ The expected traces are tests/golden/batch_call_trace.json, every distinct trace
 The file was written by this module run as a script,
     python tests/test_gpu_batch_trace.py --write
 against the batch.py of the commit in front of the one that made batch.py one split, one upload, one partition and one prepare step:
-it is the record of that commit's behaviour and is never rewritten from later code (its first key says so).
+it is the record of that commit's behaviour and is never rewritten from later code (its first key says so).  It holds the 175
+combinations that commit had.  base_auto="survey" came later (the 25 combinations of the filter value base_survey): their traces
+are held to what batch.py's docstring says of the keyword instead (SURVEY_PREFIX) -- with the widths fixed one plane-survey
+launch, one XOR-survey launch, one synchronising read and ONE split; beside planes="survey" the two survey launches in front (with
+sparse="auto" both of them the XOR survey, the plain side with base pointers of 0), the same read and one split --, and behind
+the split to the trace of base_auto=True behind its second split and estimate, launch for launch by name.
 
 The recording runs in a process of its own (this module as a script, --record FILE) and the test compares what it wrote: a process
 that has wrapped torch.Tensor's methods, uploaded the batch a second time and driven 610 calls over one more stream leaves the
@@ -46,6 +51,14 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "batch_call_trace.json")
 WRITTEN_FROM = ("the batch.py of the commit in front of 'batch.py: one split, one upload, one partition, one prepare step' "
                 "(python tests/test_gpu_batch_trace.py --write); never from later code")
 COUNTS = ("n_buffers", "n_packets", "n_regions")
+RECORDED = [c for c in VALID if c[1] != "base_survey"]         # the combinations of the golden file
+# base_auto="survey" by batch.py's docstring: (planes="survey", sparse packets counted) -> the launches and the one synchronising
+# read up to and including the one split
+SURVEY_PREFIX = {
+    (False, False): ["survey_planes_batch", "survey_xor_batch", ".tolist", "split_xor_batch"],
+    (True, False): ["survey_planes_batch", "survey_xor_batch", ".tolist", "split_xor_batch"],
+    (True, True): ["survey_xor_batch", "survey_xor_batch", ".tolist", "split_xor_batch"],
+}
 READS = ("item", "tolist", "cpu")
 
 
@@ -127,7 +140,7 @@ def traces_of(batch, rec, T, combo):
 
 
 def all_traces(monkeypatch):
-    """{"planes-filter-stored-sparse:call": trace} over the 175 combinations"""
+    """{"planes-filter-stored-sparse:call": trace} over the 200 combinations"""
     from gpuar_amd import batch
     batch.H.load()
     T = Uploaded()
@@ -157,12 +170,14 @@ def test_every_combination_makes_the_recorded_launches_uploads_and_reads(tmp_pat
     assert list(golden)[0] == "written from" and golden["written from"] == WRITTEN_FROM
     want = {key: entry["trace"].split(";") if entry["trace"] else [] for entry in golden["traces"] for key in entry["calls"]}
     assert len(want) == sum(len(entry["calls"]) for entry in golden["traces"])
-    assert len({key.split(":")[0] for key in want}) == len(VALID) == 175
+    assert len({key.split(":")[0] for key in want}) == len(RECORDED) == 175 and len(VALID) == 200
     recorded = tmp_path / "traces.json"
     child = subprocess.run([sys.executable, os.path.abspath(__file__), "--record", str(recorded)], capture_output=True, text=True, timeout=300)
     assert child.returncode == 0, (child.returncode, child.stdout[-2000:], child.stderr[-4000:])
     with open(recorded) as f:
         got = json.load(f)
+    later = {key: trace for key, trace in got.items() if key.split("-")[1] == "base_survey"}
+    got = {key: trace for key, trace in got.items() if key not in later}
     assert sorted(got) == sorted(want)
     for key in want:
         assert got[key] == want[key], key
@@ -171,6 +186,38 @@ def test_every_combination_makes_the_recorded_launches_uploads_and_reads(tmp_pat
     events = {e.split()[0] for trace in got.values() for e in trace}
     assert {".item", ".tolist", ".pin_memory", "encode_batch", "decode_stream_batch", "move_bytes", "estimate_batch"} <= events
     assert sum(key.endswith(":estimate") for key in got) == 140 and sum(key.endswith(":from_gip") for key in got) == 120
+    check_base_survey(later, got)
+
+
+def names_of(trace):
+    """the launches of a trace by name, and between them the synchronising reads"""
+    return [e.split()[0] for e in trace if e != ".pin_memory"]
+
+
+def check_base_survey(later, got):
+    """the traces of base_auto="survey" against batch.py's docstring; `got`: the recorded traces of the other filter values"""
+    combos = [c for c in VALID if c[1] == "base_survey"]
+    assert len(combos) == 25 and sorted({key.split(":")[0] for key in later}) == sorted("-".join(c) for c in combos)
+    assert sum(key.endswith(":estimate") for key in later) == 20 and sum(key.endswith(":from_gip") for key in later) == 10
+    for c in combos:
+        for call in ("compress", "estimate"):
+            key = "-".join(c) + ":" + call
+            if key not in later:
+                assert call == "estimate" and c[2] == "list"
+                continue
+            trace, names = later[key], names_of(later[key])
+            prefix = SURVEY_PREFIX[c[0] == "survey", c[0] == "survey" and c[3] == "auto"]
+            assert names[:len(prefix)] == prefix, (key, names[:8])
+            assert [e for e in trace if e.split()[0].startswith("survey_")] == [f"{name} 14 51" for name in prefix[:2]], key
+            assert sum(name.startswith("split_") for name in names) == 1, (key, names)
+            # behind the split: what base_auto=True does behind its two splits and estimates -- but for the estimate launch, which
+            # _auto_base has made already and this path makes behind the split where stored or sparse (or estimate itself) needs one
+            rest = names[len(prefix):]
+            other = names_of(got["-".join((c[0], "base_auto") + c[2:]) + ":" + call])
+            tail = other[len(other) - other[::-1].index("split_xor_batch"):]
+            assert tail[:3] == ["estimate_batch", ".tolist", ".item"] and "estimate_batch" not in tail[3:], (key, tail)   # (_auto_base's own reads)
+            assert [n for n in rest if n != "estimate_batch"] == tail[3:], (key, rest, tail)
+            assert rest.count("estimate_batch") == (1 if call == "estimate" or c[2] == "auto" or c[3] == "auto" else 0), (key, rest)
 
 
 if __name__ == "__main__":

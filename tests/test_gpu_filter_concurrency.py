@@ -1,13 +1,13 @@
 """The filter, estimate and survey kernels under concurrent streams and host threads: the contract of include/gpuar_hip.h that
 tests/test_gpu_concurrency.py pins for the coders, compaction, CRC-32 and generate, here for the entry points added since --
 split_ / merge_planes, split_ / merge_delta, split_ / merge_xor (each a full-group launch and a tail launch), estimate,
-survey_planes, survey_delta, their batch forms and move_packets -- and for what gpuar_amd/batch.py composes from them
-(planes=, delta=, stored=, base=, base_auto=, "auto" and "survey").  Every call takes an explicit stream; a launch ORs its
+survey_planes, survey_delta, survey_xor, their batch forms and move_packets -- and for what gpuar_amd/batch.py composes from them
+(planes=, delta=, stored=, base=, base_auto=, sparse=, "auto" and "survey").  Every call takes an explicit stream; a launch ORs its
 flags into its own status word and into no other; a launch without a word uses the fallback word, which status() reports once.
 
 Every test works the same way: a serial pass (one launch at a time, synchronised) is pinned against existing host code --
 planes_ref.numpy_split, delta_ref.numpy_split_delta, xor_ref.numpy_split_xor, hip.estimate_host, hip.survey_planes_host,
-hip.survey_delta_host, the reference encoder on 64-packet windows, zlib.crc32 --; then the same work runs concurrently and must
+hip.survey_delta_host, hip.survey_xor_host, the reference encoder on 64-packet windows, zlib.crc32 --; then the same work runs concurrently and must
 give the same bytes, with every status word exactly what its own launch should report.  Everything is integer-exact.
 Comparisons run on the device; one copy of the verdicts per test.
 
@@ -30,11 +30,24 @@ goes round the chip two to four times and eight of them contend for it).
 2. Fan-out with status isolation, one family at a time, eight streams: planes / delta / XOR (single split, a copy, merge in
    place; the batch forms over a dozen buffers, stream 1's batch with one unusable descriptor), estimate and both surveys
    (single and batch, canaries behind every row and in the rows a widths mask leaves out, stream 1 with a misaligned buffer),
+   the XOR survey (single and batch; both outputs, the est rows alone or the scan rows alone by stream, the output that was not
+   asked for keeping every canary; base pointers of 0 in every batch; stream 1 with a base pointer that is 8 mod 16),
    move_packets (stream 1 with a region of 8193 bytes).  BAD_BATCH in stream 1's words and in no other.
 3. The fallback word: each batch entry point with d_status=None and one unusable descriptor; status() reports BAD_BATCH once.
 4. Mixed co-residency: a 256 MiB throughput encode next to survey_delta, estimate_batch, split_xor, merge_delta in place,
-   move_packets and crc32_batch, the encoder enqueued first or last.
-5. batch.compress / decompress from six threads, each with its own stream and one keyword family.
+   move_packets, crc32_batch and survey_xor_batch, the encoder enqueued first or last.
+5. batch.compress / decompress from seven threads, each with its own stream and one keyword family.
+
+Time, pytest --durations=0 on an MI355X, with tests/test_gpu_batch_trace.py behind it: 13 passed in 10.6 s, 4.0 s of it that
+module's one test and 2 s importing torch and collecting.
+    1.39 s  test_thread_batch_compress_families (seven families; the host rule of the seventh -- eight numpy splits, estimates and
+            scans of its 16 MiB tensor -- takes 0.7 s on one core)
+    1.38 s  setup of test_stream_order[2] (the eight workloads and their references; survey_xor_host takes 0.3 s on one core for
+            each of the four 16 MiB workloads)
+    0.46 s, 0.39 s  test_stream_order[2], [6] (33 cases each, two of them the XOR survey's)
+    0.50 s, 0.15 s  test_mixed_co_residency[encoder_first], [encoder_last]
+    0.05 s  test_survey_xor_fan_out, test_estimate_and_survey_fan_out and each test_filter_fan_out
+    0.04 s  test_fallback_word_of_the_batch_entry_points; 0.02 s test_move_packets_fan_out
 
 Not covered here: the grid-stride loops of the plane, delta, XOR and move kernels start at 2^22 workgroups (32 GiB, or four million
 buffers); tests/test_gpu_grid_cap.py runs their later passes on a build whose cap is 3.  Tensors on a device that is not the current one.  Fixed seeds throughout.
@@ -169,7 +182,8 @@ def _describe(i, what):
 @pytest.fixture(scope="module")
 def W(H):
     """Each workload: its bytes, its XOR base, and the references of every single-buffer entry point at the workload's width
-    (survey_delta at the stream's mask) as images on the device, canaries behind them."""
+    (survey_delta at the stream's mask) as images on the device, canaries behind them.  The XOR survey has a base of its own
+    (`xbase`, _survey_base): against the uniform base of the filters every packet of the XORed bytes is alike."""
     ws = []
     for i, (w, _kind, n) in enumerate(WORKLOADS):
         x = _host_input(i)
@@ -181,12 +195,25 @@ def W(H):
         base[:n] = b
         sp_img, stride = _rows_image(H.survey_planes_host(raw), npk)
         sd_img, _stride = _rows_image(H.survey_delta_host(raw, MASKS[i]), npk)
+        xb = _survey_base(x, 700 + i)
+        xe, xs = H.survey_xor_host(raw, xb.tobytes())
         ws.append(dict(i=i, w=w, n=n, npk=npk, S=_r16(n) + GUARD, host=x, base=_dev(base), stride=stride,
                        img=dict(x=_image(x), planes=_image(P.numpy_split(x, w)), delta=_image(D.numpy_split_delta(x, w)),
                                 xor=_image(X.numpy_split_xor(x, b, w))),
-                       est=_est_image(H.estimate_host(raw), npk), sp=sp_img, sd=sd_img))
+                       est=_est_image(H.estimate_host(raw), npk), sp=sp_img, sd=sd_img,
+                       xbase=_image(xb), xe=_rows_image(xe, npk)[0], xs=_rows_image(xs, npk)[0]))
     torch.cuda.synchronize()
     return ws
+
+
+def _survey_base(x, seed):
+    """A base for the XOR survey of x (tests/test_gpu_xor_survey.py::_base_of): independent uniform bytes in the first half of every
+    third half-packet, x elsewhere -- so that the XORed bytes have packets that are all zeros, half zeros and, at the wider widths,
+    neither, and the scan rows are not one word throughout."""
+    b = x.copy()
+    pick = (np.arange(x.size) // (PACKET // 2)) % 3 == 0
+    b[pick] = np.random.default_rng([71, seed]).integers(0, 256, x.size, dtype=np.uint8)[pick]
+    return b
 
 
 def _layout(sizes):
@@ -201,7 +228,10 @@ class Batch:
     """A dozen buffers in one arena (tests/test_gpu_delta.py::_layout: GUARD canaries behind each): an empty one, the packet
     boundaries, groups and tails, mixed widths, filter flags and bases; `extra`: one more buffer (bytes, base bytes, width).
     `bad`: buffer BAD carries an unusable descriptor -- "planes": width 3; "delta": filter word 2; "xor": a base pointer that
-    is 8 mod 16; "ptr": a buffer pointer that is 8 mod 16 (for the calls that only read) -- and the references leave it alone.
+    is 8 mod 16; "ptr": a buffer pointer that is 8 mod 16 (for the calls that only read); "base_ptr": a base pointer of the XOR
+    survey that is 8 mod 16 -- and the references leave it alone.  The XOR survey reads the bases of the filter through base
+    pointers of its own (xbase_ptrs): 0, which is "no base", for the buffers without one and for every third buffer besides.  Every
+    second base is a _survey_base of its buffer, the others are uniform bytes.
     Descriptors on the device; references as arena images."""
 
     def __init__(self, H, seed, mask, extra=None, bad=None):
@@ -212,6 +242,7 @@ class Batch:
         based = [1, 1, 1, 0, 1, 1, 0, 1, 1, 1, 0, 1]
         hosts = [D.bytes_of(D.KINDS[(seed + b) % 3], n, widths[b], seed=1000 * seed + b) for b, n in enumerate(sizes)]
         bases = [rng.integers(0, 256, n, dtype=np.uint8) for n in sizes]
+        bases = [_survey_base(h, 1000 * seed + b) if b % 2 == 0 else q for b, (h, q) in enumerate(zip(hosts, bases))]
         if extra is not None:
             hosts.append(extra[0])
             bases.append(extra[1])
@@ -230,14 +261,18 @@ class Batch:
         skip = BAD if bad else None
         self.split = {fam: self._arena(want[fam], skip) for fam in FAMILIES}
         self.merged = self._arena(hosts, skip)                     # what merging `split` in place leaves
-        est, sp, sd = [], [[], [], [], []], [[], [], [], []]
+        self.xbased = [bool(f) and b % 3 != 2 for b, f in enumerate(based)]
+        assert self.xbased[BAD] and True in self.xbased[:BAD] and False in self.xbased[BAD + 1:]
+        est, sp, sd, xe, xs = [], [[], [], [], []], [[], [], [], []], [[], [], [], []], [[], [], [], []]
         for b, h in enumerate(hosts):
             mine = self.fp[b + 1] - self.fp[b]
             left = b == skip
             est += [CANARY32] * mine if left else H.estimate_host(h.tobytes())
-            for rows, got in ((sp, H.survey_planes_host(h.tobytes())), (sd, H.survey_delta_host(h.tobytes(), mask))):
+            xor = H.survey_xor_host(h.tobytes(), (bases[b] if self.xbased[b] else np.zeros_like(h)).tobytes())
+            for rows, got in ((sp, H.survey_planes_host(h.tobytes())), (sd, H.survey_delta_host(h.tobytes(), mask)), (xe, xor[0]), (xs, xor[1])):
                 for j in range(4):
                     rows[j] += [CANARY32] * mine if left or got[j] is None else got[j]
+        self.xe, self.xs = _rows_image(xe, self.npk)[0], _rows_image(xs, self.npk)[0]
         self.mask = mask
         self.est = _est_image(est, self.npk)
         self.sp, self.stride = _rows_image(sp, self.npk)
@@ -265,6 +300,14 @@ class Batch:
         """The buffers' pointers in `arena` (bad="ptr": buffer BAD's is misaligned)."""
         p = [arena.data_ptr() + o for o in self.offs]
         if self.bad == "ptr":
+            p[BAD] += 8
+        return torch.tensor(p, dtype=torch.int64, device="cuda")
+
+    def xbase_ptrs(self, arena):
+        """The XOR survey's base pointers into `arena`, which holds the bases as self.base does: 0 where xbased says none
+        (bad="base_ptr": buffer BAD's is misaligned)."""
+        p = [arena.data_ptr() + o if f else 0 for o, f in zip(self.offs, self.xbased)]
+        if self.bad == "base_ptr":
             p[BAD] += 8
         return torch.tensor(p, dtype=torch.int64, device="cuda")
 
@@ -346,6 +389,8 @@ def _cases(H, k, bt, mv):
     e, rows = _blank(k["est"].numel()), _blank(k["sp"].numel())
     E, ROWS = _blank(bt.est.numel()), _blank(bt.sp.numel())
     pa, pb = bt.ptrs(A), bt.ptrs(B)
+    xe, xs, XE, XS = _blank(k["xe"].numel()), _blank(k["xs"].numel()), _blank(bt.xe.numel()), _blank(bt.xs.numel())
+    xb = bt.xbase_ptrs(B)                                      # (the survey's bases stand in B, fed like the buffers in A)
     cases = []
     for fam in FAMILIES:
         for merge in (False, True):
@@ -373,6 +418,12 @@ def _cases(H, k, bt, mv):
         Case(f"survey_delta_batch widths {bt.mask}, {bt.describe()} with {tag}", [(bt.src, A)],
              lambda s, word: H.survey_delta_batch(pa, bt.d_bytes, bt.d_fp, bt.n, bt.npk, d_est=_as_rows(ROWS, bt.stride), stream=s, d_status=word,
                                                   widths=bt.mask), [(ROWS, bt.sd)]),
+        Case(f"survey_xor, {tag}", [(k["img"]["x"], a), (k["xbase"], b)],
+             lambda s, _w: H.survey_xor(a, b, d_est=_as_rows(xe, k["stride"]), d_scan=_as_rows(xs, k["stride"]), n_bytes=n, stream=s),
+             [(xe, k["xe"]), (xs, k["xs"])]),
+        Case(f"survey_xor_batch, {bt.describe()} with {tag}", [(bt.src, A), (bt.base, B)],
+             lambda s, word: H.survey_xor_batch(pa, bt.d_bytes, bt.d_fp, xb, bt.n, bt.npk, d_est=_as_rows(XE, bt.stride),
+                                                d_scan=_as_rows(XS, bt.stride), stream=s, d_status=word), [(XE, bt.xe), (XS, bt.xs)]),
     ]
     # move_packets reads its own source, which the producer fills from a copy of it
     image = mv.src.clone()
@@ -596,6 +647,66 @@ def test_estimate_and_survey_fan_out(H, W):
     assert H.status() == 0, "the single-buffer forms report into the fallback word and had nothing to report"
 
 
+def test_survey_xor_fan_out(H, W):
+    """survey_xor and survey_xor_batch on each of eight streams at once, into est and scan rows with canaries behind them.  Stream i
+    asks for both outputs, for the est rows alone or for the scan rows alone, by i mod 3: the output that was not asked for keeps
+    every canary under contention too.  Stream 1's batch has a base pointer that is 8 mod 16: BAD_BATCH in its word and in no
+    other, and that buffer's columns keep the canary in both outputs.  Buffers whose base pointer is 0 get the rows of their
+    own bytes."""
+    k8 = len(W)
+    bts = [Batch(H, 20 + i, MASKS[i], bad="base_ptr" if i == 1 else None) for i in range(k8)]
+    names = ("xe", "xs", "XE", "XS")
+    asked = [(i % 3 != 2, i % 3 != 1) for i in range(k8)]                     # (est rows, scan rows)
+    assert asked[:3] == [(True, True), (True, False), (False, True)]
+    bufs = []
+    for i, (k, bt) in enumerate(zip(W, bts)):
+        wants = dict(xe=k["xe"], xs=k["xs"], XE=bt.xe, XS=bt.xs)
+        for name in names:
+            if not asked[i][name in ("xs", "XS")]:
+                wants[name] = _blank(wants[name].numel())
+        bufs.append(dict(want=wants, src=bt.ptrs(bt.src), xbase=bt.xbase_ptrs(bt.base), **{name: _blank(wants[name].numel()) for name in names}))
+    words = _status(2 * k8)
+
+    def chain(i, s, word, sync):
+        k, bt, u = W[i], bts[i], bufs[i]
+        est, scan = asked[i]
+        steps = [
+            lambda: H.survey_xor(k["img"]["x"], k["xbase"], d_est=_as_rows(u["xe"], k["stride"]) if est else False,
+                                 d_scan=_as_rows(u["xs"], k["stride"]) if scan else False, n_bytes=k["n"], stream=s),
+            lambda: H.survey_xor_batch(u["src"], bt.d_bytes, bt.d_fp, u["xbase"], bt.n, bt.npk, d_est=_as_rows(u["XE"], bt.stride) if est else False,
+                                       d_scan=_as_rows(u["XS"], bt.stride) if scan else False, stream=s, d_status=word),
+        ]
+        for step in steps:
+            step()
+            if sync:
+                torch.cuda.synchronize()
+
+    def check(tag, against):
+        return [(f"{_describe(i, call)}{', ' + bts[i].describe() if call.endswith('batch') else ''}, {what} rows "
+                 f"({'asked for' if asked[i][what == 'scan'] else 'NOT asked for'}){tag}: differs from {against}, or a canary behind a row, in "
+                 "a column that is left alone or in an output that was not asked for is gone", _same(u[name], u["want"][name]))
+                for i, u in enumerate(bufs) for name, call, what in zip(names, ("survey_xor", "survey_xor", "survey_xor_batch", "survey_xor_batch"),
+                                                                        ("est", "scan", "est", "scan"))]
+
+    verdicts = []
+    for i in range(k8):
+        chain(i, None, words[i:i + 1], True)
+    verdicts += check(" (serial)", "the reference")
+    for u in bufs:
+        for name in names:
+            u[name].fill_(CANARY)
+    streams = _streams(k8)
+    torch.cuda.synchronize()
+    for i, s in enumerate(streams):
+        chain(i, s, words[k8 + i:k8 + i + 1], False)
+    torch.cuda.synchronize()
+    verdicts += check("", "the serial result")
+    expected = [H.STATUS_BAD_BATCH if i == 1 else 0 for i in range(k8)] * 2
+    _words(verdicts, words, expected, [f"stream {i % k8}: survey_xor_batch{' (serial)' if i < k8 else ''}" for i in range(2 * k8)])
+    _fail_on(verdicts)
+    assert H.status() == 0, "survey_xor reports into the fallback word and had nothing to report"
+
+
 def _move_sets():
     return [Moves(30 + i, 64 if i < 4 else 1024, bad=i == 1) for i in range(8)]
 
@@ -631,8 +742,10 @@ def test_move_packets_fan_out(H):
 # ---------------------------------------------------------------------------------------------------------------------
 def test_fallback_word_of_the_batch_entry_points(H):
     """Each batch entry point that can report BAD_BATCH -- split_ and merge_planes_batch, _delta_batch and _xor_batch,
-    estimate_batch, survey_planes_batch, survey_delta_batch, move_packets -- with d_status=None and one unusable descriptor,
-    on a non-blocking stream, one after another: status() returns BAD_BATCH after the call and 0 when asked again."""
+    estimate_batch, survey_planes_batch, survey_delta_batch, survey_xor_batch (a base pointer that is 8 mod 16), move_packets --
+    with d_status=None and one unusable descriptor, on a non-blocking stream, one after another: status() returns BAD_BATCH after
+    the call and 0 when asked again.  The XOR survey's rows are compared too: the columns of the buffer with the unusable base keep
+    their canary in both outputs."""
     s = torch.cuda.Stream()
     calls = []
     for fam in FAMILIES:
@@ -652,6 +765,11 @@ def test_fallback_word_of_the_batch_entry_points(H):
         ("survey_delta_batch", lambda: H.survey_delta_batch(src, bt.d_bytes, bt.d_fp, bt.n, bt.npk, d_est=_as_rows(rows, bt.stride), stream=s,
                                                             d_status=None)),
     ]
+    xt = Batch(H, 53, WIDTHS, bad="base_ptr")
+    xe, xs = _blank(xt.xe.numel()), _blank(xt.xs.numel())
+    xsrc, xbase = xt.ptrs(xt.src), xt.xbase_ptrs(xt.base)
+    calls.append(("survey_xor_batch", lambda: H.survey_xor_batch(xsrc, xt.d_bytes, xt.d_fp, xbase, xt.n, xt.npk, d_est=_as_rows(xe, xt.stride),
+                                                                d_scan=_as_rows(xs, xt.stride), stream=s, d_status=None)))
     mv = Moves(52, 16, bad=True)
     calls.append(("move_packets", lambda: mv.run(H, s, None)))
     torch.cuda.synchronize()
@@ -662,6 +780,12 @@ def test_fallback_word_of_the_batch_entry_points(H):
         seen.append((name, H.status(), H.status()))
     wrong = [f"{name}: status() gave {first:#x}, then {second:#x}" for name, first, second in seen if (first, second) != (H.STATUS_BAD_BATCH, 0)]
     assert not wrong, f"the fallback word after a launch without a word of its own (want {H.STATUS_BAD_BATCH:#x}, then 0): " + "; ".join(wrong)
+    _fail_on([(f"survey_xor_batch without a status word: the {what} rows differ from the reference, or buffer {BAD}'s columns lost their canary",
+               _same(got, want)) for what, got, want in (("est", xe, xt.xe), ("scan", xs, xt.xs))])
+    # and the other way round: the same launch with a word of its own reports there and leaves the fallback word alone
+    word = _status(1)
+    H.survey_xor_batch(xsrc, xt.d_bytes, xt.d_fp, xbase, xt.n, xt.npk, d_est=_as_rows(xe, xt.stride), d_scan=False, stream=s, d_status=word)
+    assert (H.status(), int(word.item())) == (0, H.STATUS_BAD_BATCH), "survey_xor_batch with a status word of its own: the fallback word, the word"
     assert H.status() == 0
 
 
@@ -672,8 +796,8 @@ def test_fallback_word_of_the_batch_entry_points(H):
 def test_mixed_co_residency(H, oracle, W, order):
     """The LDS-heavy kernels next to the encoder and to each other: a throughput encode of 256 MiB on stream A, survey_delta of
     workload 7 on B, estimate_batch over all eight inputs on C (128 KiB of LDS per workgroup), split_xor of workload 6 on D,
-    merge_delta in place of workload 5 on E, move_packets on F, crc32_batch over all eight inputs on G; the encoder enqueued
-    first or last.  Every output equals its serial result (pinned: the slots against the reference encoder on 64-packet
+    merge_delta in place of workload 5 on E, move_packets on F, crc32_batch over all eight inputs on G, survey_xor_batch over all
+    eight inputs against their survey bases (workloads 0 and 2: base pointer 0) on H; the encoder enqueued first or last.  Every output equals its serial result (pinned: the slots against the reference encoder on 64-packet
     windows, the CRCs against zlib.crc32, the rest against the references of the fixture) and every status word is 0."""
     from test_gpu_concurrency import _slots_equal, _windows
     n = 256 * MiB + 5 * PACKET + 13
@@ -699,10 +823,26 @@ def test_mixed_co_residency(H, oracle, W, order):
     crc_serial = H.crc32_batch(d_ptrs, d_bytes, d_fp, nb, bpk, d_status=word[2:3])
     mv = Moves(70, 1024)
     mv.run(H, None, word[3:4])
+    # the XOR survey over the eight inputs: base pointer 0 for workloads 0 and 2, whose rows are those of their own bytes
+    d_xbase = torch.tensor([0 if k["i"] in (0, 2) else k["xbase"].data_ptr() for k in W], dtype=torch.int64, device="cuda")
+    x_want = []
+    for k in W:
+        if k["i"] in (0, 2):
+            x_want.append(H.survey_xor_host(k["host"].tobytes(), bytes(k["n"])))
+        else:
+            x_want.append([[[v & 0xFFFFFFFF for v in row] for row in _as_rows(k[name], k["stride"])[:, :k["npk"]].cpu().tolist()] for name in ("xe", "xs")])
+    xe_want, xs_want = (_rows_image([sum((x[which][j] for x in x_want), []) for j in range(4)], bpk) for which in (0, 1))
+    x_stride = xe_want[1]
+    xword = _status(2)
+    xe_serial, xs_serial = _blank(xe_want[0].numel()), _blank(xs_want[0].numel())
+    H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_xbase, nb, bpk, d_est=_as_rows(xe_serial, x_stride), d_scan=_as_rows(xs_serial, x_stride),
+                       d_status=xword[0:1])
     torch.cuda.synchronize()
     verdicts = [("estimate_batch over the eight inputs (serial): differs from estimate_host", _same(est_serial[:bpk], est_want)),
                 ("crc32_batch over the eight inputs (serial): differs from zlib.crc32", _same(crc_serial[:bpk], crc_want)),
-                (f"{mv.describe()} (serial): differs from the reference", _same(mv.dst, mv.want))]
+                (f"{mv.describe()} (serial): differs from the reference", _same(mv.dst, mv.want)),
+                ("survey_xor_batch over the eight inputs (serial): est rows differ from survey_xor_host", _same(xe_serial, xe_want[0])),
+                ("survey_xor_batch over the eight inputs (serial): scan rows differ from survey_xor_host", _same(xs_serial, xs_want[0]))]
     _words(verdicts, word, [0] * 4, ["encode (serial)", "estimate_batch (serial)", "crc32_batch (serial)", "move_packets (serial)"])
     mv.dst.fill_(CANARY)
 
@@ -714,7 +854,8 @@ def test_mixed_co_residency(H, oracle, W, order):
     merged = k5["img"]["delta"].clone()
     crc = _blank(_r16(4 * (bpk + 2)))
     words = _status(4)
-    sA, sB, sC, sD, sE, sF, sG = _streams(7)
+    xe, xs = _blank(xe_want[0].numel()), _blank(xs_want[0].numel())
+    sA, sB, sC, sD, sE, sF, sG, sH = _streams(8)
     launches = [
         lambda: H.survey_delta(k7["img"]["x"], d_est=_as_rows(rows, k7["stride"]), n_bytes=k7["n"], stream=sB, widths=MASKS[7]),
         lambda: H.estimate_batch(d_ptrs, d_bytes, d_fp, nb, bpk, d_est=_as_est(est), stream=sC, d_status=words[1:2]),
@@ -722,6 +863,8 @@ def test_mixed_co_residency(H, oracle, W, order):
         lambda: H.merge_delta(merged, k5["w"], d_out=merged, n_bytes=k5["n"], stream=sE),
         lambda: mv.run(H, sF, words[2:3]),
         lambda: H.crc32_batch(d_ptrs, d_bytes, d_fp, nb, bpk, d_crc=_as_est(crc), stream=sG, d_status=words[3:4]),
+        lambda: H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_xbase, nb, bpk, d_est=_as_rows(xe, x_stride), d_scan=_as_rows(xs, x_stride), stream=sH,
+                                   d_status=xword[1:2]),
     ]
     encoder = lambda: H.encode(d_in, slots, stream=sA, d_status=words[0:1], mode="throughput")
     launches = [encoder] + launches if order == "encoder_first" else launches + [encoder]
@@ -740,7 +883,10 @@ def test_mixed_co_residency(H, oracle, W, order):
         (f"{order}: stream F: {mv.describe()}: differs from the serial result", _same(mv.dst, mv.want)),
         (f"{order}: stream G: crc32_batch over the eight inputs: differs from the serial result, or wrote behind its {bpk} CRCs",
          _same(_as_est(crc)[:bpk], crc_serial[:bpk]) & _as_est(crc)[bpk:].eq(CANARY32 - (1 << 32)).all()),
+        (f"{order}: stream H: survey_xor_batch over the eight inputs: rows differ from the serial result, or a canary behind a row is gone",
+         _same(xe, xe_serial) & _same(xs, xs_serial)),
     ]
+    _words(verdicts, xword, [0] * 2, ["survey_xor_batch (serial)", f"{order}: stream H: survey_xor_batch"])
     _words(verdicts, words, [0] * 4, [f"{order}: stream {s}: {f}" for s, f in (("A", "encode"), ("C", "estimate_batch"), ("F", "move_packets"),
                                                                               ("G", "crc32_batch"))])
     _fail_on(verdicts)
@@ -756,7 +902,7 @@ def _cut(a, n_bytes):
 
 
 def _thread_families():
-    """Six keyword families of batch.compress, each with its inputs as host arrays of their own type: [(name, arrays, bases or
+    """Seven keyword families of batch.compress, each with its inputs as host arrays of their own type: [(name, arrays, bases or
     None, keywords)].  Every batch has an empty tensor, a one-byte tensor, PACKET and PACKET + 1 bytes, tensors from the tables
     of DESIGN.md 4.9 / 4.10 for which "auto" and "survey" decide each way (TABLE_DELTA_WINS, TABLE_BASE_WINS and the others),
     and one tensor of about 16 MiB."""
@@ -790,6 +936,12 @@ def _thread_families():
     for b, n in enumerate(sizes):
         mask += [b >= 5 and p % 3 == 1 for p in range((n + PACKET - 1) // PACKET)]       # (buffers 0-4 keep every packet coded)
     fams.append(("planes=4, stored=a fixed mask", arrays, None, dict(planes=4, stored=mask)))
+    # width and base chosen together, raw and sparse packets counted: the inputs and bases of the base_auto family, and the big tensor
+    # against a base from which every 64th byte differs by a bit: the host rule gives widths 2, 1, 2, 1 and 8 behind the four small
+    # tensors, keeps three bases of five and drops two, and keeps 1793 of the big tensor's 2051 packets as sparse records
+    arrays = small + [prs[name][0] for name in names] + [big]
+    fams.append(("base=[...], base_auto=survey, planes=survey, stored=auto, sparse=auto", arrays, list(bases),
+                 dict(base_auto="survey", planes="survey", stored="auto", sparse="auto")))
     return fams
 
 
@@ -808,15 +960,44 @@ def _total(H, coded):
     return sum(H.estimate_host(coded.tobytes()))
 
 
+def _kinds_of(H, coded, stored_on, sparse_on):
+    """(kind, bytes it is kept in) of every packet of the bytes `coded`: hip.sparse_rule on the host estimate and the host scan word
+    (without sparse: hip.stored_rule on the estimate) -- a sparse packet its record, a raw one its bytes, a coded one its estimate"""
+    raw = coded.tobytes()
+    est = H.estimate_host(raw)
+    scan = H.sparse_scan_host(raw) if sparse_on else [None] * len(est)
+    out = []
+    for p, (e, s) in enumerate(zip(est, scan)):
+        n = min(PACKET, coded.size - p * PACKET)
+        kind = H.sparse_rule(s, e, n, stored_on) if sparse_on else int(stored_on and H.stored_rule(e, n))
+        out.append((kind, H.sparse_len(s >> 8) if kind == H.KIND_SPARSE else n if kind == H.KIND_RAW else e))
+    return out
+
+
 def _host_rule(H, hosts, bases, kw, elem_sizes):
     """What the host rules make of a batch: (widths, filter flags or None, based or None, the bytes that are coded per buffer, the
-    stored flags per packet or None) -- hip.choose_planes / choose_filter on the host surveys, the `+ n_packets` tie rule of
-    delta="auto" and base_auto on host estimates, hip.stored_rule on the host estimate of the coded bytes."""
+    stored flags per packet or None -- with sparse="auto": the kinds) -- hip.choose_planes / choose_filter on the host surveys, the
+    `+ n_packets` tie rule of delta="auto" and base_auto on host estimates, hip.stored_rule on the host estimate of the coded bytes;
+    planes="survey" with base_auto="survey": hip.choose_filter on the totals of the numpy splits of the bytes as they are and
+    XORed, every packet counted as hip.sparse_rule keeps it (a buffer without a base or without packets: hip.choose_planes of the
+    first)."""
     n = len(hosts)
     npk = [H.packet_count(h.size) for h in hosts]
     planes, delta = kw.get("planes"), kw.get("delta")
-    flags = None
-    if planes == "survey" and delta == "survey":
+    stored_on, sparse_on = kw.get("stored") == "auto", kw.get("sparse") == "auto"
+    flags = based = None
+    if planes == "survey" and kw.get("base_auto") == "survey":
+        kept = lambda coded: sum(size for _kind, size in _kinds_of(H, coded, stored_on, sparse_on))
+        widths, based = [], []
+        for h, q, p in zip(hosts, bases, npk):
+            plain = [kept(P.numpy_split(h, w)) for w in WIDTHS]
+            if q is None or p == 0:
+                choice = (H.choose_planes(plain, p), False)
+            else:
+                choice = H.choose_filter(plain, [kept(X.numpy_split_xor(h, q, w)) for w in WIDTHS], p)
+            widths.append(choice[0])
+            based.append(choice[1])
+    elif planes == "survey" and delta == "survey":
         choice = [H.choose_filter(totals_of(H.survey_planes_host(h.tobytes()), h.size), totals_of(H.survey_delta_host(h.tobytes()), h.size), p)
                   for h, p in zip(hosts, npk)]
         widths, flags = [c[0] for c in choice], [c[1] for c in choice]
@@ -828,8 +1009,7 @@ def _host_rule(H, hosts, bases, kw, elem_sizes):
         flags = [p > 0 and _total(H, D.numpy_split_delta(h, w)) + p <= _total(H, P.numpy_split(h, w)) for h, w, p in zip(hosts, widths, npk)]
     elif isinstance(delta, list):
         flags = delta
-    based = None
-    if bases is not None:
+    if bases is not None and based is None:
         based = [q is not None and p > 0 and _total(H, X.numpy_split_xor(h, q, w)) + p <= _total(H, P.numpy_split(h, w))
                  for h, q, w, p in zip(hosts, bases, widths, npk)]
     coded = []
@@ -841,7 +1021,9 @@ def _host_rule(H, hosts, bases, kw, elem_sizes):
         else:
             coded.append(P.numpy_split(h, w))
     stored = kw.get("stored")
-    if isinstance(stored, str):
+    if sparse_on:
+        stored = [kind for c in coded for kind, _size in _kinds_of(H, c, stored_on, True)]
+    elif isinstance(stored, str):
         stored = [H.stored_rule(e, min(PACKET, c.size - p * PACKET)) for c in coded for p, e in enumerate(H.estimate_host(c.tobytes()))]
     return widths, flags, based, coded, stored
 
@@ -853,12 +1035,13 @@ def _same_or_none(a, b):
 
 
 def test_thread_batch_compress_families(H, oracle):
-    """batch.compress(..., stream=s) then batch.decompress(c, stream=s) from six threads at once, each with its own stream and
+    """batch.compress(..., stream=s) then batch.decompress(c, stream=s) from seven threads at once, each with its own stream and
     one keyword family: the paths that allocate and free temporaries (the split copy, both halves of base_auto, the slots)
     between launches on a side stream while other threads do the same.  The serial pass pins every family: widths, filter
     flags, kept bases and the stored mask against the host rules, the first 64 packets of every buffer without a stored packet
     against the reference encoder on the host composition of the references, the CRCs against zlib.crc32 of the original
-    bytes.  The concurrent pass reproduces stream, offsets, crc32, stored, raw, raw_offsets and the three host lists exactly,
+    bytes.  The concurrent pass reproduces stream, offsets, crc32, stored, raw, raw_offsets, sparse, sparse_offsets and the three
+    host lists exactly,
     and every buffer round-trips."""
     from gpuar_amd import batch
     fams = _thread_families()
@@ -888,6 +1071,10 @@ def test_thread_batch_compress_families(H, oracle):
             assert True in flags[4:] and False in flags[4:], f"{tag}: the rule decides one way only: {flags}"
         if based is not None:
             assert True in based[4:] and False in based[4:], f"{tag}: the rule decides one way only: {based}"
+        if r["kw"].get("sparse") == "auto":                    # the kinds themselves: 0 coded, 1 raw, 2 sparse
+            assert c.stored.cpu().tolist() == stored, f"{tag}: the kinds differ from the host rule"
+            assert set(stored) == {H.KIND_CODED, H.KIND_RAW, H.KIND_SPARSE}, f"{tag}: the rule never keeps a packet as {sorted({0, 1, 2} - set(stored))}"
+            assert len(set(widths[4:])) > 1, f"{tag}: one width throughout: {widths}"
         got_stored = None if c.stored is None else [bool(v) for v in c.stored.cpu().tolist()]
         assert got_stored == (None if stored is None else [bool(v) for v in stored]), f"{tag}: the stored mask differs from the host rule"
         if stored is not None:
@@ -931,7 +1118,7 @@ def test_thread_batch_compress_families(H, oracle):
         assert (c.planes, c.delta, c.based) == (want.planes, want.delta, want.based), \
             f"{tag}: planes / delta / based {(c.planes, c.delta, c.based)}, the serial run chose {(want.planes, want.delta, want.based)}"
         assert (c.first_packet, c.sizes) == (want.first_packet, want.sizes), tag
-        for field in ("stream", "offsets", "crc32", "stored", "raw", "raw_offsets"):
+        for field in ("stream", "offsets", "crc32", "stored", "raw", "raw_offsets", "sparse", "sparse_offsets"):
             verdicts.append((f"{tag}: {field} differs from the serial run's", _same_or_none(getattr(c, field), getattr(want, field))))
         for b, (o, v) in enumerate(zip(outs, r["tensors"])):
             verdicts.append((f"{tag}: batch.decompress buffer {b} ({o.numel()} bytes) does not round-trip", _same(o, _bytes_view(v))))
