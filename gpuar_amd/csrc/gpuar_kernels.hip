@@ -3643,55 +3643,121 @@ __device__ __forceinline__ void survey_count8(uint32_t *hist, uint32_t lo, uint3
     }
 }
 
-// one supergroup: `len` bytes (1 .. 65536) at `sg` (16-byte aligned), whose first packet is entry `first` of every row; the whole
-// workgroup, with the histograms clear on entry and on return
-__device__ __forceinline__ void survey_supergroup(const SurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, CrcQuad *lds,
-                                                  uint64_t (*sums)[16]) {
-    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
-    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, eighths / packets 4 half .. + 3
-    const bool full = len == kSurveyBytes;                                   // workgroup-uniform
-    if (full) {
-        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + wave * kPacket + kCrcChunk * lane));
-        CrcQuad q[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
-        const uint32_t c = lane & 7u;
-        uint32_t slot[8];
-#pragma unroll
-        for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            survey_count8(hist, q[k].x, q[k].y, c, slot);
-            survey_count8(hist, q[k].z, q[k].w, c, slot);
-        }
-    } else {
-        // the general path: packet histogram (j, p) at dword (8 j + p) * 256
-        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg));
-        for (uint32_t i = threadIdx.x; i * 16u < len; i += kSurveyThreads) {
-            const CrcQuad q = src[i];
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-            for (uint32_t d = 0; d < 4; ++d) {
-#pragma unroll 1
-                for (uint32_t b = 0; b < 4; ++b) {
-                    const uint32_t o = 16u * i + 4u * d + b, byte = (w[d] >> (8u * b)) & 255u;
-                    if (o >= len) break;
-#pragma unroll
-                    for (uint32_t j = 0; j < kSurveyWidths; ++j)
-                        __hip_atomic_fetch_add(hist + ((j * kSurveyPackets + survey_packet(o, len, j)) * 256u + byte), 1u, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
+// The pieces the three surveys (this one, the delta survey and the XOR-base survey below) are made of.
+
+// The walk over windows and descriptors with the supergroup's work as a parameter: every supergroup that starts in one of this
+// workgroup's windows goes to body(sg, bs, len, first) -- `len` bytes (1 .. 65536) at `sg`, whose first packet is batch packet
+// `first` -- and every unusable descriptor to BAD_BATCH.  kBased: the XOR survey's walk, with a base beside the buffer (`base`,
+// or one pointer per buffer in `bases`); bs is the base's bytes of the supergroup, null where a batch's base pointer is 0 ("no
+// base"), and a base pointer that is not 16-byte aligned makes its buffer BAD_BATCH.  Otherwise bs is null at compile time.
+template <bool kBased, typename Body>
+__device__ __forceinline__ void survey_walk(const SurveyArgs &a, const uint8_t *base, const uint8_t *const *bases, Body body) {
+    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
+    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
+        uint64_t p = 8ull * u;
+        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
+        while (p < end) {                   // (every value here is the same in all threads)
+            const uint8_t *sg = nullptr, *bs = nullptr;
+            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
+            if (!a.ptrs) {                  // one buffer: the window is the supergroup
+                sg = a.in + p * kPacket;
+                if constexpr (kBased) bs = base + p * kPacket;
+                left = a.n_bytes - p * kPacket;
+            } else {
+                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
+                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
+                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    next = p + 1u;
+                } else {
+                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
+                    const uint8_t *own = nullptr;                      // the buffer's base
+                    if constexpr (kBased) own = bases[bl.buffer];
+                    const uint64_t j = p - lead;
+                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
+                    if (!bl.owned || (reinterpret_cast<uintptr_t>(own) & 15u) != 0u || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
+                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
+                        sg = bl.ptr;
+                        bs = own ? own + j * kPacket : nullptr;
+                        left = n_bytes - j * kPacket;
+                    }
                 }
+            }
+            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
+            if (len != 0u) body(sg, bs, len, p);
+            p = next;
+        }
+    }
+}
+
+// every kernel's first step: the histograms clear, and a barrier
+__device__ __forceinline__ void survey_prologue(CrcQuad *lds) {
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
+    __syncthreads();
+}
+
+// slot[t]: the wavefront's base and the residue (t + c) & 7, c = lane & 7, that survey_count8's step t counts into
+__device__ __forceinline__ void survey_slots(uint32_t wave, uint32_t lane, uint32_t (&slot)[8]) {
+#pragma unroll
+    for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + (lane & 7u)) & 7u);
+}
+
+// a full supergroup's bytes of this lane: [128 lane, 128 lane + 128) of eighth `wave` as eight 16-byte loads -- XORed, where
+// there is a base (bs != nullptr), with the same bytes of the base
+template <bool kXor>
+__device__ __forceinline__ void survey_load8(const uint8_t *sg, const uint8_t *bs, uint32_t wave, uint32_t lane, CrcQuad (&q)[8]) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    const uint32_t at = wave * kPacket + kCrcChunk * lane;
+    GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + at));
+#pragma unroll
+    for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
+    if constexpr (kXor) {
+        if (bs != nullptr) {                                                 // workgroup-uniform
+            GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs + at));
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k) {
+                const CrcQuad b = bsrc[k];
+                q[k].x ^= b.x, q[k].y ^= b.y, q[k].z ^= b.z, q[k].w ^= b.w;
             }
         }
     }
-    __syncthreads();
-    // cnt[4 j + m]: bin s of packet 4 half + m at width 1 << j
-    uint32_t cnt[16];
+}
+
+// the general path's fill: every byte of the short supergroup (XORed with the base's, where there is one) into packet histogram
+// (j, p) at dword (8 j + p) * 256, for every width j
+template <bool kXor>
+__device__ __forceinline__ void survey_short(uint32_t *hist, const uint8_t *sg, const uint8_t *bs, uint32_t len) {
+    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
+    GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg));
+    GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs));
+    for (uint32_t i = threadIdx.x; i * 16u < len; i += kSurveyThreads) {
+        const CrcQuad q = src[i];
+        uint32_t w[4] = {q.x, q.y, q.z, q.w};
+        if constexpr (kXor) {
+            if (bs != nullptr) {
+                const CrcQuad b = bsrc[i];
+                w[0] ^= b.x, w[1] ^= b.y, w[2] ^= b.z, w[3] ^= b.w;
+            }
+        }
+#pragma unroll
+        for (uint32_t d = 0; d < 4; ++d) {
+#pragma unroll 1
+            for (uint32_t b = 0; b < 4; ++b) {
+                const uint32_t o = 16u * i + 4u * d + b, byte = (w[d] >> (8u * b)) & 255u;
+                if (o >= len) break;
+#pragma unroll
+                for (uint32_t j = 0; j < kSurveyWidths; ++j)
+                    __hip_atomic_fetch_add(hist + ((j * kSurveyPackets + survey_packet(o, len, j)) * 256u + byte), 1u, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    }
+}
+
+// cnt[4 j + m]: bin s of packet 4 half + m at width 1 << j -- of a full supergroup from the residue histograms, of a short one
+// from the packet histograms
+__device__ __forceinline__ void survey_counts16(const CrcQuad *lds, bool full, uint32_t half, uint32_t s, uint32_t (&cnt)[16]) {
     if (full) {
         CrcQuad lo[4], hi[4], other[4];      // residues 0-3 and 4-7 of the half's own eighths; residues 4 half .. + 3 of the other half's
 #pragma unroll
@@ -3713,88 +3779,138 @@ __device__ __forceinline__ void survey_supergroup(const SurveyArgs &a, const uin
         cnt[8] = w4.x, cnt[9] = w4.y, cnt[10] = w4.z, cnt[11] = w4.w;
         cnt[12] = w8.x, cnt[13] = w8.y, cnt[14] = w8.z, cnt[15] = w8.w;
     } else {
+        const uint32_t *hist = reinterpret_cast<const uint32_t *>(lds);
 #pragma unroll
         for (uint32_t i = 0; i < 16; ++i) cnt[i] = hist[((i >> 2) * kSurveyPackets + 4u * half + (i & 3u)) * 256u + s];
     }
-    // 16 wave sums in 17 exchanges instead of 96: every step halves the values a lane carries (it keeps the half its lane bit
-    // names and hands the other half to its partner), so lane l ends with the whole wavefront's sum of value l >> 2
-    uint64_t sum[16];
+}
+
+// a value's trip to lane ^ off: a 64-bit one as the two __shfl_xor of its halves
+__device__ __forceinline__ uint32_t lane_swap(uint32_t v, uint32_t off) { return __shfl_xor(v, off); }
+__device__ __forceinline__ uint64_t lane_swap(uint64_t v, uint32_t off) {
+    const uint32_t lo = __shfl_xor(static_cast<uint32_t>(v), off), hi = __shfl_xor(static_cast<uint32_t>(v >> 32), off);
+    return static_cast<uint64_t>(hi) << 32 | lo;
+}
+
+// N wave reductions by `op` in N - 1 + log2(64 / N) exchanges instead of 6 N (N = 16: 17 instead of 96): every step halves the
+// values a lane carries (it keeps the half its lane bit names and hands the other half to its partner), then a plain butterfly
+// over the offsets left, so lane l ends with the whole wavefront's result for value l / (64 / N) in v[0]
+template <uint32_t N, typename T, typename Op>
+__device__ __forceinline__ void wave_fold(T (&v)[N], uint32_t lane, Op op) {
+    static_assert(N >= 2u && N <= 64u && (N & (N - 1u)) == 0u, "a power of two of values, at most one per lane");
 #pragma unroll
-    for (uint32_t i = 0; i < 16; ++i) sum[i] = lf[cnt[i]];
-#pragma unroll
-    for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
+    for (uint32_t n = N / 2u, off = 32; n >= 1; n >>= 1, off >>= 1) {
         const bool upper = (lane & off) != 0u;
 #pragma unroll
         for (uint32_t m = 0; m < n; ++m) {
-            const uint64_t keep = upper ? sum[m + n] : sum[m], give = upper ? sum[m] : sum[m + n];
-            const uint32_t lo = __shfl_xor(static_cast<uint32_t>(give), off), hi = __shfl_xor(static_cast<uint32_t>(give >> 32), off);
-            sum[m] = keep + (static_cast<uint64_t>(hi) << 32 | lo);
+            const T low = v[m], high = v[m + n];                  // (values, so that the choice is of registers and never of addresses)
+            v[m] = op(upper ? high : low, lane_swap(upper ? low : high, off));
         }
     }
 #pragma unroll
-    for (uint32_t off = 2; off >= 1; off >>= 1) {
-        const uint32_t lo = __shfl_xor(static_cast<uint32_t>(sum[0]), off), hi = __shfl_xor(static_cast<uint32_t>(sum[0] >> 32), off);
-        sum[0] += static_cast<uint64_t>(hi) << 32 | lo;
-    }
-    if ((lane & 3u) == 0u) sums[wave][lane >> 2] = sum[0];
-    __syncthreads();
-    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
+    for (uint32_t off = 32u / N; off >= 1; off >>= 1) v[0] = op(v[0], lane_swap(v[0], off));
+}
+
+// every counter was read in front of the barrier before: clear them (thread (half, s): both quads of bin s of its four eighths)
+__device__ __forceinline__ void survey_clear(CrcQuad *lds, uint32_t half, uint32_t s) {
 #pragma unroll
     for (uint32_t e = 0; e < 4; ++e) {
         lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
         lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
     }
+}
+
+// the bytes of packet p of a supergroup of `len` bytes (p * kPacket < len)
+__device__ __forceinline__ uint32_t survey_packet_bytes(uint32_t len, uint32_t p) {
+    return len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
+}
+
+// one estimate, one writer: packet p of the supergroup at width 1 << j, from column `col` of the exchange of its half's four
+// wave sums, into entry first + p of row j
+template <uint32_t N>
+__device__ __forceinline__ void survey_store_est(uint32_t *est_rows, size_t stride, uint32_t j, uint64_t first, uint32_t p, uint32_t len,
+                                                 const uint64_t (*sums)[N], uint32_t col) {
+    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+    const uint32_t w0 = p & ~3u, count = survey_packet_bytes(len, p);
+    const uint64_t total = sums[w0][col] + sums[w0 + 1u][col] + sums[w0 + 2u][col] + sums[w0 + 3u][col];
+    GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(est_rows));
+    est[j * stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
+}
+
+// one supergroup of the plane survey (kXor = false: bs, scan and keys unused, a.est there) and of the XOR-base survey (kXor = true:
+// the bytes counted are the buffer's XORed with the base's unless bs is null, and a.est or scan may be null): `len` bytes
+// (1 .. 65536) at `sg` and at `bs` (both 16-byte aligned), whose first packet is entry `first` of every row; the whole workgroup,
+// with the histograms clear on entry and on return
+template <bool kXor>
+__device__ __forceinline__ void survey_supergroup(const SurveyArgs &a, uint32_t *scan, const uint8_t *sg, const uint8_t *bs, uint32_t len,
+                                                  uint64_t first, CrcQuad *lds, uint64_t (*sums)[16], uint32_t (*keys)[16]) {
+    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
+    using GlobalWord = __attribute__((address_space(1))) uint32_t;
+    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
+    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, eighths / packets 4 half .. + 3
+    const bool full = len == kSurveyBytes;                                   // workgroup-uniform
+    const bool want_est = !kXor || a.est != nullptr, want_scan = kXor && scan != nullptr;
+    if (full) {
+        CrcQuad q[8];
+        survey_load8<kXor>(sg, bs, wave, lane, q);
+        uint32_t slot[8];
+        survey_slots(wave, lane, slot);
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            survey_count8(hist, q[k].x, q[k].y, lane & 7u, slot);
+            survey_count8(hist, q[k].z, q[k].w, lane & 7u, slot);
+        }
+    } else {
+        survey_short<kXor>(hist, sg, bs, len);
+    }
+    __syncthreads();
+    uint32_t cnt[16];
+    survey_counts16(lds, full, half, s, cnt);
+    // the scan words: 16 wave maxima of the keys (xor_scan_key: count << 8 | s), lane l ending with that of value l >> 2
+    if (want_scan) {
+        uint32_t key[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) key[i] = xor_scan_key(cnt[i], s);
+        wave_fold(key, lane, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
+        if ((lane & 3u) == 0u) keys[wave][lane >> 2] = key[0];
+    }
+    // the estimates: 16 wave sums of the counts' LF
+    if (want_est) {
+        uint64_t sum[16];
+#pragma unroll
+        for (uint32_t i = 0; i < 16; ++i) sum[i] = lf[cnt[i]];
+        wave_fold(sum, lane, [](uint64_t x, uint64_t y) { return x + y; });
+        if ((lane & 3u) == 0u) sums[wave][lane >> 2] = sum[0];
+    }
+    __syncthreads();
+    survey_clear(lds, half, s);
     if (threadIdx.x < 32u) {
         const uint32_t i = threadIdx.x & 15u, hh = threadIdx.x >> 4, p = 4u * hh + (i & 3u);
         if (p * kPacket < len) {
-            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
-            const uint64_t total = sums[4u * hh][i] + sums[4u * hh + 1u][i] + sums[4u * hh + 2u][i] + sums[4u * hh + 3u][i];
-            GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(a.est));
-            est[(i >> 2) * a.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
+            if (want_est) survey_store_est(a.est, a.stride, i >> 2, first, p, len, sums, i);
+            if (want_scan) {
+                const uint32_t k01 = keys[4u * hh][i] > keys[4u * hh + 1u][i] ? keys[4u * hh][i] : keys[4u * hh + 1u][i];
+                const uint32_t k23 = keys[4u * hh + 2u][i] > keys[4u * hh + 3u][i] ? keys[4u * hh + 2u][i] : keys[4u * hh + 3u][i];
+                GlobalWord *out = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(scan));
+                out[(i >> 2) * a.stride + first + p] = xor_scan_word(k01 > k23 ? k01 : k23, survey_packet_bytes(len, p));
+            }
         }
     }
-    __syncthreads();      // the clears and the reads of `sums` in front of the next supergroup
+    __syncthreads();      // the clears and the reads of the exchanges in front of the next supergroup
 }
 
 __global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_per_eu(4)))      // two workgroups per CU: 128 VGPRs
 survey_planes_kernel(SurveyArgs a) {
     __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
     __shared__ uint64_t sums[kSurveyWaves][16];
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
-    __syncthreads();
-    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
-    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
-        uint64_t p = 8ull * u;
-        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
-        while (p < end) {                   // (every value here is the same in all threads)
-            const uint8_t *sg = nullptr;
-            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
-            if (!a.ptrs) {                  // one buffer: the window is the supergroup
-                sg = a.in + p * kPacket;
-                left = a.n_bytes - p * kPacket;
-            } else {
-                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
-                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
-                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    next = p + 1u;
-                } else {
-                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
-                    const uint64_t j = p - lead;
-                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
-                    if (!bl.owned || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
-                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
-                        sg = bl.ptr;
-                        left = n_bytes - j * kPacket;
-                    }
-                }
-            }
-            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
-            if (len != 0u) survey_supergroup(a, sg, len, p, lds, sums);
-            p = next;
-        }
-    }
+    survey_prologue(lds);
+    survey_walk<false>(a, nullptr, nullptr, [&](const uint8_t *sg, const uint8_t *, uint32_t len, uint64_t first) {
+        survey_supergroup<false>(a, nullptr, sg, nullptr, len, first, lds, sums, nullptr);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -3822,46 +3938,6 @@ struct DeltaSurveyArgs {
     SurveyArgs s;
     uint32_t widths_mask;                   // bit j: row j (width 1 << j) is wanted
 };
-
-// survey_planes_kernel's walk over windows and descriptors with the supergroup's work as a parameter: every supergroup that
-// starts in one of this workgroup's windows goes to body(sg, len, first) -- `len` bytes (1 .. 65536) at `sg`, whose first packet
-// is batch packet `first` -- and every unusable descriptor to BAD_BATCH.  (A copy: survey_planes_kernel written over this
-// function compiles to another instruction stream and four registers fewer, and that kernel's code object stays as it is.)
-template <typename Body>
-__device__ __forceinline__ void survey_walk(const SurveyArgs &a, Body body) {
-    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
-    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
-        uint64_t p = 8ull * u;
-        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
-        while (p < end) {                   // (every value here is the same in all threads)
-            const uint8_t *sg = nullptr;
-            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
-            if (!a.ptrs) {                  // one buffer: the window is the supergroup
-                sg = a.in + p * kPacket;
-                left = a.n_bytes - p * kPacket;
-            } else {
-                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
-                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
-                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    next = p + 1u;
-                } else {
-                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
-                    const uint64_t j = p - lead;
-                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
-                    if (!bl.owned || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
-                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
-                        sg = bl.ptr;
-                        left = n_bytes - j * kPacket;
-                    }
-                }
-            }
-            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
-            if (len != 0u) body(sg, len, p);
-            p = next;
-        }
-    }
-}
 
 // the last W-byte element of the 8 bytes {lo, hi}
 template <int W>
@@ -3958,7 +4034,6 @@ template <int J>
 __device__ __forceinline__ void dsurvey_width(const DeltaSurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, const uint32_t (&d)[32],
                                               uint32_t front_lo, uint32_t front_hi, CrcQuad *lds, uint64_t (*sums)[4]) {
     using GlobalLf = const __attribute__((address_space(1))) uint64_t;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
     constexpr int W = 1 << J;
     GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
     uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
@@ -3967,7 +4042,7 @@ __device__ __forceinline__ void dsurvey_width(const DeltaSurveyArgs &a, const ui
     const bool full = len == kSurveyBytes;                                   // workgroup-uniform
     if (full) {
         const uint32_t c = lane & 7u;
-        uint32_t slot[8];
+        uint32_t slot[8];                   // survey_slots, written out (see dsurvey_supergroup)
 #pragma unroll
         for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
         dsurvey_count<W>(hist, d, front_lo, front_hi, lane == 0u && (wave & (W - 1u)) == 0u, c, slot);
@@ -3982,7 +4057,8 @@ __device__ __forceinline__ void dsurvey_width(const DeltaSurveyArgs &a, const ui
 #pragma unroll
         for (uint32_t m = 0; m < 4; ++m) cnt[m] = hist[(4u * half + m) * 256u + s];
     }
-    // four wave sums: two steps halve the values a lane carries (as survey_supergroup's), four more sum value lane >> 4 up
+    // four wave sums: wave_fold<4>, written out (see dsurvey_supergroup) -- two steps halve the values a lane carries, four more
+    // sum value lane >> 4 up
     uint64_t sum[4];
 #pragma unroll
     for (uint32_t m = 0; m < 4; ++m) sum[m] = lf[cnt[m]];
@@ -4003,25 +4079,22 @@ __device__ __forceinline__ void dsurvey_width(const DeltaSurveyArgs &a, const ui
     }
     if ((lane & 15u) == 0u) sums[wave][lane >> 4] = sum[0];
     __syncthreads();
-    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
-#pragma unroll
-    for (uint32_t e = 0; e < 4; ++e) {
-        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
-        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
-    }
-    if (threadIdx.x < 8u) {
-        const uint32_t m = threadIdx.x & 3u, hh = threadIdx.x >> 2, p = 4u * hh + m;
-        if (p * kPacket < len) {
-            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
-            const uint64_t total = sums[4u * hh][m] + sums[4u * hh + 1u][m] + sums[4u * hh + 2u][m] + sums[4u * hh + 3u][m];
-            GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(a.s.est));
-            est[J * a.s.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
-        }
-    }
+    survey_clear(lds, half, s);
+    if (threadIdx.x < 8u && threadIdx.x * kPacket < len) survey_store_est(a.s.est, a.s.stride, J, first, threadIdx.x, len, sums, threadIdx.x & 3u);
     __syncthreads();      // the clears and the reads of `sums` in front of the next width
 }
 
-// one supergroup: `len` bytes (1 .. 65536) at `sg` (16-byte aligned), whose first packet is entry `first` of every row
+// one supergroup: `len` bytes (1 .. 65536) at `sg` (16-byte aligned), whose first packet is entry `first` of every row.
+// This kernel takes the walk, the prologue, the clear and the estimate writer from the plane survey and keeps three pieces written
+// out, survey_load8 here and survey_slots and wave_fold<4> in dsurvey_width, for a measured reason.  With all three shared the
+// kernel was 231 instructions shorter (wave_fold chooses between registers where the text below makes the compiler index sum[]
+// through compare-and-select chains) and 0.8 % faster with all four widths on 8 GiB, but a single width of incompressible bytes
+// was slower in both of two alternating runs against the kernel as it is here: w = 1 on uniform bytes 2.530 / 2.546 ms against
+// 2.462 / 2.457 ms, w = 1 on bf16 2.534 / 2.545 against 2.462 / 2.461, w = 2 on uniform 2.587 / 2.590 against 2.555 / 2.548; with
+// only the reduction written out it was slower still (w = 1 on uniform 2.568 / 2.550 against 2.460 / 2.454).  Why was not found:
+// the kernel and the LF table lie at the same addresses in all three code objects and the loads and their waits are the same;
+// what differs is register allocation and address arithmetic throughout.  With these three written out the instruction stream
+// is the one that was measured as the faster.
 __device__ __forceinline__ void dsurvey_supergroup(const DeltaSurveyArgs &a, const uint8_t *sg, uint32_t len, uint64_t first, CrcQuad *lds,
                                                    uint64_t (*sums)[4]) {
     using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
@@ -4052,21 +4125,22 @@ __global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_pe
 survey_delta_kernel(DeltaSurveyArgs a) {
     __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
     __shared__ uint64_t sums[kSurveyWaves][4];
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
-    __syncthreads();
-    survey_walk(a.s, [&](const uint8_t *sg, uint32_t len, uint64_t first) { dsurvey_supergroup(a, sg, len, first, lds, sums); });
+    survey_prologue(lds);
+    survey_walk<false>(a.s, nullptr, nullptr, [&](const uint8_t *sg, const uint8_t *, uint32_t len, uint64_t first) {
+        dsurvey_supergroup(a, sg, len, first, lds, sums);
+    });
 }
 
 // ---------------------------------------------------------------------------
 // XOR-base survey (xor_survey.h): est[j][p] = estimate(split_xor(buffer, base, 1 << j))[p] and scan[j][p] =
 // sparse_scan(split_xor(buffer, base, 1 << j))[p] for the four widths at once, from one read of the buffer and one of its base and
 // without XORing or splitting anything into memory, for one buffer or a batch.  XOR commutes with the regrouping, so this is the
-// plane survey of buffer ^ base: supergroups, windows, the workgroup, the residue histograms and the sums behind the barrier are
-// survey_planes_kernel's.  Wavefront e loads eighth e of the buffer and of the base, lane l bytes [128 l, 128 l + 128) of each as
-// eight 16-byte loads, XORs them in registers and counts the result with survey_count8: a tensor equal to its base is all zeros,
-// all lanes on one bin, which is what the rotation by (lane & 7) is for.
-// Behind the barrier thread (half, s) forms survey_supergroup's 16 counts of bin s.  The estimates leave through the sum exchange;
+// plane survey of buffer ^ base and runs that survey's own code: survey_walk<true> (the walk with a base beside the buffer) and
+// survey_supergroup<true> (the XOR in front of the count, a second reduction behind it).  Wavefront e loads eighth e of the
+// buffer and of the base, lane l bytes [128 l, 128 l + 128) of each as eight 16-byte loads, XORs them in registers and counts the
+// result with survey_count8: a tensor equal to its base is all zeros, all lanes on one bin, which is what the rotation by
+// (lane & 7) is for.
+// Behind the barrier thread (half, s) forms the plane survey's 16 counts of bin s.  The estimates leave through the sum exchange;
 // the scan words through a second reduction of the same shape over 32-bit keys (xor_scan_key: count << 8 | s) by MAXIMUM --
 // a packet's majority byte, if it has one, is its fullest bin -- with an exchange of 8 x 16 words and one writer per entry.
 // A short supergroup takes the general path, with the base read by the same 16-byte pieces and the same two reductions.
@@ -4081,219 +4155,17 @@ struct XorSurveyArgs {
     uint32_t *scan;                         // row j at scan + j * s.stride; may be null
 };
 
-// survey_walk with the base beside the buffer: body(sg, bs, len, first), bs the base's bytes of the supergroup or null.  (A copy,
-// as survey_walk is: the other surveys' code objects stay as they are.)
-template <typename Body>
-__device__ __forceinline__ void xsurvey_walk(const XorSurveyArgs &x, Body body) {
-    const SurveyArgs &a = x.s;
-    const uint32_t n_windows = (a.n_packets >> 3) + ((a.n_packets & 7u) ? 1u : 0u);
-    for (uint32_t u = blockIdx.x; u < n_windows; u += gridDim.x) {
-        uint64_t p = 8ull * u;
-        const uint64_t end = p + 8u < a.n_packets ? p + 8u : a.n_packets;
-        while (p < end) {                   // (every value here is the same in all threads)
-            const uint8_t *sg = nullptr, *bs = nullptr;
-            uint64_t left = 0, next = end;  // left: the buffer's bytes from this supergroup on; 0: nothing to survey at p
-            if (!a.ptrs) {                  // one buffer: the window is the supergroup
-                sg = a.in + p * kPacket;
-                bs = x.base + p * kPacket;
-                left = a.n_bytes - p * kPacket;
-            } else {
-                const BatchLane bl = batch_lane(a.ptrs, a.bytes, a.first_packet, a.n_buffers, p);
-                if (!bl.owned && bl.ptr == nullptr) {                  // no buffer owns the packet
-                    if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    next = p + 1u;
-                } else {
-                    const uint64_t lead = a.first_packet[bl.buffer], behind = a.first_packet[bl.buffer + 1u], n_bytes = a.bytes[bl.buffer];
-                    const uint8_t *base = x.bases[bl.buffer];
-                    const uint64_t j = p - lead;
-                    next = p + 8u - (j & 7u) < behind ? p + 8u - (j & 7u) : behind;      // the buffer's next supergroup, or the next buffer
-                    if (!bl.owned || (reinterpret_cast<uintptr_t>(base) & 15u) != 0u || behind - lead != (n_bytes + kPacket - 1u) / kPacket) {
-                        if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
-                    } else if ((j & 7u) == 0u) {                       // (else: the supergroup started in another window)
-                        sg = bl.ptr;
-                        bs = base ? base + j * kPacket : nullptr;
-                        left = n_bytes - j * kPacket;
-                    }
-                }
-            }
-            const uint32_t len = __builtin_amdgcn_readfirstlane(left < kSurveyBytes ? static_cast<uint32_t>(left) : kSurveyBytes);
-            if (len != 0u) body(sg, bs, len, p);
-            p = next;
-        }
-    }
-}
-
-// one supergroup: `len` bytes (1 .. 65536) at `sg` and, unless null, at `bs` (both 16-byte aligned), whose first packet is entry
-// `first` of every row; the whole workgroup, with the histograms clear on entry and on return
-__device__ __forceinline__ void xsurvey_supergroup(const XorSurveyArgs &x, const uint8_t *sg, const uint8_t *bs, uint32_t len, uint64_t first,
-                                                   CrcQuad *lds, uint64_t (*sums)[16], uint32_t (*keys)[16]) {
-    using GlobalQuad = const __attribute__((address_space(1))) CrcQuad;
-    using GlobalLf = const __attribute__((address_space(1))) uint64_t;
-    using GlobalWord = __attribute__((address_space(1))) uint32_t;
-    GlobalLf *lf = reinterpret_cast<GlobalLf *>(reinterpret_cast<uintptr_t>(g_est_table.lf));
-    uint32_t *hist = reinterpret_cast<uint32_t *>(lds);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t s = threadIdx.x & 255u, half = threadIdx.x >> 8;          // of the aggregation: bin s, eighths / packets 4 half .. + 3
-    const bool full = len == kSurveyBytes, based = bs != nullptr;            // workgroup-uniform
-    if (full) {
-        const uint32_t at = wave * kPacket + kCrcChunk * lane;
-        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg + at));
-        CrcQuad q[8];
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) q[k] = src[k];
-        if (based) {
-            GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs + at));
-#pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) {
-                const CrcQuad b = bsrc[k];
-                q[k].x ^= b.x, q[k].y ^= b.y, q[k].z ^= b.z, q[k].w ^= b.w;
-            }
-        }
-        const uint32_t c = lane & 7u;
-        uint32_t slot[8];
-#pragma unroll
-        for (uint32_t t = 0; t < 8; ++t) slot[t] = wave * kSurveyEighthDwords + ((t + c) & 7u);
-#pragma unroll
-        for (uint32_t k = 0; k < 8; ++k) {
-            survey_count8(hist, q[k].x, q[k].y, c, slot);
-            survey_count8(hist, q[k].z, q[k].w, c, slot);
-        }
-    } else {
-        // the general path: packet histogram (j, p) at dword (8 j + p) * 256
-        GlobalQuad *src = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(sg));
-        GlobalQuad *bsrc = reinterpret_cast<GlobalQuad *>(reinterpret_cast<uintptr_t>(bs));
-        for (uint32_t i = threadIdx.x; i * 16u < len; i += kSurveyThreads) {
-            const CrcQuad q = src[i];
-            uint32_t w[4] = {q.x, q.y, q.z, q.w};
-            if (based) {
-                const CrcQuad b = bsrc[i];
-                w[0] ^= b.x, w[1] ^= b.y, w[2] ^= b.z, w[3] ^= b.w;
-            }
-#pragma unroll
-            for (uint32_t d = 0; d < 4; ++d) {
-#pragma unroll 1
-                for (uint32_t b = 0; b < 4; ++b) {
-                    const uint32_t o = 16u * i + 4u * d + b, byte = (w[d] >> (8u * b)) & 255u;
-                    if (o >= len) break;
-#pragma unroll
-                    for (uint32_t j = 0; j < kSurveyWidths; ++j)
-                        __hip_atomic_fetch_add(hist + ((j * kSurveyPackets + survey_packet(o, len, j)) * 256u + byte), 1u, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
-        }
-    }
-    __syncthreads();
-    // cnt[4 j + m]: bin s of packet 4 half + m at width 1 << j
-    uint32_t cnt[16];
-    if (full) {
-        CrcQuad lo[4], hi[4], other[4];      // residues 0-3 and 4-7 of the half's own eighths; residues 4 half .. + 3 of the other half's
-#pragma unroll
-        for (uint32_t e = 0; e < 4; ++e) {
-            lo[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u];
-            hi[e] = lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u];
-            other[e] = lds[((4u * (1u - half) + e) * kSurveyEighthDwords + 8u * s) / 4u + half];
-        }
-#pragma unroll
-        for (uint32_t e = 0; e < 4; ++e) cnt[e] = lo[e].x + lo[e].y + lo[e].z + lo[e].w + hi[e].x + hi[e].y + hi[e].z + hi[e].w;
-#pragma unroll
-        for (uint32_t g = 0; g < 2; ++g) {
-            const CrcQuad t = lo[2 * g] + hi[2 * g] + lo[2 * g + 1] + hi[2 * g + 1];
-            cnt[4 + 2 * g] = t.x + t.z;
-            cnt[4 + 2 * g + 1] = t.y + t.w;
-        }
-        const CrcQuad l4 = lo[0] + lo[1] + lo[2] + lo[3], h4 = hi[0] + hi[1] + hi[2] + hi[3];
-        const CrcQuad w4 = l4 + h4, w8 = (half ? h4 : l4) + other[0] + other[1] + other[2] + other[3];
-        cnt[8] = w4.x, cnt[9] = w4.y, cnt[10] = w4.z, cnt[11] = w4.w;
-        cnt[12] = w8.x, cnt[13] = w8.y, cnt[14] = w8.z, cnt[15] = w8.w;
-    } else {
-#pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) cnt[i] = hist[((i >> 2) * kSurveyPackets + 4u * half + (i & 3u)) * 256u + s];
-    }
-    // the scan words: 16 wave maxima of the keys, by survey_supergroup's halving pattern -- every step halves the values a lane
-    // carries, so lane l ends with the whole wavefront's maximum of value l >> 2
-    if (x.scan) {
-        uint32_t key[16];
-#pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) key[i] = xor_scan_key(cnt[i], s);
-#pragma unroll
-        for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
-            const bool upper = (lane & off) != 0u;
-#pragma unroll
-            for (uint32_t m = 0; m < n; ++m) {
-                const uint32_t keep = upper ? key[m + n] : key[m], give = upper ? key[m] : key[m + n];
-                const uint32_t got = __shfl_xor(give, off);
-                key[m] = keep > got ? keep : got;
-            }
-        }
-#pragma unroll
-        for (uint32_t off = 2; off >= 1; off >>= 1) {
-            const uint32_t got = __shfl_xor(key[0], off);
-            key[0] = key[0] > got ? key[0] : got;
-        }
-        if ((lane & 3u) == 0u) keys[wave][lane >> 2] = key[0];
-    }
-    // the estimates: 16 wave sums, as survey_supergroup's
-    if (x.s.est) {
-        uint64_t sum[16];
-#pragma unroll
-        for (uint32_t i = 0; i < 16; ++i) sum[i] = lf[cnt[i]];
-#pragma unroll
-        for (uint32_t n = 8, off = 32; n >= 1; n >>= 1, off >>= 1) {
-            const bool upper = (lane & off) != 0u;
-#pragma unroll
-            for (uint32_t m = 0; m < n; ++m) {
-                const uint64_t keep = upper ? sum[m + n] : sum[m], give = upper ? sum[m] : sum[m + n];
-                const uint32_t lo = __shfl_xor(static_cast<uint32_t>(give), off), hi = __shfl_xor(static_cast<uint32_t>(give >> 32), off);
-                sum[m] = keep + (static_cast<uint64_t>(hi) << 32 | lo);
-            }
-        }
-#pragma unroll
-        for (uint32_t off = 2; off >= 1; off >>= 1) {
-            const uint32_t lo = __shfl_xor(static_cast<uint32_t>(sum[0]), off), hi = __shfl_xor(static_cast<uint32_t>(sum[0] >> 32), off);
-            sum[0] += static_cast<uint64_t>(hi) << 32 | lo;
-        }
-        if ((lane & 3u) == 0u) sums[wave][lane >> 2] = sum[0];
-    }
-    __syncthreads();
-    // every counter was read in front of that barrier: clear them (thread (half, s): both quads of bin s of its four eighths)
-#pragma unroll
-    for (uint32_t e = 0; e < 4; ++e) {
-        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u] = CrcQuad(0u);
-        lds[((4u * half + e) * kSurveyEighthDwords + 8u * s) / 4u + 1u] = CrcQuad(0u);
-    }
-    if (threadIdx.x < 32u) {
-        const uint32_t i = threadIdx.x & 15u, hh = threadIdx.x >> 4, p = 4u * hh + (i & 3u);
-        if (p * kPacket < len) {
-            const uint32_t count = len - p * kPacket < kPacket ? len - p * kPacket : kPacket;
-            if (x.s.est) {
-                const uint64_t total = sums[4u * hh][i] + sums[4u * hh + 1u][i] + sums[4u * hh + 2u][i] + sums[4u * hh + 3u][i];
-                GlobalWord *est = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(x.s.est));
-                est[(i >> 2) * x.s.stride + first + p] = est_clen_from_sum(lf[count + 255u], lf[255], total);
-            }
-            if (x.scan) {
-                const uint32_t k01 = keys[4u * hh][i] > keys[4u * hh + 1u][i] ? keys[4u * hh][i] : keys[4u * hh + 1u][i];
-                const uint32_t k23 = keys[4u * hh + 2u][i] > keys[4u * hh + 3u][i] ? keys[4u * hh + 2u][i] : keys[4u * hh + 3u][i];
-                GlobalWord *scan = reinterpret_cast<GlobalWord *>(reinterpret_cast<uintptr_t>(x.scan));
-                scan[(i >> 2) * x.s.stride + first + p] = xor_scan_word(k01 > k23 ? k01 : k23, count);
-            }
-        }
-    }
-    __syncthreads();      // the clears and the reads of both exchanges in front of the next supergroup
-}
-
 __global__ void __launch_bounds__(kSurveyThreads) __attribute__((amdgpu_waves_per_eu(4)))      // two workgroups per CU: 128 VGPRs
 survey_xor_kernel(XorSurveyArgs a) {
     __shared__ CrcQuad lds[kSurveyWaves * kSurveyEighthDwords / 4u];
     __shared__ uint64_t sums[kSurveyWaves][16];
     __shared__ uint32_t keys[kSurveyWaves][16];
-#pragma unroll
-    for (uint32_t k = 0; k < 8; ++k) lds[threadIdx.x + kSurveyThreads * k] = CrcQuad(0u);
-    __syncthreads();
-    xsurvey_walk(a, [&](const uint8_t *sg, const uint8_t *bs, uint32_t len, uint64_t first) {
-        xsurvey_supergroup(a, sg, bs, len, first, lds, sums, keys);
+    survey_prologue(lds);
+    survey_walk<true>(a.s, a.base, a.bases, [&](const uint8_t *sg, const uint8_t *bs, uint32_t len, uint64_t first) {
+        survey_supergroup<true>(a.s, a.scan, sg, bs, len, first, lds, sums, keys);
     });
 }
+
 // gpuar_hip_status: reads and clears the fallback word in ONE device atomic.  A bit that another launch ORs in at any
 // moment is then either in what this exchange returns or still in the word for the next call; a copy to the host
 // followed by a separate clear would drop a bit that arrives between the two.
@@ -4978,11 +4850,14 @@ int gpuar_hip_estimate_host(const uint8_t *in, size_t n_bytes, uint32_t *est) {
     return GPUAR_OK;
 }
 
+// the grid of the three surveys: a workgroup takes a window of 8 packets at a time
+static uint32_t survey_blocks(uint32_t n_packets) { return capped_blocks(n_packets, 8u, gpuar::kSurveyGroups); }
+
 // both surveys, into the rows at d_est: delta_mask 0 is the plane survey, anything else the delta survey of those widths
 static int launch_survey(gpuar::SurveyArgs a, uint32_t *d_est, size_t est_stride, uint32_t delta_mask, void *stream) {
     a.est = d_est;
     a.stride = est_stride;
-    const uint32_t blocks = capped_blocks(a.n_packets, 8u, gpuar::kSurveyGroups);       // a window of 8 packets at a time
+    const uint32_t blocks = survey_blocks(a.n_packets);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (delta_mask) gpuar::survey_delta_kernel<<<blocks, gpuar::kSurveyThreads, 0, s>>>(gpuar::DeltaSurveyArgs{a, delta_mask});
     else gpuar::survey_planes_kernel<<<blocks, gpuar::kSurveyThreads, 0, s>>>(a);
@@ -5056,7 +4931,7 @@ static int launch_survey_xor(gpuar::XorSurveyArgs a, uint32_t *d_est, uint32_t *
     a.s.est = d_est;
     a.s.stride = stride;
     a.scan = d_scan;
-    const uint32_t blocks = capped_blocks(a.s.n_packets, 8u, gpuar::kSurveyGroups);     // a window of 8 packets at a time
+    const uint32_t blocks = survey_blocks(a.s.n_packets);
     gpuar::survey_xor_kernel<<<blocks, gpuar::kSurveyThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
     return check_launch();
 }

@@ -2,6 +2,9 @@
 of 7), on the same resident buffers in the same run.
 
     python tools/delta_survey_timing.py [--gib G] [--kinds uniform,zeros,sorted_int64,position_ids,bf16,compress] [--timeout S]
+                                         [--lib PATH]
+
+--lib PATH times another build of libgpuar_hip.so (tools/exp_build.sh) instead of the product one, in every child.
 
 For every kind of input a child process of its own (this file with --kind, under a time limit of its own; the first child that
 fails ends the run) makes G GiB (default 8) resident in HBM and times:
@@ -184,8 +187,13 @@ def main():
     ap.add_argument("--kind", help="(the child) measure this kind in this process")
     ap.add_argument("--profile", action="store_true", help="with --kind: run the launches untimed, for a profiler (see child_profile)")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds every child may take")
+    ap.add_argument("--lib", default=None, help="an experiment build of libgpuar_hip.so to time instead of the product one")
     args = ap.parse_args()
+    lib = ["--lib", os.path.abspath(args.lib)] if args.lib else []
     if args.kind:
+        if lib:
+            from gpuar_amd import hip as H
+            H.LIB_PATH = lib[1]
         if args.profile:
             child_profile(args.kind, args.gib)
         elif args.kind == "compress":
@@ -197,7 +205,7 @@ def main():
     for kind in args.kinds.split(","):
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kind", kind, "--gib", str(args.gib), "--compress-gib",
-                                str(args.compress_gib)], capture_output=True, text=True, timeout=args.timeout)
+                                str(args.compress_gib)] + lib, capture_output=True, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
             print(f"{kind}: no result within {args.timeout:g} s; nothing more is started", flush=True)
             return 1

@@ -10,11 +10,13 @@ hipcc="${HIPCC:-/opt/rocm/bin/hipcc}"
 out="$root/gpuar_amd/lib/exp/$1.so"
 mkdir -p "$root/gpuar_amd/lib/exp" "$root/build"
 rm -f "$out"
-[ -f "$root/build/host_codec.o" ] || make -C "$root/gpuar_amd/csrc" "$root/build/host_codec.o" > /dev/null || exit 1
+for obj in host_codec.o gip_read.o; do       # the host objects the product library links (gpuar_amd/csrc/Makefile)
+    [ -f "$root/build/$obj" ] || make -C "$root/gpuar_amd/csrc" "$root/build/$obj" > /dev/null || exit 1
+done
 log="$(mktemp)"
 ( cd "$root/gpuar_amd/csrc" && "$hipcc" --offload-arch="$arch" -O3 -std=c++17 -fPIC -I"$root/include" -Wno-unused-function \
     -mllvm -phi-node-folding-threshold=64 -mllvm -two-entry-phi-node-folding-threshold=64 ${2:-} -shared \
-    -o "$out" "$root/build/host_codec.o" gpuar_kernels.hip ) > "$log" 2>&1
+    -o "$out" "$root/build/host_codec.o" "$root/build/gip_read.o" gpuar_kernels.hip ) > "$log" 2>&1
 rc=$?
 grep -E "error|warning: v" "$log"
 rm -f "$log"

@@ -1,7 +1,9 @@
 """The plane-width survey kernel against the seven launches it replaces, against estimate_kernel alone and against the copy roof
 (torch events, min of 7), on the same resident buffers in the same run.
 
-    python tools/survey_timing.py [--gib G] [--kinds uniform,zeros,text,bf16,fp32,int64] [--timeout S]
+    python tools/survey_timing.py [--gib G] [--kinds uniform,zeros,text,bf16,fp32,int64] [--timeout S] [--lib PATH]
+
+--lib PATH times another build of libgpuar_hip.so (tools/exp_build.sh) instead of the product one, in every child.
 
 For every kind of input a child process of its own (this file with --kind, under a time limit of its own; the first child that
 fails ends the run) makes G GiB (default 8) resident in HBM and times:
@@ -94,15 +96,20 @@ def main():
     ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--kind", help="(the child) measure this kind in this process")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds every child may take")
+    ap.add_argument("--lib", default=None, help="an experiment build of libgpuar_hip.so to time instead of the product one")
     args = ap.parse_args()
+    lib = ["--lib", os.path.abspath(args.lib)] if args.lib else []
     if args.kind:
+        if lib:
+            from gpuar_amd import hip as H
+            H.LIB_PATH = lib[1]
         child(args.kind, args.gib)
         return 0
     results = []
     for kind in args.kinds.split(","):
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kind", kind, "--gib", str(args.gib)], capture_output=True, text=True,
-                               timeout=args.timeout)
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--kind", kind, "--gib", str(args.gib)] + lib, capture_output=True,
+                               text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
             print(f"{kind}: no result within {args.timeout:g} s; nothing more is started", flush=True)
             return 1
