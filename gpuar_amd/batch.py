@@ -61,6 +61,13 @@ count, the exceptions' positions and values: 4 + 3 k bytes -- is smaller than th
 change since it: compress(tensors, planes="auto", base=[...], sparse="auto") keeps an unchanged packet in 4 bytes where the
 codec cannot go below 210.  Like a raw packet, a sparse one goes into a version-6 file: Compressed.gip(b, kinds=True).
 
+With planes="mixed" width and filter are chosen per 64 KiB supergroup of every tensor instead of once per tensor: survey_mixed runs
+the plane survey -- with delta="mixed" the delta survey, with base=[...] the XOR survey too --, one hip.choose_modes_batch launch
+picks every supergroup's mode byte (width, delta or base; Compressed.modes), hip.split_mixed_batch splits the batch once and
+hip.merge_mixed_batch merges it back in place.  That is for a blob of several tensors, a struct of arrays or a
+checkpoint whose layers moved unequally; its predicted size is within two bytes per packet of the best single choice.  Such a batch
+has no .gip form yet.
+
 from_gip(files) is the way back: a list of .gip files -- what Compressed.gip or `gpuar c` wrote, any trailer version or none, as
 bytes, arrays or paths -- becomes one Compressed, one buffer per file, and decompress decodes them all in one launch.  The files
 are read and checked on the host by the CLI's own reader (read_gip: hip.gip_read_host, no GPU), their streams go to the device in
@@ -178,6 +185,10 @@ class Compressed:
     (gpuar_amd/csrc/sparse.h) back to back in batch order, `sparse_offsets` (int64, device, n_sparse + 1) where; `raw` and
     `raw_offsets` are there too (empty without stored=...).  Both are None otherwise.
 
+    Compressed with planes="mixed": `modes` (host list, n_buffers, of bytes: one mode per supergroup of 65536 bytes -- log2(width) |
+    delta << 2 | base << 3, hip.mode_parts) says how every supergroup was split; `planes` and `delta` are then None, and `based[b]`
+    says whether some supergroup of buffer b took the base.  None otherwise.
+
     `kinds_rule`: (stored == "auto", sparse == "auto") where the packets' kinds were chosen by hip.sparse_rule -- what
     gip(b, kinds=True) needs to know: such a buffer has a version-6 file, one with a list of stored packets has none."""
     stream: object
@@ -194,6 +205,7 @@ class Compressed:
     sparse: object = None
     sparse_offsets: object = None
     kinds_rule: tuple = None
+    modes: list = None
 
     @property
     def n_buffers(self) -> int:
@@ -282,6 +294,9 @@ class Compressed:
         and / or --sparse=auto beside those flags -- every packet behind its 4-byte header, a version-6 trailer that says which is
         which; GpuarError for any other batch (a list of stored packets has no file form).  Without it a buffer that holds a
         raw or sparse packet raises, as ever."""
+        if self.modes is not None:
+            raise GpuarError(f"buffer {b} was compressed with planes=\"mixed\": its .gip form needs a trailer that carries a mode per "
+                             "supergroup (version 7), which is not built yet")
         xored = bool(self.based[b]) if self.based is not None else False
         if xored and self.crc32 is None:
             raise GpuarError(f"buffer {b} was XORed with a base: its .gip form (trailer version 5) needs the CRCs that tell a reader "
@@ -626,6 +641,28 @@ def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_statu
     return _Split(d_ptrs, d_bytes, d_fp, d_coded, d_split, keep)
 
 
+def _modes_tensor(modes, device):
+    """The batch's modes (per buffer bytes) back to back as one uint8 device tensor (one entry at least)"""
+    import torch
+    flat = b"".join(modes)
+    return torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(device)
+
+
+def _split_mixed(device, ptrs, sizes, first_packet, n_packets, modes, bases, stream, d_status):
+    """_split for a mixed batch: every buffer that has bytes gets a split copy, made by one hip.split_mixed_batch launch with the
+    buffers' `modes` (per buffer bytes) and `bases` (one pointer per buffer, 0: none; None: no buffer has one)."""
+    import torch
+    n = len(sizes)
+    first_mode, _n_modes = H.batch_mode_count(sizes)
+    total, places = _split_layout(sizes, [1] * n, [[1] * n])
+    d_split = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
+    coded = [p if at is None else d_split.data_ptr() + at for p, at in zip(ptrs, places)]
+    (d_ptrs, d_bytes, d_fp, d_fm, d_bases, d_coded), keep = _upload(device, ptrs, sizes, first_packet, first_mode, bases or [0] * n, coded)
+    d_modes = _modes_tensor(modes, device)
+    H.split_mixed_batch(d_ptrs, d_bytes, d_fp, d_fm, d_modes, d_bases, n, n_packets, d_coded, stream=stream, d_status=d_status)
+    return _Split(d_ptrs, d_bytes, d_fp, d_coded, (d_split, d_modes), keep)
+
+
 def _packets(d_ptrs, d_bytes, d_fp, n_buffers, n_packets):
     """Every batch packet as a buffer of its own, built on the device: (buffer index, pointer, bytes) per packet, int64 -- packet
     j of buffer b is min(8192, bytes[b] - j * 8192) bytes at ptrs[b] + j * 8192."""
@@ -782,6 +819,7 @@ class _Batch(NamedTuple):
     d_est: object = None
     d_status: object = None
     base_chosen: bool = False               # base_auto="survey" was resolved with the widths (planes="survey"): `bases` are the kept ones
+    modes: object = None                    # planes="mixed": (delta offered) for _prepare to resolve, behind it per buffer the modes as bytes
 
 
 def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=None) -> _Batch:
@@ -795,10 +833,21 @@ def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=N
         raise GpuarError("base_auto=True needs base=[...]")
     if isinstance(base_auto, str) and base_auto != "survey":
         raise GpuarError(f"base_auto={base_auto!r}: False, True or \"survey\"")
-    if base is not None and delta is not None:
+    mixed = _is(planes, "mixed")
+    if _is(delta, "mixed") and not mixed:
+        raise GpuarError("delta=\"mixed\" goes with planes=\"mixed\"")
+    if mixed and delta is not None and not _is(delta, "mixed"):
+        raise GpuarError(f"planes=\"mixed\" chooses the filter per supergroup: delta=None or \"mixed\", not {delta!r}")
+    if mixed and base_auto:
+        raise GpuarError("planes=\"mixed\" chooses the base per supergroup: base_auto has nothing left to choose")
+    if base is not None and delta is not None and not mixed:
         raise GpuarError("base together with delta: that combination is not built (DESIGN.md 4.10)")
     bases, base_chosen = base_pointers(tensors, base), False
     device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if mixed:
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return _Batch(device, ptrs, sizes, first_packet, n_packets, None, None, bases, modes=(delta is not None,))
     if _is(planes, "survey"):
         stored = _stored_argument(stored, n_packets)
         with _on(stream):
@@ -824,6 +873,11 @@ def _prepare(a: _Batch, base_auto, stream) -> _Batch:
     _auto_base where that has split it both ways, else by one _split."""
     import torch
     d_status = torch.zeros(1, dtype=torch.int32, device=a.device)
+    if a.modes is not None:
+        chosen = _survey_mixed(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.modes[0], a.bases, d_status)
+        modes = [m for m, _total in chosen]
+        split = _split_mixed(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, modes, a.bases, stream, d_status)
+        return a._replace(modes=modes, split=split, d_status=d_status)
     flags, bases, split, d_est = a.flags, a.bases, None, None
     if flags == "auto":
         flags = _auto_delta(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status)
@@ -1030,6 +1084,45 @@ def survey_base_choice(tensors, base, stored=None, sparse=None):
     return [w for w, _k in choices], [k for _w, k in choices]
 
 
+def _survey_mixed(device, ptrs, sizes, first_packet, n_packets, delta, bases, d_status):
+    """Per buffer (its modes as bytes, their predicted totals summed): the plane survey, the delta survey if `delta`, the XOR survey
+    if some buffer has a base (`bases`: one pointer per buffer, 0: none; or None) -- a buffer without one gets its plane rows there,
+    which never win --, then one hip.choose_modes_batch launch and one synchronisation, on the current stream."""
+    import torch
+    n = len(sizes)
+    first_mode, n_modes = H.batch_mode_count(sizes)
+    if n_packets == 0:
+        return [(b"", 0)] * n
+    (d_ptrs, d_bytes, d_fp, d_fm, d_bases), _keep = _upload(device, ptrs, sizes, first_packet, first_mode, bases or [0] * n)
+    d_plain = H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device)
+    d_delta = H.survey_delta_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device) if delta else None
+    d_xored = None
+    if bases is not None and any(bases):
+        d_xored, _scan = H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_bases, n, n_packets, d_scan=False, d_status=d_status, device=device)
+    d_modes, d_totals = H.choose_modes_batch(d_plain, d_delta, d_xored, d_bytes, d_fp, d_fm, n, n_packets, n_modes, d_status=d_status)
+    *flat, flags = torch.cat([d_modes.to(torch.int64), d_totals.to(torch.int64), d_status.to(torch.int64)]).tolist()      # the one synchronisation
+    if flags:
+        _raise_on_status(d_status, "choose_modes_batch")
+    modes, totals = flat[:n_modes], flat[n_modes:]
+    return [(bytes(modes[first_mode[b]:first_mode[b + 1]]), sum(totals[first_mode[b]:first_mode[b + 1]])) for b in range(n)]
+
+
+def survey_mixed(tensors, delta=False, base=None) -> list:
+    """What compress(tensors, planes="mixed", ...) would choose, without splitting or encoding anything: per tensor (modes, total) --
+    the mode byte of every supergroup of 65536 bytes as bytes (hip.mode_parts) and the predicted compressed bytes under those
+    modes.  `delta`: offer the delta filter (delta="mixed"); `base`: as compress, offer the base to the tensors that have one.  The
+    surveys' launches over the original bytes, one hip.choose_modes_batch launch and one synchronisation.  The total is at most the
+    lowest total any single (width, filter) offered gives the tensor, plus two bytes per packet (gpuar_amd/csrc/mixed.h)."""
+    tensors = list(tensors)
+    bases = base_pointers(tensors, base)
+    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    if n_packets == 0:
+        return [(b"", 0)] * len(sizes)
+    import torch
+    d_status = torch.zeros(1, dtype=torch.int32, device=device)
+    return _survey_mixed(device, ptrs, sizes, first_packet, n_packets, bool(delta), bases, d_status)
+
+
 def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False, sparse=None) -> list:
     """The predicted compressed bytes of every tensor, without encoding anything: the sum of hip.estimate_batch's per-packet
     estimates (the packets' 4-byte headers included) over the tensor's packets -- of its bytes split into planes if `planes`
@@ -1093,8 +1186,12 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     stored None or "auto"): keep the packets that are one byte value almost everywhere as that byte and a list of exceptions --
     one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one hip.sparse_scan_batch launch
     on the bytes that would be coded, hip.sparse_rule on the device, and the packets go three ways: coded, raw (hip.move_packets)
-    and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.  See
-    Compressed."""
+    and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.
+    planes="mixed": width and filter per supergroup of 65536 bytes (survey_mixed, then one hip.split_mixed_batch launch into the
+    usual temporary; Compressed.modes): planes alone at the four widths, with delta="mixed" the delta filter too, with `base` the
+    base too -- here a base and the delta filter go together, a supergroup takes one of them or neither.  Any other `delta`,
+    delta="mixed" without planes="mixed", and `base_auto` raise before any launch.  `stored`, `sparse`, `checksum` and `mode` see the
+    split bytes as ever.  See Compressed."""
     import torch
     a = _arguments(list(tensors), planes, stored, delta, base, base_auto, stream, sparse)
     device, n, n_packets = a.device, len(a.sizes), a.n_packets
@@ -1149,9 +1246,17 @@ def compress(tensors, mode=None, stream=None, checksum=False, planes=None, store
     # (the slots and the split copies were held until here; they are freed on return)
     return Compressed(stream=d_stream, offsets=d_offsets, first_packet=a.first_packet, sizes=a.sizes,
                       crc32=d_crc[:n_packets] if d_crc is not None else None, planes=a.widths, stored=d_stored, raw=d_raw,
-                      raw_offsets=d_raw_offsets, delta=a.flags, based=[bool(q) for q in a.bases] if a.bases is not None else None,
-                      sparse=d_sparse, sparse_offsets=d_sparse_offsets,
-                      kinds_rule=(stored == "auto", sparse == "auto") if isinstance(stored, str) or sparse == "auto" else None)
+                      raw_offsets=d_raw_offsets, delta=a.flags, based=_based(a), sparse=d_sparse, sparse_offsets=d_sparse_offsets,
+                      kinds_rule=(stored == "auto", sparse == "auto") if isinstance(stored, str) or sparse == "auto" else None, modes=a.modes)
+
+
+def _based(a: _Batch):
+    """Compressed.based of a prepared batch: which buffers were XORed with their base -- in a mixed batch, in some supergroup"""
+    if a.bases is None:
+        return None
+    if a.modes is not None:
+        return [any(H.mode_parts(m)[2] for m in modes) for modes in a.modes]
+    return [bool(q) for q in a.bases]
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
@@ -1160,7 +1265,8 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
     and `verify` is true, the decoded bytes are checked against them (one more launch): a mismatch raises GpuarError naming
     the first buffer and packet that differ.  Buffers that were split into byte planes are merged back in place in `out`
     after decoding and before verifying: the CRCs are those of the original bytes; where a buffer went through the delta filter,
-    that launch is hip.merge_delta_batch, which also sums the differences up again.  Packets that were stored raw are copied
+    that launch is hip.merge_delta_batch, which also sums the differences up again; a batch compressed with planes="mixed" is merged by
+    hip.merge_mixed_batch with its modes.  Packets that were stored raw are copied
     (one more launch), sparse packets rebuilt from their records (hip.sparse_unpack, one more launch; a record that is not valid
     raises: BAD_PACKET), the others decoded.  `base`: as in compress; every buffer with c.based[b] needs base[b], the tensor it
     was compressed against (a missing one, one of another size, device or alignment, or one that overlaps any tensor of `out`
@@ -1219,7 +1325,13 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
                 H.sparse_unpack(c.sparse.data_ptr() + c.sparse_offsets[:n_sparse], c.sparse_offsets[1:] - c.sparse_offsets[:n_sparse], d_pkt_ptr[packed],
                                 d_pkt_len[packed], n_sparse, stream=stream, d_status=d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
-        found = _filter(c.planes, c.delta, bases) if c.n_packets else None
+        found = _filter(c.planes, c.delta, bases) if c.n_packets and c.modes is None else None
+        if c.modes is not None and c.n_packets:
+            first_mode, _n_modes = H.batch_mode_count(c.sizes)
+            (d_fm, d_bases), _keep2 = _upload(device, first_mode, bases or [0] * c.n_buffers)
+            H.merge_mixed_batch(d_ptrs, d_sizes, d_fp, d_fm, _modes_tensor(c.modes, device), d_bases, c.n_buffers, c.n_packets, d_ptrs, stream=stream,
+                                d_status=d_status)
+            _raise_on_status(d_status, "merge_mixed_batch")
         if found is not None:
             _split_name, merge, extra = found
             (d_elem, *d_extra), _keep2 = _upload(device, c.planes, *extra)

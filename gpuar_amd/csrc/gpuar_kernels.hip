@@ -29,6 +29,8 @@
 //  * split_xor_kernel / merge_xor_kernel, xor_tail_kernel: the same with an XOR against a base buffer fused in (xorbase.h);
 //  * split_delta_kernel / merge_delta_kernel, delta_tail_kernel: the same with an element-wise delta filter fused in (delta.h,
 //    DESIGN.md 4.9);
+//  * split_mixed_kernel / merge_mixed_kernel, mixed_tail_kernel, choose_modes_kernel: the three filters chosen per 64 KiB
+//    supergroup of a buffer (mixed.h);
 //  * compaction (scan + gather), synthetic-stream generators, a plain copy (the measured HBM roof).
 //
 // Bit-exact with the reference: same counts, same integer arithmetic, same
@@ -45,6 +47,7 @@
 #include "gpuar_hip.h"
 #include "gpuar_hip_gip.h"
 #include "gpuar_hip_xsurvey.h"
+#include "gpuar_hip_mixed.h"
 
 #include "lane_codec.h"
 #include "crc32.h"
@@ -55,6 +58,7 @@
 #include "survey.h"
 #include "delta_survey.h"
 #include "xor_survey.h"
+#include "mixed.h"
 #include "sparse.h"
 #include "kinds.h"
 
@@ -2566,8 +2570,10 @@ __device__ __forceinline__ void planes_tail(const PlanesBuffer &pb, const uint8_
 // The tail kernels' loop: one buffer, or workgroup b on buffer b of a batch with a barrier between buffers.  A buffer that is
 // not filtered takes planes_tail, a filtered one tail(buffer, side); a refused one is left alone (a refused buffer with
 // packets was flagged by the full-group kernel).
-template <bool Merge, typename PerBuffer, typename Tail>
-__device__ __forceinline__ void filter_tails(const PlanesArgs &a, const BufferFilter &single, PerBuffer per_buffer, PlanesQuad *lds, Tail tail) {
+// `buffer(b)` is buffer b of a batch as the tail takes it: planes_buffer for the filters with one width per buffer (filter_tails).
+template <bool Merge, typename Buffer, typename PerBuffer, typename Tail>
+__device__ __forceinline__ void filter_tails_of(const PlanesArgs &a, Buffer buffer, const BufferFilter &single, PerBuffer per_buffer, PlanesQuad *lds,
+                                                Tail tail) {
     auto one = [&](const PlanesBuffer &pb, const BufferFilter &f) {
         if (f.bad) return;
         if (f.filtered == 0u) planes_tail<Merge, false>(pb, nullptr, lds);
@@ -2579,9 +2585,14 @@ __device__ __forceinline__ void filter_tails(const PlanesArgs &a, const BufferFi
     }
     const uint64_t n_buffers = a.n_buffers;
     for (uint64_t b = blockIdx.x; b < n_buffers; b += gridDim.x) {
-        one(planes_buffer(a, static_cast<uint32_t>(b)), per_buffer(static_cast<uint32_t>(b)));
+        one(buffer(static_cast<uint32_t>(b)), per_buffer(static_cast<uint32_t>(b)));
         __syncthreads();                                                          // the next buffer's tail goes into the same LDS
     }
+}
+
+template <bool Merge, typename PerBuffer, typename Tail>
+__device__ __forceinline__ void filter_tails(const PlanesArgs &a, const BufferFilter &single, PerBuffer per_buffer, PlanesQuad *lds, Tail tail) {
+    filter_tails_of<Merge>(a, [&](uint32_t b) { return planes_buffer(a, b); }, single, per_buffer, lds, tail);
 }
 
 template <bool Merge>
@@ -2939,6 +2950,207 @@ xor_tail_kernel(XorArgs x) {
     __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
     filter_tails<Merge>(x.p, {false, 1u, x.base}, XorPerBuffer{x.base_ptrs}, lds,
                         [&](const PlanesBuffer &pb, const uint8_t *base) { planes_tail<Merge, true>(pb, base, lds); });
+}
+
+// ---------------------------------------------------------------------------
+// Mixed filter (mixed.h): every supergroup (8 packets = 65536 bytes) of a buffer is split as planes alone, with
+// the delta filter or against the base, at a width of its own, as its mode byte says; merge_mixed is the inverse.  No filter is
+// defined anew: the kernels below read a supergroup's mode and hand the group to planes_group, delta_group or xor_group, and the
+// tail to planes_tail or delta_tail, the device functions of the three sections above.
+//
+// Full groups have the other filters' shape: 512 threads, the workgroups stride over the packets, packet j of its buffer belongs
+// to supergroup j / 8, the mode is made uniform (readfirstlane) and the workgroup of a group's first packet moves the whole group.
+// A supergroup is a multiple of every group, so a group never straddles two modes.  LDS: one group for the base (xor_group) and,
+// apart from it, the delta's two times eight predictor slots.
+// A workgroup that strides on may go from a group of one kind to a group of another.  Two things are carried from group to group:
+//  * delta_group's LDS slots.  The split has ONE barrier per group, so a wavefront may write the next delta group's predictors
+//    while another still reads this one's: the slots alternate (`turn`, advanced by delta groups alone).  A slot is written again
+//    two delta groups later; the writer has then passed the barrier of the delta group in between, which no wavefront reaches
+//    before it has read the earlier slot.  Groups of other kinds between two delta groups only add barriers; they never touch the
+//    slots, which lie apart from the base's LDS.  (The merge has two barriers per group and needs no alternation; it takes it.)
+//  * xor_group's LDS.  Its trailing barrier (w > 1) stands behind the last read of the base from LDS, so whatever group comes next
+//    -- an XOR group that writes the same LDS, or a planes or delta group that does not touch it -- starts with the LDS free; a
+//    planes or delta group in front of an XOR group never uses that LDS at all.
+// Groups touch disjoint bytes of their buffers, so no load of one group depends on a store of another, in place or not.
+// Refused, each flagged BAD_BATCH: a supergroup whose mode is not 0 .. 11, or asks for a base where the buffer has none, is left
+// alone (the others of its buffer are moved); a buffer whose pointers or base are misaligned, or that does not own exactly its
+// packets (planes_buffer's rule), is left alone as a whole.
+// The tail -- only a buffer's last supergroup has one: n mod (w_last * 8192) bytes -- is mixed_tail_kernel's, one workgroup per
+// buffer through filter_tails' frame: planes_tail, delta_tail or planes_tail with the XOR, with the width of the last mode.
+// choose_modes_kernel is the choice itself: one lane per supergroup of the batch sums the survey rows of its 1 .. 8 packets and
+// writes the mode and the predicted total with mixed.h's choose_supergroup_mode, the host's own function.
+// ---------------------------------------------------------------------------
+struct MixedArgs {
+    PlanesArgs p;                           // elem and elem_bytes are not used: the widths are in the modes
+    const uint8_t *modes;                   // one buffer: its mode_count(n_bytes) modes; a batch: every buffer's, at first_mode[b]
+    const uint64_t *first_mode;             // a batch: n_buffers entries
+    const uint8_t *base;                    // one buffer: its base, or null ...
+    const uint8_t *const *base_ptrs;        // ... a batch: per buffer 0 = no base, else the base
+};
+
+// planes_buffer's rule without a width: both pointers 16-byte aligned and exactly the packets the bytes make; w = 1 says usable
+__device__ __forceinline__ PlanesBuffer mixed_buffer(const PlanesArgs &a, uint32_t b) {
+    PlanesBuffer r = {a.in_ptrs[b], a.out_ptrs[b], a.bytes[b], 0u};
+    const uint64_t owns = a.first_packet[b + 1u] - a.first_packet[b];
+    const bool aligned = ((reinterpret_cast<uintptr_t>(r.in) | reinterpret_cast<uintptr_t>(r.out)) & 15u) == 0u;
+    if (aligned && owns == (r.n_bytes + kPacket - 1u) / kPacket) r.w = 1u;
+    return r;
+}
+
+// a mode the kernels act on: valid, and with a base where it asks for one
+__device__ __forceinline__ bool mixed_usable(uint32_t mode, const uint8_t *base) {
+    return mixed_mode_ok(mode) && (mixed_kind(mode) != kMixedBase || base != nullptr);
+}
+
+template <bool Merge>
+__device__ __forceinline__ void mixed_full(const MixedArgs &m, PlanesQuad *lds, uint64_t *slots) {
+    const PlanesArgs &a = m.p;
+    uint32_t turn = 0u;
+    for (uint64_t packet = blockIdx.x; packet < a.n_packets; packet += gridDim.x) {
+        const uint8_t *in = a.in, *base = m.base, *modes = m.modes;
+        uint8_t *out = a.out;
+        uint64_t n_bytes = a.n_bytes, j = packet;
+        if (a.in_ptrs) {
+            const BatchLane bl = batch_lane(a.in_ptrs, a.bytes, a.first_packet, a.n_buffers, packet);
+            PlanesBuffer pb = {nullptr, nullptr, 0u, 0u};
+            base = nullptr;
+            if (bl.owned && bl.count) pb = mixed_buffer(a, bl.buffer), base = m.base_ptrs[bl.buffer], modes = m.modes + m.first_mode[bl.buffer];
+            if (pb.w == 0u || (reinterpret_cast<uintptr_t>(base) & 15u) != 0u) {
+                if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+                continue;
+            }
+            in = pb.in, out = pb.out, n_bytes = pb.n_bytes;
+            j = packet - a.first_packet[bl.buffer];
+        }
+        const uint32_t mode = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(modes[j / kSurveyPackets]));
+        const uint32_t usable = __builtin_amdgcn_readfirstlane(mixed_usable(mode, base) ? 1u : 0u);
+        if (usable == 0u) {
+            if (threadIdx.x == 0u) atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            continue;
+        }
+        const uint32_t w = mixed_width(mode), kind = mixed_kind(mode);
+        const uint32_t lead = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(j & (w - 1u)));
+        const uint64_t at = j * kPacket;
+        if (lead != 0u || n_bytes - at < static_cast<uint64_t>(w) * kPacket) continue;      // not a group's first packet, or the tail
+        if (kind == kMixedPlanes) {
+            if (w == 1u && in == out) continue;
+            if (w == 8u) planes_group<8, Merge>(in + at, out + at);
+            else if (w == 4u) planes_group<4, Merge>(in + at, out + at);
+            else if (w == 2u) planes_group<2, Merge>(in + at, out + at);
+            else planes_group<1, Merge>(in + at, out + at);
+        } else if (kind == kMixedDelta) {
+            uint64_t *mine = slots + 8u * (turn++ & 1u);                                    // (the comment above: why they alternate)
+            if (w == 8u) delta_group<8, Merge>(in + at, out + at, mine);
+            else if (w == 4u) delta_group<4, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+            else if (w == 2u) delta_group<2, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+            else delta_group<1, Merge>(in + at, out + at, reinterpret_cast<uint32_t *>(mine));
+        } else {
+            if (w == 8u) xor_group<8, Merge>(in + at, base + at, out + at, lds);
+            else if (w == 4u) xor_group<4, Merge>(in + at, base + at, out + at, lds);
+            else if (w == 2u) xor_group<2, Merge>(in + at, base + at, out + at, lds);
+            else xor_group<1, Merge>(in + at, base + at, out + at, lds);
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+split_mixed_kernel(MixedArgs m) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    __shared__ uint64_t slots[16];
+    mixed_full<false>(m, lds, slots);
+}
+
+__global__ void __launch_bounds__(kPlaneThreads)
+merge_mixed_kernel(MixedArgs m) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    __shared__ uint64_t slots[16];
+    mixed_full<true>(m, lds, slots);
+}
+
+// What the tail of a buffer of n_bytes bytes is: the mode of its last supergroup decides (the buffer has bytes).
+struct MixedTail {
+    uint32_t w;                             // 0: refused
+    BufferFilter filter;                    // filtered: the mode's kind; side: the base of an XOR tail
+};
+__device__ __forceinline__ MixedTail mixed_tail_of(const uint8_t *modes, uint64_t n_bytes, const uint8_t *base) {
+    const uint32_t mode = modes[(n_bytes - 1u) / kSurveyBytes];
+    const bool bad = !mixed_usable(mode, base) || (reinterpret_cast<uintptr_t>(base) & 15u) != 0u;
+    const uint32_t kind = mixed_kind(mode);
+    return {bad ? 0u : mixed_width(mode), {bad, kind, kind == kMixedBase ? base : nullptr}};
+}
+
+template <bool Merge>
+__global__ void __launch_bounds__(kPlaneThreads)
+mixed_tail_kernel(MixedArgs m) {
+    __shared__ PlanesQuad lds[8u * kPlanePacket / 16u];
+    __shared__ uint64_t waves[kPlaneThreads / 64u];
+    PlanesArgs a = m.p;
+    BufferFilter single = kPlanesAlone;
+    if (!a.in_ptrs) {
+        const MixedTail t = mixed_tail_of(m.modes, a.n_bytes, m.base);      // (launched for a buffer with bytes alone)
+        a.elem = t.w, single = t.filter;
+    }
+    auto of = [&](uint32_t b) { return mixed_tail_of(m.modes + m.first_mode[b], a.bytes[b], m.base_ptrs[b]); };
+    filter_tails_of<Merge>(
+        a,
+        [&](uint32_t b) {
+            PlanesBuffer pb = mixed_buffer(a, b);
+            if (pb.w != 0u) pb.w = pb.n_bytes ? of(b).w : 0u;
+            return pb;
+        },
+        single, [&](uint32_t b) { return a.bytes[b] ? of(b).filter : kPlanesAlone; }, lds,
+        [&](const PlanesBuffer &pb, const uint8_t *side) {
+            if (side) planes_tail<Merge, true>(pb, side, lds);
+            else delta_tail<Merge>(pb, lds, waves);
+        });
+}
+
+struct ChooseModesArgs {
+    const uint32_t *plain;                  // the survey rows: row j at + j * stride, entry p the batch's packet p ...
+    const uint32_t *delta;                  // ... null: not offered
+    const uint32_t *xored;
+    uint64_t stride;
+    uint64_t n_bytes;                       // one buffer ...
+    const uint64_t *bytes;                  // ... or a batch (bytes != nullptr)
+    const uint64_t *first_packet;
+    const uint64_t *first_mode;
+    uint32_t n_buffers;
+    uint32_t n_packets;
+    uint32_t n_modes;
+    uint8_t *modes;
+    uint32_t *totals;                       // may be null
+    uint32_t *status;
+};
+
+constexpr uint32_t kChooseThreads = 256;
+
+__global__ void __launch_bounds__(kChooseThreads)
+choose_modes_kernel(ChooseModesArgs a) {
+    const uint64_t g = static_cast<uint64_t>(blockIdx.x) * kChooseThreads + threadIdx.x;
+    if (g >= a.n_modes) return;
+    uint64_t s = g, first = 0u, packets = (a.n_bytes + kPacket - 1u) / kPacket;
+    if (a.bytes) {
+        uint32_t lo = 0, n = a.n_buffers;                        // batch_lane's search: the last buffer with first_mode[b] <= g
+        while (n > 0u) {
+            const uint32_t half = n >> 1;
+            if (a.first_mode[lo + half] <= g) lo += half + 1u, n -= half + 1u;
+            else n = half;
+        }
+        const uint32_t b = lo - 1u;
+        bool owned = lo != 0u;
+        if (owned) {
+            s = g - a.first_mode[b], first = a.first_packet[b], packets = a.first_packet[b + 1u] - first;
+            owned = packets == (a.bytes[b] + kPacket - 1u) / kPacket && s * kSurveyPackets < packets && first + packets <= a.n_packets;
+        }
+        if (!owned) {                                            // a supergroup nobody owns, or a buffer that does not own its packets
+            atomicOr(a.status, GPUAR_STATUS_BAD_BATCH);
+            return;
+        }
+    }
+    const ModeChoice c = choose_supergroup_mode(a.plain + first, a.delta ? a.delta + first : nullptr, a.xored ? a.xored + first : nullptr, a.stride, s,
+                                                packets);
+    a.modes[g] = static_cast<uint8_t>(c.mode);
+    if (a.totals) a.totals[g] = static_cast<uint32_t>(c.total);
 }
 
 // ---------------------------------------------------------------------------
@@ -4794,6 +5006,168 @@ int gpuar_hip_split_xor_host(const uint8_t *in, const uint8_t *base, size_t n_by
 
 int gpuar_hip_merge_xor_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, uint32_t elem_bytes, uint8_t *out) {
     return xor_on_host(true, in, base, n_bytes, elem_bytes, out);
+}
+
+// ---- the mixed filter (include/gpuar_hip_mixed.h) ----
+
+size_t gpuar_hip_mode_count(size_t n_bytes) { return static_cast<size_t>(gpuar::mode_count(n_bytes)); }
+
+size_t gpuar_hip_batch_mode_count(const uint64_t *bytes, size_t n_buffers, uint64_t *first_mode) {
+    uint64_t total = 0;
+    for (size_t b = 0; b < n_buffers; ++b) {
+        if (first_mode) first_mode[b] = total;
+        total += bytes ? gpuar::mode_count(bytes[b]) : 0u;
+    }
+    if (first_mode) first_mode[n_buffers] = total;
+    return static_cast<size_t>(total);
+}
+
+int gpuar_hip_choose_mode(const uint64_t plain[4], const uint64_t *delta, const uint64_t *xored, uint64_t n_packets, uint64_t *total) {
+    if (!plain) return GPUAR_ERR_ARGUMENT;
+    const gpuar::ModeChoice c = gpuar::choose_mode(plain, delta, xored, n_packets);
+    if (total) *total = c.total;
+    return static_cast<int>(c.mode);
+}
+
+// the launch of both device calls: a lane per supergroup
+static int launch_choose_modes(gpuar::ChooseModesArgs a, const uint32_t *d_plain, const uint32_t *d_delta, const uint32_t *d_xored, size_t stride,
+                               uint8_t *d_modes, uint32_t *d_totals, void *stream) {
+    a.plain = d_plain, a.delta = d_delta, a.xored = d_xored, a.stride = stride, a.modes = d_modes, a.totals = d_totals;
+    const uint32_t blocks = capped_blocks(a.n_modes, gpuar::kChooseThreads, 0xFFFFFFFFu);
+    gpuar::choose_modes_kernel<<<blocks, gpuar::kChooseThreads, 0, static_cast<hipStream_t>(stream)>>>(a);
+    return check_launch();
+}
+
+// what both device calls check of their rows and outputs: d_plain and d_modes are there (else ARGUMENT); the rows and the totals
+// are 4-byte aligned (else ALIGNMENT)
+static int choose_modes_pointers(const uint32_t *d_plain, const uint32_t *d_delta, const uint32_t *d_xored, const uint8_t *d_modes,
+                                 const uint32_t *d_totals, const uint32_t *d_status) {
+    if (!d_plain || !d_modes) return GPUAR_ERR_ARGUMENT;
+    return misaligned(d_plain, 4) || misaligned(d_delta, 4) || misaligned(d_xored, 4) || misaligned(d_totals, 4) || misaligned(d_status, 4)
+               ? GPUAR_ERR_ALIGNMENT
+               : GPUAR_OK;
+}
+
+int gpuar_hip_choose_modes(const uint32_t *d_plain, const uint32_t *d_delta, const uint32_t *d_xored, size_t stride, size_t n_bytes,
+                           uint8_t *d_modes, uint32_t *d_totals, uint32_t *d_status, void *stream) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (stride < gpuar_hip_packet_count(n_bytes) || gpuar_hip_packet_count(n_bytes) > kMaxCount) return GPUAR_ERR_ARGUMENT;
+    const int e = choose_modes_pointers(d_plain, d_delta, d_xored, d_modes, d_totals, d_status);
+    if (e != GPUAR_OK) return e;
+    gpuar::ChooseModesArgs a = {};
+    a.n_bytes = n_bytes;
+    a.n_packets = static_cast<uint32_t>(gpuar_hip_packet_count(n_bytes));
+    a.n_modes = static_cast<uint32_t>(gpuar::mode_count(n_bytes));
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    return launch_choose_modes(a, d_plain, d_delta, d_xored, stride, d_modes, d_totals, stream);
+}
+
+int gpuar_hip_choose_modes_batch(const uint32_t *d_plain, const uint32_t *d_delta, const uint32_t *d_xored, size_t stride, const uint64_t *d_bytes,
+                                 const uint64_t *d_first_packet, const uint64_t *d_first_mode, size_t n_buffers, size_t n_packets, size_t n_modes,
+                                 uint8_t *d_modes, uint32_t *d_totals, uint32_t *d_status, void *stream) {
+    if (n_modes == 0) return GPUAR_OK;
+    if (stride < n_packets || !d_bytes || !d_first_packet || !d_first_mode || n_packets > kMaxCount || n_buffers > kMaxCount || n_modes > kMaxCount)
+        return GPUAR_ERR_ARGUMENT;
+    const int e = choose_modes_pointers(d_plain, d_delta, d_xored, d_modes, d_totals, d_status);
+    if (e != GPUAR_OK) return e;
+    if (misaligned(d_bytes, 8) || misaligned(d_first_packet, 8) || misaligned(d_first_mode, 8)) return GPUAR_ERR_ALIGNMENT;
+    gpuar::ChooseModesArgs a = {};
+    a.bytes = d_bytes, a.first_packet = d_first_packet, a.first_mode = d_first_mode;
+    a.n_buffers = static_cast<uint32_t>(n_buffers);
+    a.n_packets = static_cast<uint32_t>(n_packets);
+    a.n_modes = static_cast<uint32_t>(n_modes);
+    a.status = status_word(d_status);
+    if (!a.status) return GPUAR_ERR_NO_DEVICE;
+    return launch_choose_modes(a, d_plain, d_delta, d_xored, stride, d_modes, d_totals, stream);
+}
+
+int gpuar_hip_choose_modes_host(const uint32_t *plain, const uint32_t *delta, const uint32_t *xored, size_t stride, size_t n_bytes, uint8_t *modes,
+                                uint32_t *totals) {
+    if (n_bytes == 0) return GPUAR_OK;
+    if (!plain || !modes || stride < gpuar_hip_packet_count(n_bytes)) return GPUAR_ERR_ARGUMENT;
+    gpuar::choose_modes_host(plain, delta, xored, stride, n_bytes, modes, totals);
+    return GPUAR_OK;
+}
+
+const FilterKernels<gpuar::MixedArgs> kMixedKernels = {gpuar::split_mixed_kernel, gpuar::merge_mixed_kernel, gpuar::mixed_tail_kernel<false>,
+                                                       gpuar::mixed_tail_kernel<true>};
+
+static int mixed_single(bool merge, const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, const uint8_t *d_modes, uint8_t *d_out,
+                        uint32_t *d_status, void *stream) {
+    gpuar::MixedArgs m = {};
+    bool launch = false;
+    const int e = single_arguments(d_in, d_base != nullptr, d_base, n_bytes, 1u, d_out, &m.p, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    if (!d_modes) return GPUAR_ERR_ARGUMENT;
+    if (misaligned(d_status, 4)) return GPUAR_ERR_ALIGNMENT;
+    m.p.status = status_word(d_status);
+    if (!m.p.status) return GPUAR_ERR_NO_DEVICE;
+    m.modes = d_modes;
+    m.base = d_base;
+    // launch_filter asks p.elem whether one buffer has a tail: at 8 it has one unless it ends on a supergroup's edge, where no width has
+    m.p.elem = 8u;
+    return launch_filter(kMixedKernels, merge, m, m.p, stream);
+}
+
+static int mixed_batch(bool merge, const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                       const uint64_t *d_first_mode, const uint8_t *d_modes, const uint8_t *const *d_base_ptrs, size_t n_buffers, size_t n_packets,
+                       uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    gpuar::MixedArgs m = {};
+    bool launch = false;
+    if (n_packets != 0 && !d_modes) return GPUAR_ERR_ARGUMENT;
+    if (n_packets != 0 && misaligned(d_base_ptrs, 8)) return GPUAR_ERR_ALIGNMENT;
+    // (the widths' place in the checks goes to first_mode, `extra` to the base pointers)
+    const int e = batch_filter_arguments(d_in_ptrs, d_bytes, d_first_packet, d_first_mode, true, d_base_ptrs, n_buffers, n_packets, d_out_ptrs,
+                                         d_status, &m.p, &launch);
+    if (e != GPUAR_OK || !launch) return e;
+    m.p.elem_bytes = nullptr;
+    m.modes = d_modes;
+    m.first_mode = d_first_mode;
+    m.base_ptrs = d_base_ptrs;
+    return launch_filter(kMixedKernels, merge, m, m.p, stream);
+}
+
+int gpuar_hip_split_mixed(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, const uint8_t *d_modes, uint8_t *d_out, uint32_t *d_status,
+                          void *stream) {
+    return mixed_single(false, d_in, d_base, n_bytes, d_modes, d_out, d_status, stream);
+}
+
+int gpuar_hip_merge_mixed(const uint8_t *d_in, const uint8_t *d_base, size_t n_bytes, const uint8_t *d_modes, uint8_t *d_out, uint32_t *d_status,
+                          void *stream) {
+    return mixed_single(true, d_in, d_base, n_bytes, d_modes, d_out, d_status, stream);
+}
+
+int gpuar_hip_split_mixed_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_first_mode, const uint8_t *d_modes, const uint8_t *const *d_base_ptrs, size_t n_buffers,
+                                size_t n_packets, uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return mixed_batch(false, d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, d_status,
+                       stream);
+}
+
+int gpuar_hip_merge_mixed_batch(const uint8_t *const *d_in_ptrs, const uint64_t *d_bytes, const uint64_t *d_first_packet,
+                                const uint64_t *d_first_mode, const uint8_t *d_modes, const uint8_t *const *d_base_ptrs, size_t n_buffers,
+                                size_t n_packets, uint8_t *const *d_out_ptrs, uint32_t *d_status, void *stream) {
+    return mixed_batch(true, d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, d_status,
+                       stream);
+}
+
+static int mixed_on_host(bool merge, const uint8_t *in, const uint8_t *base, size_t n_bytes, const uint8_t *modes, uint8_t *out) {
+    bool work = false;
+    const int e = filter_checks(true, in, base != nullptr, base, n_bytes, 1u, out, &work);
+    if (e != GPUAR_OK || !work) return e;
+    if (!modes || !gpuar::mixed_modes_ok(modes, n_bytes, base != nullptr)) return GPUAR_ERR_ARGUMENT;      // before anything is written
+    if (merge) gpuar::merge_mixed_host(in, base, n_bytes, modes, out);
+    else gpuar::split_mixed_host(in, base, n_bytes, modes, out);
+    return GPUAR_OK;
+}
+
+int gpuar_hip_split_mixed_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, const uint8_t *modes, uint8_t *out) {
+    return mixed_on_host(false, in, base, n_bytes, modes, out);
+}
+
+int gpuar_hip_merge_mixed_host(const uint8_t *in, const uint8_t *base, size_t n_bytes, const uint8_t *modes, uint8_t *out) {
+    return mixed_on_host(true, in, base, n_bytes, modes, out);
 }
 
 // one 16-element block through delta.h's register transforms, as the kernels apply them, on the host (for the tests):

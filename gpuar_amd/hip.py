@@ -109,6 +109,20 @@ XSURVEY_SIGNATURES = {
     "gpuar_hip_survey_xor_batch": (_int, [_vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _sz, _vp, _vp]),
     "gpuar_hip_survey_xor_host": (_int, [_vp, _vp, _sz, _vp, _vp, _sz]),
 }
+# The mixed filter, declared in include/gpuar_hip_mixed.h: a fourth table for the same reason (tests/test_mixed_host.py).
+MIXED_SIGNATURES = {
+    "gpuar_hip_mode_count": (_sz, [_sz]),
+    "gpuar_hip_batch_mode_count": (_sz, [_pu64, _sz, _pu64]),
+    "gpuar_hip_choose_mode": (_int, [_pu64, _pu64, _pu64, _u64, _pu64]),
+    "gpuar_hip_choose_modes": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_choose_modes_batch": (_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "gpuar_hip_choose_modes_host": (_int, [_vp, _vp, _vp, _sz, _sz, _vp, _vp]),
+    **_both("mixed", _int, [_vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    **_both("mixed_batch", _int, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp, _vp]),
+    **_both("mixed_host", _int, [_vp, _vp, _sz, _vp, _vp]),
+}
+MIXED_MODES = 12                     # the valid modes of a supergroup are 0 .. 11: log2(width) | delta << 2 | base << 3
+SUPERGROUP = 8 * PACKET              # the bytes one mode stands for
 GIP_INFO_WORDS = 10                  # GPUAR_GIP_INFO_WORDS
 SURVEY_WIDTHS = (1, 2, 4, 8)         # the rows of a survey
 CLOCK_SLOTS = 256                    # GPUAR_CLOCK_SLOTS
@@ -133,10 +147,10 @@ def load() -> C.CDLL:
     lib = C.CDLL(LIB_PATH)
     # a library built from older sources lacks newer exports: say "rebuild" instead of dying with an AttributeError half-way
     # through the signatures
-    missing = [name for name in (*EXPORTS, *GIP_SIGNATURES, *XSURVEY_SIGNATURES) if not hasattr(lib, name)]
+    missing = [name for name in (*EXPORTS, *GIP_SIGNATURES, *XSURVEY_SIGNATURES, *MIXED_SIGNATURES) if not hasattr(lib, name)]
     if missing:
         raise GpuarError(f"{LIB_PATH} lacks {missing}: it was built from older sources -- rebuild the library")
-    for name, (restype, argtypes) in (*SIGNATURES.items(), *GIP_SIGNATURES.items(), *XSURVEY_SIGNATURES.items()):
+    for name, (restype, argtypes) in (*SIGNATURES.items(), *GIP_SIGNATURES.items(), *XSURVEY_SIGNATURES.items(), *MIXED_SIGNATURES.items()):
         getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     if lib.gpuar_hip_abi_version() != ABI_VERSION:
         raise GpuarError(f"{LIB_PATH} speaks ABI {lib.gpuar_hip_abi_version()}, these bindings {ABI_VERSION}: rebuild the library")
@@ -754,6 +768,201 @@ def survey_xor_host(data, base, est: bool = True, scan: bool = True) -> tuple:
     words = [(C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))() if on else None for on in (est, scan)]
     _call("gpuar_hip_survey_xor_host", data, base, len(data), words[0], words[1], npk)
     return tuple(None if w is None else [list(w[j * npk:(j + 1) * npk]) for j in range(len(SURVEY_WIDTHS))] for w in words)
+
+
+def mode_count(n_bytes: int) -> int:
+    """The modes of a buffer of n_bytes bytes: one per supergroup of 65536 bytes (gpuar_hip_mode_count)."""
+    return (n_bytes + SUPERGROUP - 1) // SUPERGROUP
+
+
+def batch_mode_count(sizes):
+    """(first_mode as a list of n + 1 ints, mode count) for buffers of `sizes` bytes (gpuar_hip_batch_mode_count)."""
+    n = len(sizes)
+    arr = (C.c_uint64 * max(n, 1))(*sizes)
+    fm = (C.c_uint64 * (n + 1))()
+    total = load().gpuar_hip_batch_mode_count(arr, n, fm)
+    return list(fm), int(total)
+
+
+def mode_parts(mode: int) -> tuple:
+    """(width, delta, base) of a mode byte; anything but 0 .. 11 raises."""
+    if not 0 <= mode < MIXED_MODES:
+        raise GpuarError(f"mode {mode}: the modes are 0 .. {MIXED_MODES - 1}")
+    return 1 << (mode & 3), mode >> 2 == 1, mode >> 2 == 2
+
+
+def choose_mode(plain, delta, xored, n_packets: int) -> tuple:
+    """(mode, its predicted total) of one supergroup from its four totals at widths 1, 2, 4, 8 as planes alone, with the delta
+    filter (None: not offered) and against the base (None: not offered) (gpuar_hip_choose_mode): choose_filter(plain, delta) --
+    without delta, choose_planes(plain) --, then the base at choose_planes(xored) iff that total + n_packets is at most the total
+    chosen so far."""
+    rows = []
+    for name, t in (("plain", plain), ("delta", delta), ("xored", xored)):
+        if t is None and name != "plain":
+            rows.append(None)
+            continue
+        t = [int(v) for v in t]
+        if len(t) != len(SURVEY_WIDTHS) or min(t) < 0:
+            raise GpuarError(f"choose_mode: {name} is four non-negative totals, not {t}")
+        rows.append((C.c_uint64 * 4)(*t))
+    total = C.c_uint64(0)
+    mode = load().gpuar_hip_choose_mode(rows[0], rows[1], rows[2], n_packets, C.byref(total))
+    if mode < 0:
+        _check(mode, "gpuar_hip_choose_mode")
+    return int(mode), int(total.value)
+
+
+def _require_modes(d_modes, n):
+    import torch
+    if not (isinstance(d_modes, torch.Tensor) and d_modes.is_cuda and d_modes.dtype == torch.uint8 and d_modes.is_contiguous() and d_modes.numel() >= n):
+        raise GpuarError(f"d_modes must be a contiguous uint8 CUDA tensor of at least {n} modes")
+
+
+def _rows_ptr(d_rows, npk):
+    """The address of a survey's rows for choose_modes (None: not offered) and their stride"""
+    if d_rows is None:
+        return None, None
+    d_rows = _survey_rows(d_rows, npk, None)
+    return d_rows.data_ptr(), d_rows.shape[1]
+
+
+def _choose_rows(d_plain, d_delta, d_xored, npk):
+    """The three row pointers of a choose_modes call and their one stride"""
+    if d_plain is None:
+        raise GpuarError("choose_modes needs the plane survey's rows")
+    found = [_rows_ptr(t, npk) for t in (d_plain, d_delta, d_xored)]
+    strides = {stride for _ptr, stride in found if stride is not None}
+    if len(strides) != 1:
+        raise GpuarError(f"the surveys' rows must have one row stride, not {sorted(strides)}")
+    return [ptr for ptr, _stride in found], strides.pop()
+
+
+def _choose_outputs(d_modes, d_totals, n_modes, device):
+    import torch
+    if d_modes is None:
+        d_modes = torch.empty(max(n_modes, 1), dtype=torch.uint8, device=device)[:n_modes]
+    _require_modes(d_modes, n_modes)
+    return d_modes, _words(d_totals, "d_totals", n_modes, device)
+
+
+def choose_modes(d_plain, d_delta, d_xored, n_bytes: int, d_modes=None, d_totals=None, stream=None, d_status=None):
+    """The mode and the predicted total of every supergroup of one buffer of n_bytes bytes from the rows survey_planes, survey_delta
+    (all four widths) and survey_xor (its d_est) gave for it (gpuar_hip_choose_modes; d_delta, d_xored: None where that filter is
+    not offered; the rows have one stride).  Returns (d_modes: uint8 CUDA tensor of mode_count(n_bytes), d_totals: int32)."""
+    ptrs, stride = _choose_rows(d_plain, d_delta, d_xored, packet_count(n_bytes))
+    d_modes, d_totals = _choose_outputs(d_modes, d_totals, mode_count(n_bytes), d_plain.device)
+    _call("gpuar_hip_choose_modes", *ptrs, stride, n_bytes, d_modes.data_ptr(), d_totals.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
+    return d_modes, d_totals
+
+
+def choose_modes_batch(d_plain, d_delta, d_xored, d_bytes, d_first_packet, d_first_mode, n_buffers: int, n_packets: int, n_modes: int,
+                       d_modes=None, d_totals=None, stream=None, d_status=None):
+    """choose_modes for every buffer of a batch in one launch (gpuar_hip_choose_modes_batch): the rows are the batch surveys',
+    d_first_mode (64-bit CUDA tensor) what batch_mode_count gives, supergroup s of buffer b gets entry d_first_mode[b] + s."""
+    for t, name, n in ((d_bytes, "d_bytes", n_buffers), (d_first_packet, "d_first_packet", n_buffers + 1), (d_first_mode, "d_first_mode", n_buffers)):
+        _require_u64_desc(t, name, n)
+    ptrs, stride = _choose_rows(d_plain, d_delta, d_xored, n_packets)
+    d_modes, d_totals = _choose_outputs(d_modes, d_totals, n_modes, d_plain.device)
+    _call("gpuar_hip_choose_modes_batch", *ptrs, stride, d_bytes.data_ptr(), d_first_packet.data_ptr(), d_first_mode.data_ptr(), n_buffers, n_packets,
+          n_modes, d_modes.data_ptr(), d_totals.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
+    return d_modes, d_totals
+
+
+def choose_modes_host(plain, delta, xored, n_bytes: int) -> tuple:
+    """choose_modes on the CPU (gpuar_hip_choose_modes_host: no device is touched) from what survey_planes_host, survey_delta_host
+    and survey_xor_host's est gave (four lists of one int per packet each; delta, xored: None where not offered): (modes as bytes,
+    the predicted totals as a list)."""
+    npk, n_modes = packet_count(n_bytes), mode_count(n_bytes)
+    rows = []
+    for name, r in (("plain", plain), ("delta", delta), ("xored", xored)):
+        if r is None and name != "plain":
+            rows.append(None)
+            continue
+        if len(r) != len(SURVEY_WIDTHS) or any(row is None or len(row) != npk for row in r):
+            raise GpuarError(f"choose_modes_host: {name} is four rows of {npk} estimates")
+        rows.append((C.c_uint32 * max(len(SURVEY_WIDTHS) * npk, 1))(*(v for row in r for v in row)))
+    modes, totals = (C.c_uint8 * max(n_modes, 1))(), (C.c_uint32 * max(n_modes, 1))()
+    _call("gpuar_hip_choose_modes_host", rows[0], rows[1], rows[2], npk, n_bytes, modes, totals)
+    return bytes(modes[:n_modes]), list(totals[:n_modes])
+
+
+def _mixed(name, d_in, d_modes, d_base, d_out, n_bytes, stream, d_status):
+    import torch
+    _require_cuda_u8(d_in, "d_in")
+    n, _npk = _span(d_in, n_bytes)
+    if d_base is not None:
+        _require_cuda_u8(d_base, "d_base")
+        if n > d_base.numel():
+            raise GpuarError("d_base too small")
+    _require_modes(d_modes, mode_count(n))
+    if d_out is None:
+        d_out = torch.empty(max(n, 1), dtype=torch.uint8, device=d_in.device)[:n]
+    _require_cuda_u8(d_out, "d_out")
+    if d_out.numel() < n:
+        raise GpuarError("d_out too small")
+    _call(name, d_in.data_ptr(), _ptr_or_null(d_base), n, d_modes.data_ptr(), d_out.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
+    return d_out
+
+
+def split_mixed(d_in, d_modes, d_base=None, d_out=None, n_bytes: int = None, stream=None, d_status=None):
+    """Split the first `n_bytes` (default: all) bytes of `d_in` supergroup by supergroup (gpuar_hip_split_mixed; include/gpuar_hip_mixed.h):
+    supergroup s -- 65536 bytes, the last one maybe fewer -- as split_planes, split_delta or split_xor (against the same bytes of
+    `d_base`) would split it alone, at the width and with the filter d_modes[s] says (mode_parts).  `d_out` may be `d_in`, never
+    the base.  A mode that is not valid, or asks for a base where there is none, is STATUS_BAD_BATCH and leaves its supergroup
+    alone.  Returns d_out."""
+    return _mixed("gpuar_hip_split_mixed", d_in, d_modes, d_base, d_out, n_bytes, stream, d_status)
+
+
+def merge_mixed(d_in, d_modes, d_base=None, d_out=None, n_bytes: int = None, stream=None, d_status=None):
+    """The inverse of split_mixed with the same modes and base (gpuar_hip_merge_mixed); `d_out` may be `d_in`."""
+    return _mixed("gpuar_hip_merge_mixed", d_in, d_modes, d_base, d_out, n_bytes, stream, d_status)
+
+
+def _mixed_batch(name, d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers, n_packets, d_out_ptrs, stream, d_status):
+    _require_batch(d_in_ptrs, d_bytes, d_first_packet, n_buffers, "d_in_ptrs",
+                   ((d_first_mode, "d_first_mode"), (d_base_ptrs, "d_base_ptrs"), (d_out_ptrs, "d_out_ptrs")))
+    _require_modes(d_modes, 0)
+    _call(name, d_in_ptrs.data_ptr(), d_bytes.data_ptr(), d_first_packet.data_ptr(), d_first_mode.data_ptr(), d_modes.data_ptr(),
+          d_base_ptrs.data_ptr(), n_buffers, n_packets, d_out_ptrs.data_ptr(), _status_ptr(d_status), _stream_handle(stream))
+
+
+def split_mixed_batch(d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs,
+                      stream=None, d_status=None):
+    """split_mixed for every buffer of a batch in one call (gpuar_hip_split_mixed_batch; descriptors as for split_xor_batch, with
+    d_first_mode -- where buffer b's modes begin in d_modes, batch_mode_count -- in the widths' place; d_base_ptrs[b] = 0: no base)."""
+    _mixed_batch("gpuar_hip_split_mixed_batch", d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers, n_packets,
+                 d_out_ptrs, stream, d_status)
+
+
+def merge_mixed_batch(d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers: int, n_packets: int, d_out_ptrs,
+                      stream=None, d_status=None):
+    """The inverse of split_mixed_batch (gpuar_hip_merge_mixed_batch)."""
+    _mixed_batch("gpuar_hip_merge_mixed_batch", d_in_ptrs, d_bytes, d_first_packet, d_first_mode, d_modes, d_base_ptrs, n_buffers, n_packets,
+                 d_out_ptrs, stream, d_status)
+
+
+def _mixed_host(name, data, modes, base):
+    data, modes = bytes(data), bytes(modes)
+    if base is not None:
+        base = bytes(base)
+        if len(base) != len(data):
+            raise GpuarError(f"{name}: a base of {len(base)} bytes for {len(data)} bytes")
+    if len(modes) != mode_count(len(data)):
+        raise GpuarError(f"{name}: {len(modes)} modes for {mode_count(len(data))} supergroups")
+    out = C.create_string_buffer(len(data))
+    _call(name, data, base, len(data), modes, out)
+    return out.raw
+
+
+def split_mixed_host(data, modes, base=None) -> bytes:
+    """split_mixed of a bytes-like object on the CPU (gpuar_hip_split_mixed_host: no device is touched); `modes`: one byte per
+    supergroup; a mode that is not valid, or a base mode without `base`, raises."""
+    return _mixed_host("gpuar_hip_split_mixed_host", data, modes, base)
+
+
+def merge_mixed_host(data, modes, base=None) -> bytes:
+    """merge_mixed of a bytes-like object on the CPU (gpuar_hip_merge_mixed_host)."""
+    return _mixed_host("gpuar_hip_merge_mixed_host", data, modes, base)
 
 
 def stored_rule(est: int, ulen: int) -> bool:
