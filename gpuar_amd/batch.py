@@ -581,86 +581,120 @@ def _base_pointer(t, i, device, where, need, whose, noun):
     return t.data_ptr() if need else 0
 
 
-# The filters in front of the coder, in the order in which they win: (hip's split function, hip's merge function, the descriptor rows
-# the two take behind the widths; None: the batch has nothing for this filter to do).  Entry b of such a row is 0 iff buffer b is not filtered.
-_FILTERS = (
-    ("split_xor_batch", "merge_xor_batch", lambda widths, flags, bases: [list(bases)] if bases is not None and any(bases) else None),
-    ("split_delta_batch", "merge_delta_batch", lambda widths, flags, bases: [[int(f) for f in flags]] if flags is not None and any(flags) else None),
-    ("split_planes_batch", "merge_planes_batch", lambda widths, flags, bases: [] if widths is not None and any(w != 1 for w in widths) else None),
-)
-
-
-def _filter(widths, flags, bases):
-    """(split function's name, merge function's name, extra descriptor rows) of the filter this batch takes -- a base over the delta
-    filter over planes alone --; None where nothing is split."""
-    for split, merge, rows in _FILTERS:
-        extra = rows(widths, flags, bases)
-        if extra is not None:
-            return split, merge, extra
-    return None
-
-
 class _Split(NamedTuple):
-    """What _split returns: the descriptors on the device, d_coded the pointers of the bytes to code, d_split the temporary buffer the split
-    copies stand in (None: nothing was split), keep the pinned host copy of the descriptors, for the caller to hold while the launches run."""
+    """What _split returns: the descriptors on the device, d_coded the pointers of the bytes to code, and `hold`: whatever must stay alive
+    while the launches run -- the temporary buffer the split copies stand in, the pinned host copy of the descriptors, the modes on the device."""
     d_ptrs: object
     d_bytes: object
     d_fp: object
     d_coded: object
-    d_split: object
-    keep: object
+    hold: object = None
 
 
-def _split_layout(sizes, widths, extra):
-    """(bytes, per buffer its offset or None): the split copies of the buffers that are split or filtered, back to back (each 16-byte
+class _Batch(NamedTuple):
+    """A batch and its filter plan.  describe's five; what _arguments makes of the keywords -- the width per buffer (None: no planes, filter or
+    base), the filter flag per buffer (None: no delta filter), the base pointer per buffer (0: none; None: no base), per buffer the modes of
+    its supergroups as bytes (None: not mixed) --; what _prepare still has to choose by measurement: `delta_by` the flags (None, "auto" or
+    "survey"), `base_by` which bases are kept (None, "auto" or "survey"), `mixed` the modes, with the delta filter offered if `mixed_delta`.
+    Behind _prepare every `*_by` is None and the batch also has its _Split, the per-packet estimates of the bytes to code where _auto_base
+    made them already (else None) and the status word of every launch so far."""
+    device: object
+    ptrs: list
+    sizes: list
+    first_packet: list
+    n_packets: int
+    widths: list = None
+    flags: list = None
+    bases: list = None
+    modes: list = None
+    delta_by: str = None
+    base_by: str = None
+    mixed: bool = False
+    mixed_delta: bool = False
+    split: _Split = None
+    d_est: object = None
+    d_status: object = None
+
+    @property
+    def n(self) -> int:
+        return len(self.sizes)
+
+    def packets(self, b: int) -> int:
+        return self.first_packet[b + 1] - self.first_packet[b]
+
+
+def _described(tensors, **plan) -> _Batch:
+    """describe's five as a _Batch, with what the caller already has of its plan"""
+    return _Batch(*describe(list(tensors)), **plan)
+
+
+def _status_word(a: _Batch):
+    """the batch's status word; a new one where nothing was launched for it yet"""
+    import torch
+    return a.d_status if a.d_status is not None else torch.zeros(1, dtype=torch.int32, device=a.device)
+
+
+def _modes_tensor(a: _Batch):
+    """The batch's modes (per buffer bytes) back to back as one uint8 device tensor (one entry at least)"""
+    import torch
+    flat = b"".join(a.modes)
+    return torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(a.device)
+
+
+# The filters in front of the coder, in the order in which they win: (hip's split function, hip's merge function, the descriptor rows the
+# two take in the widths' place and behind it -- None: the batch has nothing for this filter to do --, the device tensor they take behind
+# the first of those rows, if any).  The mixed filter takes every buffer's first mode where the others take its width, and every buffer
+# that has bytes; of the others, entry b of a row behind the widths is 0 iff buffer b is not filtered.
+_FILTERS = (
+    ("split_mixed_batch", "merge_mixed_batch", lambda a: [H.batch_mode_count(a.sizes)[0], a.bases or [0] * a.n] if a.modes is not None else None, _modes_tensor),
+    ("split_xor_batch", "merge_xor_batch", lambda a: [a.widths, list(a.bases)] if a.bases is not None and any(a.bases) else None, None),
+    ("split_delta_batch", "merge_delta_batch", lambda a: [a.widths, [int(f) for f in a.flags]] if a.flags is not None and any(a.flags) else None, None),
+    ("split_planes_batch", "merge_planes_batch", lambda a: [a.widths] if a.widths is not None and any(w != 1 for w in a.widths) else None, None),
+)
+
+
+def _filter(a: _Batch):
+    """(split function's name, merge function's name, descriptor rows, device tensor or None) of the filter this batch takes -- mixed, else
+    a base over the delta filter over planes alone --; None where nothing is split."""
+    for split, merge, rows, beside in _FILTERS:
+        found = rows(a)
+        if found is not None:
+            return split, merge, found, beside(a) if beside is not None else None
+    return None
+
+
+def _filter_arguments(d_rows, d_beside):
+    """what a split or merge function takes between the first packets and the counts: the rows on the device, `d_beside` behind the first"""
+    return [*d_rows[:1], *([d_beside] if d_beside is not None else []), *d_rows[1:]]
+
+
+def _split_layout(sizes, moved):
+    """(bytes, per buffer its offset or None): the split copies of the buffers that are `moved` and have bytes, back to back (each 16-byte
     aligned); the others (None) are coded where they are."""
     at, places = 0, []
-    for b, (size, w) in enumerate(zip(sizes, widths)):
-        moved = (w != 1 or any(row[b] for row in extra)) and size
-        places.append(at if moved else None)
-        at += (size + 15) // 16 * 16 if moved else 0
+    for size, m in zip(sizes, moved):
+        places.append(at if m and size else None)
+        at += (size + 15) // 16 * 16 if m and size else 0
     return at, places
 
 
-def _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None, bases=None):
-    """The batch's descriptors on the device and -- where `widths` asks for it -- its buffers split into byte planes (one launch,
-    into a temporary buffer): a _Split.  With `flags` (one bool per buffer, some of them true) the same launch also filters the
-    flagged buffers (hip.split_delta_batch); those get a split copy at any width.  With `bases` (one pointer per buffer, some of them
-    not 0) the same launch XORs those buffers with their bases (hip.split_xor_batch); they too get a split copy at any width."""
+def _split(a: _Batch, stream) -> _Split:
+    """The batch's descriptors on the device and -- where its plan asks for it -- its buffers split (one launch of the filter's split
+    function, into a temporary buffer): into byte planes at `widths`; with `flags` (some of them true) the same launch also filters the
+    flagged buffers (hip.split_delta_batch), with `bases` (some of them not 0) it XORs those buffers with their bases (hip.split_xor_batch):
+    both get a split copy at any width; with `modes` it splits every supergroup by its mode, and every buffer that has bytes gets a copy."""
     import torch
-    found = _filter(widths, flags, bases)
+    found = _filter(a)
     if found is None:
-        (d_ptrs, d_bytes, d_fp), keep = _upload(device, ptrs, sizes, first_packet)
-        return _Split(d_ptrs, d_bytes, d_fp, d_ptrs, None, keep)
-    split, _merge, extra = found
-    total, places = _split_layout(sizes, widths, extra)
-    d_split = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
-    coded = [p if at is None else d_split.data_ptr() + at for p, at in zip(ptrs, places)]
-    (d_ptrs, d_bytes, d_fp, d_elem, *d_extra, d_coded), keep = _upload(device, ptrs, sizes, first_packet, widths, *extra, coded)
-    getattr(H, split)(d_ptrs, d_bytes, d_fp, d_elem, *d_extra, len(sizes), n_packets, d_coded, stream=stream, d_status=d_status)
-    return _Split(d_ptrs, d_bytes, d_fp, d_coded, d_split, keep)
-
-
-def _modes_tensor(modes, device):
-    """The batch's modes (per buffer bytes) back to back as one uint8 device tensor (one entry at least)"""
-    import torch
-    flat = b"".join(modes)
-    return torch.frombuffer(bytearray(flat or b"\0"), dtype=torch.uint8).to(device)
-
-
-def _split_mixed(device, ptrs, sizes, first_packet, n_packets, modes, bases, stream, d_status):
-    """_split for a mixed batch: every buffer that has bytes gets a split copy, made by one hip.split_mixed_batch launch with the
-    buffers' `modes` (per buffer bytes) and `bases` (one pointer per buffer, 0: none; None: no buffer has one)."""
-    import torch
-    n = len(sizes)
-    first_mode, _n_modes = H.batch_mode_count(sizes)
-    total, places = _split_layout(sizes, [1] * n, [[1] * n])
-    d_split = torch.empty(max(total, 16), dtype=torch.uint8, device=device)
-    coded = [p if at is None else d_split.data_ptr() + at for p, at in zip(ptrs, places)]
-    (d_ptrs, d_bytes, d_fp, d_fm, d_bases, d_coded), keep = _upload(device, ptrs, sizes, first_packet, first_mode, bases or [0] * n, coded)
-    d_modes = _modes_tensor(modes, device)
-    H.split_mixed_batch(d_ptrs, d_bytes, d_fp, d_fm, d_modes, d_bases, n, n_packets, d_coded, stream=stream, d_status=d_status)
-    return _Split(d_ptrs, d_bytes, d_fp, d_coded, (d_split, d_modes), keep)
+        (d_ptrs, d_bytes, d_fp), keep = _upload(a.device, a.ptrs, a.sizes, a.first_packet)
+        return _Split(d_ptrs, d_bytes, d_fp, d_ptrs, keep)
+    split, _merge, rows, d_beside = found
+    total, places = _split_layout(a.sizes, [a.modes is not None or rows[0][b] != 1 or any(row[b] for row in rows[1:]) for b in range(a.n)])
+    d_split = torch.empty(max(total, 16), dtype=torch.uint8, device=a.device)
+    coded = [p if at is None else d_split.data_ptr() + at for p, at in zip(a.ptrs, places)]
+    (d_ptrs, d_bytes, d_fp, *d_rows, d_coded), keep = _upload(a.device, a.ptrs, a.sizes, a.first_packet, *rows, coded)
+    getattr(H, split)(d_ptrs, d_bytes, d_fp, *_filter_arguments(d_rows, d_beside), a.n, a.n_packets, d_coded, stream=stream, d_status=a.d_status)
+    return _Split(d_ptrs, d_bytes, d_fp, d_coded, (d_split, d_beside, keep))
 
 
 def _packets(d_ptrs, d_bytes, d_fp, n_buffers, n_packets):
@@ -731,13 +765,33 @@ def _sparse_argument(sparse, stored):
 
 def _kinds(d_scan, d_est, d_len, stored_on):
     """hip.sparse_rule on the device: (kind, sparse record bytes) per packet, int64, from the scan words, the estimates and the
-    packets' lengths."""
+    packets' lengths.  d_scan None: no packet is sparse -- the rule of stored="auto" alone, (kind, None)."""
     import torch
+    raw_ok = (d_est >= 4 + d_len) if stored_on else torch.zeros_like(d_len, dtype=torch.bool)
+    if d_scan is None:
+        return torch.where(raw_ok, H.KIND_RAW, H.KIND_CODED), None
     scan = d_scan.to(torch.int64) & 0xFFFFFFFF
     d_slen = (4 + 3 * (scan >> 8) + 3) & ~3
-    raw_ok = (d_est >= 4 + d_len) if stored_on else torch.zeros_like(d_len, dtype=torch.bool)
     is_sparse = (scan != H.SPARSE_NONE) & (d_slen + 1 < d_est) & (~raw_ok | (d_slen < d_len))
     return torch.where(is_sparse, H.KIND_SPARSE, torch.where(raw_ok, H.KIND_RAW, H.KIND_CODED)), d_slen
+
+
+def _counts_as(d_est, d_len, stored_on, d_scan=None):
+    """The counting rule: what every packet counts as in a predicted size, from the per-packet estimates (int64; one row, or the surveys'
+    4 k rows), the packets' lengths and -- where sparse packets count -- the scan words (shaped as the estimates): as _kinds would keep
+    it, a sparse packet as its record's bytes, a raw one as its own bytes, a coded one as its estimate."""
+    import torch
+    if d_scan is None and not stored_on:
+        return d_est
+    d_kind, d_slen = _kinds(d_scan, d_est, d_len, stored_on)
+    counted = torch.where(d_kind == H.KIND_RAW, d_len.expand_as(d_est), d_est)
+    return counted if d_slen is None else torch.where(d_kind == H.KIND_SPARSE, d_slen, counted)
+
+
+def _per_buffer(d_est, buf, n):
+    """d_est (one int64 per batch packet, or rows of them) summed over the packets of each of the n buffers (buf: every packet's buffer)"""
+    import torch
+    return torch.zeros(d_est.shape[:-1] + (n,), dtype=torch.int64, device=d_est.device).index_add_(d_est.dim() - 1, buf, d_est)
 
 
 def _unit_first_packet(n, device):
@@ -745,81 +799,60 @@ def _unit_first_packet(n, device):
     return torch.arange(n + 1, dtype=torch.int64, device=device)
 
 
-def _auto_delta(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status):
-    """delta="auto": per buffer, whether the filter is predicted to pay.  The batch is split and estimated twice, without and
-    with the filter (two split launches, two estimate_batch launches, one synchronisation), and a buffer takes the filter iff
-    est_delta + its packets <= est_plain: one byte per packet is the estimate's resolution (as in choose_planes), and a tie
-    goes to no filter."""
-    import torch
-    n = len(sizes)
-    if n_packets == 0:
-        return [False] * n
-    totals = []
-    for flags in (None, [True] * n):
-        s = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags)
-        d_est = H.estimate_batch(s.d_coded, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=d_status, device=device).to(torch.int64)
-        buf, _ptr, _len = _packets(s.d_coded, s.d_bytes, s.d_fp, n, n_packets)
-        totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est[:n_packets]))
-        del s                                              # (the split copy: freed in front of the next)
-    plain, filtered = torch.stack(totals).tolist()
-    _raise_on_status(d_status, "split_delta_batch")
-    return [_pays(first_packet, b, filtered[b], plain[b]) for b in range(n)]
-
-
-def _pays(first_packet, b, est_with, est_without):
+def _pays(a: _Batch, b, est_with, est_without):
     """The rule of delta="auto", delta="survey" and base_auto for buffer b: est_with + its packets <= est_without, and it has packets."""
-    packets = first_packet[b + 1] - first_packet[b]
-    return packets > 0 and est_with + packets <= est_without
+    return a.packets(b) > 0 and est_with + a.packets(b) <= est_without
 
 
-def _auto_base(device, ptrs, sizes, first_packet, n_packets, widths, bases, stream, d_status):
+def _both_ways(a: _Batch, other: _Batch, stream, what, keep):
+    """The batch split and estimated twice, without filter or base and as `other` -- the same batch with the flags or bases to try -- says:
+    two split launches, two estimate_batch launches, one synchronisation; raises on any status bit, naming `what`.  Returns (the per-buffer
+    totals without, those with, every packet's buffer, both _Splits, both per-packet estimates).  Without `keep` the last two are empty and
+    the first split copy is freed in front of the second split; with it both copies stay (twice the temporary memory)."""
+    import torch
+    halves, estimates, totals = [], [], []
+    for way in (a._replace(flags=None, bases=None), other):
+        s = _split(way, stream)
+        d_est = H.estimate_batch(s.d_coded, s.d_bytes, s.d_fp, a.n, a.n_packets, stream=stream, d_status=a.d_status, device=a.device)[:a.n_packets].to(torch.int64)
+        buf, _ptr, _len = _packets(s.d_coded, s.d_bytes, s.d_fp, a.n, a.n_packets)
+        totals.append(_per_buffer(d_est, buf, a.n))
+        if keep:
+            halves.append(s)
+            estimates.append(d_est)
+        del s                                              # (not kept: the split copy is freed in front of the next)
+    without, with_ = torch.stack(totals).tolist()
+    _raise_on_status(a.d_status, what)
+    return without, with_, buf, halves, estimates
+
+
+def _auto_delta(a: _Batch, stream):
+    """delta="auto": per buffer, whether the filter is predicted to pay.  The batch is split and estimated twice, without and
+    with the filter (_both_ways, neither copy kept), and a buffer takes the filter iff est_delta + its packets <= est_plain: one byte per
+    packet is the estimate's resolution (as in choose_planes), and a tie goes to no filter."""
+    if a.n_packets == 0:
+        return [False] * a.n
+    plain, filtered, *_rest = _both_ways(a, a._replace(flags=[True] * a.n), stream, "split_delta_batch", False)
+    return [_pays(a, b, filtered[b], plain[b]) for b in range(a.n)]
+
+
+def _auto_base(a: _Batch, stream):
     """base_auto=True: per buffer, whether its base is predicted to pay, and the batch split accordingly.  The batch is split and
     estimated twice, without and with the bases -- one split launch and one estimate launch more than the path with fixed bases and
     stored="auto" takes, and one synchronisation -- and a buffer keeps its base iff est_xor + its packets <= est_plain (the rule
     of _auto_delta; a tie goes to no base).  Nothing is split a third time: both split copies are kept (twice the temporary
     memory until the slots are freed) and every buffer is coded from the copy of its choice.  Returns (the choices, what _split
-    returns with d_coded and d_split made of both copies, the chosen copy's per-packet estimates); (all False, None, None)
+    returns with d_coded made of both copies and both held, the chosen copy's per-packet estimates); (all False, None, None)
     where there is nothing to choose."""
     import torch
-    n = len(sizes)
-    if n_packets == 0 or not any(bases):
-        return [False] * n, None, None
-    halves, estimates, totals = [], [], []
-    for with_bases in (None, bases):
-        s = _split(device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, None, with_bases)
-        halves.append(s)
-        estimates.append(H.estimate_batch(s.d_coded, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)[:n_packets].to(torch.int64))
-        buf, _ptr, _len = _packets(s.d_coded, s.d_bytes, s.d_fp, n, n_packets)
-        totals.append(torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, estimates[-1]))
-    plain, xored = torch.stack(totals).tolist()
-    _raise_on_status(d_status, "split_xor_batch")
-    keep = [bool(bases[b]) and _pays(first_packet, b, xored[b], plain[b]) for b in range(n)]
-    (d_keep,), pinned = _upload(device, [int(k) for k in keep])
+    if a.n_packets == 0 or not any(a.bases):
+        return [False] * a.n, None, None
+    plain, xored, buf, (without, with_), estimates = _both_ways(a, a, stream, "split_xor_batch", True)
+    keep = [bool(a.bases[b]) and _pays(a, b, xored[b], plain[b]) for b in range(a.n)]
+    (d_keep,), pinned = _upload(a.device, [int(k) for k in keep])
     d_keep = d_keep != 0
-    without, with_ = halves
     d_coded = torch.where(d_keep, with_.d_coded, without.d_coded)
     d_est = torch.where(d_keep[buf], estimates[1], estimates[0])
-    return keep, _Split(s.d_ptrs, s.d_bytes, s.d_fp, d_coded, (without.d_split, with_.d_split), (without.keep, with_.keep, pinned)), d_est
-
-
-class _Batch(NamedTuple):
-    """What _arguments makes of a call's tensors and keywords: describe's five, the width per buffer (None: no planes, filter or base),
-    the filter flags (None, one bool per buffer, or "auto" / "survey" for _prepare to resolve) and the base pointers (None: no base).
-    Behind _prepare also the _Split, the per-packet estimates of the bytes to code where _auto_base made them already (else None) and
-    the status word of every launch so far."""
-    device: object
-    ptrs: list
-    sizes: list
-    first_packet: list
-    n_packets: int
-    widths: list
-    flags: object
-    bases: list
-    split: _Split = None
-    d_est: object = None
-    d_status: object = None
-    base_chosen: bool = False               # base_auto="survey" was resolved with the widths (planes="survey"): `bases` are the kept ones
-    modes: object = None                    # planes="mixed": (delta offered) for _prepare to resolve, behind it per buffer the modes as bytes
+    return keep, _Split(with_.d_ptrs, with_.d_bytes, with_.d_fp, d_coded, (without.hold, with_.hold, pinned)), d_est
 
 
 def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=None) -> _Batch:
@@ -827,7 +860,7 @@ def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=N
     launch -- base_auto without a base, a base_auto that is a string other than "survey", a base beside `delta`, whatever base_pointers, describe, plane_widths and delta_flags refuse --,
     and planes="survey" resolved: the one step here that launches, on `stream`, with a `stored` that no caller takes refused in front
     of it.  A filter or a base without `planes` works on bytes (width 1).  With base_auto="survey" the same step chooses width and
-    base together (survey_base_choice; `sparse` is what its totals count)."""
+    base together (survey_base_choice; `sparse` is what its totals count), and `base_by` has nothing left to choose."""
     import torch
     if base is None and base_auto:
         raise GpuarError("base_auto=True needs base=[...]")
@@ -842,89 +875,55 @@ def _arguments(tensors, planes, stored, delta, base, base_auto, stream, sparse=N
         raise GpuarError("planes=\"mixed\" chooses the base per supergroup: base_auto has nothing left to choose")
     if base is not None and delta is not None and not mixed:
         raise GpuarError("base together with delta: that combination is not built (DESIGN.md 4.10)")
-    bases, base_chosen = base_pointers(tensors, base), False
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
+    a = _described(tensors, bases=base_pointers(tensors, base))
     if mixed:
-        if device is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        return _Batch(device, ptrs, sizes, first_packet, n_packets, None, None, bases, modes=(delta is not None,))
-    if _is(planes, "survey"):
-        stored = _stored_argument(stored, n_packets)
-        with _on(stream):
-            if _is(delta, "survey"):
-                planes, delta = survey_choice(tensors, stored)
-            elif _is(base_auto, "survey"):
-                planes, kept = survey_base_choice(tensors, base, stored if _is(stored, "auto") else None, sparse if _is(sparse, "auto") else None)
-                bases, base_chosen = [q if keep else 0 for q, keep in zip(bases, kept)], True
-            else:
-                planes = survey_widths(tensors, stored)
-    widths = plane_widths(tensors, planes)
-    if widths is None and (delta is not None or bases is not None):
-        widths = [1] * len(tensors)
-    flags = delta if isinstance(delta, str) and delta in ("auto", "survey") else delta_flags(tensors, delta)
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return _Batch(device, ptrs, sizes, first_packet, n_packets, widths, flags, bases, base_chosen=base_chosen)
+        a = a._replace(mixed=True, mixed_delta=delta is not None)
+    else:
+        base_by = None if a.bases is None or not base_auto else "survey" if _is(base_auto, "survey") else "auto"
+        if _is(planes, "survey"):
+            stored = _stored_argument(stored, a.n_packets)
+            with _on(stream):
+                if _is(delta, "survey"):
+                    planes, delta = _survey_choice(a, stored)
+                elif base_by == "survey":
+                    planes, kept = _survey_base_choice(a, stored if _is(stored, "auto") else None, sparse if _is(sparse, "auto") else None)
+                    a, base_by = a._replace(bases=[q if keep else 0 for q, keep in zip(a.bases, kept)]), None
+                else:
+                    planes = _survey_widths(a, stored)
+        widths = plane_widths(tensors, planes)
+        if widths is None and (delta is not None or a.bases is not None):
+            widths = [1] * a.n
+        delta_by = delta if isinstance(delta, str) and delta in ("auto", "survey") else None
+        a = a._replace(widths=widths, flags=None if delta_by else delta_flags(tensors, delta), delta_by=delta_by, base_by=base_by)
+    if a.device is None:
+        a = a._replace(device=torch.device("cuda", torch.cuda.current_device()))
+    return a
 
 
-def _prepare(a: _Batch, base_auto, stream) -> _Batch:
+def _prepare(a: _Batch, stream) -> _Batch:
     """The device step compress and estimate share, on the current stream (`stream`, where the caller is in its context): `a` with
-    delta="auto" / "survey" and base_auto resolved by measurement (flags, bases: lists or None) and with the batch split -- by
-    _auto_base where that has split it both ways, else by one _split."""
+    everything chosen that was left to measurement -- the modes of a mixed batch (_survey_mixed), the flags of delta="auto" / "survey", the
+    bases base_auto keeps -- and with the batch split: by _auto_base where that has split it both ways, else by one _split."""
     import torch
-    d_status = torch.zeros(1, dtype=torch.int32, device=a.device)
-    if a.modes is not None:
-        chosen = _survey_mixed(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.modes[0], a.bases, d_status)
-        modes = [m for m, _total in chosen]
-        split = _split_mixed(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, modes, a.bases, stream, d_status)
-        return a._replace(modes=modes, split=split, d_status=d_status)
-    flags, bases, split, d_est = a.flags, a.bases, None, None
-    if flags == "auto":
-        flags = _auto_delta(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status)
-    elif flags == "survey":
-        flags = _survey_delta_flags(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, d_status)
-    if bases is not None and _is(base_auto, "survey"):
-        if not a.base_chosen:
-            choice = _survey_base_keep(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, bases, d_status)
-            bases = [q if keep else 0 for q, keep in zip(bases, choice)]
-    elif bases is not None and base_auto:
-        choice, split, d_est = _auto_base(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, bases, stream, d_status)
-        bases = [q if keep else 0 for q, keep in zip(bases, choice)]
-    if split is None:
-        split = _split(a.device, a.ptrs, a.sizes, a.first_packet, a.n_packets, a.widths, stream, d_status, flags, bases)
-    return a._replace(flags=flags, bases=bases, split=split, d_est=d_est, d_status=d_status)
+    a = a._replace(d_status=torch.zeros(1, dtype=torch.int32, device=a.device))
+    if a.mixed:
+        a = a._replace(modes=[m for m, _total in _survey_mixed(a, a.mixed_delta)])
+    if a.delta_by is not None:
+        a = a._replace(flags=_auto_delta(a, stream) if a.delta_by == "auto" else _survey_delta_flags(a), delta_by=None)
+    if a.base_by is not None:
+        keep, split, d_est = _auto_base(a, stream) if a.base_by == "auto" else (_survey_base_keep(a), None, None)
+        a = a._replace(bases=[q if k else 0 for q, k in zip(a.bases, keep)], base_by=None, split=split, d_est=d_est)
+    return a if a.split is not None else a._replace(split=_split(a, stream))
 
 
-def survey(tensors, stored=None) -> list:
-    """What every tensor would compress to at each byte-plane width, without splitting or encoding anything: per tensor the four
-    predicted totals [T1, T2, T4, T8], T_w = estimate([t], planes=w, stored=stored)[0].  One hip.survey_planes_batch launch over
-    the original bytes and one synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
-    stored = _stored_auto(stored)
-    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
-    if n_packets == 0:
-        return [[0] * len(H.SURVEY_WIDTHS) for _ in sizes]
-    plain, _filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, True, None, "survey_planes_batch")
-    return plain
-
-
-def survey_widths(tensors, stored=None) -> list:
-    """planes="survey": per tensor the width hip.choose_planes picks from survey(tensors, stored) (an empty tensor: 1)."""
-    tensors = list(tensors)
-    _device, _ptrs, _sizes, first_packet, _np = describe(tensors)
-    return [H.choose_planes(totals, first_packet[b + 1] - first_packet[b])
-            for b, totals in enumerate(survey(tensors, stored="auto" if _is(stored, "auto") else None))]
-
-
-def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, widths, what, d_status=None):
+def _survey_totals(a: _Batch, stored, plain, widths, what):
     """Per buffer the four totals of the plane survey (if `plain`) and of the delta survey at `widths` (if not None; a width
     that was not asked for: 0): one hip.survey_planes_batch launch, one hip.survey_delta_batch launch, one synchronisation, on the
     current stream.  stored="auto" (any other value: as None) counts a packet that would be kept raw as its own bytes.  Raises on any
-    status bit, naming `what`; d_status: the caller's status word, where it has one."""
+    status bit, naming `what`."""
     import torch
-    n = len(sizes)
-    if d_status is None:
-        d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, ptrs, sizes, first_packet)
+    n, n_packets, device, d_status = a.n, a.n_packets, a.device, _status_word(a)
+    (d_ptrs, d_bytes, d_fp), _keep = _upload(device, a.ptrs, a.sizes, a.first_packet)
     rows = []
     if plain:
         rows.append(H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device))
@@ -933,9 +932,7 @@ def _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, plain, 
         rows.append(H.survey_delta_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_est=d_est, d_status=d_status, device=device, widths=widths))
     d_est = (rows[0] if len(rows) == 1 else torch.cat(rows)).to(torch.int64)
     buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
-    if _is(stored, "auto"):
-        d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
-    both = _totals_per_buffer(d_est, buf, n, d_status, what)
+    both = _totals_per_buffer(_counts_as(d_est, d_len, _is(stored, "auto")), buf, n, d_status, what)
     return (both[0] if plain else None), (both[-1] if widths is not None else None)
 
 
@@ -944,12 +941,104 @@ def _totals_per_buffer(d_est, buf, n, d_status, what):
     the packets of each of the n buffers (buf: every packet's buffer), as [survey][buffer][four totals]; raises on any status bit,
     naming `what`."""
     import torch
-    totals = torch.zeros((d_est.shape[0], n), dtype=torch.int64, device=d_est.device).index_add_(1, buf, d_est)
-    *flat, flags = torch.cat([totals.t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
+    *flat, flags = torch.cat([_per_buffer(d_est, buf, n).t().reshape(-1), d_status.to(torch.int64)]).tolist()      # the one synchronisation
     if flags:
         _raise_on_status(d_status, what)
     per = len(flat) // n
     return [[flat[per * b + 4 * k:per * b + 4 * k + 4] for b in range(n)] for k in range(per // 4)]
+
+
+def _survey_xor_totals(a: _Batch, stored, sparse, plain, what):
+    """Per buffer the four totals of the XOR survey against the batch's bases (one pointer per buffer, 0: none) and, if `plain`, the four
+    of the bytes as they are: (plain or None, xored).  One hip.survey_xor_batch launch, for `plain` one launch more -- hip.survey_planes_batch,
+    or, where sparse packets count, the XOR survey with base pointers of 0, which also gives scan words --, one synchronisation, on
+    the current stream.  stored="auto" and sparse="auto" (any other value: as None) count every packet as _kinds' rule would keep
+    it at that width: its record, its own bytes or its estimate (_counts_as).  Raises on any status bit, naming `what`."""
+    import torch
+    n, n_packets, device, d_status = a.n, a.n_packets, a.device, _status_word(a)
+    count_sparse, stored_on = _is(sparse, "auto"), _is(stored, "auto")
+    (d_ptrs, d_bytes, d_fp, d_bases, d_none), _keep = _upload(device, a.ptrs, a.sizes, a.first_packet, list(a.bases), [0] * n)
+    want_scan = None if count_sparse else False
+    sides = []
+    if plain and count_sparse:
+        sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_none, n, n_packets, d_status=d_status, device=device))
+    elif plain:
+        sides.append((H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device), None))
+    sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_bases, n, n_packets, d_scan=want_scan, d_status=d_status, device=device))
+    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
+    rows = [_counts_as(d_est[:, :n_packets].to(torch.int64), d_len, stored_on, d_scan[:, :n_packets] if count_sparse else None)
+            for d_est, d_scan in sides]
+    both = _totals_per_buffer(torch.cat(rows), buf, n, d_status, what)
+    return (both[0] if plain else None), both[-1]
+
+
+def _survey_pays(a: _Batch, keyword, offered, measure):
+    """delta="survey" and base_auto="survey" with the widths fixed: per buffer, whether what is `offered` to it (the filter; its base) is
+    predicted to pay at the buffer's width -- the decision of _auto_delta and _auto_base, est_with + its packets <= est_plain on coded
+    estimates, from the (plain, with) totals of two surveys of the original bytes, which `measure` makes: two launches and one
+    synchronisation, no split and no temporary.  A width the surveys do not have raises before any launch, naming `keyword`."""
+    if a.n_packets == 0 or not any(offered):
+        return [False] * a.n
+    if any(w not in H.SURVEY_WIDTHS for w in a.widths):
+        raise GpuarError(f"{keyword}=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(a.widths) - set(H.SURVEY_WIDTHS))}")
+    plain, tried = measure()
+    rows = [H.SURVEY_WIDTHS.index(w) for w in a.widths]
+    return [bool(offered[b]) and _pays(a, b, tried[b][j], plain[b][j]) for b, j in enumerate(rows)]
+
+
+def _survey_delta_flags(a: _Batch):
+    """delta="survey" with the widths fixed (_survey_pays): the plane survey and the delta survey masked to the widths in use"""
+    used = sorted({w for w, size in zip(a.widths, a.sizes) if size})
+    return _survey_pays(a, "delta", [True] * a.n, lambda: _survey_totals(a, None, True, used, "survey_delta_batch"))
+
+
+def _survey_base_keep(a: _Batch):
+    """base_auto="survey" with the widths fixed (_survey_pays): the plane survey and the XOR survey; a buffer without a base keeps none"""
+    return _survey_pays(a, "base_auto", a.bases, lambda: _survey_xor_totals(a, None, None, True, "survey_xor_batch"))
+
+
+def _chosen_together(a: _Batch, offered, measure):
+    """Width and filter together: per buffer the (width, taken) hip.choose_filter picks from the (plain, with) totals `measure` makes --
+    two survey launches and one synchronisation --, as (widths, taken); a buffer with nothing `offered` gets hip.choose_planes' width
+    of its plain totals, and a batch without packets (1, False) throughout, without a launch."""
+    if a.n_packets == 0:
+        return [1] * a.n, [False] * a.n
+    plain, tried = measure()
+    choices = [H.choose_filter(plain[b], tried[b], a.packets(b)) if offered[b] else (H.choose_planes(plain[b], a.packets(b)), False)
+               for b in range(a.n)]
+    return [w for w, _t in choices], [t for _w, t in choices]
+
+
+# survey, survey_widths, survey_choice and survey_base_choice on a batch that is described already: what _arguments calls too
+def _survey_plain(a: _Batch, stored):
+    if a.n_packets == 0:
+        return [[0] * len(H.SURVEY_WIDTHS) for _ in a.sizes]
+    return _survey_totals(a, stored, True, None, "survey_planes_batch")[0]
+
+
+def _survey_widths(a: _Batch, stored):
+    return [H.choose_planes(totals, a.packets(b)) for b, totals in enumerate(_survey_plain(a, "auto" if _is(stored, "auto") else None))]
+
+
+def _survey_choice(a: _Batch, stored):
+    return _chosen_together(a, [True] * a.n, lambda: _survey_totals(a, stored, True, H.SURVEY_WIDTHS, "survey_delta_batch"))
+
+
+def _survey_base_choice(a: _Batch, stored, sparse):
+    return _chosen_together(a, a.bases, lambda: _survey_xor_totals(a, stored, sparse, True, "survey_xor_batch"))
+
+
+def survey(tensors, stored=None) -> list:
+    """What every tensor would compress to at each byte-plane width, without splitting or encoding anything: per tensor the four
+    predicted totals [T1, T2, T4, T8], T_w = estimate([t], planes=w, stored=stored)[0].  One hip.survey_planes_batch launch over
+    the original bytes and one synchronisation.  stored="auto" counts a packet that would be kept raw as its own bytes."""
+    stored = _stored_auto(stored)
+    return _survey_plain(_described(tensors), stored)
+
+
+def survey_widths(tensors, stored=None) -> list:
+    """planes="survey": per tensor the width hip.choose_planes picks from survey(tensors, stored) (an empty tensor: 1)."""
+    return _survey_widths(_described(tensors), stored)
 
 
 def survey_delta(tensors, stored=None, widths=None) -> list:
@@ -960,81 +1049,34 @@ def survey_delta(tensors, stored=None, widths=None) -> list:
     stored = _stored_auto(stored)
     widths = tuple(H.SURVEY_WIDTHS if widths is None else widths)
     H.widths_mask(widths)
-    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
-    if n_packets == 0:
-        return [[0 if w in widths else None for w in H.SURVEY_WIDTHS] for _ in sizes]
-    _plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, False, widths, "survey_delta_batch")
+    a = _described(tensors)
+    if a.n_packets == 0:
+        return [[0 if w in widths else None for w in H.SURVEY_WIDTHS] for _ in a.sizes]
+    _plain, filtered = _survey_totals(a, stored, False, widths, "survey_delta_batch")
     return [[t if w in widths else None for w, t in zip(H.SURVEY_WIDTHS, row)] for row in filtered]
-
-
-def _survey_delta_flags(device, ptrs, sizes, first_packet, n_packets, widths, d_status):
-    """delta="survey" with the widths fixed: per buffer, whether the filter is predicted to pay at the buffer's width -- the
-    decision of _auto_delta, est_delta + its packets <= est_plain, from the two surveys of the original bytes (the delta survey
-    masked to the widths in use): two launches and one synchronisation, no split and no temporary."""
-    n = len(sizes)
-    if n_packets == 0:
-        return [False] * n
-    if any(w not in H.SURVEY_WIDTHS for w in widths):
-        raise GpuarError(f"delta=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(widths) - set(H.SURVEY_WIDTHS))}")
-    used = sorted({w for w, size in zip(widths, sizes) if size})
-    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, None, True, used, "survey_delta_batch", d_status)
-    rows = [H.SURVEY_WIDTHS.index(w) for w in widths]
-    return [_pays(first_packet, b, filtered[b][j], plain[b][j]) for b, j in enumerate(rows)]
 
 
 def survey_choice(tensors, stored=None):
     """planes="survey" with delta="survey": per tensor the (width, filter) hip.choose_filter picks from both surveys of its bytes
     (an empty tensor: (1, False)), as (widths, flags).  Two launches and one synchronisation."""
-    device, ptrs, sizes, first_packet, n_packets = describe(list(tensors))
-    if n_packets == 0:
-        return [1] * len(sizes), [False] * len(sizes)
-    plain, filtered = _survey_totals(device, ptrs, sizes, first_packet, n_packets, stored, True, H.SURVEY_WIDTHS, "survey_delta_batch")
-    choices = [H.choose_filter(plain[b], filtered[b], first_packet[b + 1] - first_packet[b]) for b in range(len(sizes))]
-    return [w for w, _f in choices], [f for _w, f in choices]
-
-
-def _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, plain, what, d_status=None):
-    """Per buffer the four totals of the XOR survey against `bases` (one pointer per buffer, 0: none) and, if `plain`, the four of
-    the bytes as they are: (plain or None, xored).  One hip.survey_xor_batch launch, for `plain` one launch more -- hip.survey_planes_batch,
-    or, where sparse packets count, the XOR survey with base pointers of 0, which also gives scan words --, one synchronisation, on
-    the current stream.  stored="auto" and sparse="auto" (any other value: as None) count every packet as _kinds' rule would keep
-    it at that width: its record, its own bytes or its estimate.  Raises on any status bit, naming `what`."""
-    import torch
-    n = len(sizes)
-    if d_status is None:
-        d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    count_sparse, stored_on = _is(sparse, "auto"), _is(stored, "auto")
-    (d_ptrs, d_bytes, d_fp, d_bases, d_none), _keep = _upload(device, ptrs, sizes, first_packet, list(bases), [0] * n)
-    want_scan = None if count_sparse else False
-    sides = []
-    if plain and count_sparse:
-        sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_none, n, n_packets, d_status=d_status, device=device))
-    elif plain:
-        sides.append((H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device), None))
-    sides.append(H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_bases, n, n_packets, d_scan=want_scan, d_status=d_status, device=device))
-    buf, _ptr, d_len = _packets(d_ptrs, d_bytes, d_fp, n, n_packets)      # (a packet of a split layout has its original's length)
-    rows = []
-    for d_est, d_scan in sides:
-        d_est = d_est[:, :n_packets].to(torch.int64)
-        if count_sparse:
-            d_kind, d_slen = _kinds(d_scan[:, :n_packets], d_est, d_len, stored_on)
-            d_est = torch.where(d_kind == H.KIND_SPARSE, d_slen, torch.where(d_kind == H.KIND_RAW, d_len.expand_as(d_est), d_est))
-        elif stored_on:
-            d_est = torch.where(d_est >= 4 + d_len, d_len.expand_as(d_est), d_est)
-        rows.append(d_est)
-    both = _totals_per_buffer(torch.cat(rows), buf, n, d_status, what)
-    return (both[0] if plain else None), both[-1]
+    return _survey_choice(_described(tensors), stored)
 
 
 def _survey_xor_arguments(tensors, base, stored, sparse):
-    """What survey_xor and survey_xor_widths refuse, before any launch, and the batch's description with its base pointers"""
+    """What survey_xor, survey_xor_widths and survey_base_choice refuse, before any launch, and the batch's description with its base pointers"""
     tensors = list(tensors)
     stored = _stored_auto(stored)
     sparse = _sparse_argument(sparse, stored)
     if base is None:
         raise GpuarError("survey_xor needs base=[...]")
     bases = base_pointers(tensors, base)
-    return describe(tensors), bases, stored, sparse
+    return _described(tensors, bases=bases), stored, sparse
+
+
+def _survey_xor(a: _Batch, stored, sparse):
+    if a.n_packets == 0:
+        return [[0] * len(H.SURVEY_WIDTHS) for _ in a.sizes]
+    return _survey_xor_totals(a, stored, sparse, False, "survey_xor_batch")[1]
 
 
 def survey_xor(tensors, base, stored=None, sparse=None) -> list:
@@ -1042,62 +1084,38 @@ def survey_xor(tensors, base, stored=None, sparse=None) -> list:
     anything: per tensor [X1, X2, X4, X8], X_w = estimate([t], planes=w, base=[b], stored=stored, sparse=sparse)[0]; a tensor whose
     base is None gets its plain totals.  One hip.survey_xor_batch launch over the original bytes and the bases, and one
     synchronisation; _kinds' rule is applied per width on the device, from the survey's est and scan rows."""
-    (device, ptrs, sizes, first_packet, n_packets), bases, stored, sparse = _survey_xor_arguments(tensors, base, stored, sparse)
-    if n_packets == 0:
-        return [[0] * len(H.SURVEY_WIDTHS) for _ in sizes]
-    _plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, False, "survey_xor_batch")
-    return xored
+    return _survey_xor(*_survey_xor_arguments(tensors, base, stored, sparse))
 
 
 def survey_xor_widths(tensors, base, stored=None, sparse=None) -> list:
     """For a caller who keeps the bases: per tensor the width hip.choose_planes picks from survey_xor's totals -- the width of the
     bytes that are coded, not of the original ones (an empty tensor: 1)."""
-    tensors = list(tensors)
-    _device, _ptrs, _sizes, first_packet, _np = describe(tensors)
-    return [H.choose_planes(totals, first_packet[b + 1] - first_packet[b]) for b, totals in enumerate(survey_xor(tensors, base, stored, sparse))]
-
-
-def _survey_base_keep(device, ptrs, sizes, first_packet, n_packets, widths, bases, d_status):
-    """base_auto="survey" with the widths fixed: per buffer, whether its base is predicted to pay at the buffer's width -- the
-    decision of _auto_base, est_xor + its packets <= est_plain on coded estimates, from the plane survey and the XOR survey of the
-    original bytes: two launches and one synchronisation, no split and no temporary."""
-    n = len(sizes)
-    if n_packets == 0 or not any(bases):
-        return [False] * n
-    if any(w not in H.SURVEY_WIDTHS for w in widths):
-        raise GpuarError(f"base_auto=\"survey\": the widths are {H.SURVEY_WIDTHS}, not {sorted(set(widths) - set(H.SURVEY_WIDTHS))}")
-    plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, None, None, True, "survey_xor_batch", d_status)
-    rows = [H.SURVEY_WIDTHS.index(w) for w in widths]
-    return [bool(bases[b]) and _pays(first_packet, b, xored[b][j], plain[b][j]) for b, j in enumerate(rows)]
+    a, stored, sparse = _survey_xor_arguments(tensors, base, stored, sparse)
+    return [H.choose_planes(totals, a.packets(b)) for b, totals in enumerate(_survey_xor(a, stored, sparse))]
 
 
 def survey_base_choice(tensors, base, stored=None, sparse=None):
     """planes="survey" with base_auto="survey": per tensor the (width, base kept) hip.choose_filter picks from the totals of its
     bytes as they are and XORed against its base (an empty tensor or one without a base: its plain width, no base), as (widths,
     kept).  Two launches and one synchronisation; with sparse="auto" both sides count sparse packets."""
-    (device, ptrs, sizes, first_packet, n_packets), bases, stored, sparse = _survey_xor_arguments(tensors, base, stored, sparse)
-    if n_packets == 0:
-        return [1] * len(sizes), [False] * len(sizes)
-    plain, xored = _survey_xor_totals(device, ptrs, sizes, first_packet, n_packets, bases, stored, sparse, True, "survey_xor_batch")
-    choices = [H.choose_filter(plain[b], xored[b], first_packet[b + 1] - first_packet[b]) if bases[b] else
-               (H.choose_planes(plain[b], first_packet[b + 1] - first_packet[b]), False) for b in range(len(sizes))]
-    return [w for w, _k in choices], [k for _w, k in choices]
+    return _survey_base_choice(*_survey_xor_arguments(tensors, base, stored, sparse))
 
 
-def _survey_mixed(device, ptrs, sizes, first_packet, n_packets, delta, bases, d_status):
+def _survey_mixed(a: _Batch, delta):
     """Per buffer (its modes as bytes, their predicted totals summed): the plane survey, the delta survey if `delta`, the XOR survey
-    if some buffer has a base (`bases`: one pointer per buffer, 0: none; or None) -- a buffer without one gets its plane rows there,
-    which never win --, then one hip.choose_modes_batch launch and one synchronisation, on the current stream."""
+    if some buffer has a base (the batch's bases: one pointer per buffer, 0: none; or None) -- a buffer without one gets its plane rows
+    there, which never win --, then one hip.choose_modes_batch launch and one synchronisation, on the current stream."""
     import torch
-    n = len(sizes)
-    first_mode, n_modes = H.batch_mode_count(sizes)
+    n, n_packets, device = a.n, a.n_packets, a.device
+    first_mode, n_modes = H.batch_mode_count(a.sizes)
     if n_packets == 0:
         return [(b"", 0)] * n
-    (d_ptrs, d_bytes, d_fp, d_fm, d_bases), _keep = _upload(device, ptrs, sizes, first_packet, first_mode, bases or [0] * n)
+    d_status = _status_word(a)
+    (d_ptrs, d_bytes, d_fp, d_fm, d_bases), _keep = _upload(device, a.ptrs, a.sizes, a.first_packet, first_mode, a.bases or [0] * n)
     d_plain = H.survey_planes_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device)
     d_delta = H.survey_delta_batch(d_ptrs, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device) if delta else None
     d_xored = None
-    if bases is not None and any(bases):
+    if a.bases is not None and any(a.bases):
         d_xored, _scan = H.survey_xor_batch(d_ptrs, d_bytes, d_fp, d_bases, n, n_packets, d_scan=False, d_status=d_status, device=device)
     d_modes, d_totals = H.choose_modes_batch(d_plain, d_delta, d_xored, d_bytes, d_fp, d_fm, n, n_packets, n_modes, d_status=d_status)
     *flat, flags = torch.cat([d_modes.to(torch.int64), d_totals.to(torch.int64), d_status.to(torch.int64)]).tolist()      # the one synchronisation
@@ -1114,13 +1132,7 @@ def survey_mixed(tensors, delta=False, base=None) -> list:
     surveys' launches over the original bytes, one hip.choose_modes_batch launch and one synchronisation.  The total is at most the
     lowest total any single (width, filter) offered gives the tensor, plus two bytes per packet (gpuar_amd/csrc/mixed.h)."""
     tensors = list(tensors)
-    bases = base_pointers(tensors, base)
-    device, ptrs, sizes, first_packet, n_packets = describe(tensors)
-    if n_packets == 0:
-        return [(b"", 0)] * len(sizes)
-    import torch
-    d_status = torch.zeros(1, dtype=torch.int32, device=device)
-    return _survey_mixed(device, ptrs, sizes, first_packet, n_packets, bool(delta), bases, d_status)
+    return _survey_mixed(_described(tensors, bases=base_pointers(tensors, base)), bool(delta))
 
 
 def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto=False, sparse=None) -> list:
@@ -1136,109 +1148,143 @@ def estimate(tensors, planes=None, stored=None, delta=None, base=None, base_auto
     stored = _stored_auto(stored)                                # (no list of stored packets: compress alone takes one)
     sparse = _sparse_argument(sparse, stored)
     a = _arguments(list(tensors), planes, stored, delta, base, base_auto, None, sparse)
-    device, n, n_packets = a.device, len(a.sizes), a.n_packets
-    if n_packets == 0:
-        return [0] * n
-    a = _prepare(a, base_auto, None)
-    d_status, d_est, d_coded, d_bytes, d_fp = a.d_status, a.d_est, a.split.d_coded, a.split.d_bytes, a.split.d_fp
+    if a.n_packets == 0:
+        return [0] * a.n
+    a = _prepare(a, None)
+    d_coded, d_bytes, d_fp = a.split.d_coded, a.split.d_bytes, a.split.d_fp
+    d_est = a.d_est
     if d_est is None:
-        d_est = H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device).to(torch.int64)
-    buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
-    if sparse == "auto":
-        d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, d_status=d_status, device=device)
-        d_kind, d_slen = _kinds(d_scan, d_est[:n_packets], d_len, stored == "auto")
-        d_est = torch.where(d_kind == H.KIND_SPARSE, d_slen, torch.where(d_kind == H.KIND_RAW, d_len, d_est[:n_packets]))
-    elif stored == "auto":
-        d_est = torch.where(d_est >= 4 + d_len, d_len, d_est)
-    totals = torch.zeros(n, dtype=torch.int64, device=device).index_add_(0, buf, d_est)
-    _raise_on_status(d_status, "estimate_batch")
+        d_est = H.estimate_batch(d_coded, d_bytes, d_fp, a.n, a.n_packets, d_status=a.d_status, device=a.device).to(torch.int64)
+    buf, _ptr, d_len = _packets(d_coded, d_bytes, d_fp, a.n, a.n_packets)
+    d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, a.n, a.n_packets, d_status=a.d_status, device=a.device) if sparse == "auto" else None
+    totals = _per_buffer(_counts_as(d_est[:a.n_packets], d_len, stored == "auto", d_scan), buf, a.n)
+    _raise_on_status(a.d_status, "estimate_batch")
     return totals.tolist()
+
+
+def _encode_kinds(a: _Batch, stored, sparse, mode, stream):
+    """compress with `stored` or `sparse`: every packet a buffer of its own, and the packets go three ways, each in batch order -- the coded
+    ones to the encoder, the raw ones to the copy (hip.move_packets), the sparse ones into records (hip.sparse_pack).  The kinds are
+    _kinds' (from one estimate_batch launch -- _auto_base's, where that made one -- and, with sparse="auto", one hip.sparse_scan_batch
+    launch on the bytes that would be coded) or the caller's list of stored packets; _partition makes the one synchronisation.  Returns
+    Compressed's (stream, offsets, stored, raw, raw_offsets, sparse, sparse_offsets)."""
+    import torch
+    device, n, n_packets, d_status = a.device, a.n, a.n_packets, a.d_status
+    d_coded, d_bytes, d_fp = a.split.d_coded, a.split.d_bytes, a.split.d_fp
+    _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
+    d_scan = d_slen = d_sparse = d_sparse_offsets = None
+    if stored == "auto" or sparse == "auto":
+        d_est = a.d_est if a.d_est is not None else \
+            H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+        if sparse == "auto":
+            d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
+        d_flags, d_slen = _kinds(d_scan, d_est[:n_packets], d_pkt_len, stored == "auto")
+    else:
+        d_flags = torch.tensor(stored, dtype=torch.int64).to(device)
+    d_len16 = (d_pkt_len + 15) // 16 * 16
+    n_stored, raw_bytes, coded, kept, n_sparse, sparse_bytes, packed = _partition(d_flags, d_len16, d_slen)
+    n_coded = n_packets - n_stored - n_sparse
+    d_stream, d_offsets = torch.empty(0, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int64, device=device)
+    if n_coded:
+        d_slots = H.encode_batch(d_pkt_ptr[coded], d_pkt_len[coded], _unit_first_packet(n_coded, device), n_coded, n_coded, stream=stream,
+                                 d_status=d_status, mode=mode, device=device)
+        d_stream, d_offsets = H.compact(d_slots, n_coded, stream=stream)
+    d_raw = torch.zeros(raw_bytes, dtype=torch.uint8, device=device)           # (zeros: the pads behind partial packets)
+    d_raw_offsets = _offsets(d_len16[kept])
+    if n_stored:
+        H.move_packets(d_pkt_ptr[kept], d_raw.data_ptr() + d_raw_offsets[:n_stored], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
+    if sparse == "auto":
+        d_sparse = torch.empty(sparse_bytes, dtype=torch.uint8, device=device)         # (sparse_pack writes every byte, the pads too)
+        d_sparse_offsets = _offsets(d_slen[packed])
+        if n_sparse:
+            H.sparse_pack(d_pkt_ptr[packed], d_pkt_len[packed], d_scan[:n_packets][packed], d_sparse.data_ptr() + d_sparse_offsets[:n_sparse],
+                          n_sparse, stream=stream, d_status=d_status)
+    return d_stream, d_offsets, d_flags.to(torch.uint8), d_raw, d_raw_offsets, d_sparse, d_sparse_offsets
+
+
+def _decode_kinds(c: Compressed, d_ptrs, d_sizes, d_fp, stream, d_status):
+    """_encode_kinds' mirror in decompress: every packet a buffer of its own towards the outputs (its room: the packet's own bytes) -- the
+    coded ones are decoded, the raw ones copied, the sparse ones rebuilt from their records (hip.sparse_unpack)."""
+    device = c.stream.device
+    _buf, d_pkt_ptr, d_pkt_len = _packets(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets)
+    n_coded = c.offsets.numel() - 1
+    n_sparse = c.sparse_offsets.numel() - 1 if c.sparse_offsets is not None else 0
+    n_stored = c.n_packets - n_coded - n_sparse
+    coded, kept, packed = _by_kind(c.stored, n_coded, n_stored)
+    if n_coded:
+        H.decode_stream_batch(c.stream, c.offsets, _unit_first_packet(n_coded, device), n_coded, n_coded, d_pkt_ptr[coded], d_pkt_len[coded],
+                              stream=stream, d_status=d_status)
+    if n_stored:
+        H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
+    if n_sparse:
+        H.sparse_unpack(c.sparse.data_ptr() + c.sparse_offsets[:n_sparse], c.sparse_offsets[1:] - c.sparse_offsets[:n_sparse], d_pkt_ptr[packed],
+                        d_pkt_len[packed], n_sparse, stream=stream, d_status=d_status)
 
 
 def compress(tensors, mode=None, stream=None, checksum=False, planes=None, stored=None, delta=None, base=None, base_auto=False,
              sparse=None) -> Compressed:
     """Encode every tensor of `tensors` (contiguous CUDA tensors on one device, each taken as its bytes) in one launch and
-    compact the result.  `mode`: "auto" | "throughput" | "latency" (as hip.encode).  `checksum`: also compute the CRC-32 of
-    every packet (Compressed.crc32; one more launch on the same stream).  `planes`: None | "auto" | a width | one width per
-    tensor (plane_widths) | "survey" (survey_widths: the widths are chosen by a survey of the bytes, one launch and one
-    synchronisation in front, and recorded in Compressed.planes): split each tensor's bytes into byte planes of that element
-    width before coding (one more launch, into a temporary buffer that is freed with the slots; widths of 1 are coded as they are).  The widths the kernels take
-    are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).  `stored`: None | "auto" | one bool per batch
-    packet: keep packets raw instead of coding them -- "auto": those whose estimate (hip.estimate_batch, on the split bytes) is
-    not smaller than the packet; a sequence: those it names (a wrong length raises before any launch).  `delta`: None | True |
-    False | one bool per tensor | "auto" | "survey": replace the elements of the flagged tensors, at the width `planes` gives (planes=None:
-    1), by their differences inside every group, in the launch that splits (hip.split_delta_batch); "auto" flags the tensors
-    for which two more split and two more estimate launches predict a gain (_auto_delta); "survey" flags the same tensors from
-    two survey launches over the original bytes and one synchronisation, without a split or a temporary (_survey_delta_flags), and
-    with planes="survey" chooses width and filter together (survey_choice).  None takes exactly the path taken
-    without the keyword.  The CRCs stay those of the original bytes; `stored` sees the filtered, split bytes.  `base`: None | a
-    list with, per tensor, None or a contiguous CUDA tensor of exactly the tensor's byte count on its device, 16-byte aligned
-    (base_pointers; anything else raises before any launch, and so does a base together with `delta`): XOR the tensor with it, at
-    the width `planes` gives (planes=None: 1), in the launch that splits (hip.split_xor_batch, into the same temporary buffer:
-    inputs and bases are never modified).  planes="survey" surveys the original bytes.  `base_auto`: keep only the bases for
-    which splitting and estimating the batch both ways predicts a gain (_auto_base: one split and one estimate launch more than
-    fixed bases with stored="auto" take, one synchronisation, both split copies kept and none made a third time);
-    Compressed.based says which.  base_auto="survey" keeps the same bases from one hip.survey_planes_batch and one
-    hip.survey_xor_batch launch over the original bytes and one synchronisation, and then splits once: one temporary of the batch's
-    size instead of two (_survey_base_keep; a width the surveys do not have, any but 1, 2, 4 and 8, raises before any launch, as with
-    delta="survey", where base_auto=True gets BAD_BATCH from the split); with planes="survey" it chooses width and base together, on the bytes that would be
-    coded (survey_base_choice), and records both in Compressed.planes and Compressed.based.  base=None takes exactly the path taken without the keyword.  `sparse`: None | "auto" (with
-    stored None or "auto"): keep the packets that are one byte value almost everywhere as that byte and a list of exceptions --
-    one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one hip.sparse_scan_batch launch
-    on the bytes that would be coded, hip.sparse_rule on the device, and the packets go three ways: coded, raw (hip.move_packets)
-    and sparse (hip.sparse_pack, into Compressed.sparse).  sparse=None takes exactly the path taken without the keyword.
-    planes="mixed": width and filter per supergroup of 65536 bytes (survey_mixed, then one hip.split_mixed_batch launch into the
-    usual temporary; Compressed.modes): planes alone at the four widths, with delta="mixed" the delta filter too, with `base` the
-    base too -- here a base and the delta filter go together, a supergroup takes one of them or neither.  Any other `delta`,
-    delta="mixed" without planes="mixed", and `base_auto` raise before any launch.  `stored`, `sparse`, `checksum` and `mode` see the
-    split bytes as ever.  See Compressed."""
-    import torch
+    compact the result.  See Compressed.
+
+    `mode`: "auto" | "throughput" | "latency" (as hip.encode).
+
+    `checksum`: also compute the CRC-32 of every packet (Compressed.crc32; one more launch on the same stream).  The CRCs stay those of
+    the original bytes whatever filter is in front.
+
+    `planes`: None | "auto" | a width | one width per tensor (plane_widths) | "survey" | "mixed".  Split each tensor's bytes into byte
+    planes of that element width before coding (one more launch, into a temporary buffer that is freed with the slots; widths of 1 are
+    coded as they are).  The widths the kernels take are 1, 2, 4 and 8: any other raises from the device's status (BAD_BATCH).
+    "survey" (survey_widths): the widths are chosen by a survey of the original bytes, one launch and one synchronisation in front, and
+    recorded in Compressed.planes.
+    "mixed": width and filter per supergroup of 65536 bytes (survey_mixed, then one hip.split_mixed_batch launch into the usual
+    temporary; Compressed.modes): planes alone at the four widths, with delta="mixed" the delta filter too, with `base` the base too --
+    here a base and the delta filter go together, a supergroup takes one of them or neither.  Beside it any other `delta` and `base_auto`
+    raise before any launch, and so does delta="mixed" without it.
+
+    `stored`: None | "auto" | one bool per batch packet.  Keep packets raw instead of coding them -- "auto": those whose estimate
+    (hip.estimate_batch, on the filtered, split bytes) is not smaller than the packet; a sequence: those it names (a wrong length raises
+    before any launch).
+
+    `delta`: None | True | False | one bool per tensor | "auto" | "survey" (| "mixed", see `planes`).  Replace the elements of the flagged
+    tensors, at the width `planes` gives (planes=None: 1), by their differences inside every group, in the launch that splits
+    (hip.split_delta_batch).  "auto" flags the tensors for which two more split and two more estimate launches predict a gain
+    (_auto_delta).  "survey" flags the same tensors from two survey launches over the original bytes and one synchronisation, without a
+    split or a temporary (_survey_delta_flags), and with planes="survey" chooses width and filter together (survey_choice).  None takes
+    exactly the path taken without the keyword.
+
+    `base`: None | a list with, per tensor, None or a contiguous CUDA tensor of exactly the tensor's byte count on its device, 16-byte
+    aligned (base_pointers; anything else raises before any launch, and so does a base together with `delta`).  XOR the tensor with it,
+    at the width `planes` gives (planes=None: 1), in the launch that splits (hip.split_xor_batch, into the same temporary buffer: inputs
+    and bases are never modified).  planes="survey" surveys the original bytes.  None takes exactly the path taken without the keyword.
+
+    `base_auto`: False | True | "survey".  True keeps only the bases for which splitting and estimating the batch both ways predicts a
+    gain (_auto_base: one split and one estimate launch more than fixed bases with stored="auto" take, one synchronisation, both split
+    copies kept and none made a third time); Compressed.based says which.  "survey" keeps the same bases from one
+    hip.survey_planes_batch and one hip.survey_xor_batch launch over the original bytes and one synchronisation, and then splits once: one
+    temporary of the batch's size instead of two (_survey_base_keep; a width the surveys do not have, any but 1, 2, 4 and 8, raises before
+    any launch, as with delta="survey", where base_auto=True gets BAD_BATCH from the split); with planes="survey" it chooses width and
+    base together, on the bytes that would be coded (survey_base_choice), and records both in Compressed.planes and Compressed.based.
+
+    `sparse`: None | "auto" (with stored None or "auto").  Keep the packets that are one byte value almost everywhere as that byte and a
+    list of exceptions -- one estimate_batch launch (the one stored="auto" or base_auto made, where there is one) and one
+    hip.sparse_scan_batch launch on the bytes that would be coded, hip.sparse_rule on the device, and the packets go three ways: coded,
+    raw (hip.move_packets) and sparse (hip.sparse_pack, into Compressed.sparse).  None takes exactly the path taken without the keyword.
+
+    `stored`, `sparse`, `checksum` and `mode` see the split bytes as ever, under planes="mixed" too."""
     a = _arguments(list(tensors), planes, stored, delta, base, base_auto, stream, sparse)
-    device, n, n_packets = a.device, len(a.sizes), a.n_packets
-    stored = _stored_argument(stored, n_packets)                 # (a list of stored packets too: estimate takes none)
+    stored = _stored_argument(stored, a.n_packets)               # (a list of stored packets too: estimate takes none)
     sparse = _sparse_argument(sparse, stored)
     d_stored = d_raw = d_raw_offsets = d_sparse = d_sparse_offsets = None
     with _on(stream):
-        a = _prepare(a, base_auto, stream)
-        d_status, d_ptrs, d_bytes, d_fp, d_coded = a.d_status, a.split.d_ptrs, a.split.d_bytes, a.split.d_fp, a.split.d_coded
+        a = _prepare(a, stream)
+        s, n, n_packets = a.split, a.n, a.n_packets
         if stored is None and sparse is None:
-            d_slots = H.encode_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, mode=mode, device=device)
+            d_slots = H.encode_batch(s.d_coded, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=a.d_status, mode=mode, device=a.device)
             d_stream, d_offsets = H.compact(d_slots, n_packets, stream=stream)
         else:
-            # every packet a buffer of its own: the coded ones go to the encoder, the stored ones to the copy, both in batch order
-            _buf, d_pkt_ptr, d_pkt_len = _packets(d_coded, d_bytes, d_fp, n, n_packets)
-            d_slen = None
-            if stored == "auto" or sparse == "auto":
-                d_est = a.d_est if a.d_est is not None else \
-                    H.estimate_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
-            if sparse == "auto":
-                d_scan = H.sparse_scan_batch(d_coded, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device)
-                d_flags, d_slen = _kinds(d_scan, d_est[:n_packets], d_pkt_len, stored == "auto")
-            elif stored == "auto":
-                d_flags = (d_est[:n_packets] >= 4 + d_pkt_len).to(torch.int64)
-            else:
-                d_flags = torch.tensor(stored, dtype=torch.int64).to(device)
-            d_len16 = (d_pkt_len + 15) // 16 * 16
-            n_stored, raw_bytes, coded, kept, n_sparse, sparse_bytes, packed = _partition(d_flags, d_len16, d_slen)
-            n_coded = n_packets - n_stored - n_sparse
-            d_stream, d_offsets = torch.empty(0, dtype=torch.uint8, device=device), torch.zeros(1, dtype=torch.int64, device=device)
-            if n_coded:
-                d_slots = H.encode_batch(d_pkt_ptr[coded], d_pkt_len[coded], _unit_first_packet(n_coded, device), n_coded, n_coded, stream=stream,
-                                         d_status=d_status, mode=mode, device=device)
-                d_stream, d_offsets = H.compact(d_slots, n_coded, stream=stream)
-            d_raw = torch.zeros(raw_bytes, dtype=torch.uint8, device=device)           # (zeros: the pads behind partial packets)
-            d_raw_offsets = _offsets(d_len16[kept])
-            if n_stored:
-                H.move_packets(d_pkt_ptr[kept], d_raw.data_ptr() + d_raw_offsets[:n_stored], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
-            if sparse == "auto":
-                d_sparse = torch.empty(sparse_bytes, dtype=torch.uint8, device=device)         # (sparse_pack writes every byte, the pads too)
-                d_sparse_offsets = _offsets(d_slen[packed])
-                if n_sparse:
-                    H.sparse_pack(d_pkt_ptr[packed], d_pkt_len[packed], d_scan[:n_packets][packed], d_sparse.data_ptr() + d_sparse_offsets[:n_sparse],
-                                  n_sparse, stream=stream, d_status=d_status)
-            d_stored = d_flags.to(torch.uint8)
-        d_crc = H.crc32_batch(d_ptrs, d_bytes, d_fp, n, n_packets, stream=stream, d_status=d_status, device=device) if checksum else None
-        _raise_on_status(d_status, "encode_batch")
+            d_stream, d_offsets, d_stored, d_raw, d_raw_offsets, d_sparse, d_sparse_offsets = _encode_kinds(a, stored, sparse, mode, stream)
+        d_crc = H.crc32_batch(s.d_ptrs, s.d_bytes, s.d_fp, n, n_packets, stream=stream, d_status=a.d_status, device=a.device) if checksum else None
+        _raise_on_status(a.d_status, "encode_batch")
         # compact() wrote into a buffer of n_packets * 8704 bytes: keep only the compressed bytes (one copy), so that the
         # result takes what it compressed to, not ~1.06 x the input
         used = int(d_offsets[-1].item())
@@ -1257,6 +1303,33 @@ def _based(a: _Batch):
     if a.modes is not None:
         return [any(H.mode_parts(m)[2] for m in modes) for modes in a.modes]
     return [bool(q) for q in a.bases]
+
+
+def _decompress_bases(c: Compressed, ptrs, base, device):
+    """decompress's base pointers (0 for a buffer that needs none), or None for a batch compressed without bases; what is missing, of
+    another size, device or alignment, or overlaps a tensor of `out` (at `ptrs`) raises."""
+    if c.based is None or not any(c.based):
+        return None
+    # the outputs as intervals by their start, with the furthest end so far: a base overlaps one iff that end lies behind its start
+    spans = sorted((p, p + need, b) for b, (p, need) in enumerate(zip(ptrs, c.sizes)) if need)
+    starts, reach = [s for s, _e, _b in spans], []
+    for _s, e, b in spans:
+        reach.append(max(reach[-1], (e, b)) if reach else (e, b))
+    if not isinstance(base, (list, tuple)) or len(base) != c.n_buffers:
+        raise GpuarError(f"this batch was compressed against bases: decompress needs base=[...] with {c.n_buffers} entries")
+    bases = []
+    for b, (t, need) in enumerate(zip(base, c.sizes)):
+        if not c.based[b] or need == 0:
+            bases.append(0)
+            continue
+        if t is None:
+            raise GpuarError(f"buffer {b} was compressed against a base: base[{b}] is missing")
+        at = _base_pointer(t, b, device, "the batch", lambda: need, f"buffer {b} has", "buffer")
+        before = bisect.bisect_left(starts, at + need)                     # the outputs that start in front of the base's end
+        if before and reach[before - 1][0] > at:
+            raise GpuarError(f"base[{b}] overlaps out[{reach[before - 1][1]}]: the merge runs in place in `out` while the bases are read")
+        bases.append(at)
+    return bases
 
 
 def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
@@ -1282,60 +1355,21 @@ def decompress(c: Compressed, out=None, stream=None, verify=True, base=None):
     for b, (have, need) in enumerate(zip(room, c.sizes)):
         if have < need:
             raise GpuarError(f"out[{b}] holds {have} bytes, buffer {b} needs {need}")
-    bases = None
-    if c.based is not None and any(c.based):
-        # the outputs as intervals by their start, with the furthest end so far: a base overlaps one iff that end lies behind its start
-        spans = sorted((p, p + need, b) for b, (p, need) in enumerate(zip(ptrs, c.sizes)) if need)
-        starts, reach = [s for s, _e, _b in spans], []
-        for _s, e, b in spans:
-            reach.append(max(reach[-1], (e, b)) if reach else (e, b))
-        if not isinstance(base, (list, tuple)) or len(base) != c.n_buffers:
-            raise GpuarError(f"this batch was compressed against bases: decompress needs base=[...] with {c.n_buffers} entries")
-        bases = []
-        for b, (t, need) in enumerate(zip(base, c.sizes)):
-            if not c.based[b] or need == 0:
-                bases.append(0)
-                continue
-            if t is None:
-                raise GpuarError(f"buffer {b} was compressed against a base: base[{b}] is missing")
-            at = _base_pointer(t, b, device, "the batch", lambda: need, f"buffer {b} has", "buffer")
-            before = bisect.bisect_left(starts, at + need)                     # the outputs that start in front of the base's end
-            if before and reach[before - 1][0] > at:
-                raise GpuarError(f"base[{b}] overlaps out[{reach[before - 1][1]}]: the merge runs in place in `out` while the bases are read")
-            bases.append(at)
+    # the batch towards the outputs, with the plan it was compressed by
+    a = _Batch(device, ptrs, c.sizes, c.first_packet, c.n_packets, c.planes, c.delta, _decompress_bases(c, ptrs, base, device), c.modes)
     with _on(stream):
         (d_ptrs, d_room, d_fp, d_sizes), _keep = _upload(device, ptrs, room, c.first_packet, c.sizes)
         d_status = torch.zeros(1, dtype=torch.int32, device=device)
         if c.stored is None:
             H.decode_stream_batch(c.stream, c.offsets, d_fp, c.n_buffers, c.n_packets, d_ptrs, d_room, stream=stream, d_status=d_status)
         elif c.n_packets:
-            # every packet a buffer of its own towards the outputs (its room: the packet's own bytes): the coded ones are decoded,
-            # the stored ones copied
-            _buf, d_pkt_ptr, d_pkt_len = _packets(d_ptrs, d_sizes, d_fp, c.n_buffers, c.n_packets)
-            n_coded = c.offsets.numel() - 1
-            n_sparse = c.sparse_offsets.numel() - 1 if c.sparse_offsets is not None else 0
-            n_stored = c.n_packets - n_coded - n_sparse
-            coded, kept, packed = _by_kind(c.stored, n_coded, n_stored)
-            if n_coded:
-                H.decode_stream_batch(c.stream, c.offsets, _unit_first_packet(n_coded, device), n_coded, n_coded, d_pkt_ptr[coded], d_pkt_len[coded],
-                                      stream=stream, d_status=d_status)
-            if n_stored:
-                H.move_packets(c.raw.data_ptr() + c.raw_offsets[:n_stored], d_pkt_ptr[kept], d_pkt_len[kept], n_stored, stream=stream, d_status=d_status)
-            if n_sparse:
-                H.sparse_unpack(c.sparse.data_ptr() + c.sparse_offsets[:n_sparse], c.sparse_offsets[1:] - c.sparse_offsets[:n_sparse], d_pkt_ptr[packed],
-                                d_pkt_len[packed], n_sparse, stream=stream, d_status=d_status)
+            _decode_kinds(c, d_ptrs, d_sizes, d_fp, stream, d_status)
         _raise_on_status(d_status, "decode_stream_batch")      # (.item() waits for this stream)
-        found = _filter(c.planes, c.delta, bases) if c.n_packets and c.modes is None else None
-        if c.modes is not None and c.n_packets:
-            first_mode, _n_modes = H.batch_mode_count(c.sizes)
-            (d_fm, d_bases), _keep2 = _upload(device, first_mode, bases or [0] * c.n_buffers)
-            H.merge_mixed_batch(d_ptrs, d_sizes, d_fp, d_fm, _modes_tensor(c.modes, device), d_bases, c.n_buffers, c.n_packets, d_ptrs, stream=stream,
-                                d_status=d_status)
-            _raise_on_status(d_status, "merge_mixed_batch")
+        found = _filter(a) if c.n_packets else None
         if found is not None:
-            _split_name, merge, extra = found
-            (d_elem, *d_extra), _keep2 = _upload(device, c.planes, *extra)
-            getattr(H, merge)(d_ptrs, d_sizes, d_fp, d_elem, *d_extra, c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
+            _split_name, merge, rows, d_beside = found
+            d_rows, _keep2 = _upload(device, *rows)
+            getattr(H, merge)(d_ptrs, d_sizes, d_fp, *_filter_arguments(d_rows, d_beside), c.n_buffers, c.n_packets, d_ptrs, stream=stream, d_status=d_status)
             _raise_on_status(d_status, merge)
         if c.crc32 is not None and verify and c.n_packets:
             d_first_bad = torch.full((1,), -1, dtype=torch.int64, device=device)

@@ -2,10 +2,11 @@
 combinations of which 40 are refused by contract.  Every valid combination goes through model_compress and back through
 model_decompress; the conditions that keep tests/test_gpu_batch_matrix.py from being vacuous -- every kind of packet, every choice
 taken both ways, an empty kind -- are asserted on the model alone; the model's restatements of choose_planes and choose_filter are
-pinned against the C functions; and the parts of batch.py that are device-free torch (_kinds, _partition, and the decisions of
-_auto_delta and _auto_base with the launches replaced by the model's estimates) run on CPU tensors against the model.
+pinned against the C functions; and the parts of batch.py that are device-free torch (_kinds, _partition, the counting rule
+_counts_as with the per-buffer sum _per_buffer, and the decisions of _auto_delta and _auto_base with the launches replaced by the
+model's estimates) run on CPU tensors against the model.
 
-Wall time of the module: 6 s on one core (21 tests), 3 s of it importing torch in the first test that needs it.  The 400
+Wall time of the module: 7 s on one core (22 tests), 3 s of it importing torch in the first test that needs it.  The 400
 model_compress / model_decompress pairs (with and without CRCs) take under 2 s: 124 layouts are split, estimated, scanned and encoded
 once each for all of them.
 
@@ -441,11 +442,11 @@ class _FakeLaunches:
     def __init__(self, sizes, first_packet, plain, other):
         self.sizes, self.first_packet, self.est = sizes, first_packet, (plain, other)
 
-    def split(self, device, ptrs, sizes, first_packet, n_packets, widths, stream, d_status, flags=None, bases=None):
-        other = int(bool((flags is not None and any(flags)) or (bases is not None and any(bases))))
-        d_coded = _i64([2 * b + other for b in range(len(sizes))])               # (which copy: the estimate below looks at it)
+    def split(self, a, stream):
+        other = int(bool((a.flags is not None and any(a.flags)) or (a.bases is not None and any(a.bases))))
+        d_coded = _i64([2 * b + other for b in range(len(a.sizes))])             # (which copy: the estimate below looks at it)
         from gpuar_amd import batch
-        return batch._Split(_i64(ptrs), _i64(sizes), _i64(first_packet), d_coded, None, None)
+        return batch._Split(_i64(a.ptrs), _i64(a.sizes), _i64(a.first_packet), d_coded, None)
 
     def estimate_batch(self, d_coded, d_bytes, d_fp, n, n_packets, stream=None, d_status=None, device=None):
         import torch
@@ -482,14 +483,56 @@ def test_auto_delta_and_auto_base_decide_by_the_models_rule_at_ties(H, M, monkey
     assert {-1, 0, 1} <= margins and True in want and False in want
     status = torch.zeros(1, dtype=torch.int32)
     ptrs = [0x10000 * (b + 1) if size else 0 for b, size in enumerate(m.sizes)]
-    got = batch._auto_delta(torch.device("cpu"), ptrs, m.sizes, m.first_packet, m.first_packet[-1], m.planes, None, status)
+    a = batch._Batch(torch.device("cpu"), ptrs, m.sizes, m.first_packet, m.first_packet[-1], widths=m.planes, d_status=status)
+    got = batch._auto_delta(a, None)
     assert got == want
     bases = [0x9000000 + 0x10000 * b if size else 0 for b, size in enumerate(m.sizes)]
     bases[1] = 0                                               # a buffer without a base keeps none, whatever the totals say
-    keep, chosen, d_est = batch._auto_base(torch.device("cpu"), ptrs, m.sizes, m.first_packet, m.first_packet[-1], m.planes, bases, None, status)
+    keep, chosen, d_est = batch._auto_base(a._replace(bases=bases), None)
     want_keep = [bool(q) and w for q, w in zip(bases, want)]
     assert keep == want_keep and want[1] and not keep[1]
     assert d_est.tolist() == [e for b in range(n) for e in (other[b] if want_keep[b] else plain[b])]
     assert chosen[3].tolist() == [2 * b + int(k) for b, k in enumerate(want_keep)]           # every buffer is coded from the copy of its choice
-    assert batch._auto_delta(torch.device("cpu"), [], [], [0], 0, [], None, status) == []
-    assert batch._auto_base(torch.device("cpu"), ptrs, m.sizes, m.first_packet, m.first_packet[-1], m.planes, [0] * n, None, status) == ([False] * n, None, None)
+    assert chosen.d_coded is chosen[3]
+    assert batch._auto_delta(batch._Batch(torch.device("cpu"), [], [], [0], 0, widths=[], d_status=status), None) == []
+    assert batch._auto_base(a._replace(bases=[0] * n), None) == ([False] * n, None, None)
+
+
+def test_the_counting_rule_and_the_per_buffer_sum_give_model_estimate(H, M):
+    """batch._counts_as on the model's per-packet estimates, lengths and scan words, summed by batch._per_buffer: model_estimate for every
+    valid combination of the matrix that estimate takes (the 160 without a list of stored packets) and for the parts of the batch, where
+    each branch of the rule is taken and not taken; and the per-buffer sum, on one row and on four rows, against a loop."""
+    torch = pytest.importorskip("torch")
+    from gpuar_amd import batch
+    cases = [(c, None) for c in valid(M) if c[2] != "list"] + [(c, part) for part in M.SUBSETS for c in M.SUBSET_COMBOS]
+    kinds_seen = {part: set() for part in list(M.SUBSETS) + [None]}
+    for c, part in cases:
+        m = M.model(c, False, part)
+        which = range(len(M.ARRAYS)) if part is None else M.SUBSETS[part]
+        want = M.model_estimate([M.ARRAYS[b] for b in which], [M.DTYPES[b] for b in which], **M.keywords(c, part))
+        est = _i64([e for lay in m.layouts for e in lay.est])
+        lens = _i64([v for lay in m.layouts for v in lay.lens])
+        scan = _i32([s for lay in m.layouts for s in lay.scan]) if c[3] == "auto" else None
+        buf = _i64([b for b, lay in enumerate(m.layouts) for _ in lay.lens])
+        counted = batch._counts_as(est, lens, c[2] == "auto", scan)
+        assert counted.shape == est.shape and counted.dtype == est.dtype
+        assert batch._per_buffer(counted, buf, len(m.layouts)).tolist() == want, (c, part)
+        loop = [0] * len(m.layouts)
+        for b, v in zip(buf.tolist(), counted.tolist()):
+            loop[b] += v
+        assert batch._per_buffer(counted, buf, len(m.layouts)).tolist() == loop, (c, part)
+        # the surveys' shape: the same packets four times over, one row unchanged and three moved -- every row sums on its own
+        rows = torch.stack([counted, counted + 1, counted * 2, torch.zeros_like(counted)])
+        assert batch._per_buffer(rows, buf, len(m.layouts)).tolist() == [loop, [t + len(lay.lens) for t, lay in zip(loop, m.layouts)],
+                                                                         [2 * t for t in loop], [0] * len(loop)], (c, part)
+        four = batch._counts_as(est.expand(4, -1), lens, c[2] == "auto", scan.expand(4, -1) if scan is not None else None)
+        assert four.tolist() == [counted.tolist()] * 4, (c, part)
+        if m.stored is not None:
+            kinds_seen[part] |= set(m.stored)
+            moved = [v != e for v, e in zip(counted.tolist(), est.tolist())]
+            assert all(k != S.CODED or not mv for k, mv in zip(m.stored, moved)), (c, part)    # a coded packet counts as its estimate
+    assert len(cases) == 160 + 36
+    # every branch both ways: over the whole batch every kind, and a part without each of them
+    assert kinds_seen[None] == {S.CODED, S.RAW, S.SPARSE}
+    assert S.SPARSE not in kinds_seen["rough"] and S.RAW not in kinds_seen["calm"] and kinds_seen["rough"] >= {S.CODED, S.RAW}
+    assert any(set(M.model(c, False, "still").stored or [S.CODED]) == {S.SPARSE} for c in M.SUBSET_COMBOS)

@@ -23,12 +23,22 @@ launch, one XOR-survey launch, one synchronising read and ONE split; beside plan
 sparse="auto" both of them the XOR survey, the plain side with base pointers of 0), the same read and one split --, and behind
 the split to the trace of base_auto=True behind its second split and estimate, launch for launch by name.
 
+Two things came later still and are held byte for byte by a second file, tests/golden/batch_call_trace_later.json, written by
+    python tests/test_gpu_batch_trace.py --write-later
+against the batch.py of the commit in front of the one that made batch.py one batch description, one filter plan and one counting
+rule, and never rewritten from later code either: the full traces of the 25 base_survey combinations (beside check_base_survey, which
+stays), and planes="mixed", which is on no axis of the matrix -- the 20 combinations of MIXED on the same batch, with checksum, stream
+and mode from mixed_rotation: per combination the traces of compress, estimate and decompress(verify=True), what estimate returned,
+Compressed.modes, based and kinds_rule, and a sha256 of every device field of the Compressed (read outside the recording).  The
+recording process also checks that decompress gives the input bytes back.
+
 The recording runs in a process of its own (this module as a script, --record FILE) and the test compares what it wrote: a process
-that has wrapped torch.Tensor's methods, uploaded the batch a second time and driven 610 calls over one more stream leaves the
+that has wrapped torch.Tensor's methods, uploaded the batch a second time and driven 665 calls over one more stream leaves the
 streams of the pool in another state than it found them, and the stream-order tests of tests/test_gpu_packet_forms_concurrency.py,
 which run later in the same pytest process, then find their control launch serialised behind their producer.  The child starts,
 imports torch and records in about 5 s."""
 import contextlib
+import hashlib
 import inspect
 import json
 import os
@@ -41,7 +51,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from test_gpu_batch_matrix import ROTATION, VALID, Uploaded  # noqa: E402
+import batch_model as M  # noqa: E402
+from test_gpu_batch_matrix import MODES, ROTATION, VALID, Uploaded, on_host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -50,6 +61,9 @@ torch = pytest.importorskip("torch")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "batch_call_trace.json")
 WRITTEN_FROM = ("the batch.py of the commit in front of 'batch.py: one split, one upload, one partition, one prepare step' "
                 "(python tests/test_gpu_batch_trace.py --write); never from later code")
+LATER = os.path.join(ROOT, "tests", "golden", "batch_call_trace_later.json")
+WRITTEN_FROM_LATER = ("the batch.py of the commit in front of 'batch.py: one batch description, one filter plan, one counting rule' "
+                      "(python tests/test_gpu_batch_trace.py --write-later); never from later code")
 COUNTS = ("n_buffers", "n_packets", "n_regions")
 RECORDED = [c for c in VALID if c[1] != "base_survey"]         # the combinations of the golden file
 # base_auto="survey" by batch.py's docstring: (planes="survey", sparse packets counted) -> the launches and the one synchronising
@@ -60,6 +74,16 @@ SURVEY_PREFIX = {
     (True, True): ["survey_xor_batch", "survey_xor_batch", ".tolist", "split_xor_batch"],
 }
 READS = ("item", "tolist", "cpu")
+# planes="mixed": (delta, base, stored, sparse) by name -- delta None or "mixed", no base or the batch's bases, the five valid pairs
+MIXED = [(d, b, s, q) for d in ("none", "mixed") for b in ("none", "base") for s in M.STORED_AXIS for q in M.SPARSE_AXIS
+         if not (s == "list" and q == "auto")]
+DEVICE_FIELDS = ("stream", "offsets", "crc32", "stored", "raw", "raw_offsets", "sparse", "sparse_offsets")
+
+
+def mixed_rotation(combo):
+    """(checksum, side stream, mode) for a mixed combination, from its position i among the 20"""
+    i = MIXED.index(combo)
+    return bool(i % 2), bool((i // 2 + i // 5) % 2), MODES[(i + i // 3) % 3]
 
 
 class Recorder:
@@ -139,8 +163,41 @@ def traces_of(batch, rec, T, combo):
     return out
 
 
+def mixed_record(batch, rec, T, combo):
+    """what one mixed combination does and gives: its traces, and -- read outside the recording -- its results"""
+    checksum, side, mode = mixed_rotation(combo)
+    stream = T.side if side else None
+    d, b, s, q = combo
+    kw = dict(planes="mixed", delta=None if d == "none" else "mixed", stored=M.STORED_AXIS[s], sparse=M.SPARSE_AXIS[q])
+    if b == "base":
+        kw["base"] = T.bases
+    out = {"traces": {}}
+    with rec.during() as trace:
+        c = batch.compress(T.tensors, mode=mode, stream=stream, checksum=checksum, **kw)
+    out["traces"]["compress"] = trace
+    if stream is not None:
+        stream.synchronize()
+    if s != "list":
+        with rec.during() as trace:
+            estimate = batch.estimate(T.tensors, **kw)
+        out["traces"]["estimate"], out["estimate"] = trace, estimate
+    with rec.during() as trace:
+        back = batch.decompress(c, stream=stream, verify=True, base=kw.get("base"))
+    out["traces"]["decompress"] = trace
+    if stream is not None:
+        stream.synchronize()
+    assert [on_host(x) for x in back] == [on_host(t) for t in T.tensors], combo
+    out["modes"] = [m.hex() for m in c.modes]
+    out["based"], out["kinds_rule"] = c.based, list(c.kinds_rule) if c.kinds_rule is not None else None
+    for name in DEVICE_FIELDS:
+        field = getattr(c, name)
+        out[name] = None if field is None else hashlib.sha256(field.cpu().numpy().tobytes()).hexdigest()
+    return out
+
+
 def all_traces(monkeypatch):
-    """{"planes-filter-stored-sparse:call": trace} over the 200 combinations"""
+    """({"planes-filter-stored-sparse:call": trace} over the 200 combinations, {"delta-base-stored-sparse": mixed_record} over the 20
+    of MIXED)"""
     from gpuar_amd import batch
     batch.H.load()
     T = Uploaded()
@@ -149,9 +206,10 @@ def all_traces(monkeypatch):
     for combo in VALID:
         for call, trace in traces_of(batch, rec, T, combo).items():
             got["-".join(combo) + ":" + call] = trace
+    mixed = {"-".join(combo): mixed_record(batch, rec, T, combo) for combo in MIXED}
     T.unchanged()
     assert batch.H.status() == 0
-    return got
+    return got, mixed
 
 
 def grouped(got):
@@ -175,7 +233,7 @@ def test_every_combination_makes_the_recorded_launches_uploads_and_reads(tmp_pat
     child = subprocess.run([sys.executable, os.path.abspath(__file__), "--record", str(recorded)], capture_output=True, text=True, timeout=300)
     assert child.returncode == 0, (child.returncode, child.stdout[-2000:], child.stderr[-4000:])
     with open(recorded) as f:
-        got = json.load(f)
+        got, mixed = json.load(f)
     later = {key: trace for key, trace in got.items() if key.split("-")[1] == "base_survey"}
     got = {key: trace for key, trace in got.items() if key not in later}
     assert sorted(got) == sorted(want)
@@ -187,6 +245,36 @@ def test_every_combination_makes_the_recorded_launches_uploads_and_reads(tmp_pat
     assert {".item", ".tolist", ".pin_memory", "encode_batch", "decode_stream_batch", "move_bytes", "estimate_batch"} <= events
     assert sum(key.endswith(":estimate") for key in got) == 140 and sum(key.endswith(":from_gip") for key in got) == 120
     check_base_survey(later, got)
+    check_later(later, mixed)
+
+
+def check_later(later, mixed):
+    """the base_survey traces and everything recorded of the mixed combinations against the second golden file, exactly"""
+    with open(LATER) as f:
+        golden = json.load(f)
+    assert list(golden)[0] == "written from" and golden["written from"] == WRITTEN_FROM_LATER
+    want = {key: entry["trace"].split(";") if entry["trace"] else [] for entry in golden["base_survey"] for key in entry["calls"]}
+    assert len(want) == sum(len(entry["calls"]) for entry in golden["base_survey"]) == 25 + 20 + 25 + 10
+    assert sorted(later) == sorted(want)
+    for key in want:
+        assert later[key] == want[key], key
+    assert len(MIXED) == 20 and sorted(mixed) == sorted(golden["mixed"]) == sorted("-".join(c) for c in MIXED)
+    turns = [mixed_rotation(c) for c in MIXED]
+    assert {t[0] for t in turns} == {False, True} and {t[1] for t in turns} == {False, True} and {t[2] for t in turns} == set(MODES)
+    for key, record in golden["mixed"].items():
+        assert sorted(mixed[key]) == sorted(record), key
+        for name in record:
+            assert mixed[key][name] == record[name], (key, name)
+        assert sorted(record["traces"]) == (["compress", "decompress"] if "-list-" in key else ["compress", "decompress", "estimate"]), key
+        assert ("estimate" in record) == ("estimate" in record["traces"]), key
+        assert [len(m) for m in record["modes"]] == [2 * ((size + 65535) // 65536) for size in M.SIZES], key    # a mode per supergroup
+    # not vacuous: the mixed split and merge are launched once each per compress and decompress, and some supergroup takes each offer
+    for key, record in golden["mixed"].items():
+        assert sum(e.startswith("split_mixed_batch ") for e in record["traces"]["compress"]) == 1, key
+        assert sum(e.startswith("merge_mixed_batch ") for e in record["traces"]["decompress"]) == 1, key
+        assert (record["based"] is None) == ("-base-" not in "-" + key), key
+    assert any(record["based"] is not None and any(record["based"]) for record in golden["mixed"].values())
+    assert len({tuple(record["modes"]) for record in golden["mixed"].values()}) > 1
 
 
 def names_of(trace):
@@ -221,15 +309,22 @@ def check_base_survey(later, got):
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] != ["--write"] and not (len(sys.argv) == 3 and sys.argv[1] == "--record"):
-        sys.exit("usage: python tests/test_gpu_batch_trace.py --record FILE   (what the test compares), or --write   (the golden file, "
-                 "against the commit it records; see the docstring)")
+    if sys.argv[1:] not in (["--write"], ["--write-later"]) and not (len(sys.argv) == 3 and sys.argv[1] == "--record"):
+        sys.exit("usage: python tests/test_gpu_batch_trace.py --record FILE   (what the test compares), or --write / --write-later   (a "
+                 "golden file, against the commit it records; see the docstring)")
     with pytest.MonkeyPatch.context() as patch:
-        traces = all_traces(patch)
+        traces, mixed = all_traces(patch)
     if sys.argv[1] == "--record":
         with open(sys.argv[2], "w") as f:
-            json.dump(traces, f)
+            json.dump([traces, mixed], f)
+    elif sys.argv[1] == "--write-later":
+        later = {key: trace for key, trace in traces.items() if key.split("-")[1] == "base_survey"}
+        with open(LATER, "w") as f:
+            json.dump({"written from": WRITTEN_FROM_LATER, "base_survey": grouped(later), "mixed": mixed}, f, separators=(",", ":"))
+            f.write("\n")
+        print(f"{LATER}: {len(later)} base_survey calls, {len(mixed)} mixed combinations, {os.path.getsize(LATER)} bytes")
     else:
+        traces = {key: trace for key, trace in traces.items() if key.split("-")[1] != "base_survey"}
         with open(GOLDEN, "w") as f:
             json.dump({"written from": WRITTEN_FROM, "traces": grouped(traces)}, f, separators=(",", ":"))
             f.write("\n")
