@@ -32,6 +32,22 @@ class StopWatch {
     double total_ms = 0;
 };
 
+// What the packets of one job go through between the file's bytes and the coder, whichever way the job runs and on whichever
+// path: built from the compressor's options for a compress job (Compressor::plan) and from the file's trailer for a decompress job
+// (PacketPlan::of), and nowhere else.
+struct PacketPlan {
+    uint32_t elem = 1;       // the element width, 1, 2, 4 or 8: the packets hold byte planes of elements this wide (../planes.h)
+    bool delta = false;      // ... of the elements' differences (../delta.h)
+    bool based = false;      // ... of the bytes XORed with a base (../xorbase.h)
+    bool crcs = false;       // the CRC-32 of every packet's original bytes is written, or verified
+    bool stored = false, sparse = false;      // compress: a packet may be kept raw, or sparse (../kinds.h)
+    bool kinds = false;      // the file carries a kind per packet
+    // whether what is coded differs from what is read or written: XOR, else delta, else planes, else nothing
+    bool transforms() const { return elem > 1 || delta || based; }
+    // (the fields in their order)
+    static PacketPlan of(const Trailer &t) { return {t.elem_bytes, t.filtering(), t.based(), t.verify(), false, false, t.mixed()}; }
+};
+
 class Compressor {
   protected:
     std::string openFileName;
@@ -109,12 +125,11 @@ class Compressor {
     }
     // compress: whether the options ask for a trailer, and that trailer appended at the current position of the output
     bool based() const { return !baseFileName.empty(); }
-    bool mixed() const { return stored || sparse; }
-    bool wantsTrailer() const { return writeIndex || writeChecksum || planes > 1 || delta || based() || mixed(); }
-    // `kinds`: of every packet, read only where mixed()
-    void saveTrailer(const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs, const std::vector<uint8_t> &kinds) {
-        if (wantsTrailer())
-            Trailer::save(saveFile, clens, static_cast<uint32_t>(planes), writeChecksum ? &crcs : nullptr, delta, based(), mixed() ? &kinds : nullptr);
+    PacketPlan plan() const { return {static_cast<uint32_t>(planes), delta, based(), writeChecksum, stored, sparse, stored || sparse}; }
+    bool wantsTrailer() const { return writeIndex || plan().crcs || plan().transforms() || plan().kinds; }
+    // `crcs`, `kinds`: of every packet, read only where the plan has them
+    void saveTrailer(const PacketPlan &plan, const std::vector<uint16_t> &clens, const std::vector<uint32_t> &crcs, const std::vector<uint8_t> &kinds) {
+        if (wantsTrailer()) Trailer::save(saveFile, clens, plan.elem, plan.crcs ? &crcs : nullptr, plan.delta, plan.based, plan.kinds ? &kinds : nullptr);
     }
     // Opens the base file and checks that it holds exactly `expect` bytes (those of `what`); with the delta filter on it throws:
     // that combination is not built.  closeFiles() closes it.

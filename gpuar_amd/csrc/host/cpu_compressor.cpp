@@ -88,6 +88,22 @@ void for_each_packet(size_t n, unsigned threads, F &&f) {
     if (failure) std::rethrow_exception(failure);
 }
 
+// What a plan does to `n` bytes in front of the coder: XOR with `base`, else delta, else planes, else nothing.  Returns where the
+// bytes to code are: `out` when the plan transforms, else `in`.
+const uint8_t *split_host(const PacketPlan &plan, const uint8_t *in, const uint8_t *base, size_t n, uint8_t *out) {
+    if (plan.based) gpuar::split_xor_host(in, base, n, plan.elem, out);
+    else if (plan.delta) gpuar::split_delta_host(in, n, plan.elem, out);
+    else if (plan.elem > 1) gpuar::planes_host<false>(in, n, plan.elem, out);
+    return plan.transforms() ? out : in;
+}
+
+// ... and undoes behind the decoder: decoded[0..n) -> out[0..n); only for a plan that transforms
+void merge_host(const PacketPlan &plan, const uint8_t *decoded, const uint8_t *base, size_t n, uint8_t *out) {
+    if (plan.based) gpuar::merge_xor_host(decoded, base, n, plan.elem, out);
+    else if (plan.delta) gpuar::merge_delta_host(decoded, n, plan.elem, out);
+    else gpuar::planes_host<true>(decoded, n, plan.elem, out);
+}
+
 }  // namespace
 
 CPUCompressor::CPUCompressor() {}
@@ -112,8 +128,8 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     static_assert(kBatchPackets % 8 == 0, "a batch starts on a group boundary for every element width");
     // --delta: the same with the elements' differences inside every group in front of the split (at a width of 1 too)
     // --base: the same with the XOR against the base's bytes at the same file offsets in front of the split (at a width of 1 too)
-    const bool splitting = planes > 1 || delta || based();
-    std::vector<uint8_t> split(splitting ? in.size() : 0), base(based() ? in.size() : 0);
+    const PacketPlan plan = this->plan();
+    std::vector<uint8_t> split(plan.transforms() ? in.size() : 0), base(plan.based ? in.size() : 0);
     uint64_t file_at = 0;
     std::vector<uint32_t> clen(kBatchPackets), crc(kBatchPackets);
     std::vector<uint16_t> all_clens;                   // for the optional index trailer
@@ -121,32 +137,29 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
     std::vector<uint8_t> kind(kBatchPackets), all_kinds;      // --stored / --sparse: what every packet is kept as (version-6 trailer)
     const bool trailer = wantsTrailer();
     try {
-        if (based()) openBase(info.uncompressedFileSize, "the input");
+        if (plan.based) openBase(info.uncompressedFileSize, "the input");
         for (;;) {
             io_timer.start();
             const size_t got = std::fread(in.data(), 1, kBatchPackets * gpuar::kPacket, openFile);
-            if (got && based()) readBase(base.data(), got, file_at);
+            if (got && plan.based) readBase(base.data(), got, file_at);
             file_at += got;
             io_timer.stop();
             if (got == 0) break;
             const size_t np = (got + gpuar::kPacket - 1) / gpuar::kPacket;
             process_timer.start();     // model init + codec only, as src/cpu_compressor.cpp:157-161
-            if (based()) gpuar::split_xor_host(in.data(), base.data(), got, static_cast<uint32_t>(planes), split.data());
-            else if (delta) gpuar::split_delta_host(in.data(), got, static_cast<uint32_t>(planes), split.data());
-            else if (planes > 1) gpuar::planes_host<false>(in.data(), got, static_cast<uint32_t>(planes), split.data());
-            const uint8_t *coded = splitting ? split.data() : in.data();
+            const uint8_t *coded = split_host(plan, in.data(), base.data(), got, split.data());
             for_each_packet(np, nthreads, [&](size_t p) {
                 const size_t off = p * gpuar::kPacket;
                 const uint32_t len = static_cast<uint32_t>(std::min<size_t>(gpuar::kPacket, got - off));
                 // --stored=auto / --sparse=auto: the rule of ../kinds.h over the bytes that are coded; a raw or sparse packet is
                 // its own stream form in the slot (what the GPU pipeline overwrites the encoder's packet with), a coded one as ever
                 uint32_t kept = 0;
-                if (mixed()) {
-                    kind[p] = static_cast<uint8_t>(gpuar::kinds_store_packet(coded + off, len, stored, sparse, slots.data() + p * gpuar::kSlot, gpuar::kSlot, &kept));
+                if (plan.kinds) {
+                    kind[p] = static_cast<uint8_t>(gpuar::kinds_store_packet(coded + off, len, plan.stored, plan.sparse, slots.data() + p * gpuar::kSlot, gpuar::kSlot, &kept));
                     if (kind[p] > gpuar::kSparseSparse) throw std::runtime_error("a packet outgrew its 8704-byte slot");
                 }
                 clen[p] = kept ? kept : static_cast<uint32_t>(encode_one(coded + off, len, slots.data() + p * gpuar::kSlot));
-                if (writeChecksum) crc[p] = gpuar::crc32_update(0, in.data() + off, len);
+                if (plan.crcs) crc[p] = gpuar::crc32_update(0, in.data() + off, len);
             });
             process_timer.stop();
             io_timer.start();
@@ -155,15 +168,15 @@ CompressionInfo CPUCompressor::compress(ProgressMonitor *monitor) {
                     throw std::runtime_error("Write data to file failed");
                 info.compressedFileSize += clen[p];
                 if (trailer) all_clens.push_back(static_cast<uint16_t>(clen[p]));
-                if (writeChecksum) all_crcs.push_back(crc[p]);
-                if (mixed()) all_kinds.push_back(kind[p]);
+                if (plan.crcs) all_crcs.push_back(crc[p]);
+                if (plan.kinds) all_kinds.push_back(kind[p]);
             }
             io_timer.stop();
             info.processedUncompressedSize += got;
             monitor->updateProgress(&info);
         }
         io_timer.start();
-        saveTrailer(all_clens, all_crcs, all_kinds);
+        saveTrailer(plan, all_clens, all_crcs, all_kinds);
         FileHeader header;
         header.setCompressedFileSize(info.compressedFileSize);
         header.setUncompressedFileSize(info.uncompressedFileSize);
@@ -200,8 +213,9 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         // packets hold (merged back below), as far as the file's trailer gives them
         const Trailer trailer = loadTrailer(stream_end, fileSize);
         const std::vector<uint16_t> &index = trailer.clens;
-        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging(), mixed = trailer.mixed();
-        mixed_file = mixed;
+        const PacketPlan plan = PacketPlan::of(trailer);
+        const bool indexed = trailer.indexed(), merging = plan.transforms();
+        mixed_file = plan.kinds;
         size_t first_packet = 0;                 // of the window
         io_timer.stop();
 
@@ -213,8 +227,8 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
         const unsigned nthreads = threads ? threads : std::max(1u, std::thread::hardware_concurrency());
         std::vector<uint8_t> window(kBatchPackets * gpuar::kSlot + 65536 + 16), out(kBatchPackets * gpuar::kPacket);
         std::vector<uint8_t> decoded(merging ? out.size() : 0);      // byte planes: a window is decoded here and merged into `out`
-        std::vector<uint8_t> base(trailer.based() ? out.size() : 0);  // ... and XORed with these bytes of the base
-        if (trailer.based()) openBase(info.uncompressedFileSize, "the file");
+        std::vector<uint8_t> base(plan.based ? out.size() : 0);      // ... and XORed with these bytes of the base
+        if (plan.based) openBase(info.uncompressedFileSize, "the file");
         std::vector<size_t> offsets(kBatchPackets + 1);
         std::vector<uint32_t> ulen(kBatchPackets);
         size_t file_pos = FileHeader::HEADER_LENGTH, next_packet = 0;
@@ -227,7 +241,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                     const size_t c = index[next_packet++];
                     // (byte planes: no packet longer than a slot, so that every window but the last holds kBatchPackets packets,
                     // a whole number of groups)
-                    if (c < gpuar::kHdr || ((merging || mixed) && c > gpuar::kSlot)) throw std::runtime_error("Incorrect file format");
+                    if (c < gpuar::kHdr || ((merging || plan.kinds) && c > gpuar::kSlot)) throw std::runtime_error("Incorrect file format");
                     bytes += c;
                     offsets[++np] = bytes;
                 }
@@ -258,7 +272,7 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
             uint8_t *const plain = merging ? decoded.data() : out.data();
             for_each_packet(np, nthreads, [&](size_t p) {
                 const uint8_t *pkt = window.data() + offsets[p];
-                const uint32_t kind = mixed ? trailer.kinds[first_packet + p] : gpuar::kSparseCoded;
+                const uint32_t kind = plan.kinds ? trailer.kinds[first_packet + p] : gpuar::kSparseCoded;
                 if (kind == gpuar::kSparseCoded) {
                     ulen[p] = static_cast<uint32_t>(decode_one(pkt, window.data() + bytes, plain + p * gpuar::kPacket));
                 } else {                                   // raw or sparse (../kinds.h): the header is checked, the decoder never sees it
@@ -269,23 +283,18 @@ CompressionInfo CPUCompressor::decompress(ProgressMonitor *monitor) {
                     ulen[p] = n;
                 }
             });
-            // (raw and sparse packets: every packet but the file's last holds 8192 bytes, as the GPU pipeline requires of such a file)
-            if (mixed)
+            // (byte planes, and raw and sparse packets, as the GPU pipeline requires of such a file: every packet but the file's last
+            // holds 8192 bytes)
+            if (merging || plan.kinds)
                 for (size_t p = 0; p < np; ++p) checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
             if (merging) {
                 size_t total = 0;
-                for (size_t p = 0; p < np; ++p) {
-                    checkPlanesPacket(first_packet + p, index.size(), ulen[p]);
-                    total += ulen[p];
-                }
-                if (trailer.based()) {
-                    // (every packet in front of this window holds 8192 bytes: checkPlanesPacket)
-                    readBase(base.data(), total, static_cast<uint64_t>(first_packet) * gpuar::kPacket);
-                    gpuar::merge_xor_host(decoded.data(), base.data(), total, trailer.elem_bytes, out.data());
-                } else if (trailer.filtering()) gpuar::merge_delta_host(decoded.data(), total, trailer.elem_bytes, out.data());
-                else gpuar::planes_host<true>(decoded.data(), total, trailer.elem_bytes, out.data());
+                for (size_t p = 0; p < np; ++p) total += ulen[p];
+                // (every packet in front of this window holds 8192 bytes: checkPlanesPacket)
+                if (plan.based) readBase(base.data(), total, static_cast<uint64_t>(first_packet) * gpuar::kPacket);
+                merge_host(plan, decoded.data(), base.data(), total, out.data());
             }
-            if (verify) {
+            if (plan.crcs) {
                 for (size_t p = 0; p < np; ++p) {
                     const size_t g = first_packet + p;
                     const uint64_t begin = static_cast<uint64_t>(g) * gpuar::kPacket;

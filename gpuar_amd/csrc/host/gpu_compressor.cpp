@@ -28,33 +28,27 @@
 // index trailer (packet_index.hpp) or from a scanner thread that walks the packet headers through the mapping
 // (`off += clen`, 4 bytes per packet) ahead of the lanes.  The files produced are byte-identical to those
 // of the reference's loop from byte 20 on.
+//
+// What never touches the HIP runtime -- the trace, sliced file I/O, the writer and its pieces, the chunk map, the chunks' turn at
+// the output offset, the first failure -- lives in pipeline_parts.hpp and is tested on the CPU.  What a job's packets go through
+// (element width, delta, base, CRCs, raw and sparse packets) is one PacketPlan (compressor.hpp), built from the options when
+// compressing and from the trailer when decompressing; a lane's buffers are prepared for it and its chunks coded by it.
 #include "gpu_compressor.hpp"
 
 #include <fcntl.h>
 #include <hip/hip_runtime_api.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
-#include <unistd.h>
 
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <deque>
-#include <functional>
-#include <map>
-#include <mutex>
-#include <thread>
 
-#include "file_header.hpp"
 #include "gpuar_hip.h"
 #include "input_guard.hpp"
-#include "packet_index.hpp"
+#include "pipeline_parts.hpp"
 
 namespace gip {
+
+using namespace pipeline;
 
 namespace {
 
@@ -63,20 +57,6 @@ constexpr size_t kSlot = GPUAR_SLOT_BYTES;
 constexpr size_t kLanesPerDevice = 3;      // chunks in flight per GPU
 constexpr size_t kPieceBytes = 64u << 20;  // what one D2H copy / one pwrite moves
 constexpr size_t kPiecesPerLane = 2;       // pinned buffers per lane: one being filled while the other is written
-constexpr size_t kIoSlice = 16u << 20;     // a pread / pwrite is cut into slices of this size, one helper thread each
-constexpr size_t kIoThreads = 4;           // ... at most this many at a time
-
-// GPUAR_TRACE=1: a timeline of the pipeline on stderr (seconds since the first call), for tools/cli_timing.sh
-double trace_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-void trace(const char *what, double value = -1) {
-    static const bool on = std::getenv("GPUAR_TRACE") != nullptr;
-    static const double t0 = trace_now();
-    static std::mutex lock;
-    if (!on) return;
-    std::lock_guard<std::mutex> hold(lock);
-    if (value >= 0) std::fprintf(stderr, "[gpuar %8.3f s] %s %.3f\n", trace_now() - t0, what, value);
-    else std::fprintf(stderr, "[gpuar %8.3f s] %s\n", trace_now() - t0, what);
-}
 
 void hip_check(hipError_t e, const char *what) {
     // same message shape as src/gpu_compressor.cpp:189-192
@@ -84,32 +64,6 @@ void hip_check(hipError_t e, const char *what) {
 }
 void gpuar_check(int code, const char *what) {
     if (code != GPUAR_OK) throw std::runtime_error(std::string("Fail to execute kernel code: ") + what + ": " + gpuar_hip_error_string(code));
-}
-
-// pread / pwrite of a large range, cut into slices that run on a few threads
-template <bool kWrite>
-void sliced_io(int fd, uint8_t *buf, size_t n, uint64_t at, const char *error) {
-    const size_t slices = std::max<size_t>(1, std::min(kIoThreads, (n + kIoSlice - 1) / kIoSlice));
-    const size_t per = ((n + slices - 1) / slices + 4095) & ~static_cast<size_t>(4095);
-    std::atomic<bool> failed{false};
-    auto run = [&](size_t k) {
-        size_t done = std::min(n, k * per);
-        const size_t end = std::min(n, done + per);
-        while (done < end) {
-            const ssize_t got = kWrite ? ::pwrite(fd, buf + done, end - done, static_cast<off_t>(at + done))
-                                       : ::pread(fd, buf + done, end - done, static_cast<off_t>(at + done));
-            if (got <= 0) {
-                failed = true;
-                return;
-            }
-            done += static_cast<size_t>(got);
-        }
-    };
-    std::vector<std::thread> helpers;
-    for (size_t k = 1; k < slices; ++k) helpers.emplace_back(run, k);
-    run(0);
-    for (auto &h : helpers) h.join();
-    if (failed) throw std::runtime_error(error);
 }
 
 // The input file mapped read-only and registered with the HIP runtime, so that hipMemcpyAsync reads the page
@@ -271,143 +225,42 @@ class MappedInput {
     bool refused = false;
 };
 
-// A pinned buffer handed from a lane to the writer and back.
-struct Piece {
-    uint8_t *data = nullptr;
-    size_t bytes = 0;
-    uint64_t at = 0;           // file offset (unordered mode); ignored when the writer keeps the running offset
-    bool last_of_chunk = false;
-    size_t plain_bytes = 0;    // uncompressed bytes this piece completes (progress line)
-    std::function<void()> give_back;
-};
-
-// The writer: ONE thread that turns pieces into pwrite()s.
-//   ordered (compress): chunk c is written behind chunk c-1 -- where it starts is the sum of what came before,
-//       the pipeline's one serial quantity, which this thread simply carries; pieces of a chunk arrive in order.
-//   unordered (decompress): every piece knows its own file offset; pieces are written as they arrive.
-class Writer {
+// Device memory (kPinned: pinned host memory) that frees itself, and moves but is never copied.  ensure(count) makes room for
+// `count` elements, on the current device, unless there is room already: all of a lane's buffers are sized by the lane's one chunk size.
+template <typename T, bool kPinned>
+class Memory {
   public:
-    Writer(int fd, bool ordered, uint64_t start, const char *error) : fd(fd), ordered(ordered), at(start), error(error) {
-        worker = std::thread([this] { run(); });
+    Memory() = default;
+    Memory(Memory &&other) noexcept { std::swap(p, other.p); }
+    ~Memory() {
+        if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p));
     }
-    ~Writer() {
-        abort();
-        if (worker.joinable()) worker.join();
+    void ensure(size_t count) {
+        void **to = reinterpret_cast<void **>(&p);
+        if (!p) hip_check(kPinned ? hipHostMalloc(to, count * sizeof(T), hipHostMallocDefault) : hipMalloc(to, count * sizeof(T)), kPinned ? "hipHostMalloc" : "hipMalloc");
     }
-    void submit(size_t chunk, Piece p) {
-        std::lock_guard<std::mutex> hold(lock);
-        if (aborted) {
-            if (p.give_back) p.give_back();
-            return;
-        }
-        queues[ordered ? chunk : 0].push_back(std::move(p));
-        wake.notify_all();
-    }
-    // no more pieces will come; waits for everything submitted to be written and rethrows the writer's failure
-    uint64_t finish(size_t n_chunks) {
-        {
-            std::lock_guard<std::mutex> hold(lock);
-            expect_chunks = n_chunks;
-            closing = true;
-            wake.notify_all();
-        }
-        if (worker.joinable()) worker.join();
-        if (failure) std::rethrow_exception(failure);
-        return at;
-    }
-    void abort() {
-        std::lock_guard<std::mutex> hold(lock);
-        aborted = true;
-        wake.notify_all();
-    }
-    std::function<void(size_t)> on_progress;      // called with the plain bytes of every piece written
-    std::function<void()> on_failure;             // the writer itself failed (disk full ...): lets the lanes go
+    operator T *() const { return p; }
 
   private:
-    void run() {
-        try {
-            for (;;) {
-                Piece p;
-                {
-                    std::unique_lock<std::mutex> hold(lock);
-                    const size_t key = 0;
-                    wake.wait(hold, [&] {
-                        if (aborted) return true;
-                        auto it = queues.find(ordered ? next_chunk : key);
-                        if (it != queues.end() && !it->second.empty()) return true;
-                        return closing && (!ordered || next_chunk >= expect_chunks);
-                    });
-                    if (aborted) break;
-                    auto it = queues.find(ordered ? next_chunk : key);
-                    if (it == queues.end() || it->second.empty()) break;          // closing and drained
-                    p = std::move(it->second.front());
-                    it->second.pop_front();
-                    if (ordered && p.last_of_chunk) {
-                        queues.erase(it);
-                        ++next_chunk;
-                    }
-                }
-                try {
-                    const double w0 = trace_now();
-                    if (first_write < 0) first_write = w0, trace("writer: first piece");
-                    if (p.bytes) sliced_io<true>(fd, p.data, p.bytes, ordered ? at : p.at, error);
-                    busy_s += trace_now() - w0;
-                    bytes_written += p.bytes;
-                } catch (...) {
-                    if (p.give_back) p.give_back();
-                    throw;
-                }
-                if (ordered) at += p.bytes;
-                if (p.give_back) p.give_back();
-                if (on_progress) on_progress(p.plain_bytes);
-            }
-        } catch (...) {
-            failure = std::current_exception();
-        }
-        if (first_write >= 0) {
-            trace("writer: done; seconds inside pwrite:", busy_s);
-            trace("writer: GB/s while writing:", bytes_written / std::max(busy_s, 1e-9) / 1e9);
-            trace("writer: seconds between first piece and last:", trace_now() - first_write);
-        }
-        // whatever is still queued goes back to its lane (which may be waiting for it)
-        {
-            std::lock_guard<std::mutex> hold(lock);
-            aborted = true;
-            for (auto &q : queues)
-                for (auto &p : q.second)
-                    if (p.give_back) p.give_back();
-            queues.clear();
-        }
-        if (failure && on_failure) on_failure();
-    }
+    T *p = nullptr;
+};
+template <typename T>
+using Device = Memory<T, false>;
+template <typename T>
+using Pinned = Memory<T, true>;
 
-    int fd;
-    bool ordered;
-    uint64_t at;
-    const char *error;
-    std::mutex lock;
-    std::condition_variable wake;
-    std::map<size_t, std::deque<Piece>> queues;
-    size_t next_chunk = 0, expect_chunks = 0;
-    bool closing = false, aborted = false;
-    std::exception_ptr failure;
-    std::thread worker;
-    double first_write = -1, busy_s = 0, bytes_written = 0;
+// what a chunk's kernels reported (GPUAR_STATUS_*), and how many bytes its packets came to
+struct Encoded {
+    size_t n_stream;
+    uint32_t flags;
+};
+// ... and, under GPUAR_STATUS_CHECKSUM, the chunk's lowest packet that does not match its CRC
+struct Decoded {
+    uint32_t flags;
+    uint64_t first_bad;
 };
 
 }  // namespace
-
-// Keeps the first failure of any lane and tells the others to stop.
-struct GPUCompressor::Failure {
-    std::mutex lock;
-    std::exception_ptr first;
-    std::atomic<bool> stop{false};
-    void set(std::exception_ptr e) {
-        std::lock_guard<std::mutex> hold(lock);
-        if (!first) first = e;
-        stop = true;
-    }
-};
 
 // Everything one lane needs for one chunk of `cap` packets.
 struct GPUCompressor::DeviceBuffers {
@@ -416,33 +269,31 @@ struct GPUCompressor::DeviceBuffers {
     size_t piece_bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    uint8_t *d_plain = nullptr;     // cap * 8192
-    uint8_t *d_slots = nullptr;     // cap * 8704 (compress only)
-    uint8_t *d_stream = nullptr;    // cap * 8704 (+16)
-    uint64_t *d_offsets = nullptr;  // cap + 1, then this lane's status word
-    uint64_t *h_offsets = nullptr;  // pinned, cap + 2: the word behind the offsets receives the status word
-    uint32_t *d_status = nullptr;   // this lane's own status word (device): its launches report here, nobody else's do
-    uint32_t *d_crc = nullptr;      // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
-    uint32_t *h_crc = nullptr;      // pinned, the same
-    uint8_t *d_planes = nullptr;    // cap * 8192 (--planes, --delta / a version-3 or -4 trailer): the chunk split into byte planes, or merged back
-    uint8_t *d_base = nullptr;      // cap * 8192 (--base / a version-5 trailer): the base's bytes of the chunk's byte range
-    uint32_t *d_est = nullptr;      // cap estimates and cap scan words (--stored / --sparse): what the kind of every packet is decided from
-    uint32_t *d_scan = nullptr;
-    uint8_t *d_kind = nullptr;      // cap packet kinds (--stored / --sparse, a version-6 trailer)
-    uint8_t *h_kind = nullptr;      // pinned, the same
-    uint64_t *d_desc = nullptr;     // 4 * (cap + 1): a version-6 chunk's coded packets as a batch of one-packet buffers (decodeChunk)
-    uint64_t *h_desc = nullptr;     // pinned, the same
+    Device<uint8_t> d_plain;       // cap * 8192
+    Device<uint8_t> d_slots;       // cap * 8704 (compress only)
+    Device<uint8_t> d_stream;      // cap * 8704 (+16)
+    Device<uint64_t> d_offsets;    // cap + 1, then this lane's status word
+    Pinned<uint64_t> h_offsets;    // cap + 2: the word behind the offsets receives the status word
+    Device<uint32_t> d_crc;        // cap packet CRC-32s (--checksum), then the verify's lowest bad packet (u64)
+    Pinned<uint32_t> h_crc;        // the same
+    Device<uint8_t> d_planes;      // cap * 8192 (--planes, --delta / a version-3 or -4 trailer): the chunk split into byte planes, or merged back
+    Device<uint8_t> d_base;        // cap * 8192 (--base / a version-5 trailer): the base's bytes of the chunk's byte range
+    Device<uint32_t> d_est;        // cap estimates and cap scan words (--stored / --sparse): what the kind of every packet is decided from
+    Device<uint32_t> d_scan;
+    Device<uint8_t> d_kind;        // cap packet kinds (--stored / --sparse, a version-6 trailer)
+    Pinned<uint8_t> h_kind;        // the same
+    Device<uint64_t> d_desc;       // 4 * (cap + 1): a version-6 chunk's coded packets as a batch of one-packet buffers (decodeChunk)
+    Pinned<uint64_t> h_desc;       // the same
+    Pinned<uint8_t> pieces[kPiecesPerLane];      // the lane's pinned pieces
     hipEvent_t epoch = nullptr;     // the device's common time base (owned by the GPUCompressor)
     std::vector<std::pair<float, float>> busy;   // [begin, end) of every chunk's kernels, ms since `epoch`
-    // the lane's pinned pieces and which of them are free
-    uint8_t *pieces[kPiecesPerLane] = {};
+    // which of the lane's pinned pieces are free
     std::mutex piece_lock;
     std::condition_variable piece_free;
     bool piece_busy[kPiecesPerLane] = {};
     bool aborted = false;
 
-    void allocate(int dev, size_t packets, bool compressing) {
-        device = dev;
+    void allocate(size_t packets, bool compressing) {
         cap = packets;
         piece_bytes = std::min(kPieceBytes, cap * kSlot + 16);
         hip_check(hipSetDevice(device), "hipSetDevice");
@@ -450,83 +301,38 @@ struct GPUCompressor::DeviceBuffers {
         hip_check(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
         hip_check(hipEventCreate(&t0), "hipEventCreate");
         hip_check(hipEventCreate(&t1), "hipEventCreate");
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_plain), cap * kPacket), "hipMalloc");
-        if (compressing) hip_check(hipMalloc(reinterpret_cast<void **>(&d_slots), cap * kSlot), "hipMalloc");
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_stream), cap * kSlot + 16), "hipMalloc");
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_offsets), (cap + 2) * sizeof(uint64_t)), "hipMalloc");
-        d_status = reinterpret_cast<uint32_t *>(d_offsets + cap + 1);
-        hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_offsets), (cap + 2) * sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc");
+        d_plain.ensure(cap * kPacket);
+        if (compressing) d_slots.ensure(cap * kSlot);
+        d_stream.ensure(cap * kSlot + 16);
+        d_offsets.ensure(cap + 2);
+        h_offsets.ensure(cap + 2);
         // (the pinned pieces are allocated when the first one is asked for: by then the lane's first copy and kernels are
         // on their way, and pinning 128 MiB takes as long as they do)
-        has_slots = compressing;
     }
-    bool has_slots = false;
-    // room for a chunk's CRC-32s: only for a job that writes or verifies them (compress --checksum, decompress of a file with a
-    // version-2 trailer); the current device is the lane's
-    void allocateCrc() {
-        if (d_crc) return;
-        hip_check(hipMalloc(reinterpret_cast<void **>(&d_crc), crcBytes()), "hipMalloc");
-        hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_crc), crcBytes(), hipHostMallocDefault), "hipHostMalloc");
+    // this lane's own status word (device), behind the offsets: its launches report here, nobody else's do
+    uint32_t *status() const { return reinterpret_cast<uint32_t *>(d_offsets + cap + 1); }
+    // What a job of this plan needs beside that; the current device is the lane's.  An object's lanes outlive a job, and the next
+    // one may go the other way: what is there stays.
+    //   CRCs (compress --checksum, decompress of a file whose trailer has them): room for a chunk's CRC-32s
+    //   a transform: one more buffer of chunk size for the chunk split into byte planes, or merged back
+    //   a base: and one for the base's bytes
+    //   kinds (compress --stored / --sparse, decompress of a version-6 file): room for a chunk's packet kinds, with the estimates and
+    //   scan words they are decided from when compressing, with the descriptors of the chunk's coded packets when decompressing
+    void prepare(const PacketPlan &plan, bool compressing) {
+        if (plan.crcs) d_crc.ensure(crcSlots() + 2), h_crc.ensure(crcSlots() + 2);
+        if (plan.transforms()) d_planes.ensure(cap * kPacket);
+        if (plan.based) d_base.ensure(cap * kPacket);
+        if (plan.kinds) d_kind.ensure(cap), h_kind.ensure(cap);
+        if (plan.kinds && compressing) d_est.ensure(cap), d_scan.ensure(cap);
+        if (plan.kinds && !compressing) d_desc.ensure(4 * (cap + 1)), h_desc.ensure(4 * (cap + 1));
     }
-    // one more buffer of chunk size for a job that splits its input into byte planes or merges them back; the current device is the lane's
-    void allocatePlanes() {
-        if (!d_planes) hip_check(hipMalloc(reinterpret_cast<void **>(&d_planes), cap * kPacket), "hipMalloc");
-    }
-    // and one for the base's bytes of a job that XORs against a base
-    void allocateBase() {
-        if (!d_base) hip_check(hipMalloc(reinterpret_cast<void **>(&d_base), cap * kPacket), "hipMalloc");
-    }
-    // room for a chunk's packet kinds: only for a job that writes or reads raw and sparse packets (compress --stored / --sparse,
-    // with the estimates and scan words they are decided from; decompress of a file with a version-6 trailer, with the
-    // descriptors of its coded packets); the current device is the lane's
-    void allocateKinds(bool compressing) {
-        if (!d_kind) {
-            hip_check(hipMalloc(reinterpret_cast<void **>(&d_kind), cap), "hipMalloc");
-            hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_kind), cap, hipHostMallocDefault), "hipHostMalloc");
-        }
-        // (an object's lanes outlive a job: the next one may go the other way)
-        if (compressing && !d_est) {
-            hip_check(hipMalloc(reinterpret_cast<void **>(&d_est), cap * sizeof(uint32_t)), "hipMalloc");
-            hip_check(hipMalloc(reinterpret_cast<void **>(&d_scan), cap * sizeof(uint32_t)), "hipMalloc");
-        } else if (!compressing && !d_desc) {
-            hip_check(hipMalloc(reinterpret_cast<void **>(&d_desc), 4 * (cap + 1) * sizeof(uint64_t)), "hipMalloc");
-            hip_check(hipHostMalloc(reinterpret_cast<void **>(&h_desc), 4 * (cap + 1) * sizeof(uint64_t), hipHostMallocDefault), "hipHostMalloc");
-        }
-    }
-    void release() {
+    // (a lane's buffers live as long as the object that holds them: the memory frees itself behind this)
+    ~DeviceBuffers() {
         if (!cap) return;
         (void)hipSetDevice(device);
-        (void)hipFree(d_plain);
-        if (d_kind) (void)hipFree(d_kind);
-        if (h_kind) (void)hipHostFree(h_kind);
-        if (d_est) (void)hipFree(d_est);
-        if (d_scan) (void)hipFree(d_scan);
-        if (d_desc) (void)hipFree(d_desc);
-        if (h_desc) (void)hipHostFree(h_desc);
-        d_kind = h_kind = nullptr;
-        d_est = d_scan = nullptr;
-        d_desc = h_desc = nullptr;
-        if (d_base) (void)hipFree(d_base);
-        d_base = nullptr;
-        if (d_planes) (void)hipFree(d_planes);
-        d_planes = nullptr;
-        if (d_slots) (void)hipFree(d_slots);
-        (void)hipFree(d_stream);
-        (void)hipFree(d_offsets);
-        (void)hipHostFree(h_offsets);
-        if (d_crc) (void)hipFree(d_crc);
-        if (h_crc) (void)hipHostFree(h_crc);
-        d_crc = nullptr;
-        h_crc = nullptr;
-        for (auto &p : pieces) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-        }
         (void)hipEventDestroy(t0);
         (void)hipEventDestroy(t1);
         (void)hipStreamDestroy(stream);
-        d_slots = nullptr;
-        cap = 0;
     }
 
     // a free pinned piece (blocks while the writer still holds both)
@@ -537,13 +343,12 @@ struct GPUCompressor::DeviceBuffers {
             for (size_t k = 0; k < kPiecesPerLane; ++k)
                 if (!piece_busy[k]) {
                     piece_busy[k] = true;
-                    if (!pieces[k]) {
-                        hold.unlock();
-                        const hipError_t e = hipHostMalloc(reinterpret_cast<void **>(&pieces[k]), piece_bytes, hipHostMallocDefault);
-                        if (e != hipSuccess) {
-                            givePiece(k);
-                            hip_check(e, "hipHostMalloc");
-                        }
+                    hold.unlock();
+                    try {
+                        pieces[k].ensure(piece_bytes);
+                    } catch (...) {
+                        givePiece(k);
+                        throw;
                     }
                     return k;
                 }
@@ -640,57 +445,65 @@ struct GPUCompressor::DeviceBuffers {
         } while (done < n);
     }
 
-    // d_plain[0..n_plain) -> d_stream[0..n_stream), h_offsets[0..n_packets]; returns n_stream and, through `flags`,
+    // Which buffer holds the bytes that are coded (compress), or the bytes that are written (decompress): the far side of the
+    // plan's transform when it has one.
+    uint8_t *transformed(const PacketPlan &plan) const { return plan.transforms() ? d_planes : d_plain; }
+    // d_plain[0..n) -> d_planes: XORed with d_base, else the elements' differences, else as they are, split into byte planes of
+    // elements plan.elem wide (delta and base at a width of 1 too); else nothing
+    void split(const PacketPlan &plan, size_t n) {
+        if (plan.based) gpuar_check(gpuar_hip_split_xor(d_plain, d_base, n, plan.elem, d_planes, stream), "gpuar_hip_split_xor");
+        else if (plan.delta) gpuar_check(gpuar_hip_split_delta(d_plain, n, plan.elem, d_planes, stream), "gpuar_hip_split_delta");
+        else if (plan.elem > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n, plan.elem, d_planes, stream), "gpuar_hip_split_planes");
+    }
+    // ... and back: the n decoded bytes in d_plain are such byte planes, merged into d_planes
+    void merge(const PacketPlan &plan, size_t n) {
+        if (plan.based) gpuar_check(gpuar_hip_merge_xor(d_plain, d_base, n, plan.elem, d_planes, stream), "gpuar_hip_merge_xor");
+        else if (plan.delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n, plan.elem, d_planes, stream), "gpuar_hip_merge_delta");
+        else if (plan.elem > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n, plan.elem, d_planes, stream), "gpuar_hip_merge_planes");
+    }
+
+    // d_plain[0..n_plain) -> d_stream[0..n_stream), h_offsets[0..n_packets]; returns n_stream and
     // what THIS chunk's launches reported (GPUAR_STATUS_*): the status word travels back with the offsets, on the
     // lane's own stream -- no device-wide synchronisation, no flag shared with another lane
     // `mode`: GPUAR_MODE_* -- which encode kernel (the caller knows whether this launch has the chip to itself)
-    // `checksum`: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
-    // `planes` > 1: what is coded is the chunk split into byte planes of elements that wide (d_planes); the CRCs stay the input's
-    // `delta`: ... of the elements' differences (at a width of 1 too)
-    // `based`: ... of the chunk XORed with d_base (at a width of 1 too)
-    // `stored` / `sparse`: behind the encoder, the packets the rule of ../kinds.h keeps raw or sparse overwrite their slots (every packet
+    // plan.crcs: also the CRC-32 of every packet of the input, into h_crc[0..n_packets)
+    // a plan that transforms: what is coded is the chunk after split(); the CRCs stay the input's
+    // plan.stored / plan.sparse: behind the encoder, the packets the rule of ../kinds.h keeps raw or sparse overwrite their slots (every packet
     // is coded first: the CLI is bound by the file system, not by the encoder); the kinds go to h_kind[0..n_packets)
-    size_t encodeChunk(size_t n_plain, uint32_t &flags, int mode, bool checksum, int planes, bool delta, bool based = false, bool stored = false,
-                       bool sparse = false) {
+    Encoded encodeChunk(size_t n_plain, const PacketPlan &plan, int mode) {
         const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
-        hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
+        hip_check(hipMemsetAsync(status(), 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipEventRecord(t0, stream), "event");
-        if (based) gpuar_check(gpuar_hip_split_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_xor");
-        else if (delta) gpuar_check(gpuar_hip_split_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_delta");
-        else if (planes > 1) gpuar_check(gpuar_hip_split_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_split_planes");
-        const uint8_t *coded = planes > 1 || delta || based ? d_planes : d_plain;
-        gpuar_check(gpuar_hip_encode_mode(coded, n_plain, d_slots, d_status, stream, mode), "gpuar_hip_encode_mode");
-        if (stored || sparse) {
+        split(plan, n_plain);
+        const uint8_t *coded = transformed(plan);
+        gpuar_check(gpuar_hip_encode_mode(coded, n_plain, d_slots, status(), stream, mode), "gpuar_hip_encode_mode");
+        if (plan.kinds) {
             gpuar_check(gpuar_hip_estimate(coded, n_plain, d_est, stream), "gpuar_hip_estimate");
-            if (sparse) gpuar_check(gpuar_hip_sparse_scan(coded, n_plain, d_scan, stream), "gpuar_hip_sparse_scan");
-            gpuar_check(gpuar_hip_kinds_store(coded, n_plain, d_est, sparse ? d_scan : nullptr, stored ? 1 : 0, d_slots, d_kind, d_status, stream),
+            if (plan.sparse) gpuar_check(gpuar_hip_sparse_scan(coded, n_plain, d_scan, stream), "gpuar_hip_sparse_scan");
+            gpuar_check(gpuar_hip_kinds_store(coded, n_plain, d_est, plan.sparse ? &d_scan[0] : nullptr, plan.stored ? 1 : 0, d_slots, d_kind, status(), stream),
                         "gpuar_hip_kinds_store");
         }
         gpuar_check(gpuar_hip_compact(d_slots, n_packets, d_stream, d_offsets, stream), "gpuar_hip_compact");
-        if (checksum) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
+        if (plan.crcs) gpuar_check(gpuar_hip_crc32(d_plain, n_plain, d_crc, stream), "gpuar_hip_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
         hip_check(hipMemcpyAsync(h_offsets, d_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
-        hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
-        if (checksum) hip_check(hipMemcpyAsync(h_crc, d_crc, n_packets * sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
-        if (stored || sparse) hip_check(hipMemcpyAsync(h_kind, d_kind, n_packets, hipMemcpyDeviceToHost, stream), "D2H");
+        hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, status(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        if (plan.crcs) hip_check(hipMemcpyAsync(h_crc, d_crc, n_packets * sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        if (plan.kinds) hip_check(hipMemcpyAsync(h_kind, d_kind, n_packets, hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipStreamSynchronize(stream), "sync");
-        flags = *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1);
         noteBusy();
-        return static_cast<size_t>(h_offsets[n_packets]);
+        return {static_cast<size_t>(h_offsets[n_packets]), *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1)};
     }
 
     // d_stream[0..n_stream) with h_offsets[0..n_packets] -> d_plain[0..n_packets*8192); returns this chunk's status flags.
     // crcs (n_packets values, or null): the decoded packets -- n_plain bytes back to back -- are verified against them;
     // GPUAR_STATUS_CHECKSUM in the flags then, and the chunk's lowest bad packet in `first_bad`
-    // `planes` > 1: the n_plain decoded bytes are byte planes, merged into d_planes before they are verified; the result is there
-    // `delta`: ... of differences, summed up by the merge (at a width of 1 too)
-    // `based`: ... XORed with d_base by the merge (at a width of 1 too)
+    // a plan that transforms: the n_plain decoded bytes go through merge() before they are verified; the result is in transformed(plan)
     // `kinds` (n_packets values, or null: every packet is coded): the chunk of a version-6 file, whose packets all hold 8192 bytes but
     // the last.  Its coded packets are decoded as a batch of one-packet buffers (raw bytes are never fed to the decoder; a chunk
     // without a coded packet launches no decoder), then one launch takes the raw and sparse ones out of the stream
-    uint32_t decodeChunk(size_t n_packets, const uint32_t *crcs = nullptr, size_t n_plain = 0, uint64_t *first_bad = nullptr, int planes = 1,
-                         bool delta = false, bool based = false, const uint8_t *kinds = nullptr) {
-        hip_check(hipMemsetAsync(d_status, 0, sizeof(uint32_t), stream), "memset");
+    Decoded decodeChunk(size_t n_packets, size_t n_plain, const PacketPlan &plan, const uint32_t *crcs, const uint8_t *kinds) {
+        hip_check(hipMemsetAsync(status(), 0, sizeof(uint32_t), stream), "memset");
         hip_check(hipMemcpyAsync(d_offsets, h_offsets, (n_packets + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
         uint64_t *d_first_bad = crcs ? reinterpret_cast<uint64_t *>(d_crc + crcSlots()) : nullptr;
         if (crcs) {
@@ -716,27 +529,25 @@ struct GPUCompressor::DeviceBuffers {
             if (n_coded) {
                 hip_check(hipMemcpyAsync(d_desc, h_desc, 4 * (cap + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), "H2D");
                 gpuar_check(gpuar_hip_decode_stream_batch(d_stream, d_desc + 3 * (cap + 1), d_desc + 2 * (cap + 1), n_coded, n_coded,
-                                                          reinterpret_cast<uint8_t *const *>(d_desc), d_desc + (cap + 1), d_status, stream),
+                                                          reinterpret_cast<uint8_t *const *>(&d_desc[0]), d_desc + (cap + 1), status(), stream),
                             "gpuar_hip_decode_stream_batch");
             }
-            gpuar_check(gpuar_hip_kinds_expand(d_stream, d_offsets, d_kind, n_packets, d_plain, n_plain, d_status, stream), "gpuar_hip_kinds_expand");
+            gpuar_check(gpuar_hip_kinds_expand(d_stream, d_offsets, d_kind, n_packets, d_plain, n_plain, status(), stream), "gpuar_hip_kinds_expand");
         } else {
-            gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, d_status, stream), "gpuar_hip_decode_stream");
+            gpuar_check(gpuar_hip_decode_stream(d_stream, d_offsets, n_packets, d_plain, status(), stream), "gpuar_hip_decode_stream");
         }
-        if (based) gpuar_check(gpuar_hip_merge_xor(d_plain, d_base, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_xor");
-        else if (delta) gpuar_check(gpuar_hip_merge_delta(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_delta");
-        else if (planes > 1) gpuar_check(gpuar_hip_merge_planes(d_plain, n_plain, static_cast<uint32_t>(planes), d_planes, stream), "gpuar_hip_merge_planes");
-        if (crcs) gpuar_check(gpuar_hip_verify_crc32(planes > 1 || delta || based ? d_planes : d_plain, n_plain, d_crc, d_first_bad, d_status, stream), "gpuar_hip_verify_crc32");
+        merge(plan, n_plain);
+        if (crcs) gpuar_check(gpuar_hip_verify_crc32(transformed(plan), n_plain, d_crc, d_first_bad, status(), stream), "gpuar_hip_verify_crc32");
         hip_check(hipEventRecord(t1, stream), "event");
-        hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, d_status, sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
+        hip_check(hipMemcpyAsync(h_offsets + n_packets + 1, status(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream), "D2H");
         if (crcs) hip_check(hipMemcpyAsync(h_crc + crcSlots(), d_first_bad, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), "D2H");
         hip_check(hipStreamSynchronize(stream), "sync");
         noteBusy();
-        if (crcs && first_bad) std::memcpy(first_bad, h_crc + crcSlots(), sizeof(uint64_t));
-        return *reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1);
+        Decoded done{*reinterpret_cast<const uint32_t *>(h_offsets + n_packets + 1), 0};
+        if (crcs) std::memcpy(&done.first_bad, h_crc + crcSlots(), sizeof(uint64_t));
+        return done;
     }
-    size_t crcSlots() const { return (cap + 1) / 2 * 2; }                       // u32 slots in front of the u64 (8-byte aligned)
-    size_t crcBytes() const { return crcSlots() * sizeof(uint32_t) + sizeof(uint64_t); }
+    size_t crcSlots() const { return (cap + 1) / 2 * 2; }      // u32 slots in front of the u64 (8-byte aligned), itself two more
 };
 
 GPUCompressor::GPUCompressor() {
@@ -752,10 +563,7 @@ GPUCompressor::GPUCompressor() {
 GPUCompressor::~GPUCompressor() { releaseBuffers(); }
 
 void GPUCompressor::releaseBuffers() {
-    for (DeviceBuffers *b : buffers) {
-        b->release();
-        delete b;
-    }
+    for (DeviceBuffers *b : buffers) delete b;
     buffers.clear();
     for (size_t g = 0; g < epochs.size(); ++g)
         if (epochs[g]) {
@@ -778,7 +586,7 @@ void GPUCompressor::ensureBuffers(size_t total_packets, bool compressing) {
     const size_t cap = std::max<size_t>(64, std::min(batchPackets, share));
     bool have = buffers.size() == lanes && !buffers.empty() && chunkPackets == cap;
     if (have && compressing)
-        for (DeviceBuffers *b : buffers) have = have && (!b->cap || b->has_slots);
+        for (DeviceBuffers *b : buffers) have = have && (!b->cap || b->d_slots);
     if (have) {
         for (DeviceBuffers *b : buffers) b->resetPieces();
         return;
@@ -813,16 +621,6 @@ void GPUCompressor::useDevices(const int n) {
     for (int d = 0; d < n; ++d) devices.push_back(d % count);
 }
 
-// How many packets chunk c holds.  The first chunks of a job are small and double from one to the next (64 MiB of input,
-// 128, 256 ...) until they reach the full chunk size: the writer gets its first piece a few milliseconds after the
-// start instead of after the first 512 MiB have crossed PCIe three lanes abreast, and it is the writer that bounds the
-// wall time.  (Chunks stay multiples of 64 packets: whole wavefronts.)
-static size_t rampPackets(size_t c, size_t full) {
-    constexpr size_t kFirst = 8192;
-    if (c >= 8 || full <= kFirst) return full;
-    return std::min(full, kFirst << c);
-}
-
 // Runs `work(lane, buffers, failure)` on every lane (lanes g*kLanesPerDevice .. belong to device g) and
 // rethrows the first failure.  `work` pulls chunk numbers until there are none left; `on_failure` runs on the
 // failing lane's thread, so that whoever the other lanes are waiting for lets them go.
@@ -854,7 +652,68 @@ void GPUCompressor::runLanes(Work &&work, OnFailure &&on_failure) {
     }
 }
 
-CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
+namespace {
+
+// Deals a job's chunks to the devices -- contiguous packet ranges in file order, dealt round-robin: chunk c belongs to device
+// c mod G -- and counts what each device did (GPUAR_TRACE).
+struct Dealer {
+    explicit Dealer(size_t G) : next_of_device(G), device_bytes(G), device_chunks(G) {}      // (all zero)
+    // the next chunk of device g
+    size_t take(size_t g) { return g + next_of_device.size() * next_of_device[g].fetch_add(1); }
+    void count(size_t g, uint64_t bytes) {
+        device_bytes[g] += bytes;
+        device_chunks[g] += 1;
+    }
+    // "<job>: device g <did> N bytes in M chunks<of>"
+    void report(const char *job, const char *did, const std::string &of = "") {
+        for (size_t g = 0; g < next_of_device.size(); ++g)
+            trace((std::string(job) + ": device " + std::to_string(g) + " " + did + " " + std::to_string(device_bytes[g].load()) + " bytes in " + std::to_string(device_chunks[g].load()) + " chunks" + of).c_str());
+    }
+    std::vector<std::atomic<size_t>> next_of_device;
+    std::vector<std::atomic<uint64_t>> device_bytes, device_chunks;
+};
+
+// the writer's progress callback (the writer is one thread): what the pieces written so far complete, to the monitor
+std::function<void(size_t)> progressTo(CompressionInfo &info, ProgressMonitor *monitor) {
+    return [&info, monitor](size_t plain) {
+        if (!plain) return;
+        info.processedUncompressedSize += plain;
+        monitor->updateProgress(&info);
+    };
+}
+
+// After the lanes: if one of them failed, its failure goes on up -- unless the writer has a failure of its own (disk full), which
+// is the cause then: the lanes only saw "pipeline stopped".
+void rethrowLaneFailure(Writer &writer, std::exception_ptr lane_failure) {
+    if (!lane_failure) return;
+    writer.abort();
+    (void)writer.finish(0);      // rethrows the writer's own failure when it has one: that is the cause then
+    std::rethrow_exception(lane_failure);
+}
+
+// the chunks' tables, one behind the other
+template <typename T>
+std::vector<T> joined(const std::vector<std::vector<T>> &chunks) {
+    std::vector<T> all;
+    for (const auto &v : chunks) all.insert(all.end(), v.begin(), v.end());
+    return all;
+}
+
+// How many packets chunk c holds.  The first chunks of a job are small and double from one to the next (64 MiB of input,
+// 128, 256 ...) until they reach the full chunk size: the writer gets its first piece a few milliseconds after the
+// start instead of after the first 512 MiB have crossed PCIe three lanes abreast, and it is the writer that bounds the
+// wall time.  (Chunks stay multiples of 64 packets: whole wavefronts.)
+size_t rampPackets(size_t c, size_t full) {
+    constexpr size_t kFirst = 8192;
+    if (c >= 8 || full <= kFirst) return full;
+    return std::min(full, kFirst << c);
+}
+
+}  // namespace
+
+// Runs `job()` between the opening of the files and the times: a failed job leaves an empty file, not a half-written one.
+template <typename Job>
+CompressionInfo GPUCompressor::runJob(ProgressMonitor *monitor, Job &&job) {
     CompressionInfo info;
     monitor->reset();
     process_timer.reset();
@@ -863,142 +722,7 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
     openFiles(false);
     const int out_fd = fileno(saveFile);
     try {
-        info.uncompressedFileSize = getFileSize(openFile);
-        if (based()) openBase(info.uncompressedFileSize, "the input");
-        const size_t total_packets = (info.uncompressedFileSize + kPacket - 1) / kPacket;
-        ensureBuffers(total_packets, true);
-        const size_t G = devices.size();
-        // contiguous packet ranges in file order: where chunk c starts and how long it is
-        std::vector<uint64_t> chunk_at;
-        for (uint64_t at = 0; at < info.uncompressedFileSize; at += rampPackets(chunk_at.size() - 1, chunkPackets) * kPacket) chunk_at.push_back(at);
-        const size_t n_chunks = chunk_at.size();
-        chunk_at.push_back(info.uncompressedFileSize);
-        for (size_t c = 0; c < n_chunks && c < 8; ++c)      // (GPUAR_TRACE: the ramp, and where the chunks behind it start)
-            trace(("compress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>((chunk_at[c + 1] - chunk_at[c] + kPacket - 1) / kPacket));
-        // The latency-mode encode kernel is faster only for a launch that has the chip to itself (include/gpuar_hip.h):
-        // a job of one chunk.  With several chunks the lanes of a device keep three launches in flight (the ramped first
-        // chunks are small enough for GPUAR_MODE_AUTO to pick the latency kernel), so the pipeline names the kernel itself.
-        const int encode_mode = n_chunks == 1 ? GPUAR_MODE_AUTO : GPUAR_MODE_THROUGHPUT;
-        const int in_fd = fileno(openFile);
-        hip_check(hipSetDevice(devices[0]), "hipSetDevice");
-        trace("compress: files open, device set");
-        MappedInput mapped;
-        mapped.open(in_fd, info.uncompressedFileSize);
-        trace(mapped.data() ? "compress: input mapped" : "compress: input NOT mapped (pread path)");
-        mapped.warmFirstWindow(devices[0]);
-        // room for the worst case up front: writing into allocated blocks is faster than growing the file, and the real
-        // length is set at the end (best effort: a file system without fallocate just grows the file as it goes)
-        // (the fallocate system call, not posix_fallocate: where the file system cannot do it, glibc's stand-in would write zeros)
-        (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(FileHeader::HEADER_LENGTH + total_packets * kSlot));
-        const bool trailer = wantsTrailer();
-        std::vector<std::vector<uint16_t>> chunk_clens(trailer ? n_chunks : 0);        // for the optional index trailer
-        std::vector<std::vector<uint32_t>> chunk_crcs(writeChecksum ? n_chunks : 0);   // and the checksums in it
-        std::vector<std::vector<uint8_t>> chunk_kinds(mixed() ? n_chunks : 0);         // and the packet kinds (--stored / --sparse)
-        std::vector<std::atomic<size_t>> next_of_device(G);
-        for (auto &n : next_of_device) n = 0;
-        std::vector<std::atomic<uint64_t>> device_bytes(G), device_chunks(G);      // what each device coded (GPUAR_TRACE)
-        for (size_t g = 0; g < G; ++g) device_bytes[g] = 0, device_chunks[g] = 0;
-        std::mutex progress_lock;
-        {
-            Writer writer(out_fd, true, FileHeader::HEADER_LENGTH, "Write compressed data to output file failed");
-            writer.on_progress = [&](size_t plain) {
-                if (!plain) return;
-                std::lock_guard<std::mutex> hold(progress_lock);
-                info.processedUncompressedSize += plain;
-                monitor->updateProgress(&info);
-            };
-            writer.on_failure = [&] {
-                for (DeviceBuffers *b : buffers) b->abortWaits();
-            };
-            std::exception_ptr lane_failure;
-            try {
-                runLanes(
-                    [&](size_t lane, DeviceBuffers &b, Failure &failure) {
-                        const size_t g = lane / kLanesPerDevice;
-                        for (;;) {
-                            // contiguous packet ranges in file order, dealt round-robin: chunk c belongs to device c mod G
-                            const size_t c = g + G * next_of_device[g].fetch_add(1);
-                            if (c >= n_chunks || failure.stop) break;
-                            if (c == 0) trace("compress: lane of chunk 0 starts");
-                            if (!b.cap) b.allocate(b.device, chunkPackets, true);
-                            if (c == 0) trace("compress: its buffers allocated");
-                            hip_check(hipSetDevice(b.device), "hipSetDevice");
-                            if (writeChecksum) b.allocateCrc();
-                            if (planes > 1 || delta || based()) b.allocatePlanes();
-                            if (based()) b.allocateBase();
-                            if (mixed()) b.allocateKinds(true);
-                            b.epoch = static_cast<hipEvent_t>(epochOf(g));
-                            const uint64_t at = chunk_at[c];
-                            const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
-                            const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
-                            if (based()) b.uploadBase(baseFd, at, n_plain);      // the same byte range of the base
-                            if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
-                            uint32_t flags = 0;
-                            const size_t n_stream = b.encodeChunk(n_plain, flags, encode_mode, writeChecksum, planes, delta, based(), stored, sparse);     // (synchronises the lane's stream)
-                            if (from_mapping) mapped.release(at, n_plain);
-                            // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
-                            // (src/gpu_compressor.cpp:146-150)
-                            if (!mapped.intact(in_fd)) throw std::runtime_error("Read input file failed");
-                            if (c < 3) trace("compress: kernels of an early chunk done, chunk", static_cast<double>(c));
-                            if (flags & GPUAR_STATUS_SLOT_OVERFLOW)
-                                throw std::runtime_error("a packet outgrew its 8704-byte slot (input bytes " + std::to_string(at) + " .. " +
-                                                         std::to_string(at + n_plain) + ")");
-                            // (the scan words are computed from the very bytes: this cannot happen, and the file would still be valid)
-                            if (flags & GPUAR_STATUS_BAD_BATCH) throw std::runtime_error("Fail to execute kernel code: gpuar_hip_kinds_store: inconsistent scan");
-                            const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
-                            if (writeChecksum) chunk_crcs[c].assign(b.h_crc, b.h_crc + n_packets);
-                            if (mixed()) chunk_kinds[c].assign(b.h_kind, b.h_kind + n_packets);
-                            if (trailer) {
-                                chunk_clens[c].resize(n_packets);
-                                for (size_t p = 0; p < n_packets; ++p) chunk_clens[c][p] = static_cast<uint16_t>(b.h_offsets[p + 1] - b.h_offsets[p]);
-                            }
-                            device_bytes[g] += n_plain;
-                            device_chunks[g] += 1;
-                            b.drain(writer, c, b.d_stream, n_stream, 0, n_plain);     // the ordered writer knows where chunk c goes
-                        }
-                    },
-                    [&] { writer.abort(); });
-            } catch (...) {
-                lane_failure = std::current_exception();
-            }
-            if (lane_failure) {
-                // the writer's own failure (disk full) is the cause when it has one: the lanes only saw "pipeline stopped"
-                writer.abort();
-                (void)writer.finish(0);      // rethrows the writer's own failure when it has one: that is the cause then
-                std::rethrow_exception(lane_failure);
-            }
-            trace("compress: lanes done");
-            trace(mapped.wasRefused() ? "compress: a window could not be registered: the rest was read with pread" : "compress: every window registered");
-            trace("compress: input windows unregistered while the job ran:", static_cast<double>(mapped.windowsTrimmed()));
-            trace("compress: seconds inside hipHostUnregister for that:", mapped.trimSeconds());
-            for (size_t g = 0; g < G; ++g)
-                trace(("compress: device " + std::to_string(g) + " coded " + std::to_string(device_bytes[g].load()) + " bytes in " +
-                       std::to_string(device_chunks[g].load()) + " chunks of at most " + std::to_string(chunkPackets * kPacket) + " bytes").c_str());
-            info.compressedFileSize = static_cast<size_t>(writer.finish(n_chunks));
-        }
-        uint64_t file_end = info.compressedFileSize;
-        if (trailer) {
-            std::vector<uint16_t> all;
-            for (const auto &v : chunk_clens) all.insert(all.end(), v.begin(), v.end());
-            std::vector<uint32_t> crcs;
-            for (const auto &v : chunk_crcs) crcs.insert(crcs.end(), v.begin(), v.end());
-            if (std::fseek(saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
-            std::vector<uint8_t> kinds;
-            for (const auto &v : chunk_kinds) kinds.insert(kinds.end(), v.begin(), v.end());
-            saveTrailer(all, crcs, kinds);
-            if (std::fflush(saveFile) != 0) throw std::runtime_error("Write packet index failed");
-            file_end = static_cast<uint64_t>(std::ftell(saveFile));
-        }
-        FileHeader header;
-        header.setCompressedFileSize(info.compressedFileSize);
-        header.setUncompressedFileSize(info.uncompressedFileSize);
-        if (::pwrite(out_fd, header.getData(), FileHeader::HEADER_LENGTH, 0) != FileHeader::HEADER_LENGTH)
-            throw std::runtime_error("Write data to file failed");
-        if (::ftruncate(out_fd, static_cast<off_t>(file_end)) != 0) throw std::runtime_error("Write data to file failed");
-        trace("compress: header written, length set");
-        mapped.close();
-        closeFiles();
-        trace("compress: files closed");
+        job(info, out_fd);
     } catch (...) {
         if (::ftruncate(out_fd, 0) != 0) {}      // a failed job leaves an empty file, not a half-written one
         closeFiles();
@@ -1008,6 +732,144 @@ CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
     io_timer.stop();
     finishTimes(info);
     return info;
+}
+
+// One compress job: what its steps share.
+struct GPUCompressor::CompressJob {
+    GPUCompressor &self;
+    CompressionInfo &info;
+    ProgressMonitor *monitor;
+    const int out_fd;
+    const PacketPlan plan = self.plan();
+    const bool trailer = self.wantsTrailer();
+    const int in_fd = fileno(self.openFile);
+    MappedInput mapped;
+    std::vector<uint64_t> chunk_at;      // where chunk c starts in the input; one entry more: the input's end
+    size_t n_chunks = 0;
+    std::vector<std::vector<uint16_t>> chunk_clens;      // for the optional index trailer
+    std::vector<std::vector<uint32_t>> chunk_crcs;       // and the checksums in it
+    std::vector<std::vector<uint8_t>> chunk_kinds;       // and the packet kinds (--stored / --sparse)
+    Dealer deal{self.devices.size()};
+
+    // contiguous packet ranges in file order: where chunk c starts and how long it is
+    void cutChunks() {
+        for (uint64_t at = 0; at < info.uncompressedFileSize; at += rampPackets(chunk_at.size() - 1, self.chunkPackets) * kPacket) chunk_at.push_back(at);
+        n_chunks = chunk_at.size();
+        chunk_at.push_back(info.uncompressedFileSize);
+        for (size_t c = 0; c < n_chunks && c < 8; ++c)      // (GPUAR_TRACE: the ramp, and where the chunks behind it start)
+            trace(("compress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>((chunk_at[c + 1] - chunk_at[c] + kPacket - 1) / kPacket));
+        chunk_clens.resize(trailer ? n_chunks : 0);
+        chunk_crcs.resize(plan.crcs ? n_chunks : 0);
+        chunk_kinds.resize(plan.kinds ? n_chunks : 0);
+    }
+
+    // chunk c, of device g, on lane b: input -> device -> packets -> the writer
+    void codeChunk(size_t c, size_t g, DeviceBuffers &b, Writer &writer) {
+        const uint64_t at = chunk_at[c];
+        const size_t n_plain = static_cast<size_t>(chunk_at[c + 1] - at);
+        const bool from_mapping = b.upload(b.d_plain, mapped, in_fd, at, n_plain, "Read input file failed");
+        if (plan.based) b.uploadBase(self.baseFd, at, n_plain);      // the same byte range of the base
+        if (c == 0) trace("compress: its input on its way (window registered, copy queued)");
+        // The latency-mode encode kernel is faster only for a launch that has the chip to itself (include/gpuar_hip.h):
+        // a job of one chunk.  With several chunks the lanes of a device keep three launches in flight (the ramped first
+        // chunks are small enough for GPUAR_MODE_AUTO to pick the latency kernel), so the pipeline names the kernel itself.
+        const Encoded coded = b.encodeChunk(n_plain, plan, n_chunks == 1 ? GPUAR_MODE_AUTO : GPUAR_MODE_THROUGHPUT);     // (synchronises the lane's stream)
+        if (from_mapping) mapped.release(at, n_plain);
+        // the file was cut short (or replaced) under the mapping: what the reference's fread() reports
+        // (src/gpu_compressor.cpp:146-150)
+        if (!mapped.intact(in_fd)) throw std::runtime_error("Read input file failed");
+        if (c < 3) trace("compress: kernels of an early chunk done, chunk", static_cast<double>(c));
+        if (coded.flags & GPUAR_STATUS_SLOT_OVERFLOW)
+            throw std::runtime_error("a packet outgrew its 8704-byte slot (input bytes " + std::to_string(at) + " .. " + std::to_string(at + n_plain) + ")");
+        // (the scan words are computed from the very bytes: this cannot happen, and the file would still be valid)
+        if (coded.flags & GPUAR_STATUS_BAD_BATCH) throw std::runtime_error("Fail to execute kernel code: gpuar_hip_kinds_store: inconsistent scan");
+        const size_t n_packets = (n_plain + kPacket - 1) / kPacket;
+        if (plan.crcs) chunk_crcs[c].assign(&b.h_crc[0], &b.h_crc[n_packets]);
+        if (plan.kinds) chunk_kinds[c].assign(&b.h_kind[0], &b.h_kind[n_packets]);
+        if (trailer) {
+            chunk_clens[c].resize(n_packets);
+            for (size_t p = 0; p < n_packets; ++p) chunk_clens[c][p] = static_cast<uint16_t>(b.h_offsets[p + 1] - b.h_offsets[p]);
+        }
+        deal.count(g, n_plain);
+        b.drain(writer, c, b.d_stream, coded.n_stream, 0, n_plain);     // the ordered writer knows where chunk c goes
+    }
+
+    // the lanes and the ordered writer, from the first chunk to the last byte of the stream
+    void codeAll() {
+        Writer writer(out_fd, true, FileHeader::HEADER_LENGTH, "Write compressed data to output file failed");
+        writer.on_progress = progressTo(info, monitor);
+        writer.on_failure = [&] {
+            for (DeviceBuffers *b : self.buffers) b->abortWaits();
+        };
+        std::exception_ptr lane_failure;
+        try {
+            self.runLanes(
+                [&](size_t lane, DeviceBuffers &b, Failure &failure) {      // what one lane does: its device's chunks, one after the other
+                    const size_t g = lane / kLanesPerDevice;
+                    for (;;) {
+                        const size_t c = deal.take(g);
+                        if (c >= n_chunks || failure.stop) break;
+                        if (c == 0) trace("compress: lane of chunk 0 starts");
+                        if (!b.cap) b.allocate(self.chunkPackets, true);
+                        if (c == 0) trace("compress: its buffers allocated");
+                        hip_check(hipSetDevice(b.device), "hipSetDevice");
+                        b.prepare(plan, true);
+                        b.epoch = static_cast<hipEvent_t>(self.epochOf(g));
+                        codeChunk(c, g, b, writer);
+                    }
+                },
+                [&] { writer.abort(); });
+        } catch (...) {
+            lane_failure = std::current_exception();
+        }
+        rethrowLaneFailure(writer, lane_failure);
+        trace("compress: lanes done");
+        trace(mapped.wasRefused() ? "compress: a window could not be registered: the rest was read with pread" : "compress: every window registered");
+        trace("compress: input windows unregistered while the job ran:", static_cast<double>(mapped.windowsTrimmed()));
+        trace("compress: seconds inside hipHostUnregister for that:", mapped.trimSeconds());
+        deal.report("compress", "coded", " of at most " + std::to_string(self.chunkPackets * kPacket) + " bytes");
+        info.compressedFileSize = static_cast<size_t>(writer.finish(n_chunks));
+    }
+
+    void run() {
+        info.uncompressedFileSize = self.getFileSize(self.openFile);
+        if (plan.based) self.openBase(info.uncompressedFileSize, "the input");
+        const size_t total_packets = (info.uncompressedFileSize + kPacket - 1) / kPacket;
+        self.ensureBuffers(total_packets, true);
+        cutChunks();
+        hip_check(hipSetDevice(self.devices[0]), "hipSetDevice");
+        trace("compress: files open, device set");
+        mapped.open(in_fd, info.uncompressedFileSize);
+        trace(mapped.data() ? "compress: input mapped" : "compress: input NOT mapped (pread path)");
+        mapped.warmFirstWindow(self.devices[0]);
+        // room for the worst case up front: writing into allocated blocks is faster than growing the file, and the real
+        // length is set at the end (best effort: a file system without fallocate just grows the file as it goes)
+        // (the fallocate system call, not posix_fallocate: where the file system cannot do it, glibc's stand-in would write zeros)
+        (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(FileHeader::HEADER_LENGTH + total_packets * kSlot));
+        codeAll();
+        // behind the stream: the trailer the options ask for, then the header in front of it, and the file's real length
+        uint64_t file_end = info.compressedFileSize;
+        if (trailer) {
+            if (std::fseek(self.saveFile, static_cast<long>(info.compressedFileSize), SEEK_SET) != 0) throw std::runtime_error("Seek file failed");
+            self.saveTrailer(plan, joined(chunk_clens), joined(chunk_crcs), joined(chunk_kinds));
+            if (std::fflush(self.saveFile) != 0) throw std::runtime_error("Write packet index failed");
+            file_end = static_cast<uint64_t>(std::ftell(self.saveFile));
+        }
+        FileHeader header;
+        header.setCompressedFileSize(info.compressedFileSize);
+        header.setUncompressedFileSize(info.uncompressedFileSize);
+        if (::pwrite(out_fd, header.getData(), FileHeader::HEADER_LENGTH, 0) != FileHeader::HEADER_LENGTH)
+            throw std::runtime_error("Write data to file failed");
+        if (::ftruncate(out_fd, static_cast<off_t>(file_end)) != 0) throw std::runtime_error("Write data to file failed");
+        trace("compress: header written, length set");
+        mapped.close();
+        self.closeFiles();
+        trace("compress: files closed");
+    }
+};
+
+CompressionInfo GPUCompressor::compress(ProgressMonitor *monitor) {
+    return runJob(monitor, [&](CompressionInfo &info, int out_fd) { CompressJob{*this, info, monitor, out_fd}.run(); });
 }
 
 // "Compute time" = kernels + their sync, as src/gpu_compressor.cpp:184-194.  The lanes of a device run their
@@ -1063,100 +925,233 @@ void *GPUCompressor::epochOf(size_t g) {
     return epochs[g];
 }
 
-namespace {
+// One decompress job: what its steps share.
+struct GPUCompressor::DecompressJob {
+    GPUCompressor &self;
+    CompressionInfo &info;
+    ProgressMonitor *monitor;
+    const int out_fd;
+    const int in_fd = fileno(self.openFile);
+    uint64_t stream_end = 0;
+    MappedInput mapped;
+    Trailer trailer;
+    PacketPlan plan;
+    ChunkMap map;
+    std::thread scanner;
+    std::atomic<bool> stop_scan{false};
+    OrderedOffsets place;
+    Dealer deal{self.devices.size()};
 
-// Where the packets of each chunk sit in the stream.  Filled by the index trailer in one go, or by
-// the scanner thread as it walks the headers; lanes wait for the chunk they are about to take.
-struct ChunkMap {
-    struct Chunk {
-        uint64_t begin = 0, end = 0;     // file offsets of the chunk's first byte / one past its last
-        size_t n_packets = 0;
-        size_t first_packet = 0;         // index of its first packet in the file
-    };
-    std::mutex lock;
-    std::condition_variable more;
-    std::vector<Chunk> chunks;
-    bool complete = false;
-    std::exception_ptr failure;
+    // whatever way the job is left, the scanner is told to stop and joined before `map` and `mapped` go away
+    ~DecompressJob() { stopScanner(); }
+    void stopScanner() {
+        stop_scan = true;
+        if (scanner.joinable()) scanner.join();
+    }
 
-    void push(const Chunk &c) {
-        std::lock_guard<std::mutex> hold(lock);
-        chunks.push_back(c);
-        more.notify_all();
-    }
-    void finish(std::exception_ptr e = nullptr) {
-        std::lock_guard<std::mutex> hold(lock);
-        complete = true;
-        failure = e;
-        more.notify_all();
-    }
-    // false: there is no chunk c
-    bool get(size_t c, Chunk &out) {
-        std::unique_lock<std::mutex> hold(lock);
-        more.wait(hold, [&] { return c < chunks.size() || complete; });
-        if (c < chunks.size()) {
-            out = chunks[c];
-            return true;
+    // the chunk map of a file with an index: prefix sums of the stored lengths (already checked against the stream size)
+    void mapFromIndex() {
+        const std::vector<uint16_t> &index = trailer.clens;
+        uint64_t at = FileHeader::HEADER_LENGTH;
+        for (size_t p = 0; p < index.size();) {
+            ChunkMap::Chunk c;
+            c.begin = at;
+            c.first_packet = p;
+            const size_t want = rampPackets(map.chunks.size(), self.chunkPackets);
+            while (p < index.size() && c.n_packets < want) {
+                const size_t clen = index[p++];
+                if (clen < GPUAR_PACKET_HEADER_BYTES || clen > kSlot) throw std::runtime_error("Invalid file length");
+                at += clen;
+                ++c.n_packets;
+            }
+            c.end = at;
+            map.push(c);
         }
-        if (failure) std::rethrow_exception(failure);
-        return false;
-    }
-};
-
-// The running total of what the chunks before chunk c decode to (a stream may hold short packets in its middle:
-// the output offset of a chunk is then not c * chunk bytes).  take(c, n) blocks until chunks 0..c-1 have called and
-// returns the total before chunk c's own n bytes; it is called before the chunk's kernels, so nobody waits for it long.
-class OrderedOffsets {
-  public:
-    // `check` runs once it is the chunk's turn; if it throws, the turn is never passed on, and the chunks behind wait until abort()
-    template <typename Check>
-    uint64_t take(size_t chunk, uint64_t bytes, Check &&check) {
-        std::unique_lock<std::mutex> hold(lock);
-        turn.wait(hold, [&] { return aborted || next == chunk; });
-        if (aborted) throw std::runtime_error("pipeline stopped");
-        check();
-        const uint64_t mine = total;
-        total += bytes;
-        ++next;
-        turn.notify_all();
-        return mine;
-    }
-    void abort() {
-        std::lock_guard<std::mutex> hold(lock);
-        aborted = true;
-        turn.notify_all();
-    }
-    uint64_t sum() {
-        std::lock_guard<std::mutex> hold(lock);
-        return total;
+        map.finish();
     }
 
-  private:
-    std::mutex lock;
-    std::condition_variable turn;
-    size_t next = 0;
-    uint64_t total = 0;
-    bool aborted = false;
-};
+    // ... and of one without, on the scanner thread:
+    // the header walk of src/gpu_compressor.cpp:299-312 (`off += clen`), four bytes per packet, ahead of the lanes:
+    // through the mapping when there is one, else by pread
+    void scanHeaders() {
+        try {
+            uint64_t at = FileHeader::HEADER_LENGTH;
+            size_t n_pushed = 0, n_packets = 0;
+            while (at < stream_end && !stop_scan) {
+                ChunkMap::Chunk c;
+                c.begin = at;
+                c.first_packet = n_packets;
+                const size_t want = rampPackets(n_pushed, self.chunkPackets);
+                while (at < stream_end && c.n_packets < want) {
+                    uint8_t h[GPUAR_PACKET_HEADER_BYTES];
+                    if (stream_end - at < sizeof h) throw std::runtime_error("Incorrect file format");
+                    if (mapped.data()) std::memcpy(h, mapped.data() + at, sizeof h);
+                    else if (::pread(in_fd, h, sizeof h, static_cast<off_t>(at)) != static_cast<ssize_t>(sizeof h))
+                        throw std::runtime_error("Incorrect file format");
+                    const size_t clen = getPacketSize(h);
+                    if (clen < GPUAR_PACKET_HEADER_BYTES || clen > kSlot || at + clen > stream_end)
+                        throw std::runtime_error("Invalid file length");
+                    at += clen;
+                    ++c.n_packets;
+                }
+                c.end = at;
+                n_packets += c.n_packets;
+                map.push(c);
+                ++n_pushed;
+            }
+            map.finish();
+        } catch (...) {
+            map.finish(std::current_exception());
+        }
+    }
 
-}  // namespace
+    // what a chunk's packets say of themselves
+    struct Walked {
+        uint64_t produced = 0;      // bytes the chunk decodes to
+        bool all_full = true;       // every packet but the chunk's last holds 8192 bytes
+    };
+    // packet offsets inside the chunk (into b.h_offsets), and what every packet says it holds (u16 at +2): all but the
+    // file's last one hold 8192 bytes (src/gpu_compressor.cpp:326-331).  What is written comes from
+    // the packets, not from the header's size field: a file written by the reference carries garbage
+    // in the upper half of that field (src/file_header.hpp:31-36), and --host decodes by ulen too.
+    static Walked walkChunk(DeviceBuffers &b, const ChunkMap::Chunk &chunk, const uint8_t *bytes) {
+        const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
+        Walked w;
+        size_t off = 0;
+        for (size_t p = 0; p < chunk.n_packets; ++p) {
+            b.h_offsets[p] = off;
+            if (n_stream - off < GPUAR_PACKET_HEADER_BYTES) throw std::runtime_error("Invalid file length");
+            const uint8_t *pkt = bytes + off;
+            const size_t clen = getPacketSize(pkt);
+            if (clen < GPUAR_PACKET_HEADER_BYTES || off + clen > n_stream) throw std::runtime_error("Invalid file length");
+            const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
+            w.all_full = w.all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
+            w.produced += ulen;
+            off += clen;
+        }
+        if (off != n_stream) throw std::runtime_error("Invalid file length");
+        b.h_offsets[chunk.n_packets] = off;
+        return w;
+    }
 
-CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
-    CompressionInfo info;
-    monitor->reset();
-    process_timer.reset();
-    io_timer.reset();
-    io_timer.start();
-    openFiles(false);
-    const int out_fd = fileno(saveFile);
-    try {
+    static std::runtime_error malformedIn(const ChunkMap::Chunk &chunk) {
+        return std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) + " and " + std::to_string(chunk.end) + ")");
+    }
+
+    // What the trailer forbids the packets to say of themselves.  Checked in the chunk's turn (place.take), after
+    // every chunk in front of it has passed: of several such packets in a file the FIRST is the one refused and
+    // named, as --host does it, whichever lane gets to its chunk first.
+    void refuse(const DeviceBuffers &b, const ChunkMap::Chunk &chunk, const uint8_t *bytes, uint64_t produced) const {
+        for (size_t p = 0; p < chunk.n_packets; ++p) {
+            const uint8_t *pkt = bytes + b.h_offsets[p];
+            const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
+            // (a packet that says it holds more than 8192 bytes is malformed, which the decoder would say
+            // too -- but only after a CRC trailer had it called a checksum mismatch below; --host calls it
+            // malformed under every trailer)
+            if (getPacketUlen(pkt) > kPacket) throw malformedIn(chunk);
+            // (byte planes: so every chunk but the last is whole groups, and all_full holds; raw and sparse packets: the same, so
+            // that packet p of the chunk goes to byte 8192 p of it)
+            if (plan.transforms() || plan.kinds) checkPlanesPacket(chunk.first_packet + p, trailer.clens.size(), ulen);
+            // (a raw packet is its header and its bytes)
+            if (plan.kinds && trailer.kinds[chunk.first_packet + p] == 1 && b.h_offsets[p + 1] - b.h_offsets[p] != GPUAR_PACKET_HEADER_BYTES + getPacketUlen(pkt))
+                throw malformedIn(chunk);
+        }
+        if (plan.kinds && (produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
+        if (plan.crcs) {
+            // (With this, the chunk's `produced` bytes hold exactly its n_packets packets, and the verify below covers
+            // every one of them: a last packet whose ulen had become 0 would otherwise drop out of it.)
+            for (size_t p = 0; p < chunk.n_packets; ++p) checkChecksumPacket(chunk.first_packet + p, trailer.crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
+            if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
+        }
+    }
+
+    // A decoded chunk goes to the writer, at `at` of the output, in one of two ways.  Full packets (but the last): the chunk's
+    // bytes as they stand.  Short packets inside the chunk: one piece per packet.
+    void drainDecoded(DeviceBuffers &b, Writer &writer, size_t c, const ChunkMap::Chunk &chunk, const uint8_t *bytes, const Walked &walked, uint64_t at) {
+        if (walked.all_full) return b.drain(writer, c, b.transformed(plan), static_cast<size_t>(walked.produced), at, static_cast<size_t>(walked.produced));
+        for (size_t p = 0; p < chunk.n_packets; ++p) {
+            const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(bytes + b.h_offsets[p]));
+            if (ulen) b.drain(writer, c, b.d_plain + p * kPacket, ulen, at, ulen);
+            at += ulen;
+        }
+    }
+
+    // chunk c, of device g, on lane b: stream -> device -> decoded bytes -> the writer.  `staged`: the lane's room for the chunk's
+    // bytes where the input is not mapped, for the header walk
+    void decodeOne(size_t c, size_t g, DeviceBuffers &b, const ChunkMap::Chunk &chunk, std::vector<uint8_t> &staged, Writer &writer) {
+        const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
+        const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
+        const uint8_t *bytes = mapped.data() ? mapped.data() + chunk.begin : nullptr;
+        if (!bytes) {
+            staged.resize(n_stream);
+            sliced_io<false>(in_fd, staged.data(), n_stream, chunk.begin, "Invalid file length");
+            bytes = staged.data();
+        }
+        const Walked walked = walkChunk(b, chunk, bytes);
+        const uint64_t out_at = place.take(c, walked.produced, [&] { refuse(b, chunk, bytes, walked.produced); });
+        deal.count(g, walked.produced);
+        // (every packet in front of this chunk holds 8192 bytes: checkPlanesPacket)
+        if (plan.based) b.uploadBase(self.baseFd, static_cast<uint64_t>(chunk.first_packet) * kPacket, static_cast<size_t>(walked.produced));
+        const Decoded decoded = b.decodeChunk(chunk.n_packets, static_cast<size_t>(walked.produced), plan, plan.crcs ? trailer.crcs.data() + chunk.first_packet : nullptr,
+                                              plan.kinds ? trailer.kinds.data() + chunk.first_packet : nullptr);        // (synchronises the lane's stream)
+        if (from_mapping) mapped.release(chunk.begin, n_stream);
+        // the file was cut short under the mapping (what was read behind its new end are zeros,
+        // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307
+        if (!mapped.intact(in_fd)) throw std::runtime_error("Invalid file length");
+        if (decoded.flags & GPUAR_STATUS_BAD_PACKET) throw malformedIn(chunk);
+        if (decoded.flags & GPUAR_STATUS_CHECKSUM) {
+            const size_t bad = chunk.first_packet + static_cast<size_t>(decoded.first_bad);
+            const uint64_t begin = static_cast<uint64_t>(bad) * kPacket;
+            throw checksumError(bad, begin, std::min<uint64_t>(begin + kPacket, static_cast<uint64_t>(chunk.first_packet) * kPacket + walked.produced));
+        }
+        drainDecoded(b, writer, c, chunk, bytes, walked, out_at);
+    }
+
+    // the lanes and the unordered writer, from the first chunk to the last byte of the output
+    void decodeAll() {
+        Writer writer(out_fd, false, 0, "Write uncompressed data to output file failed");
+        writer.on_progress = progressTo(info, monitor);
+        writer.on_failure = [&] {
+            for (DeviceBuffers *b : self.buffers) b->abortWaits();
+            place.abort();
+        };
+        std::exception_ptr lane_failure;
+        try {
+            self.runLanes(
+                [&](size_t lane, DeviceBuffers &b, Failure &failure) {      // what one lane does: its device's chunks, as the map has them
+                    const size_t g = lane / kLanesPerDevice;
+                    std::vector<uint8_t> staged;        // unmapped input only: the chunk's bytes, for the header walk
+                    for (;;) {
+                        const size_t c = deal.take(g);
+                        ChunkMap::Chunk chunk;
+                        if (failure.stop || !map.get(c, chunk)) break;
+                        if (c < 8) trace(("decompress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>(chunk.n_packets));
+                        if (!b.cap) b.allocate(self.chunkPackets, false);
+                        hip_check(hipSetDevice(b.device), "hipSetDevice");
+                        b.prepare(plan, false);
+                        b.epoch = static_cast<hipEvent_t>(self.epochOf(g));
+                        decodeOne(c, g, b, chunk, staged, writer);
+                    }
+                },
+                [&] { writer.abort(), place.abort(); });
+        } catch (...) {
+            lane_failure = std::current_exception();
+        }
+        stopScanner();
+        rethrowLaneFailure(writer, lane_failure);
+        trace("decompress: lanes done");
+        trace("decompress: input windows unregistered while the job ran:", static_cast<double>(mapped.windowsTrimmed()));
+        deal.report("decompress", "decoded");
+        (void)writer.finish(0);
+    }
+
+    void run() {
         FileHeader header;
-        const size_t fileSize = getFileSize(openFile);
-        if (std::fread(header.getData(), FileHeader::HEADER_LENGTH, 1, openFile) != 1 || !header.checkHeaderVersion())
+        const size_t fileSize = self.getFileSize(self.openFile);
+        if (std::fread(header.getData(), FileHeader::HEADER_LENGTH, 1, self.openFile) != 1 || !header.checkHeaderVersion())
             throw std::runtime_error("Incorrect file format");
         info = header.getInfo(fileSize);
-        const size_t G = devices.size();
-        const uint64_t stream_end = streamEnd(info, fileSize);
+        stream_end = streamEnd(info, fileSize);
         // How many packets to size the chunks for.  Every packet but the last holds 8192 bytes, so the header's
         // uncompressed size says; but a file written by the reference keeps only the low 32 bits of that size
         // (src/file_header.hpp:31-36) and a header can lie, so the count is bounded from below by the stream itself
@@ -1165,257 +1160,34 @@ CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
         const size_t by_header = (info.uncompressedFileSize + kPacket - 1) / kPacket;
         const size_t at_least = (stream_bytes + kSlot - 1) / kSlot, at_most = stream_bytes / GPUAR_PACKET_HEADER_BYTES + 1;
         const size_t expect_packets = std::min(std::max(by_header, at_least), at_most);
-        ensureBuffers(expect_packets, false);
-        const int in_fd = fileno(openFile);
-        hip_check(hipSetDevice(devices[0]), "hipSetDevice");
+        self.ensureBuffers(expect_packets, false);
+        hip_check(hipSetDevice(self.devices[0]), "hipSetDevice");
         trace("decompress: files open, device set");
-        MappedInput mapped;
         mapped.open(in_fd, fileSize);
-        mapped.warmFirstWindow(devices[0]);
+        mapped.warmFirstWindow(self.devices[0]);
         // packet lengths, per-packet CRCs (every decoded chunk is verified against them) and the width of the byte planes the
         // packets hold (merged back on the device), as far as the file's trailer gives them (packet_index.hpp)
-        const Trailer trailer = loadTrailer(stream_end, fileSize);
-        const std::vector<uint16_t> &index = trailer.clens;
-        const std::vector<uint32_t> &crcs = trailer.crcs;
-        const bool indexed = trailer.indexed(), verify = trailer.verify(), merging = trailer.merging(), mixed = trailer.mixed();
-        if (trailer.based()) openBase(info.uncompressedFileSize, "the file");
-
-        ChunkMap map;
-        std::thread scanner;
-        std::atomic<bool> stop_scan{false};
-        // whatever way this scope is left, the scanner is told to stop and joined before `map` and `mapped` go away
-        struct JoinScanner {
-            std::thread &t;
-            std::atomic<bool> &stop;
-            ~JoinScanner() {
-                stop = true;
-                if (t.joinable()) t.join();
-            }
-        } join_scanner{scanner, stop_scan};
-        if (indexed) {                   // prefix sums of the stored lengths (already checked against the stream size)
-            uint64_t at = FileHeader::HEADER_LENGTH;
-            for (size_t p = 0; p < index.size();) {
-                ChunkMap::Chunk c;
-                c.begin = at;
-                c.first_packet = p;
-                const size_t want = rampPackets(map.chunks.size(), chunkPackets);
-                while (p < index.size() && c.n_packets < want) {
-                    const size_t clen = index[p++];
-                    if (clen < GPUAR_PACKET_HEADER_BYTES || clen > kSlot) throw std::runtime_error("Invalid file length");
-                    at += clen;
-                    ++c.n_packets;
-                }
-                c.end = at;
-                map.push(c);
-            }
-            map.finish();
-        } else {
-            // the header walk of src/gpu_compressor.cpp:299-312 (`off += clen`), four bytes per packet, ahead of the lanes:
-            // through the mapping when there is one, else by pread
-            scanner = std::thread([&] {
-                try {
-                    uint64_t at = FileHeader::HEADER_LENGTH;
-                    size_t n_pushed = 0, n_packets = 0;
-                    while (at < stream_end && !stop_scan) {
-                        ChunkMap::Chunk c;
-                        c.begin = at;
-                        c.first_packet = n_packets;
-                        const size_t want = rampPackets(n_pushed, chunkPackets);
-                        while (at < stream_end && c.n_packets < want) {
-                            uint8_t h[GPUAR_PACKET_HEADER_BYTES];
-                            if (stream_end - at < sizeof h) throw std::runtime_error("Incorrect file format");
-                            if (mapped.data()) std::memcpy(h, mapped.data() + at, sizeof h);
-                            else if (::pread(in_fd, h, sizeof h, static_cast<off_t>(at)) != static_cast<ssize_t>(sizeof h))
-                                throw std::runtime_error("Incorrect file format");
-                            const size_t clen = getPacketSize(h);
-                            if (clen < GPUAR_PACKET_HEADER_BYTES || clen > kSlot || at + clen > stream_end)
-                                throw std::runtime_error("Invalid file length");
-                            at += clen;
-                            ++c.n_packets;
-                        }
-                        c.end = at;
-                        n_packets += c.n_packets;
-                        map.push(c);
-                        ++n_pushed;
-                    }
-                    map.finish();
-                } catch (...) {
-                    map.finish(std::current_exception());
-                }
-            });
-        }
-
+        trailer = self.loadTrailer(stream_end, fileSize);
+        plan = PacketPlan::of(trailer);
+        if (plan.based) self.openBase(info.uncompressedFileSize, "the file");
+        if (trailer.indexed()) mapFromIndex();
+        else scanner = std::thread([this] { scanHeaders(); });
         // what the packet count promises, allocated up front (best effort); the real length is set at the end.  A header
         // may claim anything up to 2048 times the stream's size (a packet is at least 4 bytes): the preallocation is bounded
         // by what packets can plausibly hold -- 64 times the stream (8192 zeros code to 210 bytes, 39 times) -- and the file
         // simply grows beyond that if the packets really say so.
         const size_t prealloc_packets = std::min(expect_packets, 64 * at_least);
         (void)::fallocate(out_fd, 0, 0, static_cast<off_t>(static_cast<uint64_t>(prealloc_packets) * kPacket));
-        OrderedOffsets place;
-        std::vector<std::atomic<size_t>> next_of_device(G);
-        for (auto &n : next_of_device) n = 0;
-        std::vector<std::atomic<uint64_t>> device_bytes(G), device_chunks(G);      // what each device decoded (GPUAR_TRACE)
-        for (size_t g = 0; g < G; ++g) device_bytes[g] = 0, device_chunks[g] = 0;
-        std::mutex progress_lock;
-        {
-            Writer writer(out_fd, false, 0, "Write uncompressed data to output file failed");
-            writer.on_progress = [&](size_t plain) {
-                if (!plain) return;
-                std::lock_guard<std::mutex> hold(progress_lock);
-                info.processedUncompressedSize += plain;
-                monitor->updateProgress(&info);
-            };
-            writer.on_failure = [&] {
-                for (DeviceBuffers *b : buffers) b->abortWaits();
-                place.abort();
-            };
-            std::exception_ptr lane_failure;
-            try {
-                runLanes(
-                    [&](size_t lane, DeviceBuffers &b, Failure &failure) {
-                        const size_t g = lane / kLanesPerDevice;
-                        std::vector<uint8_t> staged;        // unmapped input only: the chunk's bytes, for the header walk below
-                        for (;;) {
-                            const size_t c = g + G * next_of_device[g].fetch_add(1);
-                            ChunkMap::Chunk chunk;
-                            if (failure.stop || !map.get(c, chunk)) break;
-                            if (c < 8) trace(("decompress: packets in chunk " + std::to_string(c) + ":").c_str(), static_cast<double>(chunk.n_packets));
-                            if (!b.cap) b.allocate(b.device, chunkPackets, false);
-                            hip_check(hipSetDevice(b.device), "hipSetDevice");
-                            if (verify) b.allocateCrc();
-                            if (merging) b.allocatePlanes();
-                            if (trailer.based()) b.allocateBase();
-                            if (mixed) b.allocateKinds(false);
-                            b.epoch = static_cast<hipEvent_t>(epochOf(g));
-                            const size_t n_stream = static_cast<size_t>(chunk.end - chunk.begin);
-                            const bool from_mapping = b.upload(b.d_stream, mapped, in_fd, chunk.begin, n_stream, "Invalid file length");
-                            const uint8_t *bytes = mapped.data() ? mapped.data() + chunk.begin : nullptr;
-                            if (!bytes) {
-                                staged.resize(n_stream);
-                                sliced_io<false>(in_fd, staged.data(), n_stream, chunk.begin, "Invalid file length");
-                                bytes = staged.data();
-                            }
-                            // packet offsets inside the chunk, and what every packet says it holds (u16 at +2): all but the
-                            // file's last one hold 8192 bytes (src/gpu_compressor.cpp:326-331).  What is written comes from
-                            // the packets, not from the header's size field: a file written by the reference carries garbage
-                            // in the upper half of that field (src/file_header.hpp:31-36), and --host decodes by ulen too.
-                            uint64_t produced = 0;
-                            size_t off = 0;
-                            bool all_full = true;
-                            for (size_t p = 0; p < chunk.n_packets; ++p) {
-                                b.h_offsets[p] = off;
-                                if (n_stream - off < GPUAR_PACKET_HEADER_BYTES) throw std::runtime_error("Invalid file length");
-                                const uint8_t *pkt = bytes + off;
-                                const size_t clen = getPacketSize(pkt);
-                                if (clen < GPUAR_PACKET_HEADER_BYTES || off + clen > n_stream) throw std::runtime_error("Invalid file length");
-                                const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
-                                all_full = all_full && (ulen == kPacket || p + 1 == chunk.n_packets);
-                                produced += ulen;
-                                off += clen;
-                            }
-                            if (off != n_stream) throw std::runtime_error("Invalid file length");
-                            b.h_offsets[chunk.n_packets] = off;
-                            // What the trailer forbids the packets to say of themselves.  Checked in the chunk's turn (place.take), after
-                            // every chunk in front of it has passed: of several such packets in a file the FIRST is the one refused and
-                            // named, as --host does it, whichever lane gets to its chunk first.
-                            const auto refuse = [&] {
-                                for (size_t p = 0; p < chunk.n_packets; ++p) {
-                                    const uint8_t *pkt = bytes + b.h_offsets[p];
-                                    const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(pkt));
-                                    // (a packet that says it holds more than 8192 bytes is malformed, which the decoder would say
-                                    // too -- but only after a CRC trailer had it called a checksum mismatch below; --host calls it
-                                    // malformed under every trailer)
-                                    if (getPacketUlen(pkt) > kPacket)
-                                        throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
-                                                                 " and " + std::to_string(chunk.end) + ")");
-                                    // (byte planes: so every chunk but the last is whole groups, and all_full holds)
-                                    if (merging) checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
-                                    // (raw and sparse packets: the same, so that packet p of the chunk goes to byte 8192 p of it; a raw
-                                    // packet is its header and its bytes)
-                                    if (mixed) {
-                                        checkPlanesPacket(chunk.first_packet + p, index.size(), ulen);
-                                        if (trailer.kinds[chunk.first_packet + p] == 1 &&
-                                            b.h_offsets[p + 1] - b.h_offsets[p] != GPUAR_PACKET_HEADER_BYTES + getPacketUlen(pkt))
-                                            throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
-                                                                     " and " + std::to_string(chunk.end) + ")");
-                                    }
-                                }
-                                if (mixed && (produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
-                                if (verify) {
-                                    // (With this, the chunk's `produced` bytes hold exactly its n_packets packets, and the verify below covers
-                                    // every one of them: a last packet whose ulen had become 0 would otherwise drop out of it.)
-                                    for (size_t p = 0; p < chunk.n_packets; ++p)
-                                        checkChecksumPacket(chunk.first_packet + p, crcs.size(), getPacketUlen(bytes + b.h_offsets[p]));
-                                    if ((produced + kPacket - 1) / kPacket != chunk.n_packets) throw std::runtime_error("Invalid file length");
-                                }
-                            };
-                            const uint64_t out_at = place.take(c, produced, refuse);
-                            device_bytes[g] += produced;
-                            device_chunks[g] += 1;
-                            // (every packet in front of this chunk holds 8192 bytes: checkPlanesPacket)
-                            if (trailer.based()) b.uploadBase(baseFd, static_cast<uint64_t>(chunk.first_packet) * kPacket, static_cast<size_t>(produced));
-                            uint64_t first_bad = 0;
-                            const uint32_t flags = b.decodeChunk(chunk.n_packets, verify ? crcs.data() + chunk.first_packet : nullptr, static_cast<size_t>(produced),
-                                                                 &first_bad, static_cast<int>(trailer.elem_bytes), trailer.filtering(), trailer.based(),
-                                                                 mixed ? trailer.kinds.data() + chunk.first_packet : nullptr);        // (synchronises the lane's stream)
-                            if (from_mapping) mapped.release(chunk.begin, n_stream);
-                            // the file was cut short under the mapping (what was read behind its new end are zeros,
-                            // input_guard.hpp): the reference's short fread(), src/gpu_compressor.cpp:299-307
-                            if (!mapped.intact(in_fd)) throw std::runtime_error("Invalid file length");
-                            if (flags & GPUAR_STATUS_BAD_PACKET)
-                                throw std::runtime_error("Incorrect file format (malformed packet between file offsets " + std::to_string(chunk.begin) +
-                                                         " and " + std::to_string(chunk.end) + ")");
-                            if (flags & GPUAR_STATUS_CHECKSUM) {
-                                const size_t g = chunk.first_packet + static_cast<size_t>(first_bad);
-                                const uint64_t begin = static_cast<uint64_t>(g) * kPacket;
-                                throw checksumError(g, begin, std::min<uint64_t>(begin + kPacket, static_cast<uint64_t>(chunk.first_packet) * kPacket + produced));
-                            }
-                            if (all_full) {
-                                b.drain(writer, c, merging ? b.d_planes : b.d_plain, static_cast<size_t>(produced), out_at, static_cast<size_t>(produced));
-                            } else {             // short packets inside the chunk: one piece per packet
-                                uint64_t at = out_at;
-                                for (size_t p = 0; p < chunk.n_packets; ++p) {
-                                    const size_t ulen = std::min<size_t>(kPacket, getPacketUlen(bytes + b.h_offsets[p]));
-                                    if (ulen) b.drain(writer, c, b.d_plain + p * kPacket, ulen, at, ulen);
-                                    at += ulen;
-                                }
-                            }
-                        }
-                    },
-                    [&] {
-                        writer.abort();
-                        place.abort();
-                    });
-            } catch (...) {
-                lane_failure = std::current_exception();
-            }
-            stop_scan = true;
-            if (scanner.joinable()) scanner.join();
-            if (lane_failure) {
-                writer.abort();
-                (void)writer.finish(0);      // rethrows the writer's own failure when it has one: that is the cause then
-                std::rethrow_exception(lane_failure);
-            }
-            trace("decompress: lanes done");
-            trace("decompress: input windows unregistered while the job ran:", static_cast<double>(mapped.windowsTrimmed()));
-            for (size_t g = 0; g < G; ++g)
-                trace(("decompress: device " + std::to_string(g) + " decoded " + std::to_string(device_bytes[g].load()) + " bytes in " +
-                       std::to_string(device_chunks[g].load()) + " chunks").c_str());
-            (void)writer.finish(0);
-        }
+        decodeAll();
         info.uncompressedFileSize = info.processedUncompressedSize = static_cast<size_t>(place.sum());     // what the packets held
         if (::ftruncate(out_fd, static_cast<off_t>(place.sum())) != 0) throw std::runtime_error("Write uncompressed data to output file failed");
         mapped.close();
-        closeFiles();
-    } catch (...) {
-        if (::ftruncate(out_fd, 0) != 0) {}      // a failed job leaves an empty file, not a half-written one
-        closeFiles();
-        dropTimes();
-        throw;
+        self.closeFiles();
     }
-    io_timer.stop();
-    finishTimes(info);
-    return info;
+};
+
+CompressionInfo GPUCompressor::decompress(ProgressMonitor *monitor) {
+    return runJob(monitor, [&](CompressionInfo &info, int out_fd) { DecompressJob{*this, info, monitor, out_fd}.run(); });
 }
 
 }  // namespace gip

@@ -41,7 +41,8 @@ class GPUCompressor : public Compressor {
 
   private:
     struct DeviceBuffers;
-    struct Failure;
+    struct CompressJob;                        // the state and the steps of one compress() ...
+    struct DecompressJob;                      // ... and of one decompress()
     std::vector<int> devices;
     std::vector<DeviceBuffers *> buffers;      // one per lane, device-major
     size_t batchPackets = 65536;
@@ -53,6 +54,8 @@ class GPUCompressor : public Compressor {
     void ensureBuffers(size_t total_packets, bool compressing);
     template <typename Work, typename OnFailure>
     void runLanes(Work &&work, OnFailure &&on_failure);
+    template <typename Job>
+    CompressionInfo runJob(ProgressMonitor *monitor, Job &&job);
     void finishTimes(CompressionInfo &info);
     void dropTimes();                          // a failed job's kernel spans are nobody's: not the next job's
     void *epochOf(size_t device_index);
